@@ -9,7 +9,13 @@ chip inside a launch and is carried in HBM between launches.  Inputs are synthet
 the GPU and resident in HBM before the timed region; one launch touches more bytes than the
 256 MiB Infinity Cache holds and a ring of distinct buffers is cycled, so the traffic is HBM's.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-per-launch T] [--workload NAME]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames-per-launch T] [--workload NAME] [--full] [--dump-outputs DIR]
+
+A plain run does what its headline figure needs and nothing more: it sets up, runs W launches of
+warm-up, times exactly K launches, writes the last timed launch's outputs if `--dump-outputs DIR`
+is given, and prints the result line.  `--full` adds what the benchmark measures and checks beyond
+that: the timed stream replayed against the CPU oracle, the CPU baseline, and (N = 1, headline
+workload) the other workloads of OTHER_WORKLOADS, each timed and replayed against the oracle.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment makes this process a launcher: it
 starts N rank processes (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set) before
@@ -20,7 +26,7 @@ the environment instead.  Either way `--gpus` must equal the world size RCCL rep
 Rank 0 prints ONE JSON line (the contract in the task description): whole-job MSamples/s (input
 complex samples, all ranks), `roofline` (algorithmic 12 B/sample over the kernel's average launch
 duration from HIP events, vs 8 TB/s; `traffic` from the committed rocprofv3 PMC passes if they
-were taken from this very kernel source) and, at N = 1, `cpu_baseline` (the CPU oracle timed on
+were taken from this very kernel source) and, with `--full` at N = 1, `cpu_baseline` (the CPU oracle timed on
 this host's cores on a bounded sample).
 """
 import argparse
@@ -102,7 +108,7 @@ KERNEL_SOURCES = tuple("t41_sdr_amd/csrc/" + f for f in (
     "rx_experiments.hpp", "rx_internal.hpp", "rx_kernels.hpp", "wave_fft.hpp", "rx_device.hpp", "rx_chains.hpp", "rx512_kernel.hpp",
     "rx512_launch.hpp", "rx_launch.hpp", "fastconv_kernels.hpp", "rx512_ssb.hip", "rx512_am.hip", "rx512_nfm.hip", "rx512_sam.hip",
     "rx_long.hip", "fastconv.hip", "rx_dispatch.hip", "nr_kernels.hip", "nr_kernels.hpp"))
-# what the default run times behind the headline (N = 1): every mode and sample format the README claims, each replayed
+# what `--full` times behind the headline (N = 1): every mode and sample format the README claims, each replayed
 # against the oracle, and the headline workload in the firmware's own calling shape (1 frame per call) and at 4 frames
 # (frames per launch: 128 for the headline and for the workloads whose serial chains run as a pipeline across the frames of a
 # launch -- AGC on, SAM: the pipeline's fill and drain are per launch --, 64 long frames for configs[3], 32 for the rest;
@@ -383,13 +389,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--frames-per-launch", type=int, default=0,
                     help="consecutive frames per channel per launch (default %d; 1 = one ProcessIQData() per launch)" % DEFAULT_FRAMES)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the other modes' timings + parity checks behind the headline (N = 1, ssb)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the oracle replay of the timed stream, the CPU baseline and the other workloads (N = 1, ssb)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-workloads", action="store_true", help="with --full: skip the other modes' timings + parity checks behind the headline (N = 1, ssb)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the audio the last timed launch returned, a fixed sample of its channels, as DIR/audio.npy (float32)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="ssb")
     ap.add_argument("--dry-run", action="store_true", help="CPU-only rehearsal of the multi-rank plumbing (gloo)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -430,8 +442,11 @@ def main():
 
     head = Workload(torch, T, args.workload, world, rank, local_rank, dev, dist, args.frames_per_launch)
     wall, kernel_ms = head.time(args.steps, args.warmup)
-    if not head.q15 and not os.environ.get("T41RX_BENCH_NOCHECK") and not torch.isfinite(head.outs[(args.warmup + args.steps - 1) % head.ring]).all():
+    last = (args.warmup + args.steps - 1) % head.ring  # the ring buffer the last timed launch wrote
+    if not head.q15 and not os.environ.get("T41RX_BENCH_NOCHECK") and not torch.isfinite(head.outs[last]).all():
         raise SystemExit("non-finite audio output")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(head, last, args.dump_outputs)
 
     wl = head.wl
     value = world * head.samples_per_step * args.steps / wall / 1e6
@@ -459,7 +474,7 @@ def main():
         },
         "roofline": head.roofline(kernel_ms),
     }
-    if rank == 0:
+    if rank == 0 and args.full:
         # the timed stream against the CPU oracle, in the timed launch shape (replayed: see parity_check)
         # (the noise-reduction workloads start their adaptive stages on the path's start-up transient: their parity is
         # the business of tests/test_noise_reduction.py, which feeds both sides identical audio)
@@ -468,7 +483,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline and args.workload == "ssb":
             line["cpu_baseline"] = cpu_baseline(torch, head.Is, head.Qs, head.nco, head.params_kw, head.n, head.frame_len)
     head.free()
-    if rank == 0 and world == 1 and args.workload == "ssb" and not args.no_other_workloads:
+    if args.full and rank == 0 and world == 1 and args.workload == "ssb" and not args.no_other_workloads:
         # BASELINE configs[2] / [3] and the firmware's default AGC mode, timed in this same run
         others = {}
         for name in OTHER_WORKLOADS:
@@ -617,6 +632,25 @@ class Workload:
         self.rx.close()
         self.Is = self.Qs = self.outs = None
         self.torch.cuda.empty_cache()
+
+
+DUMP_BYTES = 48 << 20    # --dump-outputs: bytes of samples written at most
+DUMP_CHANNELS = 256      # ... from at most this many channels
+DUMP_SEED = 0x44554D50   # which channels: a fixed draw, the same in every run of a workload
+
+
+def dump_outputs(w, k, out_dir):
+    """--dump-outputs: what the caller of launch k (the last timed one) received -- the audio of a fixed, seeded sample of
+    the channels, every sample of the launch in each (the launch's last DUMP_BYTES / 4 where one channel holds more) --
+    as out_dir/audio.npy, float32 [channels, samples] in ascending channel order (q15 workloads: the int16 values).
+    The inputs are seeded, so two builds run with the same arguments can be compared output for output."""
+    per_channel = w.frames * w.frame_len
+    keep = min(per_channel, DUMP_BYTES // 4)
+    n = max(1, min(w.n, DUMP_CHANNELS, DUMP_BYTES // (4 * keep)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(w.n, n, replace=False))
+    rows = w.channels_of(w.outs[k], w.torch.as_tensor(idx, device=w.dev))[:, per_channel - keep:]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "audio.npy"), np.ascontiguousarray(rows.float().cpu().numpy()))
 
 
 def parity_check(torch, w, launches, launches_timed, sample=16):

@@ -3,7 +3,7 @@
 # ssb_agc workload with either, and the diagnostic build's counters (tools/build_variant.sh pstat -DT41RX_PIPE_STAT)
 ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 cd "$ROOT" && mkdir -p gpurun_out
-B="python bench.py --workload ssb_agc --steps 20 --warmup 5 --no-cpu-baseline --no-other-workloads"
+B="python bench.py --full --workload ssb_agc --steps 20 --warmup 5 --no-cpu-baseline --no-other-workloads"
 timeout -k 10 300 python tools/agc_pipe_probe.py check > gpurun_out/pipe_check.log 2>&1 || { tail -5 gpurun_out/pipe_check.log; exit 1; }
 grep -c "True" gpurun_out/pipe_check.log; grep "False" gpurun_out/pipe_check.log
 timeout -k 10 200 $B > gpurun_out/pipe_b1.log 2>&1 || exit 1
