@@ -155,6 +155,18 @@ T41RX_API int t41rx_set_nco_freq(t41rx_ctx *ctx, const int32_t *nco_freq_hz, int
  * (Freq_Shift.cpp:13-14, Process.cpp:42,47). */
 T41RX_API int t41rx_reset(t41rx_ctx *ctx);
 
+/* NB_on (Process.cpp:873-876): 1 = the receive noise blanker NoiseBlanker() / AltNoiseBlanking() (DSP_Fn.cpp:105-362)
+ * on the demodulated audio @24 kS/s, behind the noise reduction and the notch and in front of the interpolators: an
+ * order-10 LPC fit per 256-sample block, a matched-filter detector at 2.5 x its spread, and 7 samples around each of up
+ * to 20 detected impulses replaced by forward / backward linear prediction.  0 = off (the default; the firmware's
+ * NB_on = 0).  Only 0 and 1 are accepted (T41RX_ERR_ARG otherwise); fft_length 512 only (T41RX_ERR_UNSUPPORTED for
+ * NB_on = 1 at a long fft_length).  A context switch, not a t41rx_params field: it survives t41rx_set_params() and
+ * t41rx_set_coeffs().  Its one memory, last_frame_end (the previous block's samples 242 .. 254), starts at zero,
+ * changes only while the blanker runs (switched off and on again it is stale, as in the reference), is zeroed by
+ * t41rx_reset() and travels in the checkpoint (section bit 2).  Takes effect from the next process call. */
+T41RX_API int t41rx_set_noise_blanker(t41rx_ctx *ctx, int NB_on);
+T41RX_API int t41rx_get_noise_blanker(const t41rx_ctx *ctx);  /* 0 / 1, or T41RX_ERR_ARG for a NULL context */
+
 T41RX_API int t41rx_n_channels(const t41rx_ctx *ctx);
 T41RX_API int t41rx_frame_len(const t41rx_ctx *ctx);
 
@@ -210,8 +222,11 @@ T41RX_API int t41rx_process_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, cons
  *     bit 0  noise reduction / notch: Xanr()'s taps, delay line and leak words, then the Kim / spectral per-bin memories
  *            (Noise.cpp:19-56) -- present once one of those stages has run in this context;
  *     bit 1  display FFT: zoom filters, ring, FFT_spec_old (FFT.cpp:14-26) -- present while
- *            t41rx_set_display_spectrum() is on.
- * t41rx_state_bytes() therefore GROWS when a noise-reduction stage first runs or the display spectrum is switched on:
+ *            t41rx_set_display_spectrum() is on;
+ *     bit 2  noise blanker: last_frame_end[0 .. 12] (DSP_Fn.cpp:143), 16 floats per channel (13 used) -- present once
+ *            the blanker has run in this context; refused at a long fft_length.
+ * t41rx_state_bytes() therefore GROWS when a noise-reduction stage or the noise blanker first runs or the display
+ * spectrum is switched on:
  * query it right before every t41rx_get_state() (a buffer sized at creation gets T41RX_ERR_STATE "state buffer too
  * small").  fft_length cannot change on a live context, so the path records' size never does.
  * t41rx_set_state() refuses (T41RX_ERR_STATE) a checkpoint of another ABI, FFT length or channel count, one with an
@@ -221,7 +236,7 @@ T41RX_API int t41rx_process_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, cons
  * [0, 2 pi], frequency within +-pll_fmax), the notch's leak index, the noise reduction's ring pointers, the zoom ring's
  * pointer.  What it does to the side stages: a section the checkpoint carries is restored; a memory this context has
  * allocated but the checkpoint does not carry goes back to its power-on values (InitializeDataArrays() /
- * SpectralNoiseReductionInit() / ZoomFFTPrep()) -- never the values of the stream being replaced.
+ * SpectralNoiseReductionInit() / ZoomFFTPrep() / the blanker's zero carry) -- never the values of the stream being replaced.
  * T41RX_ERR_STATE is also what t41rx_get_state(), t41rx_process_host() and t41rx_process_host_q15() -- the calls that
  * synchronise -- return if a wait inside the pipelined AGC / SAM kernels has run out since the last t41rx_reset() or
  * restored checkpoint (their waits are bounded so that a broken hand-over cannot hang the GPU; it cannot happen unless

@@ -16,6 +16,8 @@
 #include <string>
 #include <vector>
 
+#include "nb_kernels.hpp"
+#include "nb_kernel.hip"  // the noise blanker's kernel and launcher
 #include "nr_kernels.hpp"
 #include "rx_experiments.hpp"
 #include "rx_internal.hpp"
@@ -51,6 +53,11 @@ struct t41rx_ctx {
   // noise reduction / notch (Process.cpp:841-866): state of Xanr() and of the two spectral functions, window tables;
   // allocated when a call first needs them
   float *d_nr_anr = nullptr, *d_nr_spec = nullptr, *d_nr_tab = nullptr;
+  // noise blanker (NB_on, Process.cpp:873-876; t41rx_set_noise_blanker): AltNoiseBlanking()'s last_frame_end per channel,
+  // two slots [2][nchan][kNbCarryPitch] (nb_kernel.hip); allocated when the blanker first runs
+  int nb_on = 0;
+  float *d_nb = nullptr;
+  int nb_sel = 0;  // the slot holding the current carry (flips with every blanker launch)
   // staging for t41rx_process_host
   float *d_in_i = nullptr, *d_in_q = nullptr, *d_out = nullptr;
   size_t staging_floats = 0;
@@ -250,7 +257,26 @@ int reset_state(t41rx_ctx *ctx) {
   HIP_TRY(hipMemcpy(ctx->d_state, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
   ctx->nco_sel = 0;
   if (ctx->d_disp) HIP_TRY(hipMemset(ctx->d_disp, 0, sizeof(float) * kDispFloats * (size_t)ctx->nchan));
+  if (ctx->d_nb) {  // last_frame_end is a static: zero at power-on
+    HIP_TRY(hipMemset(ctx->d_nb, 0, sizeof(float) * 2 * kNbCarryPitch * (size_t)ctx->nchan));
+    ctx->nb_sel = 0;
+  }
   if (ctx->d_nr_anr) return reset_nr(ctx);
+  return T41RX_OK;
+}
+
+// the noise blanker's carry, on first use (power-on: zero)
+int ensure_nb(t41rx_ctx *ctx) {
+  if (ctx->d_nb) return T41RX_OK;
+  const size_t bytes = sizeof(float) * 2 * kNbCarryPitch * (size_t)ctx->nchan;
+  float *nb = nullptr;
+  if (hipMalloc((void **)&nb, bytes) != hipSuccess) return fail(T41RX_ERR_NOMEM, "noise-blanker state allocation failed");
+  if (hipMemset(nb, 0, bytes) != hipSuccess) {
+    (void)hipFree(nb);
+    return fail(T41RX_ERR_HIP, "noise-blanker state upload failed");
+  }
+  ctx->d_nb = nb;
+  ctx->nb_sel = 0;
   return T41RX_OK;
 }
 
@@ -312,6 +338,7 @@ void free_ctx(t41rx_ctx *ctx) {
   (void)hipFree(ctx->d_nr_anr);
   (void)hipFree(ctx->d_nr_spec);
   (void)hipFree(ctx->d_nr_tab);
+  (void)hipFree(ctx->d_nb);
   delete ctx;
 }
 
@@ -545,6 +572,15 @@ int t41rx_set_buffer_layout(t41rx_ctx *ctx, int layout) {
 }
 int t41rx_get_buffer_layout(const t41rx_ctx *ctx) { return ctx ? ctx->layout : T41RX_ERR_ARG; }
 
+int t41rx_set_noise_blanker(t41rx_ctx *ctx, int NB_on) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (NB_on != 0 && NB_on != 1) return fail(T41RX_ERR_ARG, "NB_on must be 0 or 1");
+  if (NB_on && ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the noise blanker is built for fft_length 512");
+  ctx->nb_on = NB_on;
+  return T41RX_OK;
+}
+int t41rx_get_noise_blanker(const t41rx_ctx *ctx) { return ctx ? ctx->nb_on : T41RX_ERR_ARG; }
+
 int t41rx_n_channels(const t41rx_ctx *ctx) { return ctx ? ctx->nchan : T41RX_ERR_ARG; }
 int t41rx_frame_len(const t41rx_ctx *ctx) { return ctx ? 4 * ctx->params.fft_length : T41RX_ERR_ARG; }
 
@@ -581,7 +617,13 @@ int process_device_impl(t41rx_ctx *ctx, const float *dI, const float *dQ, float 
     const int rc = ensure_nr(ctx);
     if (rc != T41RX_OK) return rc;
   }
-  if ((seg > 1 || nr_on) && n_frames > ctx->scratch_frames) {
+  const bool nb_on = ctx->nb_on != 0;  // (fft_length 512: t41rx_set_noise_blanker)
+  if (nb_on) {
+    const int rc = ensure_nb(ctx);
+    if (rc != T41RX_OK) return rc;
+  }
+  const bool stages_on = nr_on || nb_on;  // the fused kernel stops behind the demodulator; stage kernels; back kernel
+  if ((seg > 1 || stages_on) && n_frames > ctx->scratch_frames) {
     // scratch between the kernels of the long-FFT pipeline / the noise-reduction pipeline (grown on demand, kept)
     HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
     (void)hipFree(ctx->d_mid);
@@ -673,11 +715,11 @@ int process_device_impl(t41rx_ctx *ctx, const float *dI, const float *dQ, float 
   a.dbg_demod = ctx->dbg_demod;
   a.spect = ctx->spect;
   a.spect_max = ctx->spect_max;
-  if (nr_on) a.aud_out = ctx->d_aud24;  // the fused kernel stops behind the demodulator
+  if (stages_on) a.aud_out = ctx->d_aud24;  // the fused kernel stops behind the demodulator
   hipError_t e = launch_rx(a, ctx->params.fft_length, ctx->params.mode, (hipStream_t)hip_stream);
   if (e != hipSuccess) return hip_fail(e, "kernel launch");
   if (nr_on) {
-    // Process.cpp:841-866 on the call's audio @24 kS/s, then the interpolators, volume and stores (Process.cpp:917-937)
+    // Process.cpp:841-866 on the call's audio @24 kS/s
     NrArgs n{};
     n.aud = ctx->d_aud24;
     n.anr = ctx->d_nr_anr;
@@ -694,6 +736,21 @@ int process_device_impl(t41rx_ctx *ctx, const float *dI, const float *dQ, float 
     nr_vad_range(ctx->params.FLoCut, ctx->params.FHiCut, &n.vad_lo, &n.vad_hi);
     e = launch_nr(n, (hipStream_t)hip_stream);
     if (e != hipSuccess) return hip_fail(e, "noise-reduction kernel launch");
+  }
+  if (nb_on) {
+    // Process.cpp:873-876 behind them
+    NbArgs b{};
+    b.aud = ctx->d_aud24;
+    b.carry = ctx->d_nb;
+    b.nchan = ctx->nchan;
+    b.nframes = n_frames;
+    b.sel = ctx->nb_sel;
+    e = launch_nb(b, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "noise-blanker kernel launch");
+    ctx->nb_sel ^= 1;  // the last frame wrote the other slot
+  }
+  if (stages_on) {
+    // then the interpolators, volume and stores (Process.cpp:917-937)
     a.aud_out = nullptr;
     a.aud24 = ctx->d_aud24;
     e = launch_back512(a, (hipStream_t)hip_stream);
@@ -785,18 +842,22 @@ constexpr size_t kStateHeaderBytes = 32;
 //          Kim / spectral records [n_channels][kNrSpecFloats] (Noise.cpp:19-56) -- present once the stages have run
 //   bit 1  display FFT: zoom filters, ring, FFT_spec_old [n_channels][kDispFloats] (FFT.cpp:14-26) -- present while
 //          t41rx_set_display_spectrum is on; header word 6 = its spectrumZoom
-constexpr int32_t kSecNr = 1, kSecDisp = 2;
+//   bit 2  noise blanker: last_frame_end[0 .. 12] (DSP_Fn.cpp:143), [n_channels][kNbCarryPitch] (3 floats of
+//          padding) -- present once the blanker has run
+constexpr int32_t kSecNr = 1, kSecDisp = 2, kSecNb = 4;
 static size_t nr_section_bytes(int nchan) { return sizeof(float) * ((size_t)kAnrStRows + (size_t)kNrSpecFloats) * (size_t)nchan; }
 static size_t disp_section_bytes(int nchan) { return sizeof(float) * (size_t)kDispFloats * (size_t)nchan; }
+static size_t nb_section_bytes(int nchan) { return sizeof(float) * (size_t)kNbCarryPitch * (size_t)nchan; }
 static int32_t state_sections(const t41rx_ctx *ctx) {
-  return (ctx->d_nr_anr ? kSecNr : 0) | ((ctx->disp_spec && ctx->d_disp) ? kSecDisp : 0);
+  return (ctx->d_nr_anr ? kSecNr : 0) | ((ctx->disp_spec && ctx->d_disp) ? kSecDisp : 0) | (ctx->d_nb ? kSecNb : 0);
 }
 
 size_t t41rx_state_bytes(const t41rx_ctx *ctx) {
   if (!ctx) return 0;
   const int32_t sec = state_sections(ctx);
   return kStateHeaderBytes + sizeof(float) * state_floats(ctx->params.fft_length) * (size_t)ctx->nchan +
-         ((sec & kSecNr) ? nr_section_bytes(ctx->nchan) : 0) + ((sec & kSecDisp) ? disp_section_bytes(ctx->nchan) : 0);
+         ((sec & kSecNr) ? nr_section_bytes(ctx->nchan) : 0) + ((sec & kSecDisp) ? disp_section_bytes(ctx->nchan) : 0) +
+         ((sec & kSecNb) ? nb_section_bytes(ctx->nchan) : 0);
 }
 
 // the pipelined kernels count a wait that ran out (rx_kernels.hip: pipe_wait_ge) behind their slots: a broken hand-over
@@ -855,7 +916,13 @@ int t41rx_get_state(t41rx_ctx *ctx, void *host_buf, size_t bytes) {
     HIP_TRY(hipMemcpy(out + ab, ctx->d_nr_spec, nr_section_bytes(ctx->nchan) - ab, hipMemcpyDeviceToHost));
     out += nr_section_bytes(ctx->nchan);
   }
-  if (sec & kSecDisp) HIP_TRY(hipMemcpy(out, ctx->d_disp, disp_section_bytes(ctx->nchan), hipMemcpyDeviceToHost));
+  if (sec & kSecDisp) {
+    HIP_TRY(hipMemcpy(out, ctx->d_disp, disp_section_bytes(ctx->nchan), hipMemcpyDeviceToHost));
+    out += disp_section_bytes(ctx->nchan);
+  }
+  if (sec & kSecNb)  // the current slot
+    HIP_TRY(hipMemcpy(out, ctx->d_nb + (size_t)ctx->nb_sel * kNbCarryPitch * (size_t)ctx->nchan, nb_section_bytes(ctx->nchan),
+                      hipMemcpyDeviceToHost));
   return T41RX_OK;
 }
 
@@ -869,18 +936,20 @@ int t41rx_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes) {
       hdr[3] != ctx->nchan || hdr[4] != (int32_t)sf)
     return fail(T41RX_ERR_STATE, "checkpoint header does not match this context (magic / abi / fft_length / channels)");
   const int32_t sec = hdr[5];
-  if (sec & ~(kSecNr | kSecDisp)) return fail(T41RX_ERR_STATE, "checkpoint: unknown sections");
+  if (sec & ~(kSecNr | kSecDisp | kSecNb)) return fail(T41RX_ERR_STATE, "checkpoint: unknown sections");
   const size_t path_bytes = sizeof(float) * sf * (size_t)ctx->nchan;
   if (bytes != kStateHeaderBytes + path_bytes + ((sec & kSecNr) ? nr_section_bytes(ctx->nchan) : 0) +
-                   ((sec & kSecDisp) ? disp_section_bytes(ctx->nchan) : 0))
+                   ((sec & kSecDisp) ? disp_section_bytes(ctx->nchan) : 0) + ((sec & kSecNb) ? nb_section_bytes(ctx->nchan) : 0))
     return fail(T41RX_ERR_STATE, "state size mismatch");
   if ((sec & kSecNr) && ctx->params.fft_length != 512) return fail(T41RX_ERR_STATE, "checkpoint: noise-reduction section at a long fft_length");
+  if ((sec & kSecNb) && ctx->params.fft_length != 512) return fail(T41RX_ERR_STATE, "checkpoint: noise-blanker section at a long fft_length");
   if (sec & kSecDisp) {
     if (!(ctx->disp_spec && ctx->d_disp)) return fail(T41RX_ERR_STATE, "checkpoint carries display-FFT state but the display spectrum is off here");
     if (hdr[6] != ctx->disp_zoom) return fail(T41RX_ERR_STATE, "checkpoint: display-FFT state of another spectrumZoom");
   }
   const char *nr_sec = static_cast<const char *>(host_buf) + kStateHeaderBytes + path_bytes;
   const char *disp_sec = nr_sec + ((sec & kSecNr) ? nr_section_bytes(ctx->nchan) : 0);
+  const char *nb_sec = disp_sec + ((sec & kSecDisp) ? disp_section_bytes(ctx->nchan) : 0);
   if (sec & kSecNr) {
     // what the kernels index with or divide by (nr_kernels.hip): Xanr()'s leak index, the spectral functions' ring pointers
     const float *anr = reinterpret_cast<const float *>(nr_sec);
@@ -931,6 +1000,10 @@ int t41rx_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes) {
     const int rc = ensure_nr(ctx);
     if (rc != T41RX_OK) return rc;
   }
+  if (sec & kSecNb) {
+    const int rc = ensure_nb(ctx);
+    if (rc != T41RX_OK) return rc;
+  }
   HIP_TRY(hipMemcpy(ctx->d_state, rec, path_bytes, hipMemcpyHostToDevice));
   ctx->nco_sel = 0;  // (a checkpoint carries the current oscillator state in both slots)
   // The side stages' memories follow the checkpoint too: restored where it carries them, back to power-on where it
@@ -947,6 +1020,13 @@ int t41rx_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes) {
     HIP_TRY(hipMemcpy(ctx->d_disp, disp_sec, disp_section_bytes(ctx->nchan), hipMemcpyHostToDevice));
   } else if (ctx->d_disp) {
     HIP_TRY(hipMemset(ctx->d_disp, 0, sizeof(float) * kDispFloats * (size_t)ctx->nchan));  // ZoomFFTPrep()
+  }
+  if (sec & kSecNb) {
+    HIP_TRY(hipMemcpy(ctx->d_nb, nb_sec, nb_section_bytes(ctx->nchan), hipMemcpyHostToDevice));
+    ctx->nb_sel = 0;
+  } else if (ctx->d_nb) {
+    HIP_TRY(hipMemset(ctx->d_nb, 0, sizeof(float) * 2 * kNbCarryPitch * (size_t)ctx->nchan));  // the static's power-on zero
+    ctx->nb_sel = 0;
   }
   return pipe_timeouts_clear(ctx);  // the restored state is valid again
 }

@@ -123,6 +123,18 @@ class RxChain:
         check(self._lib.t41rx_set_buffer_layout(self._ctx, code))
         self.layout = layout
 
+    def set_noise_blanker(self, on):
+        """NB_on (Process.cpp:873-876): the receive noise blanker on the demodulated audio, behind the noise reduction and
+        the notch (t41rx_set_noise_blanker; 0 / 1, fft_length 512).  Kept across CalcFilters() / set_coeffs()."""
+        check(self._lib.t41rx_set_noise_blanker(self._ctx, int(on)))
+
+    @property
+    def noise_blanker(self):
+        v = self._lib.t41rx_get_noise_blanker(self._ctx)
+        if v < 0:
+            check(v)
+        return v
+
     def get_state(self):
         n = self._lib.t41rx_state_bytes(self._ctx)
         buf = np.zeros(n, dtype=np.uint8)

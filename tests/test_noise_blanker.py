@@ -1,0 +1,448 @@
+"""Receive noise blanker (NB_on; NoiseBlanker() / AltNoiseBlanking(), DSP_Fn.cpp:105-362, call site Process.cpp:873-876).
+
+CPU: the f32 restatement (tests/nb_model.py) against the independent float64 model, what the blanker does to clicks,
+the quirks it keeps, the new entry points.  GPU (-m gpu): the HIP path with the blanker on against the HIP path's own
+demodulated audio through the restatement and the oracle's interpolators.
+"""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+
+import nb_model as M
+import oracle_lib as O
+import siggen
+
+L, D = 2048, 256
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def audio(nblocks, seed, tone=(700.0, 0.2), noise=0.05):
+    rng = np.random.default_rng(seed)
+    n = np.arange(nblocks * D)
+    return (tone[1] * np.sin(2 * np.pi * tone[0] / 24000.0 * n + 0.3) + noise * rng.standard_normal(n.size)).astype(np.float32)
+
+
+def clicks(x, where, amp=1.0):
+    y = x.copy()
+    for i, c in enumerate(where):
+        y[c] += np.float32(amp if i % 2 == 0 else -amp)
+    return y
+
+
+# ---- CPU ---------------------------------------------------------------------------------------------------------------
+def test_restatement_matches_the_f64_model():
+    x = clicks(audio(40, seed=1), [b * D + 30 + 7 * b for b in range(0, 40, 2)])
+    y32, p32, mg, _ = M.stream(x)
+    y64, p64, _, _ = M.stream(x, model="f64")
+    ok = mg >= 1e-4
+    assert ok.mean() > 0.9 and sum(map(len, p32)) >= 20
+    for b in np.flatnonzero(ok):
+        assert p32[b] == p64[b], (b, p32[b], p64[b], mg[b])
+    e = np.abs(y32.astype(np.float64) - y64).reshape(-1, D).max(1) / np.abs(y64).reshape(-1, D).max(1)
+    assert e[ok].max() < 1e-4, e[ok].max()
+
+
+def test_variance_form_changes_no_detection():
+    """arm_var_f32: two-pass (restated) against the one-pass form of older CMSIS releases -- same detections"""
+    for seed in range(4):
+        x = clicks(audio(24, seed=seed, noise=0.02 + 0.03 * seed), [b * D + 50 + 7 * b for b in range(24)])
+        _, a, _, _ = M.stream(x)
+        _, b, _, _ = M.stream(x, var="onepass")
+        assert a == b
+
+
+def test_blanker_finds_and_removes_clicks():
+    clean = audio(12, seed=7, noise=0.02)
+    where = [2 * D + 40, 3 * D + 120, 5 * D + 200, 7 * D + 77, 9 * D + 150]
+    y = clicks(clean, where, amp=1.5)
+    out, pos, _, _ = M.stream(y)
+    found = [b * D + p for b, ps in enumerate(pos) for p in ps]
+    for c in where:
+        assert c in found, (c, found)
+        w = slice(c - M.PL, c + M.PL + 1)
+        resid = np.sum((out[w].astype(np.float64) - clean[w]) ** 2)
+        assert resid < 0.1 * 1.5 ** 2, (c, resid)
+
+
+def test_blocks_without_detection_come_back_unchanged():
+    x = audio(16, seed=3)
+    out, pos, _, _ = M.stream(x)
+    quiet = [b for b, p in enumerate(pos) if not p]
+    assert len(quiet) >= 4
+    for b in quiet:
+        assert np.array_equal(out[b * D:(b + 1) * D], x[b * D:(b + 1) * D])
+    z = np.zeros(4 * D, np.float32)  # alfa = 0: NaN coefficients, NaN threshold, nothing detected
+    oz, pz, _, _ = M.stream(z)
+    assert np.array_equal(oz, z) and not any(pz)
+
+
+def test_cap_upper_boundary_and_the_carry_quirk():
+    x = audio(3, seed=9, noise=0.01)
+    gaps = np.random.default_rng(4).integers(5, 12, 40)  # an irregular train (a periodic one is predictable)
+    train = [int(v) for v in D + 14 + np.concatenate([[0], np.cumsum(gaps)]) if v < 2 * D - 20]
+    _, pos, _, _ = M.stream(clicks(x, train, amp=2.0))
+    assert len(train) > 20 and len(pos[1]) == 20 and pos[1][-1] < train[-1] - D
+    late = clicks(x, [D + 236, D + 240, D + 245], amp=3.0)
+    _, pos, _, _ = M.stream(late)
+    assert all(p <= D - M.BOUND - 1 - M.ORDER for p in pos[1])
+    # an impulse at pos < 13 seeds its forward prediction from last_frame_end[pos + k] (one sample early)
+    y = clicks(x, [D + 5], amp=2.0)
+    q, pq, _, _ = M.stream(y)
+    fx, pf, _, _ = M.stream(y, carry_fix=True)
+    assert 5 in pq[1] and pq == pf
+    assert not np.array_equal(q[D:D + 16], fx[D:D + 16])
+    o64, _, _, _ = M.stream(y, model="f64")
+    f64, _, _, _ = M.stream(y, model="f64", carry_fix=True)
+    assert np.abs(q[D:D + 16] - o64[D:D + 16]).max() < np.abs(q[D:D + 16] - f64[D:D + 16]).max()
+
+
+def test_entry_points_declared_and_exported(built):
+    import t41_sdr_amd._lib as lib
+    hdr = open(os.path.join(ROOT, "include", "t41rx.h")).read()
+    m = open(os.path.join(ROOT, "t41_sdr_amd", "csrc", "exports.map")).read()
+    for name in ("t41rx_set_noise_blanker", "t41rx_get_noise_blanker"):
+        assert re.search(r"\b%s\s*\(" % name, hdr) and (name + ";") in m and name in lib.SYMBOLS
+        assert hasattr(C.CDLL(lib.LIB_PATH), name)
+
+
+# ---- GPU ---------------------------------------------------------------------------------------------------------------
+DELAY = 140  # audio samples from a single-sample RF click to its peak in the demodulated audio (wide SSB / AM / SAM filters)
+
+
+def clicky_iq(nch, nfr, seed, amp=20.0):
+    """complex white noise (a wide filter makes the audio nearly white, so the predictor is short) with single-sample RF
+    clicks: random ones, and in every frame one timed to peak at audio sample 3 .. 8 of the block (the carry path)"""
+    rng = np.random.default_rng(seed)
+    x = 0.02 * (rng.standard_normal((nch, nfr * L)) + 1j * rng.standard_normal((nch, nfr * L)))
+    for c in range(nch):
+        at = list(rng.integers(0, nfr * L, 3 * nfr)) + [f * L + 8 * (int(rng.integers(3, 9)) - DELAY) for f in range(1, nfr)]
+        for i in at:
+            x[c, i] += amp * np.exp(2j * np.pi * rng.random())
+    return x.real.astype(np.float32), x.imag.astype(np.float32)
+
+
+WIDE = {0: dict(FLoCut=100, FHiCut=11000), 1: dict(FLoCut=-11000, FHiCut=-100), 2: dict(FLoCut=-11000, FHiCut=11000),
+        3: {}, 8: dict(FLoCut=-11000, FHiCut=11000)}
+
+
+def _vol_scale(v):
+    x = np.float32(v) / np.float32(100.0)
+    return np.float32(8.0) * (np.float32(5) * x * x * x * x * x)
+
+
+def stage24(pre, kw, model="f32", on=None, carry=None):
+    """the HIP path's pre-stage audio through the oracle's NR stage (if on) and the blanker model on the blocks where
+    on[b] (default: all); the carry is the input of the last block the blanker saw, as in the reference"""
+    lib = O.lib()
+    p = O.default_params(**kw)
+    nch, n = pre.shape
+    nb = n // D
+    on = [True] * nb if on is None else on
+    out = np.empty(pre.shape, np.float32)
+    R = np.zeros(D, np.float32)
+    stats = dict(repairs=0, low=0, cap=0, near=0)
+    pos_all, near = [], np.zeros((nch, nb), bool)
+    for ch in range(nch):
+        a = pre[ch].copy()
+        if p.nrOptionSelect or p.ANR_notchOn:
+            s = lib.t41o_nr_create()
+            for b in range(nb):
+                blk = a[b * D:(b + 1) * D].copy()
+                lib.t41o_nr_block(s, C.byref(p), O.fptr(blk), O.fptr(R))
+                a[b * D:(b + 1) * D] = blk
+            lib.t41o_nr_destroy(s)
+        cy = np.zeros(M.NCARRY + 1) if carry is None else carry[ch]
+        pos_ch = []
+        for b in range(nb):
+            blk = a[b * D:(b + 1) * D]
+            if not on[b]:
+                pos_ch.append(None)
+                continue
+            if model == "f32":
+                y, pos, mg, _ = M.block_f32(blk, cy)
+                stats["near"] += int(mg < 1e-4)
+                near[ch, b] = mg < 1e-4
+            else:
+                y, pos, _ = M.block_f64(blk, cy)
+            stats["repairs"] += len(pos)
+            stats["low"] += sum(q < 13 for q in pos)
+            stats["cap"] += len(pos) == M.MAXIMP
+            pos_ch.append(pos)
+            cy = blk[M.N - 1 - M.ORDER - M.PL:].copy()
+            a[b * D:(b + 1) * D] = y
+        out[ch] = a
+        pos_all.append(pos_ch)
+    stats["near_blocks"] = near
+    return out, stats, pos_all
+
+
+def interp(a24, kw):
+    """the oracle's interpolators and volume (Process.cpp:917-931), continuous over the stream"""
+    lib = O.lib()
+    p = O.default_params(**kw)
+    c = O.design(p)
+    nch, n = a24.shape
+    out = np.empty((nch, 8 * n), np.float32)
+    for ch in range(nch):
+        st1, st2 = np.zeros(23 + D, np.float32), np.zeros(7 + 2 * D, np.float32)
+        mid, hi = np.empty(2 * D, np.float32), np.empty(8 * D, np.float32)
+        for b in range(n // D):
+            blk = np.ascontiguousarray(a24[ch, b * D:(b + 1) * D], np.float32)
+            lib.t41o_fir_interpolate_f32(c.int1, 48, 2, O.fptr(st1), O.fptr(blk), O.fptr(mid), D)
+            lib.t41o_fir_interpolate_f32(c.int2, 32, 4, O.fptr(st2), O.fptr(mid), O.fptr(hi), 2 * D)
+            out[ch, b * L:(b + 1) * L] = hi * _vol_scale(p.audioVolume)
+    return out
+
+
+def expect(pre, kw, **k):
+    a, st, _ = stage24(pre, kw, **k)
+    return interp(a, kw), st
+
+
+def run_hip(kw, nch, nfr, seed, q15=False, layout="channel", splits=None, nb=1, iq=None):
+    import torch
+    import t41_sdr_amd as T
+    nco = siggen.nco_grid(nch, seed=seed)
+    I, Q = clicky_iq(nch, nfr, seed) if iq is None else iq
+    rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
+    rx.set_noise_blanker(nb)
+    if layout == "time":
+        rx.set_buffer_layout("time")
+    tap = torch.zeros(nch, nfr * D, device="cuda")
+    if q15:
+        I, Q = [np.clip(np.round(v * 32768.0 / 64), -32768, 32767).astype(np.int16) for v in (I, Q)]
+    got = []
+    edges = splits or [0, nfr]
+    for a, b in zip(edges[:-1], edges[1:]):
+        t = torch.zeros(nch, (b - a) * D, device="cuda")
+        rx.set_debug_taps(demod=t)
+        i, q = I[:, a * L:b * L], Q[:, a * L:b * L]
+        if layout == "time":
+            i = i.reshape(nch, b - a, L).transpose(1, 0, 2).copy()
+            q = q.reshape(nch, b - a, L).transpose(1, 0, 2).copy()
+        if q15:
+            o = rx.ProcessIQData_q15(torch.from_numpy(np.ascontiguousarray(q)).cuda(), torch.from_numpy(np.ascontiguousarray(i)).cuda())
+        else:
+            o = rx.ProcessIQData(torch.from_numpy(np.ascontiguousarray(i)).cuda(), torch.from_numpy(np.ascontiguousarray(q)).cuda())
+        o = o.cpu().numpy()
+        if layout == "time":
+            o = o.reshape(b - a, nch, L).transpose(1, 0, 2).reshape(nch, (b - a) * L)
+        got.append(o)
+        tap[:, a * D:b * D] = t
+    return np.concatenate(got, axis=1), tap.cpu().numpy(), rx
+
+
+CASES = {  # name: (params, least repairs, least impulses at pos < 13) over the 12 x 16 stream of clicky_iq(seed 21)
+    "usb": (dict(mode=0, **WIDE[0]), 10, 3), "lsb": (dict(mode=1, **WIDE[1]), 10, 3), "am": (dict(mode=2, **WIDE[2]), 5, 1),
+    "sam": (dict(mode=8, **WIDE[8]), 10, 3), "usb-agc": (dict(mode=0, AGCMode=1, **WIDE[0]), 5, 0),  # (the AGC's look-ahead gain drop mutes the frame-start clicks)
+    "sam-agc": (dict(mode=8, AGCMode=2, **WIDE[8]), 10, 1), "kim": (dict(mode=0, nrOptionSelect=1, **WIDE[0]), 10, 1),
+    "notch": (dict(mode=0, ANR_notchOn=1, **WIDE[0]), 10, 3),
+    # NFM's limiter and quadri-correlator leave no click in the audio: the stage runs and finds nothing
+    "nfm": (dict(mode=3), 0, 0),
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_gpu_whole_path_with_nb(built, name):
+    """the whole path with the blanker on = the HIP path's own demodulated audio through the (oracle's NR stage,) the f32
+    restatement and the oracle's interpolators; and no farther from the float64 blanker model than the restatement is"""
+    kw, k_rep, k_low = CASES[name]
+    got, pre, _ = run_hip(kw, 12, 16, seed=21)
+    assert np.isfinite(got).all()
+    want, st = expect(pre, kw)
+    e = siggen.block_rel_err(got, want, L)
+    want64, _ = expect(pre, kw, model="f64")
+    d_hip, d_res = siggen.block_rel_err(got, want64, L), siggen.block_rel_err(want, want64, L)
+    near = st.pop("near_blocks")
+    print(name, st, "max block-relative %.2e; vs the f64 model: HIP %.2e, restatement %.2e" % (e.max(), d_hip.max(), d_res.max()))
+    # (the kernel takes the restatement's decisions, so blocks near the threshold need no exclusion from the parity
+    # check; against the f64 model, whose decisions may differ there, they are left out -- and counted: 0 or 1 here)
+    assert st["near"] <= 2, st
+    assert st["repairs"] >= k_rep and st["low"] >= k_low, st
+    # (Kim in front: its own f32 conditioning between two evaluations, 1e-5 .. 2e-5 -- test_noise_reduction.py NR_CASES)
+    tol = 2e-5 if name == "kim" else 1e-5
+    assert e.max() <= tol, (e.max(), np.unravel_index(e.argmax(), e.shape))
+    # (per block, up to what the stage in front already differs by: Kim's own 1e-5 .. 2e-5, 2e-6 otherwise)
+    slack = tol if name == "kim" else 2e-6
+    assert (d_hip <= d_res + slack)[~near].all(), (d_hip[~near].max(), d_res[~near].max())
+    assert d_hip[~near].max() <= d_res[~near].max() + 2e-6
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("how", ["q15", "time", "splits"])
+def test_gpu_nb_entry_points_layouts_and_splits(built, how):
+    kw = CASES["sam"][0]
+    whole, pre, _ = run_hip(kw, 7, 12, seed=22)
+    _, st = expect(pre, kw)
+    assert st["low"] >= 1, st  # the carry crosses the splits
+    if how == "splits":
+        rng = np.random.default_rng(4)
+        cuts = sorted(set(rng.integers(1, 12, 4).tolist()))
+        for edges in ([0] + cuts + [12], list(range(13))):
+            got, _, _ = run_hip(kw, 7, 12, seed=22, splits=edges)
+            assert np.array_equal(got, whole), edges
+    elif how == "time":
+        got, _, _ = run_hip(kw, 7, 12, seed=22, layout="time")
+        assert np.array_equal(got, whole)
+    else:
+        got, pre, _ = run_hip(kw, 7, 12, seed=22, q15=True)
+        want, st = expect(pre, kw)
+        ref = np.clip(np.trunc(want.astype(np.float64) * 32768.0), -32768, 32767)
+        assert np.abs(got.astype(np.float64) - ref).max() <= 1 and st["repairs"] > 0, st
+
+
+@pytest.mark.gpu
+def test_gpu_checkpoint_and_refusals(built):
+    import torch
+    import t41_sdr_amd as T
+    import t41_sdr_amd._lib as lib
+    kw = CASES["sam"][0]
+    nch, nfr, cut = 5, 10, 6
+    whole, pre, _ = run_hip(kw, nch, nfr, seed=23)
+    _, st, pos = stage24(pre, kw)
+    assert any(pos[c][cut] and min(pos[c][cut]) < 13 for c in range(nch)), [pos[c][cut] for c in range(nch)]  # carry read at the cut
+    nco = siggen.nco_grid(nch, seed=23)
+    I, Q = clicky_iq(nch, nfr, 23)
+    dI, dQ = torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()
+    part = lambda a, b: (dI[:, a * L:b * L].contiguous(), dQ[:, a * L:b * L].contiguous())  # noqa: E731
+    rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
+    fresh = rx.get_state()
+    rx.set_noise_blanker(1)
+    a = rx.ProcessIQData(*part(0, cut)).cpu().numpy()
+    ck = rx.get_state()
+    assert ck.size == fresh.size + 64 * nch and ck[:32].view(np.int32)[5] & 4
+    rx.ProcessIQData(*part(0, 3))  # disturb
+    rx.set_state(ck)
+    b = rx.ProcessIQData(*part(cut, nfr)).cpu().numpy()
+    assert np.array_equal(np.concatenate([a, b], axis=1), whole)
+    ry = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
+    ry.set_noise_blanker(1)
+    ry.set_state(ck)
+    assert np.array_equal(ry.ProcessIQData(*part(cut, nfr)).cpu().numpy(), b)
+    rx.set_state(fresh)  # no section: the carry restarts at zero (= the stream from power-on)
+    assert np.array_equal(rx.ProcessIQData(*part(0, nfr)).cpu().numpy(), whole)
+    rx.reset()
+    assert np.array_equal(rx.ProcessIQData(*part(0, nfr)).cpu().numpy(), whole)
+    # refusals
+    for v in (2, -1):
+        with pytest.raises(T.T41RxError) as ei:
+            rx.set_noise_blanker(v)
+        assert ei.value.status == lib.ERR_ARG
+    bad = ck.copy()
+    bad[:32].view(np.int32)[5] |= 8
+    with pytest.raises(T.T41RxError):
+        rx.set_state(bad)
+    assert rx.noise_blanker == 1
+    rx.CalcFilters(audioVolume=40)
+    assert rx.noise_blanker == 1
+    rl = T.RxChain(2, T.default_params(fft_length=1024))
+    with pytest.raises(T.T41RxError) as ei:
+        rl.set_noise_blanker(1)
+    assert ei.value.status == lib.ERR_UNSUPPORTED
+    long_ck = rl.get_state()
+    with_nb = np.concatenate([long_ck, np.zeros(64 * 2, np.uint8)])
+    with_nb[:32].view(np.int32)[5] |= 4  # a blanker section (sized right) at fft_length 1024
+    with pytest.raises(T.T41RxError) as ei:
+        rl.set_state(with_nb)
+    assert ei.value.status == lib.ERR_STATE
+    rl.set_state(long_ck)
+    L_ = lib.load()
+    assert L_.t41rx_set_noise_blanker(None, 1) == lib.ERR_ARG and L_.t41rx_get_noise_blanker(None) == lib.ERR_ARG
+
+
+@pytest.mark.gpu
+def test_gpu_on_off_on_keeps_the_stale_carry(built):
+    """switched off and on again, the blanker's first block seeds below its start from the input of the last block it
+    saw before it was switched off (last_frame_end only changes while it runs): the whole stream, interpolators
+    continuous, against the restatement with that carry; frame 6 holds an impulse at pos < 13, and a zeroed carry would
+    not match"""
+    import torch
+    import t41_sdr_amd as T
+    kw = CASES["sam"][0]
+    nch, nfr = 12, 10
+    nco = siggen.nco_grid(nch, seed=24)
+    I, Q = clicky_iq(nch, nfr, 24)
+    dI, dQ = torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()
+    rz = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
+    tap = torch.zeros(nch, nfr * D, device="cuda")
+    outs = []
+    for (s, e), on in zip(((0, 3), (3, 6), (6, nfr)), (1, 0, 1)):
+        rz.set_noise_blanker(on)
+        t = torch.zeros(nch, (e - s) * D, device="cuda")
+        rz.set_debug_taps(demod=t)
+        outs.append(rz.ProcessIQData(dI[:, s * L:e * L].contiguous(), dQ[:, s * L:e * L].contiguous()).cpu().numpy())
+        tap[:, s * D:e * D] = t
+    got = np.concatenate(outs, axis=1)
+    pre = tap.cpu().numpy()
+    on = [b < 3 or b >= 6 for b in range(nfr)]
+    a24, st, pos = stage24(pre, kw, on=on)
+    e = siggen.block_rel_err(got, interp(a24, kw), L)
+    assert e.max() <= 1e-5, e.max()
+    low6 = [c for c in range(nch) if pos[c][6] and min(pos[c][6]) < 13]
+    assert low6, [pos[c][6] for c in range(nch)]
+    # the same with last_frame_end zeroed at the switch: frame 6 of those channels differs
+    z24 = a24.copy()
+    for c in low6:
+        y, _, _, _ = M.block_f32(pre[c, 6 * D:7 * D], np.zeros(M.NCARRY + 1))
+        z24[c, 6 * D:7 * D] = y
+    ez = siggen.block_rel_err(got[low6], interp(z24[low6], kw), L)
+    assert ez[:, 6].max() > 1e-4, ez[:, 6]
+
+
+@pytest.mark.gpu
+def test_gpu_degenerate_input_and_no_detection(built):
+    import torch
+    import t41_sdr_amd as T
+    # an all-zero channel stays zero (alfa = 0: NaN coefficients, no detection)
+    z = torch.zeros(2, 3 * L, device="cuda")
+    r0 = T.RxChain(2, T.default_params(), NCOFreq=[0, 1000])
+    r0.set_noise_blanker(1)
+    oz = r0.ProcessIQData(z, z).cpu().numpy()
+    assert np.isfinite(oz).all() and not oz.any()
+    # a pure tone without noise: the near-singular Levinson case; finite wherever the restatement's output is
+    nch, nfr = 4, 8
+    nco = siggen.nco_grid(nch, seed=5)
+    n = np.arange(nfr * L)
+    x = np.stack([0.3 * np.exp(2j * np.pi * siggen.passband_tone_hz(0, nco[c], 1000.0 + 300 * c) / 192000.0 * n) for c in range(nch)])
+    iq = (x.real.astype(np.float32), x.imag.astype(np.float32))
+    got, pre, _ = run_hip(dict(mode=0), nch, nfr, seed=5, iq=iq)
+    want, st = expect(pre, dict(mode=0))
+    fin = np.isfinite(want)
+    assert np.isfinite(got)[fin].all(), st
+    ok = fin.reshape(nch, nfr, L).all(axis=2)
+    e = siggen.block_rel_err(np.where(fin, got, 0), np.where(fin, want, 0), L)
+    print("pure tone:", st, "finite frames", ok.sum(), "max block-relative %.2e" % e[ok].max())
+    assert e[ok].max() <= 1e-5
+    # NB on where it detects nothing (NFM: the limiter leaves no click in the audio) against NB off
+    res = []
+    for on in (0, 1):
+        o, p, _ = run_hip(dict(mode=3), 12, 16, seed=21, nb=on)
+        res.append(o)
+    _, st = expect(p, dict(mode=3))
+    assert st["repairs"] == 0, st
+    d = siggen.block_rel_err(res[1], res[0], L)
+    print("NB on without detections vs off: max block-relative %.2e, bit-identical %s" % (d.max(), np.array_equal(res[0], res[1])))
+    assert d.max() <= 1e-6
+
+
+@pytest.mark.gpu
+def test_gpu_nb_large_batch_spot_check(built):
+    import torch
+    import t41_sdr_amd as T
+    nch, nfr = 4096, 4
+    kw = CASES["usb"][0]
+    nco = siggen.nco_grid(nch, seed=30)
+    I, Q = clicky_iq(nch, nfr, 30)
+    rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
+    rx.set_noise_blanker(1)
+    tap = torch.zeros(nch, nfr * D, device="cuda")
+    rx.set_debug_taps(demod=tap)
+    got = rx.ProcessIQData(torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()).cpu().numpy()
+    pre = tap.cpu().numpy()
+    pick = [0, 1, 63, 64, 2047, 4095]
+    want, st = expect(pre[pick], kw)
+    assert siggen.block_rel_err(got[pick], want, L).max() <= 1e-5, st
