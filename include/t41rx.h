@@ -167,6 +167,31 @@ T41RX_API int t41rx_reset(t41rx_ctx *ctx);
 T41RX_API int t41rx_set_noise_blanker(t41rx_ctx *ctx, int NB_on);
 T41RX_API int t41rx_get_noise_blanker(const t41rx_ctx *ctx);  /* 0 / 1, or T41RX_ERR_ARG for a NULL context */
 
+/* receiveEQFlag (Process.cpp:828-832): 1 = the receive equalizer DoReceiveEQ() (Filter.cpp:117-165) on the demodulated
+ * audio @24 kS/s, in front of the noise reduction, the notch and the noise blanker (the audio spectrum / S-meter side
+ * output is taken before it): 14 bands of 4 cascaded arm_biquad_cascade_df2T_f32 sections on the same input, band k's
+ * output times -recEQ_LevelScale[k-1] for odd k and +recEQ_LevelScale[k-1] for even k, recEQ_LevelScale[i] =
+ * (float)equalizerRec[i] / 100.0, summed EQ1 + EQ2, then + EQ3, .., + EQ14.  0 = off (the default).
+ *
+ * t41rx_set_receive_eq_bands(): the band table, coeffs[14][4][5] floats = the firmware's EQ_Band1Coeffs ..
+ *   EQ_Band14Coeffs (FIR.cpp:279-370) concatenated, {b0, b1, b2, a1, a2} per section with the a's negated (CMSIS DF2T
+ *   order).  The library has no table of its own: it must be loaded before the equalizer can be switched on.  T41RX_ERR_ARG
+ *   for NULL or a non-finite value.  Kept across t41rx_set_params() and t41rx_set_coeffs(); a new table takes effect
+ *   from the next process call and does not reset the filter memories (the firmware's tables are constant, so this has
+ *   no reference counterpart).
+ * t41rx_set_receive_eq(): receiveEQFlag 0 or 1 (T41RX_ERR_ARG otherwise; T41RX_ERR_UNSUPPORTED for 1 at a long
+ *   fft_length; T41RX_ERR_ARG for 1 before a band table is loaded).  equalizerRec = EEPROMData.equalizerRec[14], or
+ *   NULL to keep the current levels (100 each until set, EEPROM.cpp:59); any int is taken as the firmware would hold it.
+ *   A context switch, not a t41rx_params field: switch and levels survive t41rx_set_params() and t41rx_set_coeffs().
+ *   Takes effect from the next process call.
+ * The filter memories (rec_EQ_Band1_state .. rec_EQ_Band14_state, Filter.cpp:43-56; 112 floats per channel) start at
+ * zero, change only while the equalizer runs (switched off and on again they are stale, as in the reference), are
+ * zeroed by t41rx_reset() and travel in the checkpoint (section bit 3). */
+T41RX_API int t41rx_set_receive_eq_bands(t41rx_ctx *ctx, const float *coeffs);
+T41RX_API int t41rx_set_receive_eq(t41rx_ctx *ctx, int receiveEQFlag, const int32_t *equalizerRec);
+/* 0 / 1, or T41RX_ERR_ARG for a NULL context; the 14 levels into equalizerRec_out unless it is NULL */
+T41RX_API int t41rx_get_receive_eq(const t41rx_ctx *ctx, int32_t *equalizerRec_out);
+
 T41RX_API int t41rx_n_channels(const t41rx_ctx *ctx);
 T41RX_API int t41rx_frame_len(const t41rx_ctx *ctx);
 
@@ -224,9 +249,11 @@ T41RX_API int t41rx_process_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, cons
  *     bit 1  display FFT: zoom filters, ring, FFT_spec_old (FFT.cpp:14-26) -- present while
  *            t41rx_set_display_spectrum() is on;
  *     bit 2  noise blanker: last_frame_end[0 .. 12] (DSP_Fn.cpp:143), 16 floats per channel (13 used) -- present once
- *            the blanker has run in this context; refused at a long fft_length.
- * t41rx_state_bytes() therefore GROWS when a noise-reduction stage or the noise blanker first runs or the display
- * spectrum is switched on:
+ *            the blanker has run in this context; refused at a long fft_length;
+ *     bit 3  receive equalizer: rec_EQ_Band1_state .. rec_EQ_Band14_state (Filter.cpp:43-56), 112 floats per channel --
+ *            present once the equalizer has run in this context; refused at a long fft_length.
+ * t41rx_state_bytes() therefore GROWS when a noise-reduction stage, the noise blanker or the receive equalizer first
+ * runs or the display spectrum is switched on:
  * query it right before every t41rx_get_state() (a buffer sized at creation gets T41RX_ERR_STATE "state buffer too
  * small").  fft_length cannot change on a live context, so the path records' size never does.
  * t41rx_set_state() refuses (T41RX_ERR_STATE) a checkpoint of another ABI, FFT length or channel count, one with an
@@ -236,7 +263,7 @@ T41RX_API int t41rx_process_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, cons
  * [0, 2 pi], frequency within +-pll_fmax), the notch's leak index, the noise reduction's ring pointers, the zoom ring's
  * pointer.  What it does to the side stages: a section the checkpoint carries is restored; a memory this context has
  * allocated but the checkpoint does not carry goes back to its power-on values (InitializeDataArrays() /
- * SpectralNoiseReductionInit() / ZoomFFTPrep() / the blanker's zero carry) -- never the values of the stream being replaced.
+ * SpectralNoiseReductionInit() / ZoomFFTPrep() / the blanker's zero carry / the equalizer's zero memories) -- never the values of the stream being replaced.
  * T41RX_ERR_STATE is also what t41rx_get_state(), t41rx_process_host() and t41rx_process_host_q15() -- the calls that
  * synchronise -- return if a wait inside the pipelined AGC / SAM kernels has run out since the last t41rx_reset() or
  * restored checkpoint (their waits are bounded so that a broken hand-over cannot hang the GPU; it cannot happen unless
@@ -249,7 +276,8 @@ T41RX_API int    t41rx_set_state(t41rx_ctx *ctx, const void *host_buf, size_t by
  * When set, the next process calls also write, per channel and frame:
  *   post_nco : [n_channels][n_frames*frame_len*2]  I/Q after FreqShift2 (planar: I then Q per frame)
  *   dec      : [n_channels][n_frames*fft_length]   I/Q after decimate-by-8 (+ level adjust)
- *   demod    : [n_channels][n_frames*fft_length/2] audio @24 kS/s before interpolation
+ *   demod    : [n_channels][n_frames*fft_length/2] audio @24 kS/s before interpolation, as the demodulator (and AGC)
+ *              leave it: before every optional stage (receive equalizer, noise reduction / notch, noise blanker)
  * max_frames = the n_frames the buffers are sized for: a process call with more frames is refused
  * (T41RX_ERR_ARG) instead of writing past them.  fft_length 512 only (T41RX_ERR_UNSUPPORTED). */
 T41RX_API int t41rx_set_debug_taps(t41rx_ctx *ctx, float *d_post_nco, float *d_dec, float *d_demod, int max_frames);

@@ -82,6 +82,9 @@ SYMBOLS = {
     "t41rx_set_display_spectrum": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int]),
     "t41rx_set_noise_blanker": (C.c_int, [_vp, C.c_int]),
     "t41rx_get_noise_blanker": (C.c_int, [_vp]),
+    "t41rx_set_receive_eq_bands": (C.c_int, [_vp, _vp]),
+    "t41rx_set_receive_eq": (C.c_int, [_vp, C.c_int, _vp]),
+    "t41rx_get_receive_eq": (C.c_int, [_vp, _vp]),
 }
 
 _lib = None

@@ -16,6 +16,8 @@
 #include <string>
 #include <vector>
 
+#include "eq_kernels.hpp"
+#include "eq_kernel.hip"  // the receive equalizer's kernel and launcher
 #include "nb_kernels.hpp"
 #include "nb_kernel.hip"  // the noise blanker's kernel and launcher
 #include "nr_kernels.hpp"
@@ -58,6 +60,14 @@ struct t41rx_ctx {
   int nb_on = 0;
   float *d_nb = nullptr;
   int nb_sel = 0;  // the slot holding the current carry (flips with every blanker launch)
+  // receive equalizer (receiveEQFlag, Process.cpp:828-832; t41rx_set_receive_eq): the caller's band table, the levels
+  // (EEPROMData.equalizerRec, EEPROM.cpp:59: 100 each), and rec_EQ_Band1_state .. rec_EQ_Band14_state per channel
+  // [nchan][kEqStateFloats] (eq_kernel.hip), allocated when the equalizer first runs
+  int eq_on = 0;
+  bool eq_have_bands = false;
+  float eq_coef[kEqCoefs] = {};
+  int32_t eq_levels[kEqBands] = {100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100};
+  float *d_eq = nullptr;
   // staging for t41rx_process_host
   float *d_in_i = nullptr, *d_in_q = nullptr, *d_out = nullptr;
   size_t staging_floats = 0;
@@ -261,6 +271,7 @@ int reset_state(t41rx_ctx *ctx) {
     HIP_TRY(hipMemset(ctx->d_nb, 0, sizeof(float) * 2 * kNbCarryPitch * (size_t)ctx->nchan));
     ctx->nb_sel = 0;
   }
+  if (ctx->d_eq) HIP_TRY(hipMemset(ctx->d_eq, 0, sizeof(float) * kEqStateFloats * (size_t)ctx->nchan));  // zeroed statics
   if (ctx->d_nr_anr) return reset_nr(ctx);
   return T41RX_OK;
 }
@@ -277,6 +288,20 @@ int ensure_nb(t41rx_ctx *ctx) {
   }
   ctx->d_nb = nb;
   ctx->nb_sel = 0;
+  return T41RX_OK;
+}
+
+// the receive equalizer's biquad memories, on first use (power-on: zero, Filter.cpp:43-56)
+int ensure_eq(t41rx_ctx *ctx) {
+  if (ctx->d_eq) return T41RX_OK;
+  const size_t bytes = sizeof(float) * kEqStateFloats * (size_t)ctx->nchan;
+  float *eq = nullptr;
+  if (hipMalloc((void **)&eq, bytes) != hipSuccess) return fail(T41RX_ERR_NOMEM, "receive-equalizer state allocation failed");
+  if (hipMemset(eq, 0, bytes) != hipSuccess) {
+    (void)hipFree(eq);
+    return fail(T41RX_ERR_HIP, "receive-equalizer state upload failed");
+  }
+  ctx->d_eq = eq;
   return T41RX_OK;
 }
 
@@ -339,6 +364,7 @@ void free_ctx(t41rx_ctx *ctx) {
   (void)hipFree(ctx->d_nr_spec);
   (void)hipFree(ctx->d_nr_tab);
   (void)hipFree(ctx->d_nb);
+  (void)hipFree(ctx->d_eq);
   delete ctx;
 }
 
@@ -581,6 +607,33 @@ int t41rx_set_noise_blanker(t41rx_ctx *ctx, int NB_on) {
 }
 int t41rx_get_noise_blanker(const t41rx_ctx *ctx) { return ctx ? ctx->nb_on : T41RX_ERR_ARG; }
 
+int t41rx_set_receive_eq_bands(t41rx_ctx *ctx, const float *coeffs) {
+  if (!ctx || !coeffs) return fail(T41RX_ERR_ARG, "null argument");
+  for (int i = 0; i < kEqCoefs; ++i)
+    if (!std::isfinite(coeffs[i])) return fail(T41RX_ERR_ARG, "receive-equalizer band table: non-finite coefficient");
+  std::memcpy(ctx->eq_coef, coeffs, sizeof(ctx->eq_coef));  // (passed by value to every launch: the next call uses it)
+  ctx->eq_have_bands = true;
+  return T41RX_OK;
+}
+
+int t41rx_set_receive_eq(t41rx_ctx *ctx, int receiveEQFlag, const int32_t *equalizerRec) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (receiveEQFlag != 0 && receiveEQFlag != 1) return fail(T41RX_ERR_ARG, "receiveEQFlag must be 0 or 1");
+  if (receiveEQFlag && ctx->params.fft_length != 512)
+    return fail(T41RX_ERR_UNSUPPORTED, "the receive equalizer is built for fft_length 512");
+  if (receiveEQFlag && !ctx->eq_have_bands)
+    return fail(T41RX_ERR_ARG, "receive equalizer: no band table loaded (t41rx_set_receive_eq_bands)");
+  if (equalizerRec) std::memcpy(ctx->eq_levels, equalizerRec, sizeof(ctx->eq_levels));
+  ctx->eq_on = receiveEQFlag;
+  return T41RX_OK;
+}
+
+int t41rx_get_receive_eq(const t41rx_ctx *ctx, int32_t *equalizerRec_out) {
+  if (!ctx) return T41RX_ERR_ARG;
+  if (equalizerRec_out) std::memcpy(equalizerRec_out, ctx->eq_levels, sizeof(ctx->eq_levels));
+  return ctx->eq_on;
+}
+
 int t41rx_n_channels(const t41rx_ctx *ctx) { return ctx ? ctx->nchan : T41RX_ERR_ARG; }
 int t41rx_frame_len(const t41rx_ctx *ctx) { return ctx ? 4 * ctx->params.fft_length : T41RX_ERR_ARG; }
 
@@ -622,7 +675,13 @@ int process_device_impl(t41rx_ctx *ctx, const float *dI, const float *dQ, float 
     const int rc = ensure_nb(ctx);
     if (rc != T41RX_OK) return rc;
   }
-  const bool stages_on = nr_on || nb_on;  // the fused kernel stops behind the demodulator; stage kernels; back kernel
+  const bool eq_on = ctx->eq_on != 0;  // (fft_length 512: t41rx_set_receive_eq)
+  if (eq_on) {
+    const int rc = ensure_eq(ctx);
+    if (rc != T41RX_OK) return rc;
+  }
+  // the fused kernel stops behind the demodulator; stage kernels; back kernel
+  const bool stages_on = eq_on || nr_on || nb_on;
   if ((seg > 1 || stages_on) && n_frames > ctx->scratch_frames) {
     // scratch between the kernels of the long-FFT pipeline / the noise-reduction pipeline (grown on demand, kept)
     HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
@@ -718,8 +777,25 @@ int process_device_impl(t41rx_ctx *ctx, const float *dI, const float *dQ, float 
   if (stages_on) a.aud_out = ctx->d_aud24;  // the fused kernel stops behind the demodulator
   hipError_t e = launch_rx(a, ctx->params.fft_length, ctx->params.mode, (hipStream_t)hip_stream);
   if (e != hipSuccess) return hip_fail(e, "kernel launch");
+  if (eq_on) {
+    // Process.cpp:828-832 on the call's audio @24 kS/s
+    EqArgs q{};
+    q.aud = ctx->d_aud24;
+    q.state = ctx->d_eq;
+    q.nchan = ctx->nchan;
+    q.nsamp = n_frames * 256;
+    std::memcpy(q.coef, ctx->eq_coef, sizeof(q.coef));
+    for (int b = 0; b < kEqBands; ++b) {
+      // recEQ_LevelScale[b] = (float)EEPROMData.equalizerRec[b] / 100.0 (Filter.cpp:119-121); arm_scale_f32 by its
+      // negative for bands 1, 3, .., 13 (Filter.cpp:138-151)
+      const float lvl = (float)((double)(float)ctx->eq_levels[b] / 100.0);
+      q.scale[b] = (b % 2 == 0) ? -lvl : lvl;
+    }
+    e = launch_eq(q, (hipStream_t)hip_stream);
+    if (e != hipSuccess) return hip_fail(e, "receive-equalizer kernel launch");
+  }
   if (nr_on) {
-    // Process.cpp:841-866 on the call's audio @24 kS/s
+    // Process.cpp:841-866 behind it
     NrArgs n{};
     n.aud = ctx->d_aud24;
     n.anr = ctx->d_nr_anr;
@@ -844,12 +920,16 @@ constexpr size_t kStateHeaderBytes = 32;
 //          t41rx_set_display_spectrum is on; header word 6 = its spectrumZoom
 //   bit 2  noise blanker: last_frame_end[0 .. 12] (DSP_Fn.cpp:143), [n_channels][kNbCarryPitch] (3 floats of
 //          padding) -- present once the blanker has run
-constexpr int32_t kSecNr = 1, kSecDisp = 2, kSecNb = 4;
+//   bit 3  receive equalizer: rec_EQ_Band1_state .. rec_EQ_Band14_state (Filter.cpp:43-56), [n_channels][kEqStateFloats]
+//          -- present once the equalizer has run
+constexpr int32_t kSecNr = 1, kSecDisp = 2, kSecNb = 4, kSecEq = 8;
 static size_t nr_section_bytes(int nchan) { return sizeof(float) * ((size_t)kAnrStRows + (size_t)kNrSpecFloats) * (size_t)nchan; }
 static size_t disp_section_bytes(int nchan) { return sizeof(float) * (size_t)kDispFloats * (size_t)nchan; }
 static size_t nb_section_bytes(int nchan) { return sizeof(float) * (size_t)kNbCarryPitch * (size_t)nchan; }
+static size_t eq_section_bytes(int nchan) { return sizeof(float) * (size_t)kEqStateFloats * (size_t)nchan; }
 static int32_t state_sections(const t41rx_ctx *ctx) {
-  return (ctx->d_nr_anr ? kSecNr : 0) | ((ctx->disp_spec && ctx->d_disp) ? kSecDisp : 0) | (ctx->d_nb ? kSecNb : 0);
+  return (ctx->d_nr_anr ? kSecNr : 0) | ((ctx->disp_spec && ctx->d_disp) ? kSecDisp : 0) | (ctx->d_nb ? kSecNb : 0) |
+         (ctx->d_eq ? kSecEq : 0);
 }
 
 size_t t41rx_state_bytes(const t41rx_ctx *ctx) {
@@ -857,7 +937,7 @@ size_t t41rx_state_bytes(const t41rx_ctx *ctx) {
   const int32_t sec = state_sections(ctx);
   return kStateHeaderBytes + sizeof(float) * state_floats(ctx->params.fft_length) * (size_t)ctx->nchan +
          ((sec & kSecNr) ? nr_section_bytes(ctx->nchan) : 0) + ((sec & kSecDisp) ? disp_section_bytes(ctx->nchan) : 0) +
-         ((sec & kSecNb) ? nb_section_bytes(ctx->nchan) : 0);
+         ((sec & kSecNb) ? nb_section_bytes(ctx->nchan) : 0) + ((sec & kSecEq) ? eq_section_bytes(ctx->nchan) : 0);
 }
 
 // the pipelined kernels count a wait that ran out (rx_kernels.hip: pipe_wait_ge) behind their slots: a broken hand-over
@@ -920,9 +1000,12 @@ int t41rx_get_state(t41rx_ctx *ctx, void *host_buf, size_t bytes) {
     HIP_TRY(hipMemcpy(out, ctx->d_disp, disp_section_bytes(ctx->nchan), hipMemcpyDeviceToHost));
     out += disp_section_bytes(ctx->nchan);
   }
-  if (sec & kSecNb)  // the current slot
+  if (sec & kSecNb) {  // the current slot
     HIP_TRY(hipMemcpy(out, ctx->d_nb + (size_t)ctx->nb_sel * kNbCarryPitch * (size_t)ctx->nchan, nb_section_bytes(ctx->nchan),
                       hipMemcpyDeviceToHost));
+    out += nb_section_bytes(ctx->nchan);
+  }
+  if (sec & kSecEq) HIP_TRY(hipMemcpy(out, ctx->d_eq, eq_section_bytes(ctx->nchan), hipMemcpyDeviceToHost));
   return T41RX_OK;
 }
 
@@ -936,13 +1019,15 @@ int t41rx_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes) {
       hdr[3] != ctx->nchan || hdr[4] != (int32_t)sf)
     return fail(T41RX_ERR_STATE, "checkpoint header does not match this context (magic / abi / fft_length / channels)");
   const int32_t sec = hdr[5];
-  if (sec & ~(kSecNr | kSecDisp | kSecNb)) return fail(T41RX_ERR_STATE, "checkpoint: unknown sections");
+  if (sec & ~(kSecNr | kSecDisp | kSecNb | kSecEq)) return fail(T41RX_ERR_STATE, "checkpoint: unknown sections");
   const size_t path_bytes = sizeof(float) * sf * (size_t)ctx->nchan;
   if (bytes != kStateHeaderBytes + path_bytes + ((sec & kSecNr) ? nr_section_bytes(ctx->nchan) : 0) +
-                   ((sec & kSecDisp) ? disp_section_bytes(ctx->nchan) : 0) + ((sec & kSecNb) ? nb_section_bytes(ctx->nchan) : 0))
+                   ((sec & kSecDisp) ? disp_section_bytes(ctx->nchan) : 0) + ((sec & kSecNb) ? nb_section_bytes(ctx->nchan) : 0) +
+                   ((sec & kSecEq) ? eq_section_bytes(ctx->nchan) : 0))
     return fail(T41RX_ERR_STATE, "state size mismatch");
   if ((sec & kSecNr) && ctx->params.fft_length != 512) return fail(T41RX_ERR_STATE, "checkpoint: noise-reduction section at a long fft_length");
   if ((sec & kSecNb) && ctx->params.fft_length != 512) return fail(T41RX_ERR_STATE, "checkpoint: noise-blanker section at a long fft_length");
+  if ((sec & kSecEq) && ctx->params.fft_length != 512) return fail(T41RX_ERR_STATE, "checkpoint: receive-equalizer section at a long fft_length");
   if (sec & kSecDisp) {
     if (!(ctx->disp_spec && ctx->d_disp)) return fail(T41RX_ERR_STATE, "checkpoint carries display-FFT state but the display spectrum is off here");
     if (hdr[6] != ctx->disp_zoom) return fail(T41RX_ERR_STATE, "checkpoint: display-FFT state of another spectrumZoom");
@@ -950,6 +1035,7 @@ int t41rx_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes) {
   const char *nr_sec = static_cast<const char *>(host_buf) + kStateHeaderBytes + path_bytes;
   const char *disp_sec = nr_sec + ((sec & kSecNr) ? nr_section_bytes(ctx->nchan) : 0);
   const char *nb_sec = disp_sec + ((sec & kSecDisp) ? disp_section_bytes(ctx->nchan) : 0);
+  const char *eq_sec = nb_sec + ((sec & kSecNb) ? nb_section_bytes(ctx->nchan) : 0);
   if (sec & kSecNr) {
     // what the kernels index with or divide by (nr_kernels.hip): Xanr()'s leak index, the spectral functions' ring pointers
     const float *anr = reinterpret_cast<const float *>(nr_sec);
@@ -1004,6 +1090,10 @@ int t41rx_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes) {
     const int rc = ensure_nb(ctx);
     if (rc != T41RX_OK) return rc;
   }
+  if (sec & kSecEq) {
+    const int rc = ensure_eq(ctx);
+    if (rc != T41RX_OK) return rc;
+  }
   HIP_TRY(hipMemcpy(ctx->d_state, rec, path_bytes, hipMemcpyHostToDevice));
   ctx->nco_sel = 0;  // (a checkpoint carries the current oscillator state in both slots)
   // The side stages' memories follow the checkpoint too: restored where it carries them, back to power-on where it
@@ -1027,6 +1117,11 @@ int t41rx_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes) {
   } else if (ctx->d_nb) {
     HIP_TRY(hipMemset(ctx->d_nb, 0, sizeof(float) * 2 * kNbCarryPitch * (size_t)ctx->nchan));  // the static's power-on zero
     ctx->nb_sel = 0;
+  }
+  if (sec & kSecEq) {
+    HIP_TRY(hipMemcpy(ctx->d_eq, eq_sec, eq_section_bytes(ctx->nchan), hipMemcpyHostToDevice));
+  } else if (ctx->d_eq) {
+    HIP_TRY(hipMemset(ctx->d_eq, 0, eq_section_bytes(ctx->nchan)));  // the biquad memories' power-on zero
   }
   return pipe_timeouts_clear(ctx);  // the restored state is valid again
 }

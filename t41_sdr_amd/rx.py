@@ -135,6 +135,37 @@ class RxChain:
             check(v)
         return v
 
+    def set_receive_eq_bands(self, coeffs):
+        """The receive equalizer's band table (t41rx_set_receive_eq_bands): the firmware's EQ_Band1Coeffs ..
+        EQ_Band14Coeffs as [14][4][5] or [14][20], {b0, b1, b2, a1, a2} per section with the a's negated.  Kept across
+        CalcFilters() / set_coeffs(); the filter memories are not reset."""
+        c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.float32))
+        if c.size != 14 * 4 * 5 or c.shape[0] != 14:
+            raise ValueError("receive-EQ band table must be [14][4][5] or [14][20], got %r" % (c.shape,))
+        check(self._lib.t41rx_set_receive_eq_bands(self._ctx, c.ctypes.data_as(C.c_void_p)))
+
+    def set_receive_eq(self, on, levels=None):
+        """receiveEQFlag and EEPROMData.equalizerRec (Process.cpp:828-832, Filter.cpp:117-165): the receive equalizer on
+        the demodulated audio, in front of the noise reduction, the notch and the noise blanker (t41rx_set_receive_eq;
+        0 / 1, fft_length 512, a band table loaded first).  levels: 14 ints, or None to keep the current ones (100 each
+        until set).  Kept across CalcFilters() / set_coeffs()."""
+        if levels is None:
+            check(self._lib.t41rx_set_receive_eq(self._ctx, int(on), None))
+            return
+        lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
+        if lv.shape != (14,):
+            raise ValueError("receive-EQ levels must be 14 ints, got %r" % (lv.shape,))
+        check(self._lib.t41rx_set_receive_eq(self._ctx, int(on), lv.ctypes.data_as(C.c_void_p)))
+
+    @property
+    def receive_eq(self):
+        """(on, levels): the receive equalizer's switch and its 14 levels"""
+        lv = np.zeros(14, np.int32)
+        v = self._lib.t41rx_get_receive_eq(self._ctx, lv.ctypes.data_as(C.c_void_p))
+        if v < 0:
+            check(v)
+        return v, lv
+
     def get_state(self):
         n = self._lib.t41rx_state_bytes(self._ctx)
         buf = np.zeros(n, dtype=np.uint8)
