@@ -34,14 +34,8 @@ constexpr int fc_lds_floats(int R) { return 2 * kFcRow * R + 2 * (448 + 56); }  
 // 4 KiB] and nothing else: the frame's audio, then the output transposition buffers and the x4
 // interpolator's boundary samples alias the working array (one more barrier), and what crosses the
 // frames (24 audio samples, 7 x2 outputs) waits in two registers of wave 0.
-#ifndef T41RX_FC_PRIO
-#define T41RX_FC_PRIO 1
-#endif
-#ifndef T41RX_FC_X2
-#define T41RX_FC_X2 1  // pass 2: the wave's two rows in lockstep
-#endif
-// (T41RX_FCABL: timing experiments with wrong results, rx_experiments.hpp)
 constexpr int kFcWaves = 4;
+constexpr int kFcWavesPerSimd = 4;  // waves per SIMD the register allocation is held to (four workgroups per CU)
 constexpr int fc_arr_floats(int R) { return 2 * kFcRow * R < kFcWaves * 2048 + 8 * (R + 1) ? kFcWaves * 2048 + 8 * (R + 1) : 2 * kFcRow * R; }  // >= four transposition buffers + YT
 constexpr int fcb_lds_floats(int R) { return fc_arr_floats(R) + 2 * (448 + 56); }
 static_assert(fcb_lds_floats(8) * 4 * 4 <= 160 * 1024, "four fused workgroups per CU");
@@ -67,16 +61,13 @@ __device__ __forceinline__ void dft_r(cf (&v)[R]) {
 // N = 512 R, R = 2, 4, 8 (FFT_LENGTH 1024, 2048, 4096).  CPLX: hand the complex valid half on as it
 // is (AM, AGC on: the back kernel applies the AGC / gain and demodulates), else the SSB audio
 // fixed_gain * Re.
-#ifndef T41RX_FC_WAVES
-#define T41RX_FC_WAVES 4  // waves per SIMD the register allocation is held to (four workgroups per CU)
-#endif
 // BACK: SSB / NFM audio with the fixed gain goes straight on through the x2 / x4 interpolators and
 // out (Process.cpp:917-931) instead of to the `aud24` scratch and a third kernel: pass 3 leaves
 // the frame's N/2 audio samples in LDS (where the working array was), then every wave runs whole
 // 256-sample segments of the back end (s = wave, wave + 4) with the arithmetic of rx512_kernel's,
 // the x4 interpolator's 7-sample history crossing the segment boundaries through LDS.
 template <int R, bool CPLX, bool BACK = false>
-__global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_kernel(const RxArgs a) {
+__global__ __launch_bounds__((64 * kFcWaves), kFcWavesPerSimd) void fastconv_kernel(const RxArgs a) {
   static_assert(!(BACK && CPLX), "the fused back end takes real audio");
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int N = 512 * R, D = N / 2;
@@ -138,14 +129,12 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_kern
 #pragma unroll
       for (int p = 0; p < R; ++p) {
         const int e = k + 512 * p;  // index into [previous | new]
-        if (T41RX_FCABL & 4) x1[h][p] = cf{1.0f + lane, (float)f};
-        else x1[h][p] = (p < R / 2) ? prev[e] : mid[e - D];
+        x1[h][p] = (p < R / 2) ? prev[e] : mid[e - D];
       }
     }
   };
   for (int f = 0; f < a.nframes4k; ++f) {
     FRESH_LANE();
-#if T41RX_FC_PRIO
     // issue priority falls with progress: the arbiter favours the oldest waves, so without it the
     // first workgroup of a CU finishes long before the last (108 .. 195 us, stamps), which then
     // runs alone -- and alone a workgroup is latency-bound
@@ -155,7 +144,6 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_kern
       case 2: PRIO(1); break;
       default: PRIO(0); break;
     }
-#endif
     // ---- overlap-save assemble (Process.cpp:498-522): [previous N/2 | new N/2].  Inside a call the
     // previous block is the preceding frame's `mid` (just read, L2-warm); the state record supplies
     // it for the call's first frame and receives the last frame's block.  Pass 1 takes its inputs
@@ -204,7 +192,7 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_kern
     STAMP(6);
     FRESH_LANE();
     // ---- pass 2: 512-point FFT, mask (pre-scaled by 1/N), inverse 512-point FFT, per q
-    if constexpr (R == 8 && H == 2 && T41RX_FC_X2) {  // both rows of the wave in lockstep
+    if constexpr (R == 8 && H == 2) {  // both rows of the wave in lockstep
       const int q0 = wv, q1 = wv + NWV;
       cf v[8], u[8];
 #pragma unroll
@@ -234,10 +222,10 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_kern
           for (int r = 0; r < 8; ++r) v[r] = A[kFcRow * q + lane + 64 * r];
           float *xbuf = smem + 2 * kFcRow * q;  // the row itself (now in registers) is the exchange scratch
           wave_sync();
-          if (!(T41RX_FCABL & 2)) fft512_ldstw<false>(v, ltw + lane, ltw + 448 + (lane & 7), xbuf, lane, []() {});
+          fft512_ldstw<false>(v, ltw + lane, ltw + 448 + (lane & 7), xbuf, lane, []() {});
 #pragma unroll
           for (int r = 0; r < 8; ++r) v[r] = cmul(v[r], mk[h][r]);
-          if (!(T41RX_FCABL & 2)) fft512_ldstw<true>(v, ltw + lane, ltw + 448 + (lane & 7), xbuf, lane, []() {});
+          fft512_ldstw<true>(v, ltw + lane, ltw + 448 + (lane & 7), xbuf, lane, []() {});
           wave_sync();
 #pragma unroll
           for (int r = 0; r < 8; ++r) A[kFcRow * q + lane + 64 * r] = v[r];
@@ -312,7 +300,7 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_kern
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
 #pragma unroll
-              for (int t = 0; t < ((T41RX_FCABL & 16) ? 1 : 8); ++t) u1[h][u] = pk_fma(splat(w[u + b + t + 1]), f2{ci[2 * b + 1 + 2 * t], ci[2 * b + 2 * t]}, u1[h][u]);
+              for (int t = 0; t < 8; ++t) u1[h][u] = pk_fma(splat(w[u + b + t + 1]), f2{ci[2 * b + 1 + 2 * t], ci[2 * b + 2 * t]}, u1[h][u]);
             }
           }
           if (lane == 63) {  // what the next segment's x4 interpolator remembers
@@ -354,7 +342,7 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_kern
           for (int u = 0; u < 8; ++u) {
             f2 o01 = splat(0.0f), o23 = splat(0.0f);
 #pragma unroll
-            for (int t = 0; t < ((T41RX_FCABL & 8) ? 1 : 8); ++t) {
+            for (int t = 0; t < 8; ++t) {
               const f2 x = splat(w[u + t]);
               o01 = pk_fma(x, f2{c4[4 * t + 3], c4[4 * t + 2]}, o01);
               o23 = pk_fma(x, f2{c4[4 * t + 1], c4[4 * t]}, o23);
@@ -368,7 +356,7 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_kern
           for (int i = 0; i < 8; ++i) {  // float4 F = 64 i + lane: row F >> 3 = the source lane, column lane & 7
             const int row = 8 * i + (lane >> 3);
             const float4 t = lds4(tr + 4 * (8 * row + ((lane & 7) ^ (row & 7))));
-            if (!(T41RX_FCABL & 1) || t.x == 123.456f) stg_stream(gO + 256 * i, lof, t);
+            stg_stream(gO + 256 * i, lof, t);
           }
         }
       }
@@ -408,36 +396,19 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_kern
 // in 16 registers per lane in exactly the layout pass 1 wants.  From pass 1 on: fastconv_kernel<8,
 // false, true>.  HBM sees the frame once in and once out.
 // ------------------------------------------------------------------------------------------
-#ifndef T41RX_FF_X2
-#define T41RX_FF_X2 1  // pass 2: the wave's two rows in lockstep (costs registers)
-#endif
 // Register budget: four workgroups per CU hold the kernel to 128 registers.  Measured on MI355X (1024 channels x 32
 // frames, us per frame; two-kernel pipeline 57.6): two input sub-blocks in flight + the previous block in registers
 // 56.4 (42 registers spilled), two in flight + the previous block in the record 56.4 (13 spilled), ONE in flight + the
 // record 54.2 (none spilled); three workgroups per CU (168 registers, nothing spilled, 768 channel slots) 60.6.
-#ifndef T41RX_FF_PF
-#define T41RX_FF_PF 1  // input sub-blocks in flight ahead of the one being worked on (1: one register set, 2: two)
-#endif
 // Round 5: with the tap pointers laundered at their base and the wave-index offsets re-derived per phase (FRESH_WV) the
 // kernel spills 40 SGPRs instead of 85, and the balance tips: the previous block IN REGISTERS (12 VGPRs spilled, 36 B of
 // scratch per lane that stay in L2) measures 51.4-51.6 against 53.1-53.3 us per frame interleaved on one box, and the fabric
 // traffic falls from 1.153 to 1.077 x the algorithmic bytes (the 16 KiB round trip through the record is gone):
 // profiles/r05_ab_prevreg.txt.  (Round 3, 85 spilled SGPRs, two sub-blocks in flight: 56.4 against 54.2 the other way.)
-// T41RX_FF_REGTAIL=1: the /4 decimator's window tail from registers here too (rx512_kernel.hpp; measured: 49.78 against
-// 49.68 us per frame and one more spilled register, HBM traffic 1.075 -> 1.082 x: off)
-#ifndef T41RX_FF_REGTAIL
-#define T41RX_FF_REGTAIL 0
-#endif
-#ifndef T41RX_FF_PREV_GLOBAL
-#define T41RX_FF_PREV_GLOBAL 0  // 1: the "previous" block waits in the channel's record (L2) instead of 16 registers per lane
-#endif
-typedef float f2n __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ cf ldg_stream2(const cf *p) {  // 8-byte load that does not look at this CU's L1
-  const f2n t = __builtin_nontemporal_load(reinterpret_cast<const f2n *>(p));
-  return cf{t.x, t.y};
-}
+// (Round 5, measured and left off: the /4 decimator's window tail from registers here too, as in rx512_kernel.hpp: 49.78
+// against 49.68 us per frame and one more spilled register, HBM traffic 1.075 -> 1.082 x.)
 template <bool PLAIN>
-__global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fused_kernel(const RxArgs a) {
+__global__ __launch_bounds__((64 * kFcWaves), kFcWavesPerSimd) void fastconv_fused_kernel(const RxArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int R = 8, N = 512 * R, D = N / 2, L = 2048;
   constexpr int NWV = kFcWaves, H = 8 / NWV;
@@ -493,17 +464,13 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fuse
   const float g_hp = g_rf * (float)kHpB0;
   const float g_hp_i = (PLAIN && a.iq_corr_on) ? -g_hp : g_hp;
 
-  // the overlap-save "previous" block in pass 1's layout: element k + 512 p, p < 4, k = lane + 64 (wv + 4 h)
-  // (T41RX_FF_PREV_GLOBAL: it waits in the channel's record instead -- every lane re-reads next frame exactly the
-  // elements it wrote itself, 16 KiB per channel that stay in L2 -- which keeps 16 registers free through the front end)
+  // the overlap-save "previous" block in pass 1's layout, in registers: element k + 512 p, p < 4, k = lane + 64 (wv + 4 h)
   cf prevx[H][R / 2];
-  if (!T41RX_FF_PREV_GLOBAL) {
 #pragma unroll
-    for (int h = 0; h < H; ++h)
+  for (int h = 0; h < H; ++h)
 #pragma unroll
-      for (int p = 0; p < R / 2; ++p)
-        prevx[h][p] = reinterpret_cast<const cf *>(st + kStOverlap)[lane + 64 * (wv + NWV * h) + 512 * p];
-  }
+    for (int p = 0; p < R / 2; ++p)
+      prevx[h][p] = reinterpret_cast<const cf *>(st + kStOverlap)[lane + 64 * (wv + NWV * h) + 512 * p];
   cf twp[H][R - 1];
   auto load_twp = [&]() {
     // (two scalar bases, one per h, and R - 1 lane offsets shared by both: a base per entry runs the kernel out of SGPRs)
@@ -520,14 +487,12 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fuse
 
   for (int f = 0; f < a.nframes4k; ++f) {
     FRESH_LANE(); FRESH_WV(wv);
-#if T41RX_FC_PRIO
     switch ((4 * f) / a.nframes4k) {
       case 0: PRIO(3); break;
       case 1: PRIO(2); break;
       case 2: PRIO(1); break;
       default: PRIO(0); break;
     }
-#endif
     __syncthreads();  // the previous frame's back end is done with the working array (first frame: the twiddles are staged)
     // =========================== front end: segments 2 wv, 2 wv + 1 of this frame ===========================
     cf ynew[2][2][2];  // [segment][round][even / odd]: /8 outputs m = 128 round + 2 lane + e of the segment
@@ -572,15 +537,16 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fuse
           z[k] = cmulc(z[k], osc);
         }
       };
-      // input registers, two sub-blocks in flight
+      // input registers: one sub-block in flight ahead of the one being worked on (see the register budget above).
+      // (Element 0 only: the arrays keep the size of the measured two-in-flight form; with plain float4s hipcc schedules
+      // the kernel slightly differently, and this form's machine code is the one that was measured.)
       float4 pI0[2], pI1[2], pQ0[2], pQ1[2];
-      auto request = [&](int set, const float *pi, const float *pq) {
-        if (T41RX_FF_PF < 2) set = 0;
+      auto request = [&](const float *pi, const float *pq) {
         const LaneOff lof = fresh_off(8 * lane);
-        pI0[set] = ldg_stream(pi, lof);
-        pI1[set] = ldg_stream(pi, lof, 4);
-        pQ0[set] = ldg_stream(pq, lof);
-        pQ1[set] = ldg_stream(pq, lof, 4);
+        pI0[0] = ldg_stream(pi, lof);
+        pI1[0] = ldg_stream(pi, lof, 4);
+        pQ0[0] = ldg_stream(pq, lof);
+        pQ1[0] = ldg_stream(pq, lof, 4);
       };
       float dc_carry = 0.0f;
       if (wv == 0) {
@@ -589,13 +555,12 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fuse
         // in the `mid` scratch, alternating, so that wave 3 of THIS frame never writes what this wave still reads;
         // its stores were drained before the barrier above, and these loads do not look at this CU's L1)
         const float *src = (f == 0) ? st : a.mid + ((size_t)ch * 2 + ((f - 1) & 1)) * 256;
-        request(0, gI, gQ);
+        request(gI, gQ);
         float4 h1 = any_float4(), h2 = any_float4();
         const LaneOff lo4 = fresh_off(4 * lane);
         if (lane < 14) h1 = ldg_stream(src + kStDec1, lo4);
         if (lane < 24) h2 = ldg_stream(src + kStDec2, lo4);
         const float4 dcs = ldg_stream(src + kStMisc);  // (kMiscDc first)
-        if (T41RX_FF_PF >= 2) request(1, gI + 512, gQ + 512);
         wave_sync();
         if (lane < 14) *reinterpret_cast<float4 *>(lds + kX + 2 * xpad(2 * lane)) = h1;
         if (lane < 24) *reinterpret_cast<float4 *>(lds + kY1 + y1slot(lane)) = h2;
@@ -603,12 +568,10 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fuse
         dc_carry = uniform_f32(dcs.x);
       } else {
         // pre-roll: the 512 samples in front of the run through DC high-pass, mixer and /4 decimator
-        request(1, gI - 512, gQ - 512);
-        if (T41RX_FF_PF >= 2) request(0, gI, gQ);
+        request(gI - 512, gQ - 512);
         cf z[8];
-        stage_sub(pI0[T41RX_FF_PF >= 2 ? 1 : 0], pI1[T41RX_FF_PF >= 2 ? 1 : 0], pQ0[T41RX_FF_PF >= 2 ? 1 : 0], pQ1[T41RX_FF_PF >= 2 ? 1 : 0], z);
-        if (T41RX_FF_PF >= 2) request(1, gI + 512, gQ + 512);
-        else request(0, gI, gQ);
+        stage_sub(pI0[0], pI1[0], pQ0[0], pQ1[0], z);
+        request(gI, gQ);
         f2 dcs = splat(0.0f);
         dc_highpass<8>(z, dcs, lane, hp8.x, hp8.y);  // from rest: 512 samples on, its memory of the start is a1^512
         iq_corr(z);
@@ -648,11 +611,7 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fuse
           const uint64_t Pl = (uint64_t)(unsigned)(8 * lane + 1) * dphi;
 #pragma unroll
           for (int sb = 0; sb < 4; ++sb) {
-#if T41RX_PHASE_SPLIT
             osc_p[sb] = (phase0 + (uint64_t)(512 * sb) * dphi) + Pl;
-#else
-            osc_p[sb] = phase0 + (uint64_t)(512 * sb + 8 * lane + 1) * dphi;
-#endif
             osc_tab[sb] = ldg2(tab + kTabSinCos, (unsigned)(osc_p[sb] >> 56));
           }
         }
@@ -662,16 +621,11 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fuse
           for (int hh2 = 0; hh2 < 2; ++hh2) {
             const int sb = 2 * rd + hh2;
             cf z[8];
-            stage_sub(pI0[T41RX_FF_PF >= 2 ? hh2 : 0], pI1[T41RX_FF_PF >= 2 ? hh2 : 0], pQ0[T41RX_FF_PF >= 2 ? hh2 : 0], pQ1[T41RX_FF_PF >= 2 ? hh2 : 0], z);
-            // the sub-block after next / the next one (this segment's, or the run's second segment's)
-            if (T41RX_FF_PF >= 2) {
-              if (!(sg == 1 && sb >= 2)) request(hh2, gI + L * sg + 512 * (sb + 2), gQ + L * sg + 512 * (sb + 2));
-            } else if (!(sg == 1 && sb == 3)) {
-              request(0, gI + L * sg + 512 * (sb + 1), gQ + L * sg + 512 * (sb + 1));
-            }
+            stage_sub(pI0[0], pI1[0], pQ0[0], pQ1[0], z);
+            // the next sub-block (this segment's, or the run's second segment's)
+            if (!(sg == 1 && sb == 3)) request(gI + L * sg + 512 * (sb + 1), gQ + L * sg + 512 * (sb + 1));
             dc_highpass<8>(z, dc2, lane, hp8.x, hp8.y);
             iq_corr(z);
-            const int n0 = 512 * sb + 8 * lane;
             if (transient) {  // start-up of the oscillator's amplitude loop (Freq_Shift.cpp:130-134), first samples after a reset
               const NcoPtr nt = fresh_nco(nco);
               const double r_star_sq = uniform_f64(nt->r_star_sq);
@@ -694,11 +648,7 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fuse
 #pragma unroll
               for (int k = 0; k < 8; ++k) z[k] *= splat(amp[k]);
             }
-#if T41RX_PHASE_SPLIT
             mix(z, osc_p[sb], osc_tab[sb]);
-#else
-            mix(z, phase0 + (uint64_t)(n0 + 1) * dphi, osc_tab[sb]);
-#endif
             wave_sync();
             float *xw = lds + kX + 20 * lane;
 #pragma unroll
@@ -708,8 +658,7 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fuse
             cf o1[2];
             {
               auto pidx = [](int o) { return xpad(o); };
-              if (T41RX_DEC1_REGTAIL && T41RX_FF_REGTAIL) fir_pair<kDec1Taps, 1, 5, 18, 6, 14>(xw, pidx, cf0, kCoDec1, o1[0], o1[1], nullptr, z);  // (rx512_kernel.hpp)
-              else fir_pair<kDec1Taps, 1, 5, 18, 6>(xw, pidx, cf0, kCoDec1, o1[0], o1[1]);
+              fir_pair<kDec1Taps, 1, 5, 18, 6>(xw, pidx, cf0, kCoDec1, o1[0], o1[1]);
             }
             {
               float4 hh = any_float4();
@@ -761,7 +710,7 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fuse
         const int k = lane + 64 * (wv + NWV * h);
 #pragma unroll
         for (int p = 0; p < R / 2; ++p) {
-          x1[h][p] = T41RX_FF_PREV_GLOBAL ? ldg_stream2(reinterpret_cast<const cf *>(st + kStOverlap) + k + 512 * p) : prevx[h][p];
+          x1[h][p] = prevx[h][p];
           x1[h][R / 2 + p] = Nb[k + 512 * p];
         }
       }
@@ -777,7 +726,7 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fuse
         for (int p = 0; p < R; ++p) v[p] = x1[h][p];
 #pragma unroll
         for (int p = 0; p < R / 2; ++p) prevx[h][p] = x1[h][R / 2 + p];  // next frame's "previous"
-        if (T41RX_FF_PREV_GLOBAL || f == a.nframes4k - 1) {
+        if (f == a.nframes4k - 1) {
 #pragma unroll
           for (int p = R / 2; p < R; ++p) reinterpret_cast<cf *>(st + kStOverlap)[k + 512 * p - D] = v[p];
         }
@@ -798,8 +747,8 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fuse
     }
     __syncthreads();
     FRESH_LANE(); FRESH_WV(wv);
-    // ---- pass 2
-    if (T41RX_FF_X2) {
+    // ---- pass 2: the wave's two rows in lockstep
+    {
       const int q0 = wv, q1 = wv + NWV;
       cf v[8], u[8];
 #pragma unroll
@@ -819,23 +768,6 @@ __global__ __launch_bounds__((64 * kFcWaves), T41RX_FC_WAVES) void fastconv_fuse
       for (int r = 0; r < 8; ++r) A[kFcRow * q0 + lane + 64 * r] = v[r];
 #pragma unroll
       for (int r = 0; r < 8; ++r) A[kFcRow * q1 + lane + 64 * r] = u[r];
-    } else {
-#pragma unroll
-      for (int h = 0; h < H; ++h) {
-        const int q = wv + NWV * h;
-        cf v[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = A[kFcRow * q + lane + 64 * r];
-        float *xbuf = smem + 2 * kFcRow * q;
-        wave_sync();
-        fft512_ldstw<false>(v, ltw + lane, ltw + 448 + (lane & 7), xbuf, lane, []() {});
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = cmul(v[r], mk[h][r]);
-        fft512_ldstw<true>(v, ltw + lane, ltw + 448 + (lane & 7), xbuf, lane, []() {});
-        wave_sync();
-#pragma unroll
-        for (int r = 0; r < 8; ++r) A[kFcRow * q + lane + 64 * r] = v[r];
-      }
     }
     load_twp();
     __syncthreads();

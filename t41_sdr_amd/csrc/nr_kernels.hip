@@ -33,15 +33,6 @@
 
 namespace t41 {
 
-// T41RX_ANR_PREFETCH=0: the notch's window requested at the top of its own sample step, as in round 4 (A/B builds)
-#ifndef T41RX_ANR_PREFETCH
-#define T41RX_ANR_PREFETCH 1
-#endif
-// T41RX_NRSPEC_LDS_LOOP=1: the spectral function's bin loop as round 4 ran it, gains in LDS (A/B builds)
-#ifndef T41RX_NRSPEC_LDS_LOOP
-#define T41RX_NRSPEC_LDS_LOOP 0
-#endif
-
 // ------------------------------------------------------------------------------------------
 // Xanr(): 16 channels per wave, a channel's 64 taps on the four lanes (c, c + 16, c + 32, c + 48)
 // ------------------------------------------------------------------------------------------
@@ -108,7 +99,7 @@ __device__ __forceinline__ float anr_chain(const f2 (&p)[8]) {
 // alone (an IEEE double division), wave 0 the filter output, the error, the leak logic and the taps' update; sigma
 // crosses through LDS (two slots: wave 1 may be a sample ahead) behind ONE workgroup barrier per sample.  Every value
 // by the same operations in the same order as the scalar loop.
-// O (may be null): output tile; SIG: [2][16] float4.
+// O (may be null): output tile; SIG: [3][16] float4.
 template <bool NOTCH>
 __device__ __forceinline__ void anr_pass_y(const float *T, float *O, const float *SIG, f2 (&w)[8], float &lidx, float &ngamma, int lane) {
 #pragma clang fp contract(off)
@@ -119,7 +110,6 @@ __device__ __forceinline__ void anr_pass_y(const float *T, float *O, const float
   // holds): tap pair t is updated, then used.  Same values as updating all taps first.
   float c0 = 1.0f, c1 = 0.0f;  // pending update of the previous sample (none yet: w * 1 + 0 * d would not be exact for
   bool pending = false;        // -0 / NaN taps, so it is skipped rather than applied)
-#if T41RX_ANR_PREFETCH
   // Round 5: a sample's window is requested at the top of the PREVIOUS sample's step, into a third register set -- the
   // delay line is the input signal, so every window of the frame is in the tile before the pass starts.  Requested at
   // the top of its own step, as in round 4, the window is waited for twice per sample (two batches of eight reads) at the
@@ -191,55 +181,6 @@ __device__ __forceinline__ void anr_pass_y(const float *T, float *O, const float
   step(255, 0, da, dc, db, din_a, din_b);  // (255 = 3 x 85)
 #pragma unroll
   for (int t = 0; t < 8; ++t) db[t] = da[t];  // the last sample's update below takes its window from db
-#else
-  auto step = [&](int i, f2 (&dj)[8], const f2 (&dp)[8]) {
-    const float *row = T + i * kAnrRow + c;
-    const float d_in = row[kAnrHist * kAnrRow];  // ANR_d[ANR_in_idx]
-    // A register pair holds taps (j + 1, j) in (.x, .y): the window's rows ascend in time, i.e. descend in j, so one
-    // ds_read2_b32 fills a pair without a move.  (idx = in_idx + j + ANR_delay: the sample written j + 16 steps ago)
-#pragma unroll
-    for (int t = 0; t < 16; t += 2)
-      dj[t / 2] = f2{row[(kAnrTaps - 2 - tb - t) * kAnrRow], row[(kAnrTaps - 1 - tb - t) * kAnrRow]};
-    // (two taps per multiply instruction -- v_pk_mul_f32 rounds each product exactly like the scalar multiply)
-    f2 p[8];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      if (pending) w[t] = splat(c0) * w[t] + splat(c1) * dp[t];
-      p[t] = w[t] * dj[t];
-    }
-    const float y = anr_from_group2(anr_chain(p));
-    __syncthreads();  // wave 1's sigma of this sample is in its slot, with what depends on sigma alone
-    const float4 sg = *reinterpret_cast<const float4 *>(SIG + 4 * (kAnrCw * (i & 1) + c));
-    const float sigma = sg.x, inv_sigp = sg.y;  // inv_sigp = (float)(1.0 / ((double)sigma + 1e-10))
-    const double one_m = __hiloint2double(__float_as_int(sg.w), __float_as_int(sg.z));  // 1.0 - (double)(ANR_two_mu * sigma * inv_sigp)
-    const float error = d_in - y;
-    if (O && g == 0) O[i * kAnrRow + c] = NOTCH ? error : y;
-    float nel = (float)((double)error * one_m);
-    if (nel < 0.0f) nel = -nel;
-    float nev = (float)((double)d_in - (1.0 - (double)(ANR_two_mu * ngamma)) * (double)y - (double)(ANR_two_mu * error * sigma * inv_sigp));
-    if (nev < 0.0f) nev = -nev;
-    if (nev < nel) {  // as written (Noise.cpp:351-356): the else-if belongs to the inner if
-      lidx += ANR_lincr;
-      if (lidx > ANR_lidx_max) {
-        lidx = ANR_lidx_max;
-      } else {
-        lidx -= ANR_ldecr;
-        if (lidx < ANR_lidx_min) lidx = ANR_lidx_min;
-      }
-    }
-    ngamma = ANR_gamma * (lidx * lidx) * (lidx * lidx) * ANR_den_mult;
-    c0 = (float)(1.0 - (double)(ANR_two_mu * ngamma));
-    c1 = ANR_two_mu * error * inv_sigp;
-    pending = true;
-  };
-  f2 da[8], db[8];
-#pragma unroll
-  for (int t = 0; t < 8; ++t) db[t] = splat(0.0f);
-  for (int i = 0; i < 256; i += 2) {
-    step(i, da, db);
-    step(i + 1, db, da);
-  }
-#endif
   // the last sample's update (its window is in db)
 #pragma unroll
   for (int t = 0; t < 8; ++t) w[t] = splat(c0) * w[t] + splat(c1) * db[t];
@@ -260,10 +201,9 @@ __device__ __forceinline__ void anr_pass_sigma(const float *T, float *SIG, int l
     const float inv_sigp = (float)(1.0 / ((double)sigma + 1e-10));
     const double one_m = 1.0 - (double)(ANR_two_mu * sigma * inv_sigp);
     if (g == 2)
-      *reinterpret_cast<float4 *>(SIG + 4 * (kAnrCw * (T41RX_ANR_PREFETCH ? i % 3 : (i & 1)) + c)) =
+      *reinterpret_cast<float4 *>(SIG + 4 * (kAnrCw * (i % 3) + c)) =
           make_float4(sigma, inv_sigp, __int_as_float(__double2loint(one_m)), __int_as_float(__double2hiint(one_m)));
   };
-#if T41RX_ANR_PREFETCH
   // one sample AHEAD of the filter wave: sigma of sample i is in its slot before the barrier of sample i - 1, so the filter
   // wave reads it at the top of its step, not behind its chain (the slot it overwrites, i + 1's = i - 1's, was read at the
   // top of step i - 1, a barrier ago)
@@ -273,12 +213,6 @@ __device__ __forceinline__ void anr_pass_sigma(const float *T, float *SIG, int l
     if (i + 1 < 256) sigma_of(i + 1);
     __syncthreads();
   }
-#else
-  for (int i = 0; i < 256; ++i) {
-    sigma_of(i);
-    __syncthreads();
-  }
-#endif
 }
 
 __global__ __launch_bounds__(128, 2) void anr_kernel(const NrArgs a) {
@@ -635,77 +569,6 @@ __global__ __launch_bounds__(64) void nrspec_kernel(const NrArgs a) {
             if (i >= lo && i < hi) pre_part += X[k2][r];
           }
           const float pre_power = wave_sum(pre_part);
-#if T41RX_NRSPEC_LDS_LOOP
-          for (int i = lo; i < hi; ++i) {  // Noise.cpp:529-588: the musical-noise treatment runs inside this loop
-            if (lane == (i & 63)) {
-              Gst[i] = (i >> 6) ? gnew[1] : gnew[0];
-              Hk[i] = (i >> 6) ? hknew[1] : hknew[0];
-            }
-            __syncthreads();
-            float post_part = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-              const int j = lane + 64 * r;
-              if (j >= lo && j < hi) post_part += Gst[j] * Gst[j] * X[k2][r];
-            }
-            const float post_power = wave_sum(post_part);
-            float power_ratio = post_power / pre_power;
-            {
-              bool near_edge = false;
-#pragma unroll
-              for (float b : {0.4f, 0.35f, 0.25f, 0.15f, 0.05f}) near_edge = near_edge || fabsf(power_ratio - b) < 4e-5f;
-              if (near_edge) {
-                float *Pw = U + 640;  // (free between the transforms: the spectra occupy U[0 .. 520))
-                __syncthreads();
-#pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                  const int j = lane + 64 * r;
-                  Pw[j] = X[k2][r];
-                  Pw[128 + j] = Gst[j] * Gst[j] * X[k2][r];
-                }
-                __syncthreads();
-                float pre_seq = 0.0f, post_seq = 0.0f;
-                for (int j = lo; j < hi; ++j) {
-                  pre_seq += Pw[j];
-                  post_seq += Pw[128 + j];
-                }
-                power_ratio = post_seq / pre_seq;
-                __syncthreads();
-              }
-            }
-            int NN;
-            if (power_ratio > power_threshold) {
-              power_ratio = 1.0;
-              NN = 1;
-            } else {
-              NN = 1 + 2 * (int)(0.5 + (double)NR_width * (1.0 - (double)(power_ratio / power_threshold)));
-            }
-            if (NN > 1) {
-              const int h = NN / 2;
-              float nv[2] = {0.0f, 0.0f};
-              bool mine[2] = {false, false};
-#pragma unroll
-              for (int r = 0; r < 2; ++r) {
-                const int j = lane + 64 * r;
-                if (j >= lo + h && j < hi - h) {
-                  mine[r] = true;
-                  float s = 0.0;
-                  if (j >= hi - NN) {
-                    for (int m = j; m > j - NN; --m) s += Gst[m];
-                  } else {
-                    for (int m = j - h; m <= j + h; ++m) s += Gst[m];
-                  }
-                  nv[r] = s / (float)NN;
-                }
-              }
-              __syncthreads();
-#pragma unroll
-              for (int r = 0; r < 2; ++r)
-                if (mine[r]) Gst[lane + 64 * r] = nv[r];
-            }
-            __syncthreads();
-          }
-#else
           // Round 5.  The loop is serial by construction (every pass sees the gains the previous pass's smoothing left)
           // and the four waves of a SIMD keep its VALU busy: what a pass costs is its VALU instructions.  Round 4 kept
           // the gains in LDS and spent ~140 of them per pass; this form spends ~40:
@@ -837,7 +700,6 @@ __global__ __launch_bounds__(64) void nrspec_kernel(const NrArgs a) {
             if (i >= lo && i < hi) Hk[i] = hknew[r];
           }
           __syncthreads();
-#endif
 #pragma unroll
           for (int r = 0; r < 2; ++r) G[r] = Gst[lane + 64 * r] * 1.0f;  // x NR_long_tone_gain (1.0, Noise.cpp:706)
         }

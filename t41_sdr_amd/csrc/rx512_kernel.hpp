@@ -35,16 +35,13 @@ namespace t41 {
 // the slices fit.
 // PART 1 / 2 -- the two ends of the long-FFT pipeline -- keep 4-wave workgroups, 4 per CU:
 // [mask, tw1, tw2 2032 | 4 slices of 2052], scratch from the start of the slice.
-#ifndef T41RX_RESIDENT
-#define T41RX_RESIDENT 1  // 0 (experiments): the fused kernel with the 4-wave geometry and per-frame HBM state
-#endif
 // AGC on (PART 0): back to 4-wave workgroups and per-frame state in HBM.  The serial gain law
 // runs on one wave of the workgroup between two workgroup barriers; with 16 waves behind one
 // barrier the whole CU stops for every chain (47.6 us per 4096 x 2048 frame), four independent
 // workgroups per CU keep the other twelve waves busy (40.6 us).
 template <int PART, bool AGC = false>
 struct Geo {
-  static constexpr bool kResident = (PART == 0) && !AGC && T41RX_RESIDENT;
+  static constexpr bool kResident = (PART == 0) && !AGC;
   static constexpr int kWaves = kResident ? 16 : 4;
   static constexpr int kTab = kResident ? 1024 : kLdsTabFloats;
   static constexpr int kTw1 = kResident ? 0 : kLdsTabTw1;        // float2 units within the tables
@@ -80,7 +77,7 @@ template <int MODE, bool DEBUG, int PART, bool PLAIN, bool AGC = false, bool WQ1
 __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64), 4) void rx512_kernel(const RxArgs a) {
   T41RX_CLK_BEGIN();
   static_assert(!SEGPAR || (PART == 1 && MODE != kModeNfm) || (PART == 2 && MODE == kModeSsb && !AGC), "SEGPAR variants");
-  static_assert(!PIPE || ((AGC || MODE == kModeSam) && PART == 0 && !DEBUG && !SEGPAR && T41RX_RESIDENT),
+  static_assert(!PIPE || ((AGC || MODE == kModeSam) && PART == 0 && !DEBUG && !SEGPAR),
                 "PIPE: the pipelined variants -- AGC on (see agc_prep_pipe), the synchronous detector with the AGC off (sam_chain_pipe), or both (PSA)");
   constexpr bool PSAM = PIPE && MODE == kModeSam && !AGC;
   // round 4: the synchronous detector behind the AGC -- TWO serial chains per frame, each on a duty wave of its own,
@@ -89,7 +86,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
   constexpr bool PSA = PIPE && MODE == kModeSam && AGC;
   // input sub-blocks of the NEXT frame requested across the back end (the pipelined kernels hold them across the
   // preparation, a chain and the back end of an older frame: registers that spill there)
-  constexpr int kPF = PSAM ? T41RX_PIPE_PF_SAM : PIPE ? T41RX_PIPE_PF : T41RX_PF;
+  constexpr int kPF = PSAM ? kPrefetchPipeSam : PIPE ? kPrefetchPipe : kPrefetch;
   typedef Geo<PART, geo4(MODE, AGC) && !PIPE> G;
   constexpr bool KEEP = G::kResident;  // streaming state stays on chip across the frames of a launch
   constexpr int NW = G::kWaves;
@@ -154,7 +151,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
 
   const cf *ltab = reinterpret_cast<const cf *>(smem);
   float *lds = smem + G::kTab + wv * G::kSlice;
-  float *st = a.state + (size_t)(T41RX_ABLATE == 9 ? (ch & 15) : ch) * state_stride;
+  float *st = a.state + (size_t)ch * state_stride;
   // coefficients are read-only for the kernel: constant address space -> scalar (SMEM) loads,
   // re-derived through an opaque asm per phase so the compiler keeps the tap loads next to
   // their use instead of hoisting all 180 of them (and spilling SGPRs).
@@ -177,7 +174,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
   const double raw_r = ncs_rd->r;
   const float raw_dc = st[kStMisc + kMiscDc];
   uint64_t dphi = 0, phase0 = 0;
-  constexpr bool kKeepPl = T41RX_PHASE_SPLIT && T41RX_KEEP_PL && KEEP && !AGC && (MODE != kModeSam || T41RX_SAM_KEEP_PL);
+  constexpr bool kKeepPl = KEEP && !AGC && MODE != kModeSam;
   uint64_t pl_keep = 0;  // (8 lane + 1) dphi, the lane's part of the oscillator phases of a frame
   double osc_r = 1.0;
   float dc_carry = 0.0f;
@@ -196,8 +193,6 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
   float hist2c = 0.0f, audn[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   float4 agrec = make_float4(0, 0, 0, 0);  // PIPE: the AGC's delay line (its last 100 inputs), lanes 0..49, across the frames of a launch
   float2 agmag = make_float2(0, 0);        // ... and its magnitudes
-  // PIPE, SSB / NFM (T41RX_PIPE_KEEP_RE): the popped samples' real parts of the three frames between preparation and gain
-  float4 zre0 = make_float4(0, 0, 0, 0), zre1 = zre0, zre2 = zre0;
 #ifdef T41RX_STAMP
   unsigned long long stamp_acc = 0, stamp_last;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_last)::"memory");
@@ -250,12 +245,12 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
 #ifdef T41RX_PIPE_STAT
     unsigned long long ps_t = __builtin_readcyclecounter();  // [8] front end [9] AGC preparation [10] back end [11] iterations
 #endif
-    if (AGC) PRIO(2); else if (T41RX_PRIO_AGE == 2 && KEEP) { if (wv < 8) PRIO(2); else PRIO(3); } else PRIO(3);  // (AGC on: 3 is the serial chain's, see agc_apply)
+    if (AGC) PRIO(2); else PRIO(3);  // (AGC on: 3 is the serial chain's, see agc_apply)
     FRESH_LANE();
     const bool first_iter = (f == seg0);
     // sample offset of (channel, frame) in I / Q / audio: RxArgs::chan_stride / frame_stride (channel-major
     // [channel][frame][2048]: nframes * 2048 and 2048; time-major [frame][channel][2048]: 2048 and nchan * 2048)
-    const size_t chbase = (size_t)(T41RX_ABLATE == 9 ? (ch & 15) : ch) * (size_t)a.chan_stride;
+    const size_t chbase = (size_t)ch * (size_t)a.chan_stride;
     const size_t fbase = chbase + (size_t)f * (size_t)a.frame_stride;
     const int fb = PIPE ? (f >= kSkew ? f - kSkew : 0) : f;  // the frame the back end works on
     const size_t fbase_o = chbase + (size_t)fb * (size_t)a.frame_stride;
@@ -462,7 +457,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
           }
         }
         f2 dcs = splat(0.0f);
-        dc_highpass<8, !AGC && (MODE != kModeSam || T41RX_SAM_SCAN_FUSED)>(z, dcs, lane, hp8.x, hp8.y);  // from rest: 512 samples on, its memory of the start is a1^512
+        dc_highpass<8, !AGC && MODE != kModeSam>(z, dcs, lane, hp8.x, hp8.y);  // from rest: 512 samples on, its memory of the start is a1^512
         if (!PLAIN) {
   #pragma unroll
           for (int k = 0; k < 8; ++k) {
@@ -542,14 +537,13 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
           }
         }
         const float x[4] = {tailF.x * g_rf, tailF.y * g_rf, tailF.z * g_rf, tailF.w * g_rf};
-        dc2 = f2{(g_rf_i != g_rf) ? -dc_carry : dc_carry, dc_highpass_end_state<4, !AGC && (MODE != kModeSam || T41RX_SAM_SCAN_FUSED)>(x, hp4.x, hp4.y)};
+        dc2 = f2{(g_rf_i != g_rf) ? -dc_carry : dc_carry, dc_highpass_end_state<4, !AGC && MODE != kModeSam>(x, hp4.x, hp4.y)};
       } else if (preroll) {
         dc2 = dc_pre;  // inside a frame both chains simply run on
       }
 
       STAMP(15);  // prologue d: NCO/DC state uniformisation + Q's DC-block start state
       cf y2[2][2];  // /8 outputs of this frame: m = 128*round + 2*lane + e
-      cf o1x[2] = {splat(0.0f), splat(0.0f)};  // (T41RX_LOO 13: the last /4 outputs, a register source for the /2 window)
       // (cos, sin) table entries of this lane's first sample of the four sub-blocks.  All four
       // are requested HERE and nowhere later: vector-memory results return in issue order, so a
       // table read issued between two input requests could only be used once every older input
@@ -566,11 +560,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
         const uint64_t Pl = kKeepPl ? pl_keep : (uint64_t)(unsigned)(8 * lane + 1) * dphi;
   #pragma unroll
         for (int sb = 0; sb < 4; ++sb) {
-  #if T41RX_PHASE_SPLIT
           const uint64_t P = (phase0 + (uint64_t)(512 * sb) * dphi) + Pl;
-  #else
-          const uint64_t P = phase0 + (uint64_t)(512 * sb + 8 * lane + 1) * dphi;
-  #endif
           osc_u[sb] = (uint32_t)(P >> 24);
           osc_tab[sb] = (PART == 1) ? reinterpret_cast<const float2 *>(smem)[(int)(P >> 56)] : ldg2(tab + kTabSinCos, (unsigned)(P >> 56));
         }
@@ -654,7 +644,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
           }
           STAMP(s == 0 ? 14 : 0);  // wait for the sub-block's global loads + gain/interleave (14: first sub-block)
         // -- DC high-pass (127-128), band gain (133-134) / IQ amplitude (166)
-          if (!T41RX_CUT(6)) dc_highpass<8, !AGC && (MODE != kModeSam || T41RX_SAM_SCAN_FUSED)>(z, dc2, lane, hp8.x, hp8.y);
+          dc_highpass<8, !AGC && MODE != kModeSam>(z, dc2, lane, hp8.x, hp8.y);
           if (!PLAIN) {
             // band gain / IQ amplitude (Process.cpp:133-134, 166) and IQ phase correction
             // (Utility.cpp:178-187: phi < 0 mixes I into Q, phi > 0 mixes Q into I), branch-free:
@@ -706,12 +696,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
           // top of the frame, see there) x 32-bit Taylor remainder
           cf base;
           {
-  #if T41RX_PHASE_SPLIT
             const uint32_t u = osc_u[s];
-  #else
-            const uint64_t P = phase0 + (uint64_t)(n0 + 1) * dphi;
-            const uint32_t u = (uint32_t)(P >> 24);
-  #endif
             const float ang = (float)u * (float)(6.283185307179586476925 / 256.0 / 4294967296.0);
             const float a2 = ang * ang;
             const float sn = ang * fmaf(a2, -1.0f / 6.0f, 1.0f);
@@ -726,7 +711,6 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
   #pragma unroll
           for (int k = 0; k < 8; ++k) {
             const cf w = cf{ncw->wk[k][0], ncw->wk[k][1]};
-            if (T41RX_CUT(5)) continue;
             const cf osc = cmul_s(base, w);
             z[k] = cmulc(z[k], osc);
           }
@@ -751,20 +735,13 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
           // arm_fir_decimate_f32: y[m] = sum_i c[i] * state[4m + i]; state[i] = buf[i + 1]
           {
             auto pidx = [](int o) { return xpad(o); };  // window-relative, identical for every lane
-            if (T41RX_LOO == 14) {
-              fir_pair<kDec1Taps, 1, 5, 18, 6>(xw, pidx, cf0, kCoDec1, o1[0], o1[1], z);
-            } else if (!T41RX_CUT(4)) {
-              // (round 4, measured and dropped: the window requested one group ahead of its use behind scheduling
-              //  barriers, taps in 16-tap scalar loads -- 18 spilled registers, 26.7 against 22.4 us per frame)
-              // (round 5: window entries 28.. are the lane's own new samples, still in z: three of the 17 reads come from
-              // there -- in the kernels without the AGC (with it: neutral for SSB, 1 % slower behind SAM; SAM alone gains 2.8 %
-              // although it spills two registers for it, profiles/r05_ab_regtail_agc.txt))
-              if (T41RX_DEC1_REGTAIL && (!AGC || T41RX_DEC1_REGTAIL_AGC)) fir_pair<kDec1Taps, 1, 5, 18, 6, 14>(xw, pidx, cf0, kCoDec1, o1[0], o1[1], nullptr, z);
-              else fir_pair<kDec1Taps, 1, 5, 18, 6>(xw, pidx, cf0, kCoDec1, o1[0], o1[1]);
-            } else {
-              o1[0] = *reinterpret_cast<cf *>(xw);
-              o1[1] = *reinterpret_cast<cf *>(xw + 8);
-            }
+            // (round 4, measured and dropped: the window requested one group ahead of its use behind scheduling
+            //  barriers, taps in 16-tap scalar loads -- 18 spilled registers, 26.7 against 22.4 us per frame)
+            // (round 5: window entries 28.. are the lane's own new samples, still in z: three of the 17 reads come from
+            // there -- in the kernels without the AGC (with it: neutral for SSB, 1 % slower behind SAM; SAM alone gains 2.8 %
+            // although it spills two registers for it, profiles/r05_ab_regtail_agc.txt))
+            if (!AGC) fir_pair<kDec1Taps, 1, 5, 18, 6, 14>(xw, pidx, cf0, kCoDec1, o1[0], o1[1], z);
+            else fir_pair<kDec1Taps, 1, 5, 18, 6>(xw, pidx, cf0, kCoDec1, o1[0], o1[1]);
           }
           STAMP(3);  // LDS staging + /4 decimator
         // -- roll the /4 history (logical 512..539 -> 0..27) and append the /4 outputs
@@ -776,13 +753,10 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
             *reinterpret_cast<float4 *>(lds + kY1 + y1slot(24 + 64 * h + lane)) =
                 make_float4(o1[0].x, o1[0].y, o1[1].x, o1[1].y);
           }
-          if (T41RX_LOO == 13) { o1x[0] = o1[0]; o1x[1] = o1[1]; }
         }  // h
         STAMP(4);  // history roll
         if (rd == 1) {
           if (AGC) PRIO(1);
-          else if (T41RX_PRIO_AGE == 1 && KEEP) { if (wv < 8) PRIO(2); else PRIO(3); }
-          else if (T41RX_PRIO_AGE == 2 && KEEP) { if (wv < 8) PRIO(1); else PRIO(2); }
           else PRIO(2);
         }
       // ---- decimate by 2 (46 taps) over the 256 new /4 samples: m = 2*lane, 2*lane+1
@@ -791,15 +765,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
         {
           // window-relative complex offset o (even) -> offset in the planes, relative to lds + kY1 + 4 lane
           auto planes = [](int o) { return y1slot(o >> 1) / 2; };
-          if (T41RX_LOO == 13) {
-            const cf src[8] = {y2[0][0], y2[0][1], o1x[0], o1x[1], y2[0][1], o1x[1], o1x[0], y2[0][0]};
-            fir_pair<kDec2Taps, 3, 5, 26, 6>(lds + kY1 + 4 * lane, planes, cf0, kCoDec2, y2[rd][0], y2[rd][1], src);
-          } else if (!T41RX_CUT(3)) {
-            fir_pair<kDec2Taps, 3, 5, 26, 6>(lds + kY1 + 4 * lane, planes, cf0, kCoDec2, y2[rd][0], y2[rd][1]);
-          } else {
-            y2[rd][0] = *reinterpret_cast<cf *>(lds + kY1 + 4 * lane);
-            y2[rd][1] = *reinterpret_cast<cf *>(lds + kY1 + 4 * lane + 2);
-          }
+          fir_pair<kDec2Taps, 3, 5, 26, 6>(lds + kY1 + 4 * lane, planes, cf0, kCoDec2, y2[rd][0], y2[rd][1]);
         }
         STAMP(5);  // /2 decimator
       {  // roll the /2 history: logical 256..303 -> 0..47
@@ -1053,58 +1019,56 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
             tw2[q] = ltab[G::kTw2 + 8 * q + (lane & 7)];
           }
         }
-        if (!T41RX_CUT(2)) {
-          if (GMASK) {
-            fft512_ldstw<false>(v, ltab + G::kTw1 + lane, ltab + G::kTw2 + (lane & 7), lds + kScr, lane, [&]() {
-  #pragma unroll
-              for (int r = 0; r < 8; ++r) {
-                const float2 t = tab[kTabMask + 64 * r + lane];
-                mk[r] = cf{t.x, t.y};
-              }
-            });
-          } else {
-            fft512<false>(v, tw1, tw2, lds + kScr, lane);
-          }
-  #pragma unroll
-          for (int r = 0; r < 8; ++r) v[r] = cmul(v[r], GMASK ? mk[r] : ltab[kLdsTabMask + 64 * r + lane]);
-          if (DEBUG && a.spect) {
-            // ---- audio spectrum side output (Process.cpp:550-570 with updateDisplayFlag == 1):
-            // audioSpectBuffer[1023 - k] = iFFT_buffer[k]^2 over the 1024 floats of the masked
-            // spectrum.  The mask table carries 1/N (the reference applies it in the inverse FFT):
-            // a power of two, so squaring after undoing it is exact.  v[r] = bin lane + 64 r.
-            float *sp = a.spect + ((size_t)ch * a.nframes + f) * 1024;
-            float best = -1.0f;
-            int besti = 0;
+        if (GMASK) {
+          fft512_ldstw<false>(v, ltab + G::kTw1 + lane, ltab + G::kTw2 + (lane & 7), lds + kScr, lane, [&]() {
   #pragma unroll
             for (int r = 0; r < 8; ++r) {
-              const int k = lane + 64 * r;
-              const float re = v[r].x * 512.0f, im = v[r].y * 512.0f;
-              const float e0 = im * im, e1 = re * re;  // buffer indices 1022 - 2k, 1023 - 2k
-              *reinterpret_cast<float2 *>(sp + 1022 - 2 * k) = make_float2(e0, e1);
-              // arm_max_f32: the first occurrence of the maximum = the smallest buffer index
-              if (e1 >= best) { best = e1; besti = 1023 - 2 * k; }
-              if (e0 >= best) { best = e0; besti = 1022 - 2 * k; }
+              const float2 t = tab[kTabMask + 64 * r + lane];
+              mk[r] = cf{t.x, t.y};
             }
-  #pragma unroll
-            for (int m = 1; m < 64; m <<= 1) {
-              const float ob = __shfl_xor(best, m, 64);
-              const int oi = __shfl_xor(besti, m, 64);
-              if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
-            }
-            if (lane == 0) {
-              float *mx = a.spect_max + ((size_t)ch * a.nframes + f) * 3;
-              const float ave = (float)(.5 * (double)best + .5 * (double)st[kStMisc + kMiscMaxSqAve]);  // :570
-              mx[0] = best;
-              mx[1] = (float)besti;
-              mx[2] = ave;
-              st[kStMisc + kMiscMaxSqAve] = ave;
-            }
-          }
-          if (GMASK)
-            fft512_ldstw<true>(v, ltab + G::kTw1 + lane, ltab + G::kTw2 + (lane & 7), lds + kScr, lane, []() {});
-          else
-            fft512<true>(v, tw1, tw2, lds + kScr, lane);
+          });
+        } else {
+          fft512<false>(v, tw1, tw2, lds + kScr, lane);
         }
+  #pragma unroll
+        for (int r = 0; r < 8; ++r) v[r] = cmul(v[r], GMASK ? mk[r] : ltab[kLdsTabMask + 64 * r + lane]);
+        if (DEBUG && a.spect) {
+          // ---- audio spectrum side output (Process.cpp:550-570 with updateDisplayFlag == 1):
+          // audioSpectBuffer[1023 - k] = iFFT_buffer[k]^2 over the 1024 floats of the masked
+          // spectrum.  The mask table carries 1/N (the reference applies it in the inverse FFT):
+          // a power of two, so squaring after undoing it is exact.  v[r] = bin lane + 64 r.
+          float *sp = a.spect + ((size_t)ch * a.nframes + f) * 1024;
+          float best = -1.0f;
+          int besti = 0;
+  #pragma unroll
+          for (int r = 0; r < 8; ++r) {
+            const int k = lane + 64 * r;
+            const float re = v[r].x * 512.0f, im = v[r].y * 512.0f;
+            const float e0 = im * im, e1 = re * re;  // buffer indices 1022 - 2k, 1023 - 2k
+            *reinterpret_cast<float2 *>(sp + 1022 - 2 * k) = make_float2(e0, e1);
+            // arm_max_f32: the first occurrence of the maximum = the smallest buffer index
+            if (e1 >= best) { best = e1; besti = 1023 - 2 * k; }
+            if (e0 >= best) { best = e0; besti = 1022 - 2 * k; }
+          }
+  #pragma unroll
+          for (int m = 1; m < 64; m <<= 1) {
+            const float ob = __shfl_xor(best, m, 64);
+            const int oi = __shfl_xor(besti, m, 64);
+            if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
+          }
+          if (lane == 0) {
+            float *mx = a.spect_max + ((size_t)ch * a.nframes + f) * 3;
+            const float ave = (float)(.5 * (double)best + .5 * (double)st[kStMisc + kMiscMaxSqAve]);  // :570
+            mx[0] = best;
+            mx[1] = (float)besti;
+            mx[2] = ave;
+            st[kStMisc + kMiscMaxSqAve] = ave;
+          }
+        }
+        if (GMASK)
+          fft512_ldstw<true>(v, ltab + G::kTw1 + lane, ltab + G::kTw2 + (lane & 7), lds + kScr, lane, []() {});
+        else
+          fft512<true>(v, tw1, tw2, lds + kScr, lane);
       }
     }
     FRESH_LANE();
@@ -1198,7 +1162,6 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
         const int nvalid = left < NW ? left : NW;
         unsigned *flags = reinterpret_cast<unsigned *>(smem) + kPipeFlags;
         constexpr bool NEED_IM = (MODE == kModeAm);
-        constexpr bool KEEP_RE = T41RX_PIPE_KEEP_RE && !NEED_IM && !PSAM;  // re(f - 2) = zre2 here, re(f) -> zre0 below
         unsigned long long *pipe_stat = reinterpret_cast<unsigned long long *>(a.agc_pipe + (size_t)a.nchan * kPipeSlots * kPipeSlotFloats) + (size_t)job * 16;
         (void)pipe_stat;
         unsigned *pipe_err = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned long long *>(a.agc_pipe + (size_t)a.nchan * kPipeSlots * kPipeSlotFloats) +
@@ -1221,14 +1184,14 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
         if (early) {
           __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
           if (PSAM) gin.vv = *reinterpret_cast<const float4 *>(bslot + 512 + 4 * lane);  // the frame's audio
-          else gin = agc_gain_request<NEED_IM, KEEP_RE>(bslot, lane, zre2);
+          else gin = agc_gain_request<NEED_IM>(bslot, lane);
         }
         if (f < seg1) {  // this frame's chain operands and popped samples -> the channel's slot
           float *pslot = a.agc_pipe + ((size_t)ch * kPipeSlots + f % kPipeSlots) * kPipeSlotFloats;
           if (PSAM) sam_prep_pipe(v, fixed_gain, pslot, lane);
           else {
             if (first_iter) agmag = make_float2(agc_mag(cf{agrec.x, agrec.y}), agc_mag(cf{agrec.z, agrec.w}));  // (later frames: carried)
-            agrec = agc_prep_pipe<AgcLds<true>, NEED_IM, KEEP_RE>(v, agrec, agmag, lds, pslot, cf0, lane, &zre0);
+            agrec = agc_prep_pipe<AgcLds<true>, NEED_IM>(v, agrec, agmag, lds, pslot, cf0, lane);
           }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
           if (lane == 0) __hip_atomic_fetch_add(flags + f % kPipeSlots, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1236,16 +1199,10 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
           if (lane == 0) pipe_stat[9] += __builtin_readcyclecounter() - ps_t;
 #endif
         }
-        const float4 re_gain = zre2;  // the gain below works on frame f - 2 ...
-        if (KEEP_RE) {                // ... and the ring moves on for the next iteration (every iteration, also the first two)
-          zre2 = zre1;
-          zre1 = zre0;
-        }
-        (void)re_gain;
         const int g = f - 1;  // the frame whose chain is due
-#if T41RX_PIPE_CLAIM
         // the duty goes to the first wave that gets here (the one furthest ahead: it is sure to be waiting when the previous
-        // chain ends, and it can best afford to fall a chain behind) instead of rotating blindly
+        // chain ends, and it can best afford to fall a chain behind) instead of rotating blindly (frame g -> wave g mod
+        // channels: measured 1.2 % slower)
         bool duty = false;
         if (g >= seg0 && g < seg1) {
           // flags[4] = the next frame whose chain nobody has taken yet: frame g is taken by the one wave whose
@@ -1258,9 +1215,6 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
           duty = __builtin_amdgcn_readfirstlane(won) != 0u;
         }
         if (duty) {
-#else
-        if (g >= seg0 && g < seg1 && g % nvalid == wv) {
-#endif
           {
             PIPE_STAT_T0();
             pipe_wait_ge(flags + g % kPipeSlots, (unsigned)nvalid, pipe_err);
@@ -1287,7 +1241,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
           pipe_wait_ge(flags + 3, (unsigned)(fb + 1), pipe_err);
           PIPE_STAT_ADD(3);
           if (PSAM) gin.vv = *reinterpret_cast<const float4 *>(bslot + 512 + 4 * lane);
-          else gin = agc_gain_request<NEED_IM, KEEP_RE>(bslot, lane, re_gain);
+          else gin = agc_gain_request<NEED_IM>(bslot, lane);
         }
 #ifdef T41RX_PIPE_STAT
         ps_t = __builtin_readcyclecounter();
@@ -1467,15 +1421,6 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
       }
 
     }
-    if (T41RX_CUT(1)) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        // (1-KiB store instructions like the product's, so that the staged cuts time the arithmetic they
-        // remove and not a worse store pattern; 8: the 16 x 64 B form)
-        *reinterpret_cast<float4 *>(gO + (T41RX_ABLATE == 8 ? 32 * (16 * (u & 3) + (lane >> 2)) + 16 * (u >> 2) + 4 * (lane & 3)
-                                                            : 4 * lane + 256 * u)) = make_float4(aud[0], aud[1], aud[2], aud[3]);
-      continue;
-    }
     if ((DEBUG || WQ15) && PART == 0 && a.aud_out) {
       // noise reduction / notch on (Process.cpp:841-866): those stages sit between the demodulator and the
       // interpolators and run in kernels of their own (nr_kernels.hip) on the whole call's audio; this kernel
@@ -1506,7 +1451,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
     }
     wave_sync();
     STAMP(10);  // demod + x2 staging
-    if (T41RX_PRIO_AGE == 1 && KEEP && !AGC) { if (wv < 8) PRIO(0); else PRIO(1); } else PRIO(0);
+    PRIO(0);
     f2 u1[4];  // outputs (2n, 2n+1) of input n = 4 lane + u
     {
       float w[28];
@@ -1556,11 +1501,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
       for (int i = 0; i < 7; ++i) {
         const float up = lane_up1(x1[i + 1]);
         const float hs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hist2), i + 1));
-  #if T41RX_WRITELANE  // (one v_writelane_b32 instead of the move + select `lane == 0 ? hs : up` compiles to)
-        w[i] = write_lane<0>(up, hs);
-  #else
-        w[i] = (lane == 0) ? hs : up;
-  #endif
+        w[i] = write_lane<0>(up, hs);  // (one v_writelane_b32 instead of the move + select `lane == 0 ? hs : up` compiles to)
       }
 #pragma unroll
       for (int i = 0; i < 8; ++i) w[7 + i] = x1[i];
@@ -1581,17 +1522,10 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
         }
       }
       if (PART == 2 || KEEP) {  // the same seven values, kept for the next segment / frame: lane i = entry i
-  #if T41RX_WRITELANE  // (instead of move + compare + select per entry)
+        // (v_writelane_b32 instead of move + compare + select per entry)
   #define T41RX_HIST2_ENTRY(i) hist2c = write_lane<i>(hist2c, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x1[i]), 63)));
         T41RX_HIST2_ENTRY(1) T41RX_HIST2_ENTRY(2) T41RX_HIST2_ENTRY(3) T41RX_HIST2_ENTRY(4) T41RX_HIST2_ENTRY(5) T41RX_HIST2_ENTRY(6) T41RX_HIST2_ENTRY(7)
   #undef T41RX_HIST2_ENTRY
-  #else
-#pragma unroll
-        for (int i = 1; i < 8; ++i) {
-          const float t = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x1[i]), 63));
-          hist2c = (lane == i) ? t : hist2c;
-        }
-  #endif
       }
       // out[4n + j - 1] = sum_t state[n + t] * c[(4 - j) + 4 t],  state[n + t] = w[u + t]:
       // (out[4n], out[4n+1]) += w * (c[4t+3], c[4t+2]);  (out[4n+2], out[4n+3]) += w * (c[4t+1], c[4t])
@@ -1606,8 +1540,8 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
       // meanwhile: the /4 history (lanes 0..13) and the /2 history (lanes 16..39) share one
       // float4, the part of the overlap block below float 2048 (lanes 0..22) takes another.
       // (Two half-size transpositions instead -- 64-byte store segments -- cost 8..17 % of the
-      // whole kernel: measured, tools/build_variant.sh -DT41RX_X_HALFTR=1.)
-      constexpr bool PARK = KEEP && !WQ15 && !T41RX_X_HALFTR;
+      // whole kernel: measured, round 5.)
+      constexpr bool PARK = KEEP && !WQ15;
       constexpr int kOvPark = (2048 - G::kOV + 3) / 4;  // float4s of the overlap block below float 2048
       static_assert(!PARK || (kOvPark > 0 && kOvPark <= 64 && G::kH1 >= 2048), "parking layout");
       float4 park_h = any_float4(), park_o = any_float4();
@@ -1618,7 +1552,6 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
         wave_sync();
       }
       float *tr = PARK ? lds : lds + kScr;
-      constexpr bool HALFTR = (KEEP && !PARK) || T41RX_X_HALFTR;
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         f2 o01 = splat(0.0f), o23 = splat(0.0f);
@@ -1630,23 +1563,8 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
         }
         // ---- volume (Process.cpp:929): DF * VolumeToAmplification() is folded into the x4 taps by the host
         // (DevCoef::int2), one rounding per tap instead of one per output
-        if (!WQ15 && !HALFTR) {
+        if (!WQ15) {
           *reinterpret_cast<float4 *>(tr + 4 * (8 * lane + (u ^ (lane & 7)))) = make_float4(o01.x, o01.y, o23.x, o23.y);
-        } else if (!WQ15) {
-          // (experiment T41RX_X_HALFTR) a 1024-float transposition buffer: the 32 outputs of a lane
-          // go out in two halves of 16 = 64 contiguous bytes per lane: slot 4 lane + ((u & 3) ^
-          // swizzle), swizzle = (lane >> 1) & 3, and a store instruction then writes 16 rows of 64 B
-          *reinterpret_cast<float4 *>(tr + 4 * (4 * lane + ((u & 3) ^ ((lane >> 1) & 3)))) = make_float4(o01.x, o01.y, o23.x, o23.y);
-          if ((u & 3) == 3) {
-            wave_sync();
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {  // float4 F = 64 i + lane of this half: row F >> 2, column F & 3
-              const int row = 16 * i + (lane >> 2);
-              const float4 t = lds4(tr + 4 * (4 * row + ((lane & 3) ^ ((row >> 1) & 3))));
-              stg_stream(gO + 16 * (u >> 2), fresh_off(32 * row + 4 * (lane & 3)), t);
-            }
-            wave_sync();
-          }
         } else if ((u & 1) == 0) {  // arm_float_to_q15 (Process.cpp:936)
           qw[0] = q15_pack2(o01.x, o01.y);
           qw[1] = q15_pack2(o23.x, o23.y);
@@ -1661,7 +1579,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
       STAMP(12);  // x4 interpolator + LDS transpose writes
       // ... and every global store instruction then writes 1 KiB of consecutive addresses:
       // float4 index F = 64 i + lane lives in row F >> 3 = 8 i + (lane >> 3), column lane & 7
-      if (!WQ15 && !HALFTR) {
+      if (!WQ15) {
         const LaneOff lof = fresh_off(4 * lane);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -1669,7 +1587,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
           const float4 t = lds4(tr + 4 * (8 * row + ((lane & 7) ^ (row & 7))));
           stg_stream(gO + 256 * i, lof, t);
         }
-      } else if (WQ15) {  // 4 pieces per row: piece F = 64 i + lane is row F >> 2, column lane & 3
+      } else {  // 4 pieces per row: piece F = 64 i + lane is row F >> 2, column lane & 3
         const LaneOff lof = fresh_off(4 * lane);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {

@@ -6,15 +6,6 @@
 
 namespace t41 {
 
-// (T41RX_AGC_PIPE=0 in the environment: the barrier form for calls of any length -- the tests that compare the two forms)
-static inline bool agc_pipe_env() {
-  static const bool on = [] {
-    const char *e = std::getenv("T41RX_AGC_PIPE");
-    return !e || std::atoi(e) != 0;
-  }();
-  return on;
-}
-
 template <int MODE>
 static hipError_t launch512(const RxArgs &a, hipStream_t s, bool debug) {
   // One 16-wave workgroup per CU (all 160 KiB of LDS, declared statically by the kernel): a
@@ -25,10 +16,9 @@ static hipError_t launch512(const RxArgs &a, hipStream_t s, bool debug) {
   hipLaunchKernelGGL((rx512_kernel<MODE, DBG, 0, PLN, AGCv, Q15v>),                                      \
                      dim3((a.nchan + Geo<0, AGCv>::kWaves - 1) / Geo<0, AGCv>::kWaves), dim3(Geo<0, AGCv>::kWaves * 64), 0, s, a)
   // AGC on, calls of four frames or more without taps: the pipelined variant (agc_prep_pipe); shorter calls have
-  // nothing to overlap and take the barrier form, which computes the same values (T41RX_AGC_PIPE=0: experiments, tests)
-  const bool pipe_env = agc_pipe_env();
+  // nothing to overlap and take the barrier form, which computes the same values
   if constexpr (MODE != kModeSam) {
-    if (a.agc && a.agc_pipe && !debug && a.nframes >= 4 && pipe_env) {
+    if (a.agc && a.agc_pipe && !debug && a.nframes >= 4) {
 #define T41RX_GOP(PLN, Q15v)                                                                             \
   hipLaunchKernelGGL((rx512_kernel<MODE, false, 0, PLN, true, Q15v, false, true>), dim3((a.nchan + Geo<0>::kWaves - 1) / Geo<0>::kWaves), \
                      dim3(Geo<0>::kWaves * 64), 0, s, a)

@@ -5,14 +5,13 @@
 namespace t41 {
 
 hipError_t launch512_sam(const RxArgs &a, hipStream_t s, bool debug) {
-  const bool pipe_env = agc_pipe_env();
-  if (!a.agc && a.agc_pipe && !debug && a.nframes >= 4 && pipe_env) {  // the PLL pipelined against the neighbouring frames (sam_chain_pipe)
+  if (!a.agc && a.agc_pipe && !debug && a.nframes >= 4) {  // the PLL pipelined against the neighbouring frames (sam_chain_pipe)
     const dim3 g16((a.nchan + Geo<0>::kWaves - 1) / Geo<0>::kWaves), b16(Geo<0>::kWaves * 64);
     if (a.q15) hipLaunchKernelGGL((rx512_kernel<kModeSam, false, 0, false, false, true, false, true>), g16, b16, 0, s, a);
     else hipLaunchKernelGGL((rx512_kernel<kModeSam, false, 0, false, false, false, false, true>), g16, b16, 0, s, a);
     return hipGetLastError();
   }
-  if (a.agc && a.agc_pipe && !debug && a.nframes >= 4 && pipe_env) {  // round 4: AGC chain and PLL, each on a duty wave of its own (PSA)
+  if (a.agc && a.agc_pipe && !debug && a.nframes >= 4) {  // round 4: AGC chain and PLL, each on a duty wave of its own (PSA)
     const dim3 g16((a.nchan + Geo<0>::kWaves - 1) / Geo<0>::kWaves), b16(Geo<0>::kWaves * 64);
     if (a.q15) hipLaunchKernelGGL((rx512_kernel<kModeSam, false, 0, false, true, true, false, true>), g16, b16, 0, s, a);
     else hipLaunchKernelGGL((rx512_kernel<kModeSam, false, 0, false, true, false, false, true>), g16, b16, 0, s, a);

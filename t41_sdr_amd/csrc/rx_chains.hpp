@@ -42,10 +42,6 @@ static_assert(AgcLds<false>::S + kAgcScalars <= kLdsFloatsPerWave, "AGC scratch 
 static_assert(AgcLds<true>::S + kAgcScalars <= 1348 && AgcLds<true>::P0 + 256 <= 1348 + 4 * kY1Plane &&
               AgcLds<true>::P1 + 256 <= 1348 + 608, "AGC scratch vs resident state");
 static_assert(kAgcDelay == 97 && kAgcHist == 100, "window arithmetic below is written for 97 / 100");
-#ifndef T41RX_AGC_COOP
-#define T41RX_AGC_COOP 1
-#endif
-constexpr bool kAgcCoop = T41RX_AGC_COOP;
 
 // DSP_Fn.cpp:520-523 (pmode = 1): separate roundings, correctly rounded square root
 __device__ __forceinline__ float agc_mag(cf z) {
@@ -152,13 +148,17 @@ __device__ __forceinline__ void agc_slow_block(AgcState &st, const AgcConsts &g,
   st = AgcState{fast_backaverage, hang_backaverage, volts, save_volts, state, decay_type, hang_counter};
 }
 
-// State 3's decay step inside the fast block: 1 = the reference's double-precision expression (shipped); 0 = two FMAs
-// that bracket it + the slow block where they differ (round 4 experiment: bit-identical over tools/agc_decay_check.py's
-// 24 streams, and no faster -- 32.2-32.4 against 31.9-32.1 us per frame on bench.py's ssb_agc, 36.3 against 33.5 on pure
-// noise, where one block in ten then takes the slow path: the chain is paced by more than this step)
-#ifndef T41RX_AGC_DECAY64
-#define T41RX_AGC_DECAY64 1
-#endif
+// State 3's decay step, (float)((double)volts + (double)step * .05) (DSP_Fn.cpp:614), is four dependent double-precision
+// instructions (two conversions in, a multiply, an add, a conversion out).  Two FMAs bracket it: for floats c_lo < .05 < c_hi
+// the products step * c are exact in double, the double sum and both roundings are monotonic, so the reference's value lies
+// between fl(volts + step * c_lo) and fl(volts + step * c_hi).  Where the two agree that IS the reference's value; where they
+// differ (a rounding boundary between them: about |step| / |volts| / 10 of the steps, i.e. < 1e-4) the block is redone by
+// the double expression.  c_lo / c_hi are the SECOND neighbours of .05 either side: an FMA rounds once where the reference
+// rounds to double first, which can move the result by one ulp when the sum sits within 2^-53 of a boundary -- a shift 10^7
+// times smaller than the one the extra neighbour adds.  agc_fast_block() keeps the double expression: the bracket alone in
+// it (round 4 experiment) was bit-identical over 24 streams and no faster -- 32.2-32.4 against 31.9-32.1 us per frame on
+// bench.py's ssb_agc, 36.3 against 33.5 on pure noise, where one block in ten then takes the slow path: the chain is paced by
+// more than this step.  agc_fast_block_s() and agc_block_phased() below use it.
 // Lane masks as plain 64-bit scalars.  Written out by hand because the compiler, given bools,
 // rebuilds them as 0/1 integers in VGPRs every time two of them meet in a select: with these
 // three wrappers a comparison is one VALU instruction with an SGPR-pair result, the logic between
@@ -236,26 +236,8 @@ __device__ __forceinline__ lanemask agc_fast_block(AgcState &st, AgcLane &d, con
     const float step = (ring_max - volts) * pick(ge, attack_mult, d.stay);
     float next = volts + step;
     if (HAS3) {
-#if T41RX_AGC_DECAY64
       const float next3 = (float)((double)volts + (double)step * .05);
       next = pick(d.is3 & ~ge, next3, next);
-#else
-      // State 3's decay step, (float)((double)volts + (double)step * .05) (DSP_Fn.cpp:614): four dependent double-precision
-      // instructions (two conversions in, a multiply, an add, a conversion out) in a chain that is paced by its
-      // instruction count.  Sandwich instead: for floats c_lo < .05 < c_hi the products step * c are exact in double, the
-      // double sum and both roundings are monotonic, so the reference's value lies between fl(volts + step * c_lo) and
-      // fl(volts + step * c_hi) -- two FMAs.  Where the two agree that IS the reference's value; where they differ (a
-      // rounding boundary between them: about |step| / |volts| / 10 of the steps, i.e. < 1e-4) the block is redone by
-      // agc_slow_block(), which has the expression as written.  c_lo / c_hi are the SECOND neighbours of .05 either side:
-      // an FMA rounds once where the reference rounds to double first, which can move the result by one ulp when the sum
-      // sits within 2^-53 of a boundary -- a shift 10^7 times smaller than the one the extra neighbour adds.
-      const float r_lo = __builtin_fmaf(step, __uint_as_float(0x3d4ccccbu), volts);
-      const float next3 = __builtin_fmaf(step, __uint_as_float(0x3d4cccceu), volts);
-      lanemask differ;
-      asm("v_cmp_neq_f32_e64 %0, %1, %2" : "=s"(differ) : "v"(r_lo), "v"(next3));
-      ok &= ~(differ & d.is3 & ~ge);
-      next = pick(d.is3 & ~ge, next3, next);
-#endif
     }
     asm("v_max_f32 %0, %1, %2" : "=v"(volts) : "v"(next), "v"(min_volts));  // :629 (no NaNs here)
     vo[k] = volts;
@@ -278,8 +260,8 @@ __device__ __forceinline__ lanemask agc_fast_block(AgcState &st, AgcLane &d, con
 // an in-order wave.  Here both candidates are computed from the difference at once -- attack: volts + diff * attack_mult,
 // stay: volts + diff * stay, the very products and sums the reference would have formed on either branch -- and selected
 // when the comparison, issued beside the subtraction, has long returned; state 3's decay value comes from two FMAs that
-// bracket the reference's double expression (c_lo < .05 < c_hi, second float neighbours: see T41RX_AGC_DECAY64 above for
-// why their agreement proves the value) instead of through double precision; and everything that only feeds masks
+// bracket the reference's double expression (c_lo < .05 < c_hi, second float neighbours: see above for why their
+// agreement proves the value) instead of through double precision; and everything that only feeds masks
 // (the assumption check, save_volts, the state bookkeeping) waits for the end of the block, off the chain.  Dependent
 // path per step: subtract, multiply, add / FMA, two selects, max.  `sand` returns the lanes whose bracket did not close
 // in some step (their block is redone by agc_fast_block<true>, which has the double expression); the other result
@@ -343,14 +325,10 @@ __device__ __forceinline__ lanemask agc_fast_block_s(AgcState &st, AgcLane &d, c
   d.in0 = in0;
   return ok;
 }
-#ifndef T41RX_AGC_SPEC
-#define T41RX_AGC_SPEC 1  // 0: round 3's fast block only (A/B, tools/agc_decay_check.py)
-#endif
 // one block of four steps by the fastest form that is exact for it
 __device__ __forceinline__ lanemask agc_block(AgcState &t, AgcLane &dt, const AgcState &st, const AgcLane &d, const AgcConsts &g,
                                               const float (&rm)[4], const float (&pf)[4], const float (&ph)[4], float (&vo)[4]) {
   const bool has3 = (d.is3 & ~d.in0) != 0;
-#if T41RX_AGC_SPEC
   lanemask sand = 0;
   lanemask ok = has3 ? agc_fast_block_s<true>(t, dt, g, rm, pf, ph, vo, sand) : agc_fast_block_s<false>(t, dt, g, rm, pf, ph, vo, sand);
   if (sand != 0) {  // a rounding boundary between the bracketing values somewhere: the double expression decides
@@ -359,9 +337,6 @@ __device__ __forceinline__ lanemask agc_block(AgcState &t, AgcLane &dt, const Ag
     ok = agc_fast_block<true>(t, dt, g, rm, pf, ph, vo);
   }
   return ok;
-#else
-  return has3 ? agc_fast_block<true>(t, dt, g, rm, pf, ph, vo) : agc_fast_block<false>(t, dt, g, rm, pf, ph, vo);
-#endif
 }
 
 // Round 4, second step: the block of agc_chain_pipe().  The duty wave issues one instruction per ~5-6 cycles whatever it
@@ -384,15 +359,11 @@ __device__ __forceinline__ lanemask agc_block(AgcState &t, AgcLane &dt, const Ag
 //     per block: measured, no gain);
 //   * the chunk's volts stay in registers (agc_chain_pipe: `keep`) instead of a write to the stage and a read back.
 // Every float operation is one of agc_fast_block_s()'s on the same operands, or an FMA by 1 in place of a sum: bit-identical
-// (T41RX_AGC_PHASED=0 builds the form above; tools/agc_decay_check.py, the pipelined == barrier tests and
-// tools/pipe_soak.py -- 89 529 random runs, profiles/r04_pipe_soak2.json -- compare them).
-// Timing experiments on one box (wrong results, T41RX_AGC_X), before the bookkeeping went per block, 33.6 us per frame:
-// without the back-averages 31.3, without the bookkeeping 30.2, without the bracket 32.0, without all three 29.4; after:
-// 30.2 -> 29.9 / 29.5 / 29.7 / 28.8 -- what is left of the period is the sixteen waves' own work.
-#ifndef T41RX_AGC_PHASED
-#define T41RX_AGC_PHASED 1
-#endif
-// (T41RX_AGC_X: timing experiments with wrong results, rx_experiments.hpp)
+// (the pipelined == barrier tests and tools/pipe_soak.py -- 89 529 random runs, profiles/r04_pipe_soak2.json -- compare
+// it with the barrier kernels' agc_block()).
+// Timing experiments on one box (wrong results), before the bookkeeping went per block, 33.6 us per frame: without the
+// back-averages 31.3, without the bookkeeping 30.2, without the bracket 32.0, without all three 29.4; after: 30.2 -> 29.9 /
+// 29.5 / 29.7 / 28.8 -- what is left of the period is the sixteen waves' own work.
 struct AgcLaneP {
   f2 mult;  // (attack_mult, stay)
   f2 cb;    // state 3: the second float neighbours of .05 either side (see above); the others: (1, 1)
@@ -422,54 +393,42 @@ __device__ __forceinline__ lanemask agc_block_phased(AgcState &st, AgcLane &d, c
     ge[k] = lanes_ge(rm[k], volts);
     const f2 s2 = splat(diff) * lp.mult;  // (diff * attack_mult, diff * stay)
     const float na = volts + s2.x;        // the attack's value
-    float cand;
-    if (!(T41RX_AGC_X & 4)) {
-      const f2 r = pk_fma(splat(s2.y), lp.cb, splat(volts));  // state 3: the bracket; the others: volts + ss twice
-      lanemask differ;
-      asm("v_cmp_neq_f32_e64 %0, %1, %2" : "=s"(differ) : "v"(r.x), "v"(r.y));
-      df |= differ;
-      cand = r.y;
-    } else {
-      cand = volts + s2.y;
-    }
-    const float next = pick(ge[k], na, cand);
+    const f2 r = pk_fma(splat(s2.y), lp.cb, splat(volts));  // state 3: the bracket; the others: volts + ss twice
+    lanemask differ;
+    asm("v_cmp_neq_f32_e64 %0, %1, %2" : "=s"(differ) : "v"(r.x), "v"(r.y));
+    df |= differ;
+    const float next = pick(ge[k], na, r.y);
     asm("v_max_f32 %0, %1, %2" : "=v"(volts) : "v"(next), "v"(min_volts));  // :629 (no NaNs here)
     vo[k] = volts;
-    if (k >= 2 && !(T41RX_AGC_X & 1)) {  // two steps behind: their operands were requested at the top of the block
+    if (k >= 2) {  // two steps behind: their operands were requested at the top of the block
       back = splat(am[2 * (k - 2)]) * backmult + onem * back;  // :525-526
       back = splat(am[2 * (k - 2) + 1]) * backmult + onem * back;
     }
   }
   lanemask ok = ~(d.is2 & __builtin_amdgcn_ballot_w64(st.hang_counter <= 4));  // the hang counter cannot run out inside the block
-  if (!(T41RX_AGC_X & 2)) {
-    const lanemask any = ge[0] | ge[1] | ge[2] | ge[3];
-    if (__builtin_expect((any | d.in0) == 0, 1)) {
-      // no attack, no lane in state 0: every lane stays in its decay state unless its fast decay has reached save_volts --
-      // volts does not rise without an attack (diff < 0, multipliers >= 0, monotonic roundings), so "volts > thr" before
-      // the last step implies it before the three others -- EXCEPT through the clamp of :629: a block that starts below
-      // min_volts (a live set_params / set_coeffs raised it, or a restored checkpoint) is lifted to it at step 0, so
-      // vin[0] may sit at or below the threshold while vin[1..3] = min_volts sit above it; once clamped the three are
-      // equal, so the first and the last comparison cover every step
-#if T41RX_AGC_R04CHECK  // (experiment build: round 4's unsound short-cut, to show that the tests and the soak catch it)
-      ok &= lanes_gt(vin[3], d.thr);
-#else
-      ok &= lanes_gt(vin[0], d.thr) & lanes_gt(vin[3], d.thr);
-#endif
-    } else {
-      lanemask in0 = d.in0, pend = d.pend;
-      float save_volts = st.save_volts;
+  const lanemask any = ge[0] | ge[1] | ge[2] | ge[3];
+  if (__builtin_expect((any | d.in0) == 0, 1)) {
+    // no attack, no lane in state 0: every lane stays in its decay state unless its fast decay has reached save_volts --
+    // volts does not rise without an attack (diff < 0, multipliers >= 0, monotonic roundings), so "volts > thr" before
+    // the last step implies it before the three others -- EXCEPT through the clamp of :629: a block that starts below
+    // min_volts (a live set_params / set_coeffs raised it, or a restored checkpoint) is lifted to it at step 0, so
+    // vin[0] may sit at or below the threshold while vin[1..3] = min_volts sit above it; once clamped the three are
+    // equal, so the first and the last comparison cover every step
+    ok &= lanes_gt(vin[0], d.thr) & lanes_gt(vin[3], d.thr);
+  } else {
+    lanemask in0 = d.in0, pend = d.pend;
+    float save_volts = st.save_volts;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        ok &= ge[k] | (lanes_gt(vin[k], d.thr) & ~in0);
-        save_volts = pick(ge[k] & pend, vin[k], save_volts);  // the first attack out of 2, 3, 4
-        pend &= ~ge[k];
-        in0 |= ge[k];
-      }
-      st.save_volts = save_volts;
-      st.state = __float_as_int(pick(in0, __int_as_float(0), __int_as_float(st.state)));
-      d.pend = pend;
-      d.in0 = in0;
+    for (int k = 0; k < 4; ++k) {
+      ok &= ge[k] | (lanes_gt(vin[k], d.thr) & ~in0);
+      save_volts = pick(ge[k] & pend, vin[k], save_volts);  // the first attack out of 2, 3, 4
+      pend &= ~ge[k];
+      in0 |= ge[k];
     }
+    st.save_volts = save_volts;
+    st.state = __float_as_int(pick(in0, __int_as_float(0), __int_as_float(st.state)));
+    d.pend = pend;
+    d.in0 = in0;
   }
   sand = df;
   st.fast_backaverage = back.x;
@@ -532,9 +491,6 @@ __device__ __forceinline__ float sam_atan2(float y, float x) {  // ApproxAtan2, 
 // of the NEXT step (index arithmetic, four table reads, two interpolations) are evaluated while this step's
 // products, arctangent (an IEEE division) and loop filter run: two independent dependency chains per iteration
 // instead of one twice as long.  Same operations on the same values as the loop as written.
-#ifndef T41RX_SAM_DEFER
-#define T41RX_SAM_DEFER 1  // 0: the compiler's own placement of the interpolation (A/B)
-#endif
 struct SamPll {
   const float *T;  // arm_sin_f32's table (LDS)
   float omega_min, omega_max, g1, g2;
@@ -566,9 +522,7 @@ struct SamPll {
     // every step -- the longest single item of a step on the duty wave, whose fifteen neighbours keep the LDS pipe busy.
     const SamIdx is = sam_table_index_pos(phznext * 0.159154943092f), ic = sam_table_index_pos(phznext * 0.159154943092f + 0.25f);
     const float sa = T[is.index], sb = T[is.index + 1], ca = T[ic.index], cb = T[ic.index + 1];
-#if T41RX_SAM_DEFER
     __builtin_amdgcn_sched_barrier(0);
-#endif
     const float ai = Cos * z.x, bi = Sin * z.x, aq = Cos * z.y, bq = Sin * z.y;
     const float corr0 = +ai + bq, corr1 = -bi + aq;
     const float audio = (ai - bi) + (aq + bq);
@@ -577,9 +531,7 @@ struct SamPll {
     omega2 = __builtin_amdgcn_fmed3f(omega2, omega_min, omega_max);  // Demod.cpp's if / else-if clamp (omega_min < omega_max, no NaNs): one instruction, no branches
     fil_out = g1 * det + omega2;
     phzerror = phznext;
-#if T41RX_SAM_DEFER
     __builtin_amdgcn_sched_barrier(0);
-#endif
     Sin = (1.0f - is.fract) * sa + is.fract * sb;  // sincos(phznext), second half
     Cos = (1.0f - ic.fract) * ca + ic.fract * cb;
     return audio;
@@ -664,30 +616,10 @@ __device__ __forceinline__ void agc_chain(float *sl, CoefPtr cf0, int lane STAMP
 // opaque (so the offsets are small), the requests go out in two batches and the maxima are taken three at a time.
 // (fmaxf: the result does not depend on the order.)
 __device__ __forceinline__ float agc_group_max(const float *p) {
-#if T41RX_AGC_GROUPMAX
-  typedef const __attribute__((address_space(3))) float *LdsFloats;  // (kept an LDS pointer: a laundered generic one is read by flat loads)
-  LdsFloats lp = (LdsFloats)p;
-  asm volatile("" : "+v"(lp));
-  float x[12], y[11];
-#pragma unroll
-  for (int q = 0; q < 12; ++q) x[q] = lp[q];
-  asm volatile("" ::: "memory");
-#pragma unroll
-  for (int q = 0; q < 11; ++q) y[q] = lp[12 + q];
-  asm volatile("" ::: "memory");
-  float m = fmaxf(fmaxf(x[0], x[1]), x[2]);
-#pragma unroll
-  for (int q = 3; q + 1 < 12; q += 2) m = fmaxf(fmaxf(m, x[q]), x[q + 1]);
-  m = fmaxf(m, x[11]);
-#pragma unroll
-  for (int q = 0; q + 1 < 11; q += 2) m = fmaxf(fmaxf(m, y[q]), y[q + 1]);
-  return fmaxf(m, y[10]);
-#else
   float C = p[0];
 #pragma unroll
   for (int q = 1; q <= 22; ++q) C = fmaxf(C, p[q]);
   return C;
-#endif
 }
 
 // v[4 + j] = inverse FFT output sample i = lane + 64 j (the valid half); agst = this lane's
@@ -741,7 +673,7 @@ __device__ __forceinline__ void agc_apply(const cf (&v)[8], float4 agst, float *
     }
   }
   STAMP(19);  // AGC: magnitudes, look-ahead maximum
-  if (kAgcCoop) {
+  {
     __syncthreads();
     STAMP(20);  // AGC: barrier 1
     // wave 0 runs the chains of all the workgroup's channels, one lane per channel (4-wave
@@ -763,10 +695,6 @@ __device__ __forceinline__ void agc_apply(const cf (&v)[8], float4 agst, float *
     STAMP(21);  // AGC: the serial chain (chain wave only)
     __syncthreads();
     STAMP(22);  // AGC: barrier 2 (= waiting for the chain, for the other waves)
-  } else {
-    wave_sync();
-    agc_chain<AL>(lds, cf0, lane STAMP_ARGS);
-    wave_sync();
   }
   {
     const CoefPtr c = fresh_coef(cf0);
@@ -814,8 +742,8 @@ __device__ __forceinline__ void agc_apply(const cf (&v)[8], float4 agst, float *
 //     workgroup scope: the waves of a workgroup share the CU's vector memory path and L1, which
 //     keeps their global accesses in order, so the fences cost an LDS wait and no vmcnt(0).
 // Every value is computed by the same instructions as in agc_apply / agc_chain: bit-identical
-// (tools/agc_pipe_probe.py, tests/test_gpu_parity.py::test_agc_pipelined_equals_barrier_form).
-// Measured (MI355X, 4096 channels x 32 frames, tools/agc_pipe_round.sh, -DT41RX_PIPE_STAT counters in shader-clock
+// (tests/test_gpu_parity.py::test_agc_pipelined_equals_barrier_form).
+// Measured (MI355X, 4096 channels x 32 frames, round 4, -DT41RX_PIPE_STAT counters in shader-clock
 // cycles): 33-34 us per frame against 39-40 for the barrier form.  A chain takes 57-64 k cycles (175-200 per step +
 // staging + ~8 k exposed at its start), a wave's front end 38 k, preparation 9 k, back end 10 k per frame; with
 // the waits and a sixteenth of a chain ~68 k cycles = the measured period at the ~2.1 GHz sustained under this load.
@@ -827,13 +755,7 @@ __device__ __forceinline__ void agc_apply(const cf (&v)[8], float4 agst, float *
 // ------------------------------------------------------------------------------------------
 constexpr int kPipeSlots = 3, kPipeSlotFloats = 1024;  // ring_max -> volts [256] | |popped| [256] | popped re [256] | popped im [256] (AM only)
 constexpr int kPipeFlags = 1008;                        // float index in the table area: ready[3], done, next frame to claim
-#ifndef T41RX_PIPE_CLAIM
-#define T41RX_PIPE_CLAIM 1  // 0: the duty rotates (frame g -> wave g mod channels); measured 1.2 % slower
-#endif
-#ifndef T41RX_PIPE_SPINCAP
-#define T41RX_PIPE_SPINCAP (1 << 20)  // (tools: a build with 1 exercises the time-out report)
-#endif
-constexpr int kPipeSpinCap = T41RX_PIPE_SPINCAP;
+constexpr int kPipeSpinCap = 1 << 20;
 
 // -DT41RX_PIPE_STAT (diagnostic build, tools/build_variant.sh pstat -DT41RX_PIPE_STAT; T41RX_PIPE_STAT=1 prints them when
 // the context is destroyed): 16 cycle counters per wave behind the slots -- [0] chain [1] chains [2] slow blocks [3] waiting
@@ -864,7 +786,7 @@ __device__ __forceinline__ void pipe_wait_ge(const unsigned *p, unsigned target,
 }
 
 // first half of agc_apply: magnitudes, look-ahead maxima; what the chain and the gain need -> slot
-// Round 5, measured and left off (T41RX_PIPE_KEEP_RE = 1 builds it; SSB / NFM, AM needs the imaginary parts too): the popped
+// Round 5, measured and left off (SSB / NFM; AM needs the imaginary parts too): the popped
 // samples' real parts -- written by this lane at the preparation of frame f and read back by the SAME lane at the gain of
 // frame f, two iterations later -- waiting in registers of their owner (a ring of three float4 in the kernel) instead of
 // in the slot, which then holds the chain's operands only: 6 instead of 9 KiB touched per channel, 3 MiB per XCD instead of
@@ -872,13 +794,9 @@ __device__ __forceinline__ void pipe_wait_ge(const unsigned *p, unsigned target,
 // kernel spills 18 instead of 10 VGPRs (up to 40 in the q15 / general variants), runs 29.2 against 29.0 us per frame, and
 // the fabric traffic falls from 1.306 to 1.288 x only: the slots do not stay in L2 next to 3 GB of streamed samples
 // whatever their size (nontemporal accesses keep their lines in the XCD's L2 too), so a smaller cyclic set buys nothing.
-#ifndef T41RX_PIPE_KEEP_RE
-#define T41RX_PIPE_KEEP_RE 0
-#endif
-template <typename AL, bool NEED_IM, bool KEEP_RE = false>
+template <typename AL, bool NEED_IM>
 // arec: the delay line's magnitudes (computed a frame ago as that frame's newest: carried, not recomputed)
-__device__ __forceinline__ float4 agc_prep_pipe(const cf (&v)[8], float4 agst, float2 &arec, float *lds, float *slot, CoefPtr cf0, int lane,
-                                               float4 *re_out = nullptr) {
+__device__ __forceinline__ float4 agc_prep_pipe(const cf (&v)[8], float4 agst, float2 &arec, float *lds, float *slot, CoefPtr cf0, int lane) {
   constexpr int kAgZ = AL::Z, kAgA = AL::A, kAgG = AL::G;
   wave_sync();
   if (lane < 50) *reinterpret_cast<float4 *>(lds + kAgZ + 4 * lane) = agst;
@@ -911,8 +829,7 @@ __device__ __forceinline__ float4 agc_prep_pipe(const cf (&v)[8], float4 agst, f
     cf z[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) z[k] = *reinterpret_cast<const cf *>(lds + kAgZ + 2 * (3 + 4 * lane + k));
-    if (KEEP_RE) *re_out = make_float4(z[0].x, z[1].x, z[2].x, z[3].x);
-    else *reinterpret_cast<float4 *>(slot + 512 + 4 * lane) = make_float4(z[0].x, z[1].x, z[2].x, z[3].x);
+    *reinterpret_cast<float4 *>(slot + 512 + 4 * lane) = make_float4(z[0].x, z[1].x, z[2].x, z[3].x);
     if (NEED_IM) *reinterpret_cast<float4 *>(slot + 768 + 4 * lane) = make_float4(z[0].y, z[1].y, z[2].y, z[3].y);
   }
   // the delay line for the next frame: the newest 100 inputs, kept in registers (lanes 0..49; the state words are the chain's)
@@ -926,21 +843,16 @@ __device__ __forceinline__ float4 agc_prep_pipe(const cf (&v)[8], float4 agst, f
 // streaming traffic of fifteen other waves: several microseconds away.  The duty wave therefore moves them through
 // its own LDS scratch (free between its AGC preparation and its back end) in chunks of 16 steps for all the
 // channels at once -- lane (channel, quarter) loads one float4 of ring_max and one of |popped| per chunk --, requested
-// T41RX_PIPE_AHEAD chunks ahead; the first ones before the wait for the previous frame's chain.
+// kPipeAhead chunks ahead; the first ones before the wait for the previous frame's chain.
 //   grp   : slot (frame g) of the workgroup's first channel; channel c's is kPipeSlots * kPipeSlotFloats * c further
 //   stw0  : the eight state words of the workgroup's first channel, channel c's stride floats further
 //   stage : kPipeStageFloats of LDS
-constexpr int kPipeChunk = 16, kPipeChStride = 52;  // (T41RX_AGC_PHASED=0) per channel in the stage: ring_max -> volts [16] | (b x) pairs [32] | 4 pad
-constexpr int kPipeChStrideP = 36;                  // per channel and half: ring_max [16] | |popped| [16] | 4 pad (conflict-free float4 rows)
+constexpr int kPipeChunk = 16;
+constexpr int kPipeChStrideP = 36;  // per channel and half: ring_max [16] | |popped| [16] | 4 pad (conflict-free float4 rows)
 constexpr int kPipeHalfFloats = 16 * kPipeChStrideP;
-#ifndef T41RX_AGC_PHASED
-#define T41RX_AGC_PHASED 1
-#endif
-constexpr int kPipeStageFloats = T41RX_AGC_PHASED ? 2 * kPipeHalfFloats : 16 * kPipeChStride;
-#ifndef T41RX_PIPE_AHEAD
-#define T41RX_PIPE_AHEAD 2  // chunks requested ahead (measured: 1, 2, 3, 4 within 1 %; 6 spills and is 23 % slower)
-#endif
-#if T41RX_AGC_PHASED
+constexpr int kPipeStageFloats = 2 * kPipeHalfFloats;
+// chunks requested ahead (measured: 1, 2, 3, 4 within 1 %; 6 spills and is 23 % slower)
+constexpr int kPipeAhead = 2;
 // Round 4: the chunk's operands are staged ONE CHUNK AHEAD into the other half of a double buffer (ring maxima and the raw
 // |popped| -- 36 floats per channel and half instead of 52 with the two products, which the chain forms itself: one
 // v_pk_mul_f32 per step, off the dependent path), so no block waits for an LDS write -> read round trip any more (the first
@@ -1103,149 +1015,14 @@ __device__ __forceinline__ void agc_chain_pipe(float *grp, float *stw0, size_t s
   PIPE_STAT_INC(7, acc_comp);
 #endif
 }
-#else
-__device__ __forceinline__ void agc_chain_pipe(float *grp, float *stw0, size_t stride, float *stage, const unsigned *done, unsigned g,
-                                               int nvalid, CoefPtr cf0, int lane, unsigned long long *pipe_stat, unsigned *err) {
-  const CoefPtr c = fresh_coef(cf0);
-  AgcConsts gc;
-  gc.attack_mult = c->agc[kAgcAttackMult];
-  gc.decay_mult = c->agc[kAgcDecayMult];
-  gc.fast_decay_mult = c->agc[kAgcFastDecayMult];
-  gc.hang_decay_mult = c->agc[kAgcHangDecayMult];
-  gc.onemfast_backmult = c->agc[kAgcOnemFastBackmult];
-  gc.onemhang_backmult = c->agc[kAgcOnemHangBackmult];
-  gc.min_volts = c->agc[kAgcMinVolts];
-  gc.hang_level = c->agc[kAgcHangLevel];
-  gc.pop_ratio = c->agc[kAgcPopRatio];
-  gc.hang_count = (int)c->agc[kAgcHangCount];
-  float fast_backmult = c->agc[kAgcFastBackmult], hang_backmult = c->agc[kAgcHangBackmult];
-  asm volatile("" : "+v"(fast_backmult), "+v"(hang_backmult));
-  const int ch = (nvalid == 16) ? (lane & 15) : (lane & 15) % nvalid;  // this lane's channel, as a loader and as a chain
-  const int q = lane >> 4;                                              // the float4 of a chunk it moves
-  float *gsrc = grp + (size_t)ch * (kPipeSlots * kPipeSlotFloats) + 4 * q;
-  float *sw = stage + ch * kPipeChStride;
-  constexpr int AH = T41RX_PIPE_AHEAD;
-  float4 pr[AH], pa[AH];
-#pragma unroll
-  for (int u = 0; u < AH; ++u) {
-    pr[u] = *reinterpret_cast<const float4 *>(gsrc + kPipeChunk * u);
-    pa[u] = *reinterpret_cast<const float4 *>(gsrc + 256 + kPipeChunk * u);
-  }
-  {
-    PIPE_STAT_T0();
-    pipe_wait_ge(done, g, err);  // the previous frame's chain has left the state words
-    PIPE_STAT_ADD(4);
-  }
-  PIPE_STAT_T0();
-  float *stw = stw0 + (size_t)ch * stride;
-  const float4 sf = *reinterpret_cast<const float4 *>(stw);
-  const int4 si = *reinterpret_cast<const int4 *>(stw + 4);
-#ifdef T41RX_PIPE_STAT
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (lane == 0) pipe_stat[12] += __builtin_readcyclecounter() - pipe_t0;  // the state words' (and every older request's) round trip
-#endif
-  AgcState st{sf.x, sf.y, sf.z, sf.w, si.x, si.y, si.z};
-  AgcLane d = agc_lane_of(st, gc);
-#ifdef T41RX_PIPE_STAT
-  unsigned long long acc_stage = 0, acc_comp = 0, acc_slow = 0;
-#endif
-  // (rolled loops: one copy of the four-step block -- ~1300 instructions -- instead of sixteen; the register ring
-  // of requested chunks rotates by moves.  Measured: the inner loop unrolled, four copies, runs 12 % faster per step
-  // and the kernel 6 % slower (two copies: 1.5 % slower) -- the other waves' front and back ends share the instruction cache)
-#pragma nounroll
-  for (int k = 0; k < 256 / kPipeChunk; ++k) {
-    {
-      const float4 r4c = pr[0], a4c = pa[0];
-#pragma unroll
-      for (int u = 0; u + 1 < AH; ++u) {
-        pr[u] = pr[u + 1];
-        pa[u] = pa[u + 1];
-      }
-      if (k + AH < 256 / kPipeChunk) {
-        pr[AH - 1] = *reinterpret_cast<const float4 *>(gsrc + kPipeChunk * (k + AH));
-        pa[AH - 1] = *reinterpret_cast<const float4 *>(gsrc + 256 + kPipeChunk * (k + AH));
-      }
-      wave_sync();
-#ifdef T41RX_PIPE_STAT
-      const unsigned long long ts0 = __builtin_readcyclecounter();
-#endif
-      *reinterpret_cast<float4 *>(sw + 4 * q) = r4c;
-      {
-#pragma clang fp contract(off)
-        *reinterpret_cast<float4 *>(sw + 16 + 8 * q) = make_float4(fast_backmult * a4c.x, hang_backmult * a4c.x, fast_backmult * a4c.y, hang_backmult * a4c.y);
-        *reinterpret_cast<float4 *>(sw + 16 + 8 * q + 4) = make_float4(fast_backmult * a4c.z, hang_backmult * a4c.z, fast_backmult * a4c.w, hang_backmult * a4c.w);
-      }
-      wave_sync();
-#ifdef T41RX_PIPE_STAT
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      acc_stage += __builtin_readcyclecounter() - ts0;  // staging the chunk's operands
-#endif
-    }
-#ifdef T41RX_PIPE_STAT
-    const unsigned long long ts1 = __builtin_readcyclecounter();
-#endif
-    // The next block's operands are requested at the top of a block and taken over at its END, behind the four steps:
-    // by then they have long landed.  (Round 3 took them over at the top of the next block, i.e. waited out an LDS round
-    // trip per block behind fifteen other waves' traffic; the request is unconditional -- the last block re-reads its
-    // own -- so the registers are not a merge of old and new values.)
-    float4 r4 = lds4(sw), pa4 = lds4(sw + 16), pb4 = lds4(sw + 20);
-#pragma nounroll
-    for (int b = 0; b < 4; ++b) {
-      const int bn = b < 3 ? b + 1 : 3;
-      float4 nr4 = lds4(sw + 4 * bn), npa = lds4(sw + 16 + 8 * bn), npb = lds4(sw + 16 + 8 * bn + 4);
-      const float rm[4] = {r4.x, r4.y, r4.z, r4.w};
-      const float pf[4] = {pa4.x, pa4.z, pb4.x, pb4.z}, ph[4] = {pa4.y, pa4.w, pb4.y, pb4.w};
-      float vo[4];
-      AgcState t = st;
-      AgcLane dt = d;
-      const lanemask ok = agc_block(t, dt, st, d, gc, rm, pf, ph, vo);
-      if (~ok != 0) {
-#ifdef T41RX_PIPE_STAT
-        acc_slow += 1;
-#endif
-        if (((~ok >> lane) & 1ull) != 0) {
-          t = st;
-          agc_slow_block(t, gc, rm, pf, ph, vo);
-        }
-        dt = agc_lane_of(t, gc);
-      }
-      st = t;
-      d = dt;
-      *reinterpret_cast<float4 *>(sw + 4 * b) = make_float4(vo[0], vo[1], vo[2], vo[3]);  // (every lane of a channel writes the same)
-      asm volatile("" : "+v"(vo[3]));  // (the take-over below stays behind the steps)
-      r4 = nr4;
-      pa4 = npa;
-      pb4 = npb;
-    }
-    wave_sync();
-#ifdef T41RX_PIPE_STAT
-    acc_comp += __builtin_readcyclecounter() - ts1;  // the chunk's 16 steps
-#endif
-    *reinterpret_cast<float4 *>(gsrc + kPipeChunk * k) = lds4(sw + 4 * q);  // volts in ring_max's place
-  }
-  if (lane < nvalid) {
-    *reinterpret_cast<float4 *>(stw) = make_float4(st.fast_backaverage, st.hang_backaverage, st.volts, st.save_volts);
-    *reinterpret_cast<int4 *>(stw + 4) = make_int4(st.state, st.decay_type, st.hang_counter, 0);
-  }
-  PIPE_STAT_ADD(0);
-  PIPE_STAT_INC(1, 1);
-  PIPE_STAT_INC(5, 64);
-#ifdef T41RX_PIPE_STAT
-  PIPE_STAT_INC(2, acc_slow);
-  PIPE_STAT_INC(6, acc_stage);
-  PIPE_STAT_INC(7, acc_comp);
-#endif
-}
-
-#endif
 
 // last part of agc_apply: og[k] = popped sample 4 lane + k times the gain from volts
 struct AgcGainIn { float4 vv, zr, zi; };  // requested ahead of the AGC preparation of the front end's frame, which hides the round trip
-template <bool NEED_IM, bool KEEP_RE = false>
-__device__ __forceinline__ AgcGainIn agc_gain_request(const float *slot, int lane, float4 re_kept = make_float4(0, 0, 0, 0)) {
+template <bool NEED_IM>
+__device__ __forceinline__ AgcGainIn agc_gain_request(const float *slot, int lane) {
   AgcGainIn r;
   r.vv = *reinterpret_cast<const float4 *>(slot + 4 * lane);
-  r.zr = KEEP_RE ? re_kept : *reinterpret_cast<const float4 *>(slot + 512 + 4 * lane);
+  r.zr = *reinterpret_cast<const float4 *>(slot + 512 + 4 * lane);
   r.zi = make_float4(0, 0, 0, 0);
   if (NEED_IM) r.zi = *reinterpret_cast<const float4 *>(slot + 768 + 4 * lane);
   return r;
@@ -1282,7 +1059,7 @@ __device__ __forceinline__ void sam_chain_pipe(float *grp, float *ms0, size_t st
   const int q = lane >> 4;
   float *gsrc = grp + (size_t)ch * (kPipeSlots * kPipeSlotFloats);
   float *sw = stage + kPipeSamZ + ch * kPipeSamStride;
-  constexpr int AH = T41RX_PIPE_AHEAD;
+  constexpr int AH = kPipeAhead;
   float4 p0[AH], p1[AH];  // a chunk = 16 complex = 8 float4 per channel: this lane moves float4 q and q + 4
 #pragma unroll
   for (int u = 0; u < AH; ++u) {

@@ -53,58 +53,27 @@
 #include "rx_kernels.hpp"
 #include "wave_fft.hpp"
 
-// T41RX_AGC_GROUPMAX=1: the look-ahead window's 23 group maxima requested in two batches instead of pair by pair
-// (round 5: twelve LDS round trips fewer per frame and no faster, profiles/r05_ab_saddr4_modes.txt; off)
-#ifndef T41RX_AGC_GROUPMAX
-#define T41RX_AGC_GROUPMAX 0
-#endif
-// T41RX_KEEP_PL=0: the lane's part of the oscillator phases worked out per frame (A/B builds)
-#ifndef T41RX_KEEP_PL
-#define T41RX_KEEP_PL 1
-#endif
-// T41RX_DEC1_REGTAIL=0: the /4 decimator reads its whole window from LDS, the lane's own eight samples included (A/B builds)
-#ifndef T41RX_DEC1_REGTAIL
-#define T41RX_DEC1_REGTAIL 1
-#endif
-// T41RX_DEC1_REGTAIL_AGC=1: the same in the kernels with the AGC (measured: neutral to 1 % slower)
-#ifndef T41RX_DEC1_REGTAIL_AGC
-#define T41RX_DEC1_REGTAIL_AGC 0
-#endif
-// T41RX_SAM_SCAN_FUSED / T41RX_SAM_KEEP_PL = 1: the fused scan steps / the kept phase product in the SAM kernel (without the AGC) too
-// (measured: 56.1 -> 56.9 -> 58.7 us per frame with one, with both: the registers cost more than the instructions save)
-#ifndef T41RX_SAM_SCAN_FUSED
-#define T41RX_SAM_SCAN_FUSED 0
-#endif
-#ifndef T41RX_SAM_KEEP_PL
-#define T41RX_SAM_KEEP_PL 0
-#endif
-// T41RX_WRITELANE=0: a scalar goes into one lane of a register by move + compare + select (A/B builds)
-#ifndef T41RX_WRITELANE
-#define T41RX_WRITELANE 1
-#endif
-// T41RX_SCAN_DPP=0: the DC high-pass scan's steps inside the rows as moves + packed multiply-adds (A/B builds)
-#ifndef T41RX_SCAN_DPP
-#define T41RX_SCAN_DPP 1
-#endif
+// Measured and left off (round 5; the forms are in the repository's history):
+// - the AGC look-ahead window's 23 group maxima requested in two batches instead of pair by pair: twelve LDS round trips
+//   fewer per frame and no faster (profiles/r05_ab_saddr4_modes.txt)
+// - the /4 decimator's window kept in registers (dec1 section) in the kernels with the AGC too: neutral to 1 % slower
+// - the fused scan steps / the kept phase product in the SAM kernel (without the AGC) too: 56.1 -> 56.9 -> 58.7 us per
+//   frame with one, with both (the registers cost more than the instructions save)
 
 namespace t41 {
 
 // ------------------------------------------------------------------------------------------
 // small device helpers
 // ------------------------------------------------------------------------------------------
-// (T41RX_ABLATE / T41RX_LOO / T41RX_CUT: timing experiments with wrong results, rx_experiments.hpp)
 // Fused kernel: how many of the next frame's sub-blocks are requested during the current frame
 // (0: none, 1: sub-block 0 + the I tail, 2: sub-blocks 0 and 1 + the I tail).  Each one costs 16
 // registers that stay live through the back end.
-#ifndef T41RX_PIPE_PF
-#define T41RX_PIPE_PF 0  // AGC: 2 is 2.4 % slower (212 bytes of scratch per lane, spilled and reloaded every frame), 1 (108 bytes)
-#endif                   // and 0 (28 bytes) run alike, and 0 moves 1.31 instead of 1.55 x the algorithmic bytes
-#ifndef T41RX_PIPE_PF_SAM
-#define T41RX_PIPE_PF_SAM 1  // (the synchronous detector: 0 is 2 % slower)
-#endif
-#ifndef T41RX_PF
-#define T41RX_PF 2
-#endif
+constexpr int kPrefetch = 2;
+// With the pipelined AGC chain: 2 is 2.4 % slower (212 bytes of scratch per lane, spilled and reloaded every frame), 1 (108
+// bytes) and 0 (28 bytes) run alike, and 0 moves 1.31 instead of 1.55 x the algorithmic bytes.
+constexpr int kPrefetchPipe = 0;
+// With the pipelined synchronous detector: 0 is 2 % slower.
+constexpr int kPrefetchPipeSam = 1;
 
 // Issue priority falls as a wave advances through its frame (3: loads, mixer, decimators; 2:
 // FFTs and demodulator; 0: interpolators and stores), so the waves sharing a SIMD progress evenly
@@ -118,32 +87,11 @@ namespace t41 {
 // (round 5, measured and left off: a static bias by wave age.  The arbiter favours the oldest wave of a SIMD; stamps give the
 //  four generations of a 16-wave workgroup lifetimes of 627 / 645 / 664 / 673 us in a 693 us launch, profiles/r05_wave_spread.txt.
 //  1: the younger half one level up in the last two thirds of the frame; 2: the older half one level down in the first two.)
-#ifndef T41RX_PRIO_AGE
-#define T41RX_PRIO_AGE 0
-#endif
-#ifndef T41RX_FRESH
-#define T41RX_FRESH 1
-#endif
-// experiment: a 1024-float output transposition in two halves (64-byte store segments)
-#ifndef T41RX_X_HALFTR
-#define T41RX_X_HALFTR 0
-#endif
-#if T41RX_FRESH
 #define FRESH_LANE() asm volatile("" : "+v"(lane))
-#else
-#define FRESH_LANE() do {} while (0)
-#endif
 // The same for the wave index (round 5, the long-FFT one-kernel form): hipcc hoists every `row base + k * 0x100` derived from it out
 // of the frame loop as a loop invariant, runs out of SGPRs, spills the lot to VGPR lanes and reads each back with a
 // v_readlane_b32 -- a VALU instruction for what one s_add_i32 recomputes for free.
-#ifndef T41RX_FRESH_WV
-#define T41RX_FRESH_WV 1
-#endif
-#if T41RX_FRESH_WV
 #define FRESH_WV(w) asm volatile("" : "+s"(w))
-#else
-#define FRESH_WV(w) do {} while (0)
-#endif
 
 // Diagnostic build only (-DT41RX_STAMP): s_memtime stamps at phase boundaries; lane p of each wave
 // accumulates the cycles of phase p and writes them behind the demod debug tap at the end.
@@ -181,21 +129,8 @@ __device__ __forceinline__ void fft512_ldstw(cf (&v)[8], const cf *tw1l, const c
     const cf w = tw1l[64 * (q - 1)];
     v[q] = INV ? cmulc(v[q], w) : cmul(v[q], w);
   }
-#if T41RX_FFT_X1_PERM
   fft_exchange1_perm(v);
   mid();
-#else
-  wave_sync();
-#pragma unroll
-  for (int q = 0; q < 8; ++q) xb[q * kFftRow + lane] = v[q];
-  wave_sync();
-  mid();
-  {
-    const int l1 = lane & 7, q = lane >> 3;
-#pragma unroll
-    for (int k2 = 0; k2 < 8; ++k2) v[k2] = xb[q * kFftRow + l1 + 8 * k2];
-  }
-#endif
   dft8<INV>(v);
 #pragma unroll
   for (int q = 1; q < 8; ++q) {
@@ -233,21 +168,8 @@ __device__ __forceinline__ void fft512_ldstw_x2(cf (&v)[8], cf (&u)[8], const cf
     v[q] = INV ? cmulc(v[q], w) : cmul(v[q], w);
     u[q] = INV ? cmulc(u[q], w) : cmul(u[q], w);
   }
-#if T41RX_FFT_X1_PERM
   fft_exchange1_perm(v);
   fft_exchange1_perm(u);
-#else
-  wave_sync();
-#pragma unroll
-  for (int q = 0; q < 8; ++q) xv[q * kFftRow + lane] = v[q];
-#pragma unroll
-  for (int q = 0; q < 8; ++q) xu[q * kFftRow + lane] = u[q];
-  wave_sync();
-#pragma unroll
-  for (int k2 = 0; k2 < 8; ++k2) v[k2] = xv[q3 * kFftRow + l1 + 8 * k2];
-#pragma unroll
-  for (int k2 = 0; k2 < 8; ++k2) u[k2] = xu[q3 * kFftRow + l1 + 8 * k2];
-#endif
   dft8<INV>(v);
   dft8<INV>(u);
 #pragma unroll
@@ -300,7 +222,7 @@ __device__ __forceinline__ f2 hp_scan(f2 B, float m15, float m31) {
   constexpr HpTab<n> T{};
   // (FUSED: four more VGPRs hold the steps' multipliers -- the AGC / SAM kernels, which sit at the 128-register limit,
   // spill for it and keep the moves)
-  if (FUSED && T41RX_SCAN_DPP) {
+  if (FUSED) {
     // (round 5: the four steps inside the rows the same way -- two v_fmac_f32_dpp instead of two v_mov_b32_dpp and a
     // packed multiply-add; the same fused operations on the same operands, so the same bits)
     float sx = B.x, sy = B.y;
@@ -439,21 +361,13 @@ __device__ __forceinline__ float4 lds4(const float *p) { return *reinterpret_cas
 // "whatever is in the registers": the start value of a float4 that some lanes load under a condition and the same lanes
 // use under the same condition behind a wave_sync().  With zeros as the start value the compiler has to write them (it
 // cannot see through the fence that the other lanes' values are never read): 33 v_mov_b32 v, 0 per SSB frame, round 5.
-// T41RX_ZERO_INIT=1: zeros (A/B builds).
-#ifndef T41RX_ZERO_INIT
-#define T41RX_ZERO_INIT 0
-#endif
 __device__ __forceinline__ float4 any_float4() {
-#if T41RX_ZERO_INIT
-  return make_float4(0, 0, 0, 0);
-#else
   // (an undefined value on purpose; __builtin_nondeterministic_value() would do, but a frozen undef is lowered to 0)
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wuninitialized"
   float4 t;
   return t;
 #pragma clang diagnostic pop
-#endif
 }
 // streaming (read-once / write-once) global accesses: nontemporal, so they do not evict the
 // per-channel state and the constant tables from L2 / Infinity Cache
@@ -472,25 +386,12 @@ __device__ __forceinline__ void stg_stream(float *p, float4 v) {
 // widening in the request's own basic block (hence fresh_off(): a widened offset is hoisted and shared otherwise, and the
 // selector, which works block by block, then sees a 64-bit register, not a zext); and the base an opaque scalar, or
 // neighbouring requests' addresses are merged into one 64-bit VGPR sum + immediates again.
-// T41RX_SADDR=0: the previous address form (A/B builds).
-#ifndef T41RX_SADDR
-#define T41RX_SADDR 1
-#endif
-// T41RX_PHASE_SPLIT=0: the oscillator phases of a frame as round 4 worked them out (A/B builds)
-#ifndef T41RX_PHASE_SPLIT
-#define T41RX_PHASE_SPLIT 1
-#endif
-#ifndef T41RX_SADDR_BASE
-#define T41RX_SADDR_BASE 1
-#endif
 struct LaneOff {
   unsigned bytes;
 };
 __device__ __forceinline__ LaneOff fresh_off(int floats) {  // one per group of requests that share the lane offset
   unsigned o = (unsigned)floats * 4u;
-#if T41RX_SADDR
   asm volatile("" : "+v"(o));
-#endif
   return LaneOff{o};
 }
 typedef __attribute__((address_space(1))) char *GlobalBytes;
@@ -499,66 +400,40 @@ typedef const __attribute__((address_space(1))) f4n *CGlobalF4;
 typedef __attribute__((address_space(1))) f4n *GlobalF4;
 __device__ __forceinline__ CGlobalBytes global_at(const float *ubase, LaneOff o) {
   CGlobalBytes b = (CGlobalBytes)(ubase);
-#if T41RX_SADDR_BASE
   asm("" : "+s"(b));
-#endif
   return b + o.bytes;
 }
 __device__ __forceinline__ GlobalBytes global_at(float *ubase, LaneOff o) {
   GlobalBytes b = (GlobalBytes)(ubase);
-#if T41RX_SADDR_BASE
   asm("" : "+s"(b));
-#endif
   return b + o.bytes;
 }
 // (imm: a compile-time number of floats on top, for the request's immediate-offset field: up to 1023)
 __device__ __forceinline__ float4 ldg_stream(const float *ubase, LaneOff o, int imm = 0) {
-#if T41RX_SADDR
   const f4n t = __builtin_nontemporal_load((CGlobalF4)(global_at(ubase, o) + 4 * imm));
   return make_float4(t.x, t.y, t.z, t.w);
-#else
-  return ldg_stream(reinterpret_cast<const float *>(reinterpret_cast<const char *>(ubase) + (int)o.bytes) + imm);
-#endif
 }
 __device__ __forceinline__ void stg_stream(float *ubase, LaneOff o, float4 v) {
-#if T41RX_SADDR
   __builtin_nontemporal_store(f4n{v.x, v.y, v.z, v.w}, (GlobalF4)global_at(ubase, o));
-#else
-  stg_stream(reinterpret_cast<float *>(reinterpret_cast<char *>(ubase) + (int)o.bytes), v);
-#endif
 }
 __device__ __forceinline__ float2 ldg2(const float2 *ubase, unsigned idx) {  // ubase[idx] of a wave-uniform table
-#if T41RX_SADDR
   typedef float f2n __attribute__((ext_vector_type(2)));
   CGlobalBytes b = (CGlobalBytes)(ubase);
-#if T41RX_SADDR_BASE
   asm("" : "+s"(b));
-#endif
   unsigned o = idx * 8u;
   asm volatile("" : "+v"(o));  // (or zext(trunc(P >> 56) * 8) becomes a 64-bit and(P >> 53, 0x7f8): no zext left to select)
   const f2n t = *(const __attribute__((address_space(1))) f2n *)(b + o);
   return make_float2(t.x, t.y);
-#else
-  return ubase[(int)idx];
-#endif
 }
 // the 8-byte entry at ubase + o (+ imm entries: compile-time, for the offset field, up to 511) of a wave-uniform table
 __device__ __forceinline__ f2 ldg_cf(const f2 *ubase, LaneOff o, int imm = 0) {
   typedef float f2n __attribute__((ext_vector_type(2)));
-#if T41RX_SADDR
   const f2n t = *(const __attribute__((address_space(1))) f2n *)(global_at(reinterpret_cast<const float *>(ubase), o) + 8 * imm);
-#else
-  const f2n t = *reinterpret_cast<const f2n *>(reinterpret_cast<const char *>(ubase) + (int)o.bytes + 8 * imm);
-#endif
   return f2{t.x, t.y};
 }
 __device__ __forceinline__ float4 ldg4(const float *ubase, LaneOff o) {  // (ordinary, cached load)
-#if T41RX_SADDR
   const f4n t = *(CGlobalF4)global_at(ubase, o);
   return make_float4(t.x, t.y, t.z, t.w);
-#else
-  return *reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(ubase) + (int)o.bytes);
-#endif
 }
 
 // the two q15 samples packed in one 32-bit word, as floats (exact)
@@ -587,18 +462,10 @@ constexpr int kCoDec1 = offsetof(DevCoef, dec1) / 4, kCoDec2 = offsetof(DevCoef,
 // loops are unrolled -- is added behind the laundering, so it becomes the s_load's immediate.  Laundering the sum made
 // hipcc materialise one 64-bit pointer per chunk, hoist all twelve of them out of the frame loop, spill them to lanes of a
 // VGPR and read them back with two v_readlane_b32 each: 50 VALU instructions per frame and 26 SGPRs, ISA of round 4's kernel.)
-#ifndef T41RX_TAPS_SUM
-#define T41RX_TAPS_SUM 0
-#endif
 template <int N>
 __device__ __forceinline__ void load_taps(float (&dst)[N], CFloatPtr base, int off) {
-#if T41RX_TAPS_SUM  // (A/B: round 4's form)
-  CFloatPtr p = base + off;
-  asm volatile("" : "+s"(p));
-#else
   asm volatile("" : "+s"(base));
   const CFloatPtr p = base + off;
-#endif
   static_assert(N % 4 == 0, "tap chunks are multiples of 4");
   int i = 0;
 #pragma unroll
@@ -629,27 +496,14 @@ __device__ __forceinline__ void load_taps(float (&dst)[N], CFloatPtr base, int o
 // values are consumed right after their load, taps arrive in 8-wide scalar-load chunks just
 // before first use, and the accumulators are pinned every GROUP loads so the compiler cannot
 // hoist the whole window into registers.
-// one tap on a complex sample: ONE v_pk_fma_f32 (tap broadcast by op_sel), or -- T41RX_FIR_PLAIN, an experiment: is the
-// packed form the cheaper one for a chip that holds its clock down under this kernel? -- two v_fma_f32 (same roundings)
-#ifndef T41RX_FIR_PLAIN
-#define T41RX_FIR_PLAIN 0
-#endif
+// one tap on a complex sample: ONE v_pk_fma_f32 (tap broadcast by op_sel)
 __device__ __forceinline__ cf fir_mac(float tap, cf x, cf acc) {
-#if T41RX_FIR_PLAIN
-  cf r;
-  asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r.x) : "s"(tap), "v"(x.x), "v"(acc.x));
-  asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r.y) : "s"(tap), "v"(x.y), "v"(acc.y));
-  return r;
-#else
   return pk_fma(splat(tap), x, acc);
-#endif
 }
-// (T41RX_LOO 13 / 14, timing experiments: the /2 / the /4 decimator's window taken from registers `regsrc` instead of
-// LDS -- the arithmetic kept, the LDS reads gone: what would a decimator that needs no window reads be worth?)
 // (TAIL0, `tail`: round 5 -- the window's loads from TAIL0 on are the lane's OWN newest samples, which it still holds in
 // registers: taken from there, the same values, and the LDS reads are not issued)
 template <int NT, int OFF0, int OFF1, int NLOAD, int GROUP, int TAIL0 = 1 << 20, typename IDX>
-__device__ __forceinline__ void fir_pair(const float *win, IDX idx, CoefPtr coef, int taps, cf &acc0, cf &acc1, const cf *regsrc = nullptr,
+__device__ __forceinline__ void fir_pair(const float *win, IDX idx, CoefPtr coef, int taps, cf &acc0, cf &acc1,
                                          const cf *tail = nullptr) {
   constexpr int NTP = (NT + 7) & ~7;
   float tc[NTP];
@@ -659,8 +513,7 @@ __device__ __forceinline__ void fir_pair(const float *win, IDX idx, CoefPtr coef
   for (int l = 0; l < NLOAD; ++l) {
     if (l > 0 && (l % GROUP) == 0) asm volatile("" : "+v"(acc0), "+v"(acc1)::"memory");
     float4 t;
-    if (regsrc) t = make_float4(regsrc[(2 * l) & 7].x, regsrc[(2 * l) & 7].y, regsrc[(2 * l + 1) & 7].x, regsrc[(2 * l + 1) & 7].y);
-    else if (tail && l >= TAIL0) t = make_float4(tail[2 * (l - TAIL0)].x, tail[2 * (l - TAIL0)].y, tail[2 * (l - TAIL0) + 1].x, tail[2 * (l - TAIL0) + 1].y);
+    if (tail && l >= TAIL0) t = make_float4(tail[2 * (l - TAIL0)].x, tail[2 * (l - TAIL0)].y, tail[2 * (l - TAIL0) + 1].x, tail[2 * (l - TAIL0) + 1].y);
     else t = lds4(win + 2 * idx(2 * l));
     const cf tv[2] = {cf{t.x, t.y}, cf{t.z, t.w}};
 #pragma unroll

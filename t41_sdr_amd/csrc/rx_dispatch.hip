@@ -12,13 +12,9 @@ int kernel_build_flags() { return kKernelBuildFlags; }
 
 // FFT_LENGTH 512 R (R = 2, 4, 8): front half (R segments per frame) -> N-point fast convolution -> back half
 static hipError_t launch_long(const RxArgs &a, int mode, hipStream_t s) {
-  // FFT_LENGTH 4096, SSB audio with the fixed gain, f32 samples: the whole chain in one kernel (T41RX_FUSE_FRONT=0
-  // or an explicit T41RX_SEG_RUN select the two-kernel pipeline: experiments, and the tests that compare the two)
-  static const bool fuse_front_env = [] {
-    const char *e = std::getenv("T41RX_FUSE_FRONT");
-    return !e || std::atoi(e) != 0;
-  }();
-  if (a.seg == 8 && mode != T41RX_DEMOD_NFM && mode != T41RX_DEMOD_AM && !a.agc && !a.q15 && fuse_front_env && !std::getenv("T41RX_SEG_RUN")) {
+  // FFT_LENGTH 4096, SSB audio with the fixed gain, f32 samples: the whole chain in one kernel (an explicit T41RX_SEG_RUN
+  // selects the two-kernel pipeline: the tests that compare the two)
+  if (a.seg == 8 && mode != T41RX_DEMOD_NFM && mode != T41RX_DEMOD_AM && !a.agc && !a.q15 && !std::getenv("T41RX_SEG_RUN")) {
     return launch_fastconv_fused(a, s);
   }
   hipError_t e = launch_long_front(a, mode, s);
@@ -26,8 +22,7 @@ static hipError_t launch_long(const RxArgs &a, int mode, hipStream_t s) {
   const bool cplx = a.agc || mode == T41RX_DEMOD_AM;
   // real audio with the fixed gain, f32 samples out: the interpolators run behind pass 3 of the
   // fast convolution (no `aud24` round trip, no third kernel)
-  static const bool fuse_env = [] { const char *e = std::getenv("T41RX_FUSE_BACK"); return !e || std::atoi(e) != 0; }();  // experiments
-  const bool fused = !cplx && !a.q15 && fuse_env;
+  const bool fused = !cplx && !a.q15;
   e = launch_fastconv(a, cplx, fused, s);
   if (e != hipSuccess || fused) return e;
   return launch_long_back(a, mode, s);

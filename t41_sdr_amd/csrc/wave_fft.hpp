@@ -96,13 +96,10 @@ __device__ __forceinline__ constexpr int fft_x2(int l1) { return 8 * l1 + (l1 & 
 // swaps -- runs inside the VALU instead of through LDS: v_permlane32_swap (bit 5), v_permlane16_swap (bit 4), and
 // for bit 3 a pair of bank-masked DPP row shifts by 8.  40 VALU instructions per transform in place of 8
 // ds_write_b64 + 8 ds_read_b64 (+ 3 for addresses) and two LDS ordering points.  Measured on MI355X in the fused
-// FFT_LENGTH 512 kernel (interleaved rounds, tools/ablation_table.py, profiles/r03_ablation_ssb.md): 0.9 % faster
-// than the LDS form (-DT41RX_FFT_X1_PERM=0) -- the kernel is co-limited by VALU and LDS, and the LDS relief wins.
+// FFT_LENGTH 512 kernel (interleaved rounds, profiles/r03_ablation_ssb.md): 0.9 % faster than the
+// LDS form -- the kernel is co-limited by VALU and LDS, and the LDS relief wins.
 // The second exchange moves lane bits 0..2 AND swaps the lane's two octal digits; the same trade costs ~85 VALU
 // instructions there (no swap instruction below 16 lanes) and stays in LDS.
-#ifndef T41RX_FFT_X1_PERM
-#define T41RX_FFT_X1_PERM 1
-#endif
 __device__ __forceinline__ void lane_swap32(float &a, float &b) {  // lanes 32..63 of a <-> lanes 0..31 of b
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
   a = __uint_as_float(r[0]);
@@ -161,19 +158,7 @@ __device__ __forceinline__ void fft512(cf (&v)[8], const cf (&tw1)[7], const cf 
 #pragma unroll
   for (int q = 1; q < 8; ++q) v[q] = INV ? cmulc(v[q], tw1[q - 1]) : cmul(v[q], tw1[q - 1]);
   // exchange 1: (reg q, lane l1 + 8 k2) -> (reg k2, lane l1 + 8 q)
-#if T41RX_FFT_X1_PERM
   fft_exchange1_perm(v);
-#else
-  wave_sync();
-#pragma unroll
-  for (int q = 0; q < 8; ++q) xb[q * kFftRow + lane] = v[q];
-  wave_sync();
-  {
-    const int l1 = lane & 7, q = lane >> 3;
-#pragma unroll
-    for (int k2 = 0; k2 < 8; ++k2) v[k2] = xb[q * kFftRow + l1 + 8 * k2];
-  }
-#endif
   dft8<INV>(v);
 #pragma unroll
   for (int q = 1; q < 8; ++q) v[q] = INV ? cmulc(v[q], tw2[q - 1]) : cmul(v[q], tw2[q - 1]);

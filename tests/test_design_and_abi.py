@@ -154,19 +154,19 @@ def test_product_never_touches_the_oracle():
         assert "t41oracle" not in subprocess.run(["ldd", so], capture_output=True, text=True).stdout
 
 
-def test_experiment_builds_are_fenced(T, tmp_path):
-    """the timing-experiment switches that make the kernels compute WRONG results (T41RX_ABLATE, _LOO,
-    _AGC_X, _FCABL) and the diagnostic ones sit behind ONE guard (t41_sdr_amd/csrc/rx_experiments.hpp): without
-    -DT41RX_EXPERIMENT=1 they do not compile, and a library built with them refuses t41rx_create() unless the environment
-    opts in.  Checked here with the dispatch translation unit (no kernels: seconds) linked against the product's objects."""
+def test_diagnostic_builds_are_fenced(T, tmp_path):
+    """the diagnostic switches (T41RX_STAMP, _CLK, _PIPE_STAT: stamps / counters next to the product's
+    values) sit behind ONE guard (t41_sdr_amd/csrc/rx_experiments.hpp): without -DT41RX_EXPERIMENT=1 they do not compile,
+    and a library built with them refuses t41rx_create() unless the environment opts in.  Checked here with the dispatch
+    translation unit (no kernels: seconds) linked against the product's objects."""
     import subprocess
     csrc = os.path.join(ROOT, "t41_sdr_amd", "csrc")
     base = ["hipcc", "-O1", "-std=c++17", "-fPIC", "-fvisibility=hidden", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include")]
-    for flag in ("-DT41RX_ABLATE=3", "-DT41RX_LOO=2", "-DT41RX_AGC_X=1", "-DT41RX_AGC_R04CHECK=1", "-DT41RX_FCABL=2", "-DT41RX_STAMP", "-DT41RX_CLK"):
+    for flag in ("-DT41RX_STAMP", "-DT41RX_CLK", "-DT41RX_PIPE_STAT"):
         r = subprocess.run(base + [flag, "-fsyntax-only", "rx_dispatch.hip"], cwd=csrc, capture_output=True, text=True)
         assert r.returncode != 0 and "T41RX_EXPERIMENT=1" in r.stderr, (flag, r.stderr[-400:])
     obj = str(tmp_path / "rx_dispatch_exp.o")
-    subprocess.check_call(base + ["-DT41RX_EXPERIMENT=1", "-DT41RX_LOO=2", "-c", "rx_dispatch.hip", "-o", obj], cwd=csrc)
+    subprocess.check_call(base + ["-DT41RX_EXPERIMENT=1", "-DT41RX_CLK", "-c", "rx_dispatch.hip", "-o", obj], cwd=csrc)
     objs = [os.path.join(csrc, o) for o in ("rx512_ssb.o", "rx512_am.o", "rx512_nfm.o", "rx512_sam.o", "rx_long.o", "fastconv.o", "display_kernel.o",
                                             "nr_kernels.o", "rx_host.o", "design.o", "nr_tables.o", "tx_kernels.o", "tx_host.o", "tx_tables.o")]
     lib_path = str(tmp_path / "libt41rx_exp.so")
@@ -178,10 +178,29 @@ def test_experiment_builds_are_fenced(T, tmp_path):
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-500:]
     rc, msg = r.stdout.strip().split(" ", 1)
-    assert int(rc) == -2 and "timing experiment" in msg and "T41RX_ALLOW_EXPERIMENT" in msg   # T41RX_ERR_UNSUPPORTED
+    assert int(rc) == -2 and "diagnostics" in msg and "T41RX_ALLOW_EXPERIMENT" in msg   # T41RX_ERR_UNSUPPORTED
     env["T41RX_ALLOW_EXPERIMENT"] = "1"
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
-    assert "EXPERIMENT BUILD" in r.stderr and "WRONG" in r.stderr
-    assert "timing experiment" not in r.stdout   # past the fence (and, without a GPU, on to T41RX_ERR_HIP)
+    assert "EXPERIMENT BUILD" in r.stderr and "diagnostics on" in r.stderr
+    assert "kernel diagnostics" not in r.stdout   # past the fence (and, without a GPU, on to T41RX_ERR_HIP)
     # the product library is not one
     assert T.load().t41rx_abi_version() == 5
+
+
+def test_kernel_sources_carry_no_build_switches():
+    """The kernel sources build one form: the only T41RX_* macros a preprocessor conditional may test are the diagnostic
+    builds' (rx_experiments.hpp).  The A/B switches of rounds 1-5 were folded into the product form; their measurements
+    are in DESIGN.md and profiles/."""
+    allowed = {"T41RX_EXPERIMENT", "T41RX_STAMP", "T41RX_PIPE_STAT", "T41RX_CLK", "T41RX_DIAGNOSTICS"}
+    csrc = os.path.join(ROOT, "t41_sdr_amd", "csrc")
+    found = []
+    for name in sorted(os.listdir(csrc)):
+        if os.path.splitext(name)[1] not in (".hpp", ".hip", ".cpp", ".h"):
+            continue
+        with open(os.path.join(csrc, name)) as f:
+            for no, line in enumerate(f, 1):
+                if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                    for macro in re.findall(r"\bT41RX_\w+", line.split("//")[0]):
+                        if macro not in allowed:
+                            found.append("%s:%d: %s" % (name, no, line.strip()))
+    assert not found, found

@@ -284,8 +284,9 @@ def test_agc_restored_below_min_volts_in_fast_decay(T, agcmode):
     volts <= save_volts < min_volts.  DSP_Fn.cpp:579-594 leaves the fast decay at the very first step (volts is not above
     save_volts) -- to the hang, the slow or the hang decay, by hang counter and decay type -- and :629 then lifts volts to
     min_volts.  A short-cut that looks at the last step of a four-step block only sees min_volts > save_volts and keeps
-    the lane in state 1 (round 4's did: tools/build_variant.sh r04check -DT41RX_AGC_R04CHECK=1 fails this test, and
-    tools/pipe_soak.py finds it within seconds).  Pipelined form == barrier form, outputs and checkpoints."""
+    the lane in state 1 (round 4's did: a build of it -- the fenced switch lived in the kernel sources until the A/B
+    switches were folded -- fails this test, and tools/pipe_soak.py finds it within seconds).  Pipelined form == barrier
+    form, outputs and checkpoints."""
     import torch
     nch, nfr = 37, 12
     nco = siggen.nco_grid(nch, seed=191)

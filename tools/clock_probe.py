@@ -11,6 +11,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+os.environ.setdefault("T41RX_ALLOW_EXPERIMENT", "1")  # a diagnostic build: t41rx_create() refuses it otherwise
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import t41_sdr_amd as T  # noqa: E402

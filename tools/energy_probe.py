@@ -7,7 +7,7 @@ instruction stream draws, so variants are to be ranked by JOULES per frame next 
   python tools/energy_probe.py product abl7 abl9 firplain ... [--seconds 14] [--frames 32] [--out gpurun_out/r05_energy_ssb.md]
     NAME = "product" (t41_sdr_amd/libt41rx.so) or a build of tools/build_variant.sh NAME (t41_sdr_amd/abl/libt41rx_NAME.so)
 
-Per build: one child process loops the launch for `--seconds` (tools/ablation_table.py one NAME), this process samples
+Per build: one child process loops the launch for `--seconds` (tools/ab_probe.py one NAME), this process samples
 the board's power sensor at 20 Hz (sysfs hwmon power1_average / power1_input of the card that draws the most while the
 load runs -- the box shows one GPU; `rocm-smi --showpower` as a cross-check when it is there), drops the first 4 s
 (clock ramp) and the last second, and reports W, us per frame, mJ per 4096-channel frame.
@@ -90,12 +90,13 @@ def main():
         env.pop("T41RX_LIB", None)
         if n != "product":
             env["T41RX_LIB"] = os.path.join(ROOT, "t41_sdr_amd", "abl", "libt41rx_%s.so" % n)
+            env["T41RX_ALLOW_EXPERIMENT"] = "1"
             if not os.path.exists(env["T41RX_LIB"]):
                 print("no build %s" % n, flush=True)
                 continue
         reps = int(seconds / (frames * 22e-6))  # ~22 us per frame; the child warms up reps / 4 launches on top
         t0 = time.time()
-        p = subprocess.Popen([sys.executable, os.path.join(ROOT, "tools", "ablation_table.py"), "one", n, "--frames", str(frames), "--reps", str(reps)] + extra,
+        p = subprocess.Popen([sys.executable, os.path.join(ROOT, "tools", "ab_probe.py"), "one", n, "--frames", str(frames), "--reps", str(reps)] + extra,
                              env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         samples = {f: [] for f in sens}
         smi = []

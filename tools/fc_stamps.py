@@ -8,6 +8,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+os.environ.setdefault("T41RX_ALLOW_EXPERIMENT", "1")  # a diagnostic build: t41rx_create() refuses it otherwise
 import t41_sdr_amd as T  # noqa: E402
 
 NAMES = ["tail of the previous frame", "barrier (array free)", "assemble: loads -> LDS", "mask loads issued", "barrier",

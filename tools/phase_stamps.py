@@ -8,6 +8,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+os.environ.setdefault("T41RX_ALLOW_EXPERIMENT", "1")  # a diagnostic build: t41rx_create() refuses it otherwise
 import t41_sdr_amd as T  # noqa: E402
 
 NAMES = ["wait loads + gain", "DC high-pass", "NCO + mix", "LDS stage + /4 FIR", "history rolls", "/2 FIR",

@@ -14,12 +14,12 @@ export T41RX_BENCH_NOCHECK=1   # (the parity replay is bench.py's own business; 
 cd /tmp
 # one un-profiled run first: a fresh box's first seconds of load (clock / power management settling, first-touch of the
 # allocator) otherwise land in the first workload's trace (round 5: 782 us +- 82 per launch there, 693 in the bench minutes later)
-python3 "$ROOT/bench.py" --no-other-workloads --workload ssb --steps 200 --warmup 20 --no-cpu-baseline > $OUT/settle.log 2>&1
+timeout -k 10 300 python3 "$ROOT/bench.py" --no-other-workloads --workload ssb --steps 200 --warmup 20 --no-cpu-baseline > $OUT/settle.log 2>&1 || { echo "settle run failed"; exit 1; }
 for W in $WL; do
   echo "== $W"
-  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$W/trace -o t -- python3 "$ROOT/bench.py" --no-other-workloads --workload $W --steps 30 --warmup 5 --no-cpu-baseline > $OUT/$W.trace.log 2>&1 || echo "trace $W failed"
+  timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$W/trace -o t -- python3 "$ROOT/bench.py" --no-other-workloads --workload $W --steps 30 --warmup 5 --no-cpu-baseline > $OUT/$W.trace.log 2>&1 || { echo "trace $W failed"; exit 1; }
   for C in FETCH_SIZE WRITE_SIZE; do
-    timeout -k 10 240 rocprofv3 --pmc $C --output-format csv -d $OUT/$W/$C -o p -- python3 "$ROOT/bench.py" --no-other-workloads --workload $W --steps 6 --warmup 2 --no-cpu-baseline > $OUT/$W.$C.log 2>&1 || echo "pmc $C $W failed"
+    timeout -k 10 240 rocprofv3 --pmc $C --output-format csv -d $OUT/$W/$C -o p -- python3 "$ROOT/bench.py" --no-other-workloads --workload $W --steps 6 --warmup 2 --no-cpu-baseline > $OUT/$W.$C.log 2>&1 || { echo "pmc $C $W failed"; exit 1; }
   done
   tail -1 $OUT/$W.trace.log | cut -c1-200
 done
@@ -32,7 +32,7 @@ PASSES=(
 i=0
 for CNT in "${PASSES[@]}"; do
   i=$((i+1))
-  timeout -k 10 240 rocprofv3 --pmc $CNT --output-format csv -d $OUT/ssb/sq$i -o p -- python3 "$ROOT/bench.py" --no-other-workloads --workload ssb --steps 6 --warmup 2 --no-cpu-baseline > $OUT/ssb.sq$i.log 2>&1 || echo "sq pass $i failed"
+  timeout -k 10 240 rocprofv3 --pmc $CNT --output-format csv -d $OUT/ssb/sq$i -o p -- python3 "$ROOT/bench.py" --no-other-workloads --workload ssb --steps 6 --warmup 2 --no-cpu-baseline > $OUT/ssb.sq$i.log 2>&1 || { echo "sq pass $i failed"; exit 1; }
 done
 # keep the merge small: per-dispatch traces are not needed, and of the counter CSVs only our kernels' rows
 find $OUT -name "*kernel_trace.csv" -delete
