@@ -12,8 +12,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "eq_kernels.hpp"
@@ -27,38 +29,57 @@
 
 using namespace t41;
 
+namespace {
+// device memory the context owns: freed with its holder (t41rx_destroy: under the context's DeviceGuard)
+struct HipFree {
+  void operator()(void *p) const { (void)hipFree(p); }
+};
+template <class T>
+using DevBuf = std::unique_ptr<T, HipFree>;
+
+// hipMalloc into b; its previous buffer is freed first, and b stays empty when the allocation fails
+template <class T>
+hipError_t dev_alloc(DevBuf<T> &b, size_t bytes) {
+  b.reset();
+  void *p = nullptr;
+  const hipError_t e = hipMalloc(&p, bytes);
+  if (e == hipSuccess) b.reset(static_cast<T *>(p));
+  return e;
+}
+}  // namespace
+
 struct t41rx_ctx {
   int device = 0;
   int nchan = 0;
   t41rx_params params{};
   std::vector<float> blob;       // canonical coefficient blob (host)
   std::vector<int32_t> nco_hz;   // NCOFreq per channel (host)
-  float *d_state = nullptr;      // [nchan][state_floats]
-  DevCoef *d_coef = nullptr;
-  float2 *d_tab = nullptr;
-  ChanNco *d_nco = nullptr;
+  DevBuf<float> d_state;         // [nchan][state_floats]
+  DevBuf<DevCoef> d_coef;
+  DevBuf<float2> d_tab;
+  DevBuf<ChanNco> d_nco;
   float *dbg_nco = nullptr, *dbg_dec = nullptr, *dbg_demod = nullptr;
   float *spect = nullptr, *spect_max = nullptr;  // audio-spectrum side output (t41rx_set_audio_spectrum)
   int tap_frames = 0, spect_frames = 0;          // frames per call those buffers are sized for
   // display FFT side output (t41rx_set_display_spectrum)
   float *disp_spec = nullptr, *disp_old = nullptr;  // caller's buffers
-  float *d_pre = nullptr, *d_disp = nullptr;         // input tap [nchan][disp_frames][4096], state [nchan][kDispFloats]
-  double *d_win = nullptr;
+  DevBuf<float> d_pre, d_disp;                       // input tap [nchan][disp_frames][4096], state [nchan][kDispFloats]
+  DevBuf<double> d_win;
   int disp_frames = 0, disp_zoom = 0;
   // FFT_LENGTH 4096 pipeline: constant table + scratch between its three kernels
-  float2 *d_tab4k = nullptr;
-  float *d_mid = nullptr, *d_aud24 = nullptr;
-  float *d_agc_pipe = nullptr;  // AGC on, FFT_LENGTH 512: the pipelined kernel's slots (RxArgs::agc_pipe), allocated on first use
+  DevBuf<float2> d_tab4k;
+  DevBuf<float> d_mid, d_aud24;
+  DevBuf<char> d_agc_pipe;  // FFT_LENGTH 512, AGC on or SAM: the pipelined kernels' buffer (pipe_layout), allocated on first use
   int scratch_frames = 0;
   int layout = T41RX_LAYOUT_CHANNEL_MAJOR;  // of I / Q / audio (t41rx_set_buffer_layout)
   int nco_sel = 0;               // long FFT: which NcoState copy is current (flips with every process call)
   // noise reduction / notch (Process.cpp:841-866): state of Xanr() and of the two spectral functions, window tables;
   // allocated when a call first needs them
-  float *d_nr_anr = nullptr, *d_nr_spec = nullptr, *d_nr_tab = nullptr;
+  DevBuf<float> d_nr_anr, d_nr_spec, d_nr_tab;
   // noise blanker (NB_on, Process.cpp:873-876; t41rx_set_noise_blanker): AltNoiseBlanking()'s last_frame_end per channel,
   // two slots [2][nchan][kNbCarryPitch] (nb_kernel.hip); allocated when the blanker first runs
   int nb_on = 0;
-  float *d_nb = nullptr;
+  DevBuf<float> d_nb;
   int nb_sel = 0;  // the slot holding the current carry (flips with every blanker launch)
   // receive equalizer (receiveEQFlag, Process.cpp:828-832; t41rx_set_receive_eq): the caller's band table, the levels
   // (EEPROMData.equalizerRec, EEPROM.cpp:59: 100 each), and rec_EQ_Band1_state .. rec_EQ_Band14_state per channel
@@ -67,9 +88,9 @@ struct t41rx_ctx {
   bool eq_have_bands = false;
   float eq_coef[kEqCoefs] = {};
   int32_t eq_levels[kEqBands] = {100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100};
-  float *d_eq = nullptr;
+  DevBuf<float> d_eq;
   // staging for t41rx_process_host
-  float *d_in_i = nullptr, *d_in_q = nullptr, *d_out = nullptr;
+  DevBuf<float> d_in_i, d_in_q, d_out;
   size_t staging_floats = 0;
 };
 
@@ -84,6 +105,7 @@ int fail(int code, const std::string &msg) {
 int hip_fail(hipError_t e, const char *what) {
   return fail(T41RX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
+int hip_check(hipError_t e, const char *what) { return e == hipSuccess ? T41RX_OK : hip_fail(e, what); }
 #define HIP_TRY(expr)                                  \
   do {                                                 \
     hipError_t e__ = (expr);                           \
@@ -142,7 +164,7 @@ int upload_nco(t41rx_ctx *ctx) {
   std::vector<ChanNco> h((size_t)ctx->nchan);
   const int side = (int)blob_view(ctx->blob.data()).scalars[kScSideTone];
   for (int i = 0; i < ctx->nchan; ++i) h[(size_t)i] = make_nco(ctx->nco_hz[(size_t)i], side);
-  HIP_TRY(hipMemcpy(ctx->d_nco, h.data(), sizeof(ChanNco) * h.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ctx->d_nco.get(), h.data(), sizeof(ChanNco) * h.size(), hipMemcpyHostToDevice));
   return T41RX_OK;
 }
 
@@ -163,7 +185,7 @@ int upload_coeffs(t41rx_ctx *ctx) {
   std::memcpy(dc.sc, v.scalars, sizeof(float) * kNumScalars);
   std::memcpy(dc.agc, v.agc, sizeof(float) * kNumAgc);
   std::memcpy(dc.deemph, kDeemphFir24000, sizeof(float) * kDeemphTaps);
-  HIP_TRY(hipMemcpy(ctx->d_coef, &dc, sizeof(dc), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ctx->d_coef.get(), &dc, sizeof(dc), hipMemcpyHostToDevice));
 
   const int R = N / 512;  // 2048-sample segments per frame
   std::vector<float2> tab((size_t)kTabEntries512, make_float2(0.0f, 0.0f));
@@ -188,7 +210,7 @@ int upload_coeffs(t41rx_ctx *ctx) {
         const int k = q + R * m;
         t4[(size_t)((R - 1) * 512 + 512 * q + m)] = make_float2(v.mask[2 * k] * invN, v.mask[2 * k + 1] * invN);
       }
-    HIP_TRY(hipMemcpy(ctx->d_tab4k, t4.data(), sizeof(float2) * t4.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ctx->d_tab4k.get(), t4.data(), sizeof(float2) * t4.size(), hipMemcpyHostToDevice));
   }
   const double two_pi = 6.283185307179586476925286766559;
   for (int q = 1; q < 8; ++q)
@@ -240,17 +262,225 @@ int upload_coeffs(t41rx_ctx *ctx) {
     t[256] = 0.0f;
     t[512] = -0.0f;
   }
-  HIP_TRY(hipMemcpy(ctx->d_tab, tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ctx->d_tab.get(), tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
   return T41RX_OK;
 }
 
-// InitializeDataArrays() + SpectralNoiseReductionInit() (T41_SDR.ino:479-504, 657)
-int reset_nr(t41rx_ctx *ctx) {
-  std::vector<float> anr((size_t)kAnrStRows * (size_t)ctx->nchan), spec((size_t)kNrSpecFloats * (size_t)ctx->nchan);
-  nr_reset_anr(anr.data(), (size_t)ctx->nchan);
-  for (int c = 0; c < ctx->nchan; ++c) nr_reset_record(spec.data() + (size_t)kNrSpecFloats * (size_t)c);
-  HIP_TRY(hipMemcpy(ctx->d_nr_anr, anr.data(), sizeof(float) * anr.size(), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ctx->d_nr_spec, spec.data(), sizeof(float) * spec.size(), hipMemcpyHostToDevice));
+// InitializeDataArrays() + SpectralNoiseReductionInit() (T41_SDR.ino:479-504, 657): Xanr()'s and the spectral functions'
+// memories at power-on
+hipError_t nr_power_on(float *anr, float *spec, int nchan) {
+  std::vector<float> ha((size_t)kAnrStRows * (size_t)nchan), hs((size_t)kNrSpecFloats * (size_t)nchan);
+  nr_reset_anr(ha.data(), (size_t)nchan);
+  for (int c = 0; c < nchan; ++c) nr_reset_record(hs.data() + (size_t)kNrSpecFloats * (size_t)c);
+  const hipError_t e = hipMemcpy(anr, ha.data(), sizeof(float) * ha.size(), hipMemcpyHostToDevice);
+  return e != hipSuccess ? e : hipMemcpy(spec, hs.data(), sizeof(float) * hs.size(), hipMemcpyHostToDevice);
+}
+
+// state and tables of the noise-reduction stages, on first use
+int ensure_nr(t41rx_ctx *ctx) {
+  if (ctx->d_nr_anr) return T41RX_OK;
+  DevBuf<float> anr, spec, tab;
+  if (dev_alloc(anr, sizeof(float) * kAnrStRows * (size_t)ctx->nchan) != hipSuccess ||
+      dev_alloc(spec, sizeof(float) * kNrSpecFloats * (size_t)ctx->nchan) != hipSuccess ||
+      dev_alloc(tab, sizeof(float) * kNrTabFloats) != hipSuccess)
+    return fail(T41RX_ERR_NOMEM, "noise-reduction state allocation failed");
+  float h[kNrTabFloats];
+  nr_make_tables(h);
+  if (hipMemcpy(tab.get(), h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess ||
+      nr_power_on(anr.get(), spec.get(), ctx->nchan) != hipSuccess)
+    return fail(T41RX_ERR_HIP, "noise-reduction state upload failed");
+  ctx->d_nr_anr = std::move(anr);
+  ctx->d_nr_spec = std::move(spec);
+  ctx->d_nr_tab = std::move(tab);
+  return T41RX_OK;
+}
+
+// a stage memory whose power-on value is zero, on first use
+int ensure_zeroed(DevBuf<float> &b, size_t bytes, const char *what) {
+  if (b) return T41RX_OK;
+  DevBuf<float> z;
+  if (dev_alloc(z, bytes) != hipSuccess) return fail(T41RX_ERR_NOMEM, std::string(what) + " state allocation failed");
+  if (hipMemset(z.get(), 0, bytes) != hipSuccess) return fail(T41RX_ERR_HIP, std::string(what) + " state upload failed");
+  b = std::move(z);
+  return T41RX_OK;
+}
+// the noise blanker's carry, both slots (nb_sel stays 0 until the blanker first runs)
+int ensure_nb(t41rx_ctx *ctx) {
+  return ensure_zeroed(ctx->d_nb, sizeof(float) * 2 * kNbCarryPitch * (size_t)ctx->nchan, "noise-blanker");
+}
+// the receive equalizer's biquad memories (Filter.cpp:43-56)
+int ensure_eq(t41rx_ctx *ctx) {
+  return ensure_zeroed(ctx->d_eq, sizeof(float) * kEqStateFloats * (size_t)ctx->nchan, "receive-equalizer");
+}
+
+// The pipelined kernels' buffer (RxArgs::agc_pipe), byte offsets for nchan channels: the first stage's slots, three of
+// 1024 floats per channel (rx_chains.hpp: kPipeSlots, kPipeSlotFloats); blocks of 16 counters for nchan + 16 waves -- a
+// wave's own block in the -DT41RX_PIPE_STAT diagnostic build, and first in the last block the count of waits that ran out
+// (rx_chains.hpp: pipe_wait_ge); then the second stage's slots, as many as the first's (rx512_kernel.hpp, PSA: the
+// synchronous detector behind the AGC runs two chains per frame).  The kernels derive the same offsets from a.nchan.
+struct PipeLayout {
+  size_t counters, timeout, second, bytes;
+};
+PipeLayout pipe_layout(int nchan) {
+  const size_t slots = (size_t)nchan * 3 * 1024 * sizeof(float), block = 16 * sizeof(unsigned long long);
+  const size_t second = slots + ((size_t)nchan + 16) * block;
+  return {slots, second - block, second, second + slots};
+}
+
+// a broken hand-over protocol of the pipelined kernels leaves wrong samples and a count of waits that ran out, not a hung
+// GPU -- reported at the calls that synchronise anyway
+int pipe_timeouts(const t41rx_ctx *ctx) {  // < 0: the counter could not be read
+  if (!ctx->d_agc_pipe) return 0;
+  unsigned n = 0;
+  if (hipMemcpy(&n, ctx->d_agc_pipe.get() + pipe_layout(ctx->nchan).timeout, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess)
+    return -1;
+  return (int)n;
+}
+int pipe_timeouts_clear(t41rx_ctx *ctx) {
+  if (!ctx->d_agc_pipe) return T41RX_OK;
+  HIP_TRY(hipMemset(ctx->d_agc_pipe.get() + pipe_layout(ctx->nchan).timeout, 0, sizeof(unsigned long long)));
+  return T41RX_OK;
+}
+// what the synchronising entry points answer when a wait inside the pipelined kernels has run out
+int pipe_status(const t41rx_ctx *ctx) {
+  const int n = pipe_timeouts(ctx);
+  if (n < 0) return fail(T41RX_ERR_HIP, "could not read the pipelined kernels' time-out counter");
+  if (n > 0)
+    return fail(T41RX_ERR_STATE, "a wait inside the pipelined AGC / SAM kernel ran out: the samples since the last reset or restored checkpoint are not valid");
+  return T41RX_OK;
+}
+
+// ---- checkpoint (t41rx_get_state / t41rx_set_state): header, the path's records, then the sections header word 5 names
+constexpr uint32_t kStateMagic = 0x54343153u;  // "T41S"
+constexpr size_t kStateHeaderBytes = 32;
+constexpr int32_t kSecNr = 1, kSecDisp = 2, kSecNb = 4, kSecEq = 8;
+
+// One checkpoint section: the memories of a stage built for fft_length 512 only.
+struct Section {
+  int32_t bit;                         // in header word 5
+  const char *name;                    // (in the refusals)
+  size_t chan_floats;                  // size per channel
+  bool (*present)(const t41rx_ctx *);  // carried by this context's checkpoints
+  int (*ensure)(t41rx_ctx *);          // allocation on restore, where the stage allocates lazily (or null)
+  int (*check)(const t41rx_ctx *, const int32_t *hdr, const float *sec);  // refusal of a host section (or null)
+  int (*get)(const t41rx_ctx *, void *host, size_t bytes);                // device -> host
+  int (*put)(t41rx_ctx *, const void *host, size_t bytes);                // host -> device
+  int (*reset)(t41rx_ctx *, size_t bytes);                                // power-on of what the context has allocated
+};
+// in bit order
+const Section kSections[] = {
+    // noise reduction / notch: Xanr()'s taps, delay line and leak words [kAnrStRows][n_channels], then the Kim / spectral
+    // records [n_channels][kNrSpecFloats] (Noise.cpp:19-56) -- present once the stages have run
+    {kSecNr, "noise-reduction", (size_t)kAnrStRows + (size_t)kNrSpecFloats,
+     [](const t41rx_ctx *c) { return c->d_nr_anr != nullptr; }, ensure_nr,
+     [](const t41rx_ctx *c, const int32_t *, const float *anr) {
+       // what the kernels index with or divide by (nr_kernels.hip): Xanr()'s leak index, the spectral functions' ring pointers
+       const float *spec = anr + (size_t)kAnrStRows * (size_t)c->nchan;
+       for (int ch = 0; ch < c->nchan; ++ch) {
+         const float lidx = anr[(size_t)kAnrStLidx * c->nchan + ch], ng = anr[(size_t)kAnrStNgamma * c->nchan + ch];
+         if (!(lidx >= 0.0f && lidx <= 1000.0f) || !std::isfinite(ng)) return fail(T41RX_ERR_STATE, "checkpoint: notch leak words out of range");
+         const float *sc = spec + (size_t)kNrSpecFloats * (size_t)ch + kNrScal;
+         // (the kernel casts them with (int) and uses them as array indices and counters: integral values only)
+         auto whole = [](float v) { return v == std::floor(v); };
+         if (!(sc[0] >= 0.0f && sc[0] <= 2.0f) || !(sc[1] >= 0.0f && sc[1] <= 14.0f) || !(sc[2] == 0.0f || sc[2] == 1.0f || sc[2] == 2.0f) ||
+             !(sc[3] >= 0.0f && sc[3] <= 1.0e6f) || !whole(sc[0]) || !whole(sc[1]) || !whole(sc[3]))
+           return fail(T41RX_ERR_STATE, "checkpoint: noise-reduction ring pointers out of range or not integral");
+       }
+       return T41RX_OK;
+     },
+     [](const t41rx_ctx *c, void *h, size_t bytes) {
+       const size_t ab = sizeof(float) * (size_t)kAnrStRows * (size_t)c->nchan;
+       HIP_TRY(hipMemcpy(h, c->d_nr_anr.get(), ab, hipMemcpyDeviceToHost));
+       HIP_TRY(hipMemcpy(static_cast<char *>(h) + ab, c->d_nr_spec.get(), bytes - ab, hipMemcpyDeviceToHost));
+       return T41RX_OK;
+     },
+     [](t41rx_ctx *c, const void *h, size_t bytes) {
+       const size_t ab = sizeof(float) * (size_t)kAnrStRows * (size_t)c->nchan;
+       HIP_TRY(hipMemcpy(c->d_nr_anr.get(), h, ab, hipMemcpyHostToDevice));
+       HIP_TRY(hipMemcpy(c->d_nr_spec.get(), static_cast<const char *>(h) + ab, bytes - ab, hipMemcpyHostToDevice));
+       return T41RX_OK;
+     },
+     [](t41rx_ctx *c, size_t) {
+       return c->d_nr_anr ? hip_check(nr_power_on(c->d_nr_anr.get(), c->d_nr_spec.get(), c->nchan), "noise-reduction reset") : T41RX_OK;
+     }},
+    // display FFT: zoom filters, ring, FFT_spec_old [n_channels][kDispFloats] (FFT.cpp:14-26) -- present while
+    // t41rx_set_display_spectrum is on (which allocates it); header word 6 = its spectrumZoom
+    {kSecDisp, "display-FFT", (size_t)kDispFloats,
+     [](const t41rx_ctx *c) { return c->disp_spec && c->d_disp; }, nullptr,
+     [](const t41rx_ctx *c, const int32_t *hdr, const float *d) {
+       if (!(c->disp_spec && c->d_disp)) return fail(T41RX_ERR_STATE, "checkpoint carries display-FFT state but the display spectrum is off here");
+       if (hdr[6] != c->disp_zoom) return fail(T41RX_ERR_STATE, "checkpoint: display-FFT state of another spectrumZoom");
+       for (int ch = 0; ch < c->nchan; ++ch) {
+         int32_t ptr;
+         std::memcpy(&ptr, d + (size_t)kDispFloats * (size_t)ch + kDispPtr, sizeof(ptr));
+         if (ptr < 0 || ptr >= 512) return fail(T41RX_ERR_STATE, "checkpoint: zoom_sample_ptr out of range");
+       }
+       return T41RX_OK;
+     },
+     [](const t41rx_ctx *c, void *h, size_t n) { return hip_check(hipMemcpy(h, c->d_disp.get(), n, hipMemcpyDeviceToHost), "hipMemcpy"); },
+     [](t41rx_ctx *c, const void *h, size_t n) { return hip_check(hipMemcpy(c->d_disp.get(), h, n, hipMemcpyHostToDevice), "hipMemcpy"); },
+     [](t41rx_ctx *c, size_t n) { return c->d_disp ? hip_check(hipMemset(c->d_disp.get(), 0, n), "hipMemset") : T41RX_OK; }},  // ZoomFFTPrep()
+    // noise blanker: last_frame_end[0 .. 12] (DSP_Fn.cpp:143), [n_channels][kNbCarryPitch] (3 floats of padding) -- the
+    // current one of the two slots out, slot 0 in; present once the blanker has run
+    {kSecNb, "noise-blanker", (size_t)kNbCarryPitch,
+     [](const t41rx_ctx *c) { return c->d_nb != nullptr; }, ensure_nb, nullptr,
+     [](const t41rx_ctx *c, void *h, size_t n) {
+       return hip_check(hipMemcpy(h, c->d_nb.get() + (size_t)c->nb_sel * (n / sizeof(float)), n, hipMemcpyDeviceToHost), "hipMemcpy");
+     },
+     [](t41rx_ctx *c, const void *h, size_t n) {
+       c->nb_sel = 0;
+       return hip_check(hipMemcpy(c->d_nb.get(), h, n, hipMemcpyHostToDevice), "hipMemcpy");
+     },
+     [](t41rx_ctx *c, size_t n) {  // both slots: last_frame_end is a static, zero at power-on
+       c->nb_sel = 0;
+       return c->d_nb ? hip_check(hipMemset(c->d_nb.get(), 0, 2 * n), "hipMemset") : T41RX_OK;
+     }},
+    // receive equalizer: rec_EQ_Band1_state .. rec_EQ_Band14_state (Filter.cpp:43-56), [n_channels][kEqStateFloats] --
+    // present once the equalizer has run
+    {kSecEq, "receive-equalizer", (size_t)kEqStateFloats,
+     [](const t41rx_ctx *c) { return c->d_eq != nullptr; }, ensure_eq, nullptr,
+     [](const t41rx_ctx *c, void *h, size_t n) { return hip_check(hipMemcpy(h, c->d_eq.get(), n, hipMemcpyDeviceToHost), "hipMemcpy"); },
+     [](t41rx_ctx *c, const void *h, size_t n) { return hip_check(hipMemcpy(c->d_eq.get(), h, n, hipMemcpyHostToDevice), "hipMemcpy"); },
+     [](t41rx_ctx *c, size_t n) { return c->d_eq ? hip_check(hipMemset(c->d_eq.get(), 0, n), "hipMemset") : T41RX_OK; }},  // (zeroed statics)
+};
+
+size_t section_bytes(const Section &s, int nchan) { return sizeof(float) * s.chan_floats * (size_t)nchan; }
+size_t path_bytes(const t41rx_ctx *ctx) { return sizeof(float) * state_floats(ctx->params.fft_length) * (size_t)ctx->nchan; }
+int32_t state_sections(const t41rx_ctx *ctx) {
+  int32_t sec = 0;
+  for (const Section &s : kSections)
+    if (s.present(ctx)) sec |= s.bit;
+  return sec;
+}
+size_t state_bytes(const t41rx_ctx *ctx, int32_t sec) {
+  size_t n = kStateHeaderBytes + path_bytes(ctx);
+  for (const Section &s : kSections)
+    if (sec & s.bit) n += section_bytes(s, ctx->nchan);
+  return n;
+}
+
+// what the kernels consume of the path's records as they stand: the oscillator amplitude and the AGC state words
+int check_records(const t41rx_ctx *ctx, const float *rec) {
+  const size_t sf = state_floats(ctx->params.fft_length);
+  const size_t ag = st_agc(ctx->params.fft_length) + kAgcHistFloats;
+  for (int c = 0; c < ctx->nchan; ++c) {
+    const float *r = rec + sf * (size_t)c;
+    NcoState ns;
+    std::memcpy(&ns, r + kStNco, sizeof(ns));
+    if (!(ns.r > 0.25 && ns.r < 4.0)) return fail(T41RX_ERR_STATE, "checkpoint: oscillator amplitude out of range");
+    int32_t w[3];
+    std::memcpy(w, r + ag + kAgcStState, sizeof(w));
+    if (w[0] < 0 || w[0] > 4 || w[1] < 0 || w[1] > 1 || w[2] < 0 || w[2] > (1 << 20))
+      return fail(T41RX_ERR_STATE, "checkpoint: AGC state words out of range");
+    for (int k = 0; k < 4; ++k)
+      if (!std::isfinite(r[ag + k])) return fail(T41RX_ERR_STATE, "checkpoint: AGC levels not finite");
+    // AMDecodeSAM's statics (Demod.cpp:19-23): the kernel wraps phzerror with one conditional step
+    // each way, which is the reference's pair of `while` loops only for a phase already in [0, 2 pi] (2 pi itself is
+    // what a tiny negative phase + 2 pi rounds to: the loops leave it, and so does the kernel)
+    const float phz = r[kStMisc + kMiscSamPhz], fil = r[kStMisc + kMiscSamFil], om = r[kStMisc + kMiscSamOmega];
+    if (!(phz >= 0.0f && phz <= 6.2831855f) || !std::isfinite(fil) || !(std::fabs(fil) < 4.0f) || !(std::fabs(om) <= 1.05f))
+      return fail(T41RX_ERR_STATE, "checkpoint: synchronous-detector PLL words out of range");
+  }
   return T41RX_OK;
 }
 
@@ -264,108 +494,234 @@ int reset_state(t41rx_ctx *ctx) {
     std::memcpy(h.data() + sf * (size_t)c + kStNco, &ns, sizeof(ns));
     std::memcpy(h.data() + sf * (size_t)c + kStNco + 4, &ns, sizeof(ns));
   }
-  HIP_TRY(hipMemcpy(ctx->d_state, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ctx->d_state.get(), h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
   ctx->nco_sel = 0;
-  if (ctx->d_disp) HIP_TRY(hipMemset(ctx->d_disp, 0, sizeof(float) * kDispFloats * (size_t)ctx->nchan));
-  if (ctx->d_nb) {  // last_frame_end is a static: zero at power-on
-    HIP_TRY(hipMemset(ctx->d_nb, 0, sizeof(float) * 2 * kNbCarryPitch * (size_t)ctx->nchan));
-    ctx->nb_sel = 0;
+  for (const Section &s : kSections) {
+    const int rc = s.reset(ctx, section_bytes(s, ctx->nchan));
+    if (rc != T41RX_OK) return rc;
   }
-  if (ctx->d_eq) HIP_TRY(hipMemset(ctx->d_eq, 0, sizeof(float) * kEqStateFloats * (size_t)ctx->nchan));  // zeroed statics
-  if (ctx->d_nr_anr) return reset_nr(ctx);
   return T41RX_OK;
 }
 
-// the noise blanker's carry, on first use (power-on: zero)
-int ensure_nb(t41rx_ctx *ctx) {
-  if (ctx->d_nb) return T41RX_OK;
-  const size_t bytes = sizeof(float) * 2 * kNbCarryPitch * (size_t)ctx->nchan;
-  float *nb = nullptr;
-  if (hipMalloc((void **)&nb, bytes) != hipSuccess) return fail(T41RX_ERR_NOMEM, "noise-blanker state allocation failed");
-  if (hipMemset(nb, 0, bytes) != hipSuccess) {
-    (void)hipFree(nb);
-    return fail(T41RX_ERR_HIP, "noise-blanker state upload failed");
+// ---- a process call: (a) prepare_call, (b) rx_args, (c) launch_chain
+bool nr_on(const t41rx_ctx *ctx) { return ctx->params.nrOptionSelect != 0 || ctx->params.ANR_notchOn != 0; }  // (fft_length 512: params_valid)
+// the fused kernel stops behind the demodulator; stage kernels; back kernel (fft_length 512: t41rx_set_noise_blanker,
+// t41rx_set_receive_eq)
+bool stages_on(const t41rx_ctx *ctx) { return ctx->eq_on || nr_on(ctx) || ctx->nb_on; }
+// the pipelined kernels' buffer: AGC on (with the synchronous detector behind it: PSA), or the synchronous detector alone
+bool pipe_on(const t41rx_ctx *ctx, int n_frames) {
+  return (ctx->params.AGCMode != 0 || ctx->params.mode == T41RX_DEMOD_SAM) && ctx->params.fft_length == 512 && n_frames >= 4;
+}
+
+// (a) what the call needs allocated (stages and scratch on first use, kept) and the refusals that depend on the context
+int prepare_call(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
+  const int seg = ctx->params.fft_length / 512;
+  int rc = T41RX_OK;
+  if ((nr_on(ctx) && (rc = ensure_nr(ctx)) != T41RX_OK) || (ctx->nb_on && (rc = ensure_nb(ctx)) != T41RX_OK) ||
+      (ctx->eq_on && (rc = ensure_eq(ctx)) != T41RX_OK))
+    return rc;
+  if ((seg > 1 || stages_on(ctx)) && n_frames > ctx->scratch_frames) {
+    // scratch between the kernels of the long-FFT pipeline / the noise-reduction pipeline (grown on demand, kept)
+    HIP_TRY(hipStreamSynchronize(s));
+    ctx->scratch_frames = 0;
+    ctx->d_mid.reset();
+    ctx->d_aud24.reset();
+    const size_t per = (size_t)ctx->nchan * (size_t)n_frames * (size_t)(256 * seg);  // fft_length / 2 per frame
+    HIP_TRY(dev_alloc(ctx->d_mid, per * 2 * sizeof(float)));
+    HIP_TRY(dev_alloc(ctx->d_aud24, per * 2 * sizeof(float)));  // complex when the back kernel demodulates
+    ctx->scratch_frames = n_frames;
   }
-  ctx->d_nb = nb;
-  ctx->nb_sel = 0;
+  if (ctx->params.mode == T41RX_DEMOD_NFM && ctx->params.nfm_demod == 1 && seg > 1)
+    return fail(T41RX_ERR_UNSUPPORTED, "nfm_demod = 1 is built for fft_length 512");
+  if (pipe_on(ctx, n_frames) && !ctx->d_agc_pipe) {
+    const size_t bytes = pipe_layout(ctx->nchan).bytes;
+    DevBuf<char> pipe;  // the context only ever sees a buffer whose counters are zero
+    HIP_TRY(dev_alloc(pipe, bytes));
+    HIP_TRY(hipMemset(pipe.get(), 0, bytes));
+    ctx->d_agc_pipe = std::move(pipe);
+  }
+  if (ctx->params.AGCMode != 0 && (int)blob_view(ctx->blob.data()).agc[kAgcAttackBuffsize] != kAgcDelay)
+    return fail(T41RX_ERR_STATE, "coefficient blob carries an AGC look-ahead the kernel is not built for");
+  if ((ctx->dbg_nco || ctx->dbg_dec || ctx->dbg_demod) && n_frames > ctx->tap_frames)
+    return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the debug tap buffers were set with");
+  if (ctx->spect && n_frames > ctx->spect_frames)
+    return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the audio-spectrum buffers were set with");
+  if (ctx->disp_spec && n_frames > ctx->disp_frames)
+    return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the display-spectrum buffers were set with");
+  if (ctx->disp_spec && (!ctx->d_pre || !ctx->d_disp || !ctx->d_win)) return fail(T41RX_ERR_STATE, "display spectrum enabled without its buffers");
   return T41RX_OK;
 }
 
-// the receive equalizer's biquad memories, on first use (power-on: zero, Filter.cpp:43-56)
-int ensure_eq(t41rx_ctx *ctx) {
-  if (ctx->d_eq) return T41RX_OK;
-  const size_t bytes = sizeof(float) * kEqStateFloats * (size_t)ctx->nchan;
-  float *eq = nullptr;
-  if (hipMalloc((void **)&eq, bytes) != hipSuccess) return fail(T41RX_ERR_NOMEM, "receive-equalizer state allocation failed");
-  if (hipMemset(eq, 0, bytes) != hipSuccess) {
-    (void)hipFree(eq);
-    return fail(T41RX_ERR_HIP, "receive-equalizer state upload failed");
+// (b) the kernels' arguments
+RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, int n_frames, bool q15) {
+  const int seg = ctx->params.fft_length / 512;
+  RxArgs a{};
+  a.I = dI;
+  a.Q = dQ;
+  a.out = dAudio;
+  a.state = ctx->d_state.get();
+  a.coef = ctx->d_coef.get();
+  a.tab = ctx->d_tab.get();
+  a.nco = ctx->d_nco.get();
+  a.nchan = ctx->nchan;
+  a.nframes = seg * n_frames;  // 2048-sample segments
+  if (ctx->layout == T41RX_LAYOUT_TIME_MAJOR) {  // [frame][channel][frame_len] (fft_length 512: set_buffer_layout / set_params)
+    a.chan_stride = 2048;
+    a.frame_stride = (long long)ctx->nchan * 2048;
+  } else {
+    a.chan_stride = (long long)a.nframes * 2048;
+    a.frame_stride = 2048;
   }
-  ctx->d_eq = eq;
+  a.seg = seg;
+  a.nframes4k = n_frames;
+  a.mid = ctx->d_mid.get();
+  a.aud24 = ctx->d_aud24.get();
+  a.tab4k = ctx->d_tab4k.get();
+  {
+    const float *sc = blob_view(ctx->blob.data()).scalars;
+    const bool iq_on = sc[kScIqCorrOn] != 0.0f;
+    const float gi = iq_on ? sc[kScBandGain] * sc[kScNegIqAmp] : sc[kScBandGain];
+    a.g_rf = sc[kScRfGain];
+    a.g_band = sc[kScBandGain];
+    a.neg_iq_amp = sc[kScNegIqAmp];
+    a.iq_phase = sc[kScIqPhase];
+    a.iq_corr_on = iq_on ? 1 : 0;
+    // PLAIN folds "I <- -I" (IQ correction on, amplitude factor 1) into the sign of the RF gain; with
+    // the correction on and gi = +1 (IQAmpCorrectionFactor = -1) the general kernel must run
+    a.plain = ((iq_on ? gi == -1.0f : gi == 1.0f) && sc[kScBandGain] == 1.0f && (!iq_on || sc[kScIqPhase] == 0.0f)) ? 1 : 0;
+  }
+  a.q15 = q15 ? 1 : 0;
+  a.nco_rd = ctx->nco_sel;
+  a.nfm_atan = (ctx->params.mode == T41RX_DEMOD_NFM && ctx->params.nfm_demod == 1) ? 1 : 0;
+  {
+    // Segment-parallel kernels of the long-FFT pipeline: about 4096 wave slots (256 CUs x 16) to
+    // fill; a wave that starts inside the call pays one extra sub-block to rebuild its filter
+    // memories, so runs are as long as still gives every slot a wave (and never longer than 8).
+    const long segs = (long)a.nframes, waves = 4096;
+    long run = (long)ctx->nchan * segs / waves;
+    if (const char *e = std::getenv("T41RX_SEG_RUN")) run = std::atol(e);  // experiments
+    a.seg_run = (int)(run < 1 ? 1 : (run > 8 ? 8 : (run > segs ? segs : run)));
+  }
+  a.agc = ctx->params.AGCMode != 0 ? 1 : 0;
+  if (pipe_on(ctx, n_frames)) a.agc_pipe = reinterpret_cast<float *>(ctx->d_agc_pipe.get());
+  a.dbg_pre = ctx->disp_spec ? ctx->d_pre.get() : nullptr;
+  a.dbg_nco = ctx->dbg_nco;
+  a.dbg_dec = ctx->dbg_dec;
+  a.dbg_demod = ctx->dbg_demod;
+  a.spect = ctx->spect;
+  a.spect_max = ctx->spect_max;
+  if (stages_on(ctx)) a.aud_out = ctx->d_aud24.get();  // the fused kernel stops behind the demodulator
+  return a;
+}
+
+// (c) the stage chain: fused front end, then on the audio @24 kS/s the equalizer, noise reduction / notch and the
+// blanker, the back end, and the display FFT
+int launch_chain(t41rx_ctx *ctx, RxArgs a, int n_frames, hipStream_t s) {
+  hipError_t e = launch_rx(a, ctx->params.fft_length, ctx->params.mode, s);
+  if (e != hipSuccess) return hip_fail(e, "kernel launch");
+  if (ctx->eq_on) {
+    // Process.cpp:828-832 on the call's audio @24 kS/s
+    EqArgs q{};
+    q.aud = ctx->d_aud24.get();
+    q.state = ctx->d_eq.get();
+    q.nchan = ctx->nchan;
+    q.nsamp = n_frames * 256;
+    std::memcpy(q.coef, ctx->eq_coef, sizeof(q.coef));
+    for (int b = 0; b < kEqBands; ++b) {
+      // recEQ_LevelScale[b] = (float)EEPROMData.equalizerRec[b] / 100.0 (Filter.cpp:119-121); arm_scale_f32 by its
+      // negative for bands 1, 3, .., 13 (Filter.cpp:138-151)
+      const float lvl = (float)((double)(float)ctx->eq_levels[b] / 100.0);
+      q.scale[b] = (b % 2 == 0) ? -lvl : lvl;
+    }
+    e = launch_eq(q, s);
+    if (e != hipSuccess) return hip_fail(e, "receive-equalizer kernel launch");
+  }
+  if (nr_on(ctx)) {
+    // Process.cpp:841-866 behind it
+    NrArgs n{};
+    n.aud = ctx->d_aud24.get();
+    n.anr = ctx->d_nr_anr.get();
+    n.spec = ctx->d_nr_spec.get();
+    n.tab_nr = ctx->d_nr_tab.get();
+    n.tab = ctx->d_tab.get();
+    n.nchan = ctx->nchan;
+    n.nframes = n_frames;
+    n.nr_option = ctx->params.nrOptionSelect;
+    n.notch = ctx->params.ANR_notchOn;
+    n.alpha = ctx->params.NR_alpha;
+    n.beta = ctx->params.NR_beta;
+    n.psi = ctx->params.NR_PSI;
+    nr_vad_range(ctx->params.FLoCut, ctx->params.FHiCut, &n.vad_lo, &n.vad_hi);
+    e = launch_nr(n, s);
+    if (e != hipSuccess) return hip_fail(e, "noise-reduction kernel launch");
+  }
+  if (ctx->nb_on) {
+    // Process.cpp:873-876 behind them
+    NbArgs b{};
+    b.aud = ctx->d_aud24.get();
+    b.carry = ctx->d_nb.get();
+    b.nchan = ctx->nchan;
+    b.nframes = n_frames;
+    b.sel = ctx->nb_sel;
+    e = launch_nb(b, s);
+    if (e != hipSuccess) return hip_fail(e, "noise-blanker kernel launch");
+    ctx->nb_sel ^= 1;  // the last frame wrote the other slot
+  }
+  if (stages_on(ctx)) {
+    // then the interpolators, volume and stores (Process.cpp:917-937) from a.aud24
+    a.aud_out = nullptr;
+    e = launch_back512(a, s);
+    if (e != hipSuccess) return hip_fail(e, "interpolator kernel launch");
+  }
+  if (a.seg > 1) ctx->nco_sel ^= 1;  // the kernels wrote the other copy
+  if (ctx->disp_spec) {
+    DispArgs d{};
+    d.pre = ctx->d_pre.get();
+    d.disp = ctx->d_disp.get();
+    d.spec = ctx->disp_spec;
+    d.spec_old = ctx->disp_old;
+    d.tab = ctx->d_tab.get();
+    d.win = ctx->d_win.get();
+    d.nchan = ctx->nchan;
+    d.nframes = n_frames;
+    d.zoom = ctx->disp_zoom;
+    if (d.zoom > 0) {
+      std::memcpy(d.iir, kZoomIirCoeffs[d.zoom - 1], sizeof(d.iir));
+      design_zoom_fir(d.zoom, d.fir);
+    }
+    e = launch_display(d, s);
+    if (e != hipSuccess) return hip_fail(e, "display kernel launch");
+  }
   return T41RX_OK;
 }
 
-// state and tables of the noise-reduction stages, on first use
-int ensure_nr(t41rx_ctx *ctx) {
-  if (ctx->d_nr_anr) return T41RX_OK;
-  float *anr = nullptr, *spec = nullptr, *tab = nullptr;
-  if (hipMalloc((void **)&anr, sizeof(float) * kAnrStRows * (size_t)ctx->nchan) != hipSuccess ||
-      hipMalloc((void **)&spec, sizeof(float) * kNrSpecFloats * (size_t)ctx->nchan) != hipSuccess ||
-      hipMalloc((void **)&tab, sizeof(float) * kNrTabFloats) != hipSuccess) {
-    (void)hipFree(anr);
-    (void)hipFree(spec);
-    (void)hipFree(tab);
-    return fail(T41RX_ERR_NOMEM, "noise-reduction state allocation failed");
-  }
-  float h[kNrTabFloats];
-  nr_make_tables(h);
-  std::vector<float> ha((size_t)kAnrStRows * (size_t)ctx->nchan), hs((size_t)kNrSpecFloats * (size_t)ctx->nchan);
-  nr_reset_anr(ha.data(), (size_t)ctx->nchan);
-  for (int c = 0; c < ctx->nchan; ++c) nr_reset_record(hs.data() + (size_t)kNrSpecFloats * (size_t)c);
-  if (hipMemcpy(tab, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(anr, ha.data(), sizeof(float) * ha.size(), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(spec, hs.data(), sizeof(float) * hs.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(anr);
-    (void)hipFree(spec);
-    (void)hipFree(tab);
-    return fail(T41RX_ERR_HIP, "noise-reduction state upload failed");
-  }
-  ctx->d_nr_anr = anr;
-  ctx->d_nr_spec = spec;
-  ctx->d_nr_tab = tab;
-  return T41RX_OK;
+int process_device_impl(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, int n_frames,
+                        void *hip_stream, bool q15) {
+  if (!ctx || !dI || !dQ || !dAudio) return fail(T41RX_ERR_ARG, "null argument");
+  if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
+  if ((reinterpret_cast<uintptr_t>(dI) | reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dAudio)) & 15u)
+    return fail(T41RX_ERR_ARG, "I/Q/audio device pointers must be 16-byte aligned");
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  const hipStream_t s = (hipStream_t)hip_stream;
+  const int rc = prepare_call(ctx, n_frames, s);
+  if (rc != T41RX_OK) return rc;
+  return launch_chain(ctx, rx_args(ctx, dI, dQ, dAudio, n_frames, q15), n_frames, s);
 }
 
-void free_ctx(t41rx_ctx *ctx) {
-  if (!ctx) return;
-  (void)hipFree(ctx->d_state);
-  (void)hipFree(ctx->d_coef);
-  (void)hipFree(ctx->d_tab);
-  (void)hipFree(ctx->d_nco);
-  (void)hipFree(ctx->d_tab4k);
-  (void)hipFree(ctx->d_mid);
-  (void)hipFree(ctx->d_aud24);
-  if (ctx->d_agc_pipe && std::getenv("T41RX_PIPE_STAT")) {  // diagnostic build's counters (rx_kernels.hip: PIPE_STAT_*)
-    unsigned long long c[16] = {};
-    std::vector<unsigned long long> all((size_t)ctx->nchan * 16);
-    (void)hipMemcpy(all.data(), ctx->d_agc_pipe + (size_t)ctx->nchan * 3 * 1024, all.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    for (size_t i = 0; i < all.size(); ++i) c[i & 15] += all[i];
-    std::fprintf(stderr, "pipe_stat chain_cycles %llu chains %llu slow_blocks %llu back_wait %llu duty_wait %llu blocks %llu chain_stage %llu chain_steps %llu front %llu prep %llu back %llu wave_iterations %llu chain_state_wait %llu\n",
-                 c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], c[10], c[11], c[12]);
-  }
-  (void)hipFree(ctx->d_agc_pipe);
-  (void)hipFree(ctx->d_in_i);
-  (void)hipFree(ctx->d_in_q);
-  (void)hipFree(ctx->d_out);
-  (void)hipFree(ctx->d_pre);
-  (void)hipFree(ctx->d_disp);
-  (void)hipFree(ctx->d_win);
-  (void)hipFree(ctx->d_nr_anr);
-  (void)hipFree(ctx->d_nr_spec);
-  (void)hipFree(ctx->d_nr_tab);
-  (void)hipFree(ctx->d_nb);
-  (void)hipFree(ctx->d_eq);
-  delete ctx;
+// staging buffers of the host-pointer entry points, sized in bytes per array
+int ensure_staging(t41rx_ctx *ctx, size_t bytes) {
+  if (bytes <= ctx->staging_floats * sizeof(float)) return T41RX_OK;
+  ctx->staging_floats = 0;
+  ctx->d_in_i.reset();
+  ctx->d_in_q.reset();
+  ctx->d_out.reset();
+  const size_t nfl = (bytes + sizeof(float) - 1) / sizeof(float);
+  HIP_TRY(dev_alloc(ctx->d_in_i, nfl * sizeof(float)));
+  HIP_TRY(dev_alloc(ctx->d_in_q, nfl * sizeof(float)));
+  HIP_TRY(dev_alloc(ctx->d_out, nfl * sizeof(float)));
+  ctx->staging_floats = nfl;
+  return T41RX_OK;
 }
 
 }  // namespace
@@ -464,7 +820,7 @@ int t41rx_create(t41rx_ctx **out, int device_id, int n_channels, const t41rx_par
   DeviceGuard g(device_id);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
 
-  t41rx_ctx *ctx = new (std::nothrow) t41rx_ctx();
+  std::unique_ptr<t41rx_ctx> ctx(new (std::nothrow) t41rx_ctx());  // (destroyed before g on the way out)
   if (!ctx) return fail(T41RX_ERR_NOMEM, "host allocation failed");
   ctx->device = device_id;
   ctx->nchan = n_channels;
@@ -472,26 +828,18 @@ int t41rx_create(t41rx_ctx **out, int device_id, int n_channels, const t41rx_par
   ctx->blob.assign(blob_floats(p->fft_length), 0.0f);
   ctx->nco_hz.assign((size_t)n_channels, 0);
   int rc = design_blob(*p, ctx->blob.data(), ctx->blob.size() * sizeof(float));
-  if (rc != T41RX_OK) {
-    free_ctx(ctx);
-    return fail(rc, "coefficient design failed");
-  }
+  if (rc != T41RX_OK) return fail(rc, "coefficient design failed");
   hipError_t e;
   const size_t sbytes = sizeof(float) * state_floats(p->fft_length) * (size_t)n_channels;
-  if ((e = hipMalloc((void **)&ctx->d_state, sbytes)) != hipSuccess ||
-      (e = hipMalloc((void **)&ctx->d_coef, sizeof(DevCoef))) != hipSuccess ||
-      (e = hipMalloc((void **)&ctx->d_tab, sizeof(float2) * kTabEntries512)) != hipSuccess ||
-      (e = hipMalloc((void **)&ctx->d_nco, sizeof(ChanNco) * (size_t)n_channels)) != hipSuccess ||
-      (p->fft_length != 512 && (e = hipMalloc((void **)&ctx->d_tab4k, sizeof(float2) * tab_long_entries(p->fft_length / 512))) != hipSuccess)) {
-    free_ctx(ctx);
+  if ((e = dev_alloc(ctx->d_state, sbytes)) != hipSuccess || (e = dev_alloc(ctx->d_coef, sizeof(DevCoef))) != hipSuccess ||
+      (e = dev_alloc(ctx->d_tab, sizeof(float2) * kTabEntries512)) != hipSuccess ||
+      (e = dev_alloc(ctx->d_nco, sizeof(ChanNco) * (size_t)n_channels)) != hipSuccess ||
+      (p->fft_length != 512 && (e = dev_alloc(ctx->d_tab4k, sizeof(float2) * tab_long_entries(p->fft_length / 512))) != hipSuccess))
     return hip_fail(e, "hipMalloc");
-  }
-  if ((rc = upload_coeffs(ctx)) != T41RX_OK || (rc = upload_nco(ctx)) != T41RX_OK ||
-      (rc = reset_state(ctx)) != T41RX_OK) {
-    free_ctx(ctx);
+  if ((rc = upload_coeffs(ctx.get())) != T41RX_OK || (rc = upload_nco(ctx.get())) != T41RX_OK ||
+      (rc = reset_state(ctx.get())) != T41RX_OK)
     return rc;
-  }
-  *out = ctx;
+  *out = ctx.release();
   return T41RX_OK;
 }
 
@@ -499,7 +847,16 @@ int t41rx_destroy(t41rx_ctx *ctx) {
   if (!ctx) return T41RX_OK;
   DeviceGuard g(ctx->device);
   (void)hipDeviceSynchronize();
-  free_ctx(ctx);
+  if (ctx->d_agc_pipe && std::getenv("T41RX_PIPE_STAT")) {  // the diagnostic build's counters (rx_chains.hpp: PIPE_STAT_*)
+    unsigned long long c[16] = {};
+    std::vector<unsigned long long> all((size_t)ctx->nchan * 16);
+    (void)hipMemcpy(all.data(), ctx->d_agc_pipe.get() + pipe_layout(ctx->nchan).counters, all.size() * sizeof(unsigned long long),
+                    hipMemcpyDeviceToHost);
+    for (size_t i = 0; i < all.size(); ++i) c[i & 15] += all[i];
+    std::fprintf(stderr, "pipe_stat chain_cycles %llu chains %llu slow_blocks %llu back_wait %llu duty_wait %llu blocks %llu chain_stage %llu chain_steps %llu front %llu prep %llu back %llu wave_iterations %llu chain_state_wait %llu\n",
+                 c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], c[10], c[11], c[12]);
+  }
+  delete ctx;  // (its device buffers go here, on its device)
   return T41RX_OK;
 }
 
@@ -572,9 +929,6 @@ int t41rx_set_nco_freq(t41rx_ctx *ctx, const int32_t *nco_freq_hz, int n) {
   return upload_nco(ctx);
 }
 
-static int pipe_timeouts_clear(t41rx_ctx *ctx);
-static int pipe_status(t41rx_ctx *ctx);
-
 int t41rx_reset(t41rx_ctx *ctx) {
   if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
   DeviceGuard g(ctx->device);
@@ -635,11 +989,6 @@ int t41rx_get_receive_eq(const t41rx_ctx *ctx, int32_t *equalizerRec_out) {
 int t41rx_n_channels(const t41rx_ctx *ctx) { return ctx ? ctx->nchan : T41RX_ERR_ARG; }
 int t41rx_frame_len(const t41rx_ctx *ctx) { return ctx ? 4 * ctx->params.fft_length : T41RX_ERR_ARG; }
 
-namespace {
-int process_device_impl(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, int n_frames,
-                        void *hip_stream, bool q15);
-}
-
 int t41rx_process_device(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, int n_frames,
                          void *hip_stream) {
   return process_device_impl(ctx, dI, dQ, dAudio, n_frames, hip_stream, false);
@@ -653,222 +1002,6 @@ int t41rx_process_device_q15(t41rx_ctx *ctx, const int16_t *dQ_in_L, const int16
                              reinterpret_cast<float *>(dQ_out_L), n_frames, hip_stream, true);
 }
 
-namespace {
-int process_device_impl(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, int n_frames,
-                        void *hip_stream, bool q15) {
-  if (!ctx || !dI || !dQ || !dAudio) return fail(T41RX_ERR_ARG, "null argument");
-  if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
-  if ((reinterpret_cast<uintptr_t>(dI) | reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dAudio)) & 15u)
-    return fail(T41RX_ERR_ARG, "I/Q/audio device pointers must be 16-byte aligned");
-  DeviceGuard g(ctx->device);
-  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
-  const int seg = ctx->params.fft_length / 512;
-  const bool nr_on = ctx->params.nrOptionSelect != 0 || ctx->params.ANR_notchOn != 0;  // (fft_length 512: params_valid)
-  if (nr_on) {
-    const int rc = ensure_nr(ctx);
-    if (rc != T41RX_OK) return rc;
-  }
-  const bool nb_on = ctx->nb_on != 0;  // (fft_length 512: t41rx_set_noise_blanker)
-  if (nb_on) {
-    const int rc = ensure_nb(ctx);
-    if (rc != T41RX_OK) return rc;
-  }
-  const bool eq_on = ctx->eq_on != 0;  // (fft_length 512: t41rx_set_receive_eq)
-  if (eq_on) {
-    const int rc = ensure_eq(ctx);
-    if (rc != T41RX_OK) return rc;
-  }
-  // the fused kernel stops behind the demodulator; stage kernels; back kernel
-  const bool stages_on = eq_on || nr_on || nb_on;
-  if ((seg > 1 || stages_on) && n_frames > ctx->scratch_frames) {
-    // scratch between the kernels of the long-FFT pipeline / the noise-reduction pipeline (grown on demand, kept)
-    HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
-    (void)hipFree(ctx->d_mid);
-    (void)hipFree(ctx->d_aud24);
-    ctx->d_mid = ctx->d_aud24 = nullptr;
-    ctx->scratch_frames = 0;
-    const size_t per = (size_t)ctx->nchan * (size_t)n_frames * (size_t)(256 * seg);  // fft_length / 2 per frame
-    HIP_TRY(hipMalloc((void **)&ctx->d_mid, per * 2 * sizeof(float)));
-    HIP_TRY(hipMalloc((void **)&ctx->d_aud24, per * 2 * sizeof(float)));  // complex when the back kernel demodulates
-    ctx->scratch_frames = n_frames;
-  }
-  RxArgs a{};
-  a.I = dI;
-  a.Q = dQ;
-  a.out = dAudio;
-  a.state = ctx->d_state;
-  a.coef = ctx->d_coef;
-  a.tab = ctx->d_tab;
-  a.nco = ctx->d_nco;
-  a.nchan = ctx->nchan;
-  a.nframes = seg * n_frames;  // 2048-sample segments
-  if (ctx->layout == T41RX_LAYOUT_TIME_MAJOR) {  // [frame][channel][frame_len] (fft_length 512: set_buffer_layout / set_params)
-    a.chan_stride = 2048;
-    a.frame_stride = (long long)ctx->nchan * 2048;
-  } else {
-    a.chan_stride = (long long)a.nframes * 2048;
-    a.frame_stride = 2048;
-  }
-  a.seg = seg;
-  a.nframes4k = n_frames;
-  a.mid = ctx->d_mid;
-  a.aud24 = ctx->d_aud24;
-  a.tab4k = ctx->d_tab4k;
-  {
-    const float *sc = blob_view(ctx->blob.data()).scalars;
-    const bool iq_on = sc[kScIqCorrOn] != 0.0f;
-    const float gi = iq_on ? sc[kScBandGain] * sc[kScNegIqAmp] : sc[kScBandGain];
-    a.g_rf = sc[kScRfGain];
-    a.g_band = sc[kScBandGain];
-    a.neg_iq_amp = sc[kScNegIqAmp];
-    a.iq_phase = sc[kScIqPhase];
-    a.iq_corr_on = iq_on ? 1 : 0;
-    // PLAIN folds "I <- -I" (IQ correction on, amplitude factor 1) into the sign of the RF gain; with
-    // the correction on and gi = +1 (IQAmpCorrectionFactor = -1) the general kernel must run
-    a.plain = ((iq_on ? gi == -1.0f : gi == 1.0f) && sc[kScBandGain] == 1.0f && (!iq_on || sc[kScIqPhase] == 0.0f)) ? 1 : 0;
-  }
-  a.q15 = q15 ? 1 : 0;
-  a.nco_rd = ctx->nco_sel;
-  a.nfm_atan = (ctx->params.mode == T41RX_DEMOD_NFM && ctx->params.nfm_demod == 1) ? 1 : 0;
-  if (a.nfm_atan && seg > 1) return fail(T41RX_ERR_UNSUPPORTED, "nfm_demod = 1 is built for fft_length 512");
-  {
-    // Segment-parallel kernels of the long-FFT pipeline: about 4096 wave slots (256 CUs x 16) to
-    // fill; a wave that starts inside the call pays one extra sub-block to rebuild its filter
-    // memories, so runs are as long as still gives every slot a wave (and never longer than 8).
-    const long segs = (long)a.nframes, waves = 4096;
-    long run = (long)ctx->nchan * segs / waves;
-    if (const char *e = std::getenv("T41RX_SEG_RUN")) run = std::atol(e);  // experiments
-    a.seg_run = (int)(run < 1 ? 1 : (run > 8 ? 8 : (run > segs ? segs : run)));
-  }
-  a.agc = ctx->params.AGCMode != 0 ? 1 : 0;
-  // the pipelined kernels' slots: AGC on (every mode but SAM), or the synchronous detector with the AGC off
-  if ((a.agc != 0 || ctx->params.mode == T41RX_DEMOD_SAM) && seg == 1 && n_frames >= 4) {
-    if (!ctx->d_agc_pipe) {  // (+ 8 counters per wave of the -DT41RX_PIPE_STAT diagnostic build; behind them the second
-      // stage's slots: the synchronous detector behind the AGC runs two chains per frame, rx_kernels.hip PSA)
-      const size_t bytes = 2 * (size_t)ctx->nchan * 3 * 1024 * sizeof(float) + ((size_t)ctx->nchan + 16) * 16 * sizeof(unsigned long long);
-      float *slots = nullptr;  // the context only ever sees a buffer whose counters are zero
-      HIP_TRY(hipMalloc((void **)&slots, bytes));
-      const hipError_t em = hipMemset(slots, 0, bytes);
-      if (em != hipSuccess) {
-        (void)hipFree(slots);
-        return hip_fail(em, "hipMemset of the pipelined kernels' slots");
-      }
-      ctx->d_agc_pipe = slots;
-    }
-    a.agc_pipe = ctx->d_agc_pipe;
-  }
-  if (a.agc && (int)blob_view(ctx->blob.data()).agc[kAgcAttackBuffsize] != kAgcDelay)
-    return fail(T41RX_ERR_STATE, "coefficient blob carries an AGC look-ahead the kernel is not built for");
-  if ((ctx->dbg_nco || ctx->dbg_dec || ctx->dbg_demod) && n_frames > ctx->tap_frames)
-    return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the debug tap buffers were set with");
-  if (ctx->spect && n_frames > ctx->spect_frames)
-    return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the audio-spectrum buffers were set with");
-  if (ctx->disp_spec && n_frames > ctx->disp_frames)
-    return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the display-spectrum buffers were set with");
-  if (ctx->disp_spec && (!ctx->d_pre || !ctx->d_disp || !ctx->d_win)) return fail(T41RX_ERR_STATE, "display spectrum enabled without its buffers");
-  a.dbg_pre = ctx->disp_spec ? ctx->d_pre : nullptr;
-  a.dbg_nco = ctx->dbg_nco;
-  a.dbg_dec = ctx->dbg_dec;
-  a.dbg_demod = ctx->dbg_demod;
-  a.spect = ctx->spect;
-  a.spect_max = ctx->spect_max;
-  if (stages_on) a.aud_out = ctx->d_aud24;  // the fused kernel stops behind the demodulator
-  hipError_t e = launch_rx(a, ctx->params.fft_length, ctx->params.mode, (hipStream_t)hip_stream);
-  if (e != hipSuccess) return hip_fail(e, "kernel launch");
-  if (eq_on) {
-    // Process.cpp:828-832 on the call's audio @24 kS/s
-    EqArgs q{};
-    q.aud = ctx->d_aud24;
-    q.state = ctx->d_eq;
-    q.nchan = ctx->nchan;
-    q.nsamp = n_frames * 256;
-    std::memcpy(q.coef, ctx->eq_coef, sizeof(q.coef));
-    for (int b = 0; b < kEqBands; ++b) {
-      // recEQ_LevelScale[b] = (float)EEPROMData.equalizerRec[b] / 100.0 (Filter.cpp:119-121); arm_scale_f32 by its
-      // negative for bands 1, 3, .., 13 (Filter.cpp:138-151)
-      const float lvl = (float)((double)(float)ctx->eq_levels[b] / 100.0);
-      q.scale[b] = (b % 2 == 0) ? -lvl : lvl;
-    }
-    e = launch_eq(q, (hipStream_t)hip_stream);
-    if (e != hipSuccess) return hip_fail(e, "receive-equalizer kernel launch");
-  }
-  if (nr_on) {
-    // Process.cpp:841-866 behind it
-    NrArgs n{};
-    n.aud = ctx->d_aud24;
-    n.anr = ctx->d_nr_anr;
-    n.spec = ctx->d_nr_spec;
-    n.tab_nr = ctx->d_nr_tab;
-    n.tab = ctx->d_tab;
-    n.nchan = ctx->nchan;
-    n.nframes = n_frames;
-    n.nr_option = ctx->params.nrOptionSelect;
-    n.notch = ctx->params.ANR_notchOn;
-    n.alpha = ctx->params.NR_alpha;
-    n.beta = ctx->params.NR_beta;
-    n.psi = ctx->params.NR_PSI;
-    nr_vad_range(ctx->params.FLoCut, ctx->params.FHiCut, &n.vad_lo, &n.vad_hi);
-    e = launch_nr(n, (hipStream_t)hip_stream);
-    if (e != hipSuccess) return hip_fail(e, "noise-reduction kernel launch");
-  }
-  if (nb_on) {
-    // Process.cpp:873-876 behind them
-    NbArgs b{};
-    b.aud = ctx->d_aud24;
-    b.carry = ctx->d_nb;
-    b.nchan = ctx->nchan;
-    b.nframes = n_frames;
-    b.sel = ctx->nb_sel;
-    e = launch_nb(b, (hipStream_t)hip_stream);
-    if (e != hipSuccess) return hip_fail(e, "noise-blanker kernel launch");
-    ctx->nb_sel ^= 1;  // the last frame wrote the other slot
-  }
-  if (stages_on) {
-    // then the interpolators, volume and stores (Process.cpp:917-937)
-    a.aud_out = nullptr;
-    a.aud24 = ctx->d_aud24;
-    e = launch_back512(a, (hipStream_t)hip_stream);
-    if (e != hipSuccess) return hip_fail(e, "interpolator kernel launch");
-  }
-  if (seg > 1) ctx->nco_sel ^= 1;  // the kernels wrote the other copy
-  if (ctx->disp_spec) {
-    DispArgs d{};
-    d.pre = ctx->d_pre;
-    d.disp = ctx->d_disp;
-    d.spec = ctx->disp_spec;
-    d.spec_old = ctx->disp_old;
-    d.tab = ctx->d_tab;
-    d.win = ctx->d_win;
-    d.nchan = ctx->nchan;
-    d.nframes = n_frames;
-    d.zoom = ctx->disp_zoom;
-    if (d.zoom > 0) {
-      std::memcpy(d.iir, kZoomIirCoeffs[d.zoom - 1], sizeof(d.iir));
-      design_zoom_fir(d.zoom, d.fir);
-    }
-    e = launch_display(d, (hipStream_t)hip_stream);
-    if (e != hipSuccess) return hip_fail(e, "display kernel launch");
-  }
-  return T41RX_OK;
-}
-
-// staging buffers of the host-pointer entry points, sized in bytes per array
-int ensure_staging(t41rx_ctx *ctx, size_t bytes) {
-  if (bytes <= ctx->staging_floats * sizeof(float)) return T41RX_OK;
-  (void)hipFree(ctx->d_in_i);
-  (void)hipFree(ctx->d_in_q);
-  (void)hipFree(ctx->d_out);
-  ctx->d_in_i = ctx->d_in_q = ctx->d_out = nullptr;
-  ctx->staging_floats = 0;
-  const size_t nfl = (bytes + sizeof(float) - 1) / sizeof(float);
-  HIP_TRY(hipMalloc((void **)&ctx->d_in_i, nfl * sizeof(float)));
-  HIP_TRY(hipMalloc((void **)&ctx->d_in_q, nfl * sizeof(float)));
-  HIP_TRY(hipMalloc((void **)&ctx->d_out, nfl * sizeof(float)));
-  ctx->staging_floats = nfl;
-  return T41RX_OK;
-}
-}  // namespace
-
 int t41rx_process_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, const int16_t *Q_in_R, int16_t *Q_out_L, int n_frames) {
   if (!ctx || !Q_in_L || !Q_in_R || !Q_out_L) return fail(T41RX_ERR_ARG, "null argument");
   if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
@@ -877,13 +1010,13 @@ int t41rx_process_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, const int16_t 
   const size_t bytes = (size_t)ctx->nchan * (size_t)n_frames * (size_t)(4 * ctx->params.fft_length) * sizeof(int16_t);
   int rc = ensure_staging(ctx, bytes);
   if (rc != T41RX_OK) return rc;
-  HIP_TRY(hipMemcpy(ctx->d_in_i, Q_in_L, bytes, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ctx->d_in_q, Q_in_R, bytes, hipMemcpyHostToDevice));
-  rc = t41rx_process_device_q15(ctx, reinterpret_cast<const int16_t *>(ctx->d_in_i), reinterpret_cast<const int16_t *>(ctx->d_in_q),
-                                reinterpret_cast<int16_t *>(ctx->d_out), n_frames, nullptr);
+  HIP_TRY(hipMemcpy(ctx->d_in_i.get(), Q_in_L, bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ctx->d_in_q.get(), Q_in_R, bytes, hipMemcpyHostToDevice));
+  rc = t41rx_process_device_q15(ctx, reinterpret_cast<const int16_t *>(ctx->d_in_i.get()), reinterpret_cast<const int16_t *>(ctx->d_in_q.get()),
+                                reinterpret_cast<int16_t *>(ctx->d_out.get()), n_frames, nullptr);
   if (rc != T41RX_OK) return rc;
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(Q_out_L, ctx->d_out, bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(Q_out_L, ctx->d_out.get(), bytes, hipMemcpyDeviceToHost));
   return pipe_status(ctx);  // (these calls synchronise: samples of a run whose hand-over broke do not leave with OK)
 }
 
@@ -897,113 +1030,43 @@ int t41rx_process_host(t41rx_ctx *ctx, const float *I, const float *Q, float *au
     const int rc0 = ensure_staging(ctx, nfl * sizeof(float));
     if (rc0 != T41RX_OK) return rc0;
   }
-  HIP_TRY(hipMemcpy(ctx->d_in_i, I, nfl * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ctx->d_in_q, Q, nfl * sizeof(float), hipMemcpyHostToDevice));
-  int rc = t41rx_process_device(ctx, ctx->d_in_i, ctx->d_in_q, ctx->d_out, n_frames, nullptr);
+  HIP_TRY(hipMemcpy(ctx->d_in_i.get(), I, nfl * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ctx->d_in_q.get(), Q, nfl * sizeof(float), hipMemcpyHostToDevice));
+  int rc = t41rx_process_device(ctx, ctx->d_in_i.get(), ctx->d_in_q.get(), ctx->d_out.get(), n_frames, nullptr);
   if (rc != T41RX_OK) return rc;
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(audio, ctx->d_out, nfl * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(audio, ctx->d_out.get(), nfl * sizeof(float), hipMemcpyDeviceToHost));
   return pipe_status(ctx);  // (these calls synchronise: samples of a run whose hand-over broke do not leave with OK)
 }
 
-namespace {
-constexpr uint32_t kStateMagic = 0x54343153u;  // "T41S"
-constexpr size_t kStateHeaderBytes = 32;
-}  // namespace
-
-// Checkpoint sections behind the path's records (header word 5 = which are present):
-//   bit 0  noise reduction / notch: Xanr()'s taps, delay line and leak words [kAnrStRows][n_channels], then the
-//          Kim / spectral records [n_channels][kNrSpecFloats] (Noise.cpp:19-56) -- present once the stages have run
-//   bit 1  display FFT: zoom filters, ring, FFT_spec_old [n_channels][kDispFloats] (FFT.cpp:14-26) -- present while
-//          t41rx_set_display_spectrum is on; header word 6 = its spectrumZoom
-//   bit 2  noise blanker: last_frame_end[0 .. 12] (DSP_Fn.cpp:143), [n_channels][kNbCarryPitch] (3 floats of
-//          padding) -- present once the blanker has run
-//   bit 3  receive equalizer: rec_EQ_Band1_state .. rec_EQ_Band14_state (Filter.cpp:43-56), [n_channels][kEqStateFloats]
-//          -- present once the equalizer has run
-constexpr int32_t kSecNr = 1, kSecDisp = 2, kSecNb = 4, kSecEq = 8;
-static size_t nr_section_bytes(int nchan) { return sizeof(float) * ((size_t)kAnrStRows + (size_t)kNrSpecFloats) * (size_t)nchan; }
-static size_t disp_section_bytes(int nchan) { return sizeof(float) * (size_t)kDispFloats * (size_t)nchan; }
-static size_t nb_section_bytes(int nchan) { return sizeof(float) * (size_t)kNbCarryPitch * (size_t)nchan; }
-static size_t eq_section_bytes(int nchan) { return sizeof(float) * (size_t)kEqStateFloats * (size_t)nchan; }
-static int32_t state_sections(const t41rx_ctx *ctx) {
-  return (ctx->d_nr_anr ? kSecNr : 0) | ((ctx->disp_spec && ctx->d_disp) ? kSecDisp : 0) | (ctx->d_nb ? kSecNb : 0) |
-         (ctx->d_eq ? kSecEq : 0);
-}
-
-size_t t41rx_state_bytes(const t41rx_ctx *ctx) {
-  if (!ctx) return 0;
-  const int32_t sec = state_sections(ctx);
-  return kStateHeaderBytes + sizeof(float) * state_floats(ctx->params.fft_length) * (size_t)ctx->nchan +
-         ((sec & kSecNr) ? nr_section_bytes(ctx->nchan) : 0) + ((sec & kSecDisp) ? disp_section_bytes(ctx->nchan) : 0) +
-         ((sec & kSecNb) ? nb_section_bytes(ctx->nchan) : 0) + ((sec & kSecEq) ? eq_section_bytes(ctx->nchan) : 0);
-}
-
-// the pipelined kernels count a wait that ran out (rx_kernels.hip: pipe_wait_ge) behind their slots: a broken hand-over
-// protocol would leave wrong samples, not a hung GPU -- reported at the calls that synchronise anyway
-static size_t pipe_timeout_offset(const t41rx_ctx *ctx) {
-  return (size_t)ctx->nchan * 3 * 1024 * sizeof(float) + ((size_t)ctx->nchan + 15) * 16 * sizeof(unsigned long long);
-}
-static int pipe_timeouts(t41rx_ctx *ctx) {  // < 0: the counter could not be read
-  if (!ctx->d_agc_pipe) return 0;
-  unsigned n = 0;
-  const char *p = reinterpret_cast<const char *>(ctx->d_agc_pipe) + pipe_timeout_offset(ctx);
-  if (hipMemcpy(&n, p, sizeof(n), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  return (int)n;
-}
-static int pipe_timeouts_clear(t41rx_ctx *ctx) {
-  if (!ctx->d_agc_pipe) return T41RX_OK;
-  HIP_TRY(hipMemset(reinterpret_cast<char *>(ctx->d_agc_pipe) + pipe_timeout_offset(ctx), 0, sizeof(unsigned long long)));
-  return T41RX_OK;
-}
-// what the synchronising entry points answer when a wait inside the pipelined kernels has run out
-static int pipe_status(t41rx_ctx *ctx) {
-  const int n = pipe_timeouts(ctx);
-  if (n < 0) return fail(T41RX_ERR_HIP, "could not read the pipelined kernels' time-out counter");
-  if (n > 0)
-    return fail(T41RX_ERR_STATE, "a wait inside the pipelined AGC / SAM kernel ran out: the samples since the last reset or restored checkpoint are not valid");
-  return T41RX_OK;
-}
+size_t t41rx_state_bytes(const t41rx_ctx *ctx) { return ctx ? state_bytes(ctx, state_sections(ctx)) : 0; }
 
 int t41rx_get_state(t41rx_ctx *ctx, void *host_buf, size_t bytes) {
   if (!ctx || !host_buf) return fail(T41RX_ERR_ARG, "null argument");
   if (bytes < t41rx_state_bytes(ctx)) return fail(T41RX_ERR_STATE, "state buffer too small");
   DeviceGuard g(ctx->device);
   HIP_TRY(hipDeviceSynchronize());
-  {
-    const int rc = pipe_status(ctx);
-    if (rc != T41RX_OK) return rc;
-  }
+  int rc = pipe_status(ctx);
+  if (rc != T41RX_OK) return rc;
   const int32_t sec = state_sections(ctx);
+  const size_t sf = state_floats(ctx->params.fft_length);
   int32_t hdr[8] = {(int32_t)kStateMagic, T41RX_ABI_VERSION, ctx->params.fft_length, ctx->nchan,
-                    (int32_t)state_floats(ctx->params.fft_length), sec, (sec & kSecDisp) ? ctx->disp_zoom : 0, 0};
+                    (int32_t)sf, sec, (sec & kSecDisp) ? ctx->disp_zoom : 0, 0};
   std::memcpy(host_buf, hdr, sizeof(hdr));
-  const size_t path_bytes = sizeof(float) * state_floats(ctx->params.fft_length) * (size_t)ctx->nchan;
   char *out = static_cast<char *>(host_buf) + kStateHeaderBytes;
-  HIP_TRY(hipMemcpy(out, ctx->d_state, path_bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out, ctx->d_state.get(), path_bytes(ctx), hipMemcpyDeviceToHost));
   // canonical checkpoint: the current oscillator state in both slots
   float *rec = reinterpret_cast<float *>(out);
-  const size_t sf = state_floats(ctx->params.fft_length);
   for (int c = 0; c < ctx->nchan; ++c) {
     float *n = rec + sf * (size_t)c + kStNco;
     std::memcpy(n + 4 * (ctx->nco_sel ^ 1), n + 4 * ctx->nco_sel, sizeof(NcoState));
   }
-  out += path_bytes;
-  if (sec & kSecNr) {
-    const size_t ab = sizeof(float) * (size_t)kAnrStRows * (size_t)ctx->nchan;
-    HIP_TRY(hipMemcpy(out, ctx->d_nr_anr, ab, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out + ab, ctx->d_nr_spec, nr_section_bytes(ctx->nchan) - ab, hipMemcpyDeviceToHost));
-    out += nr_section_bytes(ctx->nchan);
+  out += path_bytes(ctx);
+  for (const Section &s : kSections) {
+    if (!(sec & s.bit)) continue;
+    if ((rc = s.get(ctx, out, section_bytes(s, ctx->nchan))) != T41RX_OK) return rc;
+    out += section_bytes(s, ctx->nchan);
   }
-  if (sec & kSecDisp) {
-    HIP_TRY(hipMemcpy(out, ctx->d_disp, disp_section_bytes(ctx->nchan), hipMemcpyDeviceToHost));
-    out += disp_section_bytes(ctx->nchan);
-  }
-  if (sec & kSecNb) {  // the current slot
-    HIP_TRY(hipMemcpy(out, ctx->d_nb + (size_t)ctx->nb_sel * kNbCarryPitch * (size_t)ctx->nchan, nb_section_bytes(ctx->nchan),
-                      hipMemcpyDeviceToHost));
-    out += nb_section_bytes(ctx->nchan);
-  }
-  if (sec & kSecEq) HIP_TRY(hipMemcpy(out, ctx->d_eq, eq_section_bytes(ctx->nchan), hipMemcpyDeviceToHost));
   return T41RX_OK;
 }
 
@@ -1012,114 +1075,39 @@ int t41rx_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes) {
   if (bytes < kStateHeaderBytes) return fail(T41RX_ERR_STATE, "state size mismatch");
   int32_t hdr[8];
   std::memcpy(hdr, host_buf, sizeof(hdr));
-  const size_t sf = state_floats(ctx->params.fft_length);
   if ((uint32_t)hdr[0] != kStateMagic || hdr[1] != T41RX_ABI_VERSION || hdr[2] != ctx->params.fft_length ||
-      hdr[3] != ctx->nchan || hdr[4] != (int32_t)sf)
+      hdr[3] != ctx->nchan || hdr[4] != (int32_t)state_floats(ctx->params.fft_length))
     return fail(T41RX_ERR_STATE, "checkpoint header does not match this context (magic / abi / fft_length / channels)");
   const int32_t sec = hdr[5];
-  if (sec & ~(kSecNr | kSecDisp | kSecNb | kSecEq)) return fail(T41RX_ERR_STATE, "checkpoint: unknown sections");
-  const size_t path_bytes = sizeof(float) * sf * (size_t)ctx->nchan;
-  if (bytes != kStateHeaderBytes + path_bytes + ((sec & kSecNr) ? nr_section_bytes(ctx->nchan) : 0) +
-                   ((sec & kSecDisp) ? disp_section_bytes(ctx->nchan) : 0) + ((sec & kSecNb) ? nb_section_bytes(ctx->nchan) : 0) +
-                   ((sec & kSecEq) ? eq_section_bytes(ctx->nchan) : 0))
-    return fail(T41RX_ERR_STATE, "state size mismatch");
-  if ((sec & kSecNr) && ctx->params.fft_length != 512) return fail(T41RX_ERR_STATE, "checkpoint: noise-reduction section at a long fft_length");
-  if ((sec & kSecNb) && ctx->params.fft_length != 512) return fail(T41RX_ERR_STATE, "checkpoint: noise-blanker section at a long fft_length");
-  if ((sec & kSecEq) && ctx->params.fft_length != 512) return fail(T41RX_ERR_STATE, "checkpoint: receive-equalizer section at a long fft_length");
-  if (sec & kSecDisp) {
-    if (!(ctx->disp_spec && ctx->d_disp)) return fail(T41RX_ERR_STATE, "checkpoint carries display-FFT state but the display spectrum is off here");
-    if (hdr[6] != ctx->disp_zoom) return fail(T41RX_ERR_STATE, "checkpoint: display-FFT state of another spectrumZoom");
-  }
-  const char *nr_sec = static_cast<const char *>(host_buf) + kStateHeaderBytes + path_bytes;
-  const char *disp_sec = nr_sec + ((sec & kSecNr) ? nr_section_bytes(ctx->nchan) : 0);
-  const char *nb_sec = disp_sec + ((sec & kSecDisp) ? disp_section_bytes(ctx->nchan) : 0);
-  const char *eq_sec = nb_sec + ((sec & kSecNb) ? nb_section_bytes(ctx->nchan) : 0);
-  if (sec & kSecNr) {
-    // what the kernels index with or divide by (nr_kernels.hip): Xanr()'s leak index, the spectral functions' ring pointers
-    const float *anr = reinterpret_cast<const float *>(nr_sec);
-    const float *spec = anr + (size_t)kAnrStRows * (size_t)ctx->nchan;
-    for (int c = 0; c < ctx->nchan; ++c) {
-      const float lidx = anr[(size_t)kAnrStLidx * ctx->nchan + c], ng = anr[(size_t)kAnrStNgamma * ctx->nchan + c];
-      if (!(lidx >= 0.0f && lidx <= 1000.0f) || !std::isfinite(ng)) return fail(T41RX_ERR_STATE, "checkpoint: notch leak words out of range");
-      const float *sc = spec + (size_t)kNrSpecFloats * (size_t)c + kNrScal;
-      // (the kernel casts them with (int) and uses them as array indices and counters: integral values only)
-      auto whole = [](float v) { return v == std::floor(v); };
-      if (!(sc[0] >= 0.0f && sc[0] <= 2.0f) || !(sc[1] >= 0.0f && sc[1] <= 14.0f) || !(sc[2] == 0.0f || sc[2] == 1.0f || sc[2] == 2.0f) ||
-          !(sc[3] >= 0.0f && sc[3] <= 1.0e6f) || !whole(sc[0]) || !whole(sc[1]) || !whole(sc[3]))
-        return fail(T41RX_ERR_STATE, "checkpoint: noise-reduction ring pointers out of range or not integral");
-    }
-  }
-  if (sec & kSecDisp) {
-    const float *d = reinterpret_cast<const float *>(disp_sec);
-    for (int c = 0; c < ctx->nchan; ++c) {
-      int32_t ptr;
-      std::memcpy(&ptr, d + (size_t)kDispFloats * (size_t)c + kDispPtr, sizeof(ptr));
-      if (ptr < 0 || ptr >= 512) return fail(T41RX_ERR_STATE, "checkpoint: zoom_sample_ptr out of range");
-    }
-  }
-  // what the kernels consume as it stands: the oscillator amplitude and the AGC state words
+  int32_t known = 0;
+  for (const Section &s : kSections) known |= s.bit;
+  if (sec & ~known) return fail(T41RX_ERR_STATE, "checkpoint: unknown sections");
+  if (bytes != state_bytes(ctx, sec)) return fail(T41RX_ERR_STATE, "state size mismatch");
+  // everything is checked before anything is written: a refused checkpoint changes nothing
   const float *rec = reinterpret_cast<const float *>(static_cast<const char *>(host_buf) + kStateHeaderBytes);
-  const size_t ag = st_agc(ctx->params.fft_length) + kAgcHistFloats;
-  for (int c = 0; c < ctx->nchan; ++c) {
-    const float *r = rec + sf * (size_t)c;
-    NcoState ns;
-    std::memcpy(&ns, r + kStNco, sizeof(ns));
-    if (!(ns.r > 0.25 && ns.r < 4.0)) return fail(T41RX_ERR_STATE, "checkpoint: oscillator amplitude out of range");
-    int32_t w[3];
-    std::memcpy(w, r + ag + kAgcStState, sizeof(w));
-    if (w[0] < 0 || w[0] > 4 || w[1] < 0 || w[1] > 1 || w[2] < 0 || w[2] > (1 << 20))
-      return fail(T41RX_ERR_STATE, "checkpoint: AGC state words out of range");
-    for (int k = 0; k < 4; ++k)
-      if (!std::isfinite(r[ag + k])) return fail(T41RX_ERR_STATE, "checkpoint: AGC levels not finite");
-    // AMDecodeSAM's statics (Demod.cpp:19-23): the kernel wraps phzerror with one conditional step
-    // each way, which is the reference's pair of `while` loops only for a phase already in [0, 2 pi] (2 pi itself is
-    // what a tiny negative phase + 2 pi rounds to: the loops leave it, and so does the kernel)
-    const float phz = r[kStMisc + kMiscSamPhz], fil = r[kStMisc + kMiscSamFil], om = r[kStMisc + kMiscSamOmega];
-    if (!(phz >= 0.0f && phz <= 6.2831855f) || !std::isfinite(fil) || !(std::fabs(fil) < 4.0f) || !(std::fabs(om) <= 1.05f))
-      return fail(T41RX_ERR_STATE, "checkpoint: synchronous-detector PLL words out of range");
+  const char *sections = reinterpret_cast<const char *>(rec) + path_bytes(ctx), *p = sections;
+  int rc = T41RX_OK;
+  for (const Section &s : kSections) {
+    if (!(sec & s.bit)) continue;
+    if (ctx->params.fft_length != 512)
+      return fail(T41RX_ERR_STATE, std::string("checkpoint: ") + s.name + " section at a long fft_length");
+    if (s.check && (rc = s.check(ctx, hdr, reinterpret_cast<const float *>(p))) != T41RX_OK) return rc;
+    p += section_bytes(s, ctx->nchan);
   }
+  if ((rc = check_records(ctx, rec)) != T41RX_OK) return rc;
   DeviceGuard g(ctx->device);
   HIP_TRY(hipDeviceSynchronize());
-  if (sec & kSecNr) {
-    const int rc = ensure_nr(ctx);
-    if (rc != T41RX_OK) return rc;
-  }
-  if (sec & kSecNb) {
-    const int rc = ensure_nb(ctx);
-    if (rc != T41RX_OK) return rc;
-  }
-  if (sec & kSecEq) {
-    const int rc = ensure_eq(ctx);
-    if (rc != T41RX_OK) return rc;
-  }
-  HIP_TRY(hipMemcpy(ctx->d_state, rec, path_bytes, hipMemcpyHostToDevice));
+  for (const Section &s : kSections)
+    if ((sec & s.bit) && s.ensure && (rc = s.ensure(ctx)) != T41RX_OK) return rc;
+  HIP_TRY(hipMemcpy(ctx->d_state.get(), rec, path_bytes(ctx), hipMemcpyHostToDevice));
   ctx->nco_sel = 0;  // (a checkpoint carries the current oscillator state in both slots)
   // The side stages' memories follow the checkpoint too: restored where it carries them, back to power-on where it
   // does not (a checkpoint taken before the stages first ran) -- never the values of the stream being replaced.
-  if (sec & kSecNr) {
-    const size_t ab = sizeof(float) * (size_t)kAnrStRows * (size_t)ctx->nchan;
-    HIP_TRY(hipMemcpy(ctx->d_nr_anr, nr_sec, ab, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ctx->d_nr_spec, nr_sec + ab, nr_section_bytes(ctx->nchan) - ab, hipMemcpyHostToDevice));
-  } else if (ctx->d_nr_anr) {
-    const int rc = reset_nr(ctx);
-    if (rc != T41RX_OK) return rc;
-  }
-  if (sec & kSecDisp) {
-    HIP_TRY(hipMemcpy(ctx->d_disp, disp_sec, disp_section_bytes(ctx->nchan), hipMemcpyHostToDevice));
-  } else if (ctx->d_disp) {
-    HIP_TRY(hipMemset(ctx->d_disp, 0, sizeof(float) * kDispFloats * (size_t)ctx->nchan));  // ZoomFFTPrep()
-  }
-  if (sec & kSecNb) {
-    HIP_TRY(hipMemcpy(ctx->d_nb, nb_sec, nb_section_bytes(ctx->nchan), hipMemcpyHostToDevice));
-    ctx->nb_sel = 0;
-  } else if (ctx->d_nb) {
-    HIP_TRY(hipMemset(ctx->d_nb, 0, sizeof(float) * 2 * kNbCarryPitch * (size_t)ctx->nchan));  // the static's power-on zero
-    ctx->nb_sel = 0;
-  }
-  if (sec & kSecEq) {
-    HIP_TRY(hipMemcpy(ctx->d_eq, eq_sec, eq_section_bytes(ctx->nchan), hipMemcpyHostToDevice));
-  } else if (ctx->d_eq) {
-    HIP_TRY(hipMemset(ctx->d_eq, 0, eq_section_bytes(ctx->nchan)));  // the biquad memories' power-on zero
+  p = sections;
+  for (const Section &s : kSections) {
+    const size_t n = section_bytes(s, ctx->nchan);
+    if ((rc = (sec & s.bit) ? s.put(ctx, p, n) : s.reset(ctx, n)) != T41RX_OK) return rc;
+    if (sec & s.bit) p += n;
   }
   return pipe_timeouts_clear(ctx);  // the restored state is valid again
 }
@@ -1169,19 +1157,18 @@ int t41rx_set_display_spectrum(t41rx_ctx *ctx, float *d_spec, float *d_spec_old,
   ctx->disp_spec = ctx->disp_old = nullptr;
   const int had_frames = ctx->disp_frames;
   ctx->disp_frames = 0;
-  if (max_frames > had_frames || !ctx->d_pre) {
-    (void)hipFree(ctx->d_pre);
-    ctx->d_pre = nullptr;
-    HIP_TRY(hipMalloc((void **)&ctx->d_pre, sizeof(float) * 4096 * (size_t)max_frames * (size_t)ctx->nchan));
-  }
-  if (!ctx->d_disp) HIP_TRY(hipMalloc((void **)&ctx->d_disp, sizeof(float) * kDispFloats * (size_t)ctx->nchan));
+  if (max_frames > had_frames || !ctx->d_pre)
+    HIP_TRY(dev_alloc(ctx->d_pre, sizeof(float) * 4096 * (size_t)max_frames * (size_t)ctx->nchan));
+  if (!ctx->d_disp) HIP_TRY(dev_alloc(ctx->d_disp, sizeof(float) * kDispFloats * (size_t)ctx->nchan));
   if (!ctx->d_win) {
-    HIP_TRY(hipMalloc((void **)&ctx->d_win, sizeof(double) * 512));
+    DevBuf<double> win;
     double w[512];
     for (int i = 0; i < 512; ++i) w[i] = 0.5 - 0.5 * std::cos(6.28 * i / 512);  // FFT.cpp:110, 222 ("Hanning", 6.28 as written)
-    HIP_TRY(hipMemcpy(ctx->d_win, w, sizeof(w), hipMemcpyHostToDevice));
+    HIP_TRY(dev_alloc(win, sizeof(w)));
+    HIP_TRY(hipMemcpy(win.get(), w, sizeof(w), hipMemcpyHostToDevice));
+    ctx->d_win = std::move(win);
   }
-  HIP_TRY(hipMemset(ctx->d_disp, 0, sizeof(float) * kDispFloats * (size_t)ctx->nchan));  // ZoomFFTPrep(): a fresh start
+  HIP_TRY(hipMemset(ctx->d_disp.get(), 0, sizeof(float) * kDispFloats * (size_t)ctx->nchan));  // ZoomFFTPrep(): a fresh start
   if (max_frames < had_frames) max_frames = had_frames;  // (the tap buffer was kept: it still holds that many)
   ctx->disp_spec = d_spec;
   ctx->disp_old = d_spec_old;
