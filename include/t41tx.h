@@ -29,6 +29,7 @@ extern "C" {
 #endif
 
 /* status codes and mode numbers are t41rx.h's (T41RX_OK, T41RX_ERR_*, T41RX_DEMOD_*) */
+/* t41rx_last_error() (t41rx.h) also returns the message of the calling thread's last failed t41tx_* call */
 
 typedef struct t41tx_params {
   int32_t mode;                     /* bands[currentBand].mode: LSB / USB select the sign of the I scaling (Exciter.cpp:117-126) */

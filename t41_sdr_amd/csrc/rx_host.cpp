@@ -20,6 +20,7 @@
 
 #include "eq_kernels.hpp"
 #include "eq_kernel.hip"  // the receive equalizer's kernel and launcher
+#include "last_error.hpp"
 #include "nb_kernels.hpp"
 #include "nb_kernel.hip"  // the noise blanker's kernel and launcher
 #include "nr_kernels.hpp"
@@ -95,13 +96,16 @@ struct t41rx_ctx {
 };
 
 namespace {
+thread_local std::string g_last_error;  // t41rx_last_error(); t41tx_* failures set it too (tx_host.cpp)
+}  // namespace
 
-thread_local std::string g_last_error;
-
-int fail(int code, const std::string &msg) {
+int t41::fail(int code, const std::string &msg) {
   g_last_error = msg;
   return code;
 }
+
+namespace {
+
 int hip_fail(hipError_t e, const char *what) {
   return fail(T41RX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }

@@ -6,8 +6,8 @@
 
 #include <cstring>
 #include <new>
-#include <string>
 
+#include "last_error.hpp"  // fail(): failures reach t41rx_last_error(), like the receive path's
 #include "tx_internal.hpp"
 
 using namespace t41;
@@ -23,11 +23,6 @@ struct t41tx_ctx {
 };
 
 namespace {
-thread_local std::string g_tx_error;
-int fail(int code, const char *msg) {
-  g_tx_error = msg;
-  return code;
-}
 struct Guard {
   int prev = -1;
   bool ok;
@@ -65,7 +60,8 @@ void t41tx_default_params(t41tx_params *p) {
 int t41tx_create(t41tx_ctx **out, int device_id, int n_channels, const t41tx_params *p) {
   if (!out || !p) return fail(T41RX_ERR_ARG, "null argument");
   *out = nullptr;
-  if (n_channels <= 0 || !valid(*p)) return fail(T41RX_ERR_ARG, "bad n_channels or mode");
+  if (n_channels <= 0) return fail(T41RX_ERR_ARG, "n_channels must be > 0");
+  if (!valid(*p)) return fail(T41RX_ERR_ARG, "mode must be USB, LSB, AM, NFM or SAM");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) return fail(T41RX_ERR_HIP, "no such HIP device");
   Guard g(device_id);
@@ -100,7 +96,7 @@ int t41tx_destroy(t41tx_ctx *ctx) {
 
 int t41tx_set_params(t41tx_ctx *ctx, const t41tx_params *p) {
   if (!ctx || !p) return fail(T41RX_ERR_ARG, "null argument");
-  if (!valid(*p)) return fail(T41RX_ERR_ARG, "bad mode");
+  if (!valid(*p)) return fail(T41RX_ERR_ARG, "mode must be USB, LSB, AM, NFM or SAM");
   ctx->params = *p;
   return T41RX_OK;
 }
@@ -114,7 +110,7 @@ int t41tx_reset(t41tx_ctx *ctx) {
   return T41RX_OK;
 }
 
-int t41tx_n_channels(const t41tx_ctx *ctx) { return ctx ? ctx->nchan : T41RX_ERR_ARG; }
+int t41tx_n_channels(const t41tx_ctx *ctx) { return ctx ? ctx->nchan : fail(T41RX_ERR_ARG, "null argument"); }
 
 int t41tx_process_device_q15(t41tx_ctx *ctx, const int16_t *dL, const int16_t *dR, int16_t *oL, int16_t *oR, int n_frames,
                              void *hip_stream) {

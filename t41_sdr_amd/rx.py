@@ -80,12 +80,15 @@ class RxChain:
 
     # -- configuration ---------------------------------------------------------------------
     def CalcFilters(self, **changes):
-        """Filter/mode/gain change between two ProcessIQData() calls; state is kept."""
+        """Filter/mode/gain change between two ProcessIQData() calls; state is kept.  A refused change leaves
+        self.params as it was (t41rx_set_params validates before it changes anything)."""
+        p = Params.from_buffer_copy(self.params)
         for k, v in changes.items():
-            if not hasattr(self.params, k):
+            if not hasattr(p, k):
                 raise AttributeError("t41rx_params has no field %r" % k)
-            setattr(self.params, k, v)
-        check(self._lib.t41rx_set_params(self._ctx, C.byref(self.params)))
+            setattr(p, k, v)
+        check(self._lib.t41rx_set_params(self._ctx, C.byref(p)))
+        self.params = p
 
     SetupMode = CalcFilters
 

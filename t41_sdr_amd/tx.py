@@ -67,11 +67,15 @@ class TxChain:
         self.device = int(device)
 
     def set_params(self, **changes):
+        """change fields between two ExciterIQData() calls; states are kept.  A refused change leaves self.params
+        as it was (the C side validates before it changes anything)."""
+        p = TxParams.from_buffer_copy(self.params)
         for k, v in changes.items():
-            if not hasattr(self.params, k):
+            if not hasattr(p, k):
                 raise AttributeError("t41tx_params has no field %r" % k)
-            setattr(self.params, k, v)
-        check(self._lib.t41tx_set_params(self._ctx, C.byref(self.params)))
+            setattr(p, k, v)
+        check(self._lib.t41tx_set_params(self._ctx, C.byref(p)))
+        self.params = p
 
     def reset(self):
         check(self._lib.t41tx_reset(self._ctx))
