@@ -4,7 +4,7 @@
 // automatic notch (Xanr() again).  All off in the firmware's defaults; FFT_LENGTH 512.
 //
 // They run on the call's demodulated audio @24 kS/s, which the fused kernel leaves in a scratch
-// ([channel][frame * 256], rx_kernels.hip: RxArgs::aud_out), in place, frame by frame; the long-FFT
+// ([channel][frame * 256], rx_kernels.hpp: RxArgs::aud_out), in place, frame by frame; the long-FFT
 // pipeline's back kernel then interpolates (launch_back512).
 //
 //  * anr_kernel: Xanr() is a 64-tap adaptive FIR whose every output feeds back into its taps, sample by

@@ -10,7 +10,7 @@ namespace t41 {
 // PART 0: the whole chain for FFT_LENGTH 512.  PART 1 / PART 2 are the two ends of the
 // FFT_LENGTH 4096 pipeline (front: loads .. /8 decimation + level adjust -> `mid`; back:
 // `aud24` -> interpolators -> store): a 16384-sample frame is 8 consecutive 2048-sample segments
-// for them, the 4096-point fast convolution in between is fastconv4096_kernel.
+// for them, the 4096-point fast convolution in between is fastconv_kernel (fastconv.hip).
 // PLAIN: band gain 1, |IQ amplitude correction| 1 and IQ phase correction 0 (the firmware defaults:
 // bands[].RFgain 1, gwv.cpp:71-72).  Those stages then vanish from the instruction stream: the one
 // thing left, the reference's I <- -I (Process.cpp:166), is folded into the sign of the RF-gain
@@ -56,6 +56,9 @@ struct Geo {
   static constexpr int kScr = kResident ? 80 : 0;        // FFT exchange (1152), overlap assembly, output transposition
   static constexpr int kI1 = kScr;                       // x2 interpolator window: 24 history + 256 new
 };
+// the geometry of one instantiation: what its __launch_bounds__, its LDS layout and its launcher (launch_rx512) share
+template <int MODE, int PART, bool AGC, bool PIPE>
+using Rx512Geo = Geo<PART, geo4(MODE, AGC) && !PIPE>;
 static_assert(!Geo<0>::kResident || Geo<0>::kTotal * sizeof(float) == 160 * 1024, "PART 0: one workgroup owns the CU's LDS");
 static_assert(Geo<1>::kTotal * sizeof(float) == 40960, "PART 1/2: four workgroups per CU");
 static_assert(!Geo<0>::kResident || (Geo<0>::kH1 + 24 <= Geo<0>::kSlice && Geo<0>::kScr + 8 * kFftRow * 2 <= Geo<0>::kXF &&
@@ -74,7 +77,7 @@ static_assert(!Geo<0>::kResident || (Geo<0>::kH1 + 24 <= Geo<0>::kSlice && Geo<0
 // state is written by the wave that READ it (the one that starts the call), from the call's last
 // samples in the same way: a wave of a later run may execute before that one has started.
 template <int MODE, bool DEBUG, int PART, bool PLAIN, bool AGC = false, bool WQ15 = false, bool SEGPAR = false, bool PIPE = false>
-__global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64), 4) void rx512_kernel(const RxArgs a) {
+__global__ __launch_bounds__((Rx512Geo<MODE, PART, AGC, PIPE>::kWaves * 64), 4) void rx512_kernel(const RxArgs a) {
   T41RX_CLK_BEGIN();
   static_assert(!SEGPAR || (PART == 1 && MODE != kModeNfm) || (PART == 2 && MODE == kModeSsb && !AGC), "SEGPAR variants");
   static_assert(!PIPE || ((AGC || MODE == kModeSam) && PART == 0 && !DEBUG && !SEGPAR),
@@ -87,7 +90,7 @@ __global__ __launch_bounds__((Geo<PART, geo4(MODE, AGC) && !PIPE>::kWaves * 64),
   // input sub-blocks of the NEXT frame requested across the back end (the pipelined kernels hold them across the
   // preparation, a chain and the back end of an older frame: registers that spill there)
   constexpr int kPF = PSAM ? kPrefetchPipeSam : PIPE ? kPrefetchPipe : kPrefetch;
-  typedef Geo<PART, geo4(MODE, AGC) && !PIPE> G;
+  typedef Rx512Geo<MODE, PART, AGC, PIPE> G;
   constexpr bool KEEP = G::kResident;  // streaming state stays on chip across the frames of a launch
   constexpr int NW = G::kWaves;
   constexpr int kX = G::kX, kY1 = G::kY1, kScr = G::kScr, kI1 = G::kI1;

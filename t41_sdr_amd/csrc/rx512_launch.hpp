@@ -1,66 +1,43 @@
-// t41_sdr_amd/csrc/rx512_launch.hpp -- picks the rx512_kernel instantiation for a call (FFT_LENGTH 512); included by the
-// one translation unit per demodulator family that instantiates them.
+// t41_sdr_amd/csrc/rx512_launch.hpp -- the one launcher of rx512_kernel (grid and block from the kernel's own geometry)
+// and the rules that pick the instantiation for an FFT_LENGTH 512 call; included by the translation units that
+// instantiate the kernel (one per demodulator family, and rx_long.hip).
 #pragma once
 #include "rx512_kernel.hpp"
 #include "rx_launch.hpp"
 
 namespace t41 {
 
+// The block is the kernel's __launch_bounds__ (Rx512Geo), the grid covers the kernel's `job`s, one per wave:
+// a channel, or with SEGPAR a (channel, run of a.seg_run segments) pair.
+// PART 0, AGC off: one 16-wave workgroup per CU (all 160 KiB of LDS, declared statically by the kernel) -- a
+// 4096-channel batch is one full, balanced wave of work on 256 CUs, and every wave keeps its channel for all the
+// frames of the launch.  Everything else: 4-wave workgroups (see Geo).
+template <int MODE, bool DEBUG, int PART, bool PLAIN, bool AGC, bool WQ15, bool SEGPAR = false, bool PIPE = false>
+static hipError_t launch_rx512(const RxArgs &a, hipStream_t s) {
+  constexpr size_t NW = Rx512Geo<MODE, PART, AGC, PIPE>::kWaves;
+  const size_t runs = SEGPAR ? (size_t)((a.nframes + a.seg_run - 1) / a.seg_run) : 1;
+  const size_t jobs = (size_t)a.nchan * runs;
+  hipLaunchKernelGGL((rx512_kernel<MODE, DEBUG, PART, PLAIN, AGC, WQ15, SEGPAR, PIPE>), dim3((unsigned)((jobs + NW - 1) / NW)), dim3(NW * 64),
+                     0, s, a);
+  return hipGetLastError();
+}
+
+// FFT_LENGTH 512, the whole chain in one kernel (PART 0).  `debug`: side outputs / stage taps.
 template <int MODE>
 static hipError_t launch512(const RxArgs &a, hipStream_t s, bool debug) {
-  // One 16-wave workgroup per CU (all 160 KiB of LDS, declared statically by the kernel): a
-  // 4096-channel batch is one full, balanced wave of work on 256 CUs, and every wave keeps its
-  // channel for all the frames of the launch.
-  // (AGC on: 4-wave workgroups, see Geo)
-#define T41RX_GO(DBG, PLN, AGCv, Q15v)                                                                   \
-  hipLaunchKernelGGL((rx512_kernel<MODE, DBG, 0, PLN, AGCv, Q15v>),                                      \
-                     dim3((a.nchan + Geo<0, AGCv>::kWaves - 1) / Geo<0, AGCv>::kWaves), dim3(Geo<0, AGCv>::kWaves * 64), 0, s, a)
-  // AGC on, calls of four frames or more without taps: the pipelined variant (agc_prep_pipe); shorter calls have
-  // nothing to overlap and take the barrier form, which computes the same values
-  if constexpr (MODE != kModeSam) {
-    if (a.agc && a.agc_pipe && !debug && a.nframes >= 4) {
-#define T41RX_GOP(PLN, Q15v)                                                                             \
-  hipLaunchKernelGGL((rx512_kernel<MODE, false, 0, PLN, true, Q15v, false, true>), dim3((a.nchan + Geo<0>::kWaves - 1) / Geo<0>::kWaves), \
-                     dim3(Geo<0>::kWaves * 64), 0, s, a)
-      if (a.q15) {
-        if (a.plain) T41RX_GOP(true, true); else T41RX_GOP(false, true);
-      } else {
-        if (a.plain) T41RX_GOP(true, false); else T41RX_GOP(false, false);
-      }
-#undef T41RX_GOP
-      return hipGetLastError();
-    }
-  }
-  if (a.q15 && debug) {  // q15 samples either side with the side outputs / stage taps (round 4; general front end)
-    if (a.agc)
-      T41RX_GO(true, false, true, true);
-    else
-      T41RX_GO(true, false, false, true);
-  } else if (a.q15) {  // the firmware's q15 sample format either side
-    if (a.agc) {
-      if (a.plain)
-        T41RX_GO(false, true, true, true);
-      else
-        T41RX_GO(false, false, true, true);
-    } else if (a.plain)
-      T41RX_GO(false, true, false, true);
-    else
-      T41RX_GO(false, false, false, true);
-  } else if (a.agc) {
-    if (debug)
-      T41RX_GO(true, false, true, false);
-    else if (a.plain)
-      T41RX_GO(false, true, true, false);
-    else
-      T41RX_GO(false, false, true, false);
-  } else if (debug)
-    T41RX_GO(true, false, false, false);
-  else if (a.plain)
-    T41RX_GO(false, true, false, false);
-  else
-    T41RX_GO(false, false, false, false);
-#undef T41RX_GO
-  return hipGetLastError();
+  constexpr bool SAM = MODE == kModeSam;
+  // the side outputs / stage taps and the synchronous detector run on the general front end
+  const bool plain = a.plain && !debug && !SAM;
+  // the pipelined variants (agc_prep_pipe, sam_chain_pipe, PSA): calls of four frames or more without taps; shorter
+  // calls have nothing to overlap and take the barrier form, which computes the same values
+  const bool pipe = (a.agc || SAM) && a.agc_pipe && !debug && a.nframes >= 4;
+  return with_bools(
+      [&](auto DBG, auto PLN, auto AGC, auto Q15, auto PIPE) {
+        // what the rules above never select is not compiled
+        if constexpr ((DBG && (PLN || PIPE)) || (PLN && SAM) || (PIPE && !(AGC || SAM))) return hipErrorInvalidValue;
+        else return launch_rx512<MODE, DBG, 0, PLN, AGC, Q15, false, PIPE>(a, s);
+      },
+      debug, plain, a.agc != 0, a.q15 != 0, pipe);
 }
 
 }  // namespace t41

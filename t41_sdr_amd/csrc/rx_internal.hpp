@@ -132,7 +132,7 @@ constexpr int kMiscSamPhz = 13;   // AMDecodeSAM's PLL statics phzerror, fil_out
 constexpr int kMiscSamFil = 14;
 constexpr int kMiscSamOmega = 15;
 constexpr int kStNco = 200;     // 8 floats = two NcoState (16 B each); FFT_LENGTH 512 uses the first, the long
-                                // FFT lengths alternate between them from call to call (rx_kernels.hip)
+                                // FFT lengths alternate between them from call to call (RxArgs::nco_rd)
 constexpr int kStOverlap = 256; // fft_length floats: last_sample_buffer_L/R as [k][lane] (re,im)
 struct NcoState {
   uint64_t phase;  // arg(Osc_Vect_Q + j Osc_Vect_I) in turns, 0.64 fixed point

@@ -1,8 +1,23 @@
 // t41_sdr_amd/csrc/rx_launch.hpp -- the launchers of the kernel families, one translation unit each (rx_dispatch.hip picks).
 #pragma once
+#include <type_traits>
+
 #include "rx_kernels.hpp"
 
 namespace t41 {
+
+// run-time booleans -> template arguments: with_bools(f, b0, b1, ...) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...).
+// f is instantiated for every combination, so it takes booleans that its caller has normalised by the rules of the
+// product and leaves out, with `if constexpr`, the combinations those rules never produce.
+template <class F>
+hipError_t with_bools(F &&f) {
+  return f();
+}
+template <class F, class... Bools>
+hipError_t with_bools(F &&f, bool b, Bools... rest) {
+  auto bind = [&](auto B) { return with_bools([&](auto... bs) { return f(B, bs...); }, rest...); };
+  return b ? bind(std::true_type{}) : bind(std::false_type{});
+}
 
 // FFT_LENGTH 512, the whole chain in rx512_kernel<MODE, ...> (rx512_ssb.hip / rx512_am.hip / rx512_nfm.hip / rx512_sam.hip)
 hipError_t launch512_ssb(const RxArgs &a, hipStream_t s, bool debug);

@@ -1,6 +1,6 @@
 // t41_sdr_amd/csrc/wave_fft.hpp -- device helpers shared by the gfx950 kernels of this library:
 // packed-FP32 complex arithmetic, the register-resident 512-point FFT of one wavefront, DPP moves.
-// (Product code; included by rx_kernels.hip and nr_kernels.hip.)
+// (Product code; included by rx_device.hpp and nr_kernels.hip.)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-"""The arithmetic facts the pipelined AGC chain's block rests on (t41_sdr_amd/csrc/rx_kernels.hip: agc_fast_block_s,
+"""The arithmetic facts the pipelined AGC chain's block rests on (t41_sdr_amd/csrc/rx_chains.hpp: agc_fast_block_s,
 agc_block_phased; DSP_Fn.cpp:525-629), checked in exact rational arithmetic on the CPU -- no GPU, no oracle:
 
   1. the "sandwich": state 3's decay step is (float)((double)volts + (double)step * .05) in the reference (:614).  For the

@@ -195,7 +195,7 @@ def test_parity_agc(T, agcmode, mode, nfr, segs):
 @pytest.mark.parametrize("nch,mode,agcmode", [(1, 0, 1), (5, 0, 1), (17, 1, 2), (21, 2, 3), (37, 3, 4), (64, 0, 2)],
                          ids=["1ch-usb", "5ch-usb", "17ch-lsb", "21ch-am", "37ch-nfm", "64ch-usb"])
 def test_agc_pipelined_equals_barrier_form(T, nch, mode, agcmode):
-    """Calls of four frames or more run the pipelined AGC kernel (rx_kernels.hip: agc_prep_pipe -- the chain of one
+    """Calls of four frames or more run the pipelined AGC kernel (rx_chains.hpp: agc_prep_pipe -- the chain of one
     frame on a duty wave -- the one furthest ahead -- while the others work on the neighbouring frames), shorter ones the barrier form:
     the same samples and the same checkpoint, bit for bit, on ragged batches (last workgroup 5 of 16 channels)"""
     nfr = 14
@@ -223,7 +223,7 @@ def test_agc_min_volts_raised_mid_stream(T, agcmode):
     """a live CalcFilters() that lowers AGC_thresh raises min_volts (DSP_Fn.cpp:408-415) while lanes sit in
     their decay states with volts below the new floor.  The clamp of DSP_Fn.cpp:629 then RAISES volts at the next step
     -- the one case in which volts rises without an attack -- and the pipelined chain's per-block short-cut (one
-    comparison with the fast decay's threshold per four steps, rx_kernels.hip: agc_block_phased) must still leave the
+    comparison with the fast decay's threshold per four steps, rx_chains.hpp: agc_block_phased) must still leave the
     fast decay where the step-by-step forms do: pipelined == barrier form bit for bit, both within 1e-5 of the oracle
     that makes the same switch."""
     import torch
@@ -923,7 +923,7 @@ def test_segment_run_length_invariance(T, fft_length, monkeypatch):
         states.append(rx.get_state())
     monkeypatch.delenv("T41RX_SEG_RUN", raising=False)
     # FFT_LENGTH 4096 without T41RX_SEG_RUN runs the single-kernel form (front end inside the fast convolution's
-    # workgroup, rx_kernels.hip: fastconv_fused_kernel): the same arithmetic compiled into another kernel, compared
+    # workgroup, fastconv_kernels.hpp: fastconv_fused_kernel): the same arithmetic compiled into another kernel, compared
     # to rounding level; the explicit run lengths select the two-kernel pipeline and must agree bit for bit
     same = len(outs) - (1 if fft_length == 4096 else 0)
     for o, s in zip(outs[1:same], states[1:same]):

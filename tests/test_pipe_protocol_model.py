@@ -1,4 +1,4 @@
-"""A model of the pipelined AGC / SAM kernel's hand-over protocol (rx_kernels.hip: agc_prep_pipe and the PIPE block of
+"""A model of the pipelined AGC / SAM kernel's hand-over protocol (rx_chains.hpp: agc_prep_pipe and the PIPE block of
 rx512_kernel): 16 waves of one workgroup, each running the program
 
     for f in 0 .. F + 1:

@@ -44,7 +44,7 @@ def test_fast_sine_restatement(built):
 
 
 def test_pll_table_index_short_form():
-    """rx_kernels.hip: sam_table_index_pos() -- arm_sin_f32's index arithmetic for 0 <= x < 2, where the kernel's PLL keeps
+    """rx_chains.hpp: sam_table_index_pos() -- arm_sin_f32's index arithmetic for 0 <= x < 2, where the kernel's PLL keeps
     its arguments, in 5 instructions (x - floor(x), times 512, truncate) -- against the form as CMSIS writes it, on EVERY
     float32 of [0, 1.26] (what phase * 0.159154943092f and + 0.25f can give for a phase in [0, 2 pi]) and a sample up to 2"""
     def as_written(x):

@@ -1,4 +1,4 @@
-"""GPU box: soak of the pipelined AGC / SAM kernels (rx_kernels.hip: agc_prep_pipe) against the barrier form, bit for
+"""GPU box: soak of the pipelined AGC / SAM kernels (rx_chains.hpp: agc_prep_pipe) against the barrier form, bit for
 bit, on random shapes -- the hand-over between waves rests on the CU's in-order vector memory path and LDS flags; a
 race would show as a mismatch in some run.  One call of n frames (pipelined) against the same stream in calls of at
 most three frames (barrier form), outputs and checkpoints compared; now and then the full 4096 x 32 shape.

@@ -1,5 +1,5 @@
 // Microbenchmark: cost of VALU -> SGPR -> SALU -> VALU hops and of scalar instructions in a
-// single-wave dependent loop (the shape of the AGC chain, rx_kernels.hip: agc_fast_block).
+// single-wave dependent loop (the shape of the AGC chain, rx_chains.hpp: agc_fast_block).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 typedef unsigned long long lanemask;
