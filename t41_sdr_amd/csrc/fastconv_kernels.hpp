@@ -130,6 +130,7 @@ __global__ __launch_bounds__((64 * kFcWaves), kFcWavesPerSimd) void fastconv_ker
       for (int p = 0; p < R; ++p) {
         const int e = k + 512 * p;  // index into [previous | new]
         x1[h][p] = (p < R / 2) ? prev[e] : mid[e - D];
+        if (p < R / 2 && f == 0 && a.ovl_real) x1[h][p].y = 0.0f;  // NFM: last_sample_buffer_R is not part of the block
       }
     }
   };
@@ -167,7 +168,11 @@ __global__ __launch_bounds__((64 * kFcWaves), kFcWavesPerSimd) void fastconv_ker
       for (int p = 0; p < R; ++p) v[p] = x1[h][p];
       if (f == a.nframes4k - 1) {  // next call's "previous"
 #pragma unroll
-        for (int p = R / 2; p < R; ++p) reinterpret_cast<cf *>(st + kStOverlap)[k + 512 * p - D] = v[p];
+        for (int p = R / 2; p < R; ++p) {
+          cf *ov = reinterpret_cast<cf *>(st + kStOverlap) + (k + 512 * p - D);
+          if (a.ovl_real) ov->x = v[p].x;  // NFM: last_sample_buffer_L alone (Process.cpp:765-816), R stays as it is
+          else *ov = v[p];
+        }
       }
       dft_r<R, false>(v);
 #pragma unroll

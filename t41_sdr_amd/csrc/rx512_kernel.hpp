@@ -995,16 +995,30 @@ __global__ __launch_bounds__((Rx512Geo<MODE, PART, AGC, PIPE>::kWaves * 64), 4) 
         wave_sync();
   #pragma unroll
         for (int j = 0; j < 4; ++j) v[4 + j] = tb[lane + 64 * j];
+        // NFM's overlap-save is the real one behind the discriminator (Process.cpp:765-816): it reads and writes
+        // last_sample_buffer_L alone.  The R half of the block is taken as zero and stays what the last complex mode
+        // left there, for the first frame after the next mode change to find.
+        constexpr bool OVL_REAL = MODE == kModeNfm;
         if (KEEP) {  // the previous block waits in LDS; the new one takes its place
           cf *ov = reinterpret_cast<cf *>(lds + G::kOV);
   #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = ov[64 * j + lane];
   #pragma unroll
-          for (int j = 0; j < 4; ++j) ov[64 * j + lane] = v[4 + j];
+          for (int j = 0; j < 4; ++j) {
+            if (OVL_REAL) ov[64 * j + lane].x = v[4 + j].x;
+            else ov[64 * j + lane] = v[4 + j];
+          }
         } else {
           cf *ov = reinterpret_cast<cf *>(st + kStOverlap);
   #pragma unroll
-          for (int j = 0; j < 4; ++j) ov[64 * j + lane] = v[4 + j];
+          for (int j = 0; j < 4; ++j) {
+            if (OVL_REAL) ov[64 * j + lane].x = v[4 + j].x;
+            else ov[64 * j + lane] = v[4 + j];
+          }
+        }
+        if (OVL_REAL) {
+  #pragma unroll
+          for (int j = 0; j < 4; ++j) v[j].y = 0.0f;
         }
       }
 

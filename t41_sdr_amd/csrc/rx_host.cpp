@@ -596,6 +596,7 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
   }
   a.q15 = q15 ? 1 : 0;
   a.nco_rd = ctx->nco_sel;
+  a.ovl_real = ctx->params.mode == T41RX_DEMOD_NFM ? 1 : 0;
   a.nfm_atan = (ctx->params.mode == T41RX_DEMOD_NFM && ctx->params.nfm_demod == 1) ? 1 : 0;
   {
     // Segment-parallel kernels of the long-FFT pipeline: about 4096 wave slots (256 CUs x 16) to

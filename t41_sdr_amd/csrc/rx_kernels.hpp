@@ -64,6 +64,8 @@ struct RxArgs {
   int q15;                 // 1: I, Q, out point at int16 (q15) samples instead of f32 (Process.cpp:102-111, 936)
   int nfm_atan;            // NFM: 1 = atan2 discriminator + block-wise de-emphasis (t41rx_params::nfm_demod)
   int seg_run;             // long FFT, segment-parallel kernels: consecutive segments one wave runs
+  int ovl_real;            // long FFT, NFM: the overlap block is real (Process.cpp:765-816) -- its imaginary half, last_sample_buffer_R,
+                           // is read as zero and left as the last complex mode wrote it
   int nco_rd;              // long FFT: which of the two NcoState copies holds the call's start state (the other is written)
   // noise reduction / notch pipeline (FFT_LENGTH 512, tap kernels): when set, the fused kernel stops behind the
   // demodulator and leaves the frame's 256 audio samples @24 kS/s here, [nchan][nframes * 256] in time order;
