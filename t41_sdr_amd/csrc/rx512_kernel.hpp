@@ -61,6 +61,12 @@ template <int MODE, int PART, bool AGC, bool PIPE>
 using Rx512Geo = Geo<PART, geo4(MODE, AGC) && !PIPE>;
 static_assert(!Geo<0>::kResident || Geo<0>::kTotal * sizeof(float) == 160 * 1024, "PART 0: one workgroup owns the CU's LDS");
 static_assert(Geo<1>::kTotal * sizeof(float) == 40960, "PART 1/2: four workgroups per CU");
+// The pipelined variants address RxArgs::agc_pipe with element arithmetic of their own (stated through pipe_layout() the
+// same offsets compile to other scalar instructions in every PIPE kernel): held to the one layout here
+static_assert(pipe_layout(7).counters == (size_t)7 * kPipeSlots * kPipeSlotFloats * sizeof(float) &&
+              pipe_layout(7).timeout == pipe_layout(7).counters + ((size_t)7 + 15) * 16 * sizeof(unsigned long long) &&
+              pipe_layout(7).second == pipe_layout(7).counters + ((size_t)7 + 16) * 32 * sizeof(float) && kPipeStatWords == 16,
+              "rx512_kernel's pipe_err / pipe_stat / sam_slots arithmetic follows pipe_layout()");
 static_assert(!Geo<0>::kResident || (Geo<0>::kH1 + 24 <= Geo<0>::kSlice && Geo<0>::kScr + 8 * kFftRow * 2 <= Geo<0>::kXF &&
                                      Geo<0>::kI1 + 284 <= Geo<0>::kXF && Geo<0>::kScr >= 68), "resident LDS layout");
 
@@ -1648,11 +1654,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, PART, AGC, PIPE>::kWaves * 64), 4) 
     if (lane < 8) st[kStInt2 + lane] = (lane == 0) ? 0.0f : hist2c;
   }
   if (PART != 2 && lane == 0) {
-    if (!SEGPAR) {
-      ncs->phase = phase0;
-      ncs->r = osc_r;
-      st[kStMisc + kMiscDc] = dc_carry;
-    } else if (seg0 == 0) {  // (phase0 / dc_carry: advanced to the end of the call above)
+    if (!SEGPAR || seg0 == 0) {  // (SEGPAR: phase0 / dc_carry were advanced to the end of the call above)
       ncs->phase = phase0;
       ncs->r = osc_r;
       st[kStMisc + kMiscDc] = dc_carry;

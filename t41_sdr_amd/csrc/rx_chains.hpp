@@ -753,7 +753,7 @@ __device__ __forceinline__ void agc_apply(const cf (&v)[8], float4 agst, float *
 // tests/test_pipe_protocol_model.py) together with instruction issue (2528 VALU instructions per wave-frame against
 // the AGC-off kernel's 1767 at the same 62 % VALU utilisation: every phase is stretched, the chain included).
 // ------------------------------------------------------------------------------------------
-constexpr int kPipeSlots = 3, kPipeSlotFloats = 1024;  // ring_max -> volts [256] | |popped| [256] | popped re [256] | popped im [256] (AM only)
+// (kPipeSlots, kPipeSlotFloats and the buffer's layout: rx_internal.hpp, pipe_layout)
 constexpr int kPipeFlags = 1008;                        // float index in the table area: ready[3], done, next frame to claim
 constexpr int kPipeSpinCap = 1 << 20;
 

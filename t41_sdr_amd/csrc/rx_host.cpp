@@ -317,20 +317,6 @@ int ensure_eq(t41rx_ctx *ctx) {
   return ensure_zeroed(ctx->d_eq, sizeof(float) * kEqStateFloats * (size_t)ctx->nchan, "receive-equalizer");
 }
 
-// The pipelined kernels' buffer (RxArgs::agc_pipe), byte offsets for nchan channels: the first stage's slots, three of
-// 1024 floats per channel (rx_chains.hpp: kPipeSlots, kPipeSlotFloats); blocks of 16 counters for nchan + 16 waves -- a
-// wave's own block in the -DT41RX_PIPE_STAT diagnostic build, and first in the last block the count of waits that ran out
-// (rx_chains.hpp: pipe_wait_ge); then the second stage's slots, as many as the first's (rx512_kernel.hpp, PSA: the
-// synchronous detector behind the AGC runs two chains per frame).  The kernels derive the same offsets from a.nchan.
-struct PipeLayout {
-  size_t counters, timeout, second, bytes;
-};
-PipeLayout pipe_layout(int nchan) {
-  const size_t slots = (size_t)nchan * 3 * 1024 * sizeof(float), block = 16 * sizeof(unsigned long long);
-  const size_t second = slots + ((size_t)nchan + 16) * block;
-  return {slots, second - block, second, second + slots};
-}
-
 // a broken hand-over protocol of the pipelined kernels leaves wrong samples and a count of waits that ran out, not a hung
 // GPU -- reported at the calls that synchronise anyway
 int pipe_timeouts(const t41rx_ctx *ctx) {  // < 0: the counter could not be read

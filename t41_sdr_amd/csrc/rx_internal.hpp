@@ -152,4 +152,20 @@ constexpr int kAgcStFba = 0, kAgcStHba = 1, kAgcStVolts = 2, kAgcStSave = 3, kAg
 constexpr size_t st_agc(int fft_length) { return (size_t)kStOverlap + (size_t)fft_length; }
 constexpr size_t state_floats(int fft_length) { return st_agc(fft_length) + kAgcHistFloats + kAgcScalars; }
 
+// The pipelined kernels' buffer (RxArgs::agc_pipe), byte offsets for nchan channels: the first stage's slots, kPipeSlots of
+// kPipeSlotFloats floats per channel; blocks of kPipeStatWords counters for nchan + 16 waves -- a wave's own block in the
+// -DT41RX_PIPE_STAT diagnostic build, and first in the last block the count of waits that ran out (rx_chains.hpp:
+// pipe_wait_ge); then the second stage's slots, as many as the first's (rx512_kernel.hpp, PSA: the synchronous detector
+// behind the AGC runs two chains per frame).  Host (rx_host.cpp) and kernels (rx512_kernel.hpp) both take the offsets from here.
+constexpr int kPipeSlots = 3, kPipeSlotFloats = 1024;  // ring_max -> volts [256] | |popped| [256] | popped re [256] | popped im [256] (AM only)
+constexpr int kPipeStatWords = 16;
+struct PipeLayout {
+  size_t counters, timeout, second, bytes;
+};
+constexpr PipeLayout pipe_layout(int nchan) {
+  const size_t slots = (size_t)nchan * kPipeSlots * kPipeSlotFloats * sizeof(float), block = kPipeStatWords * sizeof(unsigned long long);
+  const size_t second = slots + ((size_t)nchan + 16) * block;
+  return {slots, second - block, second, second + slots};
+}
+
 }  // namespace t41
