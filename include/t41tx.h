@@ -9,7 +9,9 @@
  * correction, interpolate by 2 (48 taps) and by 4 (32 taps) per channel, x 20, arm_float_to_q15.
  * The globals it reads become t41tx_params; its static CMSIS instance states (T41_SDR.ino:278-299)
  * become per-channel state owned by the context.  Citations: software/T41_SDR/ of the reference.
- * Not restated: the transmit equaliser (DoExciterEQ, xmitEQFlag = OFF) and the CW / data exciters.
+ * The transmit equaliser (xmitEQFlag, DoExciterEQ(), Filter.cpp:176-224) is restated as an optional stage between the
+ * decimators and the Hilbert pair, off by default like the firmware's; its switch, levels and band table are context
+ * switches below, not t41tx_params fields.  Not restated: the CW and data exciters.
  */
 #ifndef T41TX_H
 #define T41TX_H
@@ -46,6 +48,39 @@ T41RX_API int t41tx_destroy(t41tx_ctx *ctx);
 T41RX_API int t41tx_set_params(t41tx_ctx *ctx, const t41tx_params *p);  /* states are kept, like the firmware's */
 T41RX_API int t41tx_reset(t41tx_ctx *ctx);                               /* all CMSIS instance states to zero */
 T41RX_API int t41tx_n_channels(const t41tx_ctx *ctx);
+
+/* The transmit equaliser (Exciter.cpp:94-98): 14 bands of 4 cascaded arm_biquad_cascade_df2T_f32 sections on the frame's
+ * 256 samples @24 kS/s, each band's output times its level (negated for bands 1, 3, .., 13), the 14 products summed
+ * as EQ1 + EQ2, + EQ3, .., + EQ14, in place, before the copy L -> R: both Hilbert filters see equalised samples.
+ * t41tx_set_transmit_eq_bands(): the firmware's EQ_Band1Coeffs .. EQ_Band14Coeffs (the S1_Xmt .. S14_Xmt instances
+ *   point at the receive equaliser's tables, Filter.cpp:89-102) as [14][4][5] floats, {b0, b1, b2, a1, a2} per section
+ *   with the a's negated (CMSIS DF2T order).  The library has no table of its own: it must be loaded before the
+ *   equaliser can be switched on.  T41RX_ERR_ARG for NULL or a non-finite value.  Kept across t41tx_set_params(); a new
+ *   table takes effect from the next process call and does not reset the filter memories.
+ * t41tx_set_transmit_eq(): xmitEQFlag 0 or 1 (T41RX_ERR_ARG otherwise, and for 1 before a band table is loaded).
+ *   equalizerXmt = EEPROMData.equalizerXmt[14], or NULL to keep the current levels; they start at the firmware's
+ *   {0, 0, 100, 100, 100, 100, 100, 100, 100, 100, 100, 0, 0, 0} (gwv.cpp:50).  Any int is taken as the firmware would
+ *   hold it.  As written in the reference: DoExciterEQ() stores (float)level / 100.0 into an int array
+ *   (Filter.cpp:178, gwv.h:44), so a level counts in whole hundreds, truncated toward zero -- 99 -> 0, 100 and 199 -> 1,
+ *   200 -> 2, -50 -> 0, -100 -> -1.  Switch and levels are kept across t41tx_set_params().
+ * The memories xmt_EQ_Band1_state .. xmt_EQ_Band14_state (112 floats per channel, Filter.cpp:74-87) start at zero and
+ * change only while the equaliser runs (all 14 cascades advance then, even where a level is 0): switched off and on
+ * again they are stale, as in the reference.  t41tx_reset() zeroes them. */
+T41RX_API int t41tx_set_transmit_eq_bands(t41tx_ctx *ctx, const float *coeffs);
+T41RX_API int t41tx_set_transmit_eq(t41tx_ctx *ctx, int xmitEQFlag, const int32_t *equalizerXmt);
+/* 0 / 1, or T41RX_ERR_ARG for a NULL context; the 14 levels into equalizerXmt_out unless it is NULL */
+T41RX_API int t41tx_get_transmit_eq(const t41tx_ctx *ctx, int32_t *equalizerXmt_out);
+
+/* Checkpoint of every channel's memories: 8 int32 words
+ *     [0] magic "T41X"  [1] T41RX_ABI_VERSION  [2] n_channels  [3] floats per channel record  [4..7] reserved, zero
+ * then n_channels records of that many floats: the delay lines of every FIR and the equaliser's 112 floats, always
+ * present, so t41tx_state_bytes() is fixed for a context (0 for a NULL one).  t41tx_get_state() synchronises the device
+ * first (T41RX_ERR_STATE for a buffer smaller than t41tx_state_bytes()).  t41tx_set_state() refuses (T41RX_ERR_STATE)
+ * another magic, ABI, channel count, record size or byte count and any non-finite float, and then changes nothing.
+ * The equaliser's switch, levels and band table are configuration, not state: a checkpoint does not carry them. */
+T41RX_API size_t t41tx_state_bytes(const t41tx_ctx *ctx);
+T41RX_API int    t41tx_get_state(t41tx_ctx *ctx, void *host_buf, size_t bytes);
+T41RX_API int    t41tx_set_state(t41tx_ctx *ctx, const void *host_buf, size_t bytes);
 
 /* ExciterIQData() on every channel, n_frames consecutive frames of 2048 samples per queue.
  * Device pointers, [n_channels][n_frames * 2048] int16 each; dQ_in_R_Ex may be NULL: the firmware

@@ -4,8 +4,10 @@
 // without a HIP device every create / process call fails with T41RX_ERR_HIP.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "last_error.hpp"  // fail(): failures reach t41rx_last_error(), like the receive path's
 #include "tx_internal.hpp"
@@ -16,10 +18,16 @@ struct t41tx_ctx {
   int device = 0;
   int nchan = 0;
   t41tx_params params{};
-  float *d_state = nullptr;
+  float *d_state = nullptr;  // [nchan][kTxDelayFloats] delay lines, then [nchan][kTxEqStateFloats] equaliser memories
   TxCoef *d_coef = nullptr;
   int16_t *d_in = nullptr, *d_outL = nullptr, *d_outR = nullptr;  // staging of the host-pointer entry
   size_t staging = 0;
+  // transmit equaliser (xmitEQFlag, Exciter.cpp:94-98; t41tx_set_transmit_eq): the caller's band table and the levels
+  // EEPROMData.equalizerXmt (gwv.cpp:50).  Configuration: kept across t41tx_set_params(), not part of a checkpoint.
+  int eq_on = 0;
+  bool eq_have_bands = false;
+  float eq_coef[kTxEqCoefs] = {};
+  int32_t eq_levels[kTxEqBands] = {0, 0, 100, 100, 100, 100, 100, 100, 100, 100, 100, 0, 0, 0};
 };
 
 namespace {
@@ -37,6 +45,12 @@ struct Guard {
 // every mode the receive side accepts: ExciterIQData() runs in all of them and only applies the TX
 // IQ correction in LSB / USB (Exciter.cpp:117-140)
 bool valid(const t41tx_params &p) { return (p.mode >= T41RX_DEMOD_USB && p.mode <= T41RX_DEMOD_NFM) || p.mode == T41RX_DEMOD_SAM; }
+// the checkpoint: 8 int32 words, then kTxStateFloats floats per channel
+constexpr uint32_t kTxStateMagic = 0x58313454u;  // "T41X"
+constexpr size_t kTxStateHeaderBytes = 8 * sizeof(int32_t);
+size_t record_bytes(const t41tx_ctx *c) { return sizeof(float) * kTxStateFloats * (size_t)c->nchan; }
+float *eq_state(const t41tx_ctx *c) { return c->d_state + (size_t)kTxDelayFloats * (size_t)c->nchan; }
+
 void free_ctx(t41tx_ctx *c) {
   if (!c) return;
   (void)hipFree(c->d_state);
@@ -112,6 +126,82 @@ int t41tx_reset(t41tx_ctx *ctx) {
 
 int t41tx_n_channels(const t41tx_ctx *ctx) { return ctx ? ctx->nchan : fail(T41RX_ERR_ARG, "null argument"); }
 
+int t41tx_set_transmit_eq_bands(t41tx_ctx *ctx, const float *coeffs) {
+  if (!ctx || !coeffs) return fail(T41RX_ERR_ARG, "null argument");
+  for (int i = 0; i < kTxEqCoefs; ++i)
+    if (!std::isfinite(coeffs[i])) return fail(T41RX_ERR_ARG, "transmit-equaliser band table: non-finite coefficient");
+  std::memcpy(ctx->eq_coef, coeffs, sizeof(ctx->eq_coef));  // (passed by value to every launch: the next call uses it)
+  ctx->eq_have_bands = true;
+  return T41RX_OK;
+}
+
+int t41tx_set_transmit_eq(t41tx_ctx *ctx, int xmitEQFlag, const int32_t *equalizerXmt) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (xmitEQFlag != 0 && xmitEQFlag != 1) return fail(T41RX_ERR_ARG, "xmitEQFlag must be 0 or 1");
+  if (xmitEQFlag && !ctx->eq_have_bands)
+    return fail(T41RX_ERR_ARG, "transmit equaliser: no band table loaded (t41tx_set_transmit_eq_bands)");
+  if (equalizerXmt) std::memcpy(ctx->eq_levels, equalizerXmt, sizeof(ctx->eq_levels));
+  ctx->eq_on = xmitEQFlag;
+  return T41RX_OK;
+}
+
+int t41tx_get_transmit_eq(const t41tx_ctx *ctx, int32_t *equalizerXmt_out) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (equalizerXmt_out) std::memcpy(equalizerXmt_out, ctx->eq_levels, sizeof(ctx->eq_levels));
+  return ctx->eq_on;
+}
+
+size_t t41tx_state_bytes(const t41tx_ctx *ctx) { return ctx ? kTxStateHeaderBytes + record_bytes(ctx) : 0; }
+
+int t41tx_get_state(t41tx_ctx *ctx, void *host_buf, size_t bytes) {
+  if (!ctx || !host_buf) return fail(T41RX_ERR_ARG, "null argument");
+  if (bytes < t41tx_state_bytes(ctx)) return fail(T41RX_ERR_STATE, "state buffer too small");
+  Guard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  const int32_t hdr[8] = {(int32_t)kTxStateMagic, T41RX_ABI_VERSION, ctx->nchan, kTxStateFloats, 0, 0, 0, 0};
+  std::memcpy(host_buf, hdr, sizeof(hdr));
+  const size_t n = (size_t)kTxStateFloats * (size_t)ctx->nchan;
+  std::vector<float> dev(n);
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(dev.data(), ctx->d_state, sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(T41RX_ERR_HIP, "state copy out failed");
+  // a channel's record: its delay lines, then its equaliser memories
+  char *out = static_cast<char *>(host_buf) + kTxStateHeaderBytes;
+  const float *eq = dev.data() + (size_t)kTxDelayFloats * (size_t)ctx->nchan;
+  for (int c = 0; c < ctx->nchan; ++c, out += sizeof(float) * kTxStateFloats) {
+    std::memcpy(out, dev.data() + (size_t)kTxDelayFloats * c, sizeof(float) * kTxDelayFloats);
+    std::memcpy(out + sizeof(float) * kTxStEq, eq + (size_t)kTxEqStateFloats * c, sizeof(float) * kTxEqStateFloats);
+  }
+  return T41RX_OK;
+}
+
+int t41tx_set_state(t41tx_ctx *ctx, const void *host_buf, size_t bytes) {
+  if (!ctx || !host_buf) return fail(T41RX_ERR_ARG, "null argument");
+  if (bytes < kTxStateHeaderBytes) return fail(T41RX_ERR_STATE, "state size mismatch");
+  int32_t hdr[8];
+  std::memcpy(hdr, host_buf, sizeof(hdr));
+  if ((uint32_t)hdr[0] != kTxStateMagic || hdr[1] != T41RX_ABI_VERSION || hdr[2] != ctx->nchan || hdr[3] != kTxStateFloats)
+    return fail(T41RX_ERR_STATE, "checkpoint header does not match this context (magic / abi / channels / record size)");
+  if (bytes != t41tx_state_bytes(ctx)) return fail(T41RX_ERR_STATE, "state size mismatch");
+  // everything is checked before anything is written: a refused checkpoint changes nothing
+  const size_t n = (size_t)kTxStateFloats * (size_t)ctx->nchan;
+  std::vector<float> rec(n);  // (host_buf need not be aligned for float)
+  std::memcpy(rec.data(), static_cast<const char *>(host_buf) + kTxStateHeaderBytes, sizeof(float) * n);
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(rec[i])) return fail(T41RX_ERR_STATE, "checkpoint: non-finite value in a channel record");
+  std::vector<float> dev(n);
+  float *eq = dev.data() + (size_t)kTxDelayFloats * (size_t)ctx->nchan;
+  for (int c = 0; c < ctx->nchan; ++c) {
+    const float *r = rec.data() + (size_t)kTxStateFloats * c;
+    std::memcpy(dev.data() + (size_t)kTxDelayFloats * c, r, sizeof(float) * kTxDelayFloats);
+    std::memcpy(eq + (size_t)kTxEqStateFloats * c, r + kTxStEq, sizeof(float) * kTxEqStateFloats);
+  }
+  Guard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(ctx->d_state, dev.data(), sizeof(float) * n, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(T41RX_ERR_HIP, "state copy in failed");
+  return T41RX_OK;
+}
+
 int t41tx_process_device_q15(t41tx_ctx *ctx, const int16_t *dL, const int16_t *dR, int16_t *oL, int16_t *oR, int n_frames,
                              void *hip_stream) {
   (void)dR;  // decimated and then overwritten by the L channel in the reference (Exciter.cpp:85, 89, 98)
@@ -132,7 +222,24 @@ int t41tx_process_device_q15(t41tx_ctx *ctx, const int16_t *dL, const int16_t *d
   a.corr_on = (ctx->params.mode == T41RX_DEMOD_LSB || ctx->params.mode == T41RX_DEMOD_USB) ? 1 : 0;
   a.i_scale = (ctx->params.mode == T41RX_DEMOD_LSB) ? +ctx->params.IQXAmpCorrectionFactor : -ctx->params.IQXAmpCorrectionFactor;
   a.iq_phase = ctx->params.IQXPhaseCorrectionFactor;
-  if (launch_tx(a, (hipStream_t)hip_stream) != hipSuccess) return fail(T41RX_ERR_HIP, "kernel launch failed");
+  hipError_t e;
+  if (ctx->eq_on) {
+    TxEqArgs q{};
+    static_cast<TxArgs &>(q) = a;
+    q.eq_state = eq_state(ctx);
+    std::memcpy(q.eq_coef, ctx->eq_coef, sizeof(q.eq_coef));
+    for (int b = 0; b < kTxEqBands; ++b) {
+      // equalizerXmt[b] = (float)EEPROMData.equalizerXmt[b] / 100.0 into an int array (Filter.cpp:178, gwv.h:44): the
+      // level truncated toward zero to a whole number; arm_scale_f32 takes it, negated as an int for bands 1, 3, .., 13
+      // (Filter.cpp:195-208), as a float
+      const int whole = (int)((double)(float)ctx->eq_levels[b] / 100.0);
+      q.eq_scale[b] = (float)((b % 2 == 0) ? -whole : whole);
+    }
+    e = launch_tx_eq(q, (hipStream_t)hip_stream);
+  } else {
+    e = launch_tx(a, (hipStream_t)hip_stream);
+  }
+  if (e != hipSuccess) return fail(T41RX_ERR_HIP, "kernel launch failed");
   return T41RX_OK;
 }
 

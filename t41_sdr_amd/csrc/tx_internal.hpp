@@ -30,7 +30,18 @@ constexpr int kTxStInt1I = 272;  // 23 (+1)
 constexpr int kTxStInt1Q = 296;  // 23 (+1)
 constexpr int kTxStInt2I = 320;  // 7 (+1)
 constexpr int kTxStInt2Q = 328;  // 7 (+1)
-constexpr int kTxStateFloats = 336;
+constexpr int kTxDelayFloats = 336;  // the delay lines above: the kernel's stride in [nchan][kTxDelayFloats]
+
+// the transmit equaliser (DoExciterEQ(), Filter.cpp:176-224): 14 bands of 4 DF2T sections, as the receive one
+constexpr int kTxEqBands = 14;
+constexpr int kTxEqSections = 4 * kTxEqBands;   // 56: one per lane
+constexpr int kTxEqCoefs = 5 * kTxEqSections;   // {b0, b1, b2, a1, a2} per section, a's negated (CMSIS DF2T)
+// xmt_EQ_Band1_state .. xmt_EQ_Band14_state (Filter.cpp:74-87): [band][stage][d1, d2] = 2 * lane, 2 * lane + 1.  On the
+// device they lie behind all the delay lines, [nchan][kTxEqStateFloats] (the delay lines keep their stride, and with it
+// the equaliser-off kernel its code); a checkpoint's channel record holds both.
+constexpr int kTxEqStateFloats = 2 * kTxEqSections;  // 112
+constexpr int kTxStEq = kTxDelayFloats;              // where a channel record holds them
+constexpr int kTxStateFloats = kTxDelayFloats + kTxEqStateFloats;  // 448 per channel: record size and device memory
 
 struct TxArgs {
   const int16_t *__restrict__ inL;
@@ -44,6 +55,15 @@ struct TxArgs {
   int corr_on;     // LSB or USB
 };
 
-hipError_t launch_tx(const TxArgs &a, hipStream_t s);
+// the equaliser-on kernel's arguments: the caller's band table and the signed levels travel by value, so a change takes
+// effect at the next call
+struct TxEqArgs : TxArgs {
+  float *__restrict__ eq_state;  // [nchan][kTxEqStateFloats]
+  float eq_coef[kTxEqCoefs];  // [band][stage][5]
+  float eq_scale[16];         // per band: -xmtEQ_LevelScale for bands 1, 3, .., 13, + for 2, 4, .., 14 (Filter.cpp:197-210)
+};
+
+hipError_t launch_tx(const TxArgs &a, hipStream_t s);       // xmitEQFlag off
+hipError_t launch_tx_eq(const TxEqArgs &a, hipStream_t s);  // xmitEQFlag on
 
 }  // namespace t41

@@ -28,6 +28,12 @@ TX_SYMBOLS = {
     "t41tx_n_channels": (C.c_int, [_vp]),
     "t41tx_process_device_q15": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "t41tx_process_host_q15": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "t41tx_set_transmit_eq_bands": (C.c_int, [_vp, _vp]),
+    "t41tx_set_transmit_eq": (C.c_int, [_vp, C.c_int, _vp]),
+    "t41tx_get_transmit_eq": (C.c_int, [_vp, _vp]),
+    "t41tx_state_bytes": (C.c_size_t, [_vp]),
+    "t41tx_get_state": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "t41tx_set_state": (C.c_int, [_vp, _vp, C.c_size_t]),
 }
 _bound = False
 
@@ -79,6 +85,47 @@ class TxChain:
 
     def reset(self):
         check(self._lib.t41tx_reset(self._ctx))
+
+    def set_transmit_eq_bands(self, coeffs):
+        """The transmit equaliser's band table (t41tx_set_transmit_eq_bands): the firmware's EQ_Band1Coeffs ..
+        EQ_Band14Coeffs as [14][4][5] or [14][20], {b0, b1, b2, a1, a2} per section with the a's negated.  Kept across
+        set_params(); the filter memories are not reset."""
+        c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.float32))
+        if c.size != 14 * 4 * 5 or c.shape[0] != 14:
+            raise ValueError("transmit-EQ band table must be [14][4][5] or [14][20], got %r" % (c.shape,))
+        check(self._lib.t41tx_set_transmit_eq_bands(self._ctx, c.ctypes.data_as(C.c_void_p)))
+
+    def set_transmit_eq(self, on, levels=None):
+        """xmitEQFlag and EEPROMData.equalizerXmt (Exciter.cpp:94-98, Filter.cpp:176-224): the equaliser between the
+        decimators and the Hilbert pair (t41tx_set_transmit_eq; 0 / 1, a band table loaded first).  levels: 14 ints, or
+        None to keep the current ones (the firmware's defaults until set); a level counts in whole hundreds, as in the
+        reference.  Kept across set_params()."""
+        if levels is None:
+            check(self._lib.t41tx_set_transmit_eq(self._ctx, int(on), None))
+            return
+        lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
+        if lv.shape != (14,):
+            raise ValueError("transmit-EQ levels must be 14 ints, got %r" % (lv.shape,))
+        check(self._lib.t41tx_set_transmit_eq(self._ctx, int(on), lv.ctypes.data_as(C.c_void_p)))
+
+    def get_transmit_eq(self):
+        """(on, levels): the transmit equaliser's switch and its 14 levels"""
+        lv = np.zeros(14, np.int32)
+        v = self._lib.t41tx_get_transmit_eq(self._ctx, lv.ctypes.data_as(C.c_void_p))
+        if v < 0:
+            check(v)
+        return v, lv
+
+    def get_state(self):
+        """checkpoint of every channel's memories (t41tx_get_state) as a numpy uint8 array; synchronises"""
+        n = self._lib.t41tx_state_bytes(self._ctx)
+        buf = np.zeros(n, dtype=np.uint8)
+        check(self._lib.t41tx_get_state(self._ctx, buf.ctypes.data_as(C.c_void_p), n))
+        return buf
+
+    def set_state(self, buf):
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        check(self._lib.t41tx_set_state(self._ctx, buf.ctypes.data_as(C.c_void_p), buf.size))
 
     def ExciterIQData(self, Q_in_L_Ex, Q_in_R_Ex=None):
         """int16 (q15) microphone samples [n_channels, k * 2048] -> (Q_out_L_Ex, Q_out_R_Ex), the I and Q

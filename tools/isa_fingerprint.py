@@ -30,6 +30,10 @@ def fingerprints(lib):
             dis = subprocess.check_output([OBJDUMP, "-d", os.path.join(t, co)], text=True)
             name, body, base = None, [], None
             def flush():
+                # the padding behind a code object's last s_endpgm (s_nop / s_code_end up to the section's alignment) belongs
+                # to no kernel: without this the last kernel of a translation unit changes hash when another one joins it
+                while body and body[-1].split()[0] in ("s_nop", "s_code_end") and any(b.startswith("s_endpgm") for b in body):
+                    body.pop()
                 if name is not None and body:
                     out[name] = {"sha": hashlib.sha256("\n".join(body).encode()).hexdigest()[:20], "instructions": len(body)}
             for line in dis.splitlines():
