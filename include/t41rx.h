@@ -192,6 +192,54 @@ T41RX_API int t41rx_set_receive_eq(t41rx_ctx *ctx, int receiveEQFlag, const int3
 /* 0 / 1, or T41RX_ERR_ARG for a NULL context; the 14 levels into equalizerRec_out unless it is NULL */
 T41RX_API int t41rx_get_receive_eq(const t41rx_ctx *ctx, int32_t *equalizerRec_out);
 
+/* CW receive (Process.cpp:878-913): the block ProcessIQData() runs in T41State == CW_RECEIVE, on the audio @24 kS/s
+ * behind the noise blanker and in front of the interpolators -- first the tone detector of DoCWReceiveProcessing()
+ * (CWProcessing.cpp:322-373), then the narrow audio filter CWFilterIndex selects.  fft_length 512 only.
+ *
+ * Gating: both stages run only while t41rx_params.xmtMode == T41RX_CW_MODE.  That is the firmware's condition in
+ * receive: loop() turns xmtMode == CW_MODE with the key up into radioState = CW_RECEIVE_STATE (T41_SDR.ino:1039-1040),
+ * whose state machine sets T41State = CW_RECEIVE (T41_SDR.ino:1144-1148); xmtMode itself is the mode button's
+ * (ButtonProc.cpp:324-354).  With any other xmtMode the settings below are kept, nothing runs, no memory advances and
+ * d_cw is not written.
+ *
+ * t41rx_set_cw_tables(): audio_filters[5][6][5] = the firmware's CW_AudioFilterCoeffs1 .. 5 (FIR.cpp:15-65), {b0, b1,
+ *   b2, a1, a2} per section in CMSIS DF2T order with the a's negated as the firmware stores them; decode_fir[64] =
+ *   CW_Filter_Coeffs2 (FIR.cpp:93).  Either may be NULL to keep what is loaded.  The library has no table of its own.
+ *   T41RX_ERR_ARG for a non-finite value (nothing is loaded then).  Kept across t41rx_set_params() / t41rx_set_coeffs();
+ *   a new table takes effect from the next process call and resets no memory.
+ * t41rx_set_cw_filter(): CWFilterIndex 0 .. 4 (0.8 / 1.0 / 1.3 / 1.8 / 2.0 kHz low-pass, six
+ *   arm_biquad_cascade_df2T_f32 sections each, CWProcessing.cpp:36-48) or 5 = off (the default, as in the firmware);
+ *   T41RX_ERR_ARG otherwise and for 0 .. 4 before the filter tables are loaded, T41RX_ERR_UNSUPPORTED for 0 .. 4 at a
+ *   long fft_length.  Every index has its own memory: a filter switched away from and back resumes from its stale
+ *   memory, as in the firmware.  While the filter runs, the interpolators and the volume behind it (Process.cpp:917-937)
+ *   are computed in the firmware's own operations and order (no volume folded into the taps, no fused multiply-adds).
+ *   t41rx_get_cw_filter(): the index, or T41RX_ERR_ARG for a NULL context.
+ * t41rx_set_cw_detector(): decoderFlag 0 or 1 (T41RX_ERR_ARG otherwise).  With 1, every 256-sample block goes through
+ *   the 64-tap decode FIR (arm_fir_f32), its full correlation with a 750 Hz sine (arm_correlate_f32, 511 lags; sinBuffer,
+ *   Utility.cpp:72-74) and arm_max_f32 over the lags, and goertzel_mag() at 750 Hz (CWProcessing.cpp:830-857); d_cw, a
+ *   device pointer [n_channels][n_frames][4] (n_frames of the process call), receives corrResultL, goertzelMagnitude,
+ *   aveCorrResult and combinedCoeff = 10 * aveCorrResult * 100 * goertzelMagnitude of every frame.  aveCorrResult is
+ *   (corrResultR + corrResultL) / 2 with corrResultR still the block before's (CWProcessing.cpp:339 runs before :348;
+ *   0 at power-on).  The comparison `combinedCoeff > 50` (CWProcessing.cpp:365) and the Morse decoder behind it
+ *   (DoCWDecoding(), timed by millis()) stay with the caller.  T41RX_ERR_ARG for 1 with a NULL d_cw, max_frames <= 0 or
+ *   before decode_fir is loaded; T41RX_ERR_UNSUPPORTED for 1 at a long fft_length.  A process call with more than
+ *   max_frames frames is refused (T41RX_ERR_ARG), as for the stage taps.  t41rx_get_cw_detector(): 0 / 1, or
+ *   T41RX_ERR_ARG for a NULL context.
+ * One audio stream: the library carries float_buffer_L only.  The filter reads L only; the detector reads L and R, so
+ *   it is exact only while the stages in front of it leave them equal.  A process call with the detector running is
+ *   refused (T41RX_ERR_UNSUPPORTED, t41rx_last_error() names the stage) when the receive equalizer (writes L only),
+ *   nrOptionSelect 1 (x30 on L only) or 3 (Xanr() writes R, x1.5 on L only) is on and neither the notch nor the noise
+ *   blanker (both end in R -> L) runs behind it.
+ * Context switches, not t41rx_params fields: they survive t41rx_set_params() and t41rx_set_coeffs() and take effect
+ * from the next process call.  The memories (5 x 12 biquad words, the FIR's 63-sample history, corrResultR,
+ * aveCorrResultL / R; 128 floats per channel) start at zero, change only while their stage runs, are zeroed by
+ * t41rx_reset() and travel in the checkpoint (section bit 4). */
+T41RX_API int t41rx_set_cw_tables(t41rx_ctx *ctx, const float *audio_filters, const float *decode_fir);
+T41RX_API int t41rx_set_cw_filter(t41rx_ctx *ctx, int CWFilterIndex);
+T41RX_API int t41rx_get_cw_filter(const t41rx_ctx *ctx);
+T41RX_API int t41rx_set_cw_detector(t41rx_ctx *ctx, int decoderFlag, float *d_cw, int max_frames);
+T41RX_API int t41rx_get_cw_detector(const t41rx_ctx *ctx);
+
 T41RX_API int t41rx_n_channels(const t41rx_ctx *ctx);
 T41RX_API int t41rx_frame_len(const t41rx_ctx *ctx);
 
@@ -251,9 +299,12 @@ T41RX_API int t41rx_process_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, cons
  *     bit 2  noise blanker: last_frame_end[0 .. 12] (DSP_Fn.cpp:143), 16 floats per channel (13 used) -- present once
  *            the blanker has run in this context; refused at a long fft_length;
  *     bit 3  receive equalizer: rec_EQ_Band1_state .. rec_EQ_Band14_state (Filter.cpp:43-56), 112 floats per channel --
- *            present once the equalizer has run in this context; refused at a long fft_length.
- * t41rx_state_bytes() therefore GROWS when a noise-reduction stage, the noise blanker or the receive equalizer first
- * runs or the display spectrum is switched on:
+ *            present once the equalizer has run in this context; refused at a long fft_length;
+ *     bit 4  CW receive: CW_AudioFilter1_state .. CW_AudioFilter5_state (60 floats), the decode FIR's history (63),
+ *            corrResultR, aveCorrResultL, aveCorrResultR, 2 zeros: 128 floats per channel -- present once the narrow
+ *            filter or the detector has run in this context; refused at a long fft_length.
+ * t41rx_state_bytes() therefore GROWS when a noise-reduction stage, the noise blanker, the receive equalizer or a CW
+ * stage first runs or the display spectrum is switched on:
  * query it right before every t41rx_get_state() (a buffer sized at creation gets T41RX_ERR_STATE "state buffer too
  * small").  fft_length cannot change on a live context, so the path records' size never does.
  * t41rx_set_state() refuses (T41RX_ERR_STATE) a checkpoint of another ABI, FFT length or channel count, one with an

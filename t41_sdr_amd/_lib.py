@@ -82,6 +82,11 @@ SYMBOLS = {
     "t41rx_set_receive_eq_bands": (C.c_int, [_vp, _vp]),
     "t41rx_set_receive_eq": (C.c_int, [_vp, C.c_int, _vp]),
     "t41rx_get_receive_eq": (C.c_int, [_vp, _vp]),
+    "t41rx_set_cw_tables": (C.c_int, [_vp, _vp, _vp]),
+    "t41rx_set_cw_filter": (C.c_int, [_vp, C.c_int]),
+    "t41rx_get_cw_filter": (C.c_int, [_vp]),
+    "t41rx_set_cw_detector": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
+    "t41rx_get_cw_detector": (C.c_int, [_vp]),
 }
 
 _lib = None

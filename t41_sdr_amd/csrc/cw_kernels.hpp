@@ -1,0 +1,63 @@
+// t41_sdr_amd/csrc/cw_kernels.hpp -- argument blocks and launchers of the CW receive stages (cw_kernel.hip): the tone
+// detector of DoCWReceiveProcessing() (CWProcessing.cpp:322-373, goertzel_mag :830-857) and the narrow audio filter
+// selected by CWFilterIndex (Process.cpp:878-913).  Product code: nothing from oracle/.  The filter tables
+// (CW_AudioFilterCoeffs1..5) and the decode FIR (CW_Filter_Coeffs2) are the caller's: the library holds no copy of its own.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace t41 {
+
+constexpr int kCwFilters = 5;                        // CWFilterIndex 0 .. 4 (5 = off)
+constexpr int kCwStages = 6;                         // biquads per filter (S1_CW_AudioFilter1..5, numStages 6)
+constexpr int kCwFilterCoefs = 5 * kCwStages;        // {b0, b1, b2, a1, a2} per section, a's negated (CMSIS DF2T)
+constexpr int kCwFirTaps = 64;                       // CW_Filter_Coeffs2
+constexpr int kCwBlock = 256;                        // samples per block @24 kS/s
+// per-channel state, 128 floats: the five filters' memories [filter][stage][d1, d2] (CW_AudioFilter1_state ..
+// CW_AudioFilter5_state), the decode FIR's 63-sample history (FIR_CW_DecodeL_state), corrResultR of the block before,
+// the running averages aveCorrResultL / aveCorrResultR, two words of zero
+constexpr int kCwStFilter = 0;
+constexpr int kCwStFir = 2 * kCwStages * kCwFilters;  // 60
+constexpr int kCwStCorrR = kCwStFir + kCwFirTaps - 1;  // 123
+constexpr int kCwStAveL = kCwStCorrR + 1;
+constexpr int kCwStAveR = kCwStCorrR + 2;
+constexpr int kCwStateFloats = 128;
+constexpr int kCwChanPerWave = 8;                    // the filter kernel packs 8 channels into a wave (8 lanes each, 6 used)
+
+struct CwFilterArgs {
+  float *aud;     // [nchan][nsamp] audio @24 kS/s, filtered in place
+  float *state;   // [nchan][kCwStateFloats]
+  int nchan, nsamp;  // nsamp = n_frames * 256
+  int index;         // CWFilterIndex 0 .. 4: which of the five memories advances
+  float coef[kCwFilterCoefs];  // the selected filter's [stage][5]
+};
+hipError_t launch_cw_filter(const CwFilterArgs &a, hipStream_t s);
+
+struct CwDetectArgs {
+  const float *aud;  // [nchan][nframes * 256] audio @24 kS/s (read only)
+  float *state;      // [nchan][kCwStateFloats]
+  float *out;        // [nchan][nframes][4]: corrResultL, goertzelMagnitude, aveCorrResult, combinedCoeff
+  int nchan, nframes;
+  float coeff, cosine, sine;  // goertzel_mag(256, 750, 24000, .)'s constants in the firmware's types (host)
+  float fir[kCwFirTaps];      // CW_Filter_Coeffs2
+  float sinb[kCwBlock];       // sinBuffer (Utility.cpp:72-74)
+};
+hipError_t launch_cw_detect(const CwDetectArgs &a, hipStream_t s);
+
+// Behind the narrow filter: Process.cpp:917-937 as the firmware orders it -- arm_fir_interpolate_f32 x2 (48 taps) and x4
+// (32 taps), each output one accumulator over its phase's taps, then the volume as a multiply of its own
+// (arm_scale_f32) and, for q15 samples out, arm_float_to_q15.  The fused back kernel folds the volume into the x4 taps
+// and accumulates with fused multiply-adds; this one is the oracle's interpolators bit for bit.
+struct CwBackArgs {
+  const float *aud;  // [nchan][nframes * 256] audio @24 kS/s
+  float *state;      // the path's per-channel records (rx_internal.hpp: kStInt1, kStInt2), state_stride floats apart
+  void *out;         // audio out, f32 or q15
+  int nchan, nframes;
+  long long chan_stride, frame_stride, state_stride;  // of out, in samples; of state, in floats
+  int q15;
+  float scale;       // DF * VolumeToAmplification(audioVolume)
+  float int1[48];    // FIR_int1_coeffs
+  float int2[32];    // FIR_int2_coeffs (not scaled)
+};
+hipError_t launch_cw_back(const CwBackArgs &a, hipStream_t s);
+
+}  // namespace t41

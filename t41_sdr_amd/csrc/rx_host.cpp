@@ -18,6 +18,8 @@
 #include <utility>
 #include <vector>
 
+#include "cw_kernels.hpp"
+#include "cw_kernel.hip"  // the CW receive stages' kernels and launchers
 #include "eq_kernels.hpp"
 #include "eq_kernel.hip"  // the receive equalizer's kernel and launcher
 #include "last_error.hpp"
@@ -90,6 +92,18 @@ struct t41rx_ctx {
   float eq_coef[kEqCoefs] = {};
   int32_t eq_levels[kEqBands] = {100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100};
   DevBuf<float> d_eq;
+  // CW receive (Process.cpp:878-913; t41rx_set_cw_tables / _filter / _detector): the caller's filter tables and decode
+  // FIR, CWFilterIndex (5 = off), decoderFlag with the caller's result buffer, and the stages' memories per channel
+  // [nchan][kCwStateFloats] (cw_kernel.hip), allocated when a CW stage first runs.  Both stages run only while
+  // params.xmtMode == T41RX_CW_MODE.
+  int cw_filter = kCwFilters;
+  int cw_det = 0;
+  bool cw_have_filters = false, cw_have_fir = false;
+  float cw_coef[kCwFilters * kCwFilterCoefs] = {};
+  float cw_fir[kCwFirTaps] = {};
+  float *cw_out = nullptr;  // [nchan][n_frames][4]
+  int cw_frames = 0;        // frames per call cw_out is sized for
+  DevBuf<float> d_cw;
   // staging for t41rx_process_host
   DevBuf<float> d_in_i, d_in_q, d_out;
   size_t staging_floats = 0;
@@ -317,6 +331,11 @@ int ensure_eq(t41rx_ctx *ctx) {
   return ensure_zeroed(ctx->d_eq, sizeof(float) * kEqStateFloats * (size_t)ctx->nchan, "receive-equalizer");
 }
 
+// the CW stages' memories: five filter states, the decode FIR's history, the detector's carried words (zeroed statics)
+int ensure_cw(t41rx_ctx *ctx) {
+  return ensure_zeroed(ctx->d_cw, sizeof(float) * kCwStateFloats * (size_t)ctx->nchan, "CW-receive");
+}
+
 // a broken hand-over protocol of the pipelined kernels leaves wrong samples and a count of waits that ran out, not a hung
 // GPU -- reported at the calls that synchronise anyway
 int pipe_timeouts(const t41rx_ctx *ctx) {  // < 0: the counter could not be read
@@ -343,7 +362,7 @@ int pipe_status(const t41rx_ctx *ctx) {
 // ---- checkpoint (t41rx_get_state / t41rx_set_state): header, the path's records, then the sections header word 5 names
 constexpr uint32_t kStateMagic = 0x54343153u;  // "T41S"
 constexpr size_t kStateHeaderBytes = 32;
-constexpr int32_t kSecNr = 1, kSecDisp = 2, kSecNb = 4, kSecEq = 8;
+constexpr int32_t kSecNr = 1, kSecDisp = 2, kSecNb = 4, kSecEq = 8, kSecCw = 16;
 
 // One checkpoint section: the memories of a stage built for fft_length 512 only.
 struct Section {
@@ -432,6 +451,14 @@ const Section kSections[] = {
      [](const t41rx_ctx *c, void *h, size_t n) { return hip_check(hipMemcpy(h, c->d_eq.get(), n, hipMemcpyDeviceToHost), "hipMemcpy"); },
      [](t41rx_ctx *c, const void *h, size_t n) { return hip_check(hipMemcpy(c->d_eq.get(), h, n, hipMemcpyHostToDevice), "hipMemcpy"); },
      [](t41rx_ctx *c, size_t n) { return c->d_eq ? hip_check(hipMemset(c->d_eq.get(), 0, n), "hipMemset") : T41RX_OK; }},  // (zeroed statics)
+    // CW receive: CW_AudioFilter1_state .. CW_AudioFilter5_state (CWProcessing.cpp:37-41), the decode FIR's history
+    // (FIR_CW_DecodeL_state, T41_SDR.ino:281), corrResultR, aveCorrResultL / R, [n_channels][kCwStateFloats] -- present
+    // once a CW stage has run
+    {kSecCw, "CW-receive", (size_t)kCwStateFloats,
+     [](const t41rx_ctx *c) { return c->d_cw != nullptr; }, ensure_cw, nullptr,
+     [](const t41rx_ctx *c, void *h, size_t n) { return hip_check(hipMemcpy(h, c->d_cw.get(), n, hipMemcpyDeviceToHost), "hipMemcpy"); },
+     [](t41rx_ctx *c, const void *h, size_t n) { return hip_check(hipMemcpy(c->d_cw.get(), h, n, hipMemcpyHostToDevice), "hipMemcpy"); },
+     [](t41rx_ctx *c, size_t n) { return c->d_cw ? hip_check(hipMemset(c->d_cw.get(), 0, n), "hipMemset") : T41RX_OK; }},  // (zeroed statics)
 };
 
 size_t section_bytes(const Section &s, int nchan) { return sizeof(float) * s.chan_floats * (size_t)nchan; }
@@ -495,9 +522,25 @@ int reset_state(t41rx_ctx *ctx) {
 
 // ---- a process call: (a) prepare_call, (b) rx_args, (c) launch_chain
 bool nr_on(const t41rx_ctx *ctx) { return ctx->params.nrOptionSelect != 0 || ctx->params.ANR_notchOn != 0; }  // (fft_length 512: params_valid)
+// the CW block runs in T41State == CW_RECEIVE (Process.cpp:878), which in receive is xmtMode == CW_MODE
+// (T41_SDR.ino:1039-1040, 1144-1148); with another xmtMode the switches are kept and nothing runs
+bool cw_filter_on(const t41rx_ctx *ctx) { return ctx->params.xmtMode == T41RX_CW_MODE && ctx->cw_filter != kCwFilters; }
+bool cw_det_on(const t41rx_ctx *ctx) { return ctx->params.xmtMode == T41RX_CW_MODE && ctx->cw_det != 0; }
 // the fused kernel stops behind the demodulator; stage kernels; back kernel (fft_length 512: t41rx_set_noise_blanker,
-// t41rx_set_receive_eq)
-bool stages_on(const t41rx_ctx *ctx) { return ctx->eq_on || nr_on(ctx) || ctx->nb_on; }
+// t41rx_set_receive_eq, t41rx_set_cw_filter, t41rx_set_cw_detector)
+bool stages_on(const t41rx_ctx *ctx) { return ctx->eq_on || nr_on(ctx) || ctx->nb_on || cw_filter_on(ctx) || cw_det_on(ctx); }
+// The library carries one audio stream where the firmware has float_buffer_L and float_buffer_R; the detector reads both.
+// The stage that leaves L different from R in front of it, or null: the equalizer writes L only (Filter.cpp:151-164),
+// Kim1_NR() and SpectralNoiseReduction() end with R = L (Noise.cpp:307-308, 636-637) but x30 behind Kim scales L only
+// (Process.cpp:846), Xanr() writes R only and x1.5 behind it scales L only (Noise.cpp:345-347, Process.cpp:855); the
+// notch and the blanker end in arm_copy_f32(R, L) (Process.cpp:865, 875), which joins them again.
+const char *cw_split_stage(const t41rx_ctx *ctx) {
+  if (ctx->params.ANR_notchOn != 0 || ctx->nb_on) return nullptr;
+  if (ctx->params.nrOptionSelect == 1) return "Kim noise reduction (nrOptionSelect 1)";
+  if (ctx->params.nrOptionSelect == 3) return "LMS noise reduction (nrOptionSelect 3)";
+  if (ctx->eq_on && ctx->params.nrOptionSelect == 0) return "receive equalizer";
+  return nullptr;
+}
 // the pipelined kernels' buffer: AGC on (with the synchronous detector behind it: PSA), or the synchronous detector alone
 bool pipe_on(const t41rx_ctx *ctx, int n_frames) {
   return (ctx->params.AGCMode != 0 || ctx->params.mode == T41RX_DEMOD_SAM) && ctx->params.fft_length == 512 && n_frames >= 4;
@@ -508,7 +551,8 @@ int prepare_call(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
   const int seg = ctx->params.fft_length / 512;
   int rc = T41RX_OK;
   if ((nr_on(ctx) && (rc = ensure_nr(ctx)) != T41RX_OK) || (ctx->nb_on && (rc = ensure_nb(ctx)) != T41RX_OK) ||
-      (ctx->eq_on && (rc = ensure_eq(ctx)) != T41RX_OK))
+      (ctx->eq_on && (rc = ensure_eq(ctx)) != T41RX_OK) ||
+      ((cw_filter_on(ctx) || cw_det_on(ctx)) && (rc = ensure_cw(ctx)) != T41RX_OK))
     return rc;
   if ((seg > 1 || stages_on(ctx)) && n_frames > ctx->scratch_frames) {
     // scratch between the kernels of the long-FFT pipeline / the noise-reduction pipeline (grown on demand, kept)
@@ -538,6 +582,13 @@ int prepare_call(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
     return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the audio-spectrum buffers were set with");
   if (ctx->disp_spec && n_frames > ctx->disp_frames)
     return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the display-spectrum buffers were set with");
+  if (cw_det_on(ctx) && n_frames > ctx->cw_frames)
+    return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the CW detector's buffer was set with");
+  if (cw_det_on(ctx))
+    if (const char *stage = cw_split_stage(ctx))
+      return fail(T41RX_ERR_UNSUPPORTED, std::string("CW detector: the ") + stage +
+                                             " leaves float_buffer_L different from float_buffer_R and neither the notch nor the noise "
+                                             "blanker joins them behind it; the library carries one audio stream");
   if (ctx->disp_spec && (!ctx->d_pre || !ctx->d_disp || !ctx->d_win)) return fail(T41RX_ERR_STATE, "display spectrum enabled without its buffers");
   return T41RX_OK;
 }
@@ -606,7 +657,7 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
 }
 
 // (c) the stage chain: fused front end, then on the audio @24 kS/s the equalizer, noise reduction / notch and the
-// blanker, the back end, and the display FFT
+// blanker, the CW detector and narrow filter, the back end, and the display FFT
 int launch_chain(t41rx_ctx *ctx, RxArgs a, int n_frames, hipStream_t s) {
   hipError_t e = launch_rx(a, ctx->params.fft_length, ctx->params.mode, s);
   if (e != hipSuccess) return hip_fail(e, "kernel launch");
@@ -658,7 +709,64 @@ int launch_chain(t41rx_ctx *ctx, RxArgs a, int n_frames, hipStream_t s) {
     if (e != hipSuccess) return hip_fail(e, "noise-blanker kernel launch");
     ctx->nb_sel ^= 1;  // the last frame wrote the other slot
   }
-  if (stages_on(ctx)) {
+  if (cw_det_on(ctx)) {
+    // Process.cpp:878-879 behind it: DoCWReceiveProcessing() reads the audio, its results go to the caller's buffer
+    CwDetectArgs d{};
+    d.aud = ctx->d_aud24.get();
+    d.state = ctx->d_cw.get();
+    d.out = ctx->cw_out;
+    d.nchan = ctx->nchan;
+    d.nframes = n_frames;
+    {
+      // goertzel_mag(256, 750, 24000, .) (CWProcessing.cpp:835-842) in its types: k = (int)(0.5 + 256.0f * 750 / 24000) = 8
+      const float fn = (float)kCwBlock;
+      const int k = (int)(0.5 + (double)((fn * 750) / 24000));
+      const float omega = (float)((2.0 * 3.14159265358979323846 * k) / (double)fn);
+      d.sine = (float)std::sin((double)omega);
+      d.cosine = (float)std::cos((double)omega);
+      d.coeff = (float)(2.0 * (double)d.cosine);
+      // sineTone() (Utility.cpp:72-74): float theta = kf * 0.19634950849362; sinBuffer[kf] = sin(theta)
+      for (int kf = 0; kf < kCwBlock; ++kf) {
+        const float theta = (float)(kf * 0.19634950849362);
+        d.sinb[kf] = (float)std::sin((double)theta);
+      }
+    }
+    std::memcpy(d.fir, ctx->cw_fir, sizeof(d.fir));
+    e = launch_cw_detect(d, s);
+    if (e != hipSuccess) return hip_fail(e, "CW detector kernel launch");
+  }
+  if (cw_filter_on(ctx)) {
+    // Process.cpp:882-912: the narrow filter CWFilterIndex selects, on its own memory
+    CwFilterArgs f{};
+    f.aud = ctx->d_aud24.get();
+    f.state = ctx->d_cw.get();
+    f.nchan = ctx->nchan;
+    f.nsamp = n_frames * 256;
+    f.index = ctx->cw_filter;
+    std::memcpy(f.coef, ctx->cw_coef + kCwFilterCoefs * ctx->cw_filter, sizeof(f.coef));
+    e = launch_cw_filter(f, s);
+    if (e != hipSuccess) return hip_fail(e, "CW filter kernel launch");
+  }
+  if (cw_filter_on(ctx)) {
+    // then the interpolators, volume and stores (Process.cpp:917-937) in the firmware's own operations and order
+    // (cw_back_kernel): the narrow filter's audio is held to the oracle's interpolators bit for bit
+    const BlobView v = blob_view(ctx->blob.data());
+    CwBackArgs b{};
+    b.aud = ctx->d_aud24.get();
+    b.state = ctx->d_state.get();
+    b.out = a.out;
+    b.nchan = ctx->nchan;
+    b.nframes = n_frames;
+    b.chan_stride = a.chan_stride;
+    b.frame_stride = a.frame_stride;
+    b.state_stride = (long long)state_floats(512);
+    b.q15 = a.q15;
+    b.scale = v.scalars[kScOutScale];
+    std::memcpy(b.int1, v.int1, sizeof(b.int1));
+    std::memcpy(b.int2, v.int2, sizeof(b.int2));
+    e = launch_cw_back(b, s);
+    if (e != hipSuccess) return hip_fail(e, "CW interpolator kernel launch");
+  } else if (stages_on(ctx)) {
     // then the interpolators, volume and stores (Process.cpp:917-937) from a.aud24
     a.aud_out = nullptr;
     e = launch_back512(a, s);
@@ -976,6 +1084,55 @@ int t41rx_get_receive_eq(const t41rx_ctx *ctx, int32_t *equalizerRec_out) {
   if (equalizerRec_out) std::memcpy(equalizerRec_out, ctx->eq_levels, sizeof(ctx->eq_levels));
   return ctx->eq_on;
 }
+
+int t41rx_set_cw_tables(t41rx_ctx *ctx, const float *audio_filters, const float *decode_fir) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (audio_filters)
+    for (int i = 0; i < kCwFilters * kCwFilterCoefs; ++i)
+      if (!std::isfinite(audio_filters[i])) return fail(T41RX_ERR_ARG, "CW filter tables: non-finite coefficient");
+  if (decode_fir)
+    for (int i = 0; i < kCwFirTaps; ++i)
+      if (!std::isfinite(decode_fir[i])) return fail(T41RX_ERR_ARG, "CW decode FIR: non-finite coefficient");
+  // (passed by value to every launch: the next call uses them; no memory is reset)
+  if (audio_filters) {
+    std::memcpy(ctx->cw_coef, audio_filters, sizeof(ctx->cw_coef));
+    ctx->cw_have_filters = true;
+  }
+  if (decode_fir) {
+    std::memcpy(ctx->cw_fir, decode_fir, sizeof(ctx->cw_fir));
+    ctx->cw_have_fir = true;
+  }
+  return T41RX_OK;
+}
+
+int t41rx_set_cw_filter(t41rx_ctx *ctx, int CWFilterIndex) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (CWFilterIndex < 0 || CWFilterIndex > kCwFilters) return fail(T41RX_ERR_ARG, "CWFilterIndex must be 0 .. 4, or 5 (off)");
+  if (CWFilterIndex != kCwFilters) {
+    if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the CW audio filters are built for fft_length 512");
+    if (!ctx->cw_have_filters) return fail(T41RX_ERR_ARG, "CW audio filter: no filter tables loaded (t41rx_set_cw_tables)");
+  }
+  ctx->cw_filter = CWFilterIndex;
+  return T41RX_OK;
+}
+int t41rx_get_cw_filter(const t41rx_ctx *ctx) { return ctx ? ctx->cw_filter : T41RX_ERR_ARG; }
+
+int t41rx_set_cw_detector(t41rx_ctx *ctx, int decoderFlag, float *d_cw, int max_frames) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (decoderFlag != 0 && decoderFlag != 1) return fail(T41RX_ERR_ARG, "decoderFlag must be 0 or 1");
+  if (decoderFlag) {
+    if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the CW detector is built for fft_length 512");
+    if (!d_cw) return fail(T41RX_ERR_ARG, "CW detector: no result buffer (d_cw is NULL)");
+    if (reinterpret_cast<uintptr_t>(d_cw) & 3u) return fail(T41RX_ERR_ARG, "unaligned pointer");
+    if (max_frames <= 0) return fail(T41RX_ERR_ARG, "max_frames must be > 0");
+    if (!ctx->cw_have_fir) return fail(T41RX_ERR_ARG, "CW detector: no decode FIR loaded (t41rx_set_cw_tables)");
+  }
+  ctx->cw_det = decoderFlag;
+  ctx->cw_out = decoderFlag ? d_cw : nullptr;
+  ctx->cw_frames = decoderFlag ? max_frames : 0;
+  return T41RX_OK;
+}
+int t41rx_get_cw_detector(const t41rx_ctx *ctx) { return ctx ? ctx->cw_det : T41RX_ERR_ARG; }
 
 int t41rx_n_channels(const t41rx_ctx *ctx) { return ctx ? ctx->nchan : T41RX_ERR_ARG; }
 int t41rx_frame_len(const t41rx_ctx *ctx) { return ctx ? 4 * ctx->params.fft_length : T41RX_ERR_ARG; }

@@ -169,6 +169,68 @@ class RxChain:
             check(v)
         return v, lv
 
+    def set_cw_tables(self, audio_filters=None, decode_fir=None):
+        """The CW receive tables (t41rx_set_cw_tables): audio_filters = the firmware's CW_AudioFilterCoeffs1..5 as
+        [5][6][5] or [5][30], {b0, b1, b2, a1, a2} per section with the a's negated; decode_fir = CW_Filter_Coeffs2, 64
+        taps.  None keeps what is loaded.  Kept across CalcFilters() / set_coeffs(); no memory is reset."""
+        f = d = None
+        if audio_filters is not None:
+            f = np.ascontiguousarray(np.asarray(audio_filters, dtype=np.float32))
+            if f.size != 5 * 6 * 5 or f.shape[0] != 5:
+                raise ValueError("CW filter tables must be [5][6][5] or [5][30], got %r" % (f.shape,))
+        if decode_fir is not None:
+            d = np.ascontiguousarray(np.asarray(decode_fir, dtype=np.float32))
+            if d.shape != (64,):
+                raise ValueError("CW decode FIR must be 64 taps, got %r" % (d.shape,))
+        check(self._lib.t41rx_set_cw_tables(self._ctx, None if f is None else f.ctypes.data_as(C.c_void_p),
+                                            None if d is None else d.ctypes.data_as(C.c_void_p)))
+
+    def set_cw_filter(self, CWFilterIndex):
+        """CWFilterIndex (Process.cpp:882-912): 0 .. 4 = the 0.8 / 1.0 / 1.3 / 1.8 / 2.0 kHz narrow audio filter behind the
+        noise blanker, 5 = off (the default).  Runs only while xmtMode == CW_MODE; fft_length 512; the filter tables
+        loaded first.  Kept across CalcFilters() / set_coeffs()."""
+        check(self._lib.t41rx_set_cw_filter(self._ctx, int(CWFilterIndex)))
+
+    @property
+    def cw_filter(self):
+        v = self._lib.t41rx_get_cw_filter(self._ctx)
+        if v < 0:
+            check(v)
+        return v
+
+    def set_cw_detector(self, on, max_frames=1):
+        """decoderFlag (DoCWReceiveProcessing(), CWProcessing.cpp:322-373).  on = 1 allocates and returns the result
+        tensor, float32 CUDA [n_channels, max_frames, 4]; a process call of n <= max_frames frames fills its first
+        n_channels * n * 4 floats as [n_channels][n][corrResultL, goertzelMagnitude, aveCorrResult, combinedCoeff]
+        (cw_results(n) is that view).  on = 0 switches the detector off and returns None.  The `combinedCoeff > 50`
+        decision and the Morse decoder stay with the caller.  Runs only while xmtMode == CW_MODE; fft_length 512; the
+        decode FIR loaded first.  Kept across CalcFilters() / set_coeffs()."""
+        if not on:
+            check(self._lib.t41rx_set_cw_detector(self._ctx, 0, None, 0))
+            self._cw = None
+            return None
+        import torch
+        if int(max_frames) < 1:
+            raise ValueError("max_frames must be >= 1")
+        t = torch.zeros(self.n_channels, int(max_frames), 4, dtype=torch.float32, device="cuda:%d" % self.device)
+        check(self._lib.t41rx_set_cw_detector(self._ctx, int(on), C.c_void_p(t.data_ptr()), int(max_frames)))
+        self._cw = t  # keep alive
+        return t
+
+    @property
+    def cw_detector(self):
+        v = self._lib.t41rx_get_cw_detector(self._ctx)
+        if v < 0:
+            check(v)
+        return v
+
+    def cw_results(self, n_frames):
+        """the detector's results of the last process call of n_frames frames: a view [n_channels, n_frames, 4]"""
+        t = getattr(self, "_cw", None)
+        if t is None:
+            raise ValueError("the CW detector is off")
+        return t.view(-1)[:self.n_channels * int(n_frames) * 4].view(self.n_channels, int(n_frames), 4)
+
     def get_state(self):
         n = self._lib.t41rx_state_bytes(self._ctx)
         buf = np.zeros(n, dtype=np.uint8)
