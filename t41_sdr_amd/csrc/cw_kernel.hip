@@ -10,14 +10,11 @@
 // Every value is formed by the reference's operations in the order of the f32 restatement (tests/cw_model.py), one
 // rounding per multiply and per add, so both stages are that restatement bit for bit.
 //
-// NARROW FILTER: a six-stage serial cascade, one section per lane, 8 lanes per channel (6 used) and 8 CHANNELS PER WAVE.
-// Every step, stage s takes stage s - 1's output of the step before by a DPP row shift and stage 0 takes the next input
-// sample: a 6-deep pipeline that runs through all frames of the call, so its fill and drain (5 steps each, the only steps
-// with a per-lane guard) are paid once per launch.  The section's coefficients and its two state words stay in VGPRs
-// for the whole call; the step is eq::step's (acc = b0*x + d1; d1 = b1*x + d2; d1 += a1*acc; d2 = b2*x; d2 += a2*acc):
-// the poles sit near |z| = 0.99, a reordered or contracted recurrence drifts.  Input arrives in 64-sample chunks per
-// channel (coalesced loads, prefetched a chunk ahead) through an 8 x 64 LDS buffer; stage-5 lanes gather 4 outputs in
-// registers and store them into an 8 x 128 LDS ring, from which complete chunks go back coalesced.
+// NARROW FILTER: a six-stage serial cascade on df2t_pipe.hpp's pipeline (the step, the hand-over, the ring), one section
+// per lane, 8 lanes per channel (6 used, stage s reads stage s - 1 by a DPP row shift) and 8 CHANNELS PER WAVE.  The
+// 6-deep pipeline runs through all frames of the call, so its fill and drain (5 steps each) are paid once per launch.
+// Input arrives in 64-sample chunks per channel (coalesced loads, prefetched a chunk ahead) through an 8 x 64 LDS buffer;
+// stage-5 lanes store into an 8-row ring, from which complete chunks go back coalesced.
 //
 // DETECTOR: one wave per channel, frame after frame (corrResultR of the block before enters aveCorrResult, so frames are
 // not independent).  The block, its 63-sample history, the filtered block, the sine table and the taps sit in LDS.  The
@@ -33,86 +30,45 @@
 #include <hip/hip_runtime.h>
 
 #include "cw_kernels.hpp"
+#include "df2t_pipe.hpp"
 #include "rx_internal.hpp"  // kStInt1, kStInt2: the interpolator histories in the per-channel records
 
 namespace t41 {
 
 namespace cw {
-constexpr int kChunk = 64;              // samples per input chunk
-constexpr int kInPitch = kChunk + 4;    // (4 banks apart per channel row: the 8 broadcast b128 reads do not conflict)
-constexpr int kRing = 2 * kChunk;       // output ring: the chunk being stored and the one being filtered
-constexpr int kRingPitch = kRing + 4;
-constexpr int kRowShr1 = 0x111;         // DPP row_shr:1: lane l reads lane l - 1 (stage s reads stage s - 1)
-
-struct Biquad {
-  float b0, b1, b2, a1, a2, d1, d2;
-};
-
-// one step of one section on its input xx; the state only changes where `valid` (the pipeline's fill / drain)
-__device__ __forceinline__ float step(Biquad &q, float xx, bool valid) {
-#pragma clang fp contract(off)
-  const float acc = q.b0 * xx + q.d1;
-  float d1 = q.b1 * xx + q.d2;
-  d1 += q.a1 * acc;
-  float d2 = q.b2 * xx;
-  d2 += q.a2 * acc;
-  q.d1 = valid ? d1 : q.d1;
-  q.d2 = valid ? d2 : q.d2;
-  return acc;
-}
-
-__device__ __forceinline__ float from_prev_stage(float acc) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, acc), kRowShr1, 0xf, 0xf, false));
-}
+constexpr int kInPitch = df2t::kChunk + 4;  // (4 banks apart per channel row: the 8 broadcast b128 reads do not conflict)
+constexpr int kRowShr1 = 0x111;             // DPP row_shr:1: lane l reads lane l - 1 (stage s reads stage s - 1)
 }  // namespace cw
 
 __global__ __launch_bounds__(64) void cw_filter_kernel(CwFilterArgs a) {
 #pragma clang fp contract(off)
   using namespace cw;
+  using namespace df2t;
   __shared__ __attribute__((aligned(16))) float xin[kCwChanPerWave * kInPitch];
-  __shared__ __attribute__((aligned(16))) float ring[kCwChanPerWave * kRingPitch];
+  __shared__ __attribute__((aligned(16))) float ring[kCwChanPerWave * kRowPitch];
   const int lane = threadIdx.x;
   const int grp = lane >> 3, stage = lane & 7;
   const int ch0 = blockIdx.x * kCwChanPerWave;
   const int nlive = min(kCwChanPerWave, a.nchan - ch0);  // channels of this wave (the ragged last one has fewer)
   const bool live = stage < kCwStages && grp < nlive;
-  const bool head = stage == 0;
-  const bool tail = live && stage == kCwStages - 1;
   float *x = a.aud + (size_t)ch0 * a.nsamp;
   float *st = a.state + (size_t)(ch0 + grp) * kCwStateFloats + kCwStFilter + 2 * kCwStages * a.index + 2 * stage;
   const int nchunk = a.nsamp / kChunk;
 
-  Biquad q{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  Pipe<kCwStages, kRowShr1, false, true> p;
+  p.head = stage == 0;
+  p.tail = live && stage == kCwStages - 1;
   if (live) {
     const float *c = a.coef + 5 * stage;
-    q = Biquad{c[0], c[1], c[2], c[3], c[4], st[0], st[1]};
+    p.q = Section{c[0], c[1], c[2], c[3], c[4], st[0], st[1]};
   }
   const float *in_row = xin + grp * kInPitch;
-  float *out_row = ring + grp * kRingPitch;
+  p.row = ring + grp * kRowPitch;
 
-  float acc = 0.0f;
-  float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;  // stage 5: output samples u with u & 3 = 0 .. 3
-  // one step at chunk position j (global step T = 64 c + j, sample T - stage); stage 5 yields sample u = T - 5, and
-  // every 4th step (j & 3 == 0) completes samples u - 3 .. u, 4-aligned, for the ring
-  auto run = [&](float in, int j, int c, bool valid) {
-    const float prev = from_prev_stage(acc);
-    acc = step(q, head ? in : prev, valid);
-    switch (j & 3) {
-      case 1: r0 = acc; break;
-      case 2: r1 = acc; break;
-      case 3: r2 = acc; break;
-      default:
-        r3 = acc;
-        if (tail && (c > 0 || j >= 8)) {
-          const int u0 = (kChunk * c + j - 8) & (kRing - 1);
-          *reinterpret_cast<float4 *>(out_row + u0) = make_float4(r0, r1, r2, r3);
-        }
-    }
-  };
   // samples 64 k .. 64 k + 63 of every channel of the wave back to the scratch, coalesced
   auto store_chunk = [&](int k) {
     for (int kk = 0; kk < nlive; ++kk)
-      x[(size_t)kk * a.nsamp + (size_t)k * kChunk + lane] = ring[kk * kRingPitch + (k & 1) * kChunk + lane];
+      x[(size_t)kk * a.nsamp + (size_t)k * kChunk + lane] = ring[kk * kRowPitch + (k & 1) * kChunk + lane];
   };
 
   float nxt[kCwChanPerWave];
@@ -131,19 +87,19 @@ __global__ __launch_bounds__(64) void cw_filter_kernel(CwFilterArgs a) {
 #pragma unroll
       for (int j = 0; j < kChunk; j += 4) {
         const float4 v = *reinterpret_cast<const float4 *>(in_row + j);
-        run(v.x, j, 0, j >= stage);
-        run(v.y, j + 1, 0, j + 1 >= stage);
-        run(v.z, j + 2, 0, j + 2 >= stage);
-        run(v.w, j + 3, 0, j + 3 >= stage);
+        p.run(v.x, j, 0, j >= stage);
+        p.run(v.y, j + 1, 0, j + 1 >= stage);
+        p.run(v.z, j + 2, 0, j + 2 >= stage);
+        p.run(v.w, j + 3, 0, j + 3 >= stage);
       }
     } else {
 #pragma unroll
       for (int j = 0; j < kChunk; j += 4) {
         const float4 v = *reinterpret_cast<const float4 *>(in_row + j);
-        run(v.x, j, c, true);
-        run(v.y, j + 1, c, true);
-        run(v.z, j + 2, c, true);
-        run(v.w, j + 3, c, true);
+        p.run(v.x, j, c, true);
+        p.run(v.y, j + 1, c, true);
+        p.run(v.z, j + 2, c, true);
+        p.run(v.w, j + 3, c, true);
       }
     }
     __syncthreads();
@@ -151,12 +107,12 @@ __global__ __launch_bounds__(64) void cw_filter_kernel(CwFilterArgs a) {
   }
   // the pipeline drains: step 64 n + d runs stages d + 1 .. 5 on the last samples
 #pragma unroll
-  for (int d = 0; d < kCwStages - 1; ++d) run(0.0f, kChunk + d, nchunk - 1, stage > d);
+  for (int d = 0; d < kCwStages - 1; ++d) p.run(0.0f, kChunk + d, nchunk - 1, stage > d);
   __syncthreads();
   store_chunk(nchunk - 1);
   if (live) {
-    st[0] = q.d1;
-    st[1] = q.d2;
+    st[0] = p.q.d1;
+    st[1] = p.q.d2;
   }
 }
 
@@ -313,7 +269,7 @@ __global__ __launch_bounds__(64) void cw_back_kernel(CwBackArgs a) {
 }
 
 hipError_t launch_cw_filter(const CwFilterArgs &a, hipStream_t s) {
-  if (a.nchan <= 0 || a.nsamp <= 0 || a.nsamp % cw::kChunk || a.index < 0 || a.index >= kCwFilters) return hipErrorInvalidConfiguration;
+  if (a.nchan <= 0 || a.nsamp <= 0 || a.nsamp % df2t::kChunk || a.index < 0 || a.index >= kCwFilters) return hipErrorInvalidConfiguration;
   const unsigned waves = (unsigned)((a.nchan + kCwChanPerWave - 1) / kCwChanPerWave);
   hipLaunchKernelGGL(cw_filter_kernel, dim3(waves), dim3(64), 0, s, a);
   return hipGetLastError();

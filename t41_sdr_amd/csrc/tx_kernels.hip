@@ -20,18 +20,15 @@
 //
 // The transmit equaliser (DoExciterEQ(), Filter.cpp:176-224) is the tx_kernel<true> instantiation; tx_kernel<false> is
 // the kernel of before, instruction for instruction.  It runs in place on the frame's 256 samples @24 kS/s, between the /2
-// decimator and the Hilbert pair, with eq_kernel.hip's arithmetic and lane mapping: 14 bands of 4 cascaded DF2T sections on
-// the same input (acc = b0*x + d1; d1 = b1*x + d2; d1 += a1*acc; d2 = b2*x; d2 += a2*acc; one rounding each), band k's
-// output times its signed level, the products summed as EQ1 + EQ2, then + EQ3, .., + EQ14.  One section per lane, lane
-// 4 * band + stage (56 of 64 lanes; a band is one DPP quad): stage s takes stage s - 1's output of the step before by a
-// quad_perm move, stage 0 the next sample by an LDS broadcast.  Coefficients and the two state words stay in VGPRs for
-// the whole call.  The Hilbert pair needs the whole block, so the 4-deep pipeline fills and drains once per frame: 259
-// steps, the 3 fill and 3 drain steps guarded per lane.  Stage-3 lanes store their band's scaled output, 4 samples at a
-// time, into a 14 x 128 ring (two 64-sample chunks); once a chunk is complete every lane sums one sample's 14 values in
-// the reference's order and writes it back over the input.  The ring lies over the first 1848 floats of the 192 kS/s
-// delay line, which is dead between the /4 decimator and the roll at the frame's end: the equaliser adds no LDS.
+// decimator and the Hilbert pair, on df2t_pipe.hpp's pipeline with eq_kernel.hip's lane mapping: 14 bands of 4 cascaded
+// DF2T sections on the same input, one section per lane (lane 4 * band + stage), band k's output times its signed level,
+// the products summed as EQ1 + EQ2, then + EQ3, .., + EQ14.  Stage 0 takes its sample by an LDS broadcast.  The Hilbert
+// pair needs the whole block, so the 4-deep pipeline fills and drains once per frame: 259 steps, the 3 fill and 3 drain
+// steps guarded per lane.  The ring lies over the first 1848 floats of the 192 kS/s delay line, which is dead between
+// the /4 decimator and the roll at the frame's end: the equaliser adds no LDS.
 #include <hip/hip_runtime.h>
 
+#include "df2t_pipe.hpp"
 #include "tx_internal.hpp"
 
 namespace t41 {
@@ -64,34 +61,13 @@ constexpr int kI2 = kI1 + 2 * 280;        // [2][7 + 512 (+1)]
 constexpr int kLdsFloats = kI2 + 2 * 520;
 
 // ---- transmit equaliser (tx_kernel<true>)
-constexpr int kEqChunk = 64;                // samples per sum pass
-constexpr int kEqRing = 2 * kEqChunk;       // band-output ring: the chunk being summed and the one being filtered
-constexpr int kEqRowPitch = kEqRing + 4;    // (4 banks apart per band row: the 14 b128 stores do not conflict)
+static_assert(kTxEqBands == df2t::kBands, "df2t::sum_bands sums the equaliser's bands");
+constexpr int kEqStages = kTxEqSections / kTxEqBands;
+constexpr int kEqChunk = df2t::kChunk;      // samples per sum pass
 constexpr int kEqRingAt = kXs;              // over the new samples @192 kS/s, which the /4 decimator has consumed
-static_assert(kEqRingAt % 4 == 0 && kEqRingAt + kTxEqBands * kEqRowPitch <= kXs + 2048,
+static_assert(kEqRingAt % 4 == 0 && kEqRingAt + kTxEqBands * df2t::kRowPitch <= kXs + 2048,
               "the ring must leave the delay line's last 47 samples alone: the roll at the frame's end reads them");
-constexpr int kQuadFromPrev = 0 | (0 << 2) | (1 << 4) | (2 << 6);  // quad_perm [0, 0, 1, 2]: stage s reads stage s - 1
-
-struct EqSection {
-  float b0, b1, b2, a1, a2, d1, d2;
-};
-
-// one step of one section on its input xx; the state only changes where `valid` (the pipeline's fill / drain)
-__device__ __forceinline__ float eq_step(EqSection &q, float xx, bool valid) {
-#pragma clang fp contract(off)
-  const float acc = q.b0 * xx + q.d1;
-  float d1 = q.b1 * xx + q.d2;
-  d1 += q.a1 * acc;
-  float d2 = q.b2 * xx;
-  d2 += q.a2 * acc;
-  q.d1 = valid ? d1 : q.d1;
-  q.d2 = valid ? d2 : q.d2;
-  return acc;
-}
-
-__device__ __forceinline__ float eq_from_prev_stage(float acc) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, acc), kQuadFromPrev, 0xf, 0xf, false));
-}
+typedef df2t::Pipe<kEqStages, df2t::kQuadFromPrev, true, false> EqPipe;
 
 // the kernel's argument block: TxArgs, with the equaliser's table, levels and memories behind it where it is on
 template <bool EQ>
@@ -105,7 +81,7 @@ struct TxKernelArgs<true> {
 }  // namespace
 
 // EQ: xmitEQFlag.  tx_kernel<false> is the kernel of before the equaliser existed, instruction for instruction
-// (tools/isa_fingerprint.py): a kernel that calls a shared device function instead compiles to other code.
+// (tools/isa_fingerprint.py).
 template <bool EQ>
 __global__ __launch_bounds__(64) void tx_kernel(const typename TxKernelArgs<EQ>::type a) {
 #pragma clang fp contract(off)
@@ -117,15 +93,16 @@ __global__ __launch_bounds__(64) void tx_kernel(const typename TxKernelArgs<EQ>:
   const CoefPtr cf = (CoefPtr)a.coef;
 
   // ---- equaliser: this lane's section and level, HBM -> VGPRs, once per call
-  const bool eq_live = lane < kTxEqSections, eq_head = (lane & 3) == 0, eq_tail = eq_live && (lane & 3) == 3;
-  EqSection eq{0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  float eq_sc = 0.0f, eq_acc = 0.0f;
+  const bool eq_live = lane < kTxEqSections;
+  EqPipe eq;
   if constexpr (EQ) {
+    eq.head = (lane & 3) == 0;
+    eq.tail = eq_live && (lane & 3) == kEqStages - 1;
     if (eq_live) {
       const float *c = a.eq_coef + 5 * lane;
       const float *m = a.eq_state + (size_t)ch * kTxEqStateFloats;
-      eq = EqSection{c[0], c[1], c[2], c[3], c[4], m[2 * lane], m[2 * lane + 1]};
-      eq_sc = a.eq_scale[lane >> 2];
+      eq.q = df2t::Section{c[0], c[1], c[2], c[3], c[4], m[2 * lane], m[2 * lane + 1]};
+      eq.level = a.eq_scale[lane >> 2];
     }
   }
 
@@ -190,48 +167,24 @@ __global__ __launch_bounds__(64) void tx_kernel(const typename TxKernelArgs<EQ>:
     // ---- DoExciterEQ() on those 256 samples, in place (Filter.cpp:176-224)
     if constexpr (EQ) {
       float *x = lds + kHl + 99;
-      float *row = lds + kEqRingAt + (eq_live ? (lane >> 2) : 0) * kEqRowPitch;
+      eq.row = lds + kEqRingAt + (eq_live ? (lane >> 2) : 0) * df2t::kRowPitch;
+      eq.r0 = eq.r1 = eq.r2 = eq.r3 = 0.0f;
       const int stage = lane & 3;
-      float r0 = 0.0f, r1 = 0.0f, r2 = 0.0f, r3 = 0.0f;  // stage 3: the band's scaled output, samples u with u & 3 = 0 .. 3
-      // one step at chunk position j (step T = 64 c + j of the frame, sample T - stage); stage 3 yields sample u = T - 3,
-      // and every 4th step (j & 3 == 2) completes samples u - 3 .. u, 4-aligned, for the ring
-      auto run = [&](float in, int j, int c, bool valid) {
-        const float prev = eq_from_prev_stage(eq_acc);
-        eq_acc = eq_step(eq, eq_head ? in : prev, valid);
-        const float y = eq_acc * eq_sc;
-        switch (j & 3) {
-          case 3: r0 = y; break;
-          case 0: r1 = y; break;
-          case 1: r2 = y; break;
-          default:
-            r3 = y;
-            if (eq_tail) {
-              const int u0 = (kEqChunk * c + j - 6) & (kEqRing - 1);
-              *reinterpret_cast<float4 *>(row + u0) = make_float4(r0, r1, r2, r3);
-            }
-        }
-      };
-      // samples 64 k .. 64 k + 63 through the sum, in the reference's order, and back over the input
-      auto sum_chunk = [&](int k) {
-        const float *col = lds + kEqRingAt + (k & 1) * kEqChunk + lane;
-        float s = col[0] + col[kEqRowPitch];
-#pragma unroll
-        for (int b = 2; b < kTxEqBands; ++b) s += col[b * kEqRowPitch];
-        x[k * kEqChunk + lane] = s;
-      };
+      // samples 64 k .. 64 k + 63 through the sum and back over the input
+      auto sum_chunk = [&](int k) { x[k * kEqChunk + lane] = df2t::sum_bands(lds + kEqRingAt + (k & 1) * kEqChunk + lane); };
       // chunk 0, the pipeline fills: stage s starts at step s
 #pragma unroll
-      for (int j = 0; j < kEqChunk; ++j) run(x[j], j, 0, j >= 3 || j >= stage);
+      for (int j = 0; j < kEqChunk; ++j) eq.run(x[j], j, 0, j >= 3 || j >= stage);
       for (int c = 1; c < 256 / kEqChunk; ++c) {
 #pragma unroll
-        for (int j = 0; j < kEqChunk; ++j) run(x[kEqChunk * c + j], j, c, true);
+        for (int j = 0; j < kEqChunk; ++j) eq.run(x[kEqChunk * c + j], j, c, true);
         wave_sync();
         sum_chunk(c - 1);
       }
       // the pipeline drains: step 256 + d runs stages d + 1 .. 3 on the frame's last samples
-      run(0.0f, kEqChunk + 0, 256 / kEqChunk - 1, stage > 0);
-      run(0.0f, kEqChunk + 1, 256 / kEqChunk - 1, stage > 1);
-      run(0.0f, kEqChunk + 2, 256 / kEqChunk - 1, stage > 2);
+      eq.run(0.0f, kEqChunk + 0, 256 / kEqChunk - 1, stage > 0);
+      eq.run(0.0f, kEqChunk + 1, 256 / kEqChunk - 1, stage > 1);
+      eq.run(0.0f, kEqChunk + 2, 256 / kEqChunk - 1, stage > 2);
       wave_sync();
       sum_chunk(256 / kEqChunk - 1);
       wave_sync();
@@ -364,8 +317,8 @@ __global__ __launch_bounds__(64) void tx_kernel(const typename TxKernelArgs<EQ>:
   if constexpr (EQ) {
     if (eq_live) {
       float *m = a.eq_state + (size_t)ch * kTxEqStateFloats;
-      m[2 * lane] = eq.d1;
-      m[2 * lane + 1] = eq.d2;
+      m[2 * lane] = eq.q.d1;
+      m[2 * lane + 1] = eq.q.d2;
     }
   }
 }

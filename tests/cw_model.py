@@ -3,19 +3,19 @@
 * ``Restatement`` -- the f32 restatement of one channel, a block at a time, with persistent state: the tone detector
   of DoCWReceiveProcessing() (CWProcessing.cpp:322-373; goertzel_mag, :830-857) on one audio stream (float_buffer_R =
   float_buffer_L), then the narrow audio filter CWFilterIndex selects (five arm_biquad_cascade_df2T_f32 instances of six
-  sections, CWProcessing.cpp:36-48, each with its own memory).  Every section is the oracle's ``t41o_biquad_df2T_f32``;
+  sections, CWProcessing.cpp:36-48, each with its own memory), by ``df2t_model.cascade_oracle``;
   arm_fir_f32 is ``tx_model.fir_f32`` (one accumulator in tap order); arm_correlate_f32 sums every lag sequentially in
   increasing sample index; all in float32 with one rounding per multiply and per add.  CMSIS-DSP itself is not
   available here: this restatement is the pin.
-* ``cascade_numpy`` -- one filter as a numpy float32 loop over samples, with the contracted variant (every ``a*b + c``
-  rounded once) the tests set against it.
+* ``cascade_numpy`` -- one filter on ``df2t_model.cascade_f32``, the numpy float32 loop over samples, with the
+  contracted variant (every ``a*b + c`` rounded once) the tests set against it.
 * ``filter_f64`` / ``detect_f64`` -- independent float64 models (scipy sosfilt, lfilter, np.correlate, the DFT bin).
 """
 import os
 
 import numpy as np
 
-import oracle_lib as O
+from df2t_model import block_rel, cascade_f32, cascade_oracle, sos_of  # noqa: F401  (block_rel, sos_of: for the tests)
 from tx_model import fir_f32
 
 N, TAPS, FILTERS, STAGES, OFF = 256, 64, 5, 6, 5
@@ -78,7 +78,6 @@ class Restatement:
         self.fir_state = np.zeros(TAPS - 1 + N, F)
         self.corrR = self.aveL = self.aveR = F(0)
         self.sinb = sin_buffer()
-        self.lib = O.lib()
 
     def detect(self, x):
         """one block through the detector: (corrResultL, goertzelMagnitude, aveCorrResult, combinedCoeff)"""
@@ -94,15 +93,7 @@ class Restatement:
         return np.array([corrL, g, ave, comb], F)
 
     def filter(self, x, index):
-        y = np.ascontiguousarray(x, F).copy()
-        for s in range(STAGES):
-            c = np.ascontiguousarray(self.c[index, s])
-            st = np.ascontiguousarray(self.st[index, s])
-            out = np.empty(y.size, F)
-            self.lib.t41o_biquad_df2T_f32(O.fptr(c), O.fptr(st), O.fptr(y), O.fptr(out), y.size)
-            self.st[index, s] = st
-            y = out
-        return y
+        return cascade_oracle(self.c[index], self.st[index], x)
 
     def block(self, x, index=OFF, detector=False):
         """one 256-sample block as Process.cpp:878-913 runs it: (audio, detector results or None)"""
@@ -138,38 +129,7 @@ class Restatement:
 
 def cascade_numpy(x, coeffs, fma=False):
     """one six-section filter from zero memories as a float32 loop over samples; ``fma=True`` rounds every a*b + c once"""
-    c = np.asarray(coeffs, F).reshape(STAGES, 5)
-    y = np.asarray(x, F).copy()
-    for s in range(STAGES):
-        b0, b1, b2, a1, a2 = (c[s, i] for i in range(5))
-        d1 = d2 = F(0)
-        out = np.empty_like(y)
-        if fma:
-            b0, b1, b2, a1, a2 = (np.float64(v) for v in (b0, b1, b2, a1, a2))
-            for i in range(y.size):
-                xi = np.float64(y[i])
-                acc = F(b0 * xi + np.float64(d1))
-                t = F(b1 * xi + np.float64(d2))
-                d1 = F(a1 * np.float64(acc) + np.float64(t))
-                d2 = F(a2 * np.float64(acc) + np.float64(F(b2 * xi)))
-                out[i] = acc
-        else:
-            for i in range(y.size):
-                xi = y[i]
-                acc = b0 * xi + d1
-                d1 = b1 * xi + d2
-                d1 = d1 + a1 * acc
-                d2 = b2 * xi
-                d2 = d2 + a2 * acc
-                out[i] = acc
-        y = out
-    return y
-
-
-def sos_of(coeffs):
-    """CMSIS {b0, b1, b2, a1, a2} with the a's negated -> scipy sos rows [b0, b1, b2, 1, -a1, -a2]"""
-    c = np.asarray(coeffs, np.float64).reshape(STAGES, 5)
-    return np.column_stack([c[:, 0], c[:, 1], c[:, 2], np.ones(STAGES), -c[:, 3], -c[:, 4]])
+    return cascade_f32(x, np.asarray(coeffs, F).reshape(STAGES, 5), fma)
 
 
 def filter_f64(x, coeffs):
@@ -197,10 +157,3 @@ def detect_f64(x, fir=None):
         prev = corr
         res.append((corr, g, ave, 10 * ave * 100 * g))
     return np.array(res)
-
-
-def block_rel(a, b, n=N):
-    """per 256-sample block: max|a - b| / max|b|"""
-    a = np.asarray(a, np.float64).reshape(-1, n)
-    b = np.asarray(b, np.float64).reshape(-1, n)
-    return np.abs(a - b).max(1) / np.maximum(np.abs(b).max(1), 1e-30)

@@ -1,11 +1,11 @@
 """CPU models of the receive equalizer (DoReceiveEQ(), Filter.cpp:117-165; call site Process.cpp:828-832) on streams of
 24 kS/s audio, 256-sample blocks.
 
-* ``Restatement`` -- the f32 restatement: every section is the oracle's ``t41o_biquad_df2T_f32`` (arm_biquad_cascade_
-  df2T_f32 for one stage, oracle/t41_oracle.c), band k's output times ``signed_scales()[k - 1]`` (arm_scale_f32) and
+* ``Restatement`` -- the f32 restatement: every band is ``df2t_model.cascade_oracle`` (the oracle's
+  ``t41o_biquad_df2T_f32`` section by section), band k's output times ``signed_scales()[k - 1]`` (arm_scale_f32) and
   the sum EQ1 + EQ2, then + EQ3, .., + EQ14 (arm_add_f32), all in float32 with one rounding per operation.
-* ``bank_numpy`` -- the same bank as a numpy float32 loop over samples (vectorised over bands), with the variants the
-  tests set against it: contraction (every ``a*b + c`` rounded once) and a reordered sum.
+* ``bank_numpy`` -- the same bank on ``df2t_model.cascade_f32``, the numpy float32 loop over samples, with the variants
+  the tests set against it: contraction (every ``a*b + c`` rounded once) and a reordered sum.
 * ``F64`` -- an independent float64 model: scipy's second-order sections on the same (float32-rounded) coefficients,
   float64 levels, a float64 sum.
 """
@@ -14,7 +14,7 @@ import os
 import numpy as np
 import scipy.signal as sg
 
-import oracle_lib as O
+from df2t_model import block_rel, cascade_f32, cascade_oracle, sos_of  # noqa: F401  (block_rel: for the tests)
 
 BANDS, STAGES, N = 14, 4, 256
 F = np.float32
@@ -60,23 +60,11 @@ class Restatement:
     def __init__(self, coeffs=None):
         self.c = np.ascontiguousarray(bands() if coeffs is None else coeffs, F).reshape(BANDS, STAGES, 5)
         self.st = np.zeros((BANDS, STAGES, 2), F)
-        self.lib = O.lib()
 
     def block(self, x, levels, order="ref"):
         """one 256-sample block (or any length): the equalized samples; the state advances even where a level is 0"""
         x = np.ascontiguousarray(x, F)
-        n = x.size
-        eq = np.empty((BANDS, n), F)
-        for b in range(BANDS):
-            y = x.copy()
-            for s in range(STAGES):
-                c = np.ascontiguousarray(self.c[b, s])
-                st = np.ascontiguousarray(self.st[b, s])
-                out = np.empty(n, F)
-                self.lib.t41o_biquad_df2T_f32(O.fptr(c), O.fptr(st), O.fptr(y), O.fptr(out), n)
-                self.st[b, s] = st
-                y = out
-            eq[b] = y
+        eq = np.stack([cascade_oracle(self.c[b], self.st[b], x) for b in range(BANDS)])
         eq *= signed_scales(levels)[:, None]
         return sum_bands(eq, order)
 
@@ -94,31 +82,7 @@ def bank_numpy(x, levels, coeffs=None, fma=False, order="ref"):
     """the whole bank on one stream as a float32 loop over samples, vectorised over bands; ``fma=True`` rounds every
     a*b + c once (the contracted form), ``order="reversed"`` sums from band 14 down"""
     c = (bands() if coeffs is None else np.asarray(coeffs, F)).reshape(BANDS, STAGES, 5)
-    x = np.asarray(x, F)
-    y = np.broadcast_to(x, (BANDS, x.size)).copy()
-    for s in range(STAGES):
-        b0, b1, b2, a1, a2 = (c[:, s, i].copy() for i in range(5))
-        d1, d2 = np.zeros(BANDS, F), np.zeros(BANDS, F)
-        out = np.empty_like(y)
-        if fma:
-            b0, b1, b2, a1, a2 = (v.astype(np.float64) for v in (b0, b1, b2, a1, a2))
-            for i in range(x.size):
-                xi = y[:, i].astype(np.float64)
-                acc = (b0 * xi + d1).astype(F)
-                t = (b1 * xi + d2).astype(F)
-                d1 = (a1 * acc.astype(np.float64) + t).astype(F).astype(np.float64)
-                d2 = (a2 * acc.astype(np.float64) + (b2 * xi).astype(F)).astype(F).astype(np.float64)
-                out[:, i] = acc
-        else:
-            for i in range(x.size):
-                xi = y[:, i]
-                acc = b0 * xi + d1
-                d1 = b1 * xi + d2
-                d1 = d1 + a1 * acc
-                d2 = b2 * xi
-                d2 = d2 + a2 * acc
-                out[:, i] = acc
-        y = out
+    y = cascade_f32(x, c, fma)
     return sum_bands(y * signed_scales(levels)[:, None], order)
 
 
@@ -127,9 +91,7 @@ class F64:
 
     def __init__(self, coeffs=None):
         c = np.asarray(bands() if coeffs is None else coeffs, np.float64).reshape(BANDS, STAGES, 5)
-        # CMSIS {b0, b1, b2, a1, a2} with a's negated -> sos [b0, b1, b2, 1, -a1, -a2]
-        self.sos = [np.column_stack([c[b, :, 0], c[b, :, 1], c[b, :, 2], np.ones(STAGES), -c[b, :, 3], -c[b, :, 4]])
-                    for b in range(BANDS)]
+        self.sos = [sos_of(c[b]) for b in range(BANDS)]
         self.zi = [np.zeros((STAGES, 2)) for _ in range(BANDS)]
 
     def block(self, x, levels):
@@ -153,12 +115,3 @@ class F64:
         """|H_band(f)| of one band's 4-section cascade"""
         _, h = sg.sosfreqz(self.sos[band], worN=np.atleast_1d(np.asarray(f_hz, np.float64)), fs=fs)
         return np.abs(h)
-
-
-def block_rel(a, b, n=N):
-    """per 256-sample block: max|a - b| / max|b|"""
-    a = np.asarray(a, np.float64).reshape(-1, n)
-    b = np.asarray(b, np.float64).reshape(-1, n)
-    den = np.abs(b).max(1)
-    return np.abs(a - b).max(1) / np.maximum(den, 1e-30)
-

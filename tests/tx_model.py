@@ -17,6 +17,7 @@ import os
 import numpy as np
 
 import oracle_lib as O
+from df2t_model import cascade_oracle, sos_of
 
 BANDS, STAGES = 14, 4
 F32 = np.float32
@@ -74,16 +75,7 @@ class TxModel:
 
     def exciter_eq(self, x, levels):
         """DoExciterEQ() on one 256-sample block; every cascade advances, whatever its level"""
-        n = x.size
-        eq = np.empty((BANDS, n), F32)
-        for b in range(BANDS):
-            y = x.copy()
-            for s in range(STAGES):
-                c, st, out = np.ascontiguousarray(self.c[b, s]), np.ascontiguousarray(self.eq[b, s]), np.empty(n, F32)
-                self.lib.t41o_biquad_df2T_f32(O.fptr(c), O.fptr(st), O.fptr(y), O.fptr(out), n)
-                self.eq[b, s] = st
-                y = out
-            eq[b] = y
+        eq = np.stack([cascade_oracle(self.c[b], self.eq[b], x) for b in range(BANDS)])
         eq *= signed_scales(levels)[:, None]       # arm_scale_f32
         out = eq[0] + eq[1]                        # arm_add_f32: EQ1 + EQ2, then + EQ3, .., + EQ14
         for k in range(2, BANDS):
@@ -166,9 +158,7 @@ def stream_model_f64(q, mode, amp, phase, tabs, eq_on=False, levels=DEFAULT_LEVE
         c = np.asarray(bands() if coeffs is None else coeffs, np.float64).reshape(BANDS, STAGES, 5)
         out = np.zeros(d2.size)
         for b, w in enumerate(whole_levels(levels)):
-            # CMSIS {b0, b1, b2, a1, a2} with a's negated -> sos [b0, b1, b2, 1, -a1, -a2]
-            sos = np.column_stack([c[b, :, 0], c[b, :, 1], c[b, :, 2], np.ones(STAGES), -c[b, :, 3], -c[b, :, 4]])
-            out += (-w if b % 2 == 0 else w) * sosfilt(sos, d2)
+            out += (-w if b % 2 == 0 else w) * sosfilt(sos_of(c[b]), d2)
         d2 = out
     I = lfilter(h45[::-1], 1.0, d2)
     Q = lfilter(hn45[::-1], 1.0, d2)
