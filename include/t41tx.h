@@ -11,7 +11,10 @@
  * become per-channel state owned by the context.  Citations: software/T41_SDR/ of the reference.
  * The transmit equaliser (xmitEQFlag, DoExciterEQ(), Filter.cpp:176-224) is restated as an optional stage between the
  * decimators and the Hilbert pair, off by default like the firmware's; its switch, levels and band table are context
- * switches below, not t41tx_params fields.  Not restated: the CW and data exciters.
+ * switches below, not t41tx_params fields.
+ * The CW exciter, void CW_ExciterIQData(); (CW_Excite.cpp:66-118), is the second entry of the same context
+ * (t41tx_set_cw_tone, t41tx_process_cw_*_q15 below): a stored tone, the TX IQ correction with CW's signs, and the
+ * same two interpolators per channel.  Not restated: the data exciter.
  */
 #ifndef T41TX_H
 #define T41TX_H
@@ -91,6 +94,36 @@ T41RX_API int t41tx_process_device_q15(t41tx_ctx *ctx, const int16_t *dQ_in_L_Ex
 /* host-pointer form: copies in, runs the same kernel, copies out, synchronises */
 T41RX_API int t41tx_process_host_q15(t41tx_ctx *ctx, const int16_t *Q_in_L_Ex, const int16_t *Q_in_R_Ex,
                            int16_t *Q_out_L_Ex, int16_t *Q_out_R_Ex, int n_frames);
+
+/* CW transmit: CW_ExciterIQData() (CW_Excite.cpp:66-118).  Per frame: cosBuffer2 / sinBuffer2 (256 samples @24 kS/s) times
+ * (float)0.127 into I / Q; in LSB I times -IQXAmpCorrectionFactor, in USB times +IQXAmpCorrectionFactor (the opposite of
+ * ExciterIQData()'s signs), then IQPhaseCorrection() (Utility.cpp:178-187), in any other mode no correction; x2 (48 taps)
+ * and x4 (32 taps) per channel, x 20, arm_float_to_q15: 2048 q15 I and 2048 q15 Q @192 kS/s.
+ * Shared memories: the firmware's CW exciter drives the SSB exciter's own CMSIS instances FIR_int1_EX_I / Q and
+ * FIR_int2_EX_I / Q, and so does this one: a CW call continues from the interpolator memories the last call of either
+ * kind left (the first CW frame after SSB frames differs from a cold one, and the other way round), t41tx_reset() and
+ * the checkpoint cover them, and the record size is unchanged.  A CW call touches no other memory: the decimators',
+ * the Hilbert pair's and the equaliser's stay as they were, and the equaliser's switch does not apply.
+ * t41tx_set_cw_tone(): cosBuffer2 and sinBuffer2, 256 floats each, as sineTone() fills them (Utility.cpp:66-83: numCycles
+ *   = 8 is 750 Hz).  The firmware computes them with its own libm, so the library has no table of its own: one must be
+ *   loaded before a CW call.  T41RX_ERR_ARG for NULL or a non-finite value; any finite value is taken, and an oversized
+ *   table saturates in arm_float_to_q15 as the firmware's would.  Configuration: kept across t41tx_set_params() and
+ *   t41tx_reset(), not part of a checkpoint; a new table takes effect from the next call.
+ * The key.  The firmware runs the exciter continuously in the CW transmit states and keys by switching the output
+ *   mixers modeSelectOutExL / R between gain 0 and on (T41_SDR.ino:1193-1289); a mixer gain takes effect at an audio-block
+ *   boundary, 128 samples.  d_key holds one byte per block, 16 per frame, [n_channels][n_frames * 16]: nonzero passes
+ *   the block of both outputs, zero writes zeros; NULL passes every block.  The gate sits behind arm_float_to_q15 and
+ *   the interpolator memories advance whether a block is gated or not.  powerOutCW[] and the sidetone stay with the caller.
+ * t41tx_process_cw_device_q15(): n_frames consecutive frames on every channel.  Device pointers; the outputs are
+ *   [n_channels][n_frames * 2048] int16 each, 16-byte aligned.  Enqueued on hip_stream, no sync.  T41RX_ERR_ARG before
+ *   a tone table is loaded, for n_frames <= 0 and for NULL or misaligned outputs. */
+T41RX_API int t41tx_set_cw_tone(t41tx_ctx *ctx, const float *cosBuffer2, const float *sinBuffer2);
+T41RX_API int t41tx_process_cw_device_q15(t41tx_ctx *ctx, const uint8_t *d_key, int16_t *dQ_out_L_Ex, int16_t *dQ_out_R_Ex,
+                                int n_frames, void *hip_stream);
+/* host-pointer form: copies the key in (it shares the staging buffers of t41tx_process_host_q15), runs the same kernel,
+ * copies out, synchronises */
+T41RX_API int t41tx_process_cw_host_q15(t41tx_ctx *ctx, const uint8_t *key, int16_t *Q_out_L_Ex, int16_t *Q_out_R_Ex,
+                              int n_frames);
 
 #ifdef __cplusplus
 }

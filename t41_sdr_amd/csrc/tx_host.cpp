@@ -11,6 +11,7 @@
 
 #include "last_error.hpp"  // fail(): failures reach t41rx_last_error(), like the receive path's
 #include "tx_internal.hpp"
+#include "tx_cw_kernel.hip"  // the CW exciter's kernel and launcher
 
 using namespace t41;
 
@@ -28,6 +29,10 @@ struct t41tx_ctx {
   bool eq_have_bands = false;
   float eq_coef[kTxEqCoefs] = {};
   int32_t eq_levels[kTxEqBands] = {0, 0, 100, 100, 100, 100, 100, 100, 100, 100, 100, 0, 0, 0};
+  // CW exciter (CW_ExciterIQData(), CW_Excite.cpp:66-118; t41tx_set_cw_tone): the caller's cosBuffer2 / sinBuffer2.
+  // Configuration like the equaliser's: kept across t41tx_set_params() and t41tx_reset(), not part of a checkpoint.
+  bool cw_have_tone = false;
+  float cw_cos[kTxCwTone] = {}, cw_sin[kTxCwTone] = {};
 };
 
 namespace {
@@ -50,6 +55,21 @@ constexpr uint32_t kTxStateMagic = 0x58313454u;  // "T41X"
 constexpr size_t kTxStateHeaderBytes = 8 * sizeof(int32_t);
 size_t record_bytes(const t41tx_ctx *c) { return sizeof(float) * kTxStateFloats * (size_t)c->nchan; }
 float *eq_state(const t41tx_ctx *c) { return c->d_state + (size_t)kTxDelayFloats * (size_t)c->nchan; }
+
+// staging of the host-pointer entries: one input and two output buffers of `bytes` each, grown on demand
+int ensure_staging(t41tx_ctx *ctx, size_t bytes) {
+  if (bytes <= ctx->staging) return T41RX_OK;
+  (void)hipFree(ctx->d_in);
+  (void)hipFree(ctx->d_outL);
+  (void)hipFree(ctx->d_outR);
+  ctx->d_in = ctx->d_outL = ctx->d_outR = nullptr;
+  ctx->staging = 0;
+  if (hipMalloc((void **)&ctx->d_in, bytes) != hipSuccess || hipMalloc((void **)&ctx->d_outL, bytes) != hipSuccess ||
+      hipMalloc((void **)&ctx->d_outR, bytes) != hipSuccess)
+    return fail(T41RX_ERR_NOMEM, "staging allocation failed");
+  ctx->staging = bytes;
+  return T41RX_OK;
+}
 
 void free_ctx(t41tx_ctx *c) {
   if (!c) return;
@@ -250,19 +270,65 @@ int t41tx_process_host_q15(t41tx_ctx *ctx, const int16_t *L, const int16_t *R, i
   Guard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
   const size_t bytes = sizeof(int16_t) * 2048 * (size_t)n_frames * (size_t)ctx->nchan;
-  if (bytes > ctx->staging) {
-    (void)hipFree(ctx->d_in);
-    (void)hipFree(ctx->d_outL);
-    (void)hipFree(ctx->d_outR);
-    ctx->d_in = ctx->d_outL = ctx->d_outR = nullptr;
-    ctx->staging = 0;
-    if (hipMalloc((void **)&ctx->d_in, bytes) != hipSuccess || hipMalloc((void **)&ctx->d_outL, bytes) != hipSuccess ||
-        hipMalloc((void **)&ctx->d_outR, bytes) != hipSuccess)
-      return fail(T41RX_ERR_NOMEM, "staging allocation failed");
-    ctx->staging = bytes;
-  }
+  if (const int rc = ensure_staging(ctx, bytes)) return rc;
   if (hipMemcpy(ctx->d_in, L, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(T41RX_ERR_HIP, "copy in failed");
   const int rc = t41tx_process_device_q15(ctx, ctx->d_in, nullptr, ctx->d_outL, ctx->d_outR, n_frames, nullptr);
+  if (rc != T41RX_OK) return rc;
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(oL, ctx->d_outL, bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(oR, ctx->d_outR, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(T41RX_ERR_HIP, "copy out failed");
+  return T41RX_OK;
+}
+
+int t41tx_set_cw_tone(t41tx_ctx *ctx, const float *cosBuffer2, const float *sinBuffer2) {
+  if (!ctx || !cosBuffer2 || !sinBuffer2) return fail(T41RX_ERR_ARG, "null argument");
+  for (int i = 0; i < kTxCwTone; ++i)
+    if (!std::isfinite(cosBuffer2[i]) || !std::isfinite(sinBuffer2[i])) return fail(T41RX_ERR_ARG, "CW tone table: non-finite value");
+  std::memcpy(ctx->cw_cos, cosBuffer2, sizeof(ctx->cw_cos));  // (passed by value to every launch: the next call uses it)
+  std::memcpy(ctx->cw_sin, sinBuffer2, sizeof(ctx->cw_sin));
+  ctx->cw_have_tone = true;
+  return T41RX_OK;
+}
+
+int t41tx_process_cw_device_q15(t41tx_ctx *ctx, const uint8_t *d_key, int16_t *oL, int16_t *oR, int n_frames, void *hip_stream) {
+  if (!ctx || !oL || !oR) return fail(T41RX_ERR_ARG, "null argument");
+  if (!ctx->cw_have_tone) return fail(T41RX_ERR_ARG, "CW exciter: no tone table loaded (t41tx_set_cw_tone)");
+  if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
+  if ((reinterpret_cast<uintptr_t>(oL) | reinterpret_cast<uintptr_t>(oR)) & 15u)
+    return fail(T41RX_ERR_ARG, "device pointers must be 16-byte aligned");
+  Guard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  TxCwArgs a{};
+  a.key = d_key;
+  a.outL = oL;
+  a.outR = oR;
+  a.state = ctx->d_state;
+  a.coef = ctx->d_coef;
+  a.nchan = ctx->nchan;
+  a.nframes = n_frames;
+  a.corr_on = (ctx->params.mode == T41RX_DEMOD_LSB || ctx->params.mode == T41RX_DEMOD_USB) ? 1 : 0;
+  // the opposite signs of ExciterIQData()'s (CW_Excite.cpp:79, 84)
+  a.i_scale = (ctx->params.mode == T41RX_DEMOD_LSB) ? -ctx->params.IQXAmpCorrectionFactor : +ctx->params.IQXAmpCorrectionFactor;
+  a.iq_phase = ctx->params.IQXPhaseCorrectionFactor;
+  std::memcpy(a.tone_cos, ctx->cw_cos, sizeof(a.tone_cos));
+  std::memcpy(a.tone_sin, ctx->cw_sin, sizeof(a.tone_sin));
+  if (launch_tx_cw(a, (hipStream_t)hip_stream) != hipSuccess) return fail(T41RX_ERR_HIP, "kernel launch failed");
+  return T41RX_OK;
+}
+
+int t41tx_process_cw_host_q15(t41tx_ctx *ctx, const uint8_t *key, int16_t *oL, int16_t *oR, int n_frames) {
+  if (!ctx || !oL || !oR) return fail(T41RX_ERR_ARG, "null argument");
+  if (!ctx->cw_have_tone) return fail(T41RX_ERR_ARG, "CW exciter: no tone table loaded (t41tx_set_cw_tone)");
+  if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
+  Guard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  const size_t bytes = sizeof(int16_t) * 2048 * (size_t)n_frames * (size_t)ctx->nchan;
+  if (const int rc = ensure_staging(ctx, bytes)) return rc;
+  // the gate rides in the input staging buffer: 16 bytes per frame where the microphone's samples take 4096
+  const size_t key_bytes = (size_t)kTxCwKeyPerFrame * (size_t)n_frames * (size_t)ctx->nchan;
+  if (key && hipMemcpy(ctx->d_in, key, key_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(T41RX_ERR_HIP, "copy in failed");
+  const int rc = t41tx_process_cw_device_q15(ctx, key ? reinterpret_cast<const uint8_t *>(ctx->d_in) : nullptr, ctx->d_outL,
+                                             ctx->d_outR, n_frames, nullptr);
   if (rc != T41RX_OK) return rc;
   if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(oL, ctx->d_outL, bytes, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(oR, ctx->d_outR, bytes, hipMemcpyDeviceToHost) != hipSuccess)

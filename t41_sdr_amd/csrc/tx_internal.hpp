@@ -63,7 +63,27 @@ struct TxEqArgs : TxArgs {
   float eq_scale[16];         // per band: -xmtEQ_LevelScale for bands 1, 3, .., 13, + for 2, 4, .., 14 (Filter.cpp:197-210)
 };
 
+// the CW exciter's arguments (CW_ExciterIQData(), CW_Excite.cpp:66-118): it drives the x2 / x4 interpolators of TxArgs'
+// state (kTxStInt1I .. kTxStInt2Q) and touches nothing else of a channel's record.  The caller's tone table travels by
+// value, like the equaliser's band table: a new one takes effect at the next call.
+constexpr int kTxCwTone = 256;       // cosBuffer2 / sinBuffer2: one frame @24 kS/s
+constexpr int kTxCwKeyPerFrame = 16; // gate bytes per frame: one per 128-sample audio block @192 kS/s
+struct TxCwArgs {
+  const uint8_t *__restrict__ key;  // [nchan][nframes * 16], nonzero = the block passes; nullptr = every block passes
+  int16_t *__restrict__ outL;
+  int16_t *__restrict__ outR;
+  float *__restrict__ state;        // [nchan][kTxDelayFloats]
+  const TxCoef *__restrict__ coef;
+  int nchan, nframes;
+  float i_scale;   // -IQXAmp (LSB) / +IQXAmp (USB), CW_Excite.cpp:77-87: the opposite of TxArgs'
+  float iq_phase;  // IQXPhaseCorrectionFactor
+  int corr_on;     // LSB or USB
+  float tone_cos[kTxCwTone];
+  float tone_sin[kTxCwTone];
+};
+
 hipError_t launch_tx(const TxArgs &a, hipStream_t s);       // xmitEQFlag off
 hipError_t launch_tx_eq(const TxEqArgs &a, hipStream_t s);  // xmitEQFlag on
+hipError_t launch_tx_cw(const TxCwArgs &a, hipStream_t s);  // CW_ExciterIQData()
 
 }  // namespace t41

@@ -1,7 +1,9 @@
 """Host-side mirror of the reference's transmit exciter interface, over the C ABI (include/t41tx.h).
 
 The reference drives the exciter through globals and one function:
-  ExciterIQData()   Exciter.cpp:46-169   -> TxChain.ExciterIQData(Q_in_L_Ex, Q_in_R_Ex)
+  ExciterIQData()      Exciter.cpp:46-169     -> TxChain.ExciterIQData(Q_in_L_Ex, Q_in_R_Ex)
+  CW_ExciterIQData()   CW_Excite.cpp:66-118   -> TxChain.CW_ExciterIQData(n_frames, key)
+  sineTone()           Utility.cpp:66-83      -> sine_tone(numCycles), then TxChain.set_cw_tone(cos, sin)
 All arithmetic happens in libt41rx.so (HIP); PyTorch only owns device memory and streams.  No CPU
 fallback exists.
 """
@@ -34,6 +36,9 @@ TX_SYMBOLS = {
     "t41tx_state_bytes": (C.c_size_t, [_vp]),
     "t41tx_get_state": (C.c_int, [_vp, _vp, C.c_size_t]),
     "t41tx_set_state": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "t41tx_set_cw_tone": (C.c_int, [_vp, _vp, _vp]),
+    "t41tx_process_cw_device_q15": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "t41tx_process_cw_host_q15": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
 }
 _bound = False
 
@@ -60,9 +65,20 @@ def default_tx_params(**overrides):
     return p
 
 
+def sine_tone(numCycles=8):
+    """(cosBuffer2, sinBuffer2) as sineTone(numCycles) fills them (Utility.cpp:66-83), 256 float32 each: the frequency
+    numCycles * 24000 / 256 in integer arithmetic (8 -> 750 Hz, 8 whole cycles per table; 5 -> 468 Hz, not 468.75), the
+    angle kf * 2 * PI * f / 24000 and its cosine / sine in float64, rounded to float32.  A convenience for callers
+    who do not bring the firmware's own table, whose values come from the Teensy's libm."""
+    f = float((int(numCycles) * 24000) // 256)
+    theta = np.arange(256, dtype=np.float64) * 2.0 * np.pi * f / 24000.0
+    return np.cos(theta).astype(np.float32), np.sin(theta).astype(np.float32)
+
+
 class TxChain:
-    """n_channels independent T41 SSB exciters resident on one MI355X."""
+    """n_channels independent T41 exciters (SSB and CW) resident on one MI355X."""
     FRAME = 2048
+    KEY_PER_FRAME = 16  # gate bytes per frame: one per 128-sample audio block
 
     def __init__(self, n_channels, params=None, device=0):
         self._lib = _load()
@@ -145,6 +161,49 @@ class TxChain:
         oL, oR = torch.empty_like(a), torch.empty_like(a)
         stream = torch.cuda.current_stream(a.device).cuda_stream
         check(self._lib.t41tx_process_device_q15(self._ctx, a.data_ptr(), None, oL.data_ptr(), oR.data_ptr(), nfr, C.c_void_p(stream)))
+        return oL, oR
+
+    def set_cw_tone(self, cos, sin):
+        """cosBuffer2 and sinBuffer2 (t41tx_set_cw_tone), 256 floats each, e.g. sine_tone(8).  Kept across set_params()
+        and reset(); takes effect from the next CW_ExciterIQData()."""
+        c = np.ascontiguousarray(np.asarray(cos, dtype=np.float32))
+        s = np.ascontiguousarray(np.asarray(sin, dtype=np.float32))
+        if c.shape != (256,) or s.shape != (256,):
+            raise ValueError("CW tone tables must be 256 floats each, got %r and %r" % (c.shape, s.shape))
+        check(self._lib.t41tx_set_cw_tone(self._ctx, c.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p)))
+
+    def CW_ExciterIQData(self, n_frames, key=None, device=False):
+        """n_frames frames of the CW exciter on every channel -> (Q_out_L_Ex, Q_out_R_Ex), [n_channels, n_frames * 2048]
+        int16.  key: uint8 [n_channels, n_frames * 16], one byte per 128-sample block (nonzero passes it, zero writes
+        zeros), or None for key down throughout.  A numpy key, or None with device=False, uses the host entry and
+        returns numpy arrays; a torch uint8 CUDA key, or device=True, runs on the current stream and returns torch
+        tensors.  The interpolator memories are the ones ExciterIQData() uses."""
+        nfr = int(n_frames)
+        kshape = (self.n_channels, nfr * self.KEY_PER_FRAME)
+        if key is None and not device or isinstance(key, np.ndarray):
+            k = None
+            if key is not None:
+                k = np.ascontiguousarray(key, dtype=np.uint8)
+                if k.shape != kshape:
+                    raise ValueError("key must be [n_channels=%d, n_frames*16=%d], got %r" % (kshape + (k.shape,)))
+            oL = np.empty((self.n_channels, max(nfr, 0) * self.FRAME), np.int16)
+            oR = np.empty_like(oL)
+            p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
+            check(self._lib.t41tx_process_cw_host_q15(self._ctx, p(k), p(oL), p(oR), nfr))
+            return oL, oR
+        import torch
+        dev = torch.device("cuda", self.device)
+        if key is not None:
+            if not (isinstance(key, torch.Tensor) and key.is_cuda and key.dtype == torch.uint8 and key.is_contiguous()
+                    and key.device.index == self.device):
+                raise ValueError("key must be a numpy array or a contiguous uint8 CUDA tensor on device %d" % self.device)
+            if tuple(key.shape) != kshape:
+                raise ValueError("key must be [n_channels=%d, n_frames*16=%d], got %r" % (kshape + (tuple(key.shape),)))
+        oL = torch.empty((self.n_channels, max(nfr, 0) * self.FRAME), dtype=torch.int16, device=dev)
+        oR = torch.empty_like(oL)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(self._lib.t41tx_process_cw_device_q15(self._ctx, None if key is None else key.data_ptr(), oL.data_ptr(), oR.data_ptr(),
+                                                    nfr, C.c_void_p(stream)))
         return oL, oR
 
     def _frames(self, shape):
