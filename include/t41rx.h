@@ -221,7 +221,7 @@ T41RX_API int t41rx_get_receive_eq(const t41rx_ctx *ctx, int32_t *equalizerRec_o
  *   aveCorrResult and combinedCoeff = 10 * aveCorrResult * 100 * goertzelMagnitude of every frame.  aveCorrResult is
  *   (corrResultR + corrResultL) / 2 with corrResultR still the block before's (CWProcessing.cpp:339 runs before :348;
  *   0 at power-on).  The comparison `combinedCoeff > 50` (CWProcessing.cpp:365) and the Morse decoder behind it
- *   (DoCWDecoding(), timed by millis()) stay with the caller.  T41RX_ERR_ARG for 1 with a NULL d_cw, max_frames <= 0 or
+ *   (DoCWDecoding()) are t41rx_set_cw_decoder()'s, below.  T41RX_ERR_ARG for 1 with a NULL d_cw, max_frames <= 0 or
  *   before decode_fir is loaded; T41RX_ERR_UNSUPPORTED for 1 at a long fft_length.  A process call with more than
  *   max_frames frames is refused (T41RX_ERR_ARG), as for the stage taps.  t41rx_get_cw_detector(): 0 / 1, or
  *   T41RX_ERR_ARG for a NULL context.
@@ -239,6 +239,58 @@ T41RX_API int t41rx_set_cw_filter(t41rx_ctx *ctx, int CWFilterIndex);
 T41RX_API int t41rx_get_cw_filter(const t41rx_ctx *ctx);
 T41RX_API int t41rx_set_cw_detector(t41rx_ctx *ctx, int decoderFlag, float *d_cw, int max_frames);
 T41RX_API int t41rx_get_cw_detector(const t41rx_ctx *ctx);
+
+/* The Morse decoder: the rest of DoCWReceiveProcessing() behind the detector -- audioTemp = combinedCoeff > 50
+ * (CWProcessing.cpp:365-371), DoCWDecoding() (:519-639) and its two adaptive histograms, DoGapHistogram() (:655-699) and
+ * DoSignalHistogram() (:759-815) over JackClusteredArrayMax() (:719-745) -- one state machine per channel, on the
+ * firmware's integer, float and double operations as written.  The display behind it (MorseCharacterDisplay(), the
+ * scrolling decodeBuffer, the lock indicator, UpdateIBWPM()) stays with the caller.  fft_length 512 only.
+ *
+ * Gating: the decoder runs exactly when the detector runs and the decoder is switched on -- xmtMode == T41RX_CW_MODE,
+ * t41rx_set_cw_detector(1) and t41rx_set_cw_decoder(1); in the firmware one decoderFlag gates both.  It reads the
+ * detector's combinedCoeff of the call from d_cw.  Otherwise d_text is not written and no word of its state moves.
+ *
+ * What the firmware leaves open, decided here as in the restatement the kernel is held to (tests/cw_decode_model.py):
+ *   The clock.  The firmware reads millis() several times inside one DoCWDecoding() call; here one value serves the
+ *     whole frame: millis(n) = t0_ms + floor(n * num / den), the product in 64 bits, the sum kept to its low 32 bits as
+ *     an int32.  n is the channel's count of decoder frames since power-on or t41rx_reset() (32 bits, unsigned; it
+ *     travels in the checkpoint).  t41rx_set_cw_clock(): num >= 0, den > 0 (T41RX_ERR_ARG otherwise); the default is
+ *     t0_ms = 0, num / den = 32 / 3 -- 2048 samples at 192 kS/s; it takes effect from the next process call and does
+ *     not touch n.  `static long oldTime = millis()` runs on the first call: the frame with n == 0 starts by setting
+ *     oldTime = millis(0).  signalStart and signalEnd start at 0.
+ *   The arrays.  Both histograms live in 3072-word allotments (initCW(), :859-873) of which only words 0 .. 749 are
+ *     ever cleared or scaled; gapHistogram[gapLen] is written for gapLen < 3 * thresholdGeometricMean, the clustered
+ *     maximum of :688 scans up to word 3 * thresholdGeometricMean, :675 reads word 750.  From power-on both averages
+ *     stay below 750 (only signals shorter than 750 ms enter them), so every index stays below 2304: 2304 words of
+ *     gapHistogram and 768 of signalHistogram are carried per channel, zero at power-on, and every firmware access is an
+ *     exact in-bounds access.  (A hand-made checkpoint may hold averages up to 32767 and so reach past the carried
+ *     words: such a word reads 0 and is not written.)  The firstNonEmpty loop of :797-802 has no effect and is left out.
+ *   Power-on.  The firmware's own is partly indeterminate (ditLength is not set before the first retune): the values
+ *     ResetHistograms() (:501-517) leaves, zero / false for everything it does not touch, currentDashJump = 128.
+ *   The tree.  bigMorseCodeTree (:540) is 129 characters; a byte index of 129 .. 255 reads past the literal in the
+ *     firmware and prints '-' here, the tree's own filler.
+ *
+ * t41rx_set_cw_decode_tree(): the 129 bytes of bigMorseCodeTree; n must be 129 (T41RX_ERR_ARG otherwise and for NULL).
+ *   The library has no table of its own.  Kept across t41rx_set_params() / t41rx_set_coeffs().
+ * t41rx_set_cw_decoder(): on = 0 or 1 (T41RX_ERR_ARG otherwise).  With 1, d_text, a device pointer
+ *   [n_channels][n_frames][2] of int32 (n_frames of the process call), receives per frame {the character the frame
+ *   printed or 0, ditLength behind the frame}: a frame prints at most one character -- state 5 prints
+ *   bigMorseCodeTree[currentDecoderIndex], state 6 prints ' '.  currentWPM = 1200 / ditLength is left to the caller.
+ *   T41RX_ERR_ARG for 1 with a NULL d_text, max_frames <= 0 or before the tree is loaded; T41RX_ERR_UNSUPPORTED for 1 at
+ *   a long fft_length.  A process call with more than max_frames frames is refused (T41RX_ERR_ARG).
+ *   t41rx_get_cw_decoder(): 0 / 1, or T41RX_ERR_ARG for a NULL context.
+ * t41rx_reset_cw_histograms(): ResetHistograms(), what the firmware runs at every retune (Encoders.cpp:119-121), on the
+ *   channels whose byte in channels[n] is non-zero (n = n_channels; NULL = all channels): words 0 .. 749 of both
+ *   histograms to zero, gapAtom = ditLength = aveDitLength = 80, gapChar = dahLength = aveDahLength = 240,
+ *   thresholdGeometricMean = 160, valRef1 = valRef2 = 0 -- and nothing else: not the state machine, not n.
+ * Context switches, not t41rx_params fields: tree, switch and clock survive t41rx_set_params() and t41rx_set_coeffs().
+ * The decoder's words start at power-on, change only while it runs, return to power-on with t41rx_reset() and travel in
+ * the checkpoint (section bit 5). */
+T41RX_API int t41rx_set_cw_decode_tree(t41rx_ctx *ctx, const uint8_t *tree, int n);
+T41RX_API int t41rx_set_cw_decoder(t41rx_ctx *ctx, int on, int32_t *d_text, int max_frames);
+T41RX_API int t41rx_get_cw_decoder(const t41rx_ctx *ctx);
+T41RX_API int t41rx_set_cw_clock(t41rx_ctx *ctx, int32_t t0_ms, int32_t num, int32_t den);
+T41RX_API int t41rx_reset_cw_histograms(t41rx_ctx *ctx, const uint8_t *channels, int n);
 
 T41RX_API int t41rx_n_channels(const t41rx_ctx *ctx);
 T41RX_API int t41rx_frame_len(const t41rx_ctx *ctx);
@@ -302,9 +354,16 @@ T41RX_API int t41rx_process_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, cons
  *            present once the equalizer has run in this context; refused at a long fft_length;
  *     bit 4  CW receive: CW_AudioFilter1_state .. CW_AudioFilter5_state (60 floats), the decode FIR's history (63),
  *            corrResultR, aveCorrResultL, aveCorrResultR, 2 zeros: 128 floats per channel -- present once the narrow
- *            filter or the detector has run in this context; refused at a long fft_length.
- * t41rx_state_bytes() therefore GROWS when a noise-reduction stage, the noise blanker, the receive equalizer or a CW
- * stage first runs or the display spectrum is switched on:
+ *            filter or the detector has run in this context; refused at a long fft_length;
+ *     bit 5  CW decoder: 3104 int32 words per channel -- 32 scalars, then signalHistogram[768], then gapHistogram[2304].
+ *            The scalars by word offset: 0 decodeStates, 1 n (the frame count of the clock), 2 oldTime, 3 signalStart,
+ *            4 signalEnd, 5 signalElapsedTime, 6 gapLength, 7 ditLength, 8 dahLength, 9 gapAtom, 10 gapChar,
+ *            11 thresholdGeometricMean (the float's bits), 12 aveDitLength, 13 aveDahLength, 14 valRef1, 15 valRef2,
+ *            16 gapRef1, 17 valFlag, 18 signalStartOld, 19 currentDashJump, 20 currentDecoderIndex, 21 charProcessFlag,
+ *            22 blankFlag, 23 topGapIndex, 24 topGapIndexOld, 25 currentTime, 26 interElementGap, 27 noSignalTimeStamp,
+ *            28 .. 31 zero -- present once the decoder has run in this context; refused at a long fft_length.
+ * t41rx_state_bytes() therefore GROWS when a noise-reduction stage, the noise blanker, the receive equalizer, a CW
+ * stage or the CW decoder first runs or the display spectrum is switched on:
  * query it right before every t41rx_get_state() (a buffer sized at creation gets T41RX_ERR_STATE "state buffer too
  * small").  fft_length cannot change on a live context, so the path records' size never does.
  * t41rx_set_state() refuses (T41RX_ERR_STATE) a checkpoint of another ABI, FFT length or channel count, one with an
@@ -312,7 +371,10 @@ T41RX_API int t41rx_process_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, cons
  * off here or taken at another spectrumZoom, and any word the kernels use as an index, a divisor or a state number that
  * is out of range or not integral: AGC state words, oscillator amplitude, synchronous-detector PLL words (phase in
  * [0, 2 pi], frequency within +-pll_fmax), the notch's leak index, the noise reduction's ring pointers, the zoom ring's
- * pointer.  What it does to the side stages: a section the checkpoint carries is restored; a memory this context has
+ * pointer; of the CW decoder a decodeStates outside {0, 1, 2, 5, 6}, currentDecoderIndex outside 0 .. 255,
+ * currentDashJump outside 0 .. 128, a thresholdGeometricMean that is not finite or outside [1, 750), averages or value
+ * references outside 0 .. 32767, a flag (valFlag, charProcessFlag, blankFlag) outside 0 / 1, a histogram count that is
+ * negative or above 2^27 (seven of them are summed).  What it does to the side stages: a section the checkpoint carries is restored; a memory this context has
  * allocated but the checkpoint does not carry goes back to its power-on values (InitializeDataArrays() /
  * SpectralNoiseReductionInit() / ZoomFFTPrep() / the blanker's zero carry / the equalizer's zero memories) -- never the values of the stream being replaced.
  * T41RX_ERR_STATE is also what t41rx_get_state(), t41rx_process_host() and t41rx_process_host_q15() -- the calls that

@@ -87,6 +87,11 @@ SYMBOLS = {
     "t41rx_get_cw_filter": (C.c_int, [_vp]),
     "t41rx_set_cw_detector": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
     "t41rx_get_cw_detector": (C.c_int, [_vp]),
+    "t41rx_set_cw_decode_tree": (C.c_int, [_vp, _vp, C.c_int]),
+    "t41rx_set_cw_decoder": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
+    "t41rx_get_cw_decoder": (C.c_int, [_vp]),
+    "t41rx_set_cw_clock": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32]),
+    "t41rx_reset_cw_histograms": (C.c_int, [_vp, _vp, C.c_int]),
 }
 
 _lib = None

@@ -25,9 +25,16 @@
 // consecutive table words.  The Goertzel recurrence restarts every block and rides the same walk on the same broadcast
 // sample, its dependent chain hidden behind the 4 independent sums.  The maximum over the lags is order-free.
 //
+// DECODER (cw_decode_kernel): the rest of DoCWReceiveProcessing() behind the detector -- `combinedCoeff > 50` and
+// DoCWDecoding() with its two adaptive histograms (CWProcessing.cpp:365-371, :501-815) -- on integer and double
+// arithmetic, word for word tests/cw_decode_model.py, where the choices the firmware leaves open (the clock, the arrays'
+// extent, power-on, the tree past its literal) are written down.  One lane per channel; see the kernel.
+//
 // INTERPOLATORS BEHIND THE NARROW FILTER (cw_back_kernel): Process.cpp:917-937 operation for operation, where the fused
 // back kernel folds the volume into the x4 taps and contracts; see cw_kernels.hpp.
 #include <hip/hip_runtime.h>
+
+#include <cstring>
 
 #include "cw_kernels.hpp"
 #include "df2t_pipe.hpp"
@@ -266,6 +273,341 @@ __global__ __launch_bounds__(64) void cw_back_kernel(CwBackArgs a) {
   __syncthreads();
   if (lane < P1 - 1) st[kStInt1 + 1 + lane] = s1[lane];
   if (lane < P2 - 1) st[kStInt2 + 1 + lane] = s2[lane];
+}
+
+// ---- the Morse decoder (cw_decode_kernel) -----------------------------------------------------------------------------
+namespace cwd {
+constexpr int kChunk = 32;                 // frames per staging pass: one key bit per frame in a 32-bit mask
+constexpr int kOutPitch = 2 * kChunk + 1;  // (odd: lane c writes row c, no bank conflicts)
+constexpr double kScaleConstant = 1.0 / (1.0 - 0.8);  // SCALE_CONSTANT: slightly above 5
+
+// a histogram word of the LDS copy; a word past the carried allotment reads 0 (only a hand-made checkpoint gets there)
+__device__ inline int rd(const int *h, int i, int cap) { return (unsigned)i < (unsigned)cap ? h[i] : 0; }
+__device__ inline int sub32(int a, int b) { return (int)((unsigned)a - (unsigned)b); }
+
+// JackClusteredArrayMax(&h[base], elements, ., ., ., spread) by all 64 lanes: lane l takes i = spread + l, + 64, ..; the
+// window sums come from the LDS copy.  `>=` in increasing i keeps a lane's last maximum, and the reduction prefers the
+// larger index among equal sums: the last index holding the maximum wins, as in the serial loop.
+__device__ inline void clustered_max(const int *h, int cap, int base, int elements, int spread, int lane, int *maxCount, int *maxIndex) {
+  int best = 0, idx = -1;
+  for (int i = spread + lane; i < elements - spread; i += 64) {
+    int t = 0;
+    for (int j = -spread; j <= spread; ++j) t += rd(h, base + i + j, cap);
+    if (t >= best) {
+      best = t;
+      idx = i;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const int ob = __shfl_xor(best, off), oi = __shfl_xor(idx, off);
+    if (ob > best || (ob == best && oi > idx)) {
+      best = ob;
+      idx = oi;
+    }
+  }
+  *maxCount = idx > 0 ? rd(h, base + idx, cap) : 0;
+  *maxIndex = idx > 0 ? idx : 0;
+}
+}  // namespace cwd
+
+// One lane per channel, 64 channels per wave, frame after frame; the scalars live in registers from the first frame of
+// the call to the last.  Per pass of 32 frames the wave reads the 32 combinedCoeff words of each of its channels with
+// one load (consecutive frames in consecutive lanes), turns them into key bits by a ballot that the channel's lane
+// keeps, runs the frames, and stores the staged {character, ditLength} words row by row.
+// A histogram call (at most one per channel and 5000 ms of its clock) is served by the whole wave inside the frame
+// loop, since its results feed the next frame: the lanes with an event are balloted and taken one at a time, the
+// channel's parameters broadcast, its histogram copied to LDS, and all 64 lanes do the scaling pass, the clustered
+// maxima and the top-of-range scan there.  What the lane itself can do -- the value references, the averages, the
+// geometric mean -- it does before the wave serves it.
+__global__ __launch_bounds__(64) void cw_decode_kernel(CwDecodeArgs a) {
+#pragma clang fp contract(off)
+  using namespace cwd;
+  __shared__ int hl[kCwDecGapWords];
+  __shared__ int outl[64 * kOutPitch];
+  __shared__ unsigned char tree[kCwTreeChars + 3];
+  const int lane = threadIdx.x;
+  const int ch0 = blockIdx.x * 64;
+  const int nlive = min(64, a.nchan - ch0);
+  const bool live = lane < nlive;
+  int32_t *w = a.state + (size_t)(ch0 + (live ? lane : 0)) * kCwDecWords;
+  for (int i = lane; i < kCwTreeChars; i += 64) tree[i] = a.tree[i];
+
+  int st = w[kCwDecState];
+  unsigned n = (unsigned)w[kCwDecN];
+  int oldTime = w[kCwDecOldTime], signalStart = w[kCwDecSignalStart], signalEnd = w[kCwDecSignalEnd];
+  int elapsed = w[kCwDecElapsed], gapLength = w[kCwDecGapLength];
+  unsigned ditLength = (unsigned)w[kCwDecDitLength];
+  int dahLength = w[kCwDecDahLength], gapAtom = w[kCwDecGapAtom], gapChar = w[kCwDecGapChar];
+  float tgm = __int_as_float(w[kCwDecTgm]);
+  int aveDit = w[kCwDecAveDit], aveDah = w[kCwDecAveDah], valRef1 = w[kCwDecValRef1], valRef2 = w[kCwDecValRef2];
+  int gapRef1 = w[kCwDecGapRef1], valFlag = w[kCwDecValFlag], signalStartOld = w[kCwDecSignalStartOld];
+  int dashJump = w[kCwDecDashJump], index = w[kCwDecIndex];
+  bool charFlag = w[kCwDecCharFlag] != 0, blankFlag = w[kCwDecBlankFlag] != 0;
+  int topGap = w[kCwDecTopGap], topGapOld = w[kCwDecTopGapOld];
+  int currentTime = w[kCwDecCurrentTime], interGap = w[kCwDecInterGap], noSignal = w[kCwDecNoSignal];
+  __syncthreads();
+
+  for (int f0 = 0; f0 < a.nframes; f0 += kChunk) {
+    const int nf = min(kChunk, a.nframes - f0);
+    unsigned keys = 0;  // bit k: combinedCoeff > 50 in frame f0 + k (CWProcessing.cpp:365)
+    for (int k0 = 0; k0 < nlive; k0 += 8) {  // (8 channels' loads in flight)
+      float v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        v[j] = (k0 + j < nlive && lane < nf) ? a.cw[((size_t)(ch0 + k0 + j) * a.nframes + f0 + lane) * 4 + 3] : 0.0f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const unsigned m = (unsigned)__ballot(v[j] > 50.0f);
+        if (lane == k0 + j) keys = m;
+      }
+    }
+    for (int fr = 0; fr < nf; ++fr) {
+      const bool key = (keys >> fr) & 1u;
+      const int now = (int)((unsigned)a.t0 + (unsigned)(((unsigned long long)n * (unsigned)a.num) / (unsigned)a.den));
+      if (n == 0) oldTime = a.t0;  // static long oldTime = millis();
+      int ch = 0, ev = 0, evval = 0;  // ev: 1 = DoGapHistogram(evval), 2 = DoSignalHistogram(evval)
+      if (st == 0) {
+        if (key) {
+          signalStart = now;
+          st = 1;
+          gapLength = sub32(signalStart, signalEnd);
+          if (gapLength > 20 && (unsigned)gapLength < (unsigned)(tgm * 3.0f) && sub32(signalStart, oldTime) > 5000) {
+            ev = 1;
+            evval = gapLength;
+            oldTime = signalStart;
+          }
+        } else {
+          noSignal = now;
+          interGap = sub32(noSignal, signalEnd);
+          if ((double)interGap > (double)ditLength * 1.95 && charFlag)
+            st = 5;
+          else if ((double)interGap > (double)ditLength * 4.5 && !blankFlag && !charFlag)
+            st = 6;
+        }
+      } else if (st == 1) {
+        if (!key) {
+          currentTime = now;
+          elapsed = sub32(currentTime, signalStart);
+          if (elapsed < 20) {
+            st = 0;
+          } else {
+            if (elapsed > 20 && elapsed < kCwHistElements && sub32(currentTime, oldTime) > 5000) {
+              ev = 2;
+              evval = elapsed;
+              oldTime = currentTime;
+              // DoSignalHistogram() up to the arrays, :765-789
+              if (valFlag == 0) {
+                valRef1 = elapsed;
+                signalStartOld = now;
+                valFlag = 1;
+              }
+              if ((unsigned)now - (unsigned)signalStartOld > 20u && valFlag == 1) {
+                gapRef1 = gapLength;
+                valRef2 = elapsed;
+                valFlag = 0;
+              }
+              const float v1 = (float)valRef1, v2 = (float)valRef2, g1 = (float)gapRef1;
+              if ((v2 >= v1 * 2.0f && g1 <= v1 * 2.0f) || (v1 >= v2 * 2.0f && g1 <= v2 * 2.0f)) {
+                const bool ditFirst = valRef2 >= valRef1;
+                const int dit = ditFirst ? valRef1 : valRef2, dah = ditFirst ? valRef2 : valRef1;
+                aveDit = (int)(0.9 * (double)aveDit + 0.1 * (double)dit);
+                aveDah = (int)(0.9 * (double)aveDah + 0.1 * (double)dah);
+              }
+              // sqrt() in double, then to float.  The device's f64 sqrt is correctly rounded, as the host's.  (And the
+              // float behind it does not hang on the double's last bit: the product N is an integer below 2^30 and a
+              // midpoint m between two floats has 25 bits, so N - m^2 is zero or at least 2^-51 of N -- the root is an
+              // integer or two double ulps and more away from every midpoint.)
+              tgm = (float)sqrt((double)(int)((unsigned)aveDit * (unsigned)aveDah));
+            }
+            signalEnd = currentTime;
+            st = 2;
+          }
+        }
+      } else if (st == 2) {
+        if ((double)elapsed > 0.5 * (double)ditLength) {
+          dashJump >>= 1;
+          index = (index + (elapsed < (int)tgm ? 1 : dashJump)) & 255;
+          charFlag = true;
+        }
+        st = 0;
+      } else if (st == 5) {
+        ch = index < kCwTreeChars ? (int)tree[index] : (int)'-';  // (past the literal: the tree's own filler)
+        index = 0;
+        dashJump = 128;
+        charFlag = false;
+        blankFlag = false;
+        st = 0;
+      } else if (st == 6) {
+        ch = (int)' ';
+        blankFlag = true;
+        st = 0;
+      }
+      ++n;
+      if (!live) ev = 0;
+
+      // the histogram calls of this frame, one channel at a time, by the whole wave
+      unsigned long long pending = __ballot(ev != 0);
+      while (pending) {
+        const int src = __ffsll((long long)pending) - 1;
+        pending &= pending - 1;
+        // (wave-uniform by construction; said so, so that the branches and loop bounds below are scalar)
+        const int type = __builtin_amdgcn_readfirstlane(__shfl(ev, src)), val = __builtin_amdgcn_readfirstlane(__shfl(evval, src));
+        const float t = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(__shfl(tgm, src))));
+        int32_t *g = a.state + (size_t)(ch0 + src) * kCwDecWords + (type == 1 ? kCwDecOffGap : kCwDecOffSig);
+        const int cap = type == 1 ? kCwDecGapWords : kCwDecSigWords;
+        __syncthreads();
+        for (int k = lane; k < cap; k += 64) hl[k] = g[k];
+        __syncthreads();
+        bool scaled;
+        if (type == 2) {
+          // :791-814
+          if (lane == 0 && (unsigned)val < (unsigned)cap) hl[val] += 1;
+          __syncthreads();
+          const int offset = (int)((unsigned)t - 1u);
+          int tempDit, dit, tempDah, dah;
+          clustered_max(hl, cap, 0, offset, 1, lane, &tempDit, &dit);
+          clustered_max(hl, cap, offset, kCwHistElements - offset, 3, lane, &tempDah, &dah);
+          scaled = (double)tempDit > kScaleConstant && (double)tempDah > kScaleConstant;
+          __syncthreads();
+          if (scaled)
+            for (int k = lane; k < kCwHistElements; k += 64) hl[k] = (int)(0.8 * (double)hl[k]);
+          if (lane == src) {
+            ditLength = (unsigned)dit;
+            dahLength = dah + offset;
+          }
+        } else {
+          // DoGapHistogram(), :660-698
+          scaled = rd(hl, val, cap) > 10;
+          __syncthreads();
+          if (scaled)
+            for (int k = lane; k < kCwHistElements; k += 64) hl[k] = (int)(unsigned)(.8 * (double)(float)hl[k]);
+          __syncthreads();
+          if (lane == 0 && (unsigned)val < (unsigned)cap) hl[val] += 1;
+          __syncthreads();
+          int atom = __shfl(gapAtom, src), top = __shfl(topGap, src), chr = 0;
+          const int topOld = __shfl(topGapOld, src);
+          const bool atomBranch = (float)val <= t;
+          if (atomBranch) {
+            int cnt, atomIndex;
+            clustered_max(hl, cap, 0, (int)(unsigned)t, 1, lane, &cnt, &atomIndex);
+            if (atomIndex) atom = atomIndex;
+            // :674-684: the highest non-empty word below 2 * gapAtom, counting down from word 750
+            const int twice = (int)(2u * (unsigned)atom);
+            int found = 0;
+            for (int i = 1 + lane; i <= kCwHistElements; i += 64)
+              if (hl[i] > 0 && i < twice) found = i;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) found = max(found, __shfl_xor(found, off));
+            if (found)
+              top = found;
+            else if (top > twice)
+              top = topOld;  // discard outliers
+          } else if ((float)val <= t * 2.0f) {
+            int cnt;
+            clustered_max(hl, cap, (int)t + 1, (int)(unsigned)(t * 2.0f), 3, lane, &cnt, &chr);
+          }
+          if (lane == src) {
+            gapAtom = atom;
+            if (atomBranch) {
+              topGap = top;
+              topGapOld = top;
+            }
+            if (chr) gapChar = chr;
+          }
+        }
+        __syncthreads();
+        // what changed goes back: words 0 .. 749 after a scaling pass, and the incremented word where that pass did not
+        // cover it (no pass, or a gap of 750 ms and more: gapLen runs up to 3 * thresholdGeometricMean)
+        if (scaled)
+          for (int k = lane; k < kCwHistElements; k += 64) g[k] = hl[k];
+        if (lane == 0 && (unsigned)val < (unsigned)cap && (!scaled || val >= kCwHistElements)) g[val] = hl[val];
+      }
+      outl[lane * kOutPitch + 2 * fr] = ch;
+      outl[lane * kOutPitch + 2 * fr + 1] = (int)ditLength;
+    }
+    __syncthreads();
+    for (int kk = 0; kk < nlive; ++kk)
+      if (lane < 2 * nf) a.text[((size_t)(ch0 + kk) * a.nframes + f0) * 2 + lane] = outl[kk * kOutPitch + lane];
+    __syncthreads();
+  }
+  if (live) {
+    w[kCwDecState] = st;
+    w[kCwDecN] = (int)n;
+    w[kCwDecOldTime] = oldTime;
+    w[kCwDecSignalStart] = signalStart;
+    w[kCwDecSignalEnd] = signalEnd;
+    w[kCwDecElapsed] = elapsed;
+    w[kCwDecGapLength] = gapLength;
+    w[kCwDecDitLength] = (int)ditLength;
+    w[kCwDecDahLength] = dahLength;
+    w[kCwDecGapAtom] = gapAtom;
+    w[kCwDecGapChar] = gapChar;
+    w[kCwDecTgm] = __float_as_int(tgm);
+    w[kCwDecAveDit] = aveDit;
+    w[kCwDecAveDah] = aveDah;
+    w[kCwDecValRef1] = valRef1;
+    w[kCwDecValRef2] = valRef2;
+    w[kCwDecGapRef1] = gapRef1;
+    w[kCwDecValFlag] = valFlag;
+    w[kCwDecSignalStartOld] = signalStartOld;
+    w[kCwDecDashJump] = dashJump;
+    w[kCwDecIndex] = index;
+    w[kCwDecCharFlag] = charFlag ? 1 : 0;
+    w[kCwDecBlankFlag] = blankFlag ? 1 : 0;
+    w[kCwDecTopGap] = topGap;
+    w[kCwDecTopGapOld] = topGapOld;
+    w[kCwDecCurrentTime] = currentTime;
+    w[kCwDecInterGap] = interGap;
+    w[kCwDecNoSignal] = noSignal;
+  }
+}
+
+// ResetHistograms() (CWProcessing.cpp:501-517), one wave per channel
+__global__ __launch_bounds__(64) void cw_decode_reset_kernel(int32_t *state, const uint8_t *mask, int nchan) {
+  const int chan = blockIdx.x, lane = threadIdx.x;
+  if (chan >= nchan || (mask && !mask[chan])) return;
+  int32_t *w = state + (size_t)chan * kCwDecWords;
+  for (int k = lane; k < kCwHistElements; k += 64) {
+    w[kCwDecOffSig + k] = 0;
+    w[kCwDecOffGap + k] = 0;
+  }
+  if (lane == 0) {
+    w[kCwDecGapAtom] = 80;
+    w[kCwDecDitLength] = 80;
+    w[kCwDecGapChar] = 240;
+    w[kCwDecDahLength] = 240;
+    w[kCwDecTgm] = __float_as_int(160.0f);
+    w[kCwDecAveDit] = 80;
+    w[kCwDecAveDah] = 240;
+    w[kCwDecValRef1] = 0;
+    w[kCwDecValRef2] = 0;
+  }
+}
+
+void cw_decode_power_on(int32_t *w) {
+  for (int k = 0; k < kCwDecWords; ++k) w[k] = 0;
+  const float tgm = 160.0f;
+  w[kCwDecGapAtom] = 80;
+  w[kCwDecDitLength] = 80;
+  w[kCwDecGapChar] = 240;
+  w[kCwDecDahLength] = 240;
+  std::memcpy(&w[kCwDecTgm], &tgm, sizeof(tgm));
+  w[kCwDecAveDit] = 80;
+  w[kCwDecAveDah] = 240;
+  w[kCwDecDashJump] = 128;  // DECODER_BUFFER_SIZE
+}
+
+hipError_t launch_cw_decode(const CwDecodeArgs &a, hipStream_t s) {
+  if (a.nchan <= 0 || a.nframes <= 0 || !a.cw || !a.state || !a.text || a.num < 0 || a.den <= 0) return hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(cw_decode_kernel, dim3((unsigned)((a.nchan + 63) / 64)), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_cw_decode_reset(int32_t *state, const uint8_t *mask, int nchan, hipStream_t s) {
+  if (nchan <= 0 || !state) return hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(cw_decode_reset_kernel, dim3((unsigned)nchan), dim3(64), 0, s, state, mask, nchan);
+  return hipGetLastError();
 }
 
 hipError_t launch_cw_filter(const CwFilterArgs &a, hipStream_t s) {

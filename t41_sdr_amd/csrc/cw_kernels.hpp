@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+
 namespace t41 {
 
 constexpr int kCwFilters = 5;                        // CWFilterIndex 0 .. 4 (5 = off)
@@ -59,5 +61,64 @@ struct CwBackArgs {
   float int2[32];    // FIR_int2_coeffs (not scaled)
 };
 hipError_t launch_cw_back(const CwBackArgs &a, hipStream_t s);
+
+// ---- the Morse decoder behind the detector: DoCWDecoding() and its histograms (CWProcessing.cpp:365-371, :501-815) ----
+// Per channel kCwDecWords int32 words, the checkpoint section's layout and the device's alike: kCwDecScalars scalars (by
+// name below; thresholdGeometricMean as its float's bits, the two flags as 0 / 1, words 28 .. 31 zero), then
+// signalHistogram (kCwDecSigWords), then gapHistogram (kCwDecGapWords).  The firmware gives either histogram a 3072-word
+// allotment and clears and scales words 0 .. 749 only; from power-on no access goes past word 2303 (gap) or 749
+// (signal), so carrying 2304 and 768 words makes every firmware access an exact in-bounds one (tests/cw_decode_model.py).
+constexpr int kCwDecScalars = 32, kCwDecSigWords = 768, kCwDecGapWords = 2304;
+constexpr int kCwDecOffSig = kCwDecScalars, kCwDecOffGap = kCwDecScalars + kCwDecSigWords;
+constexpr int kCwDecWords = kCwDecOffGap + kCwDecGapWords;  // 3104
+constexpr int kCwHistElements = 750;                       // HISTOGRAM_ELEMENTS
+constexpr int kCwTreeChars = 129;                          // bigMorseCodeTree
+enum CwDecWord : int {
+  kCwDecState = 0,     // decodeStates: 0, 1, 2, 5, 6
+  kCwDecN,             // decoder frames since power-on or reset (unsigned): millis(n) = t0 + floor(n * num / den)
+  kCwDecOldTime,       // oldTime (set to millis(0) by the frame with n == 0, as the static's initialiser does)
+  kCwDecSignalStart,
+  kCwDecSignalEnd,
+  kCwDecElapsed,       // signalElapsedTime
+  kCwDecGapLength,
+  kCwDecDitLength,     // (unsigned long)
+  kCwDecDahLength,
+  kCwDecGapAtom,
+  kCwDecGapChar,
+  kCwDecTgm,           // thresholdGeometricMean, float bits
+  kCwDecAveDit,
+  kCwDecAveDah,
+  kCwDecValRef1,
+  kCwDecValRef2,
+  kCwDecGapRef1,
+  kCwDecValFlag,
+  kCwDecSignalStartOld,
+  kCwDecDashJump,      // currentDashJump (byte)
+  kCwDecIndex,         // currentDecoderIndex (byte)
+  kCwDecCharFlag,      // charProcessFlag
+  kCwDecBlankFlag,
+  kCwDecTopGap,        // topGapIndex
+  kCwDecTopGapOld,
+  kCwDecCurrentTime,
+  kCwDecInterGap,      // interElementGap
+  kCwDecNoSignal,      // noSignalTimeStamp
+  kCwDecNamed          // 28
+};
+static_assert(kCwDecNamed <= kCwDecScalars, "scalars");
+
+struct CwDecodeArgs {
+  const float *cw;   // the detector's results of this call [nchan][nframes][4]: combinedCoeff is word 3
+  int32_t *state;    // [nchan][kCwDecWords]
+  int32_t *text;     // [nchan][nframes][2]: {character code or 0, ditLength behind the frame}
+  int nchan, nframes;
+  int32_t t0, num, den;               // the clock (t41rx_set_cw_clock)
+  uint8_t tree[kCwTreeChars + 3];     // bigMorseCodeTree (the caller's)
+};
+hipError_t launch_cw_decode(const CwDecodeArgs &a, hipStream_t s);
+// ResetHistograms() (CWProcessing.cpp:501-517) on the channels whose mask byte is non-zero (mask: device pointer, or null
+// for all): words 0 .. 749 of both histograms and the scalars it names
+hipError_t launch_cw_decode_reset(int32_t *state, const uint8_t *mask, int nchan, hipStream_t s);
+// the power-on words of one channel (host): what ResetHistograms() leaves, currentDashJump = 128, everything else zero
+void cw_decode_power_on(int32_t *w);
 
 }  // namespace t41

@@ -104,6 +104,17 @@ struct t41rx_ctx {
   float *cw_out = nullptr;  // [nchan][n_frames][4]
   int cw_frames = 0;        // frames per call cw_out is sized for
   DevBuf<float> d_cw;
+  // the Morse decoder behind the detector (DoCWDecoding(), CWProcessing.cpp:519-639; t41rx_set_cw_decode_tree / _decoder /
+  // _clock): the caller's bigMorseCodeTree, the switch with the caller's text buffer, the clock millis(n) = t0 +
+  // floor(n * num / den), and the decoder's words per channel [nchan][kCwDecWords] (cw_kernels.hpp), allocated when the
+  // decoder first runs.  It runs exactly when the detector runs and the switch is on.
+  bool cw_have_tree = false;
+  uint8_t cw_tree[kCwTreeChars + 3] = {};
+  int cw_dec = 0;
+  int32_t *cw_text = nullptr;  // [nchan][n_frames][2]
+  int cw_text_frames = 0;      // frames per call cw_text is sized for
+  int32_t cw_t0 = 0, cw_num = 32, cw_den = 3;  // 2048 samples at 192 kS/s
+  DevBuf<int32_t> d_cwdec;
   // staging for t41rx_process_host
   DevBuf<float> d_in_i, d_in_q, d_out;
   size_t staging_floats = 0;
@@ -336,6 +347,44 @@ int ensure_cw(t41rx_ctx *ctx) {
   return ensure_zeroed(ctx->d_cw, sizeof(float) * kCwStateFloats * (size_t)ctx->nchan, "CW-receive");
 }
 
+// the decoder's words at power-on: what ResetHistograms() leaves, currentDashJump = 128, everything else zero
+hipError_t cw_decode_upload_power_on(int32_t *d, int nchan) {
+  std::vector<int32_t> h((size_t)kCwDecWords * (size_t)nchan);
+  for (int c = 0; c < nchan; ++c) cw_decode_power_on(h.data() + (size_t)kCwDecWords * (size_t)c);
+  return hipMemcpy(d, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice);
+}
+int ensure_cw_decode(t41rx_ctx *ctx) {
+  if (ctx->d_cwdec) return T41RX_OK;
+  DevBuf<int32_t> d;
+  if (dev_alloc(d, sizeof(int32_t) * kCwDecWords * (size_t)ctx->nchan) != hipSuccess) return fail(T41RX_ERR_NOMEM, "CW-decoder state allocation failed");
+  if (cw_decode_upload_power_on(d.get(), ctx->nchan) != hipSuccess) return fail(T41RX_ERR_HIP, "CW-decoder state upload failed");
+  ctx->d_cwdec = std::move(d);
+  return T41RX_OK;
+}
+// what cw_decode_kernel indexes, loops or branches with (cw_kernel.hip), per channel of a host section
+int check_cw_decode(const t41rx_ctx *c, const int32_t *, const float *sec) {
+  const int32_t *all = reinterpret_cast<const int32_t *>(sec);
+  for (int ch = 0; ch < c->nchan; ++ch) {
+    const int32_t *w = all + (size_t)kCwDecWords * (size_t)ch;
+    const int st = w[kCwDecState];
+    if (!(st == 0 || st == 1 || st == 2 || st == 5 || st == 6)) return fail(T41RX_ERR_STATE, "checkpoint: CW decoder state number out of range");
+    if (w[kCwDecIndex] < 0 || w[kCwDecIndex] > 255) return fail(T41RX_ERR_STATE, "checkpoint: CW decoder currentDecoderIndex out of range");
+    if (w[kCwDecDashJump] < 0 || w[kCwDecDashJump] > 128) return fail(T41RX_ERR_STATE, "checkpoint: CW decoder currentDashJump out of range");
+    float tgm;
+    std::memcpy(&tgm, &w[kCwDecTgm], sizeof(tgm));
+    if (!std::isfinite(tgm) || !(tgm >= 1.0f && tgm < 750.0f))
+      return fail(T41RX_ERR_STATE, "checkpoint: CW decoder thresholdGeometricMean not finite or out of range");
+    // (the averages' product is formed in 32 bits; the value references enter the averages)
+    for (int k : {kCwDecAveDit, kCwDecAveDah, kCwDecValRef1, kCwDecValRef2})
+      if (w[k] < 0 || w[k] > 32767) return fail(T41RX_ERR_STATE, "checkpoint: CW decoder averages or value references out of range");
+    for (int k : {kCwDecValFlag, kCwDecCharFlag, kCwDecBlankFlag})
+      if (w[k] != 0 && w[k] != 1) return fail(T41RX_ERR_STATE, "checkpoint: CW decoder flag (valFlag, charProcessFlag, blankFlag) not 0 or 1");
+    for (int k = kCwDecOffSig; k < kCwDecWords; ++k)  // seven of them are summed in 32 bits
+      if (w[k] < 0 || w[k] > (1 << 27)) return fail(T41RX_ERR_STATE, "checkpoint: CW decoder histogram count out of range");
+  }
+  return T41RX_OK;
+}
+
 // a broken hand-over protocol of the pipelined kernels leaves wrong samples and a count of waits that ran out, not a hung
 // GPU -- reported at the calls that synchronise anyway
 int pipe_timeouts(const t41rx_ctx *ctx) {  // < 0: the counter could not be read
@@ -362,7 +411,7 @@ int pipe_status(const t41rx_ctx *ctx) {
 // ---- checkpoint (t41rx_get_state / t41rx_set_state): header, the path's records, then the sections header word 5 names
 constexpr uint32_t kStateMagic = 0x54343153u;  // "T41S"
 constexpr size_t kStateHeaderBytes = 32;
-constexpr int32_t kSecNr = 1, kSecDisp = 2, kSecNb = 4, kSecEq = 8, kSecCw = 16;
+constexpr int32_t kSecNr = 1, kSecDisp = 2, kSecNb = 4, kSecEq = 8, kSecCw = 16, kSecCwDec = 32;
 
 // One checkpoint section: the memories of a stage built for fft_length 512 only.
 struct Section {
@@ -459,6 +508,16 @@ const Section kSections[] = {
      [](const t41rx_ctx *c, void *h, size_t n) { return hip_check(hipMemcpy(h, c->d_cw.get(), n, hipMemcpyDeviceToHost), "hipMemcpy"); },
      [](t41rx_ctx *c, const void *h, size_t n) { return hip_check(hipMemcpy(c->d_cw.get(), h, n, hipMemcpyHostToDevice), "hipMemcpy"); },
      [](t41rx_ctx *c, size_t n) { return c->d_cw ? hip_check(hipMemset(c->d_cw.get(), 0, n), "hipMemset") : T41RX_OK; }},  // (zeroed statics)
+    // CW decoder: DoCWDecoding()'s statics and the globals it shares with its histograms (CWProcessing.cpp:26-99,
+    // :538-550), then signalHistogram, then gapHistogram, [n_channels][kCwDecWords] int32 words (cw_kernels.hpp names
+    // them) -- present once the decoder has run
+    {kSecCwDec, "CW-decoder", (size_t)kCwDecWords,
+     [](const t41rx_ctx *c) { return c->d_cwdec != nullptr; }, ensure_cw_decode, check_cw_decode,
+     [](const t41rx_ctx *c, void *h, size_t n) { return hip_check(hipMemcpy(h, c->d_cwdec.get(), n, hipMemcpyDeviceToHost), "hipMemcpy"); },
+     [](t41rx_ctx *c, const void *h, size_t n) { return hip_check(hipMemcpy(c->d_cwdec.get(), h, n, hipMemcpyHostToDevice), "hipMemcpy"); },
+     [](t41rx_ctx *c, size_t) {
+       return c->d_cwdec ? hip_check(cw_decode_upload_power_on(c->d_cwdec.get(), c->nchan), "CW-decoder reset") : T41RX_OK;
+     }},
 };
 
 size_t section_bytes(const Section &s, int nchan) { return sizeof(float) * s.chan_floats * (size_t)nchan; }
@@ -526,6 +585,8 @@ bool nr_on(const t41rx_ctx *ctx) { return ctx->params.nrOptionSelect != 0 || ctx
 // (T41_SDR.ino:1039-1040, 1144-1148); with another xmtMode the switches are kept and nothing runs
 bool cw_filter_on(const t41rx_ctx *ctx) { return ctx->params.xmtMode == T41RX_CW_MODE && ctx->cw_filter != kCwFilters; }
 bool cw_det_on(const t41rx_ctx *ctx) { return ctx->params.xmtMode == T41RX_CW_MODE && ctx->cw_det != 0; }
+// the decoder runs exactly when the detector runs (in the firmware one decoderFlag gates both, CWProcessing.cpp:322-372)
+bool cw_dec_on(const t41rx_ctx *ctx) { return cw_det_on(ctx) && ctx->cw_dec != 0; }
 // the fused kernel stops behind the demodulator; stage kernels; back kernel (fft_length 512: t41rx_set_noise_blanker,
 // t41rx_set_receive_eq, t41rx_set_cw_filter, t41rx_set_cw_detector)
 bool stages_on(const t41rx_ctx *ctx) { return ctx->eq_on || nr_on(ctx) || ctx->nb_on || cw_filter_on(ctx) || cw_det_on(ctx); }
@@ -582,6 +643,8 @@ int prepare_call(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
     return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the audio-spectrum buffers were set with");
   if (ctx->disp_spec && n_frames > ctx->disp_frames)
     return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the display-spectrum buffers were set with");
+  if (cw_dec_on(ctx) && n_frames > ctx->cw_text_frames)
+    return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the CW decoder's buffer was set with");
   if (cw_det_on(ctx) && n_frames > ctx->cw_frames)
     return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the CW detector's buffer was set with");
   if (cw_det_on(ctx))
@@ -590,6 +653,8 @@ int prepare_call(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
                                              " leaves float_buffer_L different from float_buffer_R and neither the notch nor the noise "
                                              "blanker joins them behind it; the library carries one audio stream");
   if (ctx->disp_spec && (!ctx->d_pre || !ctx->d_disp || !ctx->d_win)) return fail(T41RX_ERR_STATE, "display spectrum enabled without its buffers");
+  // the decoder's words, behind every refusal: its checkpoint section appears with the first call in which it runs
+  if (cw_dec_on(ctx) && (rc = ensure_cw_decode(ctx)) != T41RX_OK) return rc;
   return T41RX_OK;
 }
 
@@ -734,6 +799,21 @@ int launch_chain(t41rx_ctx *ctx, RxArgs a, int n_frames, hipStream_t s) {
     std::memcpy(d.fir, ctx->cw_fir, sizeof(d.fir));
     e = launch_cw_detect(d, s);
     if (e != hipSuccess) return hip_fail(e, "CW detector kernel launch");
+  }
+  if (cw_dec_on(ctx)) {
+    // CWProcessing.cpp:365-371 behind it: the threshold on the detector's combinedCoeff and DoCWDecoding()
+    CwDecodeArgs d{};
+    d.cw = ctx->cw_out;
+    d.state = ctx->d_cwdec.get();
+    d.text = ctx->cw_text;
+    d.nchan = ctx->nchan;
+    d.nframes = n_frames;
+    d.t0 = ctx->cw_t0;
+    d.num = ctx->cw_num;
+    d.den = ctx->cw_den;
+    std::memcpy(d.tree, ctx->cw_tree, sizeof(d.tree));
+    e = launch_cw_decode(d, s);
+    if (e != hipSuccess) return hip_fail(e, "CW decoder kernel launch");
   }
   if (cw_filter_on(ctx)) {
     // Process.cpp:882-912: the narrow filter CWFilterIndex selects, on its own memory
@@ -1133,6 +1213,57 @@ int t41rx_set_cw_detector(t41rx_ctx *ctx, int decoderFlag, float *d_cw, int max_
   return T41RX_OK;
 }
 int t41rx_get_cw_detector(const t41rx_ctx *ctx) { return ctx ? ctx->cw_det : T41RX_ERR_ARG; }
+
+int t41rx_set_cw_decode_tree(t41rx_ctx *ctx, const uint8_t *tree, int n) {
+  if (!ctx || !tree) return fail(T41RX_ERR_ARG, "null argument");
+  if (n != kCwTreeChars) return fail(T41RX_ERR_ARG, "CW decode tree: n must be 129 (bigMorseCodeTree)");
+  std::memcpy(ctx->cw_tree, tree, (size_t)kCwTreeChars);  // (passed by value to every launch: the next call uses it)
+  ctx->cw_have_tree = true;
+  return T41RX_OK;
+}
+
+int t41rx_set_cw_decoder(t41rx_ctx *ctx, int on, int32_t *d_text, int max_frames) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (on != 0 && on != 1) return fail(T41RX_ERR_ARG, "CW decoder: on must be 0 or 1");
+  if (on) {
+    if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the CW decoder is built for fft_length 512");
+    if (!d_text) return fail(T41RX_ERR_ARG, "CW decoder: no text buffer (d_text is NULL)");
+    if (reinterpret_cast<uintptr_t>(d_text) & 3u) return fail(T41RX_ERR_ARG, "unaligned pointer");
+    if (max_frames <= 0) return fail(T41RX_ERR_ARG, "max_frames must be > 0");
+    if (!ctx->cw_have_tree) return fail(T41RX_ERR_ARG, "CW decoder: no decode tree loaded (t41rx_set_cw_decode_tree)");
+  }
+  ctx->cw_dec = on;
+  ctx->cw_text = on ? d_text : nullptr;
+  ctx->cw_text_frames = on ? max_frames : 0;
+  return T41RX_OK;
+}
+int t41rx_get_cw_decoder(const t41rx_ctx *ctx) { return ctx ? ctx->cw_dec : T41RX_ERR_ARG; }
+
+int t41rx_set_cw_clock(t41rx_ctx *ctx, int32_t t0_ms, int32_t num, int32_t den) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (num < 0 || den <= 0) return fail(T41RX_ERR_ARG, "CW clock: num must be >= 0 and den > 0");
+  ctx->cw_t0 = t0_ms;  // (passed by value to every launch: the next call uses it; the frame counters stay)
+  ctx->cw_num = num;
+  ctx->cw_den = den;
+  return T41RX_OK;
+}
+
+int t41rx_reset_cw_histograms(t41rx_ctx *ctx, const uint8_t *channels, int n) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (channels && n != ctx->nchan) return fail(T41RX_ERR_ARG, "n must equal n_channels");
+  if (!ctx->d_cwdec) return T41RX_OK;  // the decoder has not run: its words are the power-on ones, which are ResetHistograms()'s
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  HIP_TRY(hipDeviceSynchronize());
+  DevBuf<uint8_t> mask;
+  if (channels) {
+    HIP_TRY(dev_alloc(mask, (size_t)ctx->nchan));
+    HIP_TRY(hipMemcpy(mask.get(), channels, (size_t)ctx->nchan, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(launch_cw_decode_reset(ctx->d_cwdec.get(), mask.get(), ctx->nchan, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  return T41RX_OK;
+}
 
 int t41rx_n_channels(const t41rx_ctx *ctx) { return ctx ? ctx->nchan : T41RX_ERR_ARG; }
 int t41rx_frame_len(const t41rx_ctx *ctx) { return ctx ? 4 * ctx->params.fft_length : T41RX_ERR_ARG; }

@@ -203,7 +203,7 @@ class RxChain:
         tensor, float32 CUDA [n_channels, max_frames, 4]; a process call of n <= max_frames frames fills its first
         n_channels * n * 4 floats as [n_channels][n][corrResultL, goertzelMagnitude, aveCorrResult, combinedCoeff]
         (cw_results(n) is that view).  on = 0 switches the detector off and returns None.  The `combinedCoeff > 50`
-        decision and the Morse decoder stay with the caller.  Runs only while xmtMode == CW_MODE; fft_length 512; the
+        decision and the Morse decoder behind it are set_cw_decoder()'s.  Runs only while xmtMode == CW_MODE; fft_length 512; the
         decode FIR loaded first.  Kept across CalcFilters() / set_coeffs()."""
         if not on:
             check(self._lib.t41rx_set_cw_detector(self._ctx, 0, None, 0))
@@ -230,6 +230,63 @@ class RxChain:
         if t is None:
             raise ValueError("the CW detector is off")
         return t.view(-1)[:self.n_channels * int(n_frames) * 4].view(self.n_channels, int(n_frames), 4)
+
+    def set_cw_decode_tree(self, tree):
+        """The Morse decoder's bigMorseCodeTree (CWProcessing.cpp:540; t41rx_set_cw_decode_tree): 129 bytes, as bytes,
+        str or uint8 array.  The library has no table of its own.  Kept across CalcFilters() / set_coeffs()."""
+        if isinstance(tree, str):
+            tree = tree.encode("ascii")
+        t = np.ascontiguousarray(np.frombuffer(tree, np.uint8) if isinstance(tree, (bytes, bytearray)) else np.asarray(tree, dtype=np.uint8))
+        check(self._lib.t41rx_set_cw_decode_tree(self._ctx, t.ctypes.data_as(C.c_void_p), int(t.size)))
+
+    def set_cw_decoder(self, on, max_frames=1):
+        """The Morse decoder behind the detector (DoCWDecoding(), CWProcessing.cpp:365-371, :519-815;
+        t41rx_set_cw_decoder).  on = 1 allocates and returns the text tensor, int32 CUDA [n_channels, max_frames, 2]; a
+        process call of n <= max_frames frames fills its first n_channels * n * 2 words as [n_channels][n][character
+        code or 0, ditLength behind the frame] (cw_text(n) is that view).  on = 0 switches it off and returns None.  Runs
+        exactly when the detector runs (xmtMode == CW_MODE, set_cw_detector(1)); fft_length 512; the tree loaded first.
+        Kept across CalcFilters() / set_coeffs()."""
+        if not on:
+            check(self._lib.t41rx_set_cw_decoder(self._ctx, 0, None, 0))
+            self._cw_text = None
+            return None
+        import torch
+        if int(max_frames) < 1:
+            raise ValueError("max_frames must be >= 1")
+        t = torch.zeros(self.n_channels, int(max_frames), 2, dtype=torch.int32, device="cuda:%d" % self.device)
+        check(self._lib.t41rx_set_cw_decoder(self._ctx, int(on), C.c_void_p(t.data_ptr()), int(max_frames)))
+        self._cw_text = t  # keep alive
+        return t
+
+    @property
+    def cw_decoder(self):
+        v = self._lib.t41rx_get_cw_decoder(self._ctx)
+        if v < 0:
+            check(v)
+        return v
+
+    def cw_text(self, n_frames):
+        """the decoder's words of the last process call of n_frames frames: a view [n_channels, n_frames, 2]"""
+        t = getattr(self, "_cw_text", None)
+        if t is None:
+            raise ValueError("the CW decoder is off")
+        return t.view(-1)[:self.n_channels * int(n_frames) * 2].view(self.n_channels, int(n_frames), 2)
+
+    def set_cw_clock(self, t0_ms=0, num=32, den=3):
+        """The decoder's clock (t41rx_set_cw_clock): millis(n) = t0_ms + floor(n * num / den) for the channel's n-th
+        decoder frame; the default is one frame of 2048 samples at 192 kS/s.  From the next call; n is not touched."""
+        check(self._lib.t41rx_set_cw_clock(self._ctx, int(t0_ms), int(num), int(den)))
+
+    def reset_cw_histograms(self, channels=None):
+        """ResetHistograms() (CWProcessing.cpp:501-517), what the firmware runs at every retune, on the channels whose
+        entry is non-zero (None: all): both histograms' words 0 .. 749 and the scalars it names, nothing else."""
+        if channels is None:
+            check(self._lib.t41rx_reset_cw_histograms(self._ctx, None, 0))
+            return
+        m = np.ascontiguousarray(np.asarray(channels).astype(bool).astype(np.uint8))
+        if m.shape != (self.n_channels,):
+            raise ValueError("channels must have n_channels = %d entries, got %r" % (self.n_channels, m.shape))
+        check(self._lib.t41rx_reset_cw_histograms(self._ctx, m.ctypes.data_as(C.c_void_p), self.n_channels))
 
     def get_state(self):
         n = self._lib.t41rx_state_bytes(self._ctx)
