@@ -422,6 +422,69 @@ T41RX_API int t41rx_set_audio_spectrum(t41rx_ctx *ctx, float *d_spect, float *d_
  * fft_length 512; f32 and q15 entry points; max_frames as for the stage taps. */
 T41RX_API int t41rx_set_display_spectrum(t41rx_ctx *ctx, float *d_spec, float *d_spec_old, int spectrumZoom, int max_frames);
 
+/* ---- IQ calibration: ProcessIQData2() and the sideband measurement (Process2.cpp:295-399, 478-547) ----
+ * DoReceiveCalibrate() / DoXmitCalibrate() loop over ShowSpectrum2(), whose PlotCalSpectrum() runs ProcessIQData2() and
+ * turns two windows of pixelnew[] into adjdB, the level of the unwanted sideband against the wanted one; the operator
+ * turns an encoder until it is smallest.  Here the batch axis replaces the operator: every channel of a context tries its
+ * own (IQAmpCorrectionFactor, IQPhaseCorrectionFactor) candidate, if need be on the same recording.  The transmit half
+ * (the tone through the TX correction and the exciter's interpolators) is t41tx_process_cal_*_q15 in t41tx.h; this is the
+ * receive half.  Per frame, in the firmware's order:
+ *   updateDisplayFlag, one byte per frame for all channels (PlotCalSpectrum() sets it on the first call of a sweep only):
+ *     a frame with flag 0 reads no samples and advances no memory (Process2.cpp:387-395, FFT.cpp:209); with flag 1:
+ *   q15 -> float with the queues swapped (:359-360), or f32; x 10^(rfGainAllBands/20); x recBandFactor (1.0);
+ *   in USB and LSB I x -IQAmpCorrectionFactor, then IQPhaseCorrection() (:376-384) -- no DC high-pass; FreqShift1();
+ *   spectrumZoom 0: CalcZoom1Magn() on the first 512 samples AFTER the shift (the audio path calls it before);
+ *   spectrumZoom 1..4: ZoomFFTExe() on the shifted 2048 samples;
+ *   pixelnew[x] = baseOffset + pixel_offset + (int16_t)(dBScale * log10f_fast(v)), v = FFT_spec[x] un-smoothed at zoom 0
+ *     (FFT.cpp:245) and smoothed at zoom >= 1 (:157); {dBScale, baseOffset} = displayScale[currentScale] (Display.cpp:127-135);
+ * and in every frame, flag 0 included, from the channel's current pixelnew[]: arm_max_q15 over [bin0 - capture_bins,
+ * bin0 + capture_bins) and [bin1 - capture_bins, bin1 + capture_bins); LSB: refAmplitude = window 0, adjAmplitude =
+ * window 1, USB the other way round, any other mode both 0; adjdB = ((float)adj - (float)ref) / 1.95 (:498-505, 524).
+ * The calibration memory -- FFT_spec_old[512], the zoom filters' memories, the ring and its pointer, pixelnew[512] per
+ * channel -- is the context's own: allocated when calibration is first configured, set to power-on values (all zero) by
+ * t41rx_set_calibration() and t41rx_reset(), and NOT part of the checkpoint: t41rx_state_bytes() and the section mask are
+ * unchanged.  The calibration calls read and write nothing of the audio path's state, and the other way round.
+ * t41rx_set_calibration(): on = 0 switches it off (the other arguments are ignored).  T41RX_ERR_ARG for spectrumZoom or
+ *   currentScale outside 0..4, a pixel_offset that does not fit an int16, capture_bins < 1, or a window that leaves
+ *   [2, 512] (ShowSpectrum2() zeroes pixelnew[0..1] every sweep: windows off those two bins sidestep that);
+ *   T41RX_ERR_UNSUPPORTED at a long fft_length or on a time-major context.  The firmware's settings are below; it
+ *   calibrates at currentScale 1 (20.0, 10), capture_bins 10, spectrumZoom 0 for receive and 2 for transmit calibration.
+ * t41rx_set_cal_corrections(): one candidate per channel, host arrays of n_channels floats, copied (synchronises).  Both
+ *   NULL: every channel uses the params' IQAmpCorrectionFactor / IQPhaseCorrectionFactor.  One NULL, or a non-finite
+ *   value: T41RX_ERR_ARG.  They apply to the calibration calls only.
+ * t41rx_calibrate_device(): n_frames frames on every channel.  dI / dQ: [n_channels][n_frames * 2048] f32, or with
+ *   shared_input != 0 one channel's [n_frames * 2048] that every channel reads (the sweep's shape: thousands of
+ *   candidates, one recording).  d_update: [n_frames] bytes, NULL = every frame 1.  d_result: [n_channels][n_frames][3] =
+ *   refAmplitude, adjAmplitude, adjdB, written for every frame.  d_pixel [n_channels][n_frames][512] int16 and d_spec
+ *   [n_channels][n_frames][512] f32 (pixelnew and FFT_spec) may be NULL; their rows are written for update frames only,
+ *   other rows are left alone.  Enqueued on hip_stream, no sync.  T41RX_ERR_ARG before t41rx_set_calibration(on), for
+ *   n_frames <= 0, and for NULL input or a NULL d_result.  The _q15 form takes the two queues' int16 samples; the _host
+ *   forms copy in (d_pixel / d_spec too), run the same kernel, copy out and synchronise. */
+#define T41RX_CAL_RX_LSB_BIN0 310 /* cal_bins[], Process2.cpp:429-444 */
+#define T41RX_CAL_RX_LSB_BIN1 460
+#define T41RX_CAL_RX_USB_BIN0 65
+#define T41RX_CAL_RX_USB_BIN1 192
+#define T41RX_CAL_TX_LSB_BIN0 240
+#define T41RX_CAL_TX_LSB_BIN1 305
+#define T41RX_CAL_TX_USB_BIN0 209
+#define T41RX_CAL_TX_USB_BIN1 273
+#define T41RX_CAL_CAPTURE_BINS 10 /* :415 */
+#define T41RX_CAL_RX_ZOOM 0
+#define T41RX_CAL_TX_ZOOM 2
+#define T41RX_CAL_SCALE 1
+T41RX_API int t41rx_set_calibration(t41rx_ctx *ctx, int on, int spectrumZoom, int currentScale, int pixel_offset, int bin0,
+                          int bin1, int capture_bins);
+T41RX_API int t41rx_set_cal_corrections(t41rx_ctx *ctx, const float *amp, const float *phase);
+T41RX_API int t41rx_calibrate_device(t41rx_ctx *ctx, const float *dI, const float *dQ, int shared_input, const uint8_t *d_update,
+                           float *d_result, int16_t *d_pixel, float *d_spec, int n_frames, void *hip_stream);
+T41RX_API int t41rx_calibrate_device_q15(t41rx_ctx *ctx, const int16_t *dQ_in_L, const int16_t *dQ_in_R, int shared_input,
+                               const uint8_t *d_update, float *d_result, int16_t *d_pixel, float *d_spec, int n_frames,
+                               void *hip_stream);
+T41RX_API int t41rx_calibrate_host(t41rx_ctx *ctx, const float *I, const float *Q, int shared_input, const uint8_t *update,
+                         float *result, int16_t *pixel, float *spec, int n_frames);
+T41RX_API int t41rx_calibrate_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, const int16_t *Q_in_R, int shared_input,
+                             const uint8_t *update, float *result, int16_t *pixel, float *spec, int n_frames);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,9 @@
  * The CW exciter, void CW_ExciterIQData(); (CW_Excite.cpp:66-118), is the second entry of the same context
  * (t41tx_set_cw_tone, t41tx_process_cw_*_q15 below): a stored tone, the TX IQ correction with CW's signs, and the
  * same two interpolators per channel.  Not restated: the data exciter.
+ * The transmit half of the IQ calibration, ProcessIQData2() (Process2.cpp:309-349), is the third entry
+ * (t41tx_set_cal_tone, t41tx_set_cal_corrections, t41tx_process_cal_*_q15 below); its receive half and the sideband
+ * measurement are t41rx_calibrate_* in t41rx.h.
  */
 #ifndef T41TX_H
 #define T41TX_H
@@ -124,6 +127,31 @@ T41RX_API int t41tx_process_cw_device_q15(t41tx_ctx *ctx, const uint8_t *d_key, 
  * copies out, synchronises */
 T41RX_API int t41tx_process_cw_host_q15(t41tx_ctx *ctx, const uint8_t *key, int16_t *Q_out_L_Ex, int16_t *Q_out_R_Ex,
                               int n_frames);
+
+/* IQ calibration, transmit half: what ProcessIQData2() plays (Process2.cpp:309-349).  Per frame: cosBuffer3 / sinBuffer3
+ * (256 samples @24 kS/s, 3000 Hz, Utility.cpp:78-80) times level into I / Q; in LSB I times -IQXAmpCorrectionFactor, in USB
+ * times +IQXAmpCorrectionFactor (ProcessIQData2()'s signs, :317-325: the CW exciter's, not ExciterIQData()'s), then
+ * IQPhaseCorrection(), in any other mode no correction; x2 (48 taps) and x4 (32 taps) per channel; arm_float_to_q15
+ * straight from the interpolators (:344-345): no x 20 and no key.  The interpolators are the SSB exciter's own instances
+ * FIR_int1_EX_I / Q and FIR_int2_EX_I / Q: a calibration call continues from the memories the last SSB, CW or calibration
+ * call left, t41tx_reset() and the checkpoint cover them, the record size is unchanged, and no other memory is touched.
+ * t41tx_set_cal_tone(): cosBuffer3 and sinBuffer3, 256 floats each, and level = the firmware's bandOutputFactor
+ *   (Process2.cpp:309; the caller computes it, CWPowerCalibrationFactor[] stays with the caller).  The library has no
+ *   table of its own: one must be loaded before a calibration call.  T41RX_ERR_ARG for NULL or a non-finite value.
+ *   Configuration: kept across t41tx_set_params() and t41tx_reset(), not part of a checkpoint.
+ * t41tx_set_cal_corrections(): one (amplitude, phase) candidate per channel, host arrays of n_channels floats, copied
+ *   (synchronises).  Both NULL: every channel uses the params' IQXAmpCorrectionFactor / IQXPhaseCorrectionFactor, the
+ *   state of a new context.  One NULL, or a non-finite value: T41RX_ERR_ARG, and the candidates stay as they were.
+ *   They apply to the calibration calls only.  Configuration, like the tone.
+ * t41tx_process_cal_device_q15(): n_frames consecutive frames on every channel.  Device pointers; the outputs are
+ *   [n_channels][n_frames * 2048] int16 each, 16-byte aligned.  Enqueued on hip_stream, no sync.  T41RX_ERR_ARG before
+ *   a tone table is loaded, for n_frames <= 0 and for NULL or misaligned outputs. */
+T41RX_API int t41tx_set_cal_tone(t41tx_ctx *ctx, const float *cosBuffer3, const float *sinBuffer3, float level);
+T41RX_API int t41tx_set_cal_corrections(t41tx_ctx *ctx, const float *amp, const float *phase);
+T41RX_API int t41tx_process_cal_device_q15(t41tx_ctx *ctx, int16_t *dQ_out_L_Ex, int16_t *dQ_out_R_Ex, int n_frames,
+                                 void *hip_stream);
+/* host-pointer form: runs the same kernel into the staging buffers of t41tx_process_host_q15, copies out, synchronises */
+T41RX_API int t41tx_process_cal_host_q15(t41tx_ctx *ctx, int16_t *Q_out_L_Ex, int16_t *Q_out_R_Ex, int n_frames);
 
 #ifdef __cplusplus
 }

@@ -92,6 +92,12 @@ SYMBOLS = {
     "t41rx_get_cw_decoder": (C.c_int, [_vp]),
     "t41rx_set_cw_clock": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32]),
     "t41rx_reset_cw_histograms": (C.c_int, [_vp, _vp, C.c_int]),
+    "t41rx_set_calibration": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "t41rx_set_cal_corrections": (C.c_int, [_vp, _vp, _vp]),
+    "t41rx_calibrate_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "t41rx_calibrate_device_q15": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "t41rx_calibrate_host": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int]),
+    "t41rx_calibrate_host_q15": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int]),
 }
 
 _lib = None

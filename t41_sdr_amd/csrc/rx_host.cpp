@@ -115,6 +115,14 @@ struct t41rx_ctx {
   int cw_text_frames = 0;      // frames per call cw_text is sized for
   int32_t cw_t0 = 0, cw_num = 32, cw_den = 3;  // 2048 samples at 192 kS/s
   DevBuf<int32_t> d_cwdec;
+  // IQ calibration (ProcessIQData2() / PlotCalSpectrum(), Process2.cpp:352-397, 478-547; t41rx_set_calibration): its
+  // settings, a correction candidate per channel, and the calibration memory [nchan][kCalFloats] (cal_kernel.hip),
+  // allocated when calibration is first configured.  The context's own: no checkpoint section, no audio-path kernel
+  // touches it.
+  bool cal_on = false, cal_per_channel = false;
+  int cal_zoom = 0, cal_base = 0, cal_lo0 = 0, cal_lo1 = 0, cal_width = 0;
+  float cal_dbscale = 0.0f;
+  DevBuf<float> d_cal, d_cal_corr;
   // staging for t41rx_process_host
   DevBuf<float> d_in_i, d_in_q, d_out;
   size_t staging_floats = 0;
@@ -888,6 +896,110 @@ int process_device_impl(t41rx_ctx *ctx, const float *dI, const float *dQ, float 
   return launch_chain(ctx, rx_args(ctx, dI, dQ, dAudio, n_frames, q15), n_frames, s);
 }
 
+// the display FFT's window, 0.5 - 0.5 cos(6.28 i / 512) as the reference's double expression, once per context
+int ensure_window(t41rx_ctx *ctx) {
+  if (ctx->d_win) return T41RX_OK;
+  DevBuf<double> win;
+  double w[512];
+  for (int i = 0; i < 512; ++i) w[i] = 0.5 - 0.5 * std::cos(6.28 * i / 512);  // FFT.cpp:110, 222 ("Hanning", 6.28 as written)
+  HIP_TRY(dev_alloc(win, sizeof(w)));
+  HIP_TRY(hipMemcpy(win.get(), w, sizeof(w), hipMemcpyHostToDevice));
+  ctx->d_win = std::move(win);
+  return T41RX_OK;
+}
+
+// IQ calibration: what every t41rx_calibrate_* entry checks, then the launch.  I / Q are float_buffer_L's and
+// float_buffer_R's sources (the q15 entries have swapped the queues already)
+int calibrate_impl(t41rx_ctx *ctx, const void *dI, const void *dQ, int shared_input, const uint8_t *d_update, float *d_result,
+                   int16_t *d_pixel, float *d_spec, int n_frames, void *hip_stream, bool q15) {
+  if (!ctx || !dI || !dQ || !d_result) return fail(T41RX_ERR_ARG, "null argument");
+  if (!ctx->cal_on) return fail(T41RX_ERR_ARG, "calibration is not switched on (t41rx_set_calibration)");
+  if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
+  if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the calibration is built for fft_length 512");
+  if (ctx->layout != T41RX_LAYOUT_CHANNEL_MAJOR) return fail(T41RX_ERR_UNSUPPORTED, "the calibration is built for the channel-major layout");
+  if (((reinterpret_cast<uintptr_t>(dI) | reinterpret_cast<uintptr_t>(dQ)) & (q15 ? 1u : 3u)) ||
+      ((reinterpret_cast<uintptr_t>(d_result) | reinterpret_cast<uintptr_t>(d_spec)) & 3u) || (reinterpret_cast<uintptr_t>(d_pixel) & 1u))
+    return fail(T41RX_ERR_ARG, "unaligned pointer");
+  if (!ctx->d_cal || !ctx->d_win) return fail(T41RX_ERR_STATE, "calibration enabled without its buffers");
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  CalArgs a{};
+  a.I = dI;
+  a.Q = dQ;
+  a.update = d_update;
+  a.result = d_result;
+  a.pixel = d_pixel;
+  a.spec = d_spec;
+  a.cal = ctx->d_cal.get();
+  a.tab = ctx->d_tab.get();
+  a.win = ctx->d_win.get();
+  a.corr = ctx->cal_per_channel ? ctx->d_cal_corr.get() : nullptr;
+  a.zoom = ctx->cal_zoom;
+  if (a.zoom > 0) {
+    std::memcpy(a.iir, kZoomIirCoeffs[a.zoom - 1], sizeof(a.iir));
+    design_zoom_fir(a.zoom, a.fir);
+  }
+  a.chan_stride = shared_input ? 0 : (long long)n_frames * 2048;
+  a.nchan = ctx->nchan;
+  a.nframes = n_frames;
+  a.q15 = q15 ? 1 : 0;
+  a.g_rf = blob_view(ctx->blob.data()).scalars[kScRfGain];  // the same expression, Process.cpp:117 / Process2.cpp:365
+  a.rec_band = 1.0f;                                        // recBandFactor[], Process2.cpp:299
+  a.iq_amp = ctx->params.IQAmpCorrectionFactor;
+  a.iq_phase = ctx->params.IQPhaseCorrectionFactor;
+  a.corr_on = (ctx->params.mode == T41RX_DEMOD_LSB || ctx->params.mode == T41RX_DEMOD_USB) ? 1 : 0;
+  a.dBScale = ctx->cal_dbscale;
+  a.base = ctx->cal_base;
+  a.lo0 = ctx->cal_lo0;
+  a.lo1 = ctx->cal_lo1;
+  a.width = ctx->cal_width;
+  a.sideband = ctx->params.mode == T41RX_DEMOD_LSB ? 1 : ctx->params.mode == T41RX_DEMOD_USB ? 2 : 0;
+  const hipError_t e = launch_cal(a, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return hip_fail(e, "calibration kernel launch");
+  return T41RX_OK;
+}
+
+// host-pointer form: temporaries of its own (the audio path's staging buffers are not touched); the rows of d_pixel /
+// d_spec a call leaves alone keep the caller's contents, so those two travel both ways
+int calibrate_host_impl(t41rx_ctx *ctx, const void *I, const void *Q, int shared_input, const uint8_t *update, float *result,
+                        int16_t *pixel, float *spec, int n_frames, bool q15) {
+  if (!ctx || !I || !Q || !result) return fail(T41RX_ERR_ARG, "null argument");
+  if (!ctx->cal_on) return fail(T41RX_ERR_ARG, "calibration is not switched on (t41rx_set_calibration)");
+  if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  const size_t rows = (size_t)ctx->nchan * (size_t)n_frames;
+  const size_t in_bytes = (shared_input ? (size_t)n_frames : rows) * 2048 * (q15 ? sizeof(int16_t) : sizeof(float));
+  DevBuf<char> dI, dQ, dU;
+  DevBuf<float> dR, dS;
+  DevBuf<int16_t> dP;
+  HIP_TRY(dev_alloc(dI, in_bytes));
+  HIP_TRY(dev_alloc(dQ, in_bytes));
+  HIP_TRY(dev_alloc(dR, rows * 3 * sizeof(float)));
+  HIP_TRY(hipMemcpy(dI.get(), I, in_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dQ.get(), Q, in_bytes, hipMemcpyHostToDevice));
+  if (update) {
+    HIP_TRY(dev_alloc(dU, (size_t)n_frames));
+    HIP_TRY(hipMemcpy(dU.get(), update, (size_t)n_frames, hipMemcpyHostToDevice));
+  }
+  if (pixel) {
+    HIP_TRY(dev_alloc(dP, rows * 512 * sizeof(int16_t)));
+    HIP_TRY(hipMemcpy(dP.get(), pixel, rows * 512 * sizeof(int16_t), hipMemcpyHostToDevice));
+  }
+  if (spec) {
+    HIP_TRY(dev_alloc(dS, rows * 512 * sizeof(float)));
+    HIP_TRY(hipMemcpy(dS.get(), spec, rows * 512 * sizeof(float), hipMemcpyHostToDevice));
+  }
+  const int rc = calibrate_impl(ctx, dI.get(), dQ.get(), shared_input, reinterpret_cast<const uint8_t *>(dU.get()), dR.get(), dP.get(),
+                                dS.get(), n_frames, nullptr, q15);
+  if (rc != T41RX_OK) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(result, dR.get(), rows * 3 * sizeof(float), hipMemcpyDeviceToHost));
+  if (pixel) HIP_TRY(hipMemcpy(pixel, dP.get(), rows * 512 * sizeof(int16_t), hipMemcpyDeviceToHost));
+  if (spec) HIP_TRY(hipMemcpy(spec, dS.get(), rows * 512 * sizeof(float), hipMemcpyDeviceToHost));
+  return T41RX_OK;
+}
+
 // staging buffers of the host-pointer entry points, sized in bytes per array
 int ensure_staging(t41rx_ctx *ctx, size_t bytes) {
   if (bytes <= ctx->staging_floats * sizeof(float)) return T41RX_OK;
@@ -1116,6 +1228,8 @@ int t41rx_reset(t41rx_ctx *ctx) {
     const int rc = pipe_timeouts_clear(ctx);
     if (rc != T41RX_OK) return rc;
   }
+  // the calibration memory to power-on: FFT_spec_old, zoom memories, ring, pointer and pixelnew[] all zero
+  if (ctx->d_cal) HIP_TRY(hipMemset(ctx->d_cal.get(), 0, sizeof(float) * kCalFloats * (size_t)ctx->nchan));
   return reset_state(ctx);
 }
 
@@ -1439,14 +1553,7 @@ int t41rx_set_display_spectrum(t41rx_ctx *ctx, float *d_spec, float *d_spec_old,
   if (max_frames > had_frames || !ctx->d_pre)
     HIP_TRY(dev_alloc(ctx->d_pre, sizeof(float) * 4096 * (size_t)max_frames * (size_t)ctx->nchan));
   if (!ctx->d_disp) HIP_TRY(dev_alloc(ctx->d_disp, sizeof(float) * kDispFloats * (size_t)ctx->nchan));
-  if (!ctx->d_win) {
-    DevBuf<double> win;
-    double w[512];
-    for (int i = 0; i < 512; ++i) w[i] = 0.5 - 0.5 * std::cos(6.28 * i / 512);  // FFT.cpp:110, 222 ("Hanning", 6.28 as written)
-    HIP_TRY(dev_alloc(win, sizeof(w)));
-    HIP_TRY(hipMemcpy(win.get(), w, sizeof(w), hipMemcpyHostToDevice));
-    ctx->d_win = std::move(win);
-  }
+  if (const int rc = ensure_window(ctx)) return rc;
   HIP_TRY(hipMemset(ctx->d_disp.get(), 0, sizeof(float) * kDispFloats * (size_t)ctx->nchan));  // ZoomFFTPrep(): a fresh start
   if (max_frames < had_frames) max_frames = had_frames;  // (the tap buffer was kept: it still holds that many)
   ctx->disp_spec = d_spec;
@@ -1454,6 +1561,85 @@ int t41rx_set_display_spectrum(t41rx_ctx *ctx, float *d_spec, float *d_spec_old,
   ctx->disp_frames = max_frames;
   ctx->disp_zoom = spectrumZoom;
   return T41RX_OK;
+}
+
+int t41rx_set_calibration(t41rx_ctx *ctx, int on, int spectrumZoom, int currentScale, int pixel_offset, int bin0, int bin1,
+                          int capture_bins) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  DeviceGuard g(ctx->device);
+  HIP_TRY(hipDeviceSynchronize());
+  if (!on) {
+    ctx->cal_on = false;
+    return T41RX_OK;
+  }
+  if (spectrumZoom < 0 || spectrumZoom > 4) return fail(T41RX_ERR_ARG, "spectrumZoom must be 0 (1x) .. 4 (16x)");
+  if (currentScale < 0 || currentScale > 4) return fail(T41RX_ERR_ARG, "currentScale must be 0 .. 4");
+  if (pixel_offset < -32768 || pixel_offset > 32767) return fail(T41RX_ERR_ARG, "pixel_offset must fit an int16");
+  if (capture_bins < 1) return fail(T41RX_ERR_ARG, "capture_bins must be >= 1");
+  for (const int b : {bin0, bin1})
+    if ((long long)b - capture_bins < 2 || (long long)b + capture_bins > 512)
+      return fail(T41RX_ERR_ARG, "a window [bin - capture_bins, bin + capture_bins) must lie within [2, 512]");
+  if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the calibration is built for fft_length 512");
+  if (ctx->layout != T41RX_LAYOUT_CHANNEL_MAJOR) return fail(T41RX_ERR_UNSUPPORTED, "the calibration is built for the channel-major layout");
+  // anything that fails from here on leaves calibration switched off
+  ctx->cal_on = false;
+  if (!ctx->d_cal) HIP_TRY(dev_alloc(ctx->d_cal, sizeof(float) * kCalFloats * (size_t)ctx->nchan));
+  if (const int rc = ensure_window(ctx)) return rc;
+  HIP_TRY(hipMemset(ctx->d_cal.get(), 0, sizeof(float) * kCalFloats * (size_t)ctx->nchan));  // power-on: ZoomFFTPrep(), pixelnew[] = 0
+  // displayScale[] (Display.cpp:127-135): dBScale, baseOffset
+  static const float kDbScale[5] = {10.0f, 20.0f, 40.0f, 100.0f, 200.0f};
+  static const int kBaseOffset[5] = {24, 10, 58, 120, 200};
+  ctx->cal_zoom = spectrumZoom;
+  ctx->cal_dbscale = kDbScale[currentScale];
+  ctx->cal_base = kBaseOffset[currentScale] + pixel_offset;
+  ctx->cal_lo0 = bin0 - capture_bins;
+  ctx->cal_lo1 = bin1 - capture_bins;
+  ctx->cal_width = 2 * capture_bins;
+  ctx->cal_on = true;
+  return T41RX_OK;
+}
+
+int t41rx_set_cal_corrections(t41rx_ctx *ctx, const float *amp, const float *phase) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (!amp && !phase) {  // back to the params' factors
+    ctx->cal_per_channel = false;
+    return T41RX_OK;
+  }
+  if (!amp || !phase) return fail(T41RX_ERR_ARG, "calibration corrections: amp and phase must both be given or both be NULL");
+  std::vector<float> h(2 * (size_t)ctx->nchan);
+  for (int c = 0; c < ctx->nchan; ++c) {
+    if (!std::isfinite(amp[c]) || !std::isfinite(phase[c])) return fail(T41RX_ERR_ARG, "calibration corrections: non-finite value");
+    h[2 * (size_t)c] = amp[c];
+    h[2 * (size_t)c + 1] = phase[c];
+  }
+  DeviceGuard g(ctx->device);
+  HIP_TRY(hipDeviceSynchronize());  // (a launch still in flight reads the old candidates)
+  if (!ctx->d_cal_corr) HIP_TRY(dev_alloc(ctx->d_cal_corr, sizeof(float) * h.size()));
+  HIP_TRY(hipMemcpy(ctx->d_cal_corr.get(), h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
+  ctx->cal_per_channel = true;
+  return T41RX_OK;
+}
+
+int t41rx_calibrate_device(t41rx_ctx *ctx, const float *dI, const float *dQ, int shared_input, const uint8_t *d_update,
+                           float *d_result, int16_t *d_pixel, float *d_spec, int n_frames, void *hip_stream) {
+  return calibrate_impl(ctx, dI, dQ, shared_input, d_update, d_result, d_pixel, d_spec, n_frames, hip_stream, false);
+}
+
+// float_buffer_L (= I) is filled from the R queue and float_buffer_R (= Q) from the L queue (Process2.cpp:359-360)
+int t41rx_calibrate_device_q15(t41rx_ctx *ctx, const int16_t *dQ_in_L, const int16_t *dQ_in_R, int shared_input,
+                               const uint8_t *d_update, float *d_result, int16_t *d_pixel, float *d_spec, int n_frames,
+                               void *hip_stream) {
+  return calibrate_impl(ctx, dQ_in_R, dQ_in_L, shared_input, d_update, d_result, d_pixel, d_spec, n_frames, hip_stream, true);
+}
+
+int t41rx_calibrate_host(t41rx_ctx *ctx, const float *I, const float *Q, int shared_input, const uint8_t *update, float *result,
+                         int16_t *pixel, float *spec, int n_frames) {
+  return calibrate_host_impl(ctx, I, Q, shared_input, update, result, pixel, spec, n_frames, false);
+}
+
+int t41rx_calibrate_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, const int16_t *Q_in_R, int shared_input, const uint8_t *update,
+                             float *result, int16_t *pixel, float *spec, int n_frames) {
+  return calibrate_host_impl(ctx, Q_in_R, Q_in_L, shared_input, update, result, pixel, spec, n_frames, true);
 }
 
 }  // extern "C"

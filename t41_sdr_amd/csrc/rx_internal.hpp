@@ -85,6 +85,11 @@ constexpr int kDispPtr = 40;      // zoom_sample_ptr (int32)
 constexpr int kDispRing = 64;     // [2][512]: FFT_ring_buffer_x / _y
 constexpr int kDispOld = 64 + 1024;  // [512]: FFT_spec_old
 constexpr int kDispFloats = kDispOld + 512;
+// per-channel calibration memory (t41rx_set_calibration; cal_kernel.hip): the display state's layout -- ProcessIQData2()
+// runs the display FFT on its own samples -- and behind it pixelnew[512] as int16.  The context's own: not part of a
+// checkpoint, and no audio-path kernel reads or writes it.
+constexpr int kCalPixel = kDispFloats;  // [512] int16
+constexpr int kCalFloats = kCalPixel + 256;
 
 // host designer (design.cpp)
 int design_blob(const t41rx_params &p, void *blob, size_t blob_bytes);

@@ -102,4 +102,31 @@ struct DispArgs {
 };
 hipError_t launch_display(const DispArgs &a, hipStream_t s);
 
+// IQ calibration, receive half and measurement (ProcessIQData2() / PlotCalSpectrum(), Process2.cpp:352-397, 478-547)
+struct CalArgs {
+  const void *I;           // float_buffer_L's source: f32, or the R queue's q15 samples (Process2.cpp:359)
+  const void *Q;           // float_buffer_R's: f32, or the L queue's
+  const uint8_t *update;   // [nframes] updateDisplayFlag per frame, shared by all channels; null = every frame 1
+  float *result;           // [nchan][nframes][3]: refAmplitude, adjAmplitude, adjdB
+  int16_t *pixel;          // [nchan][nframes][512] pixelnew, rows of update frames only (or null)
+  float *spec;             // [nchan][nframes][512] FFT_spec, rows of update frames only (or null)
+  float *cal;              // [nchan][kCalFloats] calibration memory
+  const float2 *tab;       // the context's constant table (FFT twiddles)
+  const double *win;       // [512]: 0.5 - 0.5 cos(6.28 i / 512)
+  const float *corr;       // [nchan][2] = IQAmp, IQPhase per channel; null = iq_amp / iq_phase for all
+  float iir[20];           // mag_coeffs[spectrumZoom] (unused for zoom 0)
+  float fir[4];            // Fir_Zoom_FFT_Decimate_coeffs
+  long long chan_stride;   // samples between two channels' input; 0 = every channel reads the same recording
+  int nchan, nframes, zoom, q15;
+  float g_rf;              // (float)pow(10, rfGainAllBands / 20), Process2.cpp:365
+  float rec_band;          // recBandFactor[currentBand] = 1.0, :372-373
+  float iq_amp, iq_phase;  // IQAmpCorrectionFactor (I is scaled by its negative, :377, 381), IQPhaseCorrectionFactor
+  int corr_on;             // LSB or USB
+  float dBScale;           // displayScale[currentScale].dBScale
+  int base;                // displayScale[currentScale].baseOffset + pixel_offset
+  int lo0, lo1, width;     // the windows [bin0 - capture, bin0 + capture), [bin1 - capture, bin1 + capture)
+  int sideband;            // 1 LSB (ref = window 0), 2 USB (ref = window 1), 0 any other mode (no measurement)
+};
+hipError_t launch_cal(const CalArgs &a, hipStream_t s);
+
 }  // namespace t41

@@ -12,6 +12,7 @@
 #include "last_error.hpp"  // fail(): failures reach t41rx_last_error(), like the receive path's
 #include "tx_internal.hpp"
 #include "tx_cw_kernel.hip"  // the CW exciter's kernel and launcher
+#include "tx_cal_kernel.hip"  // the calibration exciter's (behind the CW exciter's: it uses that file's helpers)
 
 using namespace t41;
 
@@ -33,6 +34,12 @@ struct t41tx_ctx {
   // Configuration like the equaliser's: kept across t41tx_set_params() and t41tx_reset(), not part of a checkpoint.
   bool cw_have_tone = false;
   float cw_cos[kTxCwTone] = {}, cw_sin[kTxCwTone] = {};
+  // calibration exciter (ProcessIQData2(), Process2.cpp:309-349; t41tx_set_cal_tone, t41tx_set_cal_corrections): the
+  // caller's cosBuffer3 / sinBuffer3 and bandOutputFactor, and a correction candidate per channel.  Configuration too.
+  bool cal_have_tone = false;
+  float cal_cos[kTxCwTone] = {}, cal_sin[kTxCwTone] = {}, cal_level = 0.0f;
+  float *d_cal_corr = nullptr;  // [nchan][2] amplitude, phase; allocated by the first t41tx_set_cal_corrections()
+  bool cal_per_channel = false;
 };
 
 namespace {
@@ -78,6 +85,7 @@ void free_ctx(t41tx_ctx *c) {
   (void)hipFree(c->d_in);
   (void)hipFree(c->d_outL);
   (void)hipFree(c->d_outR);
+  (void)hipFree(c->d_cal_corr);
   delete c;
 }
 }  // namespace
@@ -329,6 +337,87 @@ int t41tx_process_cw_host_q15(t41tx_ctx *ctx, const uint8_t *key, int16_t *oL, i
   if (key && hipMemcpy(ctx->d_in, key, key_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(T41RX_ERR_HIP, "copy in failed");
   const int rc = t41tx_process_cw_device_q15(ctx, key ? reinterpret_cast<const uint8_t *>(ctx->d_in) : nullptr, ctx->d_outL,
                                              ctx->d_outR, n_frames, nullptr);
+  if (rc != T41RX_OK) return rc;
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(oL, ctx->d_outL, bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(oR, ctx->d_outR, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(T41RX_ERR_HIP, "copy out failed");
+  return T41RX_OK;
+}
+
+int t41tx_set_cal_tone(t41tx_ctx *ctx, const float *cosBuffer3, const float *sinBuffer3, float level) {
+  if (!ctx || !cosBuffer3 || !sinBuffer3) return fail(T41RX_ERR_ARG, "null argument");
+  if (!std::isfinite(level)) return fail(T41RX_ERR_ARG, "calibration tone: non-finite level");
+  for (int i = 0; i < kTxCwTone; ++i)
+    if (!std::isfinite(cosBuffer3[i]) || !std::isfinite(sinBuffer3[i])) return fail(T41RX_ERR_ARG, "calibration tone table: non-finite value");
+  std::memcpy(ctx->cal_cos, cosBuffer3, sizeof(ctx->cal_cos));  // (passed by value to every launch: the next call uses it)
+  std::memcpy(ctx->cal_sin, sinBuffer3, sizeof(ctx->cal_sin));
+  ctx->cal_level = level;
+  ctx->cal_have_tone = true;
+  return T41RX_OK;
+}
+
+int t41tx_set_cal_corrections(t41tx_ctx *ctx, const float *amp, const float *phase) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (!amp && !phase) {  // back to the params' factors
+    ctx->cal_per_channel = false;
+    return T41RX_OK;
+  }
+  if (!amp || !phase) return fail(T41RX_ERR_ARG, "calibration corrections: amp and phase must both be given or both be NULL");
+  std::vector<float> h(2 * (size_t)ctx->nchan);
+  for (int c = 0; c < ctx->nchan; ++c) {
+    if (!std::isfinite(amp[c]) || !std::isfinite(phase[c])) return fail(T41RX_ERR_ARG, "calibration corrections: non-finite value");
+    h[2 * (size_t)c] = amp[c];
+    h[2 * (size_t)c + 1] = phase[c];
+  }
+  Guard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  if (!ctx->d_cal_corr && hipMalloc((void **)&ctx->d_cal_corr, sizeof(float) * h.size()) != hipSuccess) {
+    ctx->d_cal_corr = nullptr;
+    return fail(T41RX_ERR_NOMEM, "calibration corrections: device allocation failed");
+  }
+  // (a launch still in flight reads the old candidates: wait for it, as the state copies do)
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(ctx->d_cal_corr, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(T41RX_ERR_HIP, "calibration corrections: copy in failed");
+  ctx->cal_per_channel = true;
+  return T41RX_OK;
+}
+
+int t41tx_process_cal_device_q15(t41tx_ctx *ctx, int16_t *oL, int16_t *oR, int n_frames, void *hip_stream) {
+  if (!ctx || !oL || !oR) return fail(T41RX_ERR_ARG, "null argument");
+  if (!ctx->cal_have_tone) return fail(T41RX_ERR_ARG, "calibration exciter: no tone table loaded (t41tx_set_cal_tone)");
+  if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
+  if ((reinterpret_cast<uintptr_t>(oL) | reinterpret_cast<uintptr_t>(oR)) & 15u)
+    return fail(T41RX_ERR_ARG, "device pointers must be 16-byte aligned");
+  Guard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  TxCalArgs a{};
+  a.outL = oL;
+  a.outR = oR;
+  a.state = ctx->d_state;
+  a.coef = ctx->d_coef;
+  a.corr = ctx->cal_per_channel ? ctx->d_cal_corr : nullptr;
+  a.nchan = ctx->nchan;
+  a.nframes = n_frames;
+  a.level = ctx->cal_level;
+  a.iq_amp = ctx->params.IQXAmpCorrectionFactor;
+  a.iq_phase = ctx->params.IQXPhaseCorrectionFactor;
+  a.corr_on = (ctx->params.mode == T41RX_DEMOD_LSB || ctx->params.mode == T41RX_DEMOD_USB) ? 1 : 0;
+  a.lsb = ctx->params.mode == T41RX_DEMOD_LSB ? 1 : 0;  // Process2.cpp:318, 322: CW's signs, not ExciterIQData()'s
+  std::memcpy(a.tone_cos, ctx->cal_cos, sizeof(a.tone_cos));
+  std::memcpy(a.tone_sin, ctx->cal_sin, sizeof(a.tone_sin));
+  if (launch_tx_cal(a, (hipStream_t)hip_stream) != hipSuccess) return fail(T41RX_ERR_HIP, "kernel launch failed");
+  return T41RX_OK;
+}
+
+int t41tx_process_cal_host_q15(t41tx_ctx *ctx, int16_t *oL, int16_t *oR, int n_frames) {
+  if (!ctx || !oL || !oR) return fail(T41RX_ERR_ARG, "null argument");
+  if (!ctx->cal_have_tone) return fail(T41RX_ERR_ARG, "calibration exciter: no tone table loaded (t41tx_set_cal_tone)");
+  if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
+  Guard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  const size_t bytes = sizeof(int16_t) * 2048 * (size_t)n_frames * (size_t)ctx->nchan;
+  if (const int rc = ensure_staging(ctx, bytes)) return rc;
+  const int rc = t41tx_process_cal_device_q15(ctx, ctx->d_outL, ctx->d_outR, n_frames, nullptr);
   if (rc != T41RX_OK) return rc;
   if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(oL, ctx->d_outL, bytes, hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(oR, ctx->d_outR, bytes, hipMemcpyDeviceToHost) != hipSuccess)

@@ -82,7 +82,26 @@ struct TxCwArgs {
   float tone_sin[kTxCwTone];
 };
 
+// the calibration exciter's arguments (ProcessIQData2(), Process2.cpp:309-349): the CW exciter's shape on the same
+// memories, with cosBuffer3 / sinBuffer3, the caller's level and a correction candidate per channel
+struct TxCalArgs {
+  int16_t *__restrict__ outL;
+  int16_t *__restrict__ outR;
+  float *__restrict__ state;        // [nchan][kTxDelayFloats]
+  const TxCoef *__restrict__ coef;
+  const float *__restrict__ corr;   // [nchan][2] = IQXAmp, IQXPhase per channel; nullptr = iq_amp / iq_phase for all
+  int nchan, nframes;
+  float level;     // bandOutputFactor, Process2.cpp:309
+  float iq_amp;    // IQXAmpCorrectionFactor: LSB scales I by its negative, USB by it (Process2.cpp:317-325)
+  float iq_phase;  // IQXPhaseCorrectionFactor
+  int corr_on;     // LSB or USB
+  int lsb;
+  float tone_cos[kTxCwTone];
+  float tone_sin[kTxCwTone];
+};
+
 hipError_t launch_tx(const TxArgs &a, hipStream_t s);       // xmitEQFlag off
+hipError_t launch_tx_cal(const TxCalArgs &a, hipStream_t s);  // ProcessIQData2(), transmit half
 hipError_t launch_tx_eq(const TxEqArgs &a, hipStream_t s);  // xmitEQFlag on
 hipError_t launch_tx_cw(const TxCwArgs &a, hipStream_t s);  // CW_ExciterIQData()
 

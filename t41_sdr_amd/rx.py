@@ -403,6 +403,99 @@ class RxChain:
         check(self._lib.t41rx_set_display_spectrum(self._ctx, ps, po, int(spectrumZoom), min(frames) if frames else 0))
         self._disp = (spec, spec_old)  # keep alive
 
+    # -- IQ calibration ----------------------------------------------------------------------
+    CAL_BINS = {("rx", DEMOD_LSB): (310, 460), ("rx", DEMOD_USB): (65, 192),   # cal_bins[], Process2.cpp:429-444
+                ("tx", DEMOD_LSB): (240, 305), ("tx", DEMOD_USB): (209, 273)}
+
+    def set_calibration(self, on=True, spectrumZoom=0, currentScale=1, pixel_offset=0, bin0=310, bin1=460, capture_bins=10):
+        """ProcessIQData2() / PlotCalSpectrum() (t41rx_set_calibration): the display FFT's zoom, displayScale[currentScale],
+        bands[].pixel_offset and the two windows [bin - capture_bins, bin + capture_bins).  Starts the calibration memory
+        from power-on.  fft_length 512, channel-major."""
+        check(self._lib.t41rx_set_calibration(self._ctx, int(bool(on)), int(spectrumZoom), int(currentScale), int(pixel_offset),
+                                              int(bin0), int(bin1), int(capture_bins)))
+
+    def set_cal_corrections(self, amp=None, phase=None):
+        """one (IQAmpCorrectionFactor, IQPhaseCorrectionFactor) candidate per channel for the calibration calls
+        (t41rx_set_cal_corrections): two arrays of n_channels floats, or None, None for the params' factors"""
+        if amp is None and phase is None:
+            check(self._lib.t41rx_set_cal_corrections(self._ctx, None, None))
+            return
+        if amp is None or phase is None:
+            raise ValueError("amp and phase must both be given or both be None")
+        a = np.ascontiguousarray(np.asarray(amp, dtype=np.float32))
+        p = np.ascontiguousarray(np.asarray(phase, dtype=np.float32))
+        if a.shape != (self.n_channels,) or p.shape != (self.n_channels,):
+            raise ValueError("corrections must be %d floats each, got %r and %r" % (self.n_channels, a.shape, p.shape))
+        check(self._lib.t41rx_set_cal_corrections(self._ctx, a.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p)))
+
+    def ProcessIQData2_rx(self, I, Q, update=None, shared_input=False, pixel=False, spec=False):
+        """The receive half of ProcessIQData2() with PlotCalSpectrum()'s measurement, n_frames frames per channel.
+        I / Q: float32 (float_buffer_L / _R) or int16 (the queues Q_in_L / Q_in_R: I is taken from the R queue),
+        [n_channels, n_frames * 2048], or with shared_input one recording [n_frames * 2048] (or [1, ...]) for all channels.
+        update: n_frames bytes, updateDisplayFlag per frame, None = every frame.  pixel / spec: True for a fresh zeroed
+        buffer, or a buffer [n_channels, n_frames, 512] (int16 / float32) whose rows of frames without the flag are left
+        alone.  numpy arrays use the host entries, torch CUDA tensors the device entries on the current stream.
+        Returns (result [n_channels, n_frames, 3] = refAmplitude, adjAmplitude, adjdB, pixel or None, spec or None)."""
+        host = isinstance(I, np.ndarray)
+        if host:
+            q15 = I.dtype == np.int16
+            I = np.ascontiguousarray(I, dtype=np.int16 if q15 else np.float32)
+            Q = np.ascontiguousarray(Q, dtype=I.dtype)
+        else:
+            import torch
+            q15 = I.dtype == torch.int16
+            if not (I.is_cuda and Q.is_cuda and I.dtype == Q.dtype and I.dtype in (torch.int16, torch.float32)
+                    and I.is_contiguous() and Q.is_contiguous() and I.device.index == self.device and Q.device.index == self.device):
+                raise ValueError("I/Q must be contiguous float32 or int16 CUDA tensors on device %d" % self.device)
+        si, sq = tuple(I.shape), tuple(Q.shape)
+        rows = 1 if shared_input else self.n_channels
+        if len(si) == 1 and shared_input:
+            si = (1,) + si
+        if tuple(Q.shape) != tuple(I.shape) or len(si) != 2 or si[0] != rows or si[1] == 0 or si[1] % 2048:
+            raise ValueError("I/Q must be [%d, k*2048], got %r / %r" % (rows, tuple(I.shape), sq))
+        nfr = si[1] // 2048
+        shape = (self.n_channels, nfr)
+
+        def side(buf, dtype_np, what):
+            if buf is False or buf is None:
+                return None
+            if buf is True:
+                if host:
+                    return np.zeros(shape + (512,), dtype_np)
+                return torch.zeros(shape + (512,), dtype=torch.int16 if dtype_np == np.int16 else torch.float32, device=I.device)
+            ok = tuple(buf.shape) == shape + (512,) and (
+                (isinstance(buf, np.ndarray) and buf.dtype == dtype_np and buf.flags["C_CONTIGUOUS"] and buf.flags["WRITEABLE"]) if host
+                else (buf.is_cuda and buf.is_contiguous() and buf.device == I.device
+                      and buf.dtype == (torch.int16 if dtype_np == np.int16 else torch.float32)))
+            if not ok:
+                raise ValueError("%s must be a contiguous %s buffer of shape %r next to I/Q" % (what, np.dtype(dtype_np).name, shape + (512,)))
+            return buf
+
+        pixel, spec = side(pixel, np.int16, "pixel"), side(spec, np.float32, "spec")
+        if host:
+            u = None
+            if update is not None:
+                u = np.ascontiguousarray(np.asarray(update) != 0, dtype=np.uint8)
+                if u.shape != (nfr,):
+                    raise ValueError("update must hold n_frames=%d flags, got %r" % (nfr, u.shape))
+            res = np.zeros(shape + (3,), np.float32)
+            p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
+            fn = self._lib.t41rx_calibrate_host_q15 if q15 else self._lib.t41rx_calibrate_host
+            check(fn(self._ctx, p(I), p(Q), int(bool(shared_input)), p(u), p(res), p(pixel), p(spec), nfr))
+            return res, pixel, spec
+        u = None
+        if update is not None:
+            u = update if isinstance(update, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(update) != 0, dtype=np.uint8)).to(I.device)
+            if not (u.is_cuda and u.dtype == torch.uint8 and u.is_contiguous() and tuple(u.shape) == (nfr,)):
+                raise ValueError("update must hold n_frames=%d uint8 flags" % nfr)
+        res = torch.zeros(shape + (3,), dtype=torch.float32, device=I.device)
+        p = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        stream = torch.cuda.current_stream(I.device).cuda_stream
+        fn = self._lib.t41rx_calibrate_device_q15 if q15 else self._lib.t41rx_calibrate_device
+        check(fn(self._ctx, p(I), p(Q), int(bool(shared_input)), p(u), p(res), p(pixel), p(spec), nfr, C.c_void_p(stream)))
+        self._cal_keep = (I, Q, u)  # alive until the next call: the launch is asynchronous
+        return res, pixel, spec
+
     def _check_out_torch(self, out, like):
         if not (out.is_cuda and out.dtype == like.dtype and out.is_contiguous() and tuple(out.shape) == tuple(like.shape)
                 and out.device == like.device):

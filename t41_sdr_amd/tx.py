@@ -4,6 +4,7 @@ The reference drives the exciter through globals and one function:
   ExciterIQData()      Exciter.cpp:46-169     -> TxChain.ExciterIQData(Q_in_L_Ex, Q_in_R_Ex)
   CW_ExciterIQData()   CW_Excite.cpp:66-118   -> TxChain.CW_ExciterIQData(n_frames, key)
   sineTone()           Utility.cpp:66-83      -> sine_tone(numCycles), then TxChain.set_cw_tone(cos, sin)
+  ProcessIQData2()     Process2.cpp:309-349   -> cal_tone(), TxChain.set_cal_tone(cos, sin, level), TxChain.ProcessIQData2_tx(n_frames)
 All arithmetic happens in libt41rx.so (HIP); PyTorch only owns device memory and streams.  No CPU
 fallback exists.
 """
@@ -39,6 +40,10 @@ TX_SYMBOLS = {
     "t41tx_set_cw_tone": (C.c_int, [_vp, _vp, _vp]),
     "t41tx_process_cw_device_q15": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
     "t41tx_process_cw_host_q15": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
+    "t41tx_set_cal_tone": (C.c_int, [_vp, _vp, _vp, C.c_float]),
+    "t41tx_set_cal_corrections": (C.c_int, [_vp, _vp, _vp]),
+    "t41tx_process_cal_device_q15": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "t41tx_process_cal_host_q15": (C.c_int, [_vp, _vp, _vp, C.c_int]),
 }
 _bound = False
 
@@ -73,6 +78,14 @@ def sine_tone(numCycles=8):
     f = float((int(numCycles) * 24000) // 256)
     theta = np.arange(256, dtype=np.float64) * 2.0 * np.pi * f / 24000.0
     return np.cos(theta).astype(np.float32), np.sin(theta).astype(np.float32)
+
+
+def cal_tone():
+    """(cosBuffer3, sinBuffer3) as sineTone() fills them (Utility.cpp:78-80), 256 float32 each, 3000 Hz: the angle
+    kf * 2.0 * PI * 3000 / 24000 is computed in float64 and stored in the float ``theta``, whose float64 cosine / sine
+    are rounded to float32.  A convenience, like sine_tone()."""
+    theta = (np.arange(256, dtype=np.float64) * 2.0 * np.pi * 3000.0 / 24000.0).astype(np.float32)
+    return np.cos(theta.astype(np.float64)).astype(np.float32), np.sin(theta.astype(np.float64)).astype(np.float32)
 
 
 class TxChain:
@@ -204,6 +217,47 @@ class TxChain:
         stream = torch.cuda.current_stream(dev).cuda_stream
         check(self._lib.t41tx_process_cw_device_q15(self._ctx, None if key is None else key.data_ptr(), oL.data_ptr(), oR.data_ptr(),
                                                     nfr, C.c_void_p(stream)))
+        return oL, oR
+
+    def set_cal_tone(self, cos, sin, level):
+        """cosBuffer3, sinBuffer3 (256 floats each, e.g. cal_tone()) and the firmware's bandOutputFactor
+        (t41tx_set_cal_tone).  Kept across set_params() and reset(); takes effect from the next ProcessIQData2_tx()."""
+        c = np.ascontiguousarray(np.asarray(cos, dtype=np.float32))
+        s = np.ascontiguousarray(np.asarray(sin, dtype=np.float32))
+        if c.shape != (256,) or s.shape != (256,):
+            raise ValueError("calibration tone tables must be 256 floats each, got %r and %r" % (c.shape, s.shape))
+        check(self._lib.t41tx_set_cal_tone(self._ctx, c.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p), float(level)))
+
+    def set_cal_corrections(self, amp=None, phase=None):
+        """one (IQXAmpCorrectionFactor, IQXPhaseCorrectionFactor) candidate per channel for the calibration exciter
+        (t41tx_set_cal_corrections): two arrays of n_channels floats, or None, None for the params' factors"""
+        if amp is None and phase is None:
+            check(self._lib.t41tx_set_cal_corrections(self._ctx, None, None))
+            return
+        if amp is None or phase is None:
+            raise ValueError("amp and phase must both be given or both be None")
+        a = np.ascontiguousarray(np.asarray(amp, dtype=np.float32))
+        p = np.ascontiguousarray(np.asarray(phase, dtype=np.float32))
+        if a.shape != (self.n_channels,) or p.shape != (self.n_channels,):
+            raise ValueError("corrections must be %d floats each, got %r and %r" % (self.n_channels, a.shape, p.shape))
+        check(self._lib.t41tx_set_cal_corrections(self._ctx, a.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p)))
+
+    def ProcessIQData2_tx(self, n_frames, device=False):
+        """n_frames frames of the calibration exciter (the transmit half of ProcessIQData2()) on every channel ->
+        (Q_out_L_Ex, Q_out_R_Ex), [n_channels, n_frames * 2048] int16: numpy arrays through the host entry, or with
+        device=True torch tensors on the current stream.  The interpolator memories are ExciterIQData()'s."""
+        nfr = int(n_frames)
+        if not device:
+            oL = np.empty((self.n_channels, max(nfr, 0) * self.FRAME), np.int16)
+            oR = np.empty_like(oL)
+            check(self._lib.t41tx_process_cal_host_q15(self._ctx, oL.ctypes.data_as(C.c_void_p), oR.ctypes.data_as(C.c_void_p), nfr))
+            return oL, oR
+        import torch
+        dev = torch.device("cuda", self.device)
+        oL = torch.empty((self.n_channels, max(nfr, 0) * self.FRAME), dtype=torch.int16, device=dev)
+        oR = torch.empty_like(oL)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(self._lib.t41tx_process_cal_device_q15(self._ctx, oL.data_ptr(), oR.data_ptr(), nfr, C.c_void_p(stream)))
         return oL, oR
 
     def _frames(self, shape):
