@@ -1,7 +1,10 @@
 // t41_sdr_amd/csrc/cal_kernel.hip -- the receive half of the IQ calibration, ProcessIQData2() (Process2.cpp:352-397), with
 // the sideband measurement of PlotCalSpectrum() (:478-547) behind it.  Compiled as part of rx_dispatch.hip, which holds no
 // other kernel (a kernel that joins display_kernel's translation unit moves that kernel's LDS and with it its code); it
-// uses the display side output's FFT, twiddle, window and zoom tables, and restates display_kernel's zoom chain.
+// uses the display side output's FFT, twiddle, window and zoom tables, and zoom_fft.hpp's zoom memories and low-pass.  The
+// chain itself (IIR, decimating FIR, ring, windowed read) is this kernel's own copy of zoom_fft.hpp's zoom_frame(), statement
+// for statement: through the helper the compiler lays the frame loop out otherwise and a sweep at zoom 0 takes 2 % longer
+// ("Shared exciter interpolators and zoom chain").  A change to one of the two goes into the other.
 //
 // One 64-lane wave = one channel = one (amplitude, phase) candidate, all the frames of a call.  Per frame, in the firmware's
 // order and with contraction off:
@@ -15,10 +18,9 @@
 //   ZoomFFTExe() on the 2048 shifted samples          :391-395, FFT.cpp:67-157       (spectrumZoom 1..4)
 //   pixelnew[] = baseOffset + pixel_offset + (int16_t)(dBScale * log10f_fast(FFT_spec[]))   FFT.cpp:157, 245
 // and in every frame, from the channel's current pixelnew[]: arm_max_q15 over the two windows and adjdB (:498-505, 524).
-// The zoom IIR and the decimating FIR are serial in the sample index: every lane runs the I (even lanes) or the Q (odd
-// lanes) chain redundantly, as display_kernel does; everything else is wave-parallel.
 #include "rx_kernels.hpp"
 #include "wave_fft.hpp"
+#include "zoom_fft.hpp"
 
 namespace t41 {
 
@@ -96,7 +98,6 @@ __global__ __launch_bounds__(64) void cal_kernel(const CalArgs a) {
     tw2[q] = tab[kTabTw2 + 64 * q + lane];
   }
   const int zoom = a.zoom;
-  const int chain = lane & 1;
   // the channel's candidate, or the params' factors
   const float neg_amp = -(a.corr ? a.corr[2 * (size_t)ch] : a.iq_amp);
   const float phase = a.corr ? a.corr[2 * (size_t)ch + 1] : a.iq_phase;
@@ -104,12 +105,8 @@ __global__ __launch_bounds__(64) void cal_kernel(const CalArgs a) {
   float st[16], fh[3];
   int ptr = 0;
   if (zoom > 0) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) st[i] = ds[kDispIir + 16 * chain + i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) fh[i] = ds[kDispFir + 4 * chain + i];
-    ptr = reinterpret_cast<const int *>(ds)[kDispPtr] & 511;
-    for (int i = lane; i < 2 * R; i += 64) (&ring[0][0])[i] = ds[kDispRing + i];
+    zoom_load(st, fh, ptr, ring, ds, lane);
+    ptr &= 511;
   }
   float old[8];
 #pragma unroll
@@ -118,7 +115,6 @@ __global__ __launch_bounds__(64) void cal_kernel(const CalArgs a) {
   double win[8];
 #pragma unroll
   for (int r = 0; r < 8; ++r) win[r] = a.win[lane + 64 * r];
-  const float LPFcoeff = 0.7f;
   const size_t in0 = (size_t)ch * (size_t)a.chan_stride;
   for (int f = 0; f < a.nframes; ++f) {
     const bool upd = a.update ? a.update[f] != 0 : true;  // the same for every lane and every channel
@@ -140,11 +136,12 @@ __global__ __launch_bounds__(64) void cal_kernel(const CalArgs a) {
           stage[1][n] = x.y;
         }
         __syncthreads();
+        // ---- zoom_fft.hpp's zoom_frame(), restated
         const int M = 1 << zoom;
         const int sample_no = (L / M > R) ? R : L / M;
         float h0 = fh[0], h1 = fh[1], h2 = fh[2];
         for (int n = 0; n < L; ++n) {
-          float x = stage[chain][n];
+          float x = stage[lane & 1][n];
 #pragma unroll
           for (int s4 = 0; s4 < 4; ++s4) {  // arm_biquad_cascade_df1_f32: acc = b0 x + b1 x1 + b2 x2 + a1 y1 + a2 y2
             const float *c = a.iir + 5 * s4;
@@ -165,7 +162,7 @@ __global__ __launch_bounds__(64) void cal_kernel(const CalArgs a) {
             acc += a.fir[1] * h1;
             acc += a.fir[2] * h2;
             acc += a.fir[3] * x;
-            if (k < sample_no && lane < 2) dec[chain][k] = acc;
+            if (k < sample_no && lane < 2) dec[lane & 1][k] = acc;
           }
           h0 = h1;
           h1 = h2;
@@ -195,15 +192,8 @@ __global__ __launch_bounds__(64) void cal_kernel(const CalArgs a) {
       for (int r = 0; r < 8; ++r) {
         const int x = (lane + 64 * r + 256) & 511;  // bins 0..255 -> upper half, 256..511 -> lower half
         const float m = v[r].x * v[r].x + v[r].y * v[r].y;
-        float spec;
-        if (zoom == 0) {  // FFT.cpp:241-245: float + double into FFT_spec_old, the pixel from the un-smoothed FFT_spec
-          old[r] = (float)((double)(LPFcoeff * m) + (1.0 - (double)LPFcoeff) * (double)old[r]);
-          spec = m;
-        } else {  // FFT.cpp:153-157: all float, the pixel from the smoothed value
-          const float onem = (float)(1.0 - (double)LPFcoeff);
-          spec = LPFcoeff * m + onem * old[r];
-          old[r] = spec;
-        }
+        // the pixel: from the un-smoothed FFT_spec at zoom 0 (FFT.cpp:245), from the smoothed one at zoom 1..4 (:157)
+        const float spec = zoom_lowpass(zoom, m, old[r]);
         // uint16 + int16 + int16 in int, stored to an int16
         const short p = (short)(a.base + (int)(short)(int)(a.dBScale * cal_log10f_fast(spec)));
         pix[x] = p;
@@ -241,16 +231,7 @@ __global__ __launch_bounds__(64) void cal_kernel(const CalArgs a) {
 #pragma unroll
   for (int r = 0; r < 8; ++r) ds[kDispOld + ((lane + 64 * r + 256) & 511)] = old[r];
   for (int i = lane; i < R; i += 64) reinterpret_cast<short *>(ds + kCalPixel)[i] = pix[i];
-  if (zoom > 0) {
-    if (lane < 2) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) ds[kDispIir + 16 * chain + i] = st[i];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) ds[kDispFir + 4 * chain + i] = fh[i];
-    }
-    if (lane == 0) reinterpret_cast<int *>(ds)[kDispPtr] = ptr;
-    for (int i = lane; i < 2 * R; i += 64) ds[kDispRing + i] = (&ring[0][0])[i];
-  }
+  if (zoom > 0) zoom_store(ds, st, fh, ptr, ring, lane);
 }
 
 hipError_t launch_cal(const CalArgs &a, hipStream_t s) {

@@ -20,6 +20,7 @@
 
 #include "cw_kernels.hpp"
 #include "cw_kernel.hip"  // the CW receive stages' kernels and launchers
+#include "dev_buf.hpp"
 #include "eq_kernels.hpp"
 #include "eq_kernel.hip"  // the receive equalizer's kernel and launcher
 #include "last_error.hpp"
@@ -31,25 +32,6 @@
 #include "rx_kernels.hpp"
 
 using namespace t41;
-
-namespace {
-// device memory the context owns: freed with its holder (t41rx_destroy: under the context's DeviceGuard)
-struct HipFree {
-  void operator()(void *p) const { (void)hipFree(p); }
-};
-template <class T>
-using DevBuf = std::unique_ptr<T, HipFree>;
-
-// hipMalloc into b; its previous buffer is freed first, and b stays empty when the allocation fails
-template <class T>
-hipError_t dev_alloc(DevBuf<T> &b, size_t bytes) {
-  b.reset();
-  void *p = nullptr;
-  const hipError_t e = hipMalloc(&p, bytes);
-  if (e == hipSuccess) b.reset(static_cast<T *>(p));
-  return e;
-}
-}  // namespace
 
 struct t41rx_ctx {
   int device = 0;
@@ -148,18 +130,6 @@ int hip_check(hipError_t e, const char *what) { return e == hipSuccess ? T41RX_O
     hipError_t e__ = (expr);                           \
     if (e__ != hipSuccess) return hip_fail(e__, #expr); \
   } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = (hipSetDevice(dev) == hipSuccess);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 
 constexpr float kPiF = 3.1415926535897932384626433832795f;  // FIR.h:10
 

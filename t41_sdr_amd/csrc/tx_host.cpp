@@ -6,13 +6,15 @@
 
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
+#include "dev_buf.hpp"
 #include "last_error.hpp"  // fail(): failures reach t41rx_last_error(), like the receive path's
 #include "tx_internal.hpp"
 #include "tx_cw_kernel.hip"  // the CW exciter's kernel and launcher
-#include "tx_cal_kernel.hip"  // the calibration exciter's (behind the CW exciter's: it uses that file's helpers)
+#include "tx_cal_kernel.hip"  // the calibration exciter's
 
 using namespace t41;
 
@@ -20,9 +22,9 @@ struct t41tx_ctx {
   int device = 0;
   int nchan = 0;
   t41tx_params params{};
-  float *d_state = nullptr;  // [nchan][kTxDelayFloats] delay lines, then [nchan][kTxEqStateFloats] equaliser memories
-  TxCoef *d_coef = nullptr;
-  int16_t *d_in = nullptr, *d_outL = nullptr, *d_outR = nullptr;  // staging of the host-pointer entry
+  DevBuf<float> d_state;  // [nchan][kTxDelayFloats] delay lines, then [nchan][kTxEqStateFloats] equaliser memories
+  DevBuf<TxCoef> d_coef;
+  DevBuf<int16_t> d_in, d_outL, d_outR;  // staging of the host-pointer entries
   size_t staging = 0;
   // transmit equaliser (xmitEQFlag, Exciter.cpp:94-98; t41tx_set_transmit_eq): the caller's band table and the levels
   // EEPROMData.equalizerXmt (gwv.cpp:50).  Configuration: kept across t41tx_set_params(), not part of a checkpoint.
@@ -38,22 +40,11 @@ struct t41tx_ctx {
   // caller's cosBuffer3 / sinBuffer3 and bandOutputFactor, and a correction candidate per channel.  Configuration too.
   bool cal_have_tone = false;
   float cal_cos[kTxCwTone] = {}, cal_sin[kTxCwTone] = {}, cal_level = 0.0f;
-  float *d_cal_corr = nullptr;  // [nchan][2] amplitude, phase; allocated by the first t41tx_set_cal_corrections()
+  DevBuf<float> d_cal_corr;  // [nchan][2] amplitude, phase; allocated by the first t41tx_set_cal_corrections()
   bool cal_per_channel = false;
 };
 
 namespace {
-struct Guard {
-  int prev = -1;
-  bool ok;
-  explicit Guard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = hipSetDevice(dev) == hipSuccess;
-  }
-  ~Guard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 // every mode the receive side accepts: ExciterIQData() runs in all of them and only applies the TX
 // IQ correction in LSB / USB (Exciter.cpp:117-140)
 bool valid(const t41tx_params &p) { return (p.mode >= T41RX_DEMOD_USB && p.mode <= T41RX_DEMOD_NFM) || p.mode == T41RX_DEMOD_SAM; }
@@ -61,32 +52,57 @@ bool valid(const t41tx_params &p) { return (p.mode >= T41RX_DEMOD_USB && p.mode 
 constexpr uint32_t kTxStateMagic = 0x58313454u;  // "T41X"
 constexpr size_t kTxStateHeaderBytes = 8 * sizeof(int32_t);
 size_t record_bytes(const t41tx_ctx *c) { return sizeof(float) * kTxStateFloats * (size_t)c->nchan; }
-float *eq_state(const t41tx_ctx *c) { return c->d_state + (size_t)kTxDelayFloats * (size_t)c->nchan; }
+float *eq_state(const t41tx_ctx *c) { return c->d_state.get() + (size_t)kTxDelayFloats * (size_t)c->nchan; }
 
-// staging of the host-pointer entries: one input and two output buffers of `bytes` each, grown on demand
-int ensure_staging(t41tx_ctx *ctx, size_t bytes) {
-  if (bytes <= ctx->staging) return T41RX_OK;
-  (void)hipFree(ctx->d_in);
-  (void)hipFree(ctx->d_outL);
-  (void)hipFree(ctx->d_outR);
-  ctx->d_in = ctx->d_outL = ctx->d_outR = nullptr;
+// staging of the host-pointer entries: one input and two output buffers of `*bytes` each (a call's q15 samples of one
+// side), grown on demand
+int ensure_staging(t41tx_ctx *ctx, int n_frames, size_t *bytes) {
+  *bytes = sizeof(int16_t) * 2048 * (size_t)n_frames * (size_t)ctx->nchan;
+  if (*bytes <= ctx->staging) return T41RX_OK;
+  ctx->d_in.reset();
+  ctx->d_outL.reset();
+  ctx->d_outR.reset();
   ctx->staging = 0;
-  if (hipMalloc((void **)&ctx->d_in, bytes) != hipSuccess || hipMalloc((void **)&ctx->d_outL, bytes) != hipSuccess ||
-      hipMalloc((void **)&ctx->d_outR, bytes) != hipSuccess)
+  if (dev_alloc(ctx->d_in, *bytes) != hipSuccess || dev_alloc(ctx->d_outL, *bytes) != hipSuccess || dev_alloc(ctx->d_outR, *bytes) != hipSuccess)
     return fail(T41RX_ERR_NOMEM, "staging allocation failed");
-  ctx->staging = bytes;
+  ctx->staging = *bytes;
   return T41RX_OK;
 }
 
-void free_ctx(t41tx_ctx *c) {
-  if (!c) return;
-  (void)hipFree(c->d_state);
-  (void)hipFree(c->d_coef);
-  (void)hipFree(c->d_in);
-  (void)hipFree(c->d_outL);
-  (void)hipFree(c->d_outR);
-  (void)hipFree(c->d_cal_corr);
-  delete c;
+// the tail of the host-pointer entries: rc is what the device entry returned for the staging buffers; wait for the launch
+// and copy both sides out
+int staged_out(const t41tx_ctx *ctx, int rc, int16_t *oL, int16_t *oR, size_t bytes) {
+  if (rc != T41RX_OK) return rc;
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(oL, ctx->d_outL.get(), bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(oR, ctx->d_outR.get(), bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(T41RX_ERR_HIP, "copy out failed");
+  return T41RX_OK;
+}
+
+// the argument checks of the tone exciters' entries (CW, calibration); device pointers must be 16-byte aligned as well
+int check_tone_call(const t41tx_ctx *ctx, bool t41tx_ctx::*have_tone, const char *no_tone, const int16_t *oL, const int16_t *oR, int n_frames,
+                    bool device_ptrs) {
+  if (!ctx || !oL || !oR) return fail(T41RX_ERR_ARG, "null argument");
+  if (!(ctx->*have_tone)) return fail(T41RX_ERR_ARG, no_tone);
+  if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
+  if (device_ptrs && ((reinterpret_cast<uintptr_t>(oL) | reinterpret_cast<uintptr_t>(oR)) & 15u))
+    return fail(T41RX_ERR_ARG, "device pointers must be 16-byte aligned");
+  return T41RX_OK;
+}
+constexpr const char *kNoCwTone = "CW exciter: no tone table loaded (t41tx_set_cw_tone)";
+constexpr const char *kNoCalTone = "calibration exciter: no tone table loaded (t41tx_set_cal_tone)";
+
+// what TxArgs, TxCwArgs and TxCalArgs have in common
+template <class Args>
+void common_args(Args &a, const t41tx_ctx *ctx, int16_t *oL, int16_t *oR, int n_frames) {
+  a.outL = oL;
+  a.outR = oR;
+  a.state = ctx->d_state.get();
+  a.coef = ctx->d_coef.get();
+  a.nchan = ctx->nchan;
+  a.nframes = n_frames;
+  a.corr_on = (ctx->params.mode == T41RX_DEMOD_LSB || ctx->params.mode == T41RX_DEMOD_USB) ? 1 : 0;
+  a.iq_phase = ctx->params.IQXPhaseCorrectionFactor;
 }
 }  // namespace
 
@@ -106,9 +122,9 @@ int t41tx_create(t41tx_ctx **out, int device_id, int n_channels, const t41tx_par
   if (!valid(*p)) return fail(T41RX_ERR_ARG, "mode must be USB, LSB, AM, NFM or SAM");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) return fail(T41RX_ERR_HIP, "no such HIP device");
-  Guard g(device_id);
+  DeviceGuard g(device_id);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
-  t41tx_ctx *c = new (std::nothrow) t41tx_ctx();
+  std::unique_ptr<t41tx_ctx> c(new (std::nothrow) t41tx_ctx());  // (freed before g restores the caller's device)
   if (!c) return fail(T41RX_ERR_NOMEM, "host allocation failed");
   c->device = device_id;
   c->nchan = n_channels;
@@ -119,20 +135,18 @@ int t41tx_create(t41tx_ctx **out, int device_id, int n_channels, const t41tx_par
   std::memcpy(h.h45, kTxHilbert45, sizeof(h.h45));
   std::memcpy(h.hn45, kTxHilbertNeg45, sizeof(h.hn45));
   const size_t sb = sizeof(float) * kTxStateFloats * (size_t)n_channels;
-  if (hipMalloc((void **)&c->d_state, sb) != hipSuccess || hipMalloc((void **)&c->d_coef, sizeof(TxCoef)) != hipSuccess ||
-      hipMemset(c->d_state, 0, sb) != hipSuccess || hipMemcpy(c->d_coef, &h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess) {
-    free_ctx(c);
+  if (dev_alloc(c->d_state, sb) != hipSuccess || dev_alloc(c->d_coef, sizeof(TxCoef)) != hipSuccess ||
+      hipMemset(c->d_state.get(), 0, sb) != hipSuccess || hipMemcpy(c->d_coef.get(), &h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess)
     return fail(T41RX_ERR_HIP, "device allocation failed");
-  }
-  *out = c;
+  *out = c.release();
   return T41RX_OK;
 }
 
 int t41tx_destroy(t41tx_ctx *ctx) {
   if (!ctx) return T41RX_OK;
-  Guard g(ctx->device);
+  DeviceGuard g(ctx->device);
   (void)hipDeviceSynchronize();
-  free_ctx(ctx);
+  delete ctx;
   return T41RX_OK;
 }
 
@@ -145,9 +159,9 @@ int t41tx_set_params(t41tx_ctx *ctx, const t41tx_params *p) {
 
 int t41tx_reset(t41tx_ctx *ctx) {
   if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
-  Guard g(ctx->device);
+  DeviceGuard g(ctx->device);
   if (hipDeviceSynchronize() != hipSuccess ||
-      hipMemset(ctx->d_state, 0, sizeof(float) * kTxStateFloats * (size_t)ctx->nchan) != hipSuccess)
+      hipMemset(ctx->d_state.get(), 0, sizeof(float) * kTxStateFloats * (size_t)ctx->nchan) != hipSuccess)
     return fail(T41RX_ERR_HIP, "state reset failed");
   return T41RX_OK;
 }
@@ -184,13 +198,13 @@ size_t t41tx_state_bytes(const t41tx_ctx *ctx) { return ctx ? kTxStateHeaderByte
 int t41tx_get_state(t41tx_ctx *ctx, void *host_buf, size_t bytes) {
   if (!ctx || !host_buf) return fail(T41RX_ERR_ARG, "null argument");
   if (bytes < t41tx_state_bytes(ctx)) return fail(T41RX_ERR_STATE, "state buffer too small");
-  Guard g(ctx->device);
+  DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
   const int32_t hdr[8] = {(int32_t)kTxStateMagic, T41RX_ABI_VERSION, ctx->nchan, kTxStateFloats, 0, 0, 0, 0};
   std::memcpy(host_buf, hdr, sizeof(hdr));
   const size_t n = (size_t)kTxStateFloats * (size_t)ctx->nchan;
   std::vector<float> dev(n);
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(dev.data(), ctx->d_state, sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess)
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(dev.data(), ctx->d_state.get(), sizeof(float) * n, hipMemcpyDeviceToHost) != hipSuccess)
     return fail(T41RX_ERR_HIP, "state copy out failed");
   // a channel's record: its delay lines, then its equaliser memories
   char *out = static_cast<char *>(host_buf) + kTxStateHeaderBytes;
@@ -223,9 +237,9 @@ int t41tx_set_state(t41tx_ctx *ctx, const void *host_buf, size_t bytes) {
     std::memcpy(dev.data() + (size_t)kTxDelayFloats * c, r, sizeof(float) * kTxDelayFloats);
     std::memcpy(eq + (size_t)kTxEqStateFloats * c, r + kTxStEq, sizeof(float) * kTxEqStateFloats);
   }
-  Guard g(ctx->device);
+  DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(ctx->d_state, dev.data(), sizeof(float) * n, hipMemcpyHostToDevice) != hipSuccess)
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(ctx->d_state.get(), dev.data(), sizeof(float) * n, hipMemcpyHostToDevice) != hipSuccess)
     return fail(T41RX_ERR_HIP, "state copy in failed");
   return T41RX_OK;
 }
@@ -237,19 +251,12 @@ int t41tx_process_device_q15(t41tx_ctx *ctx, const int16_t *dL, const int16_t *d
   if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
   if ((reinterpret_cast<uintptr_t>(dL) | reinterpret_cast<uintptr_t>(oL) | reinterpret_cast<uintptr_t>(oR)) & 15u)
     return fail(T41RX_ERR_ARG, "device pointers must be 16-byte aligned");
-  Guard g(ctx->device);
+  DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
   TxArgs a{};
+  common_args(a, ctx, oL, oR, n_frames);
   a.inL = dL;
-  a.outL = oL;
-  a.outR = oR;
-  a.state = ctx->d_state;
-  a.coef = ctx->d_coef;
-  a.nchan = ctx->nchan;
-  a.nframes = n_frames;
-  a.corr_on = (ctx->params.mode == T41RX_DEMOD_LSB || ctx->params.mode == T41RX_DEMOD_USB) ? 1 : 0;
   a.i_scale = (ctx->params.mode == T41RX_DEMOD_LSB) ? +ctx->params.IQXAmpCorrectionFactor : -ctx->params.IQXAmpCorrectionFactor;
-  a.iq_phase = ctx->params.IQXPhaseCorrectionFactor;
   hipError_t e;
   if (ctx->eq_on) {
     TxEqArgs q{};
@@ -275,17 +282,13 @@ int t41tx_process_host_q15(t41tx_ctx *ctx, const int16_t *L, const int16_t *R, i
   (void)R;
   if (!ctx || !L || !oL || !oR) return fail(T41RX_ERR_ARG, "null argument");
   if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
-  Guard g(ctx->device);
+  DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
-  const size_t bytes = sizeof(int16_t) * 2048 * (size_t)n_frames * (size_t)ctx->nchan;
-  if (const int rc = ensure_staging(ctx, bytes)) return rc;
-  if (hipMemcpy(ctx->d_in, L, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(T41RX_ERR_HIP, "copy in failed");
-  const int rc = t41tx_process_device_q15(ctx, ctx->d_in, nullptr, ctx->d_outL, ctx->d_outR, n_frames, nullptr);
-  if (rc != T41RX_OK) return rc;
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(oL, ctx->d_outL, bytes, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(oR, ctx->d_outR, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(T41RX_ERR_HIP, "copy out failed");
-  return T41RX_OK;
+  size_t bytes;
+  if (const int rc = ensure_staging(ctx, n_frames, &bytes)) return rc;
+  if (hipMemcpy(ctx->d_in.get(), L, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(T41RX_ERR_HIP, "copy in failed");
+  return staged_out(ctx, t41tx_process_device_q15(ctx, ctx->d_in.get(), nullptr, ctx->d_outL.get(), ctx->d_outR.get(), n_frames, nullptr), oL, oR,
+                    bytes);
 }
 
 int t41tx_set_cw_tone(t41tx_ctx *ctx, const float *cosBuffer2, const float *sinBuffer2) {
@@ -299,25 +302,14 @@ int t41tx_set_cw_tone(t41tx_ctx *ctx, const float *cosBuffer2, const float *sinB
 }
 
 int t41tx_process_cw_device_q15(t41tx_ctx *ctx, const uint8_t *d_key, int16_t *oL, int16_t *oR, int n_frames, void *hip_stream) {
-  if (!ctx || !oL || !oR) return fail(T41RX_ERR_ARG, "null argument");
-  if (!ctx->cw_have_tone) return fail(T41RX_ERR_ARG, "CW exciter: no tone table loaded (t41tx_set_cw_tone)");
-  if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
-  if ((reinterpret_cast<uintptr_t>(oL) | reinterpret_cast<uintptr_t>(oR)) & 15u)
-    return fail(T41RX_ERR_ARG, "device pointers must be 16-byte aligned");
-  Guard g(ctx->device);
+  if (const int rc = check_tone_call(ctx, &t41tx_ctx::cw_have_tone, kNoCwTone, oL, oR, n_frames, true)) return rc;
+  DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
   TxCwArgs a{};
+  common_args(a, ctx, oL, oR, n_frames);
   a.key = d_key;
-  a.outL = oL;
-  a.outR = oR;
-  a.state = ctx->d_state;
-  a.coef = ctx->d_coef;
-  a.nchan = ctx->nchan;
-  a.nframes = n_frames;
-  a.corr_on = (ctx->params.mode == T41RX_DEMOD_LSB || ctx->params.mode == T41RX_DEMOD_USB) ? 1 : 0;
   // the opposite signs of ExciterIQData()'s (CW_Excite.cpp:79, 84)
   a.i_scale = (ctx->params.mode == T41RX_DEMOD_LSB) ? -ctx->params.IQXAmpCorrectionFactor : +ctx->params.IQXAmpCorrectionFactor;
-  a.iq_phase = ctx->params.IQXPhaseCorrectionFactor;
   std::memcpy(a.tone_cos, ctx->cw_cos, sizeof(a.tone_cos));
   std::memcpy(a.tone_sin, ctx->cw_sin, sizeof(a.tone_sin));
   if (launch_tx_cw(a, (hipStream_t)hip_stream) != hipSuccess) return fail(T41RX_ERR_HIP, "kernel launch failed");
@@ -325,23 +317,16 @@ int t41tx_process_cw_device_q15(t41tx_ctx *ctx, const uint8_t *d_key, int16_t *o
 }
 
 int t41tx_process_cw_host_q15(t41tx_ctx *ctx, const uint8_t *key, int16_t *oL, int16_t *oR, int n_frames) {
-  if (!ctx || !oL || !oR) return fail(T41RX_ERR_ARG, "null argument");
-  if (!ctx->cw_have_tone) return fail(T41RX_ERR_ARG, "CW exciter: no tone table loaded (t41tx_set_cw_tone)");
-  if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
-  Guard g(ctx->device);
+  if (const int rc = check_tone_call(ctx, &t41tx_ctx::cw_have_tone, kNoCwTone, oL, oR, n_frames, false)) return rc;
+  DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
-  const size_t bytes = sizeof(int16_t) * 2048 * (size_t)n_frames * (size_t)ctx->nchan;
-  if (const int rc = ensure_staging(ctx, bytes)) return rc;
+  size_t bytes;
+  if (const int rc = ensure_staging(ctx, n_frames, &bytes)) return rc;
   // the gate rides in the input staging buffer: 16 bytes per frame where the microphone's samples take 4096
   const size_t key_bytes = (size_t)kTxCwKeyPerFrame * (size_t)n_frames * (size_t)ctx->nchan;
-  if (key && hipMemcpy(ctx->d_in, key, key_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(T41RX_ERR_HIP, "copy in failed");
-  const int rc = t41tx_process_cw_device_q15(ctx, key ? reinterpret_cast<const uint8_t *>(ctx->d_in) : nullptr, ctx->d_outL,
-                                             ctx->d_outR, n_frames, nullptr);
-  if (rc != T41RX_OK) return rc;
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(oL, ctx->d_outL, bytes, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(oR, ctx->d_outR, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(T41RX_ERR_HIP, "copy out failed");
-  return T41RX_OK;
+  if (key && hipMemcpy(ctx->d_in.get(), key, key_bytes, hipMemcpyHostToDevice) != hipSuccess) return fail(T41RX_ERR_HIP, "copy in failed");
+  const uint8_t *d_key = key ? reinterpret_cast<const uint8_t *>(ctx->d_in.get()) : nullptr;
+  return staged_out(ctx, t41tx_process_cw_device_q15(ctx, d_key, ctx->d_outL.get(), ctx->d_outR.get(), n_frames, nullptr), oL, oR, bytes);
 }
 
 int t41tx_set_cal_tone(t41tx_ctx *ctx, const float *cosBuffer3, const float *sinBuffer3, float level) {
@@ -369,39 +354,26 @@ int t41tx_set_cal_corrections(t41tx_ctx *ctx, const float *amp, const float *pha
     h[2 * (size_t)c] = amp[c];
     h[2 * (size_t)c + 1] = phase[c];
   }
-  Guard g(ctx->device);
+  DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
-  if (!ctx->d_cal_corr && hipMalloc((void **)&ctx->d_cal_corr, sizeof(float) * h.size()) != hipSuccess) {
-    ctx->d_cal_corr = nullptr;
+  if (!ctx->d_cal_corr && dev_alloc(ctx->d_cal_corr, sizeof(float) * h.size()) != hipSuccess)
     return fail(T41RX_ERR_NOMEM, "calibration corrections: device allocation failed");
-  }
   // (a launch still in flight reads the old candidates: wait for it, as the state copies do)
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(ctx->d_cal_corr, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice) != hipSuccess)
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(ctx->d_cal_corr.get(), h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice) != hipSuccess)
     return fail(T41RX_ERR_HIP, "calibration corrections: copy in failed");
   ctx->cal_per_channel = true;
   return T41RX_OK;
 }
 
 int t41tx_process_cal_device_q15(t41tx_ctx *ctx, int16_t *oL, int16_t *oR, int n_frames, void *hip_stream) {
-  if (!ctx || !oL || !oR) return fail(T41RX_ERR_ARG, "null argument");
-  if (!ctx->cal_have_tone) return fail(T41RX_ERR_ARG, "calibration exciter: no tone table loaded (t41tx_set_cal_tone)");
-  if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
-  if ((reinterpret_cast<uintptr_t>(oL) | reinterpret_cast<uintptr_t>(oR)) & 15u)
-    return fail(T41RX_ERR_ARG, "device pointers must be 16-byte aligned");
-  Guard g(ctx->device);
+  if (const int rc = check_tone_call(ctx, &t41tx_ctx::cal_have_tone, kNoCalTone, oL, oR, n_frames, true)) return rc;
+  DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
   TxCalArgs a{};
-  a.outL = oL;
-  a.outR = oR;
-  a.state = ctx->d_state;
-  a.coef = ctx->d_coef;
-  a.corr = ctx->cal_per_channel ? ctx->d_cal_corr : nullptr;
-  a.nchan = ctx->nchan;
-  a.nframes = n_frames;
+  common_args(a, ctx, oL, oR, n_frames);
+  a.corr = ctx->cal_per_channel ? ctx->d_cal_corr.get() : nullptr;
   a.level = ctx->cal_level;
   a.iq_amp = ctx->params.IQXAmpCorrectionFactor;
-  a.iq_phase = ctx->params.IQXPhaseCorrectionFactor;
-  a.corr_on = (ctx->params.mode == T41RX_DEMOD_LSB || ctx->params.mode == T41RX_DEMOD_USB) ? 1 : 0;
   a.lsb = ctx->params.mode == T41RX_DEMOD_LSB ? 1 : 0;  // Process2.cpp:318, 322: CW's signs, not ExciterIQData()'s
   std::memcpy(a.tone_cos, ctx->cal_cos, sizeof(a.tone_cos));
   std::memcpy(a.tone_sin, ctx->cal_sin, sizeof(a.tone_sin));
@@ -410,19 +382,12 @@ int t41tx_process_cal_device_q15(t41tx_ctx *ctx, int16_t *oL, int16_t *oR, int n
 }
 
 int t41tx_process_cal_host_q15(t41tx_ctx *ctx, int16_t *oL, int16_t *oR, int n_frames) {
-  if (!ctx || !oL || !oR) return fail(T41RX_ERR_ARG, "null argument");
-  if (!ctx->cal_have_tone) return fail(T41RX_ERR_ARG, "calibration exciter: no tone table loaded (t41tx_set_cal_tone)");
-  if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
-  Guard g(ctx->device);
+  if (const int rc = check_tone_call(ctx, &t41tx_ctx::cal_have_tone, kNoCalTone, oL, oR, n_frames, false)) return rc;
+  DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
-  const size_t bytes = sizeof(int16_t) * 2048 * (size_t)n_frames * (size_t)ctx->nchan;
-  if (const int rc = ensure_staging(ctx, bytes)) return rc;
-  const int rc = t41tx_process_cal_device_q15(ctx, ctx->d_outL, ctx->d_outR, n_frames, nullptr);
-  if (rc != T41RX_OK) return rc;
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(oL, ctx->d_outL, bytes, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(oR, ctx->d_outR, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(T41RX_ERR_HIP, "copy out failed");
-  return T41RX_OK;
+  size_t bytes;
+  if (const int rc = ensure_staging(ctx, n_frames, &bytes)) return rc;
+  return staged_out(ctx, t41tx_process_cal_device_q15(ctx, ctx->d_outL.get(), ctx->d_outR.get(), n_frames, nullptr), oL, oR, bytes);
 }
 
 }  // extern "C"

@@ -18,8 +18,12 @@
 // within rounding of a truncation boundary.
 // Not tuned (scalar f32 MACs, LDS windows): a side path of this library, SURVEY 8f rank 3.
 //
-// The transmit equaliser (DoExciterEQ(), Filter.cpp:176-224) is the tx_kernel<true> instantiation; tx_kernel<false> is
-// the kernel of before, instruction for instruction.  It runs in place on the frame's 256 samples @24 kS/s, between the /2
+// The x2 / x4 interpolators, their delay lines' load, roll and store, and the q15 packing are tx_interp.hpp's, shared with
+// the CW and the calibration exciter: both instantiations keep the arithmetic they had (the same floating-point operations
+// in the same order, no contraction), not the instruction stream.
+//
+// The transmit equaliser (DoExciterEQ(), Filter.cpp:176-224) is the tx_kernel<true> instantiation; tx_kernel<false> holds
+// none of its code.  It runs in place on the frame's 256 samples @24 kS/s, between the /2
 // decimator and the Hilbert pair, on df2t_pipe.hpp's pipeline with eq_kernel.hip's lane mapping: 14 bands of 4 cascaded
 // DF2T sections on the same input, one section per lane (lane 4 * band + stage), band k's output times its signed level,
 // the products summed as EQ1 + EQ2, then + EQ3, .., + EQ14.  Stage 0 takes its sample by an LDS broadcast.  The Hilbert
@@ -29,36 +33,18 @@
 #include <hip/hip_runtime.h>
 
 #include "df2t_pipe.hpp"
-#include "tx_internal.hpp"
+#include "tx_interp.hpp"
 
 namespace t41 {
 
 namespace {
 
-__device__ __forceinline__ void wave_sync() {
-  // one wave per workgroup: LDS executes its instructions in order; only the compiler must not reorder
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ float4 lds4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
-typedef const __attribute__((address_space(4))) TxCoef *CoefPtr;
-
-// (q15_t)__SSAT((q31_t)(x * 32768.0f), 16): CMSIS-DSP's arm_float_to_q15 without ARM_MATH_ROUNDING
-__device__ __forceinline__ unsigned q15_pack2(float x0, float x1) {
-  int a = (int)(x0 * 32768.0f), b = (int)(x1 * 32768.0f);
-  a = a < -32768 ? -32768 : (a > 32767 ? 32767 : a);
-  b = b < -32768 ? -32768 : (b > 32767 ? 32767 : b);
-  return ((unsigned)a & 0xffffu) | ((unsigned)b << 16);
-}
-
 // LDS layout of the wave (floats): every delay line as [history | new], history first
 constexpr int kXs = 0;                    // 47 + 2048 (+1)
 constexpr int kY1 = kXs + 2096;           // 23 + 512 (+1)
 constexpr int kHl = kY1 + 536;            // 99 + 256 (+1): both Hilbert filters see the same samples (Exciter.cpp:98)
-constexpr int kI1 = kHl + 356;            // [2][23 + 256 (+1)]
-constexpr int kI2 = kI1 + 2 * 280;        // [2][7 + 512 (+1)]
-constexpr int kLdsFloats = kI2 + 2 * 520;
+constexpr int kIl = kHl + 356;            // the interpolators' lines, tx_interp.hpp
+constexpr int kLdsFloats = kIl + kInterpFloats;
 
 // ---- transmit equaliser (tx_kernel<true>)
 static_assert(kTxEqBands == df2t::kBands, "df2t::sum_bands sums the equaliser's bands");
@@ -80,8 +66,7 @@ struct TxKernelArgs<true> {
 };
 }  // namespace
 
-// EQ: xmitEQFlag.  tx_kernel<false> is the kernel of before the equaliser existed, instruction for instruction
-// (tools/isa_fingerprint.py).
+// EQ: xmitEQFlag
 template <bool EQ>
 __global__ __launch_bounds__(64) void tx_kernel(const typename TxKernelArgs<EQ>::type a) {
 #pragma clang fp contract(off)
@@ -90,7 +75,7 @@ __global__ __launch_bounds__(64) void tx_kernel(const typename TxKernelArgs<EQ>:
   const int ch = blockIdx.x;
   if (ch >= a.nchan) return;
   float *st = a.state + (size_t)ch * kTxDelayFloats;
-  const CoefPtr cf = (CoefPtr)a.coef;
+  CoefPtr cf = (CoefPtr)a.coef;
 
   // ---- equaliser: this lane's section and level, HBM -> VGPRs, once per call
   const bool eq_live = lane < kTxEqSections;
@@ -110,14 +95,7 @@ __global__ __launch_bounds__(64) void tx_kernel(const typename TxKernelArgs<EQ>:
   if (lane < 47) lds[kXs + lane] = st[kTxStDec1 + lane];
   if (lane < 23) lds[kY1 + lane] = st[kTxStDec2 + lane];
   for (int i = lane; i < 99; i += 64) lds[kHl + i] = st[kTxStHilL + i];  // (FIR_Hilbert_state_R holds the same samples)
-  if (lane < 23) {
-    lds[kI1 + lane] = st[kTxStInt1I + lane];
-    lds[kI1 + 280 + lane] = st[kTxStInt1Q + lane];
-  }
-  if (lane < 7) {
-    lds[kI2 + lane] = st[kTxStInt2I + lane];
-    lds[kI2 + 520 + lane] = st[kTxStInt2Q + lane];
-  }
+  interp_load(lds + kIl, st, lane);
   wave_sync();
 
   for (int f = 0; f < a.nframes; ++f) {
@@ -188,6 +166,10 @@ __global__ __launch_bounds__(64) void tx_kernel(const typename TxKernelArgs<EQ>:
       wave_sync();
       sum_chunk(256 / kEqChunk - 1);
       wave_sync();
+      // Forget what was loaded through cf.  Otherwise the compiler keeps the interpolators' coefficients in SGPRs across
+      // the frame loop, the serial loop above loses its lane masks to spill lanes (72 v_readlane_b32 in it, not 8) and a
+      // launch of 4096 x 32 takes 3 % longer; loading them again behind the equaliser costs nothing measurable.
+      asm volatile("" : "+s"(cf));
     }
     // ---- Hilbert pair: y[n] = sum_i c[i] state[n + i], n = 4 lane + j, one window for both filters
     float I4[4], Q4[4];
@@ -227,50 +209,21 @@ __global__ __launch_bounds__(64) void tx_kernel(const typename TxKernelArgs<EQ>:
     // ---- x2 (48 taps, 24 per phase) then x4 (32 taps, 8 per phase), I then Q
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      float *s1 = lds + kI1 + 280 * c, *s2 = lds + kI2 + 520 * c;
+      float *s1 = lds + kIl + kInt1Pitch * c, *s2 = lds + kIl + kInt2At + kInt2Pitch * c;
       wave_sync();
       *reinterpret_cast<float2 *>(s1 + 23 + 4 * lane + 1) = make_float2(c ? Q4[1] : I4[1], c ? Q4[2] : I4[2]);  // (23 + 4 lane + 1 is even)
       s1[23 + 4 * lane] = c ? Q4[0] : I4[0];
       s1[23 + 4 * lane + 3] = c ? Q4[3] : I4[3];
       wave_sync();
-      {
-        // out[2 n + j - 1] = sum_t state[n + t] c[(2 - j) + 2 t], n = 4 lane + u
-        float w[28];
-#pragma unroll
-        for (int q = 0; q < 7; ++q) {
-          const float4 t = lds4(s1 + 4 * lane + 4 * q);
-          w[4 * q] = t.x;
-          w[4 * q + 1] = t.y;
-          w[4 * q + 2] = t.z;
-          w[4 * q + 3] = t.w;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          float o0 = 0.0f, o1 = 0.0f;
-#pragma unroll
-          for (int t = 0; t < 24; ++t) {
-            o0 += w[u + t] * cf->c48[1 + 2 * t];
-            o1 += w[u + t] * cf->c48[2 * t];
-          }
-          s2[7 + 8 * lane + 2 * u] = o0;
-          s2[7 + 8 * lane + 2 * u + 1] = o1;
-        }
-      }
+      interp2_block(s1, s2, cf, lane);
       wave_sync();
-      // out[4 n + j - 1] = sum_t state[n + t] c[(4 - j) + 4 t], n = lane + 64 u: 8 bytes per lane and u
+      // n = lane + 64 u: 8 bytes per lane and u
       int16_t *out = (c ? a.outR : a.outL) + base;
 #pragma unroll 2
       for (int u = 0; u < 8; ++u) {
         const int n = lane + 64 * u;
-        float o[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-          const float x = s2[n + t];
-          o[0] += x * cf->c192[3 + 4 * t];
-          o[1] += x * cf->c192[2 + 4 * t];
-          o[2] += x * cf->c192[1 + 4 * t];
-          o[3] += x * cf->c192[4 * t];
-        }
+        float o[4];
+        interp4_point(s2, n, cf, o);
         // x 20 (Exciter.cpp:151-152), arm_float_to_q15 (:161-162)
         *reinterpret_cast<uint2 *>(out + 4 * n) = make_uint2(q15_pack2(o[0] * 20.0f, o[1] * 20.0f), q15_pack2(o[2] * 20.0f, o[3] * 20.0f));
       }
@@ -281,21 +234,13 @@ __global__ __launch_bounds__(64) void tx_kernel(const typename TxKernelArgs<EQ>:
       const float x1 = (lane < 47) ? lds[kXs + 2048 + lane] : 0.0f;
       const float y1 = (lane < 23) ? lds[kY1 + 512 + lane] : 0.0f;
       const float h0 = lds[kHl + 256 + lane], h1 = (lane < 35) ? lds[kHl + 256 + 64 + lane] : 0.0f;
-      const float i1a = (lane < 23) ? lds[kI1 + 256 + lane] : 0.0f, i1b = (lane < 23) ? lds[kI1 + 280 + 256 + lane] : 0.0f;
-      const float i2a = (lane < 7) ? lds[kI2 + 512 + lane] : 0.0f, i2b = (lane < 7) ? lds[kI2 + 520 + 512 + lane] : 0.0f;
+      const InterpTails it = interp_tails(lds + kIl, lane);
       wave_sync();
       if (lane < 47) lds[kXs + lane] = x1;
       if (lane < 23) lds[kY1 + lane] = y1;
       lds[kHl + lane] = h0;
       if (lane < 35) lds[kHl + 64 + lane] = h1;
-      if (lane < 23) {
-        lds[kI1 + lane] = i1a;
-        lds[kI1 + 280 + lane] = i1b;
-      }
-      if (lane < 7) {
-        lds[kI2 + lane] = i2a;
-        lds[kI2 + 520 + lane] = i2b;
-      }
+      interp_heads(lds + kIl, it, lane);
     }
     wave_sync();
   }
@@ -306,14 +251,7 @@ __global__ __launch_bounds__(64) void tx_kernel(const typename TxKernelArgs<EQ>:
     st[kTxStHilL + i] = lds[kHl + i];
     st[kTxStHilR + i] = lds[kHl + i];
   }
-  if (lane < 23) {
-    st[kTxStInt1I + lane] = lds[kI1 + lane];
-    st[kTxStInt1Q + lane] = lds[kI1 + 280 + lane];
-  }
-  if (lane < 7) {
-    st[kTxStInt2I + lane] = lds[kI2 + lane];
-    st[kTxStInt2Q + lane] = lds[kI2 + 520 + lane];
-  }
+  interp_store(st, lds + kIl, lane);
   if constexpr (EQ) {
     if (eq_live) {
       float *m = a.eq_state + (size_t)ch * kTxEqStateFloats;
