@@ -485,6 +485,68 @@ T41RX_API int t41rx_calibrate_host(t41rx_ctx *ctx, const float *I, const float *
 T41RX_API int t41rx_calibrate_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, const int16_t *Q_in_R, int shared_input,
                              const uint8_t *update, float *result, int16_t *pixel, float *spec, int n_frames);
 
+/* ---- FT8 receive up to the finished waterfall (Process.cpp:627-686, ft8.cpp:153-268) ----
+ * In DEMOD_FT8 the firmware demodulates as USB and, on float_buffer_L as the demodulator and the AGC leave it (in front of
+ * the equalizer: the position of the demod tap), resamples to 6.4 kS/s into the rolling q15 buffer ft8_dsp_buffer[3072];
+ * every 15 frames process_FT8_FFT() turns it into four rows of 368 bytes of export_fft_power, and 92 such blocks per 15 s
+ * slot are the waterfall ft8_decode() searches.  Here FT8 is a switch on a USB context, not a mode of its own; find_sync(),
+ * ft8_decode() and the RTC stay with the caller.  Per channel and frame, in the firmware's order:
+ *   while syncFlag: arm_float_to_q15 (truncating, saturating) and the 68-iteration collector loop as written -- words
+ *     1020..1023 and 2044..2047 are never rolled, with leftover >= 1 iteration i rolls the sample iteration i - leftover of
+ *     the same frame has just written, the `leftover` cell behind frames 3 / 7 / 11 is rolled by the next frame --
+ *     ++dataLoop, the leftover cells at 4 / 8 / 12, the last cell and DSP_Flag = 1 at 15;
+ *   when DSP_Flag == 1 and ft8_flag == 1: for time_sub 0 and 512 (q15_t)((float)buf[i + time_sub] * window[i]),
+ *     arm_rfft_q15 (2048 points), arm_shift_q15 by 5, (re*re + im*im) >> 17 (0 .. 16384, the sum in 64 bits), mag_db[] by
+ *     that value, and for freq_sub 0 / 1 and j < 368 (int)((mag_db[.][2j + freq_sub] + mag_db[.][2j + freq_sub + 1]) / 2)
+ *     clipped to 0..255 at 1472 * FT_8_counter + 736 * (time_sub / 512) + 368 * freq_sub + j; FT_8_counter++, at 92
+ *     ft8_flag = 0; DSP_Flag = 0.  A DSP_Flag left standing while ft8_flag was 0 makes block 0 of the next slot fire on the
+ *     first frame after the restart, off the 15-frame phase, as in the firmware;
+ *   when ft8_flag == 0 and syncFlag: update_synchronization() in uint32 on millis(n) = t0 + floor(n * num / den):
+ *     (millis(n) - start_time) % 15000 <= 200 sets ft8_flag = 1, FT_8_counter = 0;
+ *   n, the channel's count of FT8 frames since power-on or reset, advances (on unsynced channels nothing else does).
+ * arm_rfft_q15 is restated as CMSIS-DSP's Cortex-M7 build computes it (radix-4 q15 stages with their scaling, bit
+ * reversal, the real split stage with q15 tables rounded half away from zero): tests/ft8_model.py lists what that leaves
+ * open.  The stage only reads the audio: the audio out is bit for bit what it is with the stage off.
+ * t41rx_set_ft8_tables(): window = ft_blackman_i(i, 2048), i < 2048; mag_db[m] = 10.0 * log((float)(10 * m) + 0.1), m <=
+ *   16384, both from the firmware's libm (host arrays, copied; synchronises).  The library has no table of its own.
+ *   T41RX_ERR_ARG for NULL or a non-finite entry.
+ * t41rx_set_ft8(): on = 1 with device buffers d_power [n_channels][2][92 * 1472] uint8 -- two halves, so that a finished
+ *   slot stays readable while the next is written; the library never clears them -- and d_status [n_channels][n_frames][4]
+ *   int32 (16-byte aligned) = {FT_8_counter behind the frame, ft8_flag, 0 or 1 + the half completed in this frame,
+ *   dataLoop}, written for every frame of every process call of at most max_frames frames (a longer call:
+ *   T41RX_ERR_ARG).  max_frames <= 1380 (T41RX_ERR_ARG above): two completions of one channel are at least 92 x 15
+ *   frames apart, so a half reported complete is intact when the call returns.  on = 1 gets T41RX_ERR_UNSUPPORTED at a
+ *   long fft_length, T41RX_ERR_ARG with a NULL buffer or before the tables are loaded.  on = 0 switches the stage off (the
+ *   other arguments are ignored; the FT8 memory stays).  While on, a process call with mode != T41RX_DEMOD_USB is refused
+ *   with T41RX_ERR_UNSUPPORTED (t41rx_last_error() says why).  f32 and q15 entry points, both buffer layouts.  Kept across
+ *   t41rx_set_params() / t41rx_set_coeffs().  t41rx_get_ft8() returns the switch.
+ * t41rx_set_ft8_clock(): millis(n) = t0_ms + floor(n * num / den) in uint32; default 0, 32, 3 (one frame of 2048 samples
+ *   at 192 kS/s).  From the next call; n is not touched.  T41RX_ERR_ARG for num < 0 or den <= 0.
+ * t41rx_ft8_sync(): auto_sync_FT8()'s success branch on the channels whose byte is non-zero (host array of n = n_channels
+ *   bytes; NULL = all): start_time = millis(n), ft8_flag = 1, FT_8_counter = 0, syncFlag = true, nothing else
+ *   (synchronises).  The caller's clock decides when: the firmware calls it once second() % 15 turns 0.
+ * The FT8 memory -- 16 int32 scalars {n, syncFlag, ft8_flag, DSP_Flag, FT_8_counter, dataLoop, leftover, start_time, half
+ * being written, 7 zeros} and the 3072 buffer words per channel -- is the context's own: allocated at first use, at
+ * power-on values (all zero) after t41rx_reset() and after t41rx_set_state(), and NOT part of the checkpoint:
+ * t41rx_state_bytes() and the section mask are unchanged.  Its record is t41rx_ft8_state_bytes() / _get_state / _set_state:
+ * a header of 8 int32 {magic "T41F", ABI, n_channels, words per channel = 3088, 0, 0, 0, 0}, then [n_channels][3088] int32.
+ * _set_state refuses (T41RX_ERR_STATE, nothing written) another size or header, dataLoop outside 0..14, leftover outside
+ * 0..3, FT_8_counter outside 0..91 (92 only next to ft8_flag 0, where the firmware leaves it between a slot's last block
+ * and the restart), a flag or `half` outside 0 / 1, a non-zero reserved word, a buffer word outside -32768..32767. */
+#define T41RX_FT8_ROW_BYTES 368    /* ft8_buffer */
+#define T41RX_FT8_BLOCK_BYTES 1472 /* offset_step */
+#define T41RX_FT8_SLOT_BLOCKS 92   /* ft8_msg_samples */
+#define T41RX_FT8_MAX_FRAMES 1380
+#define T41RX_FT8_STATE_WORDS 3088
+T41RX_API int t41rx_set_ft8_tables(t41rx_ctx *ctx, const float *window, const float *mag_db);
+T41RX_API int t41rx_set_ft8(t41rx_ctx *ctx, int on, uint8_t *d_power, int32_t *d_status, int max_frames);
+T41RX_API int t41rx_get_ft8(const t41rx_ctx *ctx);
+T41RX_API int t41rx_set_ft8_clock(t41rx_ctx *ctx, int32_t t0_ms, int32_t num, int32_t den);
+T41RX_API int t41rx_ft8_sync(t41rx_ctx *ctx, const uint8_t *channels, int n);
+T41RX_API size_t t41rx_ft8_state_bytes(const t41rx_ctx *ctx);
+T41RX_API int t41rx_ft8_get_state(t41rx_ctx *ctx, void *host_buf, size_t bytes);
+T41RX_API int t41rx_ft8_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

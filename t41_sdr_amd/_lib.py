@@ -98,6 +98,14 @@ SYMBOLS = {
     "t41rx_calibrate_device_q15": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "t41rx_calibrate_host": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int]),
     "t41rx_calibrate_host_q15": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int]),
+    "t41rx_set_ft8_tables": (C.c_int, [_vp, _vp, _vp]),
+    "t41rx_set_ft8": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int]),
+    "t41rx_get_ft8": (C.c_int, [_vp]),
+    "t41rx_set_ft8_clock": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32]),
+    "t41rx_ft8_sync": (C.c_int, [_vp, _vp, C.c_int]),
+    "t41rx_ft8_state_bytes": (C.c_size_t, [_vp]),
+    "t41rx_ft8_get_state": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "t41rx_ft8_set_state": (C.c_int, [_vp, _vp, C.c_size_t]),
 }
 
 _lib = None

@@ -23,6 +23,8 @@
 #include "dev_buf.hpp"
 #include "eq_kernels.hpp"
 #include "eq_kernel.hip"  // the receive equalizer's kernel and launcher
+#include "ft8_kernels.hpp"
+#include "ft8_kernel.hip"  // the FT8 receive stage's kernels and launchers
 #include "last_error.hpp"
 #include "nb_kernels.hpp"
 #include "nb_kernel.hip"  // the noise blanker's kernel and launcher
@@ -105,6 +107,22 @@ struct t41rx_ctx {
   int cal_zoom = 0, cal_base = 0, cal_lo0 = 0, cal_lo1 = 0, cal_width = 0;
   float cal_dbscale = 0.0f;
   DevBuf<float> d_cal, d_cal_corr;
+  // FT8 receive up to the waterfall (Process.cpp:627-686, ft8.cpp:153-268; t41rx_set_ft8_tables / _ft8 / _ft8_clock /
+  // t41rx_ft8_sync): the caller's window and mag_db (device copies), arm_rfft_q15's tables, the switch with the caller's
+  // power and status buffers, the clock millis(n) = t0 + floor(n * num / den), and the FT8 memory per channel
+  // [nchan][kFt8Words] (ft8_kernels.hpp), allocated at first use.  The context's own: no checkpoint section (its record is
+  // t41rx_ft8_get_state / _set_state).  The stage reads the demodulated audio where the demod tap sits: d_aud24 when other
+  // stages split the chain, else the caller's demod tap buffer, else d_ft8_tap.
+  int ft8_on = 0;
+  bool ft8_have_tables = false;
+  uint8_t *ft8_power = nullptr;   // [nchan][2][kFt8HalfBytes]
+  int32_t *ft8_status = nullptr;  // [nchan][n_frames][4]
+  int ft8_frames = 0;             // frames per call ft8_status is sized for
+  int32_t ft8_t0 = 0, ft8_num = 32, ft8_den = 3;  // 2048 samples at 192 kS/s
+  DevBuf<int32_t> d_ft8;
+  DevBuf<float> d_ft8_win, d_ft8_mag, d_ft8_tap;
+  DevBuf<uint32_t> d_ft8_tab;
+  int ft8_tap_frames = 0;
   // staging for t41rx_process_host
   DevBuf<float> d_in_i, d_in_q, d_out;
   size_t staging_floats = 0;
@@ -363,6 +381,31 @@ int check_cw_decode(const t41rx_ctx *c, const int32_t *, const float *sec) {
   return T41RX_OK;
 }
 
+// the FT8 memory (power-on: every word zero -- syncFlag false, ft8_flag 0, an empty buffer) and arm_rfft_q15's tables
+int ensure_ft8(t41rx_ctx *ctx) {
+  if (ctx->d_ft8) return T41RX_OK;
+  DevBuf<int32_t> st;
+  DevBuf<uint32_t> tab;
+  const size_t bytes = sizeof(int32_t) * kFt8Words * (size_t)ctx->nchan;
+  if (dev_alloc(st, bytes) != hipSuccess || dev_alloc(tab, sizeof(uint32_t) * kFt8TabWords) != hipSuccess)
+    return fail(T41RX_ERR_NOMEM, "FT8 state allocation failed");
+  std::vector<uint32_t> h((size_t)kFt8TabWords);
+  ft8_make_fft_tables(h.data());
+  if (hipMemset(st.get(), 0, bytes) != hipSuccess ||
+      hipMemcpy(tab.get(), h.data(), sizeof(uint32_t) * h.size(), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(T41RX_ERR_HIP, "FT8 state upload failed");
+  ctx->d_ft8 = std::move(st);
+  ctx->d_ft8_tab = std::move(tab);
+  return T41RX_OK;
+}
+int ft8_power_on(t41rx_ctx *ctx) {
+  if (!ctx->d_ft8) return T41RX_OK;
+  return hip_check(hipMemset(ctx->d_ft8.get(), 0, sizeof(int32_t) * kFt8Words * (size_t)ctx->nchan), "FT8 reset");
+}
+constexpr uint32_t kFt8Magic = 0x46313454u;  // "T41F"
+constexpr size_t kFt8HeaderBytes = 32;
+size_t ft8_record_bytes(const t41rx_ctx *ctx) { return kFt8HeaderBytes + sizeof(int32_t) * kFt8Words * (size_t)ctx->nchan; }
+
 // a broken hand-over protocol of the pipelined kernels leaves wrong samples and a count of waits that ran out, not a hung
 // GPU -- reported at the calls that synchronise anyway
 int pipe_timeouts(const t41rx_ctx *ctx) {  // < 0: the counter could not be read
@@ -554,7 +597,7 @@ int reset_state(t41rx_ctx *ctx) {
     const int rc = s.reset(ctx, section_bytes(s, ctx->nchan));
     if (rc != T41RX_OK) return rc;
   }
-  return T41RX_OK;
+  return ft8_power_on(ctx);
 }
 
 // ---- a process call: (a) prepare_call, (b) rx_args, (c) launch_chain
@@ -631,6 +674,20 @@ int prepare_call(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
                                              " leaves float_buffer_L different from float_buffer_R and neither the notch nor the noise "
                                              "blanker joins them behind it; the library carries one audio stream");
   if (ctx->disp_spec && (!ctx->d_pre || !ctx->d_disp || !ctx->d_win)) return fail(T41RX_ERR_STATE, "display spectrum enabled without its buffers");
+  if (ctx->ft8_on) {
+    if (ctx->params.mode != T41RX_DEMOD_USB)
+      return fail(T41RX_ERR_UNSUPPORTED, "FT8 receive: the firmware demodulates DEMOD_FT8 as USB (Process.cpp:616-617); this context's mode is not T41RX_DEMOD_USB");
+    if (n_frames > ctx->ft8_frames) return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the FT8 status buffer was set with");
+    if ((rc = ensure_ft8(ctx)) != T41RX_OK) return rc;
+    if (!stages_on(ctx) && !ctx->dbg_demod && n_frames > ctx->ft8_tap_frames) {
+      // the demod tap of the context's own (grown on demand, kept)
+      HIP_TRY(hipStreamSynchronize(s));
+      ctx->ft8_tap_frames = 0;
+      ctx->d_ft8_tap.reset();
+      HIP_TRY(dev_alloc(ctx->d_ft8_tap, sizeof(float) * 256 * (size_t)n_frames * (size_t)ctx->nchan));
+      ctx->ft8_tap_frames = n_frames;
+    }
+  }
   // the decoder's words, behind every refusal: its checkpoint section appears with the first call in which it runs
   if (cw_dec_on(ctx) && (rc = ensure_cw_decode(ctx)) != T41RX_OK) return rc;
   return T41RX_OK;
@@ -693,6 +750,7 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
   a.dbg_nco = ctx->dbg_nco;
   a.dbg_dec = ctx->dbg_dec;
   a.dbg_demod = ctx->dbg_demod;
+  if (ctx->ft8_on && !stages_on(ctx) && !a.dbg_demod) a.dbg_demod = ctx->d_ft8_tap.get();  // the FT8 stage reads the demod tap
   a.spect = ctx->spect;
   a.spect_max = ctx->spect_max;
   if (stages_on(ctx)) a.aud_out = ctx->d_aud24.get();  // the fused kernel stops behind the demodulator
@@ -704,6 +762,27 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
 int launch_chain(t41rx_ctx *ctx, RxArgs a, int n_frames, hipStream_t s) {
   hipError_t e = launch_rx(a, ctx->params.fft_length, ctx->params.mode, s);
   if (e != hipSuccess) return hip_fail(e, "kernel launch");
+  if (ctx->ft8_on) {
+    // Process.cpp:627-685 on float_buffer_L as the demodulator and the AGC leave it, in front of the equalizer: the
+    // hand-over buffer when other stages split the chain, else the demod tap.  The stage only reads the audio.
+    Ft8Args f{};
+    f.aud = a.aud_out ? a.aud_out : a.dbg_demod;
+    f.state = ctx->d_ft8.get();
+    f.power = ctx->ft8_power;
+    f.status = ctx->ft8_status;
+    f.window = ctx->d_ft8_win.get();
+    f.mag_db = ctx->d_ft8_mag.get();
+    f.tab = ctx->d_ft8_tab.get();
+    f.nchan = ctx->nchan;
+    f.nframes = n_frames;
+    f.t0 = ctx->ft8_t0;
+    f.num = ctx->ft8_num;
+    f.den = ctx->ft8_den;
+    f.threads = 256;
+    if (const char *env = std::getenv("T41RX_FT8_THREADS")) f.threads = std::atoi(env) == 64 ? 64 : 256;  // experiments (tools/ft8_probe.py)
+    e = launch_ft8(f, s);
+    if (e != hipSuccess) return hip_fail(e, "FT8 kernel launch");
+  }
   if (ctx->eq_on) {
     // Process.cpp:828-832 on the call's audio @24 kS/s
     EqArgs q{};
@@ -1349,6 +1428,122 @@ int t41rx_reset_cw_histograms(t41rx_ctx *ctx, const uint8_t *channels, int n) {
   return T41RX_OK;
 }
 
+int t41rx_set_ft8_tables(t41rx_ctx *ctx, const float *window, const float *mag_db) {
+  if (!ctx || !window || !mag_db) return fail(T41RX_ERR_ARG, "null argument");
+  for (int i = 0; i < kFt8Fft; ++i)
+    if (!std::isfinite(window[i])) return fail(T41RX_ERR_ARG, "FT8 window: non-finite entry");
+  for (int i = 0; i < kFt8MagEntries; ++i)
+    if (!std::isfinite(mag_db[i])) return fail(T41RX_ERR_ARG, "FT8 mag_db table: non-finite entry");
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  HIP_TRY(hipDeviceSynchronize());  // (a launch still in flight reads the old tables)
+  if (!ctx->d_ft8_win) HIP_TRY(dev_alloc(ctx->d_ft8_win, sizeof(float) * kFt8Fft));
+  if (!ctx->d_ft8_mag) HIP_TRY(dev_alloc(ctx->d_ft8_mag, sizeof(float) * kFt8MagEntries));
+  HIP_TRY(hipMemcpy(ctx->d_ft8_win.get(), window, sizeof(float) * kFt8Fft, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ctx->d_ft8_mag.get(), mag_db, sizeof(float) * kFt8MagEntries, hipMemcpyHostToDevice));
+  ctx->ft8_have_tables = true;
+  return T41RX_OK;
+}
+
+int t41rx_set_ft8(t41rx_ctx *ctx, int on, uint8_t *d_power, int32_t *d_status, int max_frames) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (on != 0 && on != 1) return fail(T41RX_ERR_ARG, "FT8 receive: on must be 0 or 1");
+  if (on) {
+    if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "FT8 receive is built for fft_length 512");
+    if (!d_power || !d_status) return fail(T41RX_ERR_ARG, "FT8 receive: no power or status buffer (d_power / d_status is NULL)");
+    if (reinterpret_cast<uintptr_t>(d_status) & 15u) return fail(T41RX_ERR_ARG, "FT8 receive: d_status must be 16-byte aligned");
+    if (max_frames <= 0) return fail(T41RX_ERR_ARG, "max_frames must be > 0");
+    if (max_frames > kFt8MaxFrames)
+      return fail(T41RX_ERR_ARG, "FT8 receive: max_frames must be <= 1380 (92 blocks of 15 frames: at most one completed slot per call)");
+    if (!ctx->ft8_have_tables) return fail(T41RX_ERR_ARG, "FT8 receive: no tables loaded (t41rx_set_ft8_tables)");
+  }
+  ctx->ft8_on = on;
+  ctx->ft8_power = on ? d_power : nullptr;
+  ctx->ft8_status = on ? d_status : nullptr;
+  ctx->ft8_frames = on ? max_frames : 0;
+  return T41RX_OK;
+}
+int t41rx_get_ft8(const t41rx_ctx *ctx) { return ctx ? ctx->ft8_on : T41RX_ERR_ARG; }
+
+int t41rx_set_ft8_clock(t41rx_ctx *ctx, int32_t t0_ms, int32_t num, int32_t den) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (num < 0 || den <= 0) return fail(T41RX_ERR_ARG, "FT8 clock: num must be >= 0 and den > 0");
+  ctx->ft8_t0 = t0_ms;  // (passed by value to every launch: the next call uses it; the frame counters stay)
+  ctx->ft8_num = num;
+  ctx->ft8_den = den;
+  return T41RX_OK;
+}
+
+int t41rx_ft8_sync(t41rx_ctx *ctx, const uint8_t *channels, int n) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (channels && n != ctx->nchan) return fail(T41RX_ERR_ARG, "n must equal n_channels");
+  if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "FT8 receive is built for fft_length 512");
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  HIP_TRY(hipDeviceSynchronize());
+  if (const int rc = ensure_ft8(ctx)) return rc;
+  DevBuf<uint8_t> mask;
+  if (channels) {
+    HIP_TRY(dev_alloc(mask, (size_t)ctx->nchan));
+    HIP_TRY(hipMemcpy(mask.get(), channels, (size_t)ctx->nchan, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(launch_ft8_sync(ctx->d_ft8.get(), mask.get(), ctx->nchan, ctx->ft8_t0, ctx->ft8_num, ctx->ft8_den, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  return T41RX_OK;
+}
+
+size_t t41rx_ft8_state_bytes(const t41rx_ctx *ctx) { return ctx ? ft8_record_bytes(ctx) : 0; }
+
+int t41rx_ft8_get_state(t41rx_ctx *ctx, void *host_buf, size_t bytes) {
+  if (!ctx || !host_buf) return fail(T41RX_ERR_ARG, "null argument");
+  if (bytes < ft8_record_bytes(ctx)) return fail(T41RX_ERR_STATE, "FT8 state buffer too small");
+  const int32_t hdr[8] = {(int32_t)kFt8Magic, T41RX_ABI_VERSION, ctx->nchan, kFt8Words, 0, 0, 0, 0};
+  std::memcpy(host_buf, hdr, sizeof(hdr));
+  char *body = static_cast<char *>(host_buf) + kFt8HeaderBytes;
+  const size_t n = ft8_record_bytes(ctx) - kFt8HeaderBytes;
+  if (!ctx->d_ft8) {  // the stage has not run: its words are the power-on ones
+    std::memset(body, 0, n);
+    return T41RX_OK;
+  }
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(body, ctx->d_ft8.get(), n, hipMemcpyDeviceToHost));
+  return T41RX_OK;
+}
+
+int t41rx_ft8_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes) {
+  if (!ctx || !host_buf) return fail(T41RX_ERR_ARG, "null argument");
+  if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "FT8 receive is built for fft_length 512");
+  if (bytes != ft8_record_bytes(ctx)) return fail(T41RX_ERR_STATE, "FT8 state size mismatch");
+  int32_t hdr[8];
+  std::memcpy(hdr, host_buf, sizeof(hdr));
+  if ((uint32_t)hdr[0] != kFt8Magic || hdr[1] != T41RX_ABI_VERSION || hdr[2] != ctx->nchan || hdr[3] != kFt8Words)
+    return fail(T41RX_ERR_STATE, "FT8 state header does not match this context (magic / abi / channels / words per channel)");
+  // what ft8_kernel indexes, loops or branches with; everything is checked before anything is written
+  const int32_t *all = reinterpret_cast<const int32_t *>(static_cast<const char *>(host_buf) + kFt8HeaderBytes);
+  for (int ch = 0; ch < ctx->nchan; ++ch) {
+    const int32_t *w = all + (size_t)kFt8Words * (size_t)ch;
+    if (w[kFt8DataLoop] < 0 || w[kFt8DataLoop] > 14) return fail(T41RX_ERR_STATE, "FT8 state: dataLoop out of range (0 .. 14)");
+    if (w[kFt8Leftover] < 0 || w[kFt8Leftover] > 3) return fail(T41RX_ERR_STATE, "FT8 state: leftover out of range (0 .. 3)");
+    for (int k : {kFt8Sync, kFt8Flag, kFt8DspFlag, kFt8Half})
+      if (w[k] != 0 && w[k] != 1) return fail(T41RX_ERR_STATE, "FT8 state: flag (syncFlag, ft8_flag, DSP_Flag, half) not 0 or 1");
+    // (the firmware leaves FT_8_counter at 92 between a slot's last block and the restart, with ft8_flag 0: it indexes nothing then)
+    if (w[kFt8Counter] < 0 || w[kFt8Counter] > (w[kFt8Flag] == 0 ? kFt8SlotBlocks : kFt8SlotBlocks - 1))
+      return fail(T41RX_ERR_STATE, "FT8 state: FT_8_counter out of range (0 .. 91)");
+    for (int k = kFt8Named; k < kFt8Scalars; ++k)
+      if (w[k] != 0) return fail(T41RX_ERR_STATE, "FT8 state: reserved word not zero");
+    for (int k = kFt8Scalars; k < kFt8Words; ++k)
+      if (w[k] < -32768 || w[k] > 32767) return fail(T41RX_ERR_STATE, "FT8 state: buffer word is not a q15 sample");
+  }
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  HIP_TRY(hipDeviceSynchronize());
+  if (const int rc = ensure_ft8(ctx)) return rc;
+  HIP_TRY(hipMemcpy(ctx->d_ft8.get(), all, bytes - kFt8HeaderBytes, hipMemcpyHostToDevice));
+  return T41RX_OK;
+}
+
 int t41rx_n_channels(const t41rx_ctx *ctx) { return ctx ? ctx->nchan : T41RX_ERR_ARG; }
 int t41rx_frame_len(const t41rx_ctx *ctx) { return ctx ? 4 * ctx->params.fft_length : T41RX_ERR_ARG; }
 
@@ -1472,6 +1667,7 @@ int t41rx_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes) {
     if ((rc = (sec & s.bit) ? s.put(ctx, p, n) : s.reset(ctx, n)) != T41RX_OK) return rc;
     if (sec & s.bit) p += n;
   }
+  if ((rc = ft8_power_on(ctx)) != T41RX_OK) return rc;  // (the FT8 memory has a record of its own: a checkpoint starts it afresh)
   return pipe_timeouts_clear(ctx);  // the restored state is valid again
 }
 

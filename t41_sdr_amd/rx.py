@@ -39,7 +39,22 @@ def design_coeffs(params):
     return blob
 
 
-BLOB_HEADER_WORDS = 32   # magic, abi, fft_length, mode, sizeof(params), 3 reserved | t41rx_params padded to 24 words
+def ft8_tables():
+    """(window[2048], mag_db[16385]) for RxChain.set_ft8_tables(), in the firmware's types: ft_blackman_i(i, 2048) in f32
+    (ft8.cpp:168-178) and (float)(10.0 * log((float)(10 * m) + 0.1)) with the sum and the logarithm in double
+    (ft8.cpp:238-240).  numpy's cos / log stand in for the firmware's libm."""
+    f = np.float32
+    alpha = f(0.16)
+    a0, a1, a2 = (f(1) - alpha) / f(2), f(0.5), alpha / f(2)
+    x1 = np.cos(f(2) * f(np.pi) * np.arange(2048, dtype=np.float32) / f(2047), dtype=np.float32)
+    x2 = f(2) * x1 * x1 - f(1)
+    window = (a0 - a1 * x1 + a2 * x2).astype(np.float32)
+    m = np.arange(16385, dtype=np.int64)
+    mag_db = (10.0 * np.log((10 * m).astype(np.float32).astype(np.float64) + 0.1)).astype(np.float32)
+    return window, mag_db
+
+
+BLOB_HEADER_WORDS = 32  # magic, abi, fft_length, mode, sizeof(params), 3 reserved | t41rx_params padded to 24 words
 STATE_HEADER_BYTES = 32  # checkpoint header: magic, abi, fft_length, n_channels, floats per channel, sections, spectrumZoom, reserved
 
 
@@ -287,6 +302,92 @@ class RxChain:
         if m.shape != (self.n_channels,):
             raise ValueError("channels must have n_channels = %d entries, got %r" % (self.n_channels, m.shape))
         check(self._lib.t41rx_reset_cw_histograms(self._ctx, m.ctypes.data_as(C.c_void_p), self.n_channels))
+
+    # -- FT8 receive up to the waterfall ------------------------------------------------------
+    def set_ft8_tables(self, window=None, mag_db=None):
+        """The FT8 tables (t41rx_set_ft8_tables): window = ft_blackman_i(i, 2048), 2048 floats; mag_db[m] = 10.0 *
+        log((float)(10 * m) + 0.1), 16385 floats.  None, None computes both with ft8_tables().  The library has no table of
+        its own.  Kept across CalcFilters() / set_coeffs()."""
+        if window is None and mag_db is None:
+            window, mag_db = ft8_tables()
+        if window is None or mag_db is None:
+            raise ValueError("window and mag_db must both be given or both be None")
+        w = np.ascontiguousarray(np.asarray(window, dtype=np.float32))
+        m = np.ascontiguousarray(np.asarray(mag_db, dtype=np.float32))
+        if w.shape != (2048,) or m.shape != (16385,):
+            raise ValueError("FT8 tables must be 2048 and 16385 floats, got %r and %r" % (w.shape, m.shape))
+        check(self._lib.t41rx_set_ft8_tables(self._ctx, w.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p)))
+
+    def set_ft8(self, on, max_frames=1):
+        """FT8 receive on a USB context (Process.cpp:627-686, ft8.cpp:153-268; t41rx_set_ft8): the audio collector, the
+        two q15 FFTs per 15 frames and the waterfall rows, with the firmware's slot timing.  on = 1 allocates and returns
+        (power, status): uint8 CUDA [n_channels, 2, 92 * 1472], the two halves of export_fft_power, and int32 CUDA
+        [n_channels, max_frames, 4]; a process call of n <= max_frames <= 1380 frames fills the status' first n_channels *
+        n * 4 words as [n_channels][n][FT_8_counter, ft8_flag, 0 or 1 + the half completed in this frame, dataLoop]
+        (ft8_status(n) is that view).  on = 0 switches it off and returns None.  Nothing is collected before ft8_sync().
+        fft_length 512, mode USB; the tables loaded first.  Kept across CalcFilters() / set_coeffs()."""
+        if not on:
+            check(self._lib.t41rx_set_ft8(self._ctx, 0, None, None, 0))
+            self._ft8 = None
+            return None
+        import torch
+        if int(max_frames) < 1:
+            raise ValueError("max_frames must be >= 1")
+        dev = "cuda:%d" % self.device
+        power = torch.zeros(self.n_channels, 2, 92 * 1472, dtype=torch.uint8, device=dev)
+        status = torch.zeros(self.n_channels, int(max_frames), 4, dtype=torch.int32, device=dev)
+        check(self._lib.t41rx_set_ft8(self._ctx, int(on), C.c_void_p(power.data_ptr()), C.c_void_p(status.data_ptr()), int(max_frames)))
+        self._ft8 = (power, status)  # keep alive
+        return power, status
+
+    @property
+    def ft8(self):
+        v = self._lib.t41rx_get_ft8(self._ctx)
+        if v < 0:
+            check(v)
+        return v
+
+    def ft8_status(self, n_frames):
+        """the FT8 status words of the last process call of n_frames frames: a view [n_channels, n_frames, 4]"""
+        t = getattr(self, "_ft8", None)
+        if t is None:
+            raise ValueError("FT8 receive is off")
+        return t[1].view(-1)[:self.n_channels * int(n_frames) * 4].view(self.n_channels, int(n_frames), 4)
+
+    def ft8_power(self):
+        """export_fft_power, uint8 CUDA [n_channels, 2, 92 * 1472]: the half a status word reported complete holds the
+        finished slot, [92 blocks][time_sub 0 / 512][freq_sub 0 / 1][368]"""
+        t = getattr(self, "_ft8", None)
+        if t is None:
+            raise ValueError("FT8 receive is off")
+        return t[0]
+
+    def set_ft8_clock(self, t0_ms=0, num=32, den=3):
+        """The slot timing's clock (t41rx_set_ft8_clock): millis(n) = t0_ms + floor(n * num / den) for the channel's n-th
+        FT8 frame; the default is one frame of 2048 samples at 192 kS/s.  From the next call; n is not touched."""
+        check(self._lib.t41rx_set_ft8_clock(self._ctx, int(t0_ms), int(num), int(den)))
+
+    def ft8_sync(self, channels=None):
+        """auto_sync_FT8()'s success branch (ft8.cpp:133-136) on the channels whose entry is non-zero (None: all):
+        start_time = millis(n), ft8_flag = 1, FT_8_counter = 0, syncFlag = true.  The caller's clock decides when."""
+        if channels is None:
+            check(self._lib.t41rx_ft8_sync(self._ctx, None, 0))
+            return
+        m = np.ascontiguousarray(np.asarray(channels).astype(bool).astype(np.uint8))
+        if m.shape != (self.n_channels,):
+            raise ValueError("channels must have n_channels = %d entries, got %r" % (self.n_channels, m.shape))
+        check(self._lib.t41rx_ft8_sync(self._ctx, m.ctypes.data_as(C.c_void_p), self.n_channels))
+
+    def ft8_state(self):
+        """the FT8 memory's record (t41rx_ft8_get_state): 8 int32 of header, then [n_channels][3088] int32 (uint8 array)"""
+        n = self._lib.t41rx_ft8_state_bytes(self._ctx)
+        buf = np.zeros(n, dtype=np.uint8)
+        check(self._lib.t41rx_ft8_get_state(self._ctx, buf.ctypes.data_as(C.c_void_p), n))
+        return buf
+
+    def set_ft8_state(self, buf):
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        check(self._lib.t41rx_ft8_set_state(self._ctx, buf.ctypes.data_as(C.c_void_p), buf.size))
 
     def get_state(self):
         n = self._lib.t41rx_state_bytes(self._ctx)

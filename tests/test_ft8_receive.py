@@ -1,0 +1,405 @@
+"""FT8 receive up to the finished waterfall (Process.cpp:627-686, ft8.cpp:153-268) as a HIP stage: ft8_kernel against its
+restatement (tests/ft8_model.py).
+
+CPU: the entry points are declared, exported and bound.
+
+GPU (-m gpu): USB contexts with the demod tap set; the model is fed with the tapped audio, and every d_status word, every
+d_power byte and every word of the FT8 state record is compared with np.array_equal -- on f32, q15 and time-major calls
+split at ragged edges, over a whole slot and its restart, from prepared records, across checkpoints and resets.  The audio,
+t41rx_state_bytes() and the path checkpoint are the stage-off ones bit for bit.  Each channel has its own input amplitude:
+channel 0 saturates arm_shift_q15, the last one quantises to zero.
+"""
+import ctypes as C
+import functools
+import os
+import re
+
+import numpy as np
+import pytest
+
+import ft8_model as M
+import siggen
+
+L = 2048
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("t41rx_set_ft8_tables", "t41rx_set_ft8", "t41rx_get_ft8", "t41rx_set_ft8_clock", "t41rx_ft8_sync",
+       "t41rx_ft8_state_bytes", "t41rx_ft8_get_state", "t41rx_ft8_set_state")
+SPLITS = (1, 14, 15, 16, 47)  # 93 frames: blocks at frames 14, 29, .., 89
+GAINS = (3.0, 0.3, 0.02, 1e-7)  # x the test signal: clipped at the q15 range / ordinary / weak / below one q15 step
+
+
+# ---- CPU ---------------------------------------------------------------------------------------------------------------
+def test_entry_points_declared_exported_and_bound(built):
+    import t41_sdr_amd._lib as lib
+    hdr = open(os.path.join(ROOT, "include", "t41rx.h")).read()
+    m = open(os.path.join(ROOT, "t41_sdr_amd", "csrc", "exports.map")).read()
+    for name in NEW:
+        assert re.search(r"T41RX_API\s+(int|size_t)\s+%s\s*\(" % name, hdr) and (name + ";") in m and name in lib.SYMBOLS, name
+        assert hasattr(C.CDLL(lib.LIB_PATH), name)
+    import t41_sdr_amd as T
+    for meth in ("set_ft8_tables", "set_ft8", "ft8", "ft8_status", "ft8_power", "set_ft8_clock", "ft8_sync", "ft8_state", "set_ft8_state"):
+        assert hasattr(T.RxChain, meth)
+    assert callable(T.ft8_tables)
+    assert "T41RX_ABI_VERSION 5" in hdr and lib.load().t41rx_abi_version() == 5
+    assert not open(os.path.join(ROOT, "include", "t41tx.h")).read().count("ft8")
+
+
+# ---- GPU ---------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _iq(nch, nfr, seed=0x465438):
+    """every channel its own passband tones and noise, scaled by its gain and clipped to the q15 range; read only"""
+    nco = siggen.nco_grid(nch)
+    I, Q = siggen.make_iq(nch, nfr * L, nco, mode=0, seed=seed, sigma=0.05)
+    g = np.array([GAINS[c % len(GAINS)] for c in range(nch)], np.float32)[:, None]
+    I, Q = np.clip(I * g, -0.999, 0.999).astype(np.float32), np.clip(Q * g, -0.999, 0.999).astype(np.float32)
+    I.setflags(write=False)
+    Q.setflags(write=False)
+    return nco, I, Q
+
+
+@functools.lru_cache(maxsize=None)
+def _tables():
+    return M.ft8_tables()
+
+
+class Run:
+    """one context with FT8 on; process() runs a piece of the stream through the chosen entry point and returns (audio,
+    tapped demod audio or None, status) as numpy"""
+
+    def __init__(self, T, nch, nco, max_frames, entry="f32", tap=True, on=True, **params):
+        import torch
+        self.torch, self.nch, self.entry = torch, nch, entry
+        self.rx = T.RxChain(nch, T.default_params(mode=0, **params), NCOFreq=nco)
+        if entry == "time":
+            self.rx.set_buffer_layout("time")
+        self.tap = torch.zeros(nch, max_frames * 256, dtype=torch.float32, device="cuda") if tap else None
+        if tap:
+            self.rx.set_debug_taps(demod=self.tap)
+        self.power = None
+        if on:
+            self.rx.set_ft8_tables(*_tables())
+            self.power, _ = self.rx.set_ft8(1, max_frames)
+
+    def process(self, I, Q):
+        t = self.torch
+        n = I.shape[1] // L
+        if self.entry == "q15":
+            a, b = (np.trunc(I * 32768.0).astype(np.int16), np.trunc(Q * 32768.0).astype(np.int16))
+            out = self.rx.ProcessIQData_q15(t.from_numpy(b).cuda(), t.from_numpy(a).cuda())  # I comes from the R queue
+        elif self.entry == "time":
+            f = lambda x: t.from_numpy(np.ascontiguousarray(x.reshape(self.nch, n, L).transpose(1, 0, 2))).cuda()  # noqa: E731
+            out = self.rx.ProcessIQData(f(I), f(Q)).permute(1, 0, 2).reshape(self.nch, n * L)
+        else:
+            out = self.rx.ProcessIQData(t.from_numpy(np.array(I)).cuda(), t.from_numpy(np.array(Q)).cuda())
+        t.cuda.synchronize()
+        tap = None if self.tap is None else self.tap.view(-1)[:self.nch * n * 256].view(self.nch, n * 256).cpu().numpy().copy()
+        st = None if self.power is None else self.rx.ft8_status(n).cpu().numpy().copy()
+        return out.cpu().numpy(), tap, st
+
+
+def _stream(run, I, Q, splits, model=None):
+    """the stream in calls of `splits` frames; with a model, every call's status is held to it on the tapped audio"""
+    f0, audio, status = 0, [], []
+    for n in splits:
+        a, tap, st = run.process(I[:, f0 * L:(f0 + n) * L], Q[:, f0 * L:(f0 + n) * L])
+        if model is not None:
+            want = model.process(tap)
+            assert np.array_equal(st, want), "status words differ in the call at frame %d" % f0
+        audio.append(a)
+        status.append(st)
+        f0 += n
+    return np.concatenate(audio, axis=1), (np.concatenate(status, axis=1) if status[0] is not None else None)
+
+
+def _same_as_model(run, model):
+    assert np.array_equal(run.power.cpu().numpy(), model.power), "d_power differs from the model"
+    assert np.array_equal(run.rx.ft8_state(), model.record()), "the FT8 state record differs from the model"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry", ["f32", "q15", "time"])
+def test_gpu_ft8_equals_model(entry):
+    """4 channels, 93 frames in calls of 1 / 14 / 15 / 16 / 47 through the C ABI with the demod tap set: six blocks per
+    channel, every status word, power byte and record word the model's.  Channel 0 saturates arm_shift_q15, channel 3's
+    audio quantises to zero (its rows are mag_db[0] clipped to 0)"""
+    import t41_sdr_amd as T
+    nch, nfr = 4, sum(SPLITS)
+    nco, I, Q = _iq(nch, nfr)
+    run = Run(T, nch, nco, max(SPLITS), entry=entry)
+    model = M.FT8Model(nch, *_tables())
+    run.rx.ft8_sync()
+    model.sync()
+    _, st = _stream(run, I, Q, SPLITS, model)
+    _same_as_model(run, model)
+    assert (st[:, -1, 0] == 6).all() and (st[:, :, 2] == 0).all()
+    # the amplitudes do what they are there for
+    idx = M.mag_index(M.window_q15(model.buf[:, 512:512 + M.FFT_SIZE], _tables()[0]))
+    print("largest squared-magnitude index per channel:", idx.max(axis=1), "largest |q15| in the buffer:", np.abs(model.buf).max(axis=1))
+    assert idx[0].max() >= 8191 and 0 < idx[1].max() and not model.buf[3].any() and not model.power[3].any()
+    assert model.power[0].max() >= 113 and model.power[2, 0, :6 * M.BLOCK_BYTES].any()
+
+
+@pytest.mark.gpu
+def test_gpu_whole_slot_and_restart():
+    """3 channels, 1450 frames: the 92 blocks of a slot, the completion reported in frame 1379 alone, ft8_flag back in
+    frame 1407, block 0 of the second slot one frame later in the other half, off the 15-frame phase"""
+    import t41_sdr_amd as T
+    nch, splits = 3, (1380, 29, 41)
+    nco, I, Q = _iq(nch, sum(splits), seed=0x534C4F)
+    run = Run(T, nch, nco, max(splits))
+    model = M.FT8Model(nch, *_tables())
+    model.collect = M.collect_closed_form  # (test_ft8_model.py holds it to the literal loop)
+    run.rx.ft8_sync()
+    model.sync()
+    _, st = _stream(run, I, Q, splits, model)
+    _same_as_model(run, model)
+    for c in range(nch):
+        assert np.array_equal(np.nonzero(st[c, :, 2])[0], [1379]) and st[c, 1379].tolist() == [92, 0, 1, 0]
+        assert (st[c, 1379:1407, 1] == 0).all() and st[c, 1407, :2].tolist() == [0, 1] and st[c, 1408, 0] == 1 and st[c, 1409, 0] == 2
+    p = run.power.cpu().numpy()
+    assert p[:2, 0].reshape(2, 92, -1).any(axis=2).all() and p[0, 1, :5 * M.BLOCK_BYTES].any() and not p[:, 1, 5 * M.BLOCK_BYTES:].any()
+
+
+def _prepared(nch, seed=11):
+    """records that reach the slot's edges in tens of frames, by channel % 4:
+      0  FT_8_counter 90, dataLoop 13: blocks 90 and 91 in frames 1 and 16, completion of half 0, the flip
+      1  ft8_flag 0 with FT_8_counter 92 and a stale DSP_Flag, n = 1404: the restart in frame 3 (millis(1407) = 15008), block
+         0 one frame later, off the phase, into half 1
+      2  not synced: only n moves
+      3  half 1, FT_8_counter 91 with DSP_Flag standing: the block fires in frame 0 and reports half 1 complete"""
+    rng = np.random.default_rng(seed)
+    w = np.zeros((nch, M.WORDS), np.int32)
+    w[:, M.SCALARS:] = rng.integers(-32768, 32768, (nch, M.BUF_WORDS))
+    for c in range(nch):
+        s, k = w[c], c % 4
+        if k == 0:
+            s[M.S_N], s[M.S_SYNC], s[M.S_FT8FLAG], s[M.S_COUNTER], s[M.S_DATALOOP], s[M.S_LEFTOVER] = 1363, 1, 1, 90, 13, 3
+        elif k == 1:
+            s[M.S_N], s[M.S_SYNC], s[M.S_FT8FLAG], s[M.S_DSPFLAG], s[M.S_COUNTER], s[M.S_DATALOOP], s[M.S_LEFTOVER], s[M.S_HALF] = 1404, 1, 0, 1, 92, 9, 2, 1
+        elif k == 2:
+            s[M.S_N], s[M.S_DATALOOP], s[M.S_LEFTOVER] = 77, 5, 1
+        else:
+            s[M.S_N], s[M.S_SYNC], s[M.S_FT8FLAG], s[M.S_DSPFLAG], s[M.S_COUNTER], s[M.S_HALF], s[M.S_START] = 400, 1, 1, 1, 91, 1, -123456
+    hdr = np.array([M.MAGIC, M.ABI, nch, M.WORDS, 0, 0, 0, 0], np.int32)
+    return np.concatenate([hdr, w.ravel()]).view(np.uint8)
+
+
+@pytest.mark.gpu
+def test_gpu_prepared_records():
+    """40 frames in calls of 7 and 33 from the prepared records: completion, the half flip and the off-phase block 0"""
+    import t41_sdr_amd as T
+    nch, splits = 5, (7, 33)
+    nco, I, Q = _iq(nch, sum(splits), seed=0x505245)
+    rec = _prepared(nch)
+    run = Run(T, nch, nco, max(splits))
+    run.rx.set_ft8_state(rec)
+    assert np.array_equal(run.rx.ft8_state(), rec)
+    run.power.fill_(0xA5)  # the library never clears d_power: what is not written stays
+    model = M.FT8Model(nch, *_tables())
+    model.load_record(rec)
+    model.power[:] = 0xA5
+    _, st = _stream(run, I, Q, splits, model)
+    _same_as_model(run, model)
+    assert st[0, 1, 0] == 91 and st[0, 16].tolist() == [92, 0, 1, 0] and st[4, 16, 2] == 1
+    assert st[1, 2, 1] == 0 and st[1, 3, :3].tolist() == [0, 1, 0] and st[1, 4, 0] == 1 and st[1, 5, 0] == 2  # frame 5: dataLoop 15
+    assert (st[2, :, :3] == 0).all() and st[3, 0, :3].tolist() == [92, 0, 2]
+    p = run.power.cpu().numpy()
+    assert (p[2] == 0xA5).all() and (p[1, 0] == 0xA5).all() and (p[1, 1, 4 * M.BLOCK_BYTES:] == 0xA5).all()
+    assert (p[0, 0, :90 * M.BLOCK_BYTES] == 0xA5).all() and (p[0, 0, 90 * M.BLOCK_BYTES:] != 0xA5).any()
+    words = run.rx.ft8_state().view(np.int32)[8:].reshape(nch, M.WORDS)
+    assert words[2, M.S_N] == 77 + 40 and words[0, M.S_HALF] == 1 and words[3, M.S_HALF] == 0
+
+
+@pytest.mark.gpu
+def test_gpu_clock_in_uint32():
+    """t41rx_set_ft8_clock(-50, 1000, 7): 142.86 ms per frame from a negative t0, with n about to wrap past 2^32 in one
+    channel and start_time ahead of millis in another -- update_synchronization()'s uint32 differences as the model's"""
+    import t41_sdr_amd as T
+    nch, splits = 4, (9, 20)
+    nco, I, Q = _iq(nch, sum(splits), seed=0x434C4B)
+    w = np.zeros((nch, M.WORDS), np.int32)
+    for c, (n, start) in enumerate(((-5, 123), (1000, -2000000000), (0, 2000000000), (104, -8))):
+        w[c, [M.S_N, M.S_SYNC, M.S_COUNTER, M.S_START, M.S_DATALOOP, M.S_LEFTOVER]] = n, 1, 92, start, 7, 1
+    rec = np.concatenate([np.array([M.MAGIC, M.ABI, nch, M.WORDS, 0, 0, 0, 0], np.int32), w.ravel()]).view(np.uint8)
+    run = Run(T, nch, nco, max(splits))
+    run.rx.set_ft8_clock(-50, 1000, 7)
+    run.rx.set_ft8_state(rec)
+    model = M.FT8Model(nch, *_tables(), t0=-50, num=1000, den=7)
+    model.load_record(rec)
+    _, st = _stream(run, I, Q, splits, model)
+    _same_as_model(run, model)
+    assert model.millis(0xFFFFFFFB) == (-50 + 0xFFFFFFFB * 1000 // 7) & 0xFFFFFFFF
+    first = [int(np.argmax(st[c, :, 1])) if st[c, :, 1].any() else -1 for c in range(nch)]
+    print("frames in which ft8_flag returns:", first)
+    assert first == [7, 16, 20, 2]  # each on its own n and start_time; channel 3: millis(106) + 8 = 15100
+    run.rx.ft8_sync([1, 0, 0, 0])
+    model.sync([1, 0, 0, 0])
+    words = run.rx.ft8_state().view(np.int32)[8:].reshape(nch, M.WORDS)
+    assert np.array_equal(run.rx.ft8_state(), model.record()) and words[0, M.S_COUNTER] == 0 and words[0, M.S_FT8FLAG] == 1
+    assert words[0, M.S_N] == -5 + sum(splits) and (int(words[0, M.S_START]) & 0xFFFFFFFF) == model.millis(sum(splits) - 5)
+
+
+@pytest.mark.gpu
+def test_gpu_state_split_calls_checkpoint_and_reset():
+    """one long call equals split calls; ft8_state -> set_ft8_state on a fresh context continues bit for bit;
+    t41rx_reset() and t41rx_set_state() return the record to power-on"""
+    import t41_sdr_amd as T
+    nch, nfr = 4, sum(SPLITS)
+    nco, I, Q = _iq(nch, nfr)
+    a, b = Run(T, nch, nco, nfr), Run(T, nch, nco, nfr)
+    for r in (a, b):
+        r.rx.ft8_sync()
+    aud_a, st_a = _stream(a, I, Q, (nfr,))
+    aud_b, st_b = _stream(b, I, Q, SPLITS)
+    assert np.array_equal(st_a, st_b) and np.array_equal(aud_a, aud_b)
+    assert np.array_equal(a.power.cpu().numpy(), b.power.cpu().numpy()) and np.array_equal(a.rx.ft8_state(), b.rx.ft8_state())
+    # a checkpoint of both records after 31 frames, continued on a fresh context
+    c, d = Run(T, nch, nco, nfr), Run(T, nch, nco, nfr)
+    c.rx.ft8_sync()
+    _stream(c, I[:, :31 * L], Q[:, :31 * L], (31,))
+    path, rec = c.rx.get_state(), c.rx.ft8_state()
+    d.rx.set_state(path)
+    d.rx.set_ft8_state(rec)
+    d.power.copy_(c.power)
+    aud_d, st_d = _stream(d, I[:, 31 * L:], Q[:, 31 * L:], (nfr - 31,))
+    assert np.array_equal(st_d, st_a[:, 31:]) and np.array_equal(aud_d, aud_a[:, 31 * L:])
+    assert np.array_equal(d.power.cpu().numpy(), a.power.cpu().numpy()) and np.array_equal(d.rx.ft8_state(), a.rx.ft8_state())
+    # power-on
+    fresh = M.FT8Model(nch, *_tables()).record()
+    assert a.rx.ft8_state().view(np.int32)[8:].any()
+    a.rx.reset()
+    assert np.array_equal(a.rx.ft8_state(), fresh)
+    assert b.rx.ft8_state().view(np.int32)[8:].any()
+    b.rx.set_state(path)
+    assert np.array_equal(b.rx.ft8_state(), fresh)
+    assert np.array_equal(Run(T, nch, nco, 1).rx.ft8_state(), fresh)  # before the stage has run
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["agc_off", "agc_on", "noise_blanker"])
+def test_gpu_existing_outputs_unmoved(case):
+    """the stage only reads: audio, t41rx_state_bytes() and the path checkpoint with FT8 on are the stage-off ones bit for
+    bit -- on USB with the fixed gain, with the AGC, and with the noise blanker running behind the stage (the chain is
+    split then and the stage reads the hand-over buffer in front of the blanker).  Without a caller's tap the stage
+    reads the context's own: same status, same power"""
+    import t41_sdr_amd as T
+    nch, splits = 4, (5, 16, 3)
+    nco, I, Q = _iq(nch, sum(splits))
+    params = dict(AGCMode=1) if case == "agc_on" else {}
+    runs = {"off": Run(T, nch, nco, max(splits), tap=False, on=False, **params),
+            "on": Run(T, nch, nco, max(splits), tap=False, **params),
+            "on_tap": Run(T, nch, nco, max(splits), tap=True, **params)}
+    for r in runs.values():
+        if case == "noise_blanker":
+            r.rx.set_noise_blanker(1)
+        if r.power is not None:
+            r.rx.ft8_sync()
+    model = M.FT8Model(nch, *_tables())
+    model.sync()
+    aud_off, _ = _stream(runs["off"], I, Q, splits)
+    aud_on, st_on = _stream(runs["on"], I, Q, splits)
+    aud_tap, st_tap = _stream(runs["on_tap"], I, Q, splits, model)
+    _same_as_model(runs["on_tap"], model)
+    assert np.array_equal(aud_on, aud_off) and np.array_equal(aud_tap, aud_off)
+    assert np.array_equal(st_on, st_tap) and np.array_equal(runs["on"].power.cpu().numpy(), runs["on_tap"].power.cpu().numpy())
+    assert np.array_equal(runs["on"].rx.ft8_state(), runs["on_tap"].rx.ft8_state())
+    lib = runs["on"].rx._lib
+    assert lib.t41rx_state_bytes(runs["on"].rx._ctx) == lib.t41rx_state_bytes(runs["off"].rx._ctx)
+    assert np.array_equal(runs["on"].rx.get_state(), runs["off"].rx.get_state())
+    assert runs["on"].rx.get_state()[:32].view(np.int32)[5] == (4 if case == "noise_blanker" else 0)
+
+
+@pytest.mark.gpu
+def test_gpu_gating_and_refusals():
+    import t41_sdr_amd as T
+    import torch
+    from t41_sdr_amd import _lib
+    nch, nfr = 4, 31
+    nco, I, Q = _iq(nch, sum(SPLITS))
+    I, Q = I[:, :nfr * L], Q[:, :nfr * L]
+    # a channel mask syncs only its channels; unsynced channels leave d_power untouched and move only n
+    run = Run(T, nch, nco, nfr)
+    run.power.fill_(0x5A)
+    model = M.FT8Model(nch, *_tables())
+    model.power[:] = 0x5A
+    run.rx.ft8_sync([0, 1, 0, 1])
+    model.sync([0, 1, 0, 1])
+    _, st = _stream(run, I, Q, (nfr,), model)
+    _same_as_model(run, model)
+    p = run.power.cpu().numpy()
+    words = run.rx.ft8_state().view(np.int32)[8:].reshape(nch, M.WORDS)
+    for c in (0, 2):
+        assert (p[c] == 0x5A).all() and not st[c].any() and words[c, M.S_N] == nfr and not words[c, 1:].any()
+    assert (st[1, -1] == [2, 1, 0, 1]).all() and (p[1, 0, :2 * M.BLOCK_BYTES] != 0x5A).any()
+    with pytest.raises(ValueError):
+        run.rx.ft8_sync([1, 1])
+
+    def refused(status, words, fn, *args):
+        with pytest.raises(T.T41RxError) as e:
+            fn(*args)
+        assert e.value.status == status and words in str(e.value), str(e.value)
+
+    lib = _lib.load()
+    win, mag = _tables()
+    vp = lambda x: x.ctypes.data_as(C.c_void_p)  # noqa: E731
+    rx = T.RxChain(nch, T.default_params(mode=0), NCOFreq=nco)
+    power = torch.zeros(nch, 2, M.HALF_BYTES, dtype=torch.uint8, device="cuda")
+    status = torch.zeros(nch, 1380, 4, dtype=torch.int32, device="cuda")
+    pp, sp = C.c_void_p(power.data_ptr()), C.c_void_p(status.data_ptr())
+    ck = _lib.check
+    refused(_lib.ERR_ARG, "no tables", lambda: ck(lib.t41rx_set_ft8(rx._ctx, 1, pp, sp, 16)))
+    refused(_lib.ERR_ARG, "null", lambda: ck(lib.t41rx_set_ft8_tables(rx._ctx, None, vp(mag))))
+    refused(_lib.ERR_ARG, "null", lambda: ck(lib.t41rx_set_ft8_tables(rx._ctx, vp(win), None)))
+    bad = win.copy()
+    bad[100] = np.inf
+    refused(_lib.ERR_ARG, "window: non-finite", rx.set_ft8_tables, bad, mag)
+    bad = mag.copy()
+    bad[16384] = np.nan
+    refused(_lib.ERR_ARG, "mag_db table: non-finite", rx.set_ft8_tables, win, bad)
+    refused(_lib.ERR_ARG, "no tables", lambda: ck(lib.t41rx_set_ft8(rx._ctx, 1, pp, sp, 16)))  # (a refused table loads nothing)
+    rx.set_ft8_tables(win, mag)
+    refused(_lib.ERR_ARG, "NULL", lambda: ck(lib.t41rx_set_ft8(rx._ctx, 1, None, sp, 16)))
+    refused(_lib.ERR_ARG, "NULL", lambda: ck(lib.t41rx_set_ft8(rx._ctx, 1, pp, None, 16)))
+    refused(_lib.ERR_ARG, "<= 1380", lambda: ck(lib.t41rx_set_ft8(rx._ctx, 1, pp, sp, 1381)))
+    refused(_lib.ERR_ARG, "max_frames must be > 0", lambda: ck(lib.t41rx_set_ft8(rx._ctx, 1, pp, sp, 0)))
+    refused(_lib.ERR_ARG, "0 or 1", lambda: ck(lib.t41rx_set_ft8(rx._ctx, 2, pp, sp, 16)))
+    assert rx.ft8 == 0
+    ck(lib.t41rx_set_ft8(rx._ctx, 1, pp, sp, 1380))
+    assert rx.ft8 == 1
+    ck(lib.t41rx_set_ft8(rx._ctx, 1, pp, sp, 16))
+    refused(_lib.ERR_ARG, "num must be >= 0 and den > 0", rx.set_ft8_clock, 0, 32, 0)
+    refused(_lib.ERR_ARG, "num must be >= 0 and den > 0", rx.set_ft8_clock, 0, -1, 3)
+    dI, dQ = torch.from_numpy(np.array(I[:, :17 * L])).cuda(), torch.from_numpy(np.array(Q[:, :17 * L])).cuda()
+    refused(_lib.ERR_ARG, "FT8 status buffer", rx.ProcessIQData, dI, dQ)
+    rx.CalcFilters(mode=1, FLoCut=-3000, FHiCut=-200)  # LSB
+    refused(_lib.ERR_UNSUPPORTED, "demodulates DEMOD_FT8 as USB", rx.ProcessIQData, dI[:, :L].contiguous(), dQ[:, :L].contiguous())
+    assert not rx.ft8_state().view(np.int32)[8:].any()  # a refused call moves nothing
+    rx.CalcFilters(mode=0, FLoCut=200, FHiCut=3000)
+    rx.ProcessIQData(dI[:, :L].contiguous(), dQ[:, :L].contiguous())
+    torch.cuda.synchronize()
+    long = T.RxChain(nch, T.default_params(mode=0, fft_length=1024))
+    long.set_ft8_tables(win, mag)
+    refused(_lib.ERR_UNSUPPORTED, "fft_length 512", lambda: ck(lib.t41rx_set_ft8(long._ctx, 1, pp, sp, 16)))
+    # the record's refusals: nothing is written
+    good = _prepared(nch)
+    rx.set_ft8_state(good)
+
+    def broken(ch, word, value):
+        r = good.copy()
+        r.view(np.int32)[8 + ch * M.WORDS + word] = value
+        return r
+
+    for ch, word, value, why in ((1, M.S_DATALOOP, 15, "dataLoop"), (0, M.S_DATALOOP, -1, "dataLoop"), (2, M.S_LEFTOVER, 4, "leftover"),
+                                 (0, M.S_COUNTER, 92, "FT_8_counter"), (1, M.S_COUNTER, 93, "FT_8_counter"), (3, M.S_COUNTER, -1, "FT_8_counter"),
+                                 (0, M.S_SYNC, 2, "flag"), (1, M.S_FT8FLAG, -1, "flag"), (2, M.S_DSPFLAG, 2, "flag"), (3, M.S_HALF, 2, "flag"),
+                                 (0, 12, 1, "reserved"), (3, M.SCALARS + 3071, 32768, "q15"), (2, M.SCALARS, -32769, "q15")):
+        refused(_lib.ERR_STATE, why, rx.set_ft8_state, broken(ch, word, value))
+    hdr = good.copy()
+    hdr.view(np.int32)[0] = 0x54343153  # the path checkpoint's magic
+    refused(_lib.ERR_STATE, "header", rx.set_ft8_state, hdr)
+    refused(_lib.ERR_STATE, "size", rx.set_ft8_state, good[:-4])
+    assert np.array_equal(rx.ft8_state(), good)
+    rx.set_ft8(0)
+    assert rx.ft8 == 0
+    with pytest.raises(ValueError):
+        rx.ft8_status(1)
