@@ -489,8 +489,9 @@ T41RX_API int t41rx_calibrate_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, co
  * In DEMOD_FT8 the firmware demodulates as USB and, on float_buffer_L as the demodulator and the AGC leave it (in front of
  * the equalizer: the position of the demod tap), resamples to 6.4 kS/s into the rolling q15 buffer ft8_dsp_buffer[3072];
  * every 15 frames process_FT8_FFT() turns it into four rows of 368 bytes of export_fft_power, and 92 such blocks per 15 s
- * slot are the waterfall ft8_decode() searches.  Here FT8 is a switch on a USB context, not a mode of its own; find_sync(),
- * ft8_decode() and the RTC stay with the caller.  Per channel and frame, in the firmware's order:
+ * slot are the waterfall ft8_decode() searches.  Here FT8 is a switch on a USB context, not a mode of its own; find_sync()
+ * and ft8_decode() up to the CRC check are t41rx_ft8_decode_*() below, on the finished half; the RTC, the unpacking of the
+ * 77 payload bits into text and the decoded[] log stay with the caller.  Per channel and frame, in the firmware's order:
  *   while syncFlag: arm_float_to_q15 (truncating, saturating) and the 68-iteration collector loop as written -- words
  *     1020..1023 and 2044..2047 are never rolled, with leftover >= 1 iteration i rolls the sample iteration i - leftover of
  *     the same frame has just written, the `leftover` cell behind frames 3 / 7 / 11 is rolled by the next frame --
@@ -546,6 +547,72 @@ T41RX_API int t41rx_ft8_sync(t41rx_ctx *ctx, const uint8_t *channels, int n);
 T41RX_API size_t t41rx_ft8_state_bytes(const t41rx_ctx *ctx);
 T41RX_API int t41rx_ft8_get_state(t41rx_ctx *ctx, void *host_buf, size_t bytes);
 T41RX_API int t41rx_ft8_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes);
+
+/* ---- FT8 decode of a finished slot (ft8.cpp:270-616, 669-703, 727-790) ----
+ * find_sync(), and for every candidate of its heap extract_likelihood(), bp_decode(), pack_bits() and the CRC check, on a
+ * waterfall that stays on the device: [92 blocks][4 = 2 * time_sub + freq_sub][368 bins] uint8 per channel and slot, the
+ * layout t41rx_set_ft8()'s d_power has per half.  In the firmware's order and arithmetic:
+ *   find_sync(): alt 0..3, time_offset -7..19, freq_offset 48..359 (ft8_min_bin .. 368 - 9); the score is the sum of
+ *     8 * p8[kCostas_map[k]] - (p8[0] + .. + p8[7]) over the Costas symbols (at 0, 36, 72) that fall inside blocks 0..91,
+ *     divided by their number as C divides (toward zero); score < min_score skips; the min-heap is replayed as written
+ *     (eviction only on score > heap[0].score, heap[0] = heap[last] and heapify_down, insertion and heapify_up with >=).
+ *     The candidates come out as the heap ARRAY in array order, the order ft8_decode() walks: not sorted, and which of
+ *     several equal-minimum candidates survives follows from the replay.
+ *   extract_likelihood(): max4 differences of the symbol's eight bins through kGray_map; variance = (sum2 - sum * sum *
+ *     inv_n) * inv_n and norm_factor = sqrtf(16.0f / variance) in f32, one rounding per operation.  A variance of 0 gives
+ *     inf and 0 * inf = NaN, a negative one NaN: NaN is carried as IEEE does, `zn > 0` is false, plain is all zero, and the
+ *     all-zero codeword passes ldpc_check() and the CRC -- as in the firmware.
+ *   bp_decode(): f32 in source order, no contraction, IEEE division; plain is the hard decision of the last iteration
+ *     begun; n_errors = min_errors.  Then pack_bits(plain, 91) and crc() (CRC-14, polynomial 0x2757) over 82 bits of the
+ *     masked copy.
+ * t41rx_ft8_candidate: the Candidate as find_sync() leaves it, then n_errors, iterations = the index of the iteration whose
+ *   check found 0 errors, else ldpc_iterations, flags bit 0: n_errors == 0, bit 1: the CRC matches (looked at only with bit
+ *   0), a91 = pack_bits(plain, 91) with the CRC bits in place when bit 0 is set, else 0.  flags == 3 is what ft8_decode()
+ *   hands to unpack77_fields(); freq_hz = (freq_offset + freq_sub / 2.0f) * 6.25f.
+ * t41rx_ft8_result: num_candidates = find_sync()'s return, num_valid = the records with flags == 3, select as given;
+ *   records from num_candidates on are zero.
+ * t41rx_set_ft8_decode_tables(): kCostas_map[7], kGray_map[8], kNm[83][7], kMn[174][3], kNrw[83] from ft8_constants.cpp
+ *   (host arrays, copied; synchronises).  The library has no table of its own.  T41RX_ERR_ARG, nothing written, for NULL,
+ *   a kCostas_map or kGray_map entry above 7, kNrw outside 1..7, kNm[i][j < kNrw[i]] outside 1..174, kMn outside 1..83, or
+ *   a bit i and j for which check kMn[i][j] does not list bit i exactly once (and the converse): these keep the kernels'
+ *   indexing inside their arrays.
+ * t41rx_set_ft8_decode(): kMax_candidates 1..20, kMin_score, kLDPC_iterations 1..50; defaults 20, 40, 10 (ft8.cpp:64-72).
+ *   T41RX_ERR_ARG outside.  t41rx_get_ft8_decode() reads them back (any pointer may be NULL).
+ * t41rx_set_ft8_decode_debug(): device pointers or NULL (the default).  While set, every decode call writes
+ *   d_log174 [n_channels][20][174] f32, extract_likelihood()'s output, and d_plain [n_channels][20][174] uint8, bp_decode()'s;
+ *   rows of unused candidates are zero.
+ * t41rx_ft8_decode_device(): channel c reads d_waterfall + c * channel_stride_bytes + select[c] * T41RX_FT8_SLOT_BYTES,
+ *   select[c] in {-1 = skip, 0, 1}; select is a host array of n == n_channels entries (copied before the call returns), or
+ *   NULL for all 0.  d_waterfall == NULL: the context's own d_power (t41rx_set_ft8) with its stride of two slots, select
+ *   naming the half (d_status word 2 - 1).  A skipped channel's result is zero with select = -1.  Enqueued on hip_stream,
+ *   no sync; calls on one context belong on one stream.  It reads the waterfall and the tables and touches no state of the
+ *   receive path.  T41RX_ERR_ARG, before anything is launched, for: no tables loaded, n != n_channels, a NULL d_results, a
+ *   select entry outside {-1, 0, 1}, a NULL d_waterfall while FT8 receive is off, a waterfall or stride that is not
+ *   4-byte aligned, a stride smaller than what the call reads.
+ * t41rx_ft8_decode_host(): the same on the default stream, with the results copied to a host array; synchronises. */
+#define T41RX_FT8_MAX_CANDIDATES 20 /* kMax_candidates */
+#define T41RX_FT8_SLOT_BYTES 135424 /* 92 * 1472 */
+typedef struct {
+  int16_t score, time_offset, freq_offset;
+  uint8_t time_sub, freq_sub;
+  int16_t n_errors;
+  uint8_t iterations, flags;
+  uint8_t a91[12];
+  uint8_t reserved[8];
+} t41rx_ft8_candidate; /* 32 bytes */
+typedef struct {
+  int32_t num_candidates, num_valid, select, reserved;
+  t41rx_ft8_candidate cand[T41RX_FT8_MAX_CANDIDATES];
+} t41rx_ft8_result; /* 656 bytes */
+T41RX_API int t41rx_set_ft8_decode_tables(t41rx_ctx *ctx, const uint8_t *costas, const uint8_t *gray, const uint8_t *nm,
+                                const uint8_t *mn, const uint8_t *nrw);
+T41RX_API int t41rx_set_ft8_decode(t41rx_ctx *ctx, int max_candidates, int min_score, int ldpc_iterations);
+T41RX_API int t41rx_get_ft8_decode(const t41rx_ctx *ctx, int *max_candidates, int *min_score, int *ldpc_iterations);
+T41RX_API int t41rx_set_ft8_decode_debug(t41rx_ctx *ctx, float *d_log174, uint8_t *d_plain);
+T41RX_API int t41rx_ft8_decode_device(t41rx_ctx *ctx, const uint8_t *d_waterfall, size_t channel_stride_bytes, const int8_t *select,
+                            int n, t41rx_ft8_result *d_results, void *hip_stream);
+T41RX_API int t41rx_ft8_decode_host(t41rx_ctx *ctx, const uint8_t *d_waterfall, size_t channel_stride_bytes, const int8_t *select,
+                          int n, t41rx_ft8_result *results);
 
 #ifdef __cplusplus
 }

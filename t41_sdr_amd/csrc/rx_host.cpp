@@ -25,6 +25,8 @@
 #include "eq_kernel.hip"  // the receive equalizer's kernel and launcher
 #include "ft8_kernels.hpp"
 #include "ft8_kernel.hip"  // the FT8 receive stage's kernels and launchers
+#include "ft8_decode_kernels.hpp"
+#include "ft8_decode_kernel.hip"  // the FT8 decode's kernels and launcher
 #include "last_error.hpp"
 #include "nb_kernels.hpp"
 #include "nb_kernel.hip"  // the noise blanker's kernel and launcher
@@ -123,6 +125,20 @@ struct t41rx_ctx {
   DevBuf<float> d_ft8_win, d_ft8_mag, d_ft8_tap;
   DevBuf<uint32_t> d_ft8_tab;
   int ft8_tap_frames = 0;
+  // FT8 decode of a finished slot (ft8.cpp:270-616, 669-703, 727-790; t41rx_set_ft8_decode_tables / _ft8_decode /
+  // _ft8_decode_debug, t41rx_ft8_decode_device / _host): the caller's kCostas_map, kGray_map, kNm, kMn, kNrw as validated
+  // (device copy, with the positions worked out from them), kMax_candidates / kMin_score / kLDPC_iterations, the stage taps,
+  // and the call's `select` on its way to the device: a pinned copy, an event behind its upload (the next call waits for
+  // it before it overwrites the copy), the device array.  The decode reads the waterfall and the tables and touches no state.
+  bool ft8d_have_tables = false;
+  int ft8d_max_candidates = T41RX_FT8_MAX_CANDIDATES, ft8d_min_score = 40, ft8d_iterations = 10;
+  float *ft8d_dbg_log174 = nullptr;
+  uint8_t *ft8d_dbg_plain = nullptr;
+  DevBuf<Ft8DecodeTables> d_ft8d_tab;
+  DevBuf<int8_t> d_ft8d_sel;
+  DevBuf<t41rx_ft8_result> d_ft8d_res;  // staging for t41rx_ft8_decode_host
+  int8_t *h_ft8d_sel = nullptr;         // pinned
+  hipEvent_t ft8d_sel_ev = nullptr;
   // staging for t41rx_process_host
   DevBuf<float> d_in_i, d_in_q, d_out;
   size_t staging_floats = 0;
@@ -1196,6 +1212,8 @@ int t41rx_destroy(t41rx_ctx *ctx) {
     std::fprintf(stderr, "pipe_stat chain_cycles %llu chains %llu slow_blocks %llu back_wait %llu duty_wait %llu blocks %llu chain_stage %llu chain_steps %llu front %llu prep %llu back %llu wave_iterations %llu chain_state_wait %llu\n",
                  c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9], c[10], c[11], c[12]);
   }
+  if (ctx->ft8d_sel_ev) (void)hipEventDestroy(ctx->ft8d_sel_ev);
+  if (ctx->h_ft8d_sel) (void)hipHostFree(ctx->h_ft8d_sel);
   delete ctx;  // (its device buffers go here, on its device)
   return T41RX_OK;
 }
@@ -1541,6 +1559,161 @@ int t41rx_ft8_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes) {
   HIP_TRY(hipDeviceSynchronize());
   if (const int rc = ensure_ft8(ctx)) return rc;
   HIP_TRY(hipMemcpy(ctx->d_ft8.get(), all, bytes - kFt8HeaderBytes, hipMemcpyHostToDevice));
+  return T41RX_OK;
+}
+
+// ---- FT8 decode of a finished slot ----
+int t41rx_set_ft8_decode_tables(t41rx_ctx *ctx, const uint8_t *costas, const uint8_t *gray, const uint8_t *nm, const uint8_t *mn,
+                                const uint8_t *nrw) {
+  if (!ctx || !costas || !gray || !nm || !mn || !nrw) return fail(T41RX_ERR_ARG, "null argument");
+  // what the kernels index with: everything is checked before anything is written
+  Ft8DecodeTables h{};
+  for (int k = 0; k < 7; ++k) {
+    if (costas[k] > 7) return fail(T41RX_ERR_ARG, "FT8 decode tables: kCostas_map entry outside 0..7");
+    h.costas[k] = costas[k];
+  }
+  for (int k = 0; k < 8; ++k) {
+    if (gray[k] > 7) return fail(T41RX_ERR_ARG, "FT8 decode tables: kGray_map entry outside 0..7");
+    h.gray[k] = gray[k];
+  }
+  for (int c = 0; c < kLdpcM; ++c) {
+    if (nrw[c] < 1 || nrw[c] > 7) return fail(T41RX_ERR_ARG, "FT8 decode tables: kNrw entry outside 1..7");
+    h.nrw[c] = nrw[c];
+    for (int k = 0; k < nrw[c]; ++k) {
+      if (nm[c * 7 + k] < 1 || nm[c * 7 + k] > kLdpcN) return fail(T41RX_ERR_ARG, "FT8 decode tables: kNm entry outside 1..174");
+      h.nm[c * 7 + k] = (uint8_t)(nm[c * 7 + k] - 1);
+    }
+  }
+  for (int p = 0; p < kFt8BitChecks; ++p) {
+    if (mn[p] < 1 || mn[p] > kLdpcM) return fail(T41RX_ERR_ARG, "FT8 decode tables: kMn entry outside 1..83");
+    h.mn[p] = (uint8_t)(mn[p] - 1);
+  }
+  for (int i = 0; i < kLdpcN; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const int c = h.mn[3 * i + j];
+      int at = -1, count = 0;
+      for (int k = 0; k < h.nrw[c]; ++k)
+        if (h.nm[c * 7 + k] == i) {
+          at = k;
+          ++count;
+        }
+      if (count != 1) return fail(T41RX_ERR_ARG, "FT8 decode tables: a check of kMn does not list its bit exactly once in kNm");
+      h.pos[3 * i + j] = (uint8_t)at;
+    }
+  // the other way round (bp_decode()'s `kMn[ibj][kk] - 1 == i`): every entry of a check is one of its bit's three checks, once
+  for (int c = 0; c < kLdpcM; ++c)
+    for (int k = 0; k < h.nrw[c]; ++k) {
+      const int b = h.nm[c * 7 + k];
+      int at = -1, count = 0;
+      for (int j = 0; j < 3; ++j)
+        if (h.mn[3 * b + j] == c) {
+          at = j;
+          ++count;
+        }
+      if (count != 1) return fail(T41RX_ERR_ARG, "FT8 decode tables: a bit of kNm does not list its check exactly once in kMn");
+      h.kk[c * 7 + k] = (uint8_t)at;
+    }
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  HIP_TRY(hipDeviceSynchronize());  // (a launch still in flight reads the old tables)
+  if (!ctx->d_ft8d_tab) HIP_TRY(dev_alloc(ctx->d_ft8d_tab, sizeof(Ft8DecodeTables)));
+  HIP_TRY(hipMemcpy(ctx->d_ft8d_tab.get(), &h, sizeof(h), hipMemcpyHostToDevice));
+  ctx->ft8d_have_tables = true;
+  return T41RX_OK;
+}
+
+int t41rx_set_ft8_decode(t41rx_ctx *ctx, int max_candidates, int min_score, int ldpc_iterations) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (max_candidates < 1 || max_candidates > T41RX_FT8_MAX_CANDIDATES) return fail(T41RX_ERR_ARG, "FT8 decode: max_candidates must be 1..20");
+  if (ldpc_iterations < 1 || ldpc_iterations > 50) return fail(T41RX_ERR_ARG, "FT8 decode: ldpc_iterations must be 1..50");
+  ctx->ft8d_max_candidates = max_candidates;
+  ctx->ft8d_min_score = min_score;
+  ctx->ft8d_iterations = ldpc_iterations;
+  return T41RX_OK;
+}
+
+int t41rx_get_ft8_decode(const t41rx_ctx *ctx, int *max_candidates, int *min_score, int *ldpc_iterations) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (max_candidates) *max_candidates = ctx->ft8d_max_candidates;
+  if (min_score) *min_score = ctx->ft8d_min_score;
+  if (ldpc_iterations) *ldpc_iterations = ctx->ft8d_iterations;
+  return T41RX_OK;
+}
+
+int t41rx_set_ft8_decode_debug(t41rx_ctx *ctx, float *d_log174, uint8_t *d_plain) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  ctx->ft8d_dbg_log174 = d_log174;
+  ctx->ft8d_dbg_plain = d_plain;
+  return T41RX_OK;
+}
+
+int t41rx_ft8_decode_device(t41rx_ctx *ctx, const uint8_t *d_waterfall, size_t channel_stride_bytes, const int8_t *select, int n,
+                            t41rx_ft8_result *d_results, void *hip_stream) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (!d_results) return fail(T41RX_ERR_ARG, "FT8 decode: no result buffer (d_results is NULL)");
+  if (!ctx->ft8d_have_tables) return fail(T41RX_ERR_ARG, "FT8 decode: no tables loaded (t41rx_set_ft8_decode_tables)");
+  if (n != ctx->nchan) return fail(T41RX_ERR_ARG, "FT8 decode: n must equal n_channels");
+  bool slot1 = false;
+  if (select)
+    for (int c = 0; c < n; ++c) {
+      if (select[c] < -1 || select[c] > 1) return fail(T41RX_ERR_ARG, "FT8 decode: select must be -1 (skip), 0 or 1");
+      slot1 = slot1 || select[c] == 1;
+    }
+  if (!d_waterfall) {
+    if (!ctx->ft8_on) return fail(T41RX_ERR_ARG, "FT8 decode: d_waterfall is NULL and FT8 receive is off (no d_power to read)");
+    d_waterfall = ctx->ft8_power;
+    channel_stride_bytes = 2 * (size_t)kFt8HalfBytes;
+  }
+  if ((reinterpret_cast<uintptr_t>(d_waterfall) & 3u) || (channel_stride_bytes & 3u))
+    return fail(T41RX_ERR_ARG, "FT8 decode: the waterfall and its channel stride must be 4-byte aligned");
+  if (n > 1 && channel_stride_bytes < (size_t)kFt8HalfBytes * (slot1 ? 2 : 1))
+    return fail(T41RX_ERR_ARG, "FT8 decode: channel_stride_bytes is smaller than the slots the call reads");
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  const hipStream_t s = (hipStream_t)hip_stream;
+  if (select) {
+    if (!ctx->d_ft8d_sel) {
+      HIP_TRY(dev_alloc(ctx->d_ft8d_sel, (size_t)n));
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ctx->h_ft8d_sel), (size_t)n, hipHostMallocDefault));
+      HIP_TRY(hipEventCreateWithFlags(&ctx->ft8d_sel_ev, hipEventDisableTiming));
+    } else {
+      HIP_TRY(hipEventSynchronize(ctx->ft8d_sel_ev));  // the upload of the call before has read the pinned copy
+    }
+    std::memcpy(ctx->h_ft8d_sel, select, (size_t)n);
+    HIP_TRY(hipMemcpyAsync(ctx->d_ft8d_sel.get(), ctx->h_ft8d_sel, (size_t)n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(ctx->ft8d_sel_ev, s));
+  }
+  const size_t taps = (size_t)n * T41RX_FT8_MAX_CANDIDATES * kLdpcN;
+  if (ctx->ft8d_dbg_log174) HIP_TRY(hipMemsetAsync(ctx->ft8d_dbg_log174, 0, taps * sizeof(float), s));  // unused rows read zero
+  if (ctx->ft8d_dbg_plain) HIP_TRY(hipMemsetAsync(ctx->ft8d_dbg_plain, 0, taps, s));
+  Ft8DecodeArgs a{};
+  a.waterfall = d_waterfall;
+  a.stride = channel_stride_bytes;
+  a.select = select ? ctx->d_ft8d_sel.get() : nullptr;
+  a.tab = ctx->d_ft8d_tab.get();
+  a.results = d_results;
+  a.dbg_log174 = ctx->ft8d_dbg_log174;
+  a.dbg_plain = ctx->ft8d_dbg_plain;
+  a.nchan = n;
+  a.max_candidates = ctx->ft8d_max_candidates;
+  a.min_score = ctx->ft8d_min_score;
+  a.iterations = ctx->ft8d_iterations;
+  const hipError_t e = launch_ft8_decode(a, s);
+  if (e != hipSuccess) return hip_fail(e, "FT8 decode kernel launch");
+  return T41RX_OK;
+}
+
+int t41rx_ft8_decode_host(t41rx_ctx *ctx, const uint8_t *d_waterfall, size_t channel_stride_bytes, const int8_t *select, int n,
+                          t41rx_ft8_result *results) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (!results) return fail(T41RX_ERR_ARG, "FT8 decode: no result buffer (results is NULL)");
+  if (n != ctx->nchan) return fail(T41RX_ERR_ARG, "FT8 decode: n must equal n_channels");
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  if (!ctx->d_ft8d_res) HIP_TRY(dev_alloc(ctx->d_ft8d_res, sizeof(t41rx_ft8_result) * (size_t)n));
+  if (const int rc = t41rx_ft8_decode_device(ctx, d_waterfall, channel_stride_bytes, select, n, ctx->d_ft8d_res.get(), nullptr)) return rc;
+  HIP_TRY(hipMemcpy(results, ctx->d_ft8d_res.get(), sizeof(t41rx_ft8_result) * (size_t)n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipStreamSynchronize(nullptr));
   return T41RX_OK;
 }
 

@@ -389,6 +389,80 @@ class RxChain:
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         check(self._lib.t41rx_ft8_set_state(self._ctx, buf.ctypes.data_as(C.c_void_p), buf.size))
 
+    def set_ft8_decode_tables(self, costas, gray, nm, mn, nrw):
+        """The FT8 decode's tables (t41rx_set_ft8_decode_tables): kCostas_map[7], kGray_map[8], kNm[83][7], kMn[174][3] and
+        kNrw[83] of ft8_constants.cpp as uint8.  The library has no table of its own, and refuses tables that would take
+        the kernels' indexing outside their arrays."""
+        arrs = []
+        for a, shape, what in ((costas, (7,), "costas"), (gray, (8,), "gray"), (nm, (83, 7), "nm"), (mn, (174, 3), "mn"), (nrw, (83,), "nrw")):
+            a = np.asarray(a)
+            if a.shape != shape:
+                raise ValueError("%s must have shape %r, got %r" % (what, shape, a.shape))
+            if a.min() < 0 or a.max() > 255:
+                raise ValueError("%s does not fit uint8" % what)
+            arrs.append(np.ascontiguousarray(a, dtype=np.uint8))
+        check(self._lib.t41rx_set_ft8_decode_tables(self._ctx, *[a.ctypes.data_as(C.c_void_p) for a in arrs]))
+
+    def set_ft8_decode(self, max_candidates=20, min_score=40, ldpc_iterations=10):
+        """kMax_candidates (1..20), kMin_score and kLDPC_iterations (1..50) of the decode (t41rx_set_ft8_decode); the
+        defaults are the firmware's (ft8.cpp:64-72)."""
+        check(self._lib.t41rx_set_ft8_decode(self._ctx, int(max_candidates), int(min_score), int(ldpc_iterations)))
+
+    @property
+    def ft8_decode_params(self):
+        """(max_candidates, min_score, ldpc_iterations)"""
+        v = [C.c_int(), C.c_int(), C.c_int()]
+        check(self._lib.t41rx_get_ft8_decode(self._ctx, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def ft8_decode(self, select=None, waterfall=None, debug=False):
+        """find_sync() and, per candidate, extract_likelihood(), bp_decode(), pack_bits() and the CRC check on finished slots
+        (t41rx_ft8_decode_device, on the current torch stream; synchronises to hand the records back).  Channel c reads
+        slot select[c] (-1 = skip, 0, 1; None = all 0) of its row of `waterfall`, a uint8 CUDA tensor [n_channels, bytes
+        per channel] whose rows hold one or two slots of 92 * 1472 bytes; waterfall None reads the context's own
+        export_fft_power (set_ft8), where select names the half a status word reported complete.  Returns a numpy array
+        [n_channels] of dtype t41_sdr_amd.ft8.RESULT (ft8.messages() turns it into text); with debug also the stage taps
+        log174 [n_channels, 20, 174] f32 and plain [n_channels, 20, 174] uint8."""
+        import torch
+        from . import ft8 as F
+        n = self.n_channels
+        dev = "cuda:%d" % self.device
+        sel = None
+        if select is not None:
+            sel = np.asarray(select)
+            if sel.shape != (n,):
+                raise ValueError("select must have n_channels = %d entries, got %r" % (n, sel.shape))
+            if ((sel < -128) | (sel > 127)).any():
+                raise ValueError("select does not fit int8")
+            sel = np.ascontiguousarray(sel, dtype=np.int8)
+        ptr, stride = None, 0
+        if waterfall is not None:
+            if not (isinstance(waterfall, torch.Tensor) and waterfall.is_cuda and waterfall.dtype == torch.uint8 and waterfall.dim() == 2
+                    and waterfall.shape[0] == n and waterfall.stride(1) == 1):
+                raise ValueError("waterfall must be a uint8 CUDA tensor [n_channels, bytes per channel] with unit inner stride")
+            need = F.SLOT_BYTES * (2 if sel is not None and (sel == 1).any() else 1)
+            if waterfall.shape[1] < need:
+                raise ValueError("waterfall rows hold %d bytes, the call reads %d" % (waterfall.shape[1], need))
+            ptr, stride = C.c_void_p(waterfall.data_ptr()), int(waterfall.stride(0)) if n > 1 else int(waterfall.shape[1])
+        res = torch.zeros(n, F.RESULT.itemsize, dtype=torch.uint8, device=dev)
+        taps = None
+        if debug:
+            taps = (torch.zeros(n, F.MAX_CANDIDATES, 174, dtype=torch.float32, device=dev),
+                    torch.zeros(n, F.MAX_CANDIDATES, 174, dtype=torch.uint8, device=dev))
+            check(self._lib.t41rx_set_ft8_decode_debug(self._ctx, C.c_void_p(taps[0].data_ptr()), C.c_void_p(taps[1].data_ptr())))
+        try:
+            stream = torch.cuda.current_stream(res.device).cuda_stream
+            check(self._lib.t41rx_ft8_decode_device(self._ctx, ptr, stride, None if sel is None else sel.ctypes.data_as(C.c_void_p), n,
+                                                    C.c_void_p(res.data_ptr()), C.c_void_p(stream)))
+            out = res.cpu().numpy().view(F.RESULT).reshape(n)
+            if debug:
+                return out, taps[0].cpu().numpy(), taps[1].cpu().numpy()
+            return out
+        finally:
+            if debug:
+                torch.cuda.synchronize(res.device)
+                check(self._lib.t41rx_set_ft8_decode_debug(self._ctx, None, None))
+
     def get_state(self):
         n = self._lib.t41rx_state_bytes(self._ctx)
         buf = np.zeros(n, dtype=np.uint8)
