@@ -16,6 +16,10 @@
 // hands each a pipe end for the 128-byte ncclUniqueId rank 0 creates, waits, and fails if any rank fails.  Rank r uses
 // HIP device r.  Rank 0 prints one JSON line.  Each rank also checks the broadcast path against the direct one: a second
 // context designed locally for the new edges must produce bit-identical audio.
+//
+// Receiver groups (t41rx_set_input_map: many channels reading one shared I/Q stream) do not change this picture: the
+// sharding stays per channel, and a rank whose channels read shared streams would hold its own copy of those streams and
+// a map into it.  Nothing here sets a map; streams are not sharded (t41_sdr_amd/dist.py likewise).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 #include <sys/wait.h>

@@ -311,9 +311,33 @@ T41RX_API int t41rx_frame_len(const t41rx_ctx *ctx);
 T41RX_API int t41rx_set_buffer_layout(t41rx_ctx *ctx, int layout);
 T41RX_API int t41rx_get_buffer_layout(const t41rx_ctx *ctx);
 
+/* ---- receiver groups: many channels on one shared I/Q stream (ABI 5) ----
+ * One radio delivers one 192 kS/s stream and the channels of a context are the receivers tuned across it (NCOFreq per
+ * channel, t41rx_set_nco_freq).  With an input map set, channel c reads row stream_of_channel[c] of I / Q, and I / Q
+ * (Q_in_R / Q_in_L) of every process call hold n_streams rows instead of n_channels:
+ *   channel-major  in  [n_streams][n_frames * frame_len]      out [n_channels][n_frames * frame_len]
+ *   time-major     in  [n_frames][n_streams][frame_len]       out [n_frames][n_channels][frame_len]
+ * so input and output differ in their channel strides and, time-major, in their frame strides too.  The audio, every side
+ * output, every stage tap and every stage behind the demodulator keep their [n_channels]... shapes.  Addresses only: a
+ * mapped call computes, bit for bit, what the same call computes without a map on inputs replicated as
+ * I_rep[c] = I[stream_of_channel[c]].  Streams have no state; all state stays per channel: t41rx_state_bytes() and every
+ * checkpoint are what they are without a map.  The map is configuration, like the buffer layout: it is in no checkpoint
+ * and survives t41rx_reset, t41rx_set_state, t41rx_set_params and t41rx_set_coeffs.
+ * t41rx_set_input_map(): stream_of_channel is a host array of n == n_channels entries, each in [0, n_streams), with
+ *   1 <= n_streams <= n_channels; rows may repeat, go unused, and come in any order.  NULL with n_streams == 0 switches
+ *   the map off: one row per channel again.  Everything is checked on the host before anything changes: any violation
+ *   returns T41RX_ERR_ARG with a t41rx_last_error() text and leaves the previous map as it was.  Synchronises the device,
+ *   then uploads (the ordering rule of t41rx_set_nco_freq): the map holds from the next process call on.
+ * t41rx_get_input_map(): returns n_streams, or 0 with the map off (negative: an error status).  stream_of_channel_out,
+ *   n == n_channels entries, receives the map when one is set; it may be NULL when only the count is wanted.
+ * The host-pointer process forms allocate and copy in n_streams rows.  The calibration calls (t41rx_calibrate_*) keep
+ * their own shared_input and ignore the map. */
+T41RX_API int t41rx_set_input_map(t41rx_ctx *ctx, const int32_t *stream_of_channel, int n, int n_streams);
+T41RX_API int t41rx_get_input_map(const t41rx_ctx *ctx, int32_t *stream_of_channel_out, int n);
+
 /* ---- the hot path: ProcessIQData() on every channel ----
  * Device-pointer form: dI, dQ, dAudio are device pointers ([n_channels][n_frames*frame_len], or time-major:
- * t41rx_set_buffer_layout);
+ * t41rx_set_buffer_layout; with an input map dI / dQ hold n_streams rows: t41rx_set_input_map);
  * the kernel is enqueued on `hip_stream` (a hipStream_t, may be NULL = default stream) and the
  * call returns without synchronising. */
 T41RX_API int t41rx_process_device(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio,
@@ -330,7 +354,7 @@ T41RX_API int t41rx_process_host(t41rx_ctx *ctx, const float *I, const float *Q,
  *   arm_float_to_q15(float_buffer_L, q15_buffer_LTemp, 2048); Q_out_L.play(...)    Process.cpp:936-937
  * with CMSIS-DSP's conversions (x / 32768; truncating, saturating (q15_t)__SSAT((q31_t)(x * 32768), 16)).
  * Layout [n_channels][n_frames*frame_len] int16, the 16 blocks of 128 of a frame back to back (or time-major,
- * t41rx_set_buffer_layout).  The side outputs and stage taps work here as on the f32 entry points (ABI 5): the
+ * t41rx_set_buffer_layout; with an input map the two input queues hold n_streams rows, t41rx_set_input_map).  The side outputs and stage taps work here as on the f32 entry points (ABI 5): the
  * reference computes its display FFT and audio spectrum inside every ProcessIQData() call on exactly these q15-fed
  * buffers (Process.cpp:107-108 -> :184-186, :211-215, :550-570). */
 T41RX_API int t41rx_process_device_q15(t41rx_ctx *ctx, const int16_t *dQ_in_L, const int16_t *dQ_in_R,
@@ -459,7 +483,8 @@ T41RX_API int t41rx_set_display_spectrum(t41rx_ctx *ctx, float *d_spec, float *d
  *   [n_channels][n_frames][512] f32 (pixelnew and FFT_spec) may be NULL; their rows are written for update frames only,
  *   other rows are left alone.  Enqueued on hip_stream, no sync.  T41RX_ERR_ARG before t41rx_set_calibration(on), for
  *   n_frames <= 0, and for NULL input or a NULL d_result.  The _q15 form takes the two queues' int16 samples; the _host
- *   forms copy in (d_pixel / d_spec too), run the same kernel, copy out and synchronise. */
+ *   forms copy in (d_pixel / d_spec too), run the same kernel, copy out and synchronise.  An input map
+ *   (t41rx_set_input_map) is the audio path's: the calibration calls ignore it and keep their own shared_input. */
 #define T41RX_CAL_RX_LSB_BIN0 310 /* cal_bins[], Process2.cpp:429-444 */
 #define T41RX_CAL_RX_LSB_BIN1 460
 #define T41RX_CAL_RX_USB_BIN0 65

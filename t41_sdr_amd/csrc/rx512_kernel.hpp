@@ -82,9 +82,20 @@ static_assert(!Geo<0>::kResident || (Geo<0>::kH1 + 24 <= Geo<0>::kSlice && Geo<0
 // start-up transient); back end = the previous segment's last 28 audio samples.  The channel's
 // state is written by the wave that READ it (the one that starts the call), from the call's last
 // samples in the same way: a wave of a later run may execute before that one has started.
-template <int MODE, bool DEBUG, int PART, bool PLAIN, bool AGC = false, bool WQ15 = false, bool SEGPAR = false, bool PIPE = false>
-__global__ __launch_bounds__((Rx512Geo<MODE, PART, AGC, PIPE>::kWaves * 64), 4) void rx512_kernel(const RxArgs a) {
+// MAP (receiver groups, t41rx_set_input_map): the channel reads row a.in_map[ch] of I / Q, placed by a.in_chan_stride /
+// a.in_frame_stride; a.chan_stride / a.frame_stride then place the output alone.  Addresses only: the arithmetic is the
+// unmapped kernel's.  The switch rides on the PART argument -- PARTM = PART + kPartMap for the mapped form -- so that the
+// unmapped instantiations keep the template arguments, and with them the names, they had before the map existed, and the
+// kernel stays one function: a shared body inlined into two kernels compiles the unmapped ones to other instruction
+// streams (commuted operands, a few instructions moved), which the product's kernels are not to have.
+constexpr int kPartMap = 4;
+template <int MODE, bool DEBUG, int PARTM, bool PLAIN, bool AGC = false, bool WQ15 = false, bool SEGPAR = false, bool PIPE = false>
+__global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 64), 4) void rx512_kernel(const RxArgs a) {
   T41RX_CLK_BEGIN();
+  constexpr int PART = PARTM & 3;
+  constexpr bool MAP = (PARTM & kPartMap) != 0;
+  static_assert(PART <= 2 && (PARTM & ~(3 | kPartMap)) == 0, "PARTM = PART, or PART + kPartMap");
+  static_assert(!MAP || PART != 2, "the back end of the long-FFT pipeline reads no antenna samples");
   static_assert(!SEGPAR || (PART == 1 && MODE != kModeNfm) || (PART == 2 && MODE == kModeSsb && !AGC), "SEGPAR variants");
   static_assert(!PIPE || ((AGC || MODE == kModeSam) && PART == 0 && !DEBUG && !SEGPAR),
                 "PIPE: the pipelined variants -- AGC on (see agc_prep_pipe), the synchronous detector with the AGC off (sam_chain_pipe), or both (PSA)");
@@ -167,6 +178,10 @@ __global__ __launch_bounds__((Rx512Geo<MODE, PART, AGC, PIPE>::kWaves * 64), 4) 
   const CoefPtr cf0 = (CoefPtr)a.coef;
   const NcoPtr nco = (NcoPtr)(a.nco + ch);
   const float2 *__restrict__ tab = a.tab;
+  // MAP: the row of I / Q this channel reads.  ch is wave-uniform and the map read-only: one scalar load per wave, not one
+  // per frame; the host has checked the entry (t41rx_set_input_map), the kernel does not
+  typedef const __attribute__((address_space(4))) int *MapPtr;
+  const int strm = MAP ? ((MapPtr)a.in_map)[ch] : ch;
 
   // per-channel NCO constants and state (wave-uniform).  Only the LOADS are issued here; the
   // values are made uniform (which waits for them) after the first frame's input loads are in
@@ -260,10 +275,13 @@ __global__ __launch_bounds__((Rx512Geo<MODE, PART, AGC, PIPE>::kWaves * 64), 4) 
     // sample offset of (channel, frame) in I / Q / audio: RxArgs::chan_stride / frame_stride (channel-major
     // [channel][frame][2048]: nframes * 2048 and 2048; time-major [frame][channel][2048]: 2048 and nchan * 2048)
     const size_t chbase = (size_t)ch * (size_t)a.chan_stride;
-    const size_t fbase = chbase + (size_t)f * (size_t)a.frame_stride;
+    // MAP: the input has its own strides and the channel's row is in_map[ch]; everything derived from the input base --
+    // the next frame's prefetch, the q15 halving, the pre-roll in front of a run -- follows it
+    const size_t in_frame_stride = MAP ? (size_t)a.in_frame_stride : (size_t)a.frame_stride;
+    const size_t fbase = (MAP ? (size_t)strm * (size_t)a.in_chan_stride : chbase) + (size_t)f * in_frame_stride;
     const int fb = PIPE ? (f >= kSkew ? f - kSkew : 0) : f;  // the frame the back end works on
     const size_t fbase_o = chbase + (size_t)fb * (size_t)a.frame_stride;
-    const size_t fstep = WQ15 ? (size_t)a.frame_stride / 2 : (size_t)a.frame_stride;  // this channel's next frame, in float slots
+    const size_t fstep = WQ15 ? in_frame_stride / 2 : in_frame_stride;  // this channel's next frame of input, in float slots
     // (WQ15: two samples per float slot, so sample offsets halve)
     const float *__restrict__ gI = a.I + (WQ15 ? fbase / 2 : fbase);
     const float *__restrict__ gQ = a.Q + (WQ15 ? fbase / 2 : fbase);

@@ -12,13 +12,15 @@ namespace t41 {
 // PART 0, AGC off: one 16-wave workgroup per CU (all 160 KiB of LDS, declared statically by the kernel) -- a
 // 4096-channel batch is one full, balanced wave of work on 256 CUs, and every wave keeps its channel for all the
 // frames of the launch.  Everything else: 4-wave workgroups (see Geo).
-template <int MODE, bool DEBUG, int PART, bool PLAIN, bool AGC, bool WQ15, bool SEGPAR = false, bool PIPE = false>
+// MAP: the call carries an input map (RxArgs::in_map, receiver groups) -- the same instantiation in its mapped form
+// (PART + kPartMap), same geometry.
+template <int MODE, bool DEBUG, int PART, bool PLAIN, bool AGC, bool WQ15, bool SEGPAR = false, bool PIPE = false, bool MAP = false>
 static hipError_t launch_rx512(const RxArgs &a, hipStream_t s) {
   constexpr size_t NW = Rx512Geo<MODE, PART, AGC, PIPE>::kWaves;
   const size_t runs = SEGPAR ? (size_t)((a.nframes + a.seg_run - 1) / a.seg_run) : 1;
   const size_t jobs = (size_t)a.nchan * runs;
-  hipLaunchKernelGGL((rx512_kernel<MODE, DEBUG, PART, PLAIN, AGC, WQ15, SEGPAR, PIPE>), dim3((unsigned)((jobs + NW - 1) / NW)), dim3(NW * 64),
-                     0, s, a);
+  hipLaunchKernelGGL((rx512_kernel<MODE, DEBUG, PART + (MAP ? kPartMap : 0), PLAIN, AGC, WQ15, SEGPAR, PIPE>),
+                     dim3((unsigned)((jobs + NW - 1) / NW)), dim3(NW * 64), 0, s, a);
   return hipGetLastError();
 }
 
@@ -31,13 +33,15 @@ static hipError_t launch512(const RxArgs &a, hipStream_t s, bool debug) {
   // the pipelined variants (agc_prep_pipe, sam_chain_pipe, PSA): calls of four frames or more without taps; shorter
   // calls have nothing to overlap and take the barrier form, which computes the same values
   const bool pipe = (a.agc || SAM) && a.agc_pipe && !debug && a.nframes >= 4;
+  // an input map changes none of the rules above: a mapped call takes the instantiation the same call would take without
+  // the map, in its mapped form, and a call without a map never reaches a mapped one
   return with_bools(
-      [&](auto DBG, auto PLN, auto AGC, auto Q15, auto PIPE) {
+      [&](auto DBG, auto PLN, auto AGC, auto Q15, auto PIPE, auto MAP) {
         // what the rules above never select is not compiled
         if constexpr ((DBG && (PLN || PIPE)) || (PLN && SAM) || (PIPE && !(AGC || SAM))) return hipErrorInvalidValue;
-        else return launch_rx512<MODE, DBG, 0, PLN, AGC, Q15, false, PIPE>(a, s);
+        else return launch_rx512<MODE, DBG, 0, PLN, AGC, Q15, false, PIPE, MAP>(a, s);
       },
-      debug, plain, a.agc != 0, a.q15 != 0, pipe);
+      debug, plain, a.agc != 0, a.q15 != 0, pipe, a.in_map != nullptr);
 }
 
 }  // namespace t41

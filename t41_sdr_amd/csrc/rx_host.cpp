@@ -62,6 +62,11 @@ struct t41rx_ctx {
   int scratch_frames = 0;
   int layout = T41RX_LAYOUT_CHANNEL_MAJOR;  // of I / Q / audio (t41rx_set_buffer_layout)
   int nco_sel = 0;               // long FFT: which NcoState copy is current (flips with every process call)
+  // receiver groups (t41rx_set_input_map): channel c reads row in_map[c] of the n_streams rows of I / Q; n_streams == 0:
+  // no map, one row per channel.  Configuration like `layout`: in no checkpoint, untouched by reset / set_state / set_params
+  std::vector<int32_t> in_map;   // (host)
+  int n_streams = 0;
+  DevBuf<int32_t> d_in_map;      // [nchan], allocated with the first map
   // noise reduction / notch (Process.cpp:841-866): state of Xanr() and of the two spectral functions, window tables;
   // allocated when a call first needs them
   DevBuf<float> d_nr_anr, d_nr_spec, d_nr_tab;
@@ -141,7 +146,7 @@ struct t41rx_ctx {
   hipEvent_t ft8d_sel_ev = nullptr;
   // staging for t41rx_process_host
   DevBuf<float> d_in_i, d_in_q, d_out;
-  size_t staging_floats = 0;
+  size_t staging_in_floats = 0, staging_floats = 0;  // floats d_in_i / d_in_q and d_out hold
 };
 
 namespace {
@@ -729,6 +734,11 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
     a.chan_stride = (long long)a.nframes * 2048;
     a.frame_stride = 2048;
   }
+  if (ctx->n_streams > 0) {  // receiver groups: I / Q hold n_streams rows in the same layout, the output nchan as above
+    a.in_map = ctx->d_in_map.get();
+    a.in_chan_stride = a.chan_stride;
+    a.in_frame_stride = ctx->layout == T41RX_LAYOUT_TIME_MAJOR ? (long long)ctx->n_streams * 2048 : a.frame_stride;
+  }
   a.seg = seg;
   a.nframes4k = n_frames;
   a.mid = ctx->d_mid.get();
@@ -1065,18 +1075,28 @@ int calibrate_host_impl(t41rx_ctx *ctx, const void *I, const void *Q, int shared
   return T41RX_OK;
 }
 
-// staging buffers of the host-pointer entry points, sized in bytes per array
-int ensure_staging(t41rx_ctx *ctx, size_t bytes) {
-  if (bytes <= ctx->staging_floats * sizeof(float)) return T41RX_OK;
-  ctx->staging_floats = 0;
-  ctx->d_in_i.reset();
-  ctx->d_in_q.reset();
-  ctx->d_out.reset();
-  const size_t nfl = (bytes + sizeof(float) - 1) / sizeof(float);
-  HIP_TRY(dev_alloc(ctx->d_in_i, nfl * sizeof(float)));
-  HIP_TRY(dev_alloc(ctx->d_in_q, nfl * sizeof(float)));
-  HIP_TRY(dev_alloc(ctx->d_out, nfl * sizeof(float)));
-  ctx->staging_floats = nfl;
+// rows of I / Q a process call reads: one per channel, or the input map's n_streams
+int input_rows(const t41rx_ctx *ctx) { return ctx->n_streams > 0 ? ctx->n_streams : ctx->nchan; }
+
+// staging buffers of the host-pointer entry points, sized in bytes per array: the two inputs (with an input map they
+// hold n_streams rows, the output n_channels) and the output
+int ensure_staging(t41rx_ctx *ctx, size_t in_bytes, size_t out_bytes) {
+  if (in_bytes > ctx->staging_in_floats * sizeof(float)) {
+    ctx->staging_in_floats = 0;
+    ctx->d_in_i.reset();
+    ctx->d_in_q.reset();
+    const size_t nfl = (in_bytes + sizeof(float) - 1) / sizeof(float);
+    HIP_TRY(dev_alloc(ctx->d_in_i, nfl * sizeof(float)));
+    HIP_TRY(dev_alloc(ctx->d_in_q, nfl * sizeof(float)));
+    ctx->staging_in_floats = nfl;
+  }
+  if (out_bytes > ctx->staging_floats * sizeof(float)) {
+    ctx->staging_floats = 0;
+    ctx->d_out.reset();
+    const size_t nfl = (out_bytes + sizeof(float) - 1) / sizeof(float);
+    HIP_TRY(dev_alloc(ctx->d_out, nfl * sizeof(float)));
+    ctx->staging_floats = nfl;
+  }
   return T41RX_OK;
 }
 
@@ -1309,6 +1329,44 @@ int t41rx_set_buffer_layout(t41rx_ctx *ctx, int layout) {
   return T41RX_OK;
 }
 int t41rx_get_buffer_layout(const t41rx_ctx *ctx) { return ctx ? ctx->layout : T41RX_ERR_ARG; }
+
+int t41rx_set_input_map(t41rx_ctx *ctx, const int32_t *stream_of_channel, int n, int n_streams) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  const std::string counts = " (n_channels " + std::to_string(ctx->nchan) + ", n_streams " + std::to_string(n_streams) + ")";
+  if (!stream_of_channel) {
+    if (n_streams != 0) return fail(T41RX_ERR_ARG, "input map: a null map switches the map off and takes n_streams 0" + counts);
+    DeviceGuard g(ctx->device);
+    HIP_TRY(hipDeviceSynchronize());  // (calls in flight were launched with the map they found)
+    ctx->n_streams = 0;
+    return T41RX_OK;
+  }
+  // everything is checked here, on the host, before anything changes: the kernels index I / Q with these entries unchecked
+  if (n != ctx->nchan) return fail(T41RX_ERR_ARG, "input map: n (" + std::to_string(n) + ") must equal n_channels" + counts);
+  if (n_streams < 1 || n_streams > ctx->nchan) return fail(T41RX_ERR_ARG, "input map: n_streams must lie in [1, n_channels]" + counts);
+  for (int i = 0; i < n; ++i)
+    if (stream_of_channel[i] < 0 || stream_of_channel[i] >= n_streams)
+      return fail(T41RX_ERR_ARG, "input map: channel " + std::to_string(i) + " names stream " + std::to_string(stream_of_channel[i]) +
+                                     ", outside [0, n_streams)" + counts);
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  HIP_TRY(hipDeviceSynchronize());
+  DevBuf<int32_t> fresh;  // (the first map; later ones reuse the buffer: a failure leaves the previous map whole)
+  if (!ctx->d_in_map) HIP_TRY(dev_alloc(fresh, sizeof(int32_t) * (size_t)n));
+  HIP_TRY(hipMemcpy(fresh ? fresh.get() : ctx->d_in_map.get(), stream_of_channel, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+  if (fresh) ctx->d_in_map = std::move(fresh);
+  ctx->in_map.assign(stream_of_channel, stream_of_channel + n);
+  ctx->n_streams = n_streams;
+  return T41RX_OK;
+}
+
+int t41rx_get_input_map(const t41rx_ctx *ctx, int32_t *stream_of_channel_out, int n) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (ctx->n_streams > 0 && stream_of_channel_out) {
+    if (n != ctx->nchan) return fail(T41RX_ERR_ARG, "input map: n (" + std::to_string(n) + ") must equal n_channels (" + std::to_string(ctx->nchan) + ")");
+    std::memcpy(stream_of_channel_out, ctx->in_map.data(), sizeof(int32_t) * (size_t)n);
+  }
+  return ctx->n_streams;
+}
 
 int t41rx_set_noise_blanker(t41rx_ctx *ctx, int NB_on) {
   if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
@@ -1739,10 +1797,11 @@ int t41rx_process_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, const int16_t 
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
   const size_t bytes = (size_t)ctx->nchan * (size_t)n_frames * (size_t)(4 * ctx->params.fft_length) * sizeof(int16_t);
-  int rc = ensure_staging(ctx, bytes);
+  const size_t in_bytes = bytes / (size_t)ctx->nchan * (size_t)input_rows(ctx);  // an input map: n_streams rows come in
+  int rc = ensure_staging(ctx, in_bytes, bytes);
   if (rc != T41RX_OK) return rc;
-  HIP_TRY(hipMemcpy(ctx->d_in_i.get(), Q_in_L, bytes, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ctx->d_in_q.get(), Q_in_R, bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ctx->d_in_i.get(), Q_in_L, in_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ctx->d_in_q.get(), Q_in_R, in_bytes, hipMemcpyHostToDevice));
   rc = t41rx_process_device_q15(ctx, reinterpret_cast<const int16_t *>(ctx->d_in_i.get()), reinterpret_cast<const int16_t *>(ctx->d_in_q.get()),
                                 reinterpret_cast<int16_t *>(ctx->d_out.get()), n_frames, nullptr);
   if (rc != T41RX_OK) return rc;
@@ -1757,12 +1816,13 @@ int t41rx_process_host(t41rx_ctx *ctx, const float *I, const float *Q, float *au
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
   const size_t nfl = (size_t)ctx->nchan * (size_t)n_frames * (size_t)(4 * ctx->params.fft_length);
+  const size_t in_fl = nfl / (size_t)ctx->nchan * (size_t)input_rows(ctx);  // an input map: n_streams rows come in
   {
-    const int rc0 = ensure_staging(ctx, nfl * sizeof(float));
+    const int rc0 = ensure_staging(ctx, in_fl * sizeof(float), nfl * sizeof(float));
     if (rc0 != T41RX_OK) return rc0;
   }
-  HIP_TRY(hipMemcpy(ctx->d_in_i.get(), I, nfl * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(ctx->d_in_q.get(), Q, nfl * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ctx->d_in_i.get(), I, in_fl * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ctx->d_in_q.get(), Q, in_fl * sizeof(float), hipMemcpyHostToDevice));
   int rc = t41rx_process_device(ctx, ctx->d_in_i.get(), ctx->d_in_q.get(), ctx->d_out.get(), n_frames, nullptr);
   if (rc != T41RX_OK) return rc;
   HIP_TRY(hipDeviceSynchronize());

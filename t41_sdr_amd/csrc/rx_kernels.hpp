@@ -74,6 +74,12 @@ struct RxArgs {
   // AGC on, pipelined kernel (rx_chains.hpp: agc_prep_pipe): per channel three slots of 1024 floats -- the serial
   // chain's operands and results and the samples the gain is applied to, for the frames in flight (or null: barrier form)
   float *agc_pipe;
+  // receiver groups (t41rx_set_input_map), or null: channel c reads row in_map[c] of I / Q, whose (row, frame) starts at
+  // in_map[c] * in_chan_stride + f * in_frame_stride samples; chan_stride / frame_stride then place the output alone.
+  // The host has checked every entry against the number of rows.  Only the mapped instantiations read these fields.
+  const int *__restrict__ in_map;
+  long long in_chan_stride;
+  long long in_frame_stride;
 };
 
 // constant table of the N = 512 R point fast convolution (float2 units):

@@ -8,15 +8,17 @@ namespace t41 {
 
 hipError_t launch_long_front(const RxArgs &a, int mode, hipStream_t s) {
   if (mode == T41RX_DEMOD_NFM)  // nfmdemod()'s "last sample" chains the frames: sequential, on the general front end
-    return with_bools([&](auto Q15) { return launch_rx512<kModeNfm, false, 1, false, false, Q15>(a, s); }, a.q15 != 0);
+    return with_bools([&](auto Q15, auto MAP) { return launch_rx512<kModeNfm, false, 1, false, false, Q15, false, false, MAP>(a, s); },
+                      a.q15 != 0, a.in_map != nullptr);
   // everything else: one wave per (channel, run of segments), the segments run independently (SEGPAR).  PLAIN -- unit
   // band / IQ gains (the firmware defaults): the correction stage drops out -- for f32 samples only.
+  // An input map (receiver groups) selects the same instantiation in its mapped form; the back end reads no antenna samples.
   return with_bools(
-      [&](auto PLN, auto Q15) {
+      [&](auto PLN, auto Q15, auto MAP) {
         if constexpr (PLN && Q15) return hipErrorInvalidValue;  // never selected: not compiled
-        else return launch_rx512<kModeSsb, false, 1, PLN, false, Q15, true>(a, s);
+        else return launch_rx512<kModeSsb, false, 1, PLN, false, Q15, true, false, MAP>(a, s);
       },
-      a.plain && !a.q15, a.q15 != 0);
+      a.plain && !a.q15, a.q15 != 0, a.in_map != nullptr);
 }
 
 // SSB / NFM audio with the fixed gain: the gain law and the demodulators keep no state here

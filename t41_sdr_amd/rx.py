@@ -90,6 +90,7 @@ class RxChain:
         self.device = int(device)
         self.frame_len = self._lib.t41rx_frame_len(self._ctx)
         self.layout = "channel"
+        self._n_streams = 0  # the input map's row count (set_input_map), 0 = no map
         if NCOFreq is not None:
             self.SetNCOFreq(NCOFreq)
 
@@ -140,6 +141,39 @@ class RxChain:
         code = {"channel": 0, "time": 1}[layout]
         check(self._lib.t41rx_set_buffer_layout(self._ctx, code))
         self.layout = layout
+
+    def set_input_map(self, stream_of_channel, n_streams=None):
+        """Receiver groups (t41rx_set_input_map): channel c reads row stream_of_channel[c] of I / Q, which then hold
+        n_streams rows -- [n_streams, n_frames*frame_len], time-major [n_frames, n_streams, frame_len] -- while the audio
+        and every side output stay [n_channels, ...].  n_streams defaults to max + 1.  None switches the map off.
+        Configuration, like the buffer layout: in no checkpoint, kept across reset() / set_state() / CalcFilters()."""
+        if stream_of_channel is None:
+            check(self._lib.t41rx_set_input_map(self._ctx, None, 0, 0))
+            self._n_streams = 0
+            return
+        m = np.asarray(stream_of_channel)
+        if m.ndim != 1 or not np.issubdtype(m.dtype, np.integer) or (m.size and (m.min() < -2**31 or m.max() >= 2**31)):
+            raise ValueError("stream_of_channel must be a 1-d array of int32 stream numbers, got %r %s" % (m.shape, m.dtype))
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        if n_streams is None:
+            n_streams = int(m.max()) + 1 if m.size else 0
+        check(self._lib.t41rx_set_input_map(self._ctx, m.ctypes.data_as(C.POINTER(C.c_int32)), int(m.size), int(n_streams)))
+
+        self._n_streams = int(n_streams)
+
+    @property
+    def n_streams(self):
+        """rows of I / Q a process call reads: the input map's n_streams, or n_channels with the map off"""
+        return self._n_streams if self._n_streams > 0 else self.n_channels
+
+    @property
+    def input_map(self):
+        """the input map as an int32 array [n_channels] (a copy), or None with the map off"""
+        m = np.zeros(self.n_channels, np.int32)
+        v = self._lib.t41rx_get_input_map(self._ctx, m.ctypes.data_as(C.POINTER(C.c_int32)), self.n_channels)
+        if v < 0:
+            check(v)
+        return m if v > 0 else None
 
     def set_noise_blanker(self, on):
         """NB_on (Process.cpp:873-876): the receive noise blanker on the demodulated audio, behind the noise reduction and
@@ -491,7 +525,7 @@ class RxChain:
             I = np.ascontiguousarray(float_buffer_L, dtype=np.float32)
             Q = np.ascontiguousarray(float_buffer_R, dtype=np.float32)
             nfr = self._check_shape(I.shape, Q.shape)
-            audio = np.empty_like(I) if out is None else self._check_out_numpy(out, I)
+            audio = np.empty(self._out_shape(nfr), I.dtype) if out is None else self._check_out_numpy(out, I, nfr)
             fp = C.POINTER(C.c_float)
             check(self._lib.t41rx_process_host(self._ctx, I.ctypes.data_as(fp), Q.ctypes.data_as(fp),
                                                audio.ctypes.data_as(fp), nfr))
@@ -504,7 +538,7 @@ class RxChain:
         if I.device.index != self.device or Q.device.index != self.device:
             raise ValueError("I/Q live on another device than this RxChain")
         nfr = self._check_shape(tuple(I.shape), tuple(Q.shape))
-        audio = torch.empty_like(I) if out is None else self._check_out_torch(out, I)
+        audio = self._new_out_torch(I, nfr) if out is None else self._check_out_torch(out, I, nfr)
         stream = torch.cuda.current_stream(I.device).cuda_stream
         check(self._lib.t41rx_process_device(self._ctx, I.data_ptr(), Q.data_ptr(), audio.data_ptr(), nfr,
                                              C.c_void_p(stream)))
@@ -519,7 +553,7 @@ class RxChain:
             a = np.ascontiguousarray(Q_in_L, dtype=np.int16)
             b = np.ascontiguousarray(Q_in_R, dtype=np.int16)
             nfr = self._check_shape(a.shape, b.shape)
-            audio = np.empty_like(a) if out is None else self._check_out_numpy(out, a)
+            audio = np.empty(self._out_shape(nfr), a.dtype) if out is None else self._check_out_numpy(out, a, nfr)
             check(self._lib.t41rx_process_host_q15(self._ctx, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
                                                    audio.ctypes.data_as(C.c_void_p), nfr))
             return audio
@@ -531,7 +565,7 @@ class RxChain:
         if a.device.index != self.device or b.device.index != self.device:
             raise ValueError("the queues live on another device than this RxChain")
         nfr = self._check_shape(tuple(a.shape), tuple(b.shape))
-        audio = torch.empty_like(a) if out is None else self._check_out_torch(out, a)
+        audio = self._new_out_torch(a, nfr) if out is None else self._check_out_torch(out, a, nfr)
         stream = torch.cuda.current_stream(a.device).cuda_stream
         check(self._lib.t41rx_process_device_q15(self._ctx, a.data_ptr(), b.data_ptr(), audio.data_ptr(), nfr,
                                                  C.c_void_p(stream)))
@@ -671,28 +705,45 @@ class RxChain:
         self._cal_keep = (I, Q, u)  # alive until the next call: the launch is asynchronous
         return res, pixel, spec
 
-    def _check_out_torch(self, out, like):
-        if not (out.is_cuda and out.dtype == like.dtype and out.is_contiguous() and tuple(out.shape) == tuple(like.shape)
+    def _out_shape(self, nfr):
+        """the audio's shape for a call of nfr frames: n_channels rows, whatever the input map makes of the input's"""
+        if self.layout == "time":
+            return (nfr, self.n_channels, self.frame_len)
+        return (self.n_channels, nfr * self.frame_len)
+
+    def _new_out_torch(self, like, nfr):
+        import torch
+        return torch.empty(self._out_shape(nfr), dtype=like.dtype, device=like.device)
+
+    def _rows_text(self):
+        return "(n_channels=%d, n_streams=%d)" % (self.n_channels, self.n_streams)
+
+    def _check_out_torch(self, out, like, nfr):
+        shape = self._out_shape(nfr)
+        if not (out.is_cuda and out.dtype == like.dtype and out.is_contiguous() and tuple(out.shape) == shape
                 and out.device == like.device):
-            raise ValueError("out must be a contiguous %s CUDA tensor of shape %r on %s" % (like.dtype, tuple(like.shape), like.device))
+            raise ValueError("out must be a contiguous %s CUDA tensor of shape %r on %s %s"
+                             % (like.dtype, shape, like.device, self._rows_text()))
         return out
 
-    @staticmethod
-    def _check_out_numpy(out, like):
-        if not (isinstance(out, np.ndarray) and out.dtype == like.dtype and out.shape == like.shape
+    def _check_out_numpy(self, out, like, nfr):
+        shape = self._out_shape(nfr)
+        if not (isinstance(out, np.ndarray) and out.dtype == like.dtype and out.shape == shape
                 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]):
-            raise ValueError("out must be a writeable C-contiguous %s array of shape %r" % (like.dtype, like.shape))
+            raise ValueError("out must be a writeable C-contiguous %s array of shape %r %s" % (like.dtype, shape, self._rows_text()))
         return out
 
     def _check_shape(self, si, sq):
+        """n_frames of a call on I / Q of these shapes: one row per channel, or with an input map one per stream"""
+        rows = self.n_streams
         if self.layout == "time":
-            if si != sq or len(si) != 3 or si[0] == 0 or si[1] != self.n_channels or si[2] != self.frame_len:
-                raise ValueError("time-major I/Q must be [n_frames, n_channels=%d, frame_len=%d], got %r / %r"
-                                 % (self.n_channels, self.frame_len, si, sq))
+            if si != sq or len(si) != 3 or si[0] == 0 or si[1] != rows or si[2] != self.frame_len:
+                raise ValueError("time-major I/Q must be [n_frames, %d, frame_len=%d] %s, got %r / %r"
+                                 % (rows, self.frame_len, self._rows_text(), si, sq))
             return si[0]
-        if si != sq or len(si) != 2 or si[0] != self.n_channels or si[1] == 0 or si[1] % self.frame_len:
-            raise ValueError("I/Q must be [n_channels=%d, k*frame_len=%d], got %r / %r"
-                             % (self.n_channels, self.frame_len, si, sq))
+        if si != sq or len(si) != 2 or si[0] != rows or si[1] == 0 or si[1] % self.frame_len:
+            raise ValueError("I/Q must be [%d, k*frame_len=%d] %s, got %r / %r"
+                             % (rows, self.frame_len, self._rows_text(), si, sq))
         return si[1] // self.frame_len
 
     def close(self):
