@@ -573,6 +573,46 @@ T41RX_API size_t t41rx_ft8_state_bytes(const t41rx_ctx *ctx);
 T41RX_API int t41rx_ft8_get_state(t41rx_ctx *ctx, void *host_buf, size_t bytes);
 T41RX_API int t41rx_ft8_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes);
 
+/* ---- FT8 from 12 kS/s audio: the collector of DEMOD_FT8_WAV (Process.cpp:278-335, ft8.cpp:259-268, :1359-1374) ----
+ * For a caller who already has audio -- WSJT-X style 12 kHz recordings, another receiver's audio -- the firmware's WAV mode
+ * feeds the same ft8_dsp_buffer without the receive chain: 128 samples at 12 kS/s per ProcessIQData().  These entry points
+ * run it on the FT8 memory, the d_power halves and the d_status words of t41rx_set_ft8() (which must be on); the receive
+ * path does not run, and t41rx_ft8_decode_*() reads the finished half as it does behind the live stage.  Per channel and
+ * frame of 128 samples, in the firmware's order:
+ *   q = arm_float_to_q15(x), truncating and saturating (NaN -> 0); int16 samples are taken as they are (readWave()'s
+ *     raw / 32768.0f through that conversion is the identity);
+ *   for i < 68 and k = i + 68 * dataLoop: buf[k] = buf[k + 1024]; buf[1024 + k] = buf[2048 + k]; buf[2048 + k] =
+ *     q[(i * 15) >> 3].  No leftover, no last cell, no syncFlag gate, no DSP_Flag: words 1020..1023, 2044..2047 and
+ *     3068..3071 keep what the record held;
+ *   ++dataLoop == 15: dataLoop = 0 and process_FT8_FFT() unconditionally (ft8_flag is not asked): the block's 1472 bytes at
+ *     1472 * FT_8_counter of the half being written, FT_8_counter++; at 92 ft8_flag = 0, the frame's status reports 1 + that
+ *     half, `half` flips and FT_8_counter = 0.  update_synchronization() is never called;
+ *   n advances (a 128-sample frame lasts the 32 / 3 ms of a live one); syncFlag, DSP_Flag, leftover and start_time stay.
+ * From a power-on record a slot completes in frame 1379 (counted from 0) and the next one starts in the other half.  A
+ * record with FT_8_counter at 92 (the live stage leaves it there next to ft8_flag 0; the firmware always passes through
+ * setupFT8Wav() first) would index past the half: such a block writes nothing and the counter stays until _begin / _end.
+ * The x2 interpolation for listening (Process.cpp:293-297), the pacing by the audio queues and the SD card stay with the
+ * caller.
+ * t41rx_ft8_audio_device_q15() / _device(): device buffers [n_channels][n_frames * 128], int16 or float, ALWAYS
+ *   channel-major: the input map (t41rx_set_input_map) and t41rx_set_buffer_layout() do not apply to these entries.  Float
+ *   samples go through arm_float_to_q15.  d_status gets [n_channels][n_frames][4] as from a process call.  On the default
+ *   stream, without synchronising.  T41RX_ERR_ARG -- nothing launched, nothing in the FT8 memory, d_power or d_status
+ *   changed -- while FT8 receive is off, before the tables are loaded, for n_frames < 1, n_frames > max_frames of
+ *   t41rx_set_ft8(), n_frames > T41RX_FT8_MAX_FRAMES, a NULL pointer or one not aligned to its sample type.
+ * t41rx_ft8_audio_host_q15() / _host(): the same from host arrays; synchronises.
+ * t41rx_ft8_audio_begin(): setupFT8Wav()'s FT_8_counter = 0 on the channels whose byte is non-zero (host array of n =
+ *   n_channels bytes; NULL = all).  t41rx_ft8_audio_end(): the mode's exit (Process.cpp:339-342), syncFlag = 0,
+ *   FT_8_counter = 0, ft8_flag = 0.  Neither touches dataLoop or anything else, as in the firmware; both synchronise.
+ * The receive path's audio, t41rx_state_bytes() and every checkpoint are untouched; t41rx_ft8_get_state / _set_state carry
+ * everything, as before. */
+#define T41RX_FT8_AUDIO_FRAME 128
+T41RX_API int t41rx_ft8_audio_device_q15(t41rx_ctx *ctx, const int16_t *d_pcm, int n_frames);
+T41RX_API int t41rx_ft8_audio_device(t41rx_ctx *ctx, const float *d_audio, int n_frames);
+T41RX_API int t41rx_ft8_audio_host_q15(t41rx_ctx *ctx, const int16_t *pcm, int n_frames);
+T41RX_API int t41rx_ft8_audio_host(t41rx_ctx *ctx, const float *audio, int n_frames);
+T41RX_API int t41rx_ft8_audio_begin(t41rx_ctx *ctx, const uint8_t *channels, int n);
+T41RX_API int t41rx_ft8_audio_end(t41rx_ctx *ctx, const uint8_t *channels, int n);
+
 /* ---- FT8 decode of a finished slot (ft8.cpp:270-616, 669-703, 727-790) ----
  * find_sync(), and for every candidate of its heap extract_likelihood(), bp_decode(), pack_bits() and the CRC check, on a
  * waterfall that stays on the device: [92 blocks][4 = 2 * time_sub + freq_sub][368 bins] uint8 per channel and slot, the

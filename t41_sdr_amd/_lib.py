@@ -108,6 +108,12 @@ SYMBOLS = {
     "t41rx_ft8_state_bytes": (C.c_size_t, [_vp]),
     "t41rx_ft8_get_state": (C.c_int, [_vp, _vp, C.c_size_t]),
     "t41rx_ft8_set_state": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "t41rx_ft8_audio_device_q15": (C.c_int, [_vp, _vp, C.c_int]),
+    "t41rx_ft8_audio_device": (C.c_int, [_vp, _vp, C.c_int]),
+    "t41rx_ft8_audio_host_q15": (C.c_int, [_vp, _vp, C.c_int]),
+    "t41rx_ft8_audio_host": (C.c_int, [_vp, _vp, C.c_int]),
+    "t41rx_ft8_audio_begin": (C.c_int, [_vp, _vp, C.c_int]),
+    "t41rx_ft8_audio_end": (C.c_int, [_vp, _vp, C.c_int]),
     "t41rx_set_ft8_decode_tables": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "t41rx_set_ft8_decode": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "t41rx_get_ft8_decode": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

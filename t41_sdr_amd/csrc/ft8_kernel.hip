@@ -24,6 +24,11 @@
 // bits 4..6 and land on eight different quads.  The last stage reads its four neighbours as one 16-byte word and scatters
 // them to their bit-reversed places in a second buffer indexed through sw2(k) = k ^ (k >> 5 & 31): consecutive lanes
 // differ in the high bits of the reversed index, which sw2 folds into the bank; the split stage then reads it linearly.
+//
+// The block's text is ft8_block.inc, compiled into both kernels that run it: ft8_kernel and ft8_audio_kernel (FT8 from
+// 12 kS/s audio, below).  Two kernels from one text, not one body inlined into two: as a force-inlined device function it
+// compiles ft8_kernel to another instruction stream (the swizzled indices simplified another way, two instructions more),
+// and a template argument for the source would rename the live kernel (profiles/ft8_audio_isa_fingerprint.txt).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -122,80 +127,7 @@ __global__ __launch_bounds__(NT) void ft8_kernel(Ft8Args a) {
     if (dsp == 1 && flag == 1) {
       // ---- process_FT8_FFT() (ft8.cpp:259-268): extract_power(offset_step * FT_8_counter)
       uint8_t *row = a.power + ((size_t)ch * 2 + (size_t)half) * kFt8HalfBytes + (size_t)kFt8BlockBytes * (size_t)counter;
-      for (int ts = 0; ts < 2; ++ts) {
-        // window_ft8_dsp_buffer[i] = (q15_t)((float)ft8_dsp_buffer[i + time_sub] * window[i]); point p = samples 2p, 2p + 1
-        for (int p = t; p < 1024; p += NT) {
-          const float2 wv = reinterpret_cast<const float2 *>(a.window)[p];
-          const int re = (int)((float)sbuf[2 * p + 512 * ts] * wv.x), im = (int)((float)sbuf[2 * p + 1 + 512 * ts] * wv.y);
-          fz[sw(p)] = pack(Cq{re, im});
-        }
-        __syncthreads();
-        // first stage: inputs >> 2; outputs b and c stored swapped, here and in every stage (arm_radix4_butterfly_q15)
-        for (int j = t; j < 256; j += NT) {
-          const Cq A = shr(unpack(fz[sw(j)]), 2), B = shr(unpack(fz[sw(j + 256)]), 2);
-          const Cq C = shr(unpack(fz[sw(j + 512)]), 2), D = shr(unpack(fz[sw(j + 768)]), 2);
-          const Cq R = qadd(A, C), S = qsub(A, C), T = qadd(B, D), U = qsub(B, D);
-          fz[sw(j)] = pack(hadd(R, T));
-          fz[sw(j + 256)] = pack(twmul(tw[2 * j], qsub(R, T)));
-          fz[sw(j + 512)] = pack(twmul(tw[j], Cq{sat16(S.r + U.i), sat16(S.i - U.r)}));      // __QSAX
-          fz[sw(j + 768)] = pack(twmul(tw[3 * j], Cq{sat16(S.r - U.i), sat16(S.i + U.r)}));  // __QASX
-        }
-        __syncthreads();
-        // middle stages: n2 = 64, 16, 4; twiddle step 4, 16, 64
-#pragma unroll
-        for (int lg = 6; lg >= 2; lg -= 2) {
-          const int n2 = 1 << lg, mod = 256 >> lg;
-          for (int b = t; b < 256; b += NT) {
-            const int jj = b & (n2 - 1), i0 = ((b >> lg) << (lg + 2)) + jj, ic = jj * mod;
-            const Cq A = unpack(fz[sw(i0)]), B = unpack(fz[sw(i0 + n2)]), C = unpack(fz[sw(i0 + 2 * n2)]), D = unpack(fz[sw(i0 + 3 * n2)]);
-            const Cq R = qadd(A, C), S = qsub(A, C), T = qadd(B, D), U = qsub(B, D);
-            fz[sw(i0)] = pack(shr(hadd(R, T), 1));
-            fz[sw(i0 + n2)] = pack(twmul(tw[2 * ic], hsub(R, T)));
-            fz[sw(i0 + 2 * n2)] = pack(twmul(tw[ic], Cq{(S.r + U.i) >> 1, (S.i - U.r) >> 1}));      // __SHSAX
-            fz[sw(i0 + 3 * n2)] = pack(twmul(tw[3 * ic], Cq{(S.r - U.i) >> 1, (S.i + U.r) >> 1}));  // __SHASX
-          }
-          __syncthreads();
-        }
-        // last stage: four neighbours, one halving; arm_bitreversal_16 folded into the stores
-        for (int g = t; g < 256; g += NT) {
-          const uint4 v = *reinterpret_cast<const uint4 *>(&fz[sw(4 * g)]);
-          const Cq A = unpack(v.x), B = unpack(v.y), C = unpack(v.z), D = unpack(v.w);
-          const Cq R = qadd(A, C), S = qsub(A, C), T = qadd(B, D), U = qsub(B, D);
-          const int k0 = (int)(__brev((unsigned)(4 * g)) >> 22);  // reversed 10-bit index; + 512, 256, 768 for 4 g + 1, 2, 3
-          nat[sw2(k0)] = pack(hadd(R, T));
-          nat[sw2(k0 + 512)] = pack(hsub(R, T));
-          nat[sw2(k0 + 256)] = pack(Cq{(S.r + U.i) >> 1, (S.i - U.r) >> 1});
-          nat[sw2(k0 + 768)] = pack(Cq{(S.r - U.i) >> 1, (S.i + U.r) >> 1});
-        }
-        __syncthreads();
-        // arm_split_rfft_q15 on bins 0 .. 736, arm_shift_q15 by 5, arm_cmplx_mag_squared_q15
-        for (int k = t; k < kFt8Bins; k += NT) {
-          int re, im;
-          const Cq P = unpack(nat[sw2(k)]);
-          if (k == 0) {
-            re = (P.r + P.i) >> 1;
-            im = 0;
-          } else {
-            const Cq Q = unpack(nat[sw2(1024 - k)]), Ac = unpack(a.tab[kFt8TabA + k]), Bc = unpack(a.tab[kFt8TabB + k]);
-            const unsigned outR = (unsigned)(P.r * Ac.r) - (unsigned)(P.i * Ac.i) + (unsigned)(Q.r * Bc.r) + (unsigned)(Q.i * Bc.i);
-            const unsigned outI = (unsigned)(Q.r * Bc.i) - (unsigned)(Q.i * Bc.r) + (unsigned)(P.r * Ac.i) + (unsigned)(P.i * Ac.r);
-            re = (int)(short)((int)outR >> 16);
-            im = (int)(short)((int)outI >> 16);
-          }
-          re = sat16(re * 32);
-          im = sat16(im * 32);
-          mg[k] = (unsigned short)(((unsigned)(re * re) + (unsigned)(im * im)) >> 17);  // 0 .. 16384 (the sum in more than 31 bits)
-        }
-        __syncthreads();
-        // the two rows of this time offset: freq_sub 0 / 1, 368 bytes each (ft8.cpp:244-254)
-        for (int e = t; e < 2 * kFt8Row; e += NT) {
-          const int fs = e >= kFt8Row ? 1 : 0, j = e - kFt8Row * fs;
-          const float db = (a.mag_db[mg[2 * j + fs]] + a.mag_db[mg[2 * j + fs + 1]]) / 2;
-          const int scaled = (int)db;  // toward zero, saturating, NaN -> 0
-          row[2 * kFt8Row * ts + e] = (uint8_t)(scaled < 0 ? 0 : (scaled > 255 ? 255 : scaled));
-        }
-        __syncthreads();
-      }
+#include "ft8_block.inc"
       ++counter;
       if (counter == kFt8SlotBlocks) {
         flag = 0;  // (ft8_decode_flag = 1: the decode belongs to the caller; this frame reports the finished half)
@@ -239,6 +171,121 @@ __global__ __launch_bounds__(64) void ft8_sync_kernel(int32_t *state, const uint
   w[kFt8Flag] = 1;
   w[kFt8Counter] = 0;
   w[kFt8Sync] = 1;
+}
+
+// ---- FT8 from 12 kS/s audio: the collector of DEMOD_FT8_WAV (Process.cpp:278-335), tests/ft8_audio_model.py bit for bit.
+// Per frame of 128 samples the firmware rolls 68 cells k = i + 68 * dataLoop of each third of the buffer and writes
+// q[(i * 15) >> 3] into the last; nothing gates a frame, and a cell is read only by the iteration that then writes it.  A
+// thread therefore owns its cells -- c, c + 1024, c + 2048 -- and the collector needs no barrier; it takes up to a whole
+// gulp (frames d0 <= d < d1 of the 15, cells 68 * d0 .. 68 * d1 - 1, four per thread) in one pass, with one barrier in
+// front of the transform when d1 == 15.  Cells 1020..1023 of each third are never touched.  process_FT8_FFT() runs
+// unconditionally (ft8_flag is not asked), the slot's end sets FT_8_counter = 0 (:325), and update_synchronization() is never
+// called.  The status words have a closed form in the frame's number and are written behind the loop.
+// A record with FT_8_counter at 92 (what the live stage leaves next to ft8_flag 0) would index past the half: such a block
+// is dropped and the counter stays, until t41rx_ft8_audio_begin() / _end().
+namespace ft8 {
+__device__ __forceinline__ short audio_q15(short x) { return x; }  // (raw / 32768.0f through arm_float_to_q15 is the identity)
+__device__ __forceinline__ short audio_q15(float x) { return (short)to_q15(x); }
+}  // namespace ft8
+
+template <typename Sample>
+__global__ __launch_bounds__(256) void ft8_audio_kernel(Ft8AudioArgs a) {
+#pragma clang fp contract(off)
+  using namespace ft8;
+  constexpr int NT = 256;
+  __shared__ short sbuf[kFt8BufWords];
+  __shared__ __attribute__((aligned(16))) unsigned fz[1024];
+  __shared__ unsigned nat[1024];
+  __shared__ unsigned tw[768];
+  __shared__ unsigned short mg[kFt8Bins + 3];
+  const int ch = blockIdx.x, t = threadIdx.x;
+  int32_t *w = a.state + (size_t)ch * kFt8Words;
+  auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
+  const int flag0 = uni(w[kFt8Flag]), counter0 = uni(w[kFt8Counter]), dataLoop0 = uni(w[kFt8DataLoop]), half0 = uni(w[kFt8Half]);
+  int flag = flag0, counter = counter0, half = half0;
+  for (int i = t; i < kFt8BufWords; i += NT) sbuf[i] = (short)w[kFt8Scalars + i];
+  for (int i = t; i < 768; i += NT) tw[i] = a.tab[kFt8TabTw + i];
+  __syncthreads();
+
+  const Sample *x = static_cast<const Sample *>(a.pcm) + (size_t)ch * (size_t)a.nframes * kFt8AudioFrame;
+  int d0 = dataLoop0;
+  for (int f = 0; f < a.nframes;) {
+    const int d1 = min(15, d0 + a.nframes - f);
+    for (int c = kFt8AudioCells * d0 + t; c < kFt8AudioCells * d1; c += NT) {  // c <= 1019
+      const int d = c / kFt8AudioCells, i = c - kFt8AudioCells * d;
+      const short q = audio_q15(x[(f + d - d0) * kFt8AudioFrame + ((i * 15) >> 3)]);  // frame < nframes, sample <= 125
+      sbuf[c] = sbuf[c + 1024];
+      sbuf[c + 1024] = sbuf[c + 2048];
+      sbuf[c + 2048] = q;
+    }
+    f += d1 - d0;
+    d0 = d1;
+    if (d1 == 15) {
+      d0 = 0;
+      __syncthreads();
+      if (counter < kFt8SlotBlocks) {
+        uint8_t *row = a.power + ((size_t)ch * 2 + (size_t)half) * kFt8HalfBytes + (size_t)kFt8BlockBytes * (size_t)counter;
+  #include "ft8_block.inc"
+        ++counter;
+        if (counter == kFt8SlotBlocks) {
+          flag = 0;
+          half ^= 1;
+          counter = 0;
+        }
+      }
+    }
+  }
+  // the status words: nb blocks have run behind frame f
+  for (int f = t; f < a.nframes; f += NT) {
+    const int fed = dataLoop0 + f + 1, nb = fed / 15;
+    int c = counter0, fl = flag0, done = 0;
+    if (counter0 < kFt8SlotBlocks) {
+      c = counter0 + nb;
+      if (c >= kFt8SlotBlocks) {  // at most one completion in kFt8MaxFrames frames
+        c -= kFt8SlotBlocks;
+        fl = 0;
+      }
+      if (fed == 15 * (kFt8SlotBlocks - counter0)) done = 1 + half0;
+    }
+    *reinterpret_cast<int4 *>(a.status + ((size_t)ch * a.nframes + f) * 4) = make_int4(c, fl, done, fed - 15 * nb);
+  }
+  __syncthreads();
+  for (int i = t; i < kFt8BufWords; i += NT) w[kFt8Scalars + i] = (int)sbuf[i];
+  if (t == 0) {
+    w[kFt8N] = (int)((unsigned)w[kFt8N] + (unsigned)a.nframes);
+    w[kFt8Flag] = flag;
+    w[kFt8Counter] = counter;
+    w[kFt8DataLoop] = d0;
+    w[kFt8Half] = half;
+  }
+}
+
+// setupFT8Wav()'s FT_8_counter = 0 (ft8.cpp:1372; end = 0) or the mode's exit (Process.cpp:339-342; end = 1), one lane per channel
+__global__ __launch_bounds__(64) void ft8_audio_mark_kernel(int32_t *state, const uint8_t *mask, int nchan, int end) {
+  const int ch = blockIdx.x * 64 + threadIdx.x;
+  if (ch >= nchan || (mask && !mask[ch])) return;
+  int32_t *w = state + (size_t)ch * kFt8Words;
+  w[kFt8Counter] = 0;
+  if (end) {
+    w[kFt8Sync] = 0;
+    w[kFt8Flag] = 0;
+  }
+}
+
+hipError_t launch_ft8_audio(const Ft8AudioArgs &a, hipStream_t s) {
+  if (a.nchan <= 0 || a.nframes <= 0 || a.nframes > kFt8MaxFrames || !a.pcm || !a.state || !a.power || !a.status || !a.window || !a.mag_db || !a.tab)
+    return hipErrorInvalidConfiguration;
+  if (a.q15)
+    hipLaunchKernelGGL(ft8_audio_kernel<short>, dim3((unsigned)a.nchan), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL(ft8_audio_kernel<float>, dim3((unsigned)a.nchan), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_ft8_audio_mark(int32_t *state, const uint8_t *mask, int nchan, int end, hipStream_t s) {
+  if (nchan <= 0 || !state) return hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(ft8_audio_mark_kernel, dim3((unsigned)((nchan + 63) / 64)), dim3(64), 0, s, state, mask, nchan, end);
+  return hipGetLastError();
 }
 
 void ft8_make_fft_tables(uint32_t *tab) {

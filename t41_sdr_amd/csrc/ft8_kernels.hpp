@@ -56,6 +56,25 @@ struct Ft8Args {
 hipError_t launch_ft8(const Ft8Args &a, hipStream_t s);
 // auto_sync_FT8()'s success branch on the channels whose mask byte is non-zero (mask: device pointer, or null for all)
 hipError_t launch_ft8_sync(int32_t *state, const uint8_t *mask, int nchan, int32_t t0, int32_t num, int32_t den, hipStream_t s);
+// FT8 from 12 kS/s audio: the collector of DEMOD_FT8_WAV (Process.cpp:278-335) in front of the same transform, on the same
+// record, power halves and status words.  128 samples per frame, 68 cells of each third of the buffer per frame.
+constexpr int kFt8AudioFrame = 128;
+constexpr int kFt8AudioCells = 68;
+struct Ft8AudioArgs {
+  const void *pcm;        // [nchan][nframes * 128] int16 (q15 != 0) or float, channel-major (read only)
+  int32_t *state;         // [nchan][kFt8Words]
+  uint8_t *power;         // [nchan][2][kFt8HalfBytes]
+  int32_t *status;        // [nchan][nframes][4], as Ft8Args::status
+  const float *window;    // [kFt8Fft] (device)
+  const float *mag_db;    // [kFt8MagEntries] (device)
+  const uint32_t *tab;    // [kFt8TabWords] (device)
+  int nchan, nframes;     // nframes <= kFt8MaxFrames
+  int q15;
+};
+hipError_t launch_ft8_audio(const Ft8AudioArgs &a, hipStream_t s);
+// setupFT8Wav()'s FT_8_counter = 0 (end = 0) or the mode's exit, syncFlag = FT_8_counter = ft8_flag = 0 (end = 1), on the
+// channels whose mask byte is non-zero (mask: device pointer, or null for all)
+hipError_t launch_ft8_audio_mark(int32_t *state, const uint8_t *mask, int nchan, int end, hipStream_t s);
 // the tables above (host)
 void ft8_make_fft_tables(uint32_t *tab);
 

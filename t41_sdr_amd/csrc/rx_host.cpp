@@ -1620,6 +1620,81 @@ int t41rx_ft8_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes) {
   return T41RX_OK;
 }
 
+// ---- FT8 from 12 kS/s audio (DEMOD_FT8_WAV) ----
+namespace {
+// everything is checked before anything is allocated, launched or written
+int ft8_audio_refusal(const t41rx_ctx *ctx, const void *pcm, int n_frames, unsigned align_mask) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (!ctx->ft8_have_tables) return fail(T41RX_ERR_ARG, "FT8 audio: no tables loaded (t41rx_set_ft8_tables)");
+  if (!ctx->ft8_on) return fail(T41RX_ERR_ARG, "FT8 audio: FT8 receive is off (t41rx_set_ft8: no d_power / d_status to write)");
+  if (n_frames < 1) return fail(T41RX_ERR_ARG, "FT8 audio: n_frames must be >= 1");
+  if (n_frames > T41RX_FT8_MAX_FRAMES) return fail(T41RX_ERR_ARG, "FT8 audio: n_frames must be <= 1380 (at most one completed slot per call)");
+  if (n_frames > ctx->ft8_frames) return fail(T41RX_ERR_ARG, "FT8 audio: n_frames exceeds the max_frames the FT8 status buffer was set with");
+  if (!pcm) return fail(T41RX_ERR_ARG, "FT8 audio: no samples (NULL pointer)");
+  if (reinterpret_cast<uintptr_t>(pcm) & align_mask) return fail(T41RX_ERR_ARG, "FT8 audio: the sample pointer is not aligned to its type");
+  return T41RX_OK;
+}
+
+int ft8_audio_device(t41rx_ctx *ctx, const void *d_pcm, int n_frames, bool q15) {
+  if (const int rc = ft8_audio_refusal(ctx, d_pcm, n_frames, q15 ? 1u : 3u)) return rc;
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  if (const int rc = ensure_ft8(ctx)) return rc;
+  Ft8AudioArgs a{};
+  a.pcm = d_pcm;
+  a.state = ctx->d_ft8.get();
+  a.power = ctx->ft8_power;
+  a.status = ctx->ft8_status;
+  a.window = ctx->d_ft8_win.get();
+  a.mag_db = ctx->d_ft8_mag.get();
+  a.tab = ctx->d_ft8_tab.get();
+  a.nchan = ctx->nchan;
+  a.nframes = n_frames;
+  a.q15 = q15 ? 1 : 0;
+  const hipError_t e = launch_ft8_audio(a, nullptr);
+  if (e != hipSuccess) return hip_fail(e, "FT8 audio kernel launch");
+  return T41RX_OK;
+}
+
+int ft8_audio_host(t41rx_ctx *ctx, const void *pcm, int n_frames, bool q15) {
+  if (const int rc = ft8_audio_refusal(ctx, pcm, n_frames, q15 ? 1u : 3u)) return rc;
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  const size_t bytes = (size_t)ctx->nchan * (size_t)n_frames * kFt8AudioFrame * (q15 ? sizeof(int16_t) : sizeof(float));
+  DevBuf<char> staged;
+  if (dev_alloc(staged, bytes) != hipSuccess) return fail(T41RX_ERR_NOMEM, "FT8 audio: staging allocation failed");
+  HIP_TRY(hipMemcpy(staged.get(), pcm, bytes, hipMemcpyHostToDevice));
+  if (const int rc = ft8_audio_device(ctx, staged.get(), n_frames, q15)) return rc;
+  HIP_TRY(hipDeviceSynchronize());  // (the staging buffer is read until the kernel ends)
+  return T41RX_OK;
+}
+
+int ft8_audio_mark(t41rx_ctx *ctx, const uint8_t *channels, int n, int end) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (channels && n != ctx->nchan) return fail(T41RX_ERR_ARG, "n must equal n_channels");
+  if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "FT8 receive is built for fft_length 512");
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  HIP_TRY(hipDeviceSynchronize());
+  if (const int rc = ensure_ft8(ctx)) return rc;
+  DevBuf<uint8_t> mask;
+  if (channels) {
+    HIP_TRY(dev_alloc(mask, (size_t)ctx->nchan));
+    HIP_TRY(hipMemcpy(mask.get(), channels, (size_t)ctx->nchan, hipMemcpyHostToDevice));
+  }
+  HIP_TRY(launch_ft8_audio_mark(ctx->d_ft8.get(), mask.get(), ctx->nchan, end, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  return T41RX_OK;
+}
+}  // namespace
+
+int t41rx_ft8_audio_device_q15(t41rx_ctx *ctx, const int16_t *d_pcm, int n_frames) { return ft8_audio_device(ctx, d_pcm, n_frames, true); }
+int t41rx_ft8_audio_device(t41rx_ctx *ctx, const float *d_audio, int n_frames) { return ft8_audio_device(ctx, d_audio, n_frames, false); }
+int t41rx_ft8_audio_host_q15(t41rx_ctx *ctx, const int16_t *pcm, int n_frames) { return ft8_audio_host(ctx, pcm, n_frames, true); }
+int t41rx_ft8_audio_host(t41rx_ctx *ctx, const float *audio, int n_frames) { return ft8_audio_host(ctx, audio, n_frames, false); }
+int t41rx_ft8_audio_begin(t41rx_ctx *ctx, const uint8_t *channels, int n) { return ft8_audio_mark(ctx, channels, n, 0); }
+int t41rx_ft8_audio_end(t41rx_ctx *ctx, const uint8_t *channels, int n) { return ft8_audio_mark(ctx, channels, n, 1); }
+
 // ---- FT8 decode of a finished slot ----
 int t41rx_set_ft8_decode_tables(t41rx_ctx *ctx, const uint8_t *costas, const uint8_t *gray, const uint8_t *nm, const uint8_t *mn,
                                 const uint8_t *nrw) {

@@ -221,6 +221,60 @@ def unpack77_fields(a91):
     return -1, "", "", ""
 
 
+SLOT_SAMPLES = 1380 * 128  # a slot of DEMOD_FT8_WAV: 92 blocks of 15 frames of 128 samples at 12 kS/s
+
+
+def read_wav(path):
+    """the samples of a WAV file as an int16 array, with stdlib `wave` alone and load_wav()'s acceptance rules
+    (Utility.cpp:830): PCM, one channel, 16 bits; anything else raises ValueError.  Like the firmware it does not ask for
+    the sample rate: the collector takes the samples as 12 kS/s."""
+    import wave
+    try:
+        with wave.open(path, "rb") as f:  # (wave itself reads nothing but PCM)
+            if f.getcomptype() != "NONE" or f.getnchannels() != 1 or f.getsampwidth() != 2:
+                raise ValueError("%s: not a PCM, mono, 16-bit WAV file (channels %d, bytes per sample %d)"
+                                 % (path, f.getnchannels(), f.getsampwidth()))
+            raw = f.readframes(f.getnframes())
+    except wave.Error as e:
+        raise ValueError("%s: %s" % (path, e))
+    return np.frombuffer(raw, "<i2").astype(np.int16)
+
+
+def _golden_decode_tables():
+    import os
+    d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "ft8")
+    try:
+        ldpc, costas = np.load(os.path.join(d, "ldpc.npz")), np.load(os.path.join(d, "costas.npz"))
+    except OSError:
+        raise ValueError("decode_recordings: no tables given and none under %s (the library has no table of its own)" % d)
+    return costas["kCostas_map"], ldpc["kGray_map"], ldpc["kNm"], ldpc["kMn"], ldpc["kNrw"]
+
+
+def decode_recordings(recordings, device=0, tables=None):
+    """A decode farm on 12 kS/s recordings: a list of int16 arrays of at least 176 640 samples (a 15 s slot; what follows
+    is not read) -> per recording the list of its de-duplicated message texts.  One chain with a channel per recording, one
+    call of 1380 frames through the collector of DEMOD_FT8_WAV (RxChain.ft8_audio), ft8_decode() on the finished half and
+    messages(); the receive chain does not run.  tables = (kCostas_map, kGray_map, kNm, kMn, kNrw) of ft8_constants.cpp; None
+    reads the fixtures of a source tree (tests/golden/ft8)."""
+    from .rx import RxChain, default_params
+    recs = [np.asarray(r) for r in recordings]
+    if not recs:
+        return []
+    for k, r in enumerate(recs):
+        if r.dtype != np.int16 or r.ndim != 1 or r.size < SLOT_SAMPLES:
+            raise ValueError("recording %d must be a 1-d int16 array of at least %d samples, got %s %r" % (k, SLOT_SAMPLES, r.dtype, r.shape))
+    pcm = np.ascontiguousarray(np.stack([r[:SLOT_SAMPLES] for r in recs]))
+    rx = RxChain(len(recs), default_params(mode=0), device=device)
+    rx.set_ft8_tables()
+    rx.set_ft8_decode_tables(*(_golden_decode_tables() if tables is None else tables))
+    rx.set_ft8(1, SLOT_SAMPLES // 128)
+    rx.ft8_audio_begin()
+    done = rx.ft8_audio(pcm)[:, -1, 2].cpu().numpy()
+    if (done < 1).any():
+        raise RuntimeError("decode_recordings: a slot did not complete in its 1380 frames")
+    return [[m["text"] for m in found] for found in messages(rx.ft8_decode(select=done - 1))]
+
+
 def _cdiv(a, b):
     q = abs(a) // abs(b)
     return q if (a >= 0) == (b > 0) else -q

@@ -423,6 +423,57 @@ class RxChain:
         buf = np.ascontiguousarray(buf, dtype=np.uint8)
         check(self._lib.t41rx_ft8_set_state(self._ctx, buf.ctypes.data_as(C.c_void_p), buf.size))
 
+    # -- FT8 from 12 kS/s audio (DEMOD_FT8_WAV) ----------------------------------------------
+    def ft8_audio(self, pcm):
+        """The collector of DEMOD_FT8_WAV (Process.cpp:278-335; t41rx_ft8_audio_*) on 12 kS/s audio, without the receive
+        chain: pcm [n_channels, 128 * k], int16 (a WAV file's samples, taken as they are) or float32 (through
+        arm_float_to_q15), a CUDA tensor (default stream, no synchronisation) or a numpy array.  Always channel-major:
+        the input map and the buffer layout do not apply.  Needs set_ft8(1, max_frames >= k); writes the same power halves
+        and returns the call's status words, the view ft8_status(k)."""
+        n = self.n_channels
+        if isinstance(pcm, np.ndarray):
+            if pcm.dtype not in (np.int16, np.float32):
+                raise ValueError("pcm must be int16 or float32, got %s" % pcm.dtype)
+            a = np.ascontiguousarray(pcm)
+            k = self._ft8_audio_frames(a.shape)
+            fn = self._lib.t41rx_ft8_audio_host_q15 if a.dtype == np.int16 else self._lib.t41rx_ft8_audio_host
+            check(fn(self._ctx, a.ctypes.data_as(C.c_void_p), k))
+            return self.ft8_status(k)
+        import torch
+        if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dtype in (torch.int16, torch.float32) and pcm.is_contiguous()):
+            raise ValueError("pcm must be a contiguous int16 or float32 CUDA tensor or numpy array")
+        if pcm.device.index != self.device:
+            raise ValueError("pcm lives on another device than this RxChain")
+        k = self._ft8_audio_frames(tuple(pcm.shape))
+        fn = self._lib.t41rx_ft8_audio_device_q15 if pcm.dtype == torch.int16 else self._lib.t41rx_ft8_audio_device
+        check(fn(self._ctx, C.c_void_p(pcm.data_ptr()), k))
+        return self.ft8_status(k)
+
+    def _ft8_audio_frames(self, shape):
+        if len(shape) != 2 or shape[0] != self.n_channels or shape[1] < 128 or shape[1] % 128:
+            raise ValueError("pcm must be [n_channels = %d, 128 * k], got %r" % (self.n_channels, tuple(shape)))
+        if getattr(self, "_ft8", None) is None:
+            raise ValueError("FT8 receive is off")
+        return shape[1] // 128
+
+    def _ft8_audio_mark(self, fn, channels):
+        if channels is None:
+            check(fn(self._ctx, None, 0))
+            return
+        m = np.ascontiguousarray(np.asarray(channels).astype(bool).astype(np.uint8))
+        if m.shape != (self.n_channels,):
+            raise ValueError("channels must have n_channels = %d entries, got %r" % (self.n_channels, m.shape))
+        check(fn(self._ctx, m.ctypes.data_as(C.c_void_p), self.n_channels))
+
+    def ft8_audio_begin(self, channels=None):
+        """setupFT8Wav() (ft8.cpp:1372) on the channels whose entry is non-zero (None: all): FT_8_counter = 0, nothing else"""
+        self._ft8_audio_mark(self._lib.t41rx_ft8_audio_begin, channels)
+
+    def ft8_audio_end(self, channels=None):
+        """the WAV mode's exit (Process.cpp:339-342) on the channels whose entry is non-zero (None: all): syncFlag = 0,
+        FT_8_counter = 0, ft8_flag = 0, nothing else"""
+        self._ft8_audio_mark(self._lib.t41rx_ft8_audio_end, channels)
+
     def set_ft8_decode_tables(self, costas, gray, nm, mn, nrw):
         """The FT8 decode's tables (t41rx_set_ft8_decode_tables): kCostas_map[7], kGray_map[8], kNm[83][7], kMn[174][3] and
         kNrw[83] of ft8_constants.cpp as uint8.  The library has no table of its own, and refuses tables that would take
