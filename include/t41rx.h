@@ -437,7 +437,7 @@ T41RX_API int t41rx_set_audio_spectrum(t41rx_ctx *ctx, float *d_spect, float *d_
  * 1..4 = 2x..16x: Fs/4 shift, 4-stage elliptic IIR mag_coeffs[zoom], 4-tap decimating FIR by 2^zoom,
  * 512-sample ring, window, FFT; Process.cpp:211-215), both up to FFT_spec[512] (squared magnitudes,
  * halves swapped so that DC sits at index 256) and the display's low-pass memory FFT_spec_old[512].
- * The pixel mapping behind them (log10f_fast, display scale, pixel offsets) stays with the caller.
+ * The pixel mapping behind them (log10f_fast, display scale, pixel offsets) is t41rx_set_panadapter()'s, below.
  * Device pointers, both NULL = off (the default).  While set, every processed frame is treated as
  * one with updateDisplayFlag == 1 and writes
  *   d_spec     : [n_channels][n_frames][512]  FFT_spec
@@ -678,6 +678,81 @@ T41RX_API int t41rx_ft8_decode_device(t41rx_ctx *ctx, const uint8_t *d_waterfall
                             int n, t41rx_ft8_result *d_results, void *hip_stream);
 T41RX_API int t41rx_ft8_decode_host(t41rx_ctx *ctx, const uint8_t *d_waterfall, size_t channel_stride_bytes, const int8_t *select,
                           int n, t41rx_ft8_result *results);
+
+/* ---- the panadapter: ShowSpectrum()'s pixels and waterfall row, DrawSmeterBar()'s dBm (Display.cpp:240-504, 955-1030) ----
+ * A stage of the receive path, default off, fft_length 512: per channel the display FFT of t41rx_set_display_spectrum(),
+ * and behind it, in the firmware's integer arithmetic, what ShowSpectrum() draws from -- at the firmware's cadence.  A
+ * context that does not switch it on is unchanged; with it on, the audio of every call is bit for bit the audio without it.
+ *
+ * Cadence.  The stage counts the frames of the process calls, n = 0 at t41rx_set_panadapter() and t41rx_reset(); the
+ *   counter is host-side configuration (t41rx_get_panadapter / t41rx_set_panadapter_counter), in no checkpoint.  Frame n
+ *   is an update frame -- one with updateDisplayFlag == 1 -- when n % update_period == update_phase; the firmware sets the
+ *   flag once per sweep of 511 ProcessIQData() calls (Display.cpp:259-267): update_period 511.  Every other frame does no
+ *   display work (Process.cpp:185-187, 212, 550, 791; FFT.cpp:209): no display FFT, no zoom filter, ring, low-pass or pixel
+ *   memory advances, and audioMaxSquaredAve (the path's own word, in the checkpoint as before) stays -- while the stage is
+ *   on it advances on update frames only.  At spectrumZoom 1..4 the zoom chain therefore sees the update frames' samples
+ *   back to back: the firmware's own discontinuity.  A process call without an update frame launches exactly the kernels
+ *   of a context without the stage; the update frames of a call are frames f with (n0 + f) % update_period == update_phase,
+ *   n0 the counter in front of the call, and their rows k = 0, 1, .. are written in frame order.
+ * Per row, x = 0 .. 511 (x = 256 is DC, as for FFT_spec):
+ *   spec[x]      FFT_spec: t41rx_set_display_spectrum()'s transform (un-smoothed at spectrumZoom 0, smoothed at 1..4)
+ *   pixel[x]     pixelnew[x] = baseOffset + pixel_offset + (int16_t)(dBScale * log10f_fast(FFT_spec[x])) (FFT.cpp:157, 245),
+ *                {dBScale, baseOffset} = displayScale[currentScale] (Display.cpp:127-135)
+ *   y_new[x]     spectrumNoiseFloor - pixelnew[x] - currentNF held to [100, 249] = [SPECTRUM_TOP_Y, SPECTRUM_BOTTOM]
+ *   y_old[x]     spectrumNoiseFloor - pixelold[x] - oldNF likewise: pixelold[] = the row before's pixelnew[] (zero at
+ *                power-on), oldNF = the row before's currentNF, or this row's on the first row after t41rx_set_panadapter()
+ *                or t41rx_reset() (newSpectrumFlag, Display.cpp:250-256, 474)
+ *   waterfall[x] gradient[230 - y_new[x] held to 0 .. 116] for x = 0 .. 510 (Display.cpp:460-466); the firmware never
+ *                writes waterfall[511]: 0 here
+ *   audio_spect  audioSpectBuffer[1024] of the update frame, as t41rx_set_audio_spectrum() writes it
+ *   smeter[4]    audioMaxSquared, (float)AudioMaxIndex, audioMaxSquaredAve behind the frame, and dbm: the TCVSDR_SMETER
+ *                form of Display.cpp:980-981 in its operand types and order -- dbm_calibration (22) + gainCorrection +
+ *                (float32_t)attenuator + slope (10) * log10f_fast(audioMaxSquaredAve) + cons (-92) in float, then
+ *                - (float32_t)RFgain * 1.5 - rfGainAllBands in double, stored to a float, without contraction (whether the
+ *                firmware's compiler contracts slope * log + sum is not pinned: DESIGN.md).  RFgain and rfGainAllBands
+ *                are the params'.
+ *   The drawing itself, map() for the bar's length, audioYPixel and the control-app records stay with the caller.
+ * The stage's memory -- the display state, pixelold[512], oldNF and newSpectrumFlag per channel -- is the context's own,
+ *   like the calibration memory: zero at t41rx_set_panadapter(on) and t41rx_reset(), NOT part of the checkpoint
+ *   (t41rx_state_bytes(), the section mask and the ABI are unchanged) and left alone by t41rx_set_state().
+ * t41rx_set_panadapter_tables(): gradient[] (Display.cpp:148-161), n == 117 uint16 colour words, a host array, copied
+ *   (synchronises).  The library has no table of its own.  T41RX_ERR_ARG for NULL or n != 117.
+ * t41rx_set_panadapter(): on = 0 switches the stage off (the other arguments are ignored).  out: device pointers of the
+ *   caller's row buffers [n_channels][max_rows][...], each 16-byte aligned or NULL (not written); the struct is copied.
+ *   A call with k update frames writes rows 0 .. k-1 of every channel and leaves the others alone.  The stage's own tap
+ *   buffer holds max_rows rows (16 KiB each per channel), not frames.  T41RX_ERR_ARG, nothing changed: no table loaded,
+ *   spectrumZoom or currentScale outside 0..4, pixel_offset or spectrumNoiseFloor outside int16, update_period < 1,
+ *   update_phase outside [0, update_period), max_rows < 1, a NULL out, an unaligned pointer.  T41RX_ERR_UNSUPPORTED: a
+ *   long fft_length; t41rx_set_display_spectrum() or t41rx_set_audio_spectrum() set -- and either of those is refused
+ *   likewise while the stage is on: each tap has one owner.  The firmware's values: spectrumNoiseFloor 247 (gwv.cpp:18),
+ *   update_period 511.  Synchronises.
+ * t41rx_set_panadapter_levels(): currentNoiseFloor[currentBand] and bands[currentBand].gainCorrection per channel, host
+ *   arrays of n_channels entries, copied (NULL = zeros; zeros until first set), and `attenuator` (Display.cpp:146).  They
+ *   hold from the next process call: a noise floor changed between two rows gives the next row oldNF != currentNF.
+ *   T41RX_ERR_ARG for a noise floor outside int16 or a non-finite correction.  Synchronises.
+ * A process call (every mode, f32 and q15 entries, both layouts, with an input map; the device forms enqueue without a
+ *   sync) that would hold more than max_rows update frames is refused with T41RX_ERR_ARG and processes nothing.
+ * t41rx_get_panadapter(): 1 / 0 = the stage is on / off (negative: an error status); any pointer may be NULL.
+ *   frame_counter: n behind the last call; rows_written: the rows the last process call wrote; first_row_frame: the n of
+ *   its row 0, or -1 when it wrote none.  t41rx_set_panadapter_counter(): n >= 0 (T41RX_ERR_ARG otherwise). */
+typedef struct t41rx_panadapter_out {
+  int16_t  *pixel;       /* [n_channels][max_rows][512]  pixelnew */
+  int16_t  *y_new;       /* [n_channels][max_rows][512] */
+  int16_t  *y_old;       /* [n_channels][max_rows][512] */
+  uint16_t *waterfall;   /* [n_channels][max_rows][512] */
+  float    *spec;        /* [n_channels][max_rows][512]  FFT_spec */
+  float    *audio_spect; /* [n_channels][max_rows][1024] audioSpectBuffer */
+  float    *smeter;      /* [n_channels][max_rows][4]    audioMaxSquared, AudioMaxIndex, audioMaxSquaredAve, dbm */
+} t41rx_panadapter_out;
+#define T41RX_PANADAPTER_GRADIENT 117
+#define T41RX_PANADAPTER_NOISE_FLOOR 247 /* spectrumNoiseFloor, gwv.cpp:18 */
+#define T41RX_PANADAPTER_PERIOD 511      /* SPECTRUM_RES - 1 ProcessIQData() calls per sweep, Display.cpp:259 */
+T41RX_API int t41rx_set_panadapter_tables(t41rx_ctx *ctx, const uint16_t *gradient, int n);
+T41RX_API int t41rx_set_panadapter(t41rx_ctx *ctx, int on, int spectrumZoom, int currentScale, int pixel_offset, int spectrumNoiseFloor,
+                         int update_period, int update_phase, const t41rx_panadapter_out *out, int max_rows);
+T41RX_API int t41rx_set_panadapter_levels(t41rx_ctx *ctx, const int32_t *noise_floor, const float *gain_correction, int attenuator);
+T41RX_API int t41rx_get_panadapter(const t41rx_ctx *ctx, int64_t *frame_counter, int32_t *rows_written, int64_t *first_row_frame);
+T41RX_API int t41rx_set_panadapter_counter(t41rx_ctx *ctx, int64_t n);
 
 #ifdef __cplusplus
 }

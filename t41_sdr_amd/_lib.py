@@ -45,6 +45,19 @@ class Params(C.Structure):
     ]
 
 
+class PanadapterOut(C.Structure):
+    """struct t41rx_panadapter_out (include/t41rx.h): device pointers of the panadapter's row buffers, each may be NULL."""
+    _fields_ = [
+        ("pixel", C.c_void_p),
+        ("y_new", C.c_void_p),
+        ("y_old", C.c_void_p),
+        ("waterfall", C.c_void_p),
+        ("spec", C.c_void_p),
+        ("audio_spect", C.c_void_p),
+        ("smeter", C.c_void_p),
+    ]
+
+
 # every symbol include/t41rx.h declares: (restype, argtypes)
 _vp, _fp = C.c_void_p, C.POINTER(C.c_float)
 SYMBOLS = {
@@ -120,6 +133,11 @@ SYMBOLS = {
     "t41rx_set_ft8_decode_debug": (C.c_int, [_vp, _vp, _vp]),
     "t41rx_ft8_decode_device": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_int, _vp, _vp]),
     "t41rx_ft8_decode_host": (C.c_int, [_vp, _vp, C.c_size_t, _vp, C.c_int, _vp]),
+    "t41rx_set_panadapter_tables": (C.c_int, [_vp, C.POINTER(C.c_uint16), C.c_int]),
+    "t41rx_set_panadapter": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(PanadapterOut), C.c_int]),
+    "t41rx_set_panadapter_levels": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int]),
+    "t41rx_get_panadapter": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "t41rx_set_panadapter_counter": (C.c_int, [_vp, C.c_int64]),
 }
 
 _lib = None

@@ -19,29 +19,13 @@
 //   pixelnew[] = baseOffset + pixel_offset + (int16_t)(dBScale * log10f_fast(FFT_spec[]))   FFT.cpp:157, 245
 // and in every frame, from the channel's current pixelnew[]: arm_max_q15 over the two windows and adjdB (:498-505, 524).
 #include "rx_kernels.hpp"
+#include "display_pixel.hpp"
 #include "wave_fft.hpp"
 #include "zoom_fft.hpp"
 
 namespace t41 {
 
 namespace {
-
-// log10f_fast(), Utility.cpp:245-258, in f32 as written; frexpf(0) = 0 with exponent 0, so log10f_fast(0) is finite
-__device__ __forceinline__ float cal_log10f_fast(float X) {
-#pragma clang fp contract(off)
-  const float t = fabsf(X);
-  const float F = __builtin_amdgcn_frexp_mantf(t);
-  const int E = __builtin_amdgcn_frexp_expf(t);
-  float Y = 1.23149591368684f;
-  Y *= F;
-  Y += -4.11852516267426f;
-  Y *= F;
-  Y += 6.02197014179219f;
-  Y *= F;
-  Y += -3.13396450166353f;
-  Y += (float)E;
-  return Y * 0.3010299956639812f;
-}
 
 // one sample up to and including FreqShift1(): n & 3 selects the quarter turn (Freq_Shift.cpp:42-65)
 __device__ __forceinline__ cf cal_sample(const CalArgs &a, size_t idx, int n, float neg_amp, float phase) {
@@ -194,8 +178,7 @@ __global__ __launch_bounds__(64) void cal_kernel(const CalArgs a) {
         const float m = v[r].x * v[r].x + v[r].y * v[r].y;
         // the pixel: from the un-smoothed FFT_spec at zoom 0 (FFT.cpp:245), from the smoothed one at zoom 1..4 (:157)
         const float spec = zoom_lowpass(zoom, m, old[r]);
-        // uint16 + int16 + int16 in int, stored to an int16
-        const short p = (short)(a.base + (int)(short)(int)(a.dBScale * cal_log10f_fast(spec)));
+        const short p = display_pixel(a.base, a.dBScale, spec);  // (display_pixel.hpp, shared with the panadapter stage)
         pix[x] = p;
         if (a.spec) a.spec[row + x] = spec;
         if (a.pixel) a.pixel[row + x] = p;

@@ -272,6 +272,16 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
     if (AGC) PRIO(2); else PRIO(3);  // (AGC on: 3 is the serial chain's, see agc_apply)
     FRESH_LANE();
     const bool first_iter = (f == seg0);
+    // the row of this frame in the display taps (dbg_pre, spect, spect_max): its own, [nchan][nframes]; or with a tap
+    // cadence (RxArgs::tap_period, the panadapter stage) compact rows [nchan][tap_rows] for the flagged frames tap_first
+    // + k tap_period only, -1 for every other frame, which then writes no tap and leaves audioMaxSquaredAve alone
+    // (updateDisplayFlag == 0, Process.cpp:185, 212, 550).  Kernel arguments only: the same for every lane and channel.
+    int tap_row = f, tap_stride = a.nframes;
+    if (DEBUG && a.tap_period > 0) {
+      const int d = f - a.tap_first;
+      tap_row = (d >= 0 && d % a.tap_period == 0) ? d / a.tap_period : -1;
+      tap_stride = a.tap_rows;
+    }
     // sample offset of (channel, frame) in I / Q / audio: RxArgs::chan_stride / frame_stride (channel-major
     // [channel][frame][2048]: nframes * 2048 and 2048; time-major [frame][channel][2048]: 2048 and nchan * 2048)
     const size_t chbase = (size_t)ch * (size_t)a.chan_stride;
@@ -686,8 +696,8 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
           STAMP(1);  // DC high-pass, gains, IQ correction
         // -- oscillator for my 8 samples.  Osc_n = V_n * W has phase phase0 + (n+1) dphi.
           const int n0 = 512 * s + 8 * lane;
-          if (DEBUG && a.dbg_pre) {  // what CalcZoom1Magn() sees (Process.cpp:185), input of the display FFT
-            float *dp = a.dbg_pre + ((size_t)ch * a.nframes + f) * (2 * L);
+          if (DEBUG && a.dbg_pre && tap_row >= 0) {  // what CalcZoom1Magn() sees (Process.cpp:185), input of the display FFT
+            float *dp = a.dbg_pre + ((size_t)ch * tap_stride + tap_row) * (2 * L);
   #pragma unroll
             for (int k = 0; k < 8; ++k) {
               dp[n0 + k] = z[k].x;
@@ -1073,12 +1083,13 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
         }
   #pragma unroll
         for (int r = 0; r < 8; ++r) v[r] = cmul(v[r], GMASK ? mk[r] : ltab[kLdsTabMask + 64 * r + lane]);
-        if (DEBUG && a.spect) {
+        if (DEBUG && a.spect_max && tap_row >= 0) {
           // ---- audio spectrum side output (Process.cpp:550-570 with updateDisplayFlag == 1):
           // audioSpectBuffer[1023 - k] = iFFT_buffer[k]^2 over the 1024 floats of the masked
           // spectrum.  The mask table carries 1/N (the reference applies it in the inverse FFT):
           // a power of two, so squaring after undoing it is exact.  v[r] = bin lane + 64 r.
-          float *sp = a.spect + ((size_t)ch * a.nframes + f) * 1024;
+          // (a.spect may be null with the panadapter stage, which always takes the maximum: no spectrum rows then)
+          float *sp = a.spect ? a.spect + ((size_t)ch * tap_stride + tap_row) * 1024 : nullptr;
           float best = -1.0f;
           int besti = 0;
   #pragma unroll
@@ -1086,7 +1097,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
             const int k = lane + 64 * r;
             const float re = v[r].x * 512.0f, im = v[r].y * 512.0f;
             const float e0 = im * im, e1 = re * re;  // buffer indices 1022 - 2k, 1023 - 2k
-            *reinterpret_cast<float2 *>(sp + 1022 - 2 * k) = make_float2(e0, e1);
+            if (sp) *reinterpret_cast<float2 *>(sp + 1022 - 2 * k) = make_float2(e0, e1);
             // arm_max_f32: the first occurrence of the maximum = the smallest buffer index
             if (e1 >= best) { best = e1; besti = 1023 - 2 * k; }
             if (e0 >= best) { best = e0; besti = 1022 - 2 * k; }
@@ -1098,7 +1109,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
             if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
           }
           if (lane == 0) {
-            float *mx = a.spect_max + ((size_t)ch * a.nframes + f) * 3;
+            float *mx = a.spect_max + ((size_t)ch * tap_stride + tap_row) * 3;
             const float ave = (float)(.5 * (double)best + .5 * (double)st[kStMisc + kMiscMaxSqAve]);  // :570
             mx[0] = best;
             mx[1] = (float)besti;

@@ -31,6 +31,7 @@
 #include "nb_kernels.hpp"
 #include "nb_kernel.hip"  // the noise blanker's kernel and launcher
 #include "nr_kernels.hpp"
+#include "panadapter_kernel.hip"  // the panadapter stage's kernel and launcher
 #include "rx_experiments.hpp"
 #include "rx_internal.hpp"
 #include "rx_kernels.hpp"
@@ -114,6 +115,23 @@ struct t41rx_ctx {
   int cal_zoom = 0, cal_base = 0, cal_lo0 = 0, cal_lo1 = 0, cal_width = 0;
   float cal_dbscale = 0.0f;
   DevBuf<float> d_cal, d_cal_corr;
+  // the panadapter stage (ShowSpectrum() / DrawSmeterBar(), Display.cpp:240-504, 955-1030; t41rx_set_panadapter_tables /
+  // _panadapter / _panadapter_levels): the caller's gradient[] (device copy), the settings, the caller's row buffers, the
+  // levels per channel (device copies), the compact taps of a call's update frames [nchan][max_rows][...] that the tap
+  // kernels write and panadapter_kernel reads, and the panadapter memory [nchan][kPanFloats] (rx_internal.hpp).  The
+  // context's own: no checkpoint section, t41rx_set_state() leaves it alone.  The frame counter lives here, on the host.
+  bool pan_on = false, pan_have_tables = false;
+  t41rx_panadapter_out pan_out{};
+  int pan_zoom = 0, pan_scale = 0, pan_pixel_offset = 0, pan_floor_y = 0, pan_period = 1, pan_phase = 0, pan_max_rows = 0;
+  int pan_attenuator = 0;
+  int pan_alloc_rows = 0;       // rows d_pan_pre / d_pan_max hold
+  long long pan_counter = 0;    // frames processed since the setter / t41rx_reset() / t41rx_set_panadapter_counter()
+  int pan_call_first = 0, pan_call_rows = 0;  // of the call being prepared: its first update frame, their number
+  int pan_last_rows = 0;        // t41rx_get_panadapter(): rows the last call wrote, and the frame index of the first
+  long long pan_last_first = -1;
+  DevBuf<uint16_t> d_pan_grad;
+  DevBuf<int32_t> d_pan_nf;
+  DevBuf<float> d_pan_gc, d_pan_pre, d_pan_max, d_pan_mem;
   // FT8 receive up to the waterfall (Process.cpp:627-686, ft8.cpp:153-268; t41rx_set_ft8_tables / _ft8 / _ft8_clock /
   // t41rx_ft8_sync): the caller's window and mag_db (device copies), arm_rfft_q15's tables, the switch with the caller's
   // power and status buffers, the clock millis(n) = t0 + floor(n * num / den), and the FT8 memory per channel
@@ -171,6 +189,9 @@ int hip_check(hipError_t e, const char *what) { return e == hipSuccess ? T41RX_O
   } while (0)
 
 constexpr float kPiF = 3.1415926535897932384626433832795f;  // FIR.h:10
+// displayScale[] (Display.cpp:127-135): dBScale, baseOffset -- the calibration's and the panadapter's pixel mapping
+constexpr float kDbScale[5] = {10.0f, 20.0f, 40.0f, 100.0f, 200.0f};
+constexpr int kBaseOffset[5] = {24, 10, 58, 120, 200};
 
 // FreqShift2's per-call constants (Freq_Shift.cpp:121-124) turned into what the kernel needs:
 // the rotation per sample as a 0.64 fixed-point fraction of a turn, the steady-state
@@ -653,6 +674,16 @@ bool pipe_on(const t41rx_ctx *ctx, int n_frames) {
 int prepare_call(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
   const int seg = ctx->params.fft_length / 512;
   int rc = T41RX_OK;
+  // the panadapter stage: which frames of this call are update frames, in front of everything that allocates
+  ctx->pan_call_rows = 0;
+  ctx->pan_call_first = n_frames;
+  if (ctx->pan_on) {
+    ctx->pan_call_rows = pan_rows_of_call(ctx->pan_counter, n_frames, ctx->pan_period, ctx->pan_phase, &ctx->pan_call_first);
+    if (ctx->pan_call_rows > ctx->pan_max_rows)
+      return fail(T41RX_ERR_ARG, "the call holds more update frames than the max_rows the panadapter buffers were set with");
+    if (!ctx->d_pan_pre || !ctx->d_pan_max || !ctx->d_pan_mem || !ctx->d_pan_nf || !ctx->d_pan_gc || !ctx->d_pan_grad || !ctx->d_win)
+      return fail(T41RX_ERR_STATE, "panadapter enabled without its buffers");
+  }
   if ((nr_on(ctx) && (rc = ensure_nr(ctx)) != T41RX_OK) || (ctx->nb_on && (rc = ensure_nb(ctx)) != T41RX_OK) ||
       (ctx->eq_on && (rc = ensure_eq(ctx)) != T41RX_OK) ||
       ((cw_filter_on(ctx) || cw_det_on(ctx)) && (rc = ensure_cw(ctx)) != T41RX_OK))
@@ -779,6 +810,16 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
   if (ctx->ft8_on && !stages_on(ctx) && !a.dbg_demod) a.dbg_demod = ctx->d_ft8_tap.get();  // the FT8 stage reads the demod tap
   a.spect = ctx->spect;
   a.spect_max = ctx->spect_max;
+  if (ctx->pan_on && ctx->pan_call_rows > 0) {
+    // the panadapter owns the display taps (one owner each: the setters refuse the other): compact rows for the call's
+    // update frames.  A call without one sets no tap and so launches what a context without the stage launches.
+    a.dbg_pre = ctx->d_pan_pre.get();
+    a.spect = ctx->pan_out.audio_spect;
+    a.spect_max = ctx->d_pan_max.get();
+    a.tap_period = ctx->pan_period;
+    a.tap_first = ctx->pan_call_first;
+    a.tap_rows = ctx->pan_max_rows;
+  }
   if (stages_on(ctx)) a.aud_out = ctx->d_aud24.get();  // the fused kernel stops behind the demodulator
   return a;
 }
@@ -954,6 +995,44 @@ int launch_chain(t41rx_ctx *ctx, RxArgs a, int n_frames, hipStream_t s) {
     e = launch_display(d, s);
     if (e != hipSuccess) return hip_fail(e, "display kernel launch");
   }
+  if (ctx->pan_on) {
+    if (ctx->pan_call_rows > 0) {
+      PanArgs p{};
+      p.pre = ctx->d_pan_pre.get();
+      p.mx = ctx->d_pan_max.get();
+      p.mem = ctx->d_pan_mem.get();
+      p.tab = ctx->d_tab.get();
+      p.win = ctx->d_win.get();
+      p.gradient = ctx->d_pan_grad.get();
+      p.noise_floor = ctx->d_pan_nf.get();
+      p.gain_correction = ctx->d_pan_gc.get();
+      p.pixel = ctx->pan_out.pixel;
+      p.y_new = ctx->pan_out.y_new;
+      p.y_old = ctx->pan_out.y_old;
+      p.waterfall = ctx->pan_out.waterfall;
+      p.spec = ctx->pan_out.spec;
+      p.smeter = ctx->pan_out.smeter;
+      p.nchan = ctx->nchan;
+      p.nrows = ctx->pan_call_rows;
+      p.max_rows = ctx->pan_max_rows;
+      p.zoom = ctx->pan_zoom;
+      if (p.zoom > 0) {
+        std::memcpy(p.iir, kZoomIirCoeffs[p.zoom - 1], sizeof(p.iir));
+        design_zoom_fir(p.zoom, p.fir);
+      }
+      p.dBScale = kDbScale[ctx->pan_scale];
+      p.base = kBaseOffset[ctx->pan_scale] + ctx->pan_pixel_offset;
+      p.noise_floor_y = ctx->pan_floor_y;
+      p.attenuator = ctx->pan_attenuator;
+      p.RFgain = ctx->params.RFgain;
+      p.rfGainAllBands = ctx->params.rfGainAllBands;
+      e = launch_panadapter(p, s);
+      if (e != hipSuccess) return hip_fail(e, "panadapter kernel launch");
+    }
+    ctx->pan_last_rows = ctx->pan_call_rows;
+    ctx->pan_last_first = ctx->pan_call_rows > 0 ? ctx->pan_counter + ctx->pan_call_first : -1;
+    ctx->pan_counter += n_frames;
+  }
   return T41RX_OK;
 }
 
@@ -980,6 +1059,16 @@ int ensure_window(t41rx_ctx *ctx) {
   HIP_TRY(dev_alloc(win, sizeof(w)));
   HIP_TRY(hipMemcpy(win.get(), w, sizeof(w), hipMemcpyHostToDevice));
   ctx->d_win = std::move(win);
+  return T41RX_OK;
+}
+
+// the per-channel levels, on the device; values == nullptr: zeros
+template <class T>
+int pan_upload_levels(t41rx_ctx *ctx, DevBuf<T> &d, const T *values) {
+  std::vector<T> h((size_t)ctx->nchan, T(0));
+  if (values) std::memcpy(h.data(), values, sizeof(T) * h.size());
+  if (!d) HIP_TRY(dev_alloc(d, sizeof(T) * h.size()));
+  HIP_TRY(hipMemcpy(d.get(), h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
   return T41RX_OK;
 }
 
@@ -1317,6 +1406,11 @@ int t41rx_reset(t41rx_ctx *ctx) {
   }
   // the calibration memory to power-on: FFT_spec_old, zoom memories, ring, pointer and pixelnew[] all zero
   if (ctx->d_cal) HIP_TRY(hipMemset(ctx->d_cal.get(), 0, sizeof(float) * kCalFloats * (size_t)ctx->nchan));
+  // the panadapter memory and its frame counter likewise (pixelold = 0, newSpectrumFlag = 0)
+  if (ctx->d_pan_mem) HIP_TRY(hipMemset(ctx->d_pan_mem.get(), 0, sizeof(float) * kPanFloats * (size_t)ctx->nchan));
+  ctx->pan_counter = 0;
+  ctx->pan_last_rows = 0;
+  ctx->pan_last_first = -1;
   return reset_state(ctx);
 }
 
@@ -1999,6 +2093,7 @@ int t41rx_set_audio_spectrum(t41rx_ctx *ctx, float *d_spect, float *d_max, int m
   if (d_spect && ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the audio spectrum is built for fft_length 512");
   if ((reinterpret_cast<uintptr_t>(d_spect) | reinterpret_cast<uintptr_t>(d_max)) & 3u) return fail(T41RX_ERR_ARG, "unaligned pointer");
   if (d_spect && max_frames <= 0) return fail(T41RX_ERR_ARG, "max_frames must be > 0");
+  if (d_spect && ctx->pan_on) return fail(T41RX_ERR_UNSUPPORTED, "the panadapter stage is on and owns the audio-spectrum tap (t41rx_set_panadapter)");
   ctx->spect = d_spect;
   ctx->spect_max = d_max;
   ctx->spect_frames = d_spect ? max_frames : 0;
@@ -2016,6 +2111,7 @@ int t41rx_set_display_spectrum(t41rx_ctx *ctx, float *d_spec, float *d_spec_old,
     return T41RX_OK;
   }
   if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the display FFT is built for fft_length 512");
+  if (ctx->pan_on) return fail(T41RX_ERR_UNSUPPORTED, "the panadapter stage is on and owns the display tap (t41rx_set_panadapter)");
   if (spectrumZoom < 0 || spectrumZoom > 4) return fail(T41RX_ERR_ARG, "spectrumZoom must be 0 (1x) .. 4 (16x)");  // MAX_ZOOM_ENTRIES, ButtonProc.h:6
   if (max_frames <= 0) return fail(T41RX_ERR_ARG, "max_frames must be > 0");
   if ((reinterpret_cast<uintptr_t>(d_spec) | reinterpret_cast<uintptr_t>(d_spec_old)) & 3u) return fail(T41RX_ERR_ARG, "unaligned pointer");
@@ -2034,6 +2130,103 @@ int t41rx_set_display_spectrum(t41rx_ctx *ctx, float *d_spec, float *d_spec_old,
   ctx->disp_old = d_spec_old;
   ctx->disp_frames = max_frames;
   ctx->disp_zoom = spectrumZoom;
+  return T41RX_OK;
+}
+
+int t41rx_set_panadapter_tables(t41rx_ctx *ctx, const uint16_t *gradient, int n) {
+  if (!ctx || !gradient) return fail(T41RX_ERR_ARG, "null argument");
+  if (n != kPanGradient) return fail(T41RX_ERR_ARG, "panadapter tables: gradient[] has 117 words (Display.cpp:148-161)");
+  DeviceGuard g(ctx->device);
+  HIP_TRY(hipDeviceSynchronize());  // (a launch still in flight reads the old table)
+  if (!ctx->d_pan_grad) HIP_TRY(dev_alloc(ctx->d_pan_grad, sizeof(uint16_t) * kPanGradient));
+  HIP_TRY(hipMemcpy(ctx->d_pan_grad.get(), gradient, sizeof(uint16_t) * kPanGradient, hipMemcpyHostToDevice));
+  ctx->pan_have_tables = true;
+  return T41RX_OK;
+}
+
+int t41rx_set_panadapter(t41rx_ctx *ctx, int on, int spectrumZoom, int currentScale, int pixel_offset, int spectrumNoiseFloor,
+                         int update_period, int update_phase, const t41rx_panadapter_out *out, int max_rows) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  DeviceGuard g(ctx->device);
+  HIP_TRY(hipDeviceSynchronize());
+  if (!on) {
+    ctx->pan_on = false;
+    return T41RX_OK;
+  }
+  // every refusal in front of the first change: a refused call leaves the stage as it was
+  if (!out) return fail(T41RX_ERR_ARG, "null argument");
+  if (!ctx->pan_have_tables) return fail(T41RX_ERR_ARG, "panadapter: no colour table loaded (t41rx_set_panadapter_tables)");
+  if (spectrumZoom < 0 || spectrumZoom > 4) return fail(T41RX_ERR_ARG, "spectrumZoom must be 0 (1x) .. 4 (16x)");
+  if (currentScale < 0 || currentScale > 4) return fail(T41RX_ERR_ARG, "currentScale must be 0 .. 4");
+  if (pixel_offset < -32768 || pixel_offset > 32767) return fail(T41RX_ERR_ARG, "pixel_offset must fit an int16");
+  if (spectrumNoiseFloor < -32768 || spectrumNoiseFloor > 32767) return fail(T41RX_ERR_ARG, "spectrumNoiseFloor must fit an int16");
+  if (update_period < 1) return fail(T41RX_ERR_ARG, "update_period must be >= 1");
+  if (update_phase < 0 || update_phase >= update_period) return fail(T41RX_ERR_ARG, "update_phase must lie in [0, update_period)");
+  if (max_rows < 1) return fail(T41RX_ERR_ARG, "max_rows must be >= 1");
+  if ((reinterpret_cast<uintptr_t>(out->pixel) | reinterpret_cast<uintptr_t>(out->y_new) | reinterpret_cast<uintptr_t>(out->y_old) |
+       reinterpret_cast<uintptr_t>(out->waterfall) | reinterpret_cast<uintptr_t>(out->spec) | reinterpret_cast<uintptr_t>(out->audio_spect) |
+       reinterpret_cast<uintptr_t>(out->smeter)) & 15u)
+    return fail(T41RX_ERR_ARG, "panadapter: the row buffers must be 16-byte aligned");  // (one rule for all: the audio-spectrum rows leave as 8-byte stores)
+  if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the panadapter stage is built for fft_length 512");
+  if (ctx->disp_spec || ctx->spect)
+    return fail(T41RX_ERR_UNSUPPORTED, "t41rx_set_display_spectrum / t41rx_set_audio_spectrum is set and owns its tap: switch it off first");
+  // anything that fails from here on leaves the stage switched off
+  ctx->pan_on = false;
+  if (max_rows > ctx->pan_alloc_rows || !ctx->d_pan_pre || !ctx->d_pan_max) {
+    ctx->pan_alloc_rows = 0;
+    HIP_TRY(dev_alloc(ctx->d_pan_pre, sizeof(float) * 4096 * (size_t)max_rows * (size_t)ctx->nchan));
+    HIP_TRY(dev_alloc(ctx->d_pan_max, sizeof(float) * 3 * (size_t)max_rows * (size_t)ctx->nchan));
+    ctx->pan_alloc_rows = max_rows;
+  }
+  if (!ctx->d_pan_mem) HIP_TRY(dev_alloc(ctx->d_pan_mem, sizeof(float) * kPanFloats * (size_t)ctx->nchan));
+  if (const int rc = ensure_window(ctx)) return rc;
+  if (!ctx->d_pan_nf)
+    if (const int rc = pan_upload_levels<int32_t>(ctx, ctx->d_pan_nf, nullptr)) return rc;
+  if (!ctx->d_pan_gc)
+    if (const int rc = pan_upload_levels<float>(ctx, ctx->d_pan_gc, nullptr)) return rc;
+  // power-on: ZoomFFTPrep(), FFT_spec_old = 0, pixelold = 0, newSpectrumFlag = 0; the frame counter starts at 0
+  HIP_TRY(hipMemset(ctx->d_pan_mem.get(), 0, sizeof(float) * kPanFloats * (size_t)ctx->nchan));
+  ctx->pan_out = *out;
+  ctx->pan_zoom = spectrumZoom;
+  ctx->pan_scale = currentScale;
+  ctx->pan_pixel_offset = pixel_offset;
+  ctx->pan_floor_y = spectrumNoiseFloor;
+  ctx->pan_period = update_period;
+  ctx->pan_phase = update_phase;
+  ctx->pan_max_rows = max_rows;
+  ctx->pan_counter = 0;
+  ctx->pan_last_rows = 0;
+  ctx->pan_last_first = -1;
+  ctx->pan_on = true;
+  return T41RX_OK;
+}
+
+int t41rx_set_panadapter_levels(t41rx_ctx *ctx, const int32_t *noise_floor, const float *gain_correction, int attenuator) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  for (int c = 0; noise_floor && c < ctx->nchan; ++c)
+    if (noise_floor[c] < -32768 || noise_floor[c] > 32767) return fail(T41RX_ERR_ARG, "panadapter levels: a noise floor must fit an int16");
+  for (int c = 0; gain_correction && c < ctx->nchan; ++c)
+    if (!std::isfinite(gain_correction[c])) return fail(T41RX_ERR_ARG, "panadapter levels: non-finite gain correction");
+  DeviceGuard g(ctx->device);
+  HIP_TRY(hipDeviceSynchronize());  // (a launch still in flight reads the old levels)
+  if (const int rc = pan_upload_levels<int32_t>(ctx, ctx->d_pan_nf, noise_floor)) return rc;
+  if (const int rc = pan_upload_levels<float>(ctx, ctx->d_pan_gc, gain_correction)) return rc;
+  ctx->pan_attenuator = attenuator;
+  return T41RX_OK;
+}
+
+int t41rx_get_panadapter(const t41rx_ctx *ctx, int64_t *frame_counter, int32_t *rows_written, int64_t *first_row_frame) {
+  if (!ctx) return T41RX_ERR_ARG;
+  if (frame_counter) *frame_counter = ctx->pan_counter;
+  if (rows_written) *rows_written = ctx->pan_last_rows;
+  if (first_row_frame) *first_row_frame = ctx->pan_last_first;
+  return ctx->pan_on ? 1 : 0;
+}
+
+int t41rx_set_panadapter_counter(t41rx_ctx *ctx, int64_t n) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (n < 0) return fail(T41RX_ERR_ARG, "the frame counter must be >= 0");
+  ctx->pan_counter = n;
   return T41RX_OK;
 }
 
@@ -2060,9 +2253,6 @@ int t41rx_set_calibration(t41rx_ctx *ctx, int on, int spectrumZoom, int currentS
   if (!ctx->d_cal) HIP_TRY(dev_alloc(ctx->d_cal, sizeof(float) * kCalFloats * (size_t)ctx->nchan));
   if (const int rc = ensure_window(ctx)) return rc;
   HIP_TRY(hipMemset(ctx->d_cal.get(), 0, sizeof(float) * kCalFloats * (size_t)ctx->nchan));  // power-on: ZoomFFTPrep(), pixelnew[] = 0
-  // displayScale[] (Display.cpp:127-135): dBScale, baseOffset
-  static const float kDbScale[5] = {10.0f, 20.0f, 40.0f, 100.0f, 200.0f};
-  static const int kBaseOffset[5] = {24, 10, 58, 120, 200};
   ctx->cal_zoom = spectrumZoom;
   ctx->cal_dbscale = kDbScale[currentScale];
   ctx->cal_base = kBaseOffset[currentScale] + pixel_offset;

@@ -90,6 +90,23 @@ constexpr int kDispFloats = kDispOld + 512;
 // checkpoint, and no audio-path kernel reads or writes it.
 constexpr int kCalPixel = kDispFloats;  // [512] int16
 constexpr int kCalFloats = kCalPixel + 256;
+// per-channel panadapter memory (t41rx_set_panadapter; panadapter_kernel.hip): the display state's layout again, behind it
+// the last row's pixelnew[512] as int16 (the next row's pixelold[]), then ShowSpectrum()'s oldNF and newSpectrumFlag
+// (Display.cpp:246, 137) as int32.  The context's own, like the calibration memory: all zero at the setter and at
+// t41rx_reset(), in no checkpoint, untouched by t41rx_set_state() and by every audio-path kernel.
+constexpr int kPanPixel = kDispFloats;     // [512] int16
+constexpr int kPanOldNf = kPanPixel + 256;  // oldNF
+constexpr int kPanNewSpectrum = kPanOldNf + 1;  // newSpectrumFlag: 0 = the next row starts from oldNF = its own currentNF
+constexpr int kPanFloats = kPanOldNf + 4;
+constexpr int kPanGradient = 117;  // gradient[] (Display.cpp:148-161), the waterfall's colour words: the caller's table
+// which frames of a call are update frames (updateDisplayFlag == 1): frame f of the call is one when (counter + f) %
+// period == phase, counter being the stage's frame count in front of the call.  first = the call's first such f (or
+// n_frames), the return value their number.  The rule of t41_sdr_amd/panadapter.py: rows_of_call().
+inline int pan_rows_of_call(long long counter, int n_frames, int period, int phase, int *first) {
+  const int f0 = (int)((((long long)phase - counter) % period + period) % period);
+  *first = f0 < n_frames ? f0 : n_frames;
+  return f0 < n_frames ? (n_frames - 1 - f0) / period + 1 : 0;
+}
 
 // host designer (design.cpp)
 int design_blob(const t41rx_params &p, void *blob, size_t blob_bytes);

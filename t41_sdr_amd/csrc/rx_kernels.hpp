@@ -80,6 +80,14 @@ struct RxArgs {
   const int *__restrict__ in_map;
   long long in_chan_stride;
   long long in_frame_stride;
+  // the panadapter stage's update cadence (t41rx_set_panadapter), or tap_period == 0: every frame writes its own row of
+  // dbg_pre / spect / spect_max, [nchan][nframes].  tap_period > 0: the call's frames tap_first + k tap_period (k >= 0)
+  // are its update frames and write the compact row k of [nchan][tap_rows]; every other frame writes no tap and does not
+  // advance audioMaxSquaredAve.  By value, so a device-pointer call uploads nothing: the host has worked out tap_first
+  // from its frame counter and checked the row count against tap_rows.  Only the tap instantiations read these fields.
+  int tap_period;
+  int tap_first;
+  int tap_rows;
 };
 
 // constant table of the N = 512 R point fast convolution (float2 units):
@@ -134,5 +142,31 @@ struct CalArgs {
   int sideband;            // 1 LSB (ref = window 0), 2 USB (ref = window 1), 0 any other mode (no measurement)
 };
 hipError_t launch_cal(const CalArgs &a, hipStream_t s);
+
+// the panadapter stage (t41rx_set_panadapter; panadapter_kernel.hip): display FFT, ShowSpectrum()'s pixel mapping and
+// waterfall row and DrawSmeterBar()'s dBm on the compact tap rows of a call's update frames
+struct PanArgs {
+  const float *pre;             // RxArgs::dbg_pre, compact: [nchan][max_rows][2][2048]
+  const float *mx;              // RxArgs::spect_max, compact: [nchan][max_rows][3]
+  float *mem;                   // [nchan][kPanFloats] panadapter memory
+  const float2 *tab;            // the context's constant table (FFT twiddles)
+  const double *win;            // [512]: 0.5 - 0.5 cos(6.28 i / 512)
+  const uint16_t *gradient;     // [kPanGradient]
+  const int32_t *noise_floor;   // [nchan] currentNoiseFloor[currentBand]
+  const float *gain_correction; // [nchan] bands[currentBand].gainCorrection
+  // the caller's rows [nchan][max_rows][...], each may be null
+  int16_t *pixel, *y_new, *y_old;  // [512]
+  uint16_t *waterfall;             // [512]
+  float *spec;                     // [512] FFT_spec
+  float *smeter;                   // [4]: audioMaxSquared, AudioMaxIndex, audioMaxSquaredAve, dbm
+  float iir[20];                // mag_coeffs[spectrumZoom] (unused for zoom 0)
+  float fir[4];                 // Fir_Zoom_FFT_Decimate_coeffs
+  int nchan, nrows, max_rows, zoom;
+  float dBScale;                // displayScale[currentScale].dBScale
+  int base;                     // displayScale[currentScale].baseOffset + pixel_offset
+  int noise_floor_y;            // spectrumNoiseFloor
+  int attenuator, RFgain, rfGainAllBands;  // DrawSmeterBar()'s integers (Display.cpp:980-981)
+};
+hipError_t launch_panadapter(const PanArgs &a, hipStream_t s);
 
 }  // namespace t41

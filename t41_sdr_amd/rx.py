@@ -12,7 +12,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, panadapter
 from ._lib import DEMOD_AM, DEMOD_LSB, DEMOD_NFM, DEMOD_SAM, DEMOD_USB, Params, T41RxError, check  # noqa: F401
 
 
@@ -663,8 +663,88 @@ class RxChain:
         check(self._lib.t41rx_set_display_spectrum(self._ctx, ps, po, int(spectrumZoom), min(frames) if frames else 0))
         self._disp = (spec, spec_old)  # keep alive
 
+    # -- the panadapter stage ------------------------------------------------------------------
+    PANADAPTER_ROWS = (("pixel", "int16", 512), ("y_new", "int16", 512), ("y_old", "int16", 512), ("waterfall", "uint16", 512),
+                       ("spec", "float32", 512), ("audio_spect", "float32", 1024), ("smeter", "float32", 4))
+
+    def set_panadapter_tables(self, gradient):
+        """The waterfall's colour words gradient[] (Display.cpp:148-161; t41rx_set_panadapter_tables): 117 uint16.  The
+        library has no table of its own."""
+        g = np.asarray(gradient)
+        if g.ndim != 1 or not np.issubdtype(g.dtype, np.integer) or (g.size and (g.min() < 0 or g.max() > 0xFFFF)):
+            raise ValueError("gradient must be a 1-d array of uint16 colour words, got %r %s" % (g.shape, g.dtype))
+        g = np.ascontiguousarray(g, dtype=np.uint16)
+        check(self._lib.t41rx_set_panadapter_tables(self._ctx, g.ctypes.data_as(C.POINTER(C.c_uint16)), int(g.size)))
+
+    def set_panadapter(self, on=True, spectrumZoom=0, currentScale=1, pixel_offset=0, spectrumNoiseFloor=panadapter.SPECTRUM_NOISE_FLOOR,
+                       update_period=panadapter.UPDATE_PERIOD, update_phase=0, max_rows=1, outputs=None):
+        """ShowSpectrum()'s pixels and waterfall row and DrawSmeterBar()'s dBm as a stage of the path
+        (t41rx_set_panadapter), at the firmware's cadence: frame n of the stage's count is an update frame when n %
+        update_period == update_phase (panadapter.rows_of_call()).  outputs: None allocates every row buffer, a list of
+        names of PANADAPTER_ROWS allocates those, a dict name -> CUDA tensor [n_channels, max_rows, width] uses the
+        caller's; what is left out is not written.  Returns the dict of row buffers: a call with k update frames writes
+        rows 0 .. k-1 of every channel (panadapter_status()).  on = False switches the stage off and returns None.
+        Starts the stage's memory and its frame counter from power-on.  fft_length 512; the colour table loaded first."""
+        if not on:
+            check(self._lib.t41rx_set_panadapter(self._ctx, 0, 0, 0, 0, 0, 1, 0, None, 0))
+            self._pan = None
+            return None
+        import torch
+        if int(max_rows) < 1:
+            raise ValueError("max_rows must be >= 1")
+        kinds = {name: (getattr(torch, dt), width) for name, dt, width in self.PANADAPTER_ROWS}
+        if outputs is None:
+            outputs = list(kinds)
+        bufs = {}
+        for name in outputs:
+            if name not in kinds:
+                raise ValueError("unknown panadapter output %r (one of %s)" % (name, ", ".join(kinds)))
+            dt, width = kinds[name]
+            shape = (self.n_channels, int(max_rows), width)
+            t = outputs[name] if isinstance(outputs, dict) else None
+            if t is None:  # (uint16: allocated as int16 and viewed, the type torch fills on every build)
+                t = torch.zeros(shape, dtype=torch.int16 if dt == torch.uint16 else dt, device="cuda:%d" % self.device).view(dt)
+            elif not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape and t.device.index == self.device):
+                raise ValueError("%s must be a contiguous %s CUDA tensor of shape %r on device %d" % (name, dt, shape, self.device))
+            bufs[name] = t
+        out = _lib.PanadapterOut(**{name: C.c_void_p(t.data_ptr()) for name, t in bufs.items()})
+        self._pan = None
+        check(self._lib.t41rx_set_panadapter(self._ctx, 1, int(spectrumZoom), int(currentScale), int(pixel_offset), int(spectrumNoiseFloor),
+                                             int(update_period), int(update_phase), C.byref(out), int(max_rows)))
+        self._pan = bufs  # keep alive
+        return bufs
+
+    def set_panadapter_levels(self, noise_floor=None, gain_correction=None, attenuator=0):
+        """currentNoiseFloor[currentBand] (ints) and bands[currentBand].gainCorrection (floats) per channel, None = zeros,
+        and `attenuator` (t41rx_set_panadapter_levels).  From the next process call."""
+        nf = gc = None
+        if noise_floor is not None:
+            nf = np.asarray(noise_floor)
+            if nf.shape != (self.n_channels,) or not np.issubdtype(nf.dtype, np.integer) or (nf.min() < -2**31 or nf.max() >= 2**31):
+                raise ValueError("noise_floor must be n_channels = %d int32 values, got %r %s" % (self.n_channels, nf.shape, nf.dtype))
+            nf = np.ascontiguousarray(nf, dtype=np.int32)
+        if gain_correction is not None:
+            gc = np.ascontiguousarray(np.asarray(gain_correction, dtype=np.float32))
+            if gc.shape != (self.n_channels,):
+                raise ValueError("gain_correction must be n_channels = %d floats, got %r" % (self.n_channels, gc.shape))
+        check(self._lib.t41rx_set_panadapter_levels(self._ctx, None if nf is None else nf.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                    None if gc is None else gc.ctypes.data_as(C.POINTER(C.c_float)), int(attenuator)))
+
+    def panadapter_status(self):
+        """(on, frame_counter, rows_written, first_row_frame): the stage's switch, its frame count behind the last process
+        call, the rows that call wrote and the frame count of its row 0 (-1: none)"""
+        n, k, f = C.c_int64(), C.c_int32(), C.c_int64()
+        v = self._lib.t41rx_get_panadapter(self._ctx, C.byref(n), C.byref(k), C.byref(f))
+        if v < 0:
+            check(v)
+        return bool(v), n.value, k.value, f.value
+
+    def set_panadapter_counter(self, n):
+        """the stage's frame counter (t41rx_set_panadapter_counter), n >= 0"""
+        check(self._lib.t41rx_set_panadapter_counter(self._ctx, int(n)))
+
     # -- IQ calibration ----------------------------------------------------------------------
-    CAL_BINS = {("rx", DEMOD_LSB): (310, 460), ("rx", DEMOD_USB): (65, 192),   # cal_bins[], Process2.cpp:429-444
+    CAL_BINS ={("rx", DEMOD_LSB): (310, 460), ("rx", DEMOD_USB): (65, 192),   # cal_bins[], Process2.cpp:429-444
                 ("tx", DEMOD_LSB): (240, 305), ("tx", DEMOD_USB): (209, 273)}
 
     def set_calibration(self, on=True, spectrumZoom=0, currentScale=1, pixel_offset=0, bin0=310, bin1=460, capture_bins=10):
