@@ -1,6 +1,6 @@
 // t41_sdr_amd/csrc/cal_kernel.hip -- the receive half of the IQ calibration, ProcessIQData2() (Process2.cpp:352-397), with
-// the sideband measurement of PlotCalSpectrum() (:478-547) behind it.  Compiled as part of rx_dispatch.hip, which holds no
-// other kernel (a kernel that joins display_kernel's translation unit moves that kernel's LDS and with it its code); it
+// the sideband measurement of PlotCalSpectrum() (:478-547) behind it.  A translation unit of its own (cal_kernel.o; a kernel
+// that joins display_kernel's translation unit moves that kernel's LDS and with it its code); host side: rx_cal.cpp.  It
 // uses the display side output's FFT, twiddle, window and zoom tables, and zoom_fft.hpp's zoom memories and low-pass.  The
 // chain itself (IIR, decimating FIR, ring, windowed read) is this kernel's own copy of zoom_fft.hpp's zoom_frame(), statement
 // for statement: through the helper the compiler lays the frame loop out otherwise and a sweep at zoom 0 takes 2 % longer

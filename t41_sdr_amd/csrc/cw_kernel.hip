@@ -4,8 +4,8 @@
 //
 // Both run on the call's audio @24 kS/s in the stage scratch ([channel][frame * 256]) behind the noise blanker and in
 // front of the back kernel's interpolators (launch_back512): first the detector, which only reads the audio, then the
-// filter, in place.  Built into rx_host.o (included by rx_host.cpp, a HIP translation unit compiled without
-// contraction; the kernels also turn contraction off by pragma), so the library's object set is unchanged.
+// filter, in place.  A translation unit of its own (cw_kernel.o), compiled without contraction like the host designer
+// (the kernels also turn contraction off by pragma); rx_cw.cpp is its host side and sees it through cw_kernels.hpp.
 //
 // Every value is formed by the reference's operations in the order of the f32 restatement (tests/cw_model.py), one
 // rounding per multiply and per add, so both stages are that restatement bit for bit.

@@ -1,4 +1,4 @@
-// t41_sdr_amd/csrc/dev_buf.hpp -- what both host sides (rx_host.cpp, tx_host.cpp) hold device memory and the current
+// t41_sdr_amd/csrc/dev_buf.hpp -- what both host sides (rx_ctx.hpp, tx_host.cpp) hold device memory and the current
 // device with.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -5,8 +5,8 @@
 // ([channel][frame * 256]), in place, before the noise reduction / notch (nr_kernels.hip), the noise blanker
 // (nb_kernel.hip) and the back kernel's interpolators (launch_back512).
 //
-// Built into rx_host.o (included by rx_host.cpp, a HIP translation unit compiled without contraction; the kernel also
-// turns contraction off by pragma), so the library's object set is unchanged.
+// A translation unit of its own (eq_kernel.o), compiled without contraction like the host designer (the kernel also turns
+// contraction off by pragma); rx_audio.cpp is its host side and sees it through eq_kernels.hpp.
 //
 // The stage: 14 bands of 4 cascaded arm_biquad_cascade_df2T_f32 sections on the same input, each band's output times
 // its signed level, and the 14 products summed as EQ1 + EQ2, then + EQ3, .., + EQ14, every value by the reference's

@@ -1,7 +1,7 @@
 // t41_sdr_amd/csrc/ft8_decode_kernel.hip -- FT8 decode of a finished slot: find_sync() (ft8.cpp:337-420),
 // extract_likelihood() (:424-462), bp_decode() (:518-594), pack_bits() (:598-616), crc() (:672-703) and the loop of
-// ft8_decode() up to the CRC check (:759-783), per channel.  Included by rx_host.cpp (the library's object set stays what it
-// was).  tests/ft8_decode_model.py is the same operations in numpy, and the kernels equal it byte for byte.
+// ft8_decode() up to the CRC check (:759-783), per channel.  A translation unit of its own (ft8_decode_kernel.o); host side:
+// rx_ft8_decode.cpp.  tests/ft8_decode_model.py is the same operations in numpy, and the kernels equal it byte for byte.
 //
 //   ft8_sync_kernel  one workgroup per channel.  Per alt (time_sub, freq_sub) the alt's 92 rows of 368 bytes are staged in
 //                    LDS (they lie 1472 bytes apart in the waterfall), the 27 x 312 scores are computed in parallel into LDS

@@ -1,6 +1,6 @@
 // t41_sdr_amd/csrc/ft8_kernel.hip -- FT8 receive up to the finished waterfall: the audio collector of DEMOD_FT8
 // (Process.cpp:627-686), process_FT8_FFT() / extract_power() (ft8.cpp:223-268) and update_synchronization()
-// (ft8.cpp:154-166), per channel, frame after frame.  Included by rx_host.cpp (the library's object set stays what it was).
+// (ft8.cpp:154-166), per channel, frame after frame.  A translation unit of its own (ft8_kernel.o); host side: rx_ft8.cpp.
 //
 // Integer arithmetic throughout: tests/ft8_model.py is the same operations in numpy, and the kernel equals it bit for bit.
 //   collector  arm_float_to_q15 of the 69 samples the frame uses, then the 68-iteration loop in its closed parallel form:

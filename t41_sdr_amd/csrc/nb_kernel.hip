@@ -6,8 +6,8 @@
 // ([channel][frame * 256]), in place, after the noise reduction / notch (nr_kernels.hip) and before the back kernel's
 // interpolators (launch_back512).
 //
-// Built into rx_host.o (included by rx_host.cpp, a HIP translation unit compiled without contraction; the kernel also
-// turns contraction off by pragma), so the library's object set is unchanged.
+// A translation unit of its own (nb_kernel.o), compiled without contraction like the host designer (the kernel also turns
+// contraction off by pragma); rx_audio.cpp is its host side and sees it through nb_kernels.hpp.
 //
 // Per 256-sample block: an order-10 LPC fit (autocorrelation, Levinson-Durbin), the prediction-error filter and its
 // matched filter (two arm_fir_f32 from a zeroed state), a threshold from the filtered block's variance, a scan for

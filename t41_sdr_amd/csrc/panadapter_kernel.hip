@@ -1,7 +1,7 @@
 // t41_sdr_amd/csrc/panadapter_kernel.hip -- the panadapter stage (t41rx_set_panadapter): what ShowSpectrum() draws, per
-// receiver and at the firmware's cadence.  Compiled as part of rx_host.cpp, like the other stages' kernels: the
-// library's object set stays what it was (a kernel that joins display_kernel's translation unit moves that kernel's LDS and
-// with it its code).
+// receiver and at the firmware's cadence.  A translation unit of its own (panadapter_kernel.o), like the other stages'
+// kernels (a kernel that joins display_kernel's translation unit moves that kernel's LDS and with it its code); host
+// side: rx_display.cpp.
 //
 // One 64-lane wave = one channel, all the update frames (updateDisplayFlag == 1) of a process call: their rows of the
 // compact dbg_pre tap, which rx512_kernel's tap instantiations wrote for exactly those frames (RxArgs::tap_period).  Per

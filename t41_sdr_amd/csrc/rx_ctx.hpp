@@ -1,0 +1,298 @@
+// t41_sdr_amd/csrc/rx_ctx.hpp -- the receive context (struct t41rx_ctx) and what the host files of the receive side share.
+// Private to them: rx_host.cpp (the core and the process call), rx_state.cpp (checkpoints and reset) and one file per
+// stage family -- rx_audio.cpp, rx_cw.cpp, rx_ft8.cpp, rx_ft8_decode.cpp, rx_display.cpp, rx_cal.cpp.  Each stage family
+// holds its part of the context in a struct of its own below, and exports the few functions the process call and the
+// checkpoint table name.  No kernel is compiled into a host file: they see the kernels through the *_kernels.hpp headers.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "cw_kernels.hpp"
+#include "dev_buf.hpp"
+#include "eq_kernels.hpp"
+#include "ft8_decode_kernels.hpp"
+#include "ft8_kernels.hpp"
+#include "last_error.hpp"
+#include "nb_kernels.hpp"
+#include "nr_kernels.hpp"
+#include "rx_experiments.hpp"
+#include "rx_internal.hpp"
+#include "rx_kernels.hpp"
+
+// the product's host side is never a diagnostic build; what the KERNEL objects were built as is asked at run time
+// (kernel_build_flags(), rx_dispatch.hip): tools/build_variant.sh links these very objects with diagnostic kernels
+static_assert(T41RX_EXPERIMENT == 0 && t41::kKernelBuildFlags == 0, "the receive host is product code: build it without T41RX_EXPERIMENT / diagnostic switches");
+
+namespace t41 {
+
+// noise reduction / notch (Process.cpp:841-866): state of Xanr() and of the two spectral functions, window tables;
+// allocated when a call first needs them
+struct NrStage {
+  DevBuf<float> d_anr, d_spec, d_tab;
+};
+
+// noise blanker (NB_on, Process.cpp:873-876; t41rx_set_noise_blanker): AltNoiseBlanking()'s last_frame_end per channel,
+// two slots [2][nchan][kNbCarryPitch] (nb_kernel.hip); allocated when the blanker first runs
+struct NbStage {
+  int on = 0;
+  DevBuf<float> d_carry;
+  int sel = 0;  // the slot holding the current carry (flips with every blanker launch)
+};
+
+// receive equalizer (receiveEQFlag, Process.cpp:828-832; t41rx_set_receive_eq): the caller's band table, the levels
+// (EEPROMData.equalizerRec, EEPROM.cpp:59: 100 each), and rec_EQ_Band1_state .. rec_EQ_Band14_state per channel
+// [nchan][kEqStateFloats] (eq_kernel.hip), allocated when the equalizer first runs
+struct EqStage {
+  int on = 0;
+  bool have_bands = false;
+  float coef[kEqCoefs] = {};
+  int32_t levels[kEqBands] = {100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100};
+  DevBuf<float> d_state;
+};
+
+// a stage's clock, millis(n) = t0 + floor(n * num / den): 2048 samples at 192 kS/s
+struct StageClock {
+  int32_t t0 = 0, num = 32, den = 3;
+};
+
+// CW receive (Process.cpp:878-913; t41rx_set_cw_tables / _filter / _detector): the caller's filter tables and decode
+// FIR, CWFilterIndex (5 = off), decoderFlag with the caller's result buffer, and the stages' memories per channel
+// [nchan][kCwStateFloats] (cw_kernel.hip), allocated when a CW stage first runs.  Both stages run only while
+// params.xmtMode == T41RX_CW_MODE.
+struct CwStage {
+  int filter = kCwFilters;
+  int det = 0;
+  bool have_filters = false, have_fir = false;
+  float coef[kCwFilters * kCwFilterCoefs] = {};
+  float fir[kCwFirTaps] = {};
+  float *out = nullptr;  // [nchan][n_frames][4]
+  int frames = 0;        // frames per call `out` is sized for
+  DevBuf<float> d_state;
+  // the Morse decoder behind the detector (DoCWDecoding(), CWProcessing.cpp:519-639; t41rx_set_cw_decode_tree / _decoder /
+  // _clock): the caller's bigMorseCodeTree, the switch with the caller's text buffer, the clock, and the decoder's words per
+  // channel [nchan][kCwDecWords] (cw_kernels.hpp), allocated when the decoder first runs.  It runs exactly when the detector
+  // runs and the switch is on.
+  bool have_tree = false;
+  uint8_t tree[kCwTreeChars + 3] = {};
+  int dec = 0;
+  int32_t *text = nullptr;  // [nchan][n_frames][2]
+  int text_frames = 0;      // frames per call `text` is sized for
+  StageClock clock;
+  DevBuf<int32_t> d_dec;
+};
+
+// FT8 receive up to the waterfall (Process.cpp:627-686, ft8.cpp:153-268; t41rx_set_ft8_tables / _ft8 / _ft8_clock /
+// t41rx_ft8_sync): the caller's window and mag_db (device copies), arm_rfft_q15's tables, the switch with the caller's
+// power and status buffers, the clock, and the FT8 memory per channel [nchan][kFt8Words] (ft8_kernels.hpp), allocated at
+// first use.  The context's own: no checkpoint section (its record is t41rx_ft8_get_state / _set_state).  The stage reads
+// the demodulated audio where the demod tap sits: d_aud24 when other stages split the chain, else the caller's demod tap
+// buffer, else d_tap.
+struct Ft8Stage {
+  int on = 0;
+  bool have_tables = false;
+  uint8_t *power = nullptr;   // [nchan][2][kFt8HalfBytes]
+  int32_t *status = nullptr;  // [nchan][n_frames][4]
+  int frames = 0;             // frames per call `status` is sized for
+  StageClock clock;
+  DevBuf<int32_t> d_state;
+  DevBuf<float> d_win, d_mag, d_tap;
+  DevBuf<uint32_t> d_tab;
+  int tap_frames = 0;
+};
+
+// FT8 decode of a finished slot (ft8.cpp:270-616, 669-703, 727-790; t41rx_set_ft8_decode_tables / _ft8_decode /
+// _ft8_decode_debug, t41rx_ft8_decode_device / _host): the caller's kCostas_map, kGray_map, kNm, kMn, kNrw as validated
+// (device copy, with the positions worked out from them), kMax_candidates / kMin_score / kLDPC_iterations, the stage taps,
+// and the call's `select` on its way to the device: a pinned copy, an event behind its upload (the next call waits for
+// it before it overwrites the copy), the device array.  The decode reads the waterfall and the tables and touches no state.
+struct Ft8Decode {
+  bool have_tables = false;
+  int max_candidates = T41RX_FT8_MAX_CANDIDATES, min_score = 40, iterations = 10;
+  float *dbg_log174 = nullptr;
+  uint8_t *dbg_plain = nullptr;
+  DevBuf<Ft8DecodeTables> d_tab;
+  DevBuf<int8_t> d_sel;
+  DevBuf<t41rx_ft8_result> d_res;  // staging for t41rx_ft8_decode_host
+  int8_t *h_sel = nullptr;         // pinned
+  hipEvent_t sel_ev = nullptr;
+};
+
+// display FFT side output (t41rx_set_display_spectrum)
+struct DisplayTap {
+  float *spec = nullptr, *old = nullptr;  // caller's buffers
+  DevBuf<float> d_pre, d_state;           // input tap [nchan][frames][4096], state [nchan][kDispFloats]
+  int frames = 0, zoom = 0;
+};
+
+// the panadapter stage (ShowSpectrum() / DrawSmeterBar(), Display.cpp:240-504, 955-1030; t41rx_set_panadapter_tables /
+// _panadapter / _panadapter_levels): the caller's gradient[] (device copy), the settings, the caller's row buffers, the
+// levels per channel (device copies), the compact taps of a call's update frames [nchan][max_rows][...] that the tap
+// kernels write and panadapter_kernel reads, and the panadapter memory [nchan][kPanFloats] (rx_internal.hpp).  The
+// context's own: no checkpoint section, t41rx_set_state() leaves it alone.  The frame counter lives here, on the host.
+struct Panadapter {
+  bool on = false, have_tables = false;
+  t41rx_panadapter_out out{};
+  int zoom = 0, scale = 0, pixel_offset = 0, floor_y = 0, period = 1, phase = 0, max_rows = 0;
+  int attenuator = 0;
+  int alloc_rows = 0;       // rows d_pre / d_max hold
+  long long counter = 0;    // frames processed since the setter / t41rx_reset() / t41rx_set_panadapter_counter()
+  int call_first = 0, call_rows = 0;  // of the call being prepared: its first update frame, their number
+  int last_rows = 0;        // t41rx_get_panadapter(): rows the last call wrote, and the frame index of the first
+  long long last_first = -1;
+  DevBuf<uint16_t> d_grad;
+  DevBuf<int32_t> d_nf;
+  DevBuf<float> d_gc, d_pre, d_max, d_mem;
+};
+
+// IQ calibration (ProcessIQData2() / PlotCalSpectrum(), Process2.cpp:352-397, 478-547; t41rx_set_calibration): its
+// settings, a correction candidate per channel, and the calibration memory [nchan][kCalFloats] (cal_kernel.hip),
+// allocated when calibration is first configured.  The context's own: no checkpoint section, no audio-path kernel
+// touches it.
+struct Calibration {
+  bool on = false, per_channel = false;
+  int zoom = 0, base = 0, lo0 = 0, lo1 = 0, width = 0;
+  float dbscale = 0.0f;
+  DevBuf<float> d_mem, d_corr;
+};
+
+// staging for t41rx_process_host
+struct Staging {
+  DevBuf<float> d_in_i, d_in_q, d_out;
+  size_t in_floats = 0, out_floats = 0;  // floats d_in_i / d_in_q and d_out hold
+};
+
+}  // namespace t41
+
+struct t41rx_ctx {
+  int device = 0;
+  int nchan = 0;
+  t41rx_params params{};
+  std::vector<float> blob;       // canonical coefficient blob (host)
+  std::vector<int32_t> nco_hz;   // NCOFreq per channel (host)
+  t41::DevBuf<float> d_state;    // [nchan][state_floats]
+  t41::DevBuf<t41::DevCoef> d_coef;
+  t41::DevBuf<float2> d_tab;
+  t41::DevBuf<t41::ChanNco> d_nco;
+  float *dbg_nco = nullptr, *dbg_dec = nullptr, *dbg_demod = nullptr;
+  float *spect = nullptr, *spect_max = nullptr;  // audio-spectrum side output (t41rx_set_audio_spectrum)
+  int tap_frames = 0, spect_frames = 0;          // frames per call those buffers are sized for
+  // FFT_LENGTH 4096 pipeline: constant table + scratch between its three kernels
+  t41::DevBuf<float2> d_tab4k;
+  t41::DevBuf<float> d_mid, d_aud24;
+  t41::DevBuf<char> d_agc_pipe;  // FFT_LENGTH 512, AGC on or SAM: the pipelined kernels' buffer (pipe_layout), allocated on first use
+  int scratch_frames = 0;
+  int layout = T41RX_LAYOUT_CHANNEL_MAJOR;  // of I / Q / audio (t41rx_set_buffer_layout)
+  int nco_sel = 0;               // long FFT: which NcoState copy is current (flips with every process call)
+  // receiver groups (t41rx_set_input_map): channel c reads row in_map[c] of the n_streams rows of I / Q; n_streams == 0:
+  // no map, one row per channel.  Configuration like `layout`: in no checkpoint, untouched by reset / set_state / set_params
+  std::vector<int32_t> in_map;   // (host)
+  int n_streams = 0;
+  t41::DevBuf<int32_t> d_in_map;  // [nchan], allocated with the first map
+  t41::DevBuf<double> d_win;      // the display FFT's window (ensure_window): display spectrum, panadapter, calibration
+  t41::NrStage nr;
+  t41::NbStage nb;
+  t41::EqStage eq;
+  t41::CwStage cw;
+  t41::Ft8Stage ft8;
+  t41::Ft8Decode ft8d;
+  t41::DisplayTap disp;
+  t41::Panadapter pan;
+  t41::Calibration cal;
+  t41::Staging staging;
+};
+
+namespace t41 {
+
+inline int hip_fail(hipError_t e, const char *what) {
+  return fail(T41RX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+inline int hip_check(hipError_t e, const char *what) { return e == hipSuccess ? T41RX_OK : hip_fail(e, what); }
+#define HIP_TRY(expr)                                        \
+  do {                                                       \
+    hipError_t e__ = (expr);                                 \
+    if (e__ != hipSuccess) return t41::hip_fail(e__, #expr); \
+  } while (0)
+
+// ---- which stages a process call runs
+inline bool nr_on(const t41rx_ctx *ctx) { return ctx->params.nrOptionSelect != 0 || ctx->params.ANR_notchOn != 0; }  // (fft_length 512: params_valid)
+// the CW block runs in T41State == CW_RECEIVE (Process.cpp:878), which in receive is xmtMode == CW_MODE
+// (T41_SDR.ino:1039-1040, 1144-1148); with another xmtMode the switches are kept and nothing runs
+inline bool cw_filter_on(const t41rx_ctx *ctx) { return ctx->params.xmtMode == T41RX_CW_MODE && ctx->cw.filter != kCwFilters; }
+inline bool cw_det_on(const t41rx_ctx *ctx) { return ctx->params.xmtMode == T41RX_CW_MODE && ctx->cw.det != 0; }
+// the decoder runs exactly when the detector runs (in the firmware one decoderFlag gates both, CWProcessing.cpp:322-372)
+inline bool cw_dec_on(const t41rx_ctx *ctx) { return cw_det_on(ctx) && ctx->cw.dec != 0; }
+// the fused kernel stops behind the demodulator; stage kernels; back kernel (fft_length 512: t41rx_set_noise_blanker,
+// t41rx_set_receive_eq, t41rx_set_cw_filter, t41rx_set_cw_detector)
+inline bool stages_on(const t41rx_ctx *ctx) { return ctx->eq.on || nr_on(ctx) || ctx->nb.on || cw_filter_on(ctx) || cw_det_on(ctx); }
+// the pipelined kernels' buffer: AGC on (with the synchronous detector behind it: PSA), or the synchronous detector alone
+inline bool pipe_on(const t41rx_ctx *ctx, int n_frames) {
+  return (ctx->params.AGCMode != 0 || ctx->params.mode == T41RX_DEMOD_SAM) && ctx->params.fft_length == 512 && n_frames >= 4;
+}
+// rows of I / Q a process call reads: one per channel, or the input map's n_streams
+inline int input_rows(const t41rx_ctx *ctx) { return ctx->n_streams > 0 ? ctx->n_streams : ctx->nchan; }
+
+// ---- helpers more than one file uses
+// a stage memory whose power-on value is zero, on first use (rx_audio.cpp)
+int ensure_zeroed(DevBuf<float> &b, size_t bytes, const char *what);
+// the optional channel mask of a per-channel command (nullptr: every channel) on the device (rx_cw.cpp)
+int upload_channel_mask(const t41rx_ctx *ctx, const uint8_t *channels, DevBuf<uint8_t> &mask);
+// a stage clock's setter: `what` opens the refusal (rx_cw.cpp)
+int set_stage_clock(StageClock &clock, const char *what, int32_t t0_ms, int32_t num, int32_t den);
+// the zoom filters of a display-FFT launch (spectrumZoom 1..4: IIR_biquad_Zoom_FFT's coefficients and the decimating FIR;
+// zoom 0 leaves them alone) and the display FFT's window, once per context (rx_display.cpp)
+void zoom_filter_args(int zoom, float (&iir)[20], float (&fir)[4]);
+int ensure_window(t41rx_ctx *ctx);
+// displayScale[] (Display.cpp:127-135): dBScale, baseOffset -- the calibration's and the panadapter's pixel mapping
+constexpr float kDbScale[5] = {10.0f, 20.0f, 40.0f, 100.0f, 200.0f};
+constexpr int kBaseOffset[5] = {24, 10, 58, 120, 200};
+// the pipelined kernels' time-out counter (rx_host.cpp)
+int pipe_timeouts_clear(t41rx_ctx *ctx);
+int pipe_status(const t41rx_ctx *ctx);
+// the path's records and every stage memory to power-on (rx_state.cpp)
+int reset_state(t41rx_ctx *ctx);
+
+// ---- what the stages give the process call (`*_run`: fill the stage's argument block and launch, on the call's audio @24
+// kS/s in d_aud24) and the checkpoint table (`ensure_*` also allocates on restore; get / put / reset where a section is
+// more than one buffer)
+// rx_audio.cpp
+int ensure_nr(t41rx_ctx *ctx);
+int ensure_nb(t41rx_ctx *ctx);
+int ensure_eq(t41rx_ctx *ctx);
+int eq_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
+int nr_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
+int nb_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
+int nr_check(const t41rx_ctx *ctx, const int32_t *hdr, const float *sec);
+int nr_get(const t41rx_ctx *ctx, void *host, size_t bytes);
+int nr_put(t41rx_ctx *ctx, const void *host, size_t bytes);
+int nr_reset(t41rx_ctx *ctx, size_t bytes);
+int nb_get(const t41rx_ctx *ctx, void *host, size_t bytes);
+int nb_put(t41rx_ctx *ctx, const void *host, size_t bytes);
+int nb_reset(t41rx_ctx *ctx, size_t bytes);
+// rx_cw.cpp
+int ensure_cw(t41rx_ctx *ctx);
+int ensure_cw_decode(t41rx_ctx *ctx);
+const char *cw_split_stage(const t41rx_ctx *ctx);
+int cw_detect_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
+int cw_decode_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
+int cw_filter_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t s);  // the narrow filter and its back end
+int check_cw_decode(const t41rx_ctx *ctx, const int32_t *hdr, const float *sec);
+int cw_decode_reset(t41rx_ctx *ctx, size_t bytes);
+// rx_ft8.cpp
+int ft8_prepare(t41rx_ctx *ctx, int n_frames, hipStream_t s);  // the call's refusals, the memory and the demod tap of its own
+int ft8_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t s);
+int ft8_power_on(t41rx_ctx *ctx);
+// rx_ft8_decode.cpp
+void ft8_decode_release(t41rx_ctx *ctx);  // t41rx_destroy(): the pinned copy and the event
+// rx_display.cpp
+int display_check(const t41rx_ctx *ctx, const int32_t *hdr, const float *sec);
+int display_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
+int pan_prepare(t41rx_ctx *ctx, int n_frames);  // which frames of the call are update frames, and the stage's refusals
+int pan_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
+int pan_reset(t41rx_ctx *ctx);
+// rx_cal.cpp
+int cal_reset(t41rx_ctx *ctx);
+
+}  // namespace t41

@@ -51,5 +51,3 @@ hipError_t launch_rx(const RxArgs &a, int fft_length, int mode, hipStream_t s) {
 }
 
 }  // namespace t41
-
-#include "cal_kernel.hip"  // the IQ calibration's receive half: the only kernel of this translation unit

@@ -1,0 +1,271 @@
+// t41_sdr_amd/csrc/rx_display.cpp -- host side of the display stages behind a process call: the display FFT side output
+// (display_kernel.hip) and the panadapter stage (panadapter_kernel.hip), with the window and the zoom filters they share
+// with the calibration.
+#include <cmath>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "rx_ctx.hpp"
+
+namespace t41 {
+
+void zoom_filter_args(int zoom, float (&iir)[20], float (&fir)[4]) {
+  if (zoom > 0) {
+    std::memcpy(iir, kZoomIirCoeffs[zoom - 1], sizeof(iir));
+    design_zoom_fir(zoom, fir);
+  }
+}
+
+// the display FFT's window, 0.5 - 0.5 cos(6.28 i / 512) as the reference's double expression, once per context
+int ensure_window(t41rx_ctx *ctx) {
+  if (ctx->d_win) return T41RX_OK;
+  DevBuf<double> win;
+  double w[512];
+  for (int i = 0; i < 512; ++i) w[i] = 0.5 - 0.5 * std::cos(6.28 * i / 512);  // FFT.cpp:110, 222 ("Hanning", 6.28 as written)
+  HIP_TRY(dev_alloc(win, sizeof(w)));
+  HIP_TRY(hipMemcpy(win.get(), w, sizeof(w), hipMemcpyHostToDevice));
+  ctx->d_win = std::move(win);
+  return T41RX_OK;
+}
+
+// ---- display FFT side output
+// refusal of its checkpoint section
+int display_check(const t41rx_ctx *c, const int32_t *hdr, const float *d) {
+  if (!(c->disp.spec && c->disp.d_state)) return fail(T41RX_ERR_STATE, "checkpoint carries display-FFT state but the display spectrum is off here");
+  if (hdr[6] != c->disp.zoom) return fail(T41RX_ERR_STATE, "checkpoint: display-FFT state of another spectrumZoom");
+  for (int ch = 0; ch < c->nchan; ++ch) {
+    int32_t ptr;
+    std::memcpy(&ptr, d + (size_t)kDispFloats * (size_t)ch + kDispPtr, sizeof(ptr));
+    if (ptr < 0 || ptr >= 512) return fail(T41RX_ERR_STATE, "checkpoint: zoom_sample_ptr out of range");
+  }
+  return T41RX_OK;
+}
+
+int display_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
+  DispArgs d{};
+  d.pre = ctx->disp.d_pre.get();
+  d.disp = ctx->disp.d_state.get();
+  d.spec = ctx->disp.spec;
+  d.spec_old = ctx->disp.old;
+  d.tab = ctx->d_tab.get();
+  d.win = ctx->d_win.get();
+  d.nchan = ctx->nchan;
+  d.nframes = n_frames;
+  d.zoom = ctx->disp.zoom;
+  zoom_filter_args(d.zoom, d.iir, d.fir);
+  return hip_check(launch_display(d, s), "display kernel launch");
+}
+
+// ---- panadapter
+int pan_prepare(t41rx_ctx *ctx, int n_frames) {
+  Panadapter &p = ctx->pan;
+  p.call_rows = 0;
+  p.call_first = n_frames;
+  if (!p.on) return T41RX_OK;
+  p.call_rows = pan_rows_of_call(p.counter, n_frames, p.period, p.phase, &p.call_first);
+  if (p.call_rows > p.max_rows)
+    return fail(T41RX_ERR_ARG, "the call holds more update frames than the max_rows the panadapter buffers were set with");
+  if (!p.d_pre || !p.d_max || !p.d_mem || !p.d_nf || !p.d_gc || !p.d_grad || !ctx->d_win)
+    return fail(T41RX_ERR_STATE, "panadapter enabled without its buffers");
+  return T41RX_OK;
+}
+
+int pan_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
+  Panadapter &pan = ctx->pan;
+  if (pan.call_rows > 0) {
+    PanArgs p{};
+    p.pre = pan.d_pre.get();
+    p.mx = pan.d_max.get();
+    p.mem = pan.d_mem.get();
+    p.tab = ctx->d_tab.get();
+    p.win = ctx->d_win.get();
+    p.gradient = pan.d_grad.get();
+    p.noise_floor = pan.d_nf.get();
+    p.gain_correction = pan.d_gc.get();
+    p.pixel = pan.out.pixel;
+    p.y_new = pan.out.y_new;
+    p.y_old = pan.out.y_old;
+    p.waterfall = pan.out.waterfall;
+    p.spec = pan.out.spec;
+    p.smeter = pan.out.smeter;
+    p.nchan = ctx->nchan;
+    p.nrows = pan.call_rows;
+    p.max_rows = pan.max_rows;
+    p.zoom = pan.zoom;
+    zoom_filter_args(p.zoom, p.iir, p.fir);
+    p.dBScale = kDbScale[pan.scale];
+    p.base = kBaseOffset[pan.scale] + pan.pixel_offset;
+    p.noise_floor_y = pan.floor_y;
+    p.attenuator = pan.attenuator;
+    p.RFgain = ctx->params.RFgain;
+    p.rfGainAllBands = ctx->params.rfGainAllBands;
+    const hipError_t e = launch_panadapter(p, s);
+    if (e != hipSuccess) return hip_fail(e, "panadapter kernel launch");
+  }
+  pan.last_rows = pan.call_rows;
+  pan.last_first = pan.call_rows > 0 ? pan.counter + pan.call_first : -1;
+  pan.counter += n_frames;
+  return T41RX_OK;
+}
+
+// t41rx_reset(): the panadapter memory and its frame counter to power-on (pixelold = 0, newSpectrumFlag = 0)
+int pan_reset(t41rx_ctx *ctx) {
+  if (ctx->pan.d_mem) HIP_TRY(hipMemset(ctx->pan.d_mem.get(), 0, sizeof(float) * kPanFloats * (size_t)ctx->nchan));
+  ctx->pan.counter = 0;
+  ctx->pan.last_rows = 0;
+  ctx->pan.last_first = -1;
+  return T41RX_OK;
+}
+
+namespace {
+// the per-channel levels, on the device; values == nullptr: zeros
+template <class T>
+int pan_upload_levels(t41rx_ctx *ctx, DevBuf<T> &d, const T *values) {
+  std::vector<T> h((size_t)ctx->nchan, T(0));
+  if (values) std::memcpy(h.data(), values, sizeof(T) * h.size());
+  if (!d) HIP_TRY(dev_alloc(d, sizeof(T) * h.size()));
+  HIP_TRY(hipMemcpy(d.get(), h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+  return T41RX_OK;
+}
+}  // namespace
+
+}  // namespace t41
+
+using namespace t41;
+
+extern "C" {
+
+int t41rx_set_display_spectrum(t41rx_ctx *ctx, float *d_spec, float *d_spec_old, int spectrumZoom, int max_frames) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null context");
+  if ((d_spec == nullptr) != (d_spec_old == nullptr)) return fail(T41RX_ERR_ARG, "set both pointers or neither");
+  DeviceGuard g(ctx->device);
+  HIP_TRY(hipDeviceSynchronize());
+  DisplayTap &disp = ctx->disp;
+  if (!d_spec) {
+    disp.spec = disp.old = nullptr;
+    disp.frames = 0;
+    return T41RX_OK;
+  }
+  if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the display FFT is built for fft_length 512");
+  if (ctx->pan.on) return fail(T41RX_ERR_UNSUPPORTED, "the panadapter stage is on and owns the display tap (t41rx_set_panadapter)");
+  if (spectrumZoom < 0 || spectrumZoom > 4) return fail(T41RX_ERR_ARG, "spectrumZoom must be 0 (1x) .. 4 (16x)");  // MAX_ZOOM_ENTRIES, ButtonProc.h:6
+  if (max_frames <= 0) return fail(T41RX_ERR_ARG, "max_frames must be > 0");
+  if ((reinterpret_cast<uintptr_t>(d_spec) | reinterpret_cast<uintptr_t>(d_spec_old)) & 3u) return fail(T41RX_ERR_ARG, "unaligned pointer");
+  // Anything that fails from here on leaves the side output switched OFF (a previous successful
+  // call's pointers must not survive next to a freed tap buffer: the display kernel would read it).
+  disp.spec = disp.old = nullptr;
+  const int had_frames = disp.frames;
+  disp.frames = 0;
+  if (max_frames > had_frames || !disp.d_pre)
+    HIP_TRY(dev_alloc(disp.d_pre, sizeof(float) * 4096 * (size_t)max_frames * (size_t)ctx->nchan));
+  if (!disp.d_state) HIP_TRY(dev_alloc(disp.d_state, sizeof(float) * kDispFloats * (size_t)ctx->nchan));
+  if (const int rc = ensure_window(ctx)) return rc;
+  HIP_TRY(hipMemset(disp.d_state.get(), 0, sizeof(float) * kDispFloats * (size_t)ctx->nchan));  // ZoomFFTPrep(): a fresh start
+  if (max_frames < had_frames) max_frames = had_frames;  // (the tap buffer was kept: it still holds that many)
+  disp.spec = d_spec;
+  disp.old = d_spec_old;
+  disp.frames = max_frames;
+  disp.zoom = spectrumZoom;
+  return T41RX_OK;
+}
+
+int t41rx_set_panadapter_tables(t41rx_ctx *ctx, const uint16_t *gradient, int n) {
+  if (!ctx || !gradient) return fail(T41RX_ERR_ARG, "null argument");
+  if (n != kPanGradient) return fail(T41RX_ERR_ARG, "panadapter tables: gradient[] has 117 words (Display.cpp:148-161)");
+  DeviceGuard g(ctx->device);
+  HIP_TRY(hipDeviceSynchronize());  // (a launch still in flight reads the old table)
+  if (!ctx->pan.d_grad) HIP_TRY(dev_alloc(ctx->pan.d_grad, sizeof(uint16_t) * kPanGradient));
+  HIP_TRY(hipMemcpy(ctx->pan.d_grad.get(), gradient, sizeof(uint16_t) * kPanGradient, hipMemcpyHostToDevice));
+  ctx->pan.have_tables = true;
+  return T41RX_OK;
+}
+
+int t41rx_set_panadapter(t41rx_ctx *ctx, int on, int spectrumZoom, int currentScale, int pixel_offset, int spectrumNoiseFloor,
+                         int update_period, int update_phase, const t41rx_panadapter_out *out, int max_rows) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  DeviceGuard g(ctx->device);
+  HIP_TRY(hipDeviceSynchronize());
+  Panadapter &pan = ctx->pan;
+  if (!on) {
+    pan.on = false;
+    return T41RX_OK;
+  }
+  // every refusal in front of the first change: a refused call leaves the stage as it was
+  if (!out) return fail(T41RX_ERR_ARG, "null argument");
+  if (!pan.have_tables) return fail(T41RX_ERR_ARG, "panadapter: no colour table loaded (t41rx_set_panadapter_tables)");
+  if (spectrumZoom < 0 || spectrumZoom > 4) return fail(T41RX_ERR_ARG, "spectrumZoom must be 0 (1x) .. 4 (16x)");
+  if (currentScale < 0 || currentScale > 4) return fail(T41RX_ERR_ARG, "currentScale must be 0 .. 4");
+  if (pixel_offset < -32768 || pixel_offset > 32767) return fail(T41RX_ERR_ARG, "pixel_offset must fit an int16");
+  if (spectrumNoiseFloor < -32768 || spectrumNoiseFloor > 32767) return fail(T41RX_ERR_ARG, "spectrumNoiseFloor must fit an int16");
+  if (update_period < 1) return fail(T41RX_ERR_ARG, "update_period must be >= 1");
+  if (update_phase < 0 || update_phase >= update_period) return fail(T41RX_ERR_ARG, "update_phase must lie in [0, update_period)");
+  if (max_rows < 1) return fail(T41RX_ERR_ARG, "max_rows must be >= 1");
+  if ((reinterpret_cast<uintptr_t>(out->pixel) | reinterpret_cast<uintptr_t>(out->y_new) | reinterpret_cast<uintptr_t>(out->y_old) |
+       reinterpret_cast<uintptr_t>(out->waterfall) | reinterpret_cast<uintptr_t>(out->spec) | reinterpret_cast<uintptr_t>(out->audio_spect) |
+       reinterpret_cast<uintptr_t>(out->smeter)) & 15u)
+    return fail(T41RX_ERR_ARG, "panadapter: the row buffers must be 16-byte aligned");  // (one rule for all: the audio-spectrum rows leave as 8-byte stores)
+  if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the panadapter stage is built for fft_length 512");
+  if (ctx->disp.spec || ctx->spect)
+    return fail(T41RX_ERR_UNSUPPORTED, "t41rx_set_display_spectrum / t41rx_set_audio_spectrum is set and owns its tap: switch it off first");
+  // anything that fails from here on leaves the stage switched off
+  pan.on = false;
+  if (max_rows > pan.alloc_rows || !pan.d_pre || !pan.d_max) {
+    pan.alloc_rows = 0;
+    HIP_TRY(dev_alloc(pan.d_pre, sizeof(float) * 4096 * (size_t)max_rows * (size_t)ctx->nchan));
+    HIP_TRY(dev_alloc(pan.d_max, sizeof(float) * 3 * (size_t)max_rows * (size_t)ctx->nchan));
+    pan.alloc_rows = max_rows;
+  }
+  if (!pan.d_mem) HIP_TRY(dev_alloc(pan.d_mem, sizeof(float) * kPanFloats * (size_t)ctx->nchan));
+  if (const int rc = ensure_window(ctx)) return rc;
+  if (!pan.d_nf)
+    if (const int rc = pan_upload_levels<int32_t>(ctx, pan.d_nf, nullptr)) return rc;
+  if (!pan.d_gc)
+    if (const int rc = pan_upload_levels<float>(ctx, pan.d_gc, nullptr)) return rc;
+  // power-on: ZoomFFTPrep(), FFT_spec_old = 0, pixelold = 0, newSpectrumFlag = 0; the frame counter starts at 0
+  HIP_TRY(hipMemset(pan.d_mem.get(), 0, sizeof(float) * kPanFloats * (size_t)ctx->nchan));
+  pan.out = *out;
+  pan.zoom = spectrumZoom;
+  pan.scale = currentScale;
+  pan.pixel_offset = pixel_offset;
+  pan.floor_y = spectrumNoiseFloor;
+  pan.period = update_period;
+  pan.phase = update_phase;
+  pan.max_rows = max_rows;
+  pan.counter = 0;
+  pan.last_rows = 0;
+  pan.last_first = -1;
+  pan.on = true;
+  return T41RX_OK;
+}
+
+int t41rx_set_panadapter_levels(t41rx_ctx *ctx, const int32_t *noise_floor, const float *gain_correction, int attenuator) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  for (int c = 0; noise_floor && c < ctx->nchan; ++c)
+    if (noise_floor[c] < -32768 || noise_floor[c] > 32767) return fail(T41RX_ERR_ARG, "panadapter levels: a noise floor must fit an int16");
+  for (int c = 0; gain_correction && c < ctx->nchan; ++c)
+    if (!std::isfinite(gain_correction[c])) return fail(T41RX_ERR_ARG, "panadapter levels: non-finite gain correction");
+  DeviceGuard g(ctx->device);
+  HIP_TRY(hipDeviceSynchronize());  // (a launch still in flight reads the old levels)
+  if (const int rc = pan_upload_levels<int32_t>(ctx, ctx->pan.d_nf, noise_floor)) return rc;
+  if (const int rc = pan_upload_levels<float>(ctx, ctx->pan.d_gc, gain_correction)) return rc;
+  ctx->pan.attenuator = attenuator;
+  return T41RX_OK;
+}
+
+int t41rx_get_panadapter(const t41rx_ctx *ctx, int64_t *frame_counter, int32_t *rows_written, int64_t *first_row_frame) {
+  if (!ctx) return T41RX_ERR_ARG;
+  if (frame_counter) *frame_counter = ctx->pan.counter;
+  if (rows_written) *rows_written = ctx->pan.last_rows;
+  if (first_row_frame) *first_row_frame = ctx->pan.last_first;
+  return ctx->pan.on ? 1 : 0;
+}
+
+int t41rx_set_panadapter_counter(t41rx_ctx *ctx, int64_t n) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (n < 0) return fail(T41RX_ERR_ARG, "the frame counter must be >= 0");
+  ctx->pan.counter = n;
+  return T41RX_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// t41_sdr_amd/csrc/rx_kernels.hpp -- kernel argument block + launcher declaration (what rx_host.cpp sees of the kernels).
+// t41_sdr_amd/csrc/rx_kernels.hpp -- kernel argument block + launcher declaration (what the host files see of the kernels).
 #pragma once
 #include <hip/hip_runtime.h>
 

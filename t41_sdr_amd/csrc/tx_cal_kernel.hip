@@ -1,7 +1,7 @@
 // t41_sdr_amd/csrc/tx_cal_kernel.hip -- gfx950 kernel of the transmit half of the IQ calibration, ProcessIQData2()
 // (Process2.cpp:309-349): tx_interp.hpp's stored-tone exciter, no key and no x 20 (:344-345), fed from cosBuffer3 /
 // sinBuffer3 x bandOutputFactor (:313-314).  The TX IQ correction is per channel: LSB scales I by -IQXAmp, USB by +IQXAmp
-// (:317-325).  Compiled as part of tx_host.cpp.
+// (:317-325).  A translation unit of its own (tx_cal_kernel.o); tx_host.cpp sees it through tx_internal.hpp.
 #include <hip/hip_runtime.h>
 
 #include "tx_interp.hpp"

@@ -1,7 +1,7 @@
 // t41_sdr_amd/csrc/tx_cw_kernel.hip -- gfx950 kernel of the T41 CW exciter, CW_ExciterIQData() (CW_Excite.cpp:66-118):
 // tx_interp.hpp's stored-tone exciter, keyed and with the x 20, fed from cosBuffer2 / sinBuffer2 x 0.127 (:69-70).  The TX
 // IQ correction's signs are the opposite of ExciterIQData()'s and there is no Q x 1.00 (:77-87); the host side sets them.
-// Compiled as part of tx_host.cpp.
+// A translation unit of its own (tx_cw_kernel.o); tx_host.cpp sees it through tx_internal.hpp.
 #include <hip/hip_runtime.h>
 
 #include "tx_interp.hpp"

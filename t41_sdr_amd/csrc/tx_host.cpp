@@ -13,8 +13,6 @@
 #include "dev_buf.hpp"
 #include "last_error.hpp"  // fail(): failures reach t41rx_last_error(), like the receive path's
 #include "tx_internal.hpp"
-#include "tx_cw_kernel.hip"  // the CW exciter's kernel and launcher
-#include "tx_cal_kernel.hip"  // the calibration exciter's
 
 using namespace t41;
 

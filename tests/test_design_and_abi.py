@@ -167,8 +167,10 @@ def test_diagnostic_builds_are_fenced(T, tmp_path):
         assert r.returncode != 0 and "T41RX_EXPERIMENT=1" in r.stderr, (flag, r.stderr[-400:])
     obj = str(tmp_path / "rx_dispatch_exp.o")
     subprocess.check_call(base + ["-DT41RX_EXPERIMENT=1", "-DT41RX_CLK", "-c", "rx_dispatch.hip", "-o", obj], cwd=csrc)
-    objs = [os.path.join(csrc, o) for o in ("rx512_ssb.o", "rx512_am.o", "rx512_nfm.o", "rx512_sam.o", "rx_long.o", "fastconv.o", "display_kernel.o",
-                                            "nr_kernels.o", "rx_host.o", "design.o", "nr_tables.o", "tx_kernels.o", "tx_host.o", "tx_tables.o")]
+    # the product's objects, as the Makefile lists them (the one list): every one but the dispatch unit built above
+    listed = [subprocess.check_output(["make", "-s", target], cwd=csrc, text=True).split() for target in ("print-rxk-objs", "print-host-objs")]
+    assert "rx_dispatch.o" in listed[0] and "rx_host.o" in listed[1]
+    objs = [os.path.join(csrc, o) for o in listed[0] + listed[1] if o != "rx_dispatch.o"]
     lib_path = str(tmp_path / "libt41rx_exp.so")
     subprocess.check_call(["hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", obj] + objs + ["-o", lib_path])
     code = ("import ctypes as C, sys; lib = C.CDLL(%r); lib.t41rx_last_error.restype = C.c_char_p; ctx = C.c_void_p(); "
@@ -204,3 +206,24 @@ def test_kernel_sources_carry_no_build_switches():
                         if macro not in allowed:
                             found.append("%s:%d: %s" % (name, no, line.strip()))
     assert not found, found
+
+
+def test_no_source_includes_a_kernel_file():
+    """Every .hip file is a translation unit of its own with a Makefile rule of its own: no .cpp, .hpp or .hip file under
+    t41_sdr_amd/csrc #includes one (a host file that did would be compiled as device code, and a setter would rebuild
+    the kernels).  Kernel text shared between kernels is an .inc file; those may be included."""
+    csrc = os.path.join(ROOT, "t41_sdr_amd", "csrc")
+    found, seen = [], 0
+    for name in sorted(os.listdir(csrc)):
+        if os.path.splitext(name)[1] not in (".hpp", ".hip", ".cpp"):
+            continue
+        seen += 1
+        with open(os.path.join(csrc, name)) as f:
+            for no, line in enumerate(f, 1):
+                if re.match(r"\s*#\s*include\s*[\"<][^\">]*\.hip[\">]", line):
+                    found.append("%s:%d: %s" % (name, no, line.strip()))
+    assert seen and not found, found
+    # and the Makefile builds each of them into an object of that name, which the library links
+    listed = set(re.findall(r"\b(\w+)\.o\b", open(os.path.join(csrc, "Makefile")).read()))
+    hips = {os.path.splitext(n)[0] for n in os.listdir(csrc) if n.endswith(".hip")}
+    assert hips and hips <= listed, sorted(hips - listed)
