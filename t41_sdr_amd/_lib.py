@@ -2,6 +2,9 @@
 
 The library is the product: HIP kernels + C++ host side.  There is no Python or CPU
 implementation of the path behind it; if the shared object is missing, loading fails loudly.
+
+Both binding tables live here, SYMBOLS (include/t41rx.h, receive) and TX_SYMBOLS (include/t41tx.h, transmit), and
+load() binds both: no entry point is ever called with ctypes' default conversions.
 """
 import ctypes as C
 import os
@@ -56,6 +59,11 @@ class PanadapterOut(C.Structure):
         ("audio_spect", C.c_void_p),
         ("smeter", C.c_void_p),
     ]
+
+
+class TxParams(C.Structure):
+    """struct t41tx_params (include/t41tx.h)"""
+    _fields_ = [("mode", C.c_int32), ("IQXAmpCorrectionFactor", C.c_float), ("IQXPhaseCorrectionFactor", C.c_float)]
 
 
 # every symbol include/t41rx.h declares: (restype, argtypes)
@@ -140,6 +148,31 @@ SYMBOLS = {
     "t41rx_set_panadapter_counter": (C.c_int, [_vp, C.c_int64]),
 }
 
+# every symbol include/t41tx.h declares
+TX_SYMBOLS = {
+    "t41tx_default_params": (None, [C.POINTER(TxParams)]),
+    "t41tx_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.POINTER(TxParams)]),
+    "t41tx_destroy": (C.c_int, [_vp]),
+    "t41tx_set_params": (C.c_int, [_vp, C.POINTER(TxParams)]),
+    "t41tx_reset": (C.c_int, [_vp]),
+    "t41tx_n_channels": (C.c_int, [_vp]),
+    "t41tx_process_device_q15": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "t41tx_process_host_q15": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int]),
+    "t41tx_set_transmit_eq_bands": (C.c_int, [_vp, _vp]),
+    "t41tx_set_transmit_eq": (C.c_int, [_vp, C.c_int, _vp]),
+    "t41tx_get_transmit_eq": (C.c_int, [_vp, _vp]),
+    "t41tx_state_bytes": (C.c_size_t, [_vp]),
+    "t41tx_get_state": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "t41tx_set_state": (C.c_int, [_vp, _vp, C.c_size_t]),
+    "t41tx_set_cw_tone": (C.c_int, [_vp, _vp, _vp]),
+    "t41tx_process_cw_device_q15": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "t41tx_process_cw_host_q15": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int]),
+    "t41tx_set_cal_tone": (C.c_int, [_vp, _vp, _vp, C.c_float]),
+    "t41tx_set_cal_corrections": (C.c_int, [_vp, _vp, _vp]),
+    "t41tx_process_cal_device_q15": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "t41tx_process_cal_host_q15": (C.c_int, [_vp, _vp, _vp, C.c_int]),
+}
+
 _lib = None
 
 
@@ -166,7 +199,7 @@ def load():
     except ImportError:
         pass
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in {**SYMBOLS, **TX_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the ABI is incomplete
         fn.restype = res
         fn.argtypes = args

@@ -12,7 +12,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib, panadapter
+from . import _args, _lib, panadapter
+from ._args import F32P, I32P, U16P, channel_mask, cuda, cuda_tensor, get_blob, int_table, kept, ptr, run, set_blob, table, table_pair, value, with_fields
 from ._lib import DEMOD_AM, DEMOD_LSB, DEMOD_NFM, DEMOD_SAM, DEMOD_USB, Params, T41RxError, check  # noqa: F401
 
 
@@ -21,11 +22,7 @@ def default_params(**overrides):
     lib = _lib.load()
     p = Params()
     lib.t41rx_default_params(C.byref(p))
-    for k, v in overrides.items():
-        if not hasattr(p, k):
-            raise AttributeError("t41rx_params has no field %r" % k)
-        setattr(p, k, v)
-    return p
+    return with_fields(p, "t41rx_params", overrides)
 
 
 def design_coeffs(params):
@@ -34,9 +31,7 @@ def design_coeffs(params):
     n = lib.t41rx_coeff_blob_bytes(params.fft_length)
     if n == 0:
         raise T41RxError(_lib.ERR_ARG, "unsupported fft_length %d" % params.fft_length)
-    blob = np.zeros(n, dtype=np.uint8)
-    check(lib.t41rx_design_coeffs(C.byref(params), blob.ctypes.data_as(C.c_void_p), n))
-    return blob
+    return get_blob(lib.t41rx_design_coeffs, C.byref(params), n)
 
 
 def ft8_tables():
@@ -98,11 +93,7 @@ class RxChain:
     def CalcFilters(self, **changes):
         """Filter/mode/gain change between two ProcessIQData() calls; state is kept.  A refused change leaves
         self.params as it was (t41rx_set_params validates before it changes anything)."""
-        p = Params.from_buffer_copy(self.params)
-        for k, v in changes.items():
-            if not hasattr(p, k):
-                raise AttributeError("t41rx_params has no field %r" % k)
-            setattr(p, k, v)
+        p = with_fields(Params.from_buffer_copy(self.params), "t41rx_params", changes)
         check(self._lib.t41rx_set_params(self._ctx, C.byref(p)))
         self.params = p
 
@@ -110,7 +101,7 @@ class RxChain:
 
     def SetNCOFreq(self, NCOFreq):
         a = np.ascontiguousarray(np.broadcast_to(np.asarray(NCOFreq, dtype=np.int32), (self.n_channels,)))
-        check(self._lib.t41rx_set_nco_freq(self._ctx, a.ctypes.data_as(C.POINTER(C.c_int32)), self.n_channels))
+        check(self._lib.t41rx_set_nco_freq(self._ctx, ptr(a, I32P), self.n_channels))
 
     def get_params(self):
         """the parameters the context runs with (after set_coeffs(): the ones the blob was designed for)"""
@@ -119,14 +110,10 @@ class RxChain:
         return p
 
     def coeffs(self):
-        n = self._lib.t41rx_coeff_blob_bytes(self.params.fft_length)
-        blob = np.zeros(n, dtype=np.uint8)
-        check(self._lib.t41rx_get_coeffs(self._ctx, blob.ctypes.data_as(C.c_void_p), n))
-        return blob
+        return get_blob(self._lib.t41rx_get_coeffs, self._ctx, self._lib.t41rx_coeff_blob_bytes(self.params.fft_length))
 
     def set_coeffs(self, blob):
-        blob = np.ascontiguousarray(blob, dtype=np.uint8)
-        check(self._lib.t41rx_set_coeffs(self._ctx, blob.ctypes.data_as(C.c_void_p), blob.size))
+        set_blob(self._lib.t41rx_set_coeffs, self._ctx, blob)
         # the context now runs the parameters the blob was designed for: a later CalcFilters(one
         # field) must start from THEM, not from what this object was created with
         self.params = self.get_params()
@@ -151,14 +138,10 @@ class RxChain:
             check(self._lib.t41rx_set_input_map(self._ctx, None, 0, 0))
             self._n_streams = 0
             return
-        m = np.asarray(stream_of_channel)
-        if m.ndim != 1 or not np.issubdtype(m.dtype, np.integer) or (m.size and (m.min() < -2**31 or m.max() >= 2**31)):
-            raise ValueError("stream_of_channel must be a 1-d array of int32 stream numbers, got %r %s" % (m.shape, m.dtype))
-        m = np.ascontiguousarray(m, dtype=np.int32)
+        m = int_table(stream_of_channel, np.int32, None, "stream_of_channel must be a 1-d array of int32 stream numbers, got %r %s")
         if n_streams is None:
             n_streams = int(m.max()) + 1 if m.size else 0
-        check(self._lib.t41rx_set_input_map(self._ctx, m.ctypes.data_as(C.POINTER(C.c_int32)), int(m.size), int(n_streams)))
-
+        check(self._lib.t41rx_set_input_map(self._ctx, ptr(m, I32P), int(m.size), int(n_streams)))
         self._n_streams = int(n_streams)
 
     @property
@@ -170,10 +153,7 @@ class RxChain:
     def input_map(self):
         """the input map as an int32 array [n_channels] (a copy), or None with the map off"""
         m = np.zeros(self.n_channels, np.int32)
-        v = self._lib.t41rx_get_input_map(self._ctx, m.ctypes.data_as(C.POINTER(C.c_int32)), self.n_channels)
-        if v < 0:
-            check(v)
-        return m if v > 0 else None
+        return m if value(self._lib.t41rx_get_input_map(self._ctx, ptr(m, I32P), self.n_channels)) > 0 else None
 
     def set_noise_blanker(self, on):
         """NB_on (Process.cpp:873-876): the receive noise blanker on the demodulated audio, behind the noise reduction and
@@ -182,41 +162,28 @@ class RxChain:
 
     @property
     def noise_blanker(self):
-        v = self._lib.t41rx_get_noise_blanker(self._ctx)
-        if v < 0:
-            check(v)
-        return v
+        return value(self._lib.t41rx_get_noise_blanker(self._ctx))
 
     def set_receive_eq_bands(self, coeffs):
         """The receive equalizer's band table (t41rx_set_receive_eq_bands): the firmware's EQ_Band1Coeffs ..
         EQ_Band14Coeffs as [14][4][5] or [14][20], {b0, b1, b2, a1, a2} per section with the a's negated.  Kept across
         CalcFilters() / set_coeffs(); the filter memories are not reset."""
-        c = np.ascontiguousarray(np.asarray(coeffs, dtype=np.float32))
-        if c.size != 14 * 4 * 5 or c.shape[0] != 14:
-            raise ValueError("receive-EQ band table must be [14][4][5] or [14][20], got %r" % (c.shape,))
-        check(self._lib.t41rx_set_receive_eq_bands(self._ctx, c.ctypes.data_as(C.c_void_p)))
+        c = table(coeffs, np.float32, (14, 20), "receive-EQ band table must be [14][4][5] or [14][20], got %r", rows=True)
+        check(self._lib.t41rx_set_receive_eq_bands(self._ctx, ptr(c)))
 
     def set_receive_eq(self, on, levels=None):
         """receiveEQFlag and EEPROMData.equalizerRec (Process.cpp:828-832, Filter.cpp:117-165): the receive equalizer on
         the demodulated audio, in front of the noise reduction, the notch and the noise blanker (t41rx_set_receive_eq;
         0 / 1, fft_length 512, a band table loaded first).  levels: 14 ints, or None to keep the current ones (100 each
         until set).  Kept across CalcFilters() / set_coeffs()."""
-        if levels is None:
-            check(self._lib.t41rx_set_receive_eq(self._ctx, int(on), None))
-            return
-        lv = np.ascontiguousarray(np.asarray(levels, dtype=np.int32))
-        if lv.shape != (14,):
-            raise ValueError("receive-EQ levels must be 14 ints, got %r" % (lv.shape,))
-        check(self._lib.t41rx_set_receive_eq(self._ctx, int(on), lv.ctypes.data_as(C.c_void_p)))
+        lv = None if levels is None else table(levels, np.int32, (14,), "receive-EQ levels must be 14 ints, got %r")
+        check(self._lib.t41rx_set_receive_eq(self._ctx, int(on), ptr(lv)))
 
     @property
     def receive_eq(self):
         """(on, levels): the receive equalizer's switch and its 14 levels"""
         lv = np.zeros(14, np.int32)
-        v = self._lib.t41rx_get_receive_eq(self._ctx, lv.ctypes.data_as(C.c_void_p))
-        if v < 0:
-            check(v)
-        return v, lv
+        return value(self._lib.t41rx_get_receive_eq(self._ctx, ptr(lv))), lv
 
     def set_cw_tables(self, audio_filters=None, decode_fir=None):
         """The CW receive tables (t41rx_set_cw_tables): audio_filters = the firmware's CW_AudioFilterCoeffs1..5 as
@@ -224,15 +191,10 @@ class RxChain:
         taps.  None keeps what is loaded.  Kept across CalcFilters() / set_coeffs(); no memory is reset."""
         f = d = None
         if audio_filters is not None:
-            f = np.ascontiguousarray(np.asarray(audio_filters, dtype=np.float32))
-            if f.size != 5 * 6 * 5 or f.shape[0] != 5:
-                raise ValueError("CW filter tables must be [5][6][5] or [5][30], got %r" % (f.shape,))
+            f = table(audio_filters, np.float32, (5, 30), "CW filter tables must be [5][6][5] or [5][30], got %r", rows=True)
         if decode_fir is not None:
-            d = np.ascontiguousarray(np.asarray(decode_fir, dtype=np.float32))
-            if d.shape != (64,):
-                raise ValueError("CW decode FIR must be 64 taps, got %r" % (d.shape,))
-        check(self._lib.t41rx_set_cw_tables(self._ctx, None if f is None else f.ctypes.data_as(C.c_void_p),
-                                            None if d is None else d.ctypes.data_as(C.c_void_p)))
+            d = table(decode_fir, np.float32, (64,), "CW decode FIR must be 64 taps, got %r")
+        check(self._lib.t41rx_set_cw_tables(self._ctx, ptr(f), ptr(d)))
 
     def set_cw_filter(self, CWFilterIndex):
         """CWFilterIndex (Process.cpp:882-912): 0 .. 4 = the 0.8 / 1.0 / 1.3 / 1.8 / 2.0 kHz narrow audio filter behind the
@@ -242,10 +204,7 @@ class RxChain:
 
     @property
     def cw_filter(self):
-        v = self._lib.t41rx_get_cw_filter(self._ctx)
-        if v < 0:
-            check(v)
-        return v
+        return value(self._lib.t41rx_get_cw_filter(self._ctx))
 
     def set_cw_detector(self, on, max_frames=1):
         """decoderFlag (DoCWReceiveProcessing(), CWProcessing.cpp:322-373).  on = 1 allocates and returns the result
@@ -254,31 +213,15 @@ class RxChain:
         (cw_results(n) is that view).  on = 0 switches the detector off and returns None.  The `combinedCoeff > 50`
         decision and the Morse decoder behind it are set_cw_decoder()'s.  Runs only while xmtMode == CW_MODE; fft_length 512; the
         decode FIR loaded first.  Kept across CalcFilters() / set_coeffs()."""
-        if not on:
-            check(self._lib.t41rx_set_cw_detector(self._ctx, 0, None, 0))
-            self._cw = None
-            return None
-        import torch
-        if int(max_frames) < 1:
-            raise ValueError("max_frames must be >= 1")
-        t = torch.zeros(self.n_channels, int(max_frames), 4, dtype=torch.float32, device="cuda:%d" % self.device)
-        check(self._lib.t41rx_set_cw_detector(self._ctx, int(on), C.c_void_p(t.data_ptr()), int(max_frames)))
-        self._cw = t  # keep alive
-        return t
+        return self._result_stage("_cw", self._lib.t41rx_set_cw_detector, on, max_frames, ("float32", None, 4))
 
     @property
     def cw_detector(self):
-        v = self._lib.t41rx_get_cw_detector(self._ctx)
-        if v < 0:
-            check(v)
-        return v
+        return value(self._lib.t41rx_get_cw_detector(self._ctx))
 
     def cw_results(self, n_frames):
         """the detector's results of the last process call of n_frames frames: a view [n_channels, n_frames, 4]"""
-        t = getattr(self, "_cw", None)
-        if t is None:
-            raise ValueError("the CW detector is off")
-        return t.view(-1)[:self.n_channels * int(n_frames) * 4].view(self.n_channels, int(n_frames), 4)
+        return self._first_frames(kept(self, "_cw", "the CW detector is off"), n_frames, 4)
 
     def set_cw_decode_tree(self, tree):
         """The Morse decoder's bigMorseCodeTree (CWProcessing.cpp:540; t41rx_set_cw_decode_tree): 129 bytes, as bytes,
@@ -286,7 +229,7 @@ class RxChain:
         if isinstance(tree, str):
             tree = tree.encode("ascii")
         t = np.ascontiguousarray(np.frombuffer(tree, np.uint8) if isinstance(tree, (bytes, bytearray)) else np.asarray(tree, dtype=np.uint8))
-        check(self._lib.t41rx_set_cw_decode_tree(self._ctx, t.ctypes.data_as(C.c_void_p), int(t.size)))
+        check(self._lib.t41rx_set_cw_decode_tree(self._ctx, ptr(t), int(t.size)))
 
     def set_cw_decoder(self, on, max_frames=1):
         """The Morse decoder behind the detector (DoCWDecoding(), CWProcessing.cpp:365-371, :519-815;
@@ -295,31 +238,15 @@ class RxChain:
         code or 0, ditLength behind the frame] (cw_text(n) is that view).  on = 0 switches it off and returns None.  Runs
         exactly when the detector runs (xmtMode == CW_MODE, set_cw_detector(1)); fft_length 512; the tree loaded first.
         Kept across CalcFilters() / set_coeffs()."""
-        if not on:
-            check(self._lib.t41rx_set_cw_decoder(self._ctx, 0, None, 0))
-            self._cw_text = None
-            return None
-        import torch
-        if int(max_frames) < 1:
-            raise ValueError("max_frames must be >= 1")
-        t = torch.zeros(self.n_channels, int(max_frames), 2, dtype=torch.int32, device="cuda:%d" % self.device)
-        check(self._lib.t41rx_set_cw_decoder(self._ctx, int(on), C.c_void_p(t.data_ptr()), int(max_frames)))
-        self._cw_text = t  # keep alive
-        return t
+        return self._result_stage("_cw_text", self._lib.t41rx_set_cw_decoder, on, max_frames, ("int32", None, 2))
 
     @property
     def cw_decoder(self):
-        v = self._lib.t41rx_get_cw_decoder(self._ctx)
-        if v < 0:
-            check(v)
-        return v
+        return value(self._lib.t41rx_get_cw_decoder(self._ctx))
 
     def cw_text(self, n_frames):
         """the decoder's words of the last process call of n_frames frames: a view [n_channels, n_frames, 2]"""
-        t = getattr(self, "_cw_text", None)
-        if t is None:
-            raise ValueError("the CW decoder is off")
-        return t.view(-1)[:self.n_channels * int(n_frames) * 2].view(self.n_channels, int(n_frames), 2)
+        return self._first_frames(kept(self, "_cw_text", "the CW decoder is off"), n_frames, 2)
 
     def set_cw_clock(self, t0_ms=0, num=32, den=3):
         """The decoder's clock (t41rx_set_cw_clock): millis(n) = t0_ms + floor(n * num / den) for the channel's n-th
@@ -329,13 +256,7 @@ class RxChain:
     def reset_cw_histograms(self, channels=None):
         """ResetHistograms() (CWProcessing.cpp:501-517), what the firmware runs at every retune, on the channels whose
         entry is non-zero (None: all): both histograms' words 0 .. 749 and the scalars it names, nothing else."""
-        if channels is None:
-            check(self._lib.t41rx_reset_cw_histograms(self._ctx, None, 0))
-            return
-        m = np.ascontiguousarray(np.asarray(channels).astype(bool).astype(np.uint8))
-        if m.shape != (self.n_channels,):
-            raise ValueError("channels must have n_channels = %d entries, got %r" % (self.n_channels, m.shape))
-        check(self._lib.t41rx_reset_cw_histograms(self._ctx, m.ctypes.data_as(C.c_void_p), self.n_channels))
+        check(self._lib.t41rx_reset_cw_histograms(self._ctx, *channel_mask(channels, self.n_channels)))
 
     # -- FT8 receive up to the waterfall ------------------------------------------------------
     def set_ft8_tables(self, window=None, mag_db=None):
@@ -346,11 +267,8 @@ class RxChain:
             window, mag_db = ft8_tables()
         if window is None or mag_db is None:
             raise ValueError("window and mag_db must both be given or both be None")
-        w = np.ascontiguousarray(np.asarray(window, dtype=np.float32))
-        m = np.ascontiguousarray(np.asarray(mag_db, dtype=np.float32))
-        if w.shape != (2048,) or m.shape != (16385,):
-            raise ValueError("FT8 tables must be 2048 and 16385 floats, got %r and %r" % (w.shape, m.shape))
-        check(self._lib.t41rx_set_ft8_tables(self._ctx, w.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p)))
+        w, m = table_pair(window, mag_db, (2048,), (16385,), "FT8 tables must be 2048 and 16385 floats, got %r and %r")
+        check(self._lib.t41rx_set_ft8_tables(self._ctx, ptr(w), ptr(m)))
 
     def set_ft8(self, on, max_frames=1):
         """FT8 receive on a USB context (Process.cpp:627-686, ft8.cpp:153-268; t41rx_set_ft8): the audio collector, the
@@ -360,41 +278,20 @@ class RxChain:
         n * 4 words as [n_channels][n][FT_8_counter, ft8_flag, 0 or 1 + the half completed in this frame, dataLoop]
         (ft8_status(n) is that view).  on = 0 switches it off and returns None.  Nothing is collected before ft8_sync().
         fft_length 512, mode USB; the tables loaded first.  Kept across CalcFilters() / set_coeffs()."""
-        if not on:
-            check(self._lib.t41rx_set_ft8(self._ctx, 0, None, None, 0))
-            self._ft8 = None
-            return None
-        import torch
-        if int(max_frames) < 1:
-            raise ValueError("max_frames must be >= 1")
-        dev = "cuda:%d" % self.device
-        power = torch.zeros(self.n_channels, 2, 92 * 1472, dtype=torch.uint8, device=dev)
-        status = torch.zeros(self.n_channels, int(max_frames), 4, dtype=torch.int32, device=dev)
-        check(self._lib.t41rx_set_ft8(self._ctx, int(on), C.c_void_p(power.data_ptr()), C.c_void_p(status.data_ptr()), int(max_frames)))
-        self._ft8 = (power, status)  # keep alive
-        return power, status
+        return self._result_stage("_ft8", self._lib.t41rx_set_ft8, on, max_frames, ("uint8", 2, 92 * 1472), ("int32", None, 4))
 
     @property
     def ft8(self):
-        v = self._lib.t41rx_get_ft8(self._ctx)
-        if v < 0:
-            check(v)
-        return v
+        return value(self._lib.t41rx_get_ft8(self._ctx))
 
     def ft8_status(self, n_frames):
         """the FT8 status words of the last process call of n_frames frames: a view [n_channels, n_frames, 4]"""
-        t = getattr(self, "_ft8", None)
-        if t is None:
-            raise ValueError("FT8 receive is off")
-        return t[1].view(-1)[:self.n_channels * int(n_frames) * 4].view(self.n_channels, int(n_frames), 4)
+        return self._first_frames(kept(self, "_ft8", "FT8 receive is off")[1], n_frames, 4)
 
     def ft8_power(self):
         """export_fft_power, uint8 CUDA [n_channels, 2, 92 * 1472]: the half a status word reported complete holds the
         finished slot, [92 blocks][time_sub 0 / 512][freq_sub 0 / 1][368]"""
-        t = getattr(self, "_ft8", None)
-        if t is None:
-            raise ValueError("FT8 receive is off")
-        return t[0]
+        return kept(self, "_ft8", "FT8 receive is off")[0]
 
     def set_ft8_clock(self, t0_ms=0, num=32, den=3):
         """The slot timing's clock (t41rx_set_ft8_clock): millis(n) = t0_ms + floor(n * num / den) for the channel's n-th
@@ -404,24 +301,14 @@ class RxChain:
     def ft8_sync(self, channels=None):
         """auto_sync_FT8()'s success branch (ft8.cpp:133-136) on the channels whose entry is non-zero (None: all):
         start_time = millis(n), ft8_flag = 1, FT_8_counter = 0, syncFlag = true.  The caller's clock decides when."""
-        if channels is None:
-            check(self._lib.t41rx_ft8_sync(self._ctx, None, 0))
-            return
-        m = np.ascontiguousarray(np.asarray(channels).astype(bool).astype(np.uint8))
-        if m.shape != (self.n_channels,):
-            raise ValueError("channels must have n_channels = %d entries, got %r" % (self.n_channels, m.shape))
-        check(self._lib.t41rx_ft8_sync(self._ctx, m.ctypes.data_as(C.c_void_p), self.n_channels))
+        check(self._lib.t41rx_ft8_sync(self._ctx, *channel_mask(channels, self.n_channels)))
 
     def ft8_state(self):
         """the FT8 memory's record (t41rx_ft8_get_state): 8 int32 of header, then [n_channels][3088] int32 (uint8 array)"""
-        n = self._lib.t41rx_ft8_state_bytes(self._ctx)
-        buf = np.zeros(n, dtype=np.uint8)
-        check(self._lib.t41rx_ft8_get_state(self._ctx, buf.ctypes.data_as(C.c_void_p), n))
-        return buf
+        return get_blob(self._lib.t41rx_ft8_get_state, self._ctx, self._lib.t41rx_ft8_state_bytes(self._ctx))
 
     def set_ft8_state(self, buf):
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        check(self._lib.t41rx_ft8_set_state(self._ctx, buf.ctypes.data_as(C.c_void_p), buf.size))
+        set_blob(self._lib.t41rx_ft8_set_state, self._ctx, buf)
 
     # -- FT8 from 12 kS/s audio (DEMOD_FT8_WAV) ----------------------------------------------
     def ft8_audio(self, pcm):
@@ -430,49 +317,40 @@ class RxChain:
         arm_float_to_q15), a CUDA tensor (default stream, no synchronisation) or a numpy array.  Always channel-major:
         the input map and the buffer layout do not apply.  Needs set_ft8(1, max_frames >= k); writes the same power halves
         and returns the call's status words, the view ft8_status(k)."""
-        n = self.n_channels
-        if isinstance(pcm, np.ndarray):
+        host = isinstance(pcm, np.ndarray)
+        if host:
             if pcm.dtype not in (np.int16, np.float32):
                 raise ValueError("pcm must be int16 or float32, got %s" % pcm.dtype)
-            a = np.ascontiguousarray(pcm)
-            k = self._ft8_audio_frames(a.shape)
-            fn = self._lib.t41rx_ft8_audio_host_q15 if a.dtype == np.int16 else self._lib.t41rx_ft8_audio_host
-            check(fn(self._ctx, a.ctypes.data_as(C.c_void_p), k))
-            return self.ft8_status(k)
-        import torch
-        if not (isinstance(pcm, torch.Tensor) and pcm.is_cuda and pcm.dtype in (torch.int16, torch.float32) and pcm.is_contiguous()):
-            raise ValueError("pcm must be a contiguous int16 or float32 CUDA tensor or numpy array")
-        if pcm.device.index != self.device:
-            raise ValueError("pcm lives on another device than this RxChain")
+            pcm = np.ascontiguousarray(pcm)
+            q15 = pcm.dtype == np.int16
+        else:
+            import torch
+            if not (isinstance(pcm, torch.Tensor) and cuda_tensor(pcm, (torch.int16, torch.float32))):
+                raise ValueError("pcm must be a contiguous int16 or float32 CUDA tensor or numpy array")
+            if pcm.device.index != self.device:
+                raise ValueError("pcm lives on another device than this RxChain")
+            q15 = pcm.dtype == torch.int16
         k = self._ft8_audio_frames(tuple(pcm.shape))
-        fn = self._lib.t41rx_ft8_audio_device_q15 if pcm.dtype == torch.int16 else self._lib.t41rx_ft8_audio_device
-        check(fn(self._ctx, C.c_void_p(pcm.data_ptr()), k))
+        lib = self._lib
+        fn = ((lib.t41rx_ft8_audio_host_q15 if q15 else lib.t41rx_ft8_audio_host) if host
+              else (lib.t41rx_ft8_audio_device_q15 if q15 else lib.t41rx_ft8_audio_device))
+        check(fn(self._ctx, ptr(pcm), k))  # (the device entries run on the default stream)
         return self.ft8_status(k)
 
     def _ft8_audio_frames(self, shape):
         if len(shape) != 2 or shape[0] != self.n_channels or shape[1] < 128 or shape[1] % 128:
             raise ValueError("pcm must be [n_channels = %d, 128 * k], got %r" % (self.n_channels, tuple(shape)))
-        if getattr(self, "_ft8", None) is None:
-            raise ValueError("FT8 receive is off")
+        kept(self, "_ft8", "FT8 receive is off")
         return shape[1] // 128
-
-    def _ft8_audio_mark(self, fn, channels):
-        if channels is None:
-            check(fn(self._ctx, None, 0))
-            return
-        m = np.ascontiguousarray(np.asarray(channels).astype(bool).astype(np.uint8))
-        if m.shape != (self.n_channels,):
-            raise ValueError("channels must have n_channels = %d entries, got %r" % (self.n_channels, m.shape))
-        check(fn(self._ctx, m.ctypes.data_as(C.c_void_p), self.n_channels))
 
     def ft8_audio_begin(self, channels=None):
         """setupFT8Wav() (ft8.cpp:1372) on the channels whose entry is non-zero (None: all): FT_8_counter = 0, nothing else"""
-        self._ft8_audio_mark(self._lib.t41rx_ft8_audio_begin, channels)
+        check(self._lib.t41rx_ft8_audio_begin(self._ctx, *channel_mask(channels, self.n_channels)))
 
     def ft8_audio_end(self, channels=None):
         """the WAV mode's exit (Process.cpp:339-342) on the channels whose entry is non-zero (None: all): syncFlag = 0,
         FT_8_counter = 0, ft8_flag = 0, nothing else"""
-        self._ft8_audio_mark(self._lib.t41rx_ft8_audio_end, channels)
+        check(self._lib.t41rx_ft8_audio_end(self._ctx, *channel_mask(channels, self.n_channels)))
 
     def set_ft8_decode_tables(self, costas, gray, nm, mn, nrw):
         """The FT8 decode's tables (t41rx_set_ft8_decode_tables): kCostas_map[7], kGray_map[8], kNm[83][7], kMn[174][3] and
@@ -486,7 +364,7 @@ class RxChain:
             if a.min() < 0 or a.max() > 255:
                 raise ValueError("%s does not fit uint8" % what)
             arrs.append(np.ascontiguousarray(a, dtype=np.uint8))
-        check(self._lib.t41rx_set_ft8_decode_tables(self._ctx, *[a.ctypes.data_as(C.c_void_p) for a in arrs]))
+        check(self._lib.t41rx_set_ft8_decode_tables(self._ctx, *[ptr(a) for a in arrs]))
 
     def set_ft8_decode(self, max_candidates=20, min_score=40, ldpc_iterations=10):
         """kMax_candidates (1..20), kMin_score and kLDPC_iterations (1..50) of the decode (t41rx_set_ft8_decode); the
@@ -511,7 +389,7 @@ class RxChain:
         import torch
         from . import ft8 as F
         n = self.n_channels
-        dev = "cuda:%d" % self.device
+        dev = cuda(self.device)
         sel = None
         if select is not None:
             sel = np.asarray(select)
@@ -520,7 +398,7 @@ class RxChain:
             if ((sel < -128) | (sel > 127)).any():
                 raise ValueError("select does not fit int8")
             sel = np.ascontiguousarray(sel, dtype=np.int8)
-        ptr, stride = None, 0
+        wf, stride = None, 0
         if waterfall is not None:
             if not (isinstance(waterfall, torch.Tensor) and waterfall.is_cuda and waterfall.dtype == torch.uint8 and waterfall.dim() == 2
                     and waterfall.shape[0] == n and waterfall.stride(1) == 1):
@@ -528,17 +406,15 @@ class RxChain:
             need = F.SLOT_BYTES * (2 if sel is not None and (sel == 1).any() else 1)
             if waterfall.shape[1] < need:
                 raise ValueError("waterfall rows hold %d bytes, the call reads %d" % (waterfall.shape[1], need))
-            ptr, stride = C.c_void_p(waterfall.data_ptr()), int(waterfall.stride(0)) if n > 1 else int(waterfall.shape[1])
+            wf, stride = waterfall, int(waterfall.stride(0)) if n > 1 else int(waterfall.shape[1])
         res = torch.zeros(n, F.RESULT.itemsize, dtype=torch.uint8, device=dev)
         taps = None
         if debug:
             taps = (torch.zeros(n, F.MAX_CANDIDATES, 174, dtype=torch.float32, device=dev),
                     torch.zeros(n, F.MAX_CANDIDATES, 174, dtype=torch.uint8, device=dev))
-            check(self._lib.t41rx_set_ft8_decode_debug(self._ctx, C.c_void_p(taps[0].data_ptr()), C.c_void_p(taps[1].data_ptr())))
+            check(self._lib.t41rx_set_ft8_decode_debug(self._ctx, ptr(taps[0]), ptr(taps[1])))
         try:
-            stream = torch.cuda.current_stream(res.device).cuda_stream
-            check(self._lib.t41rx_ft8_decode_device(self._ctx, ptr, stride, None if sel is None else sel.ctypes.data_as(C.c_void_p), n,
-                                                    C.c_void_p(res.data_ptr()), C.c_void_p(stream)))
+            check(self._lib.t41rx_ft8_decode_device(self._ctx, ptr(wf), stride, ptr(sel), n, ptr(res), _args.stream_of(self.device)))
             out = res.cpu().numpy().view(F.RESULT).reshape(n)
             if debug:
                 return out, taps[0].cpu().numpy(), taps[1].cpu().numpy()
@@ -549,20 +425,38 @@ class RxChain:
                 check(self._lib.t41rx_set_ft8_decode_debug(self._ctx, None, None))
 
     def get_state(self):
-        n = self._lib.t41rx_state_bytes(self._ctx)
-        buf = np.zeros(n, dtype=np.uint8)
-        check(self._lib.t41rx_get_state(self._ctx, buf.ctypes.data_as(C.c_void_p), n))
-        return buf
+        return get_blob(self._lib.t41rx_get_state, self._ctx, self._lib.t41rx_state_bytes(self._ctx))
 
     def set_state(self, buf):
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        check(self._lib.t41rx_set_state(self._ctx, buf.ctypes.data_as(C.c_void_p), buf.size))
+        set_blob(self._lib.t41rx_set_state, self._ctx, buf)
 
     def state_records(self, buf=None):
         """the per-channel records of a checkpoint (default: a fresh one) as float32 [n_channels, floats]"""
         buf = self.get_state() if buf is None else np.ascontiguousarray(buf, dtype=np.uint8)
         per = int(buf[:STATE_HEADER_BYTES].view(np.int32)[4])  # floats per channel of the path's section (the side stages' follow it)
         return buf[STATE_HEADER_BYTES:STATE_HEADER_BYTES + 4 * per * self.n_channels].view(np.float32).reshape(self.n_channels, per)
+
+    def _result_stage(self, attr, entry, on, max_frames, *tensors):
+        """The switch of a stage that owns its result tensors, each (dtype, dimensions behind n_channels) with None for
+        max_frames.  Off: tells the library and drops them.  On: allocates them zeroed, hands them to entry(ctx, on,
+        pointers ..., max_frames) and keeps them alive in self.<attr>; a refused call leaves self.<attr> as it was."""
+        if not on:
+            check(entry(self._ctx, 0, *[None] * len(tensors), 0))
+            setattr(self, attr, None)
+            return None
+        import torch
+        if int(max_frames) < 1:
+            raise ValueError("max_frames must be >= 1")
+        ts = tuple(torch.zeros((self.n_channels,) + tuple(int(max_frames) if d is None else d for d in dims),
+                               dtype=getattr(torch, dtype), device=cuda(self.device)) for dtype, *dims in tensors)
+        check(entry(self._ctx, int(on), *[ptr(t) for t in ts], int(max_frames)))
+        keep = ts[0] if len(ts) == 1 else ts
+        setattr(self, attr, keep)  # keep alive
+        return keep
+
+    def _first_frames(self, t, n_frames, width):
+        """the part of a result tensor [n_channels, max_frames, width] a call of n_frames frames filled, as [n_channels, n_frames, width]"""
+        return t.view(-1)[:self.n_channels * int(n_frames) * width].view(self.n_channels, int(n_frames), width)
 
     # -- the hot path ----------------------------------------------------------------------
     def ProcessIQData(self, float_buffer_L, float_buffer_R, out=None):
@@ -572,95 +466,74 @@ class RxChain:
         current torch stream without synchronising and return a tensor; numpy arrays go
         through the host-pointer entry point and return a numpy array.
         """
-        if isinstance(float_buffer_L, np.ndarray):
-            I = np.ascontiguousarray(float_buffer_L, dtype=np.float32)
-            Q = np.ascontiguousarray(float_buffer_R, dtype=np.float32)
-            nfr = self._check_shape(I.shape, Q.shape)
-            audio = np.empty(self._out_shape(nfr), I.dtype) if out is None else self._check_out_numpy(out, I, nfr)
-            fp = C.POINTER(C.c_float)
-            check(self._lib.t41rx_process_host(self._ctx, I.ctypes.data_as(fp), Q.ctypes.data_as(fp),
-                                               audio.ctypes.data_as(fp), nfr))
-            return audio
-        import torch
-        I, Q = float_buffer_L, float_buffer_R
-        if not (I.is_cuda and Q.is_cuda and I.dtype == torch.float32 and Q.dtype == torch.float32
-                and I.is_contiguous() and Q.is_contiguous()):
-            raise ValueError("I/Q must be contiguous float32 CUDA tensors")
-        if I.device.index != self.device or Q.device.index != self.device:
-            raise ValueError("I/Q live on another device than this RxChain")
-        nfr = self._check_shape(tuple(I.shape), tuple(Q.shape))
-        audio = self._new_out_torch(I, nfr) if out is None else self._check_out_torch(out, I, nfr)
-        stream = torch.cuda.current_stream(I.device).cuda_stream
-        check(self._lib.t41rx_process_device(self._ctx, I.data_ptr(), Q.data_ptr(), audio.data_ptr(), nfr,
-                                             C.c_void_p(stream)))
-        return audio
+        return self._process(float_buffer_L, float_buffer_R, out, "float32", F32P, self._lib.t41rx_process_host, self._lib.t41rx_process_device,
+                             "I/Q must be contiguous float32 CUDA tensors", "I/Q live on another device than this RxChain")
 
     def ProcessIQData_q15(self, Q_in_L, Q_in_R, out=None):
         """The same on the firmware's wire format (Process.cpp:102-111, 936-937): int16 (q15) blocks
         of the L and R record queues in -- I is taken from the R queue, Q from the L queue, as the
         firmware does -- and the q15 samples handed to Q_out_L.play() out.
         torch CUDA int16 tensors or numpy int16 arrays, [n_channels, n_frames*frame_len]."""
-        if isinstance(Q_in_L, np.ndarray):
-            a = np.ascontiguousarray(Q_in_L, dtype=np.int16)
-            b = np.ascontiguousarray(Q_in_R, dtype=np.int16)
+        return self._process(Q_in_L, Q_in_R, out, "int16", C.c_void_p, self._lib.t41rx_process_host_q15, self._lib.t41rx_process_device_q15,
+                             "Q_in_L/Q_in_R must be contiguous int16 CUDA tensors", "the queues live on another device than this RxChain")
+
+    def _process(self, a, b, out, dtype, ptype, host_entry, device_entry, not_cuda, elsewhere):
+        """ProcessIQData() and ProcessIQData_q15(): numpy arrays are converted to dtype and go to the host entry, tensors
+        must be of dtype already and go to the device entry with the current stream; the messages are the caller's"""
+        if isinstance(a, np.ndarray):
+            a = np.ascontiguousarray(a, dtype=dtype)
+            b = np.ascontiguousarray(b, dtype=dtype)
             nfr = self._check_shape(a.shape, b.shape)
             audio = np.empty(self._out_shape(nfr), a.dtype) if out is None else self._check_out_numpy(out, a, nfr)
-            check(self._lib.t41rx_process_host_q15(self._ctx, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p),
-                                                   audio.ctypes.data_as(C.c_void_p), nfr))
+            check(host_entry(self._ctx, ptr(a, ptype), ptr(b, ptype), ptr(audio, ptype), nfr))
             return audio
         import torch
-        a, b = Q_in_L, Q_in_R
-        if not (a.is_cuda and b.is_cuda and a.dtype == torch.int16 and b.dtype == torch.int16
-                and a.is_contiguous() and b.is_contiguous()):
-            raise ValueError("Q_in_L/Q_in_R must be contiguous int16 CUDA tensors")
+        want = getattr(torch, dtype)
+        if not (cuda_tensor(a, want) and cuda_tensor(b, want)):
+            raise ValueError(not_cuda)
         if a.device.index != self.device or b.device.index != self.device:
-            raise ValueError("the queues live on another device than this RxChain")
+            raise ValueError(elsewhere)
         nfr = self._check_shape(tuple(a.shape), tuple(b.shape))
-        audio = self._new_out_torch(a, nfr) if out is None else self._check_out_torch(out, a, nfr)
-        stream = torch.cuda.current_stream(a.device).cuda_stream
-        check(self._lib.t41rx_process_device_q15(self._ctx, a.data_ptr(), b.data_ptr(), audio.data_ptr(), nfr,
-                                                 C.c_void_p(stream)))
+        audio = torch.empty(self._out_shape(nfr), dtype=want, device=a.device) if out is None else self._check_out_torch(out, a, nfr)
+        check(device_entry(self._ctx, a.data_ptr(), b.data_ptr(), audio.data_ptr(), nfr, _args.stream_of(self.device)))
         return audio
 
-    def _side_tensor(self, t, per_frame, what):
-        """validate a side-output tensor; returns (pointer, frames it has room for)"""
-        if t is None:
-            return None, None
-        import torch
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device.index == self.device):
-            raise ValueError("%s must be a contiguous float32 CUDA tensor on device %d" % (what, self.device))
-        frames = t.numel() // (self.n_channels * per_frame)
-        if frames < 1:
-            raise ValueError("%s holds less than one frame (%d floats per channel and frame)" % (what, per_frame))
-        return C.c_void_p(t.data_ptr()), frames
+    def _side_tensors(self, *sides):
+        """validate side-output tensors, each (tensor or None, floats per channel and frame, name); returns their pointers
+        and the frames the smallest of them has room for (0 if none is given)"""
+        ptrs, frames = [], []
+        for t, per_frame, what in sides:
+            if t is not None:
+                import torch
+                if not cuda_tensor(t, torch.float32, self.device):
+                    raise ValueError("%s must be a contiguous float32 CUDA tensor on device %d" % (what, self.device))
+                frames.append(t.numel() // (self.n_channels * per_frame))
+                if frames[-1] < 1:
+                    raise ValueError("%s holds less than one frame (%d floats per channel and frame)" % (what, per_frame))
+            ptrs.append(ptr(t))
+        return ptrs, min(frames) if frames else 0
 
     def set_debug_taps(self, post_nco=None, dec=None, demod=None):
         """stage taps (torch CUDA float32 tensors or None): post_nco [n_channels, n_frames*2*frame_len],
         dec [n_channels, n_frames*fft_length], demod [n_channels, n_frames*fft_length/2].  Calls with
         more frames than the smallest of them holds are refused."""
         N = self.params.fft_length
-        got = [self._side_tensor(post_nco, 2 * self.frame_len, "post_nco"), self._side_tensor(dec, N, "dec"),
-               self._side_tensor(demod, N // 2, "demod")]
-        frames = [f for _, f in got if f is not None]
-        check(self._lib.t41rx_set_debug_taps(self._ctx, got[0][0], got[1][0], got[2][0], min(frames) if frames else 0))
+        ptrs, frames = self._side_tensors((post_nco, 2 * self.frame_len, "post_nco"), (dec, N, "dec"), (demod, N // 2, "demod"))
+        check(self._lib.t41rx_set_debug_taps(self._ctx, *ptrs, frames))
         self._taps = (post_nco, dec, demod)  # keep alive
 
     def set_audio_spectrum(self, spect=None, maxima=None):
         """the display by-product of the path (Process.cpp:550-570): torch CUDA float32 tensors
         [n_channels, n_frames, 1024] and [n_channels, n_frames, 3], or None/None to switch it off"""
-        ps, fs = self._side_tensor(spect, 1024, "spect")
-        pm, fm = self._side_tensor(maxima, 3, "maxima")
-        frames = [f for f in (fs, fm) if f is not None]
-        check(self._lib.t41rx_set_audio_spectrum(self._ctx, ps, pm, min(frames) if frames else 0))
+        ptrs, frames = self._side_tensors((spect, 1024, "spect"), (maxima, 3, "maxima"))
+        check(self._lib.t41rx_set_audio_spectrum(self._ctx, *ptrs, frames))
         self._spect = (spect, maxima)  # keep alive
 
     def set_display_spectrum(self, spec=None, spec_old=None, spectrumZoom=1):
         """the display FFT (CalcZoom1Magn / ZoomFFTExe, FFT.cpp:67-251): torch CUDA float32 tensors
         [n_channels, n_frames, 512] for FFT_spec and FFT_spec_old, or None/None to switch it off"""
-        ps, fs = self._side_tensor(spec, 512, "spec")
-        po, fo = self._side_tensor(spec_old, 512, "spec_old")
-        frames = [f for f in (fs, fo) if f is not None]
-        check(self._lib.t41rx_set_display_spectrum(self._ctx, ps, po, int(spectrumZoom), min(frames) if frames else 0))
+        ptrs, frames = self._side_tensors((spec, 512, "spec"), (spec_old, 512, "spec_old"))
+        check(self._lib.t41rx_set_display_spectrum(self._ctx, *ptrs, int(spectrumZoom), frames))
         self._disp = (spec, spec_old)  # keep alive
 
     # -- the panadapter stage ------------------------------------------------------------------
@@ -670,11 +543,8 @@ class RxChain:
     def set_panadapter_tables(self, gradient):
         """The waterfall's colour words gradient[] (Display.cpp:148-161; t41rx_set_panadapter_tables): 117 uint16.  The
         library has no table of its own."""
-        g = np.asarray(gradient)
-        if g.ndim != 1 or not np.issubdtype(g.dtype, np.integer) or (g.size and (g.min() < 0 or g.max() > 0xFFFF)):
-            raise ValueError("gradient must be a 1-d array of uint16 colour words, got %r %s" % (g.shape, g.dtype))
-        g = np.ascontiguousarray(g, dtype=np.uint16)
-        check(self._lib.t41rx_set_panadapter_tables(self._ctx, g.ctypes.data_as(C.POINTER(C.c_uint16)), int(g.size)))
+        g = int_table(gradient, np.uint16, None, "gradient must be a 1-d array of uint16 colour words, got %r %s")
+        check(self._lib.t41rx_set_panadapter_tables(self._ctx, ptr(g, U16P), int(g.size)))
 
     def set_panadapter(self, on=True, spectrumZoom=0, currentScale=1, pixel_offset=0, spectrumNoiseFloor=panadapter.SPECTRUM_NOISE_FLOOR,
                        update_period=panadapter.UPDATE_PERIOD, update_phase=0, max_rows=1, outputs=None):
@@ -703,11 +573,11 @@ class RxChain:
             shape = (self.n_channels, int(max_rows), width)
             t = outputs[name] if isinstance(outputs, dict) else None
             if t is None:  # (uint16: allocated as int16 and viewed, the type torch fills on every build)
-                t = torch.zeros(shape, dtype=torch.int16 if dt == torch.uint16 else dt, device="cuda:%d" % self.device).view(dt)
-            elif not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape and t.device.index == self.device):
+                t = torch.zeros(shape, dtype=torch.int16 if dt == torch.uint16 else dt, device=cuda(self.device)).view(dt)
+            elif not (cuda_tensor(t, dt, self.device) and tuple(t.shape) == shape):
                 raise ValueError("%s must be a contiguous %s CUDA tensor of shape %r on device %d" % (name, dt, shape, self.device))
             bufs[name] = t
-        out = _lib.PanadapterOut(**{name: C.c_void_p(t.data_ptr()) for name, t in bufs.items()})
+        out = _lib.PanadapterOut(**{name: ptr(t) for name, t in bufs.items()})
         self._pan = None
         check(self._lib.t41rx_set_panadapter(self._ctx, 1, int(spectrumZoom), int(currentScale), int(pixel_offset), int(spectrumNoiseFloor),
                                              int(update_period), int(update_phase), C.byref(out), int(max_rows)))
@@ -719,24 +589,16 @@ class RxChain:
         and `attenuator` (t41rx_set_panadapter_levels).  From the next process call."""
         nf = gc = None
         if noise_floor is not None:
-            nf = np.asarray(noise_floor)
-            if nf.shape != (self.n_channels,) or not np.issubdtype(nf.dtype, np.integer) or (nf.min() < -2**31 or nf.max() >= 2**31):
-                raise ValueError("noise_floor must be n_channels = %d int32 values, got %r %s" % (self.n_channels, nf.shape, nf.dtype))
-            nf = np.ascontiguousarray(nf, dtype=np.int32)
+            nf = int_table(noise_floor, np.int32, (self.n_channels,), "noise_floor must be n_channels = %d int32 values, got %%r %%s" % self.n_channels)
         if gain_correction is not None:
-            gc = np.ascontiguousarray(np.asarray(gain_correction, dtype=np.float32))
-            if gc.shape != (self.n_channels,):
-                raise ValueError("gain_correction must be n_channels = %d floats, got %r" % (self.n_channels, gc.shape))
-        check(self._lib.t41rx_set_panadapter_levels(self._ctx, None if nf is None else nf.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                    None if gc is None else gc.ctypes.data_as(C.POINTER(C.c_float)), int(attenuator)))
+            gc = table(gain_correction, np.float32, (self.n_channels,), "gain_correction must be n_channels = %d floats, got %%r" % self.n_channels)
+        check(self._lib.t41rx_set_panadapter_levels(self._ctx, ptr(nf, I32P), ptr(gc, F32P), int(attenuator)))
 
     def panadapter_status(self):
         """(on, frame_counter, rows_written, first_row_frame): the stage's switch, its frame count behind the last process
         call, the rows that call wrote and the frame count of its row 0 (-1: none)"""
         n, k, f = C.c_int64(), C.c_int32(), C.c_int64()
-        v = self._lib.t41rx_get_panadapter(self._ctx, C.byref(n), C.byref(k), C.byref(f))
-        if v < 0:
-            check(v)
+        v = value(self._lib.t41rx_get_panadapter(self._ctx, C.byref(n), C.byref(k), C.byref(f)))
         return bool(v), n.value, k.value, f.value
 
     def set_panadapter_counter(self, n):
@@ -744,7 +606,7 @@ class RxChain:
         check(self._lib.t41rx_set_panadapter_counter(self._ctx, int(n)))
 
     # -- IQ calibration ----------------------------------------------------------------------
-    CAL_BINS ={("rx", DEMOD_LSB): (310, 460), ("rx", DEMOD_USB): (65, 192),   # cal_bins[], Process2.cpp:429-444
+    CAL_BINS = {("rx", DEMOD_LSB): (310, 460), ("rx", DEMOD_USB): (65, 192),   # cal_bins[], Process2.cpp:429-444
                 ("tx", DEMOD_LSB): (240, 305), ("tx", DEMOD_USB): (209, 273)}
 
     def set_calibration(self, on=True, spectrumZoom=0, currentScale=1, pixel_offset=0, bin0=310, bin1=460, capture_bins=10):
@@ -757,16 +619,7 @@ class RxChain:
     def set_cal_corrections(self, amp=None, phase=None):
         """one (IQAmpCorrectionFactor, IQPhaseCorrectionFactor) candidate per channel for the calibration calls
         (t41rx_set_cal_corrections): two arrays of n_channels floats, or None, None for the params' factors"""
-        if amp is None and phase is None:
-            check(self._lib.t41rx_set_cal_corrections(self._ctx, None, None))
-            return
-        if amp is None or phase is None:
-            raise ValueError("amp and phase must both be given or both be None")
-        a = np.ascontiguousarray(np.asarray(amp, dtype=np.float32))
-        p = np.ascontiguousarray(np.asarray(phase, dtype=np.float32))
-        if a.shape != (self.n_channels,) or p.shape != (self.n_channels,):
-            raise ValueError("corrections must be %d floats each, got %r and %r" % (self.n_channels, a.shape, p.shape))
-        check(self._lib.t41rx_set_cal_corrections(self._ctx, a.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p)))
+        _args.set_cal_corrections(self, self._lib.t41rx_set_cal_corrections, amp, phase)
 
     def ProcessIQData2_rx(self, I, Q, update=None, shared_input=False, pixel=False, spec=False):
         """The receive half of ProcessIQData2() with PlotCalSpectrum()'s measurement, n_frames frames per channel.
@@ -784,8 +637,7 @@ class RxChain:
         else:
             import torch
             q15 = I.dtype == torch.int16
-            if not (I.is_cuda and Q.is_cuda and I.dtype == Q.dtype and I.dtype in (torch.int16, torch.float32)
-                    and I.is_contiguous() and Q.is_contiguous() and I.device.index == self.device and Q.device.index == self.device):
+            if not (cuda_tensor(I, (torch.int16, torch.float32), self.device) and cuda_tensor(Q, I.dtype, self.device)):
                 raise ValueError("I/Q must be contiguous float32 or int16 CUDA tensors on device %d" % self.device)
         si, sq = tuple(I.shape), tuple(Q.shape)
         rows = 1 if shared_input else self.n_channels
@@ -799,41 +651,33 @@ class RxChain:
         def side(buf, dtype_np, what):
             if buf is False or buf is None:
                 return None
+            tdtype = None if host else getattr(torch, np.dtype(dtype_np).name)
             if buf is True:
-                if host:
-                    return np.zeros(shape + (512,), dtype_np)
-                return torch.zeros(shape + (512,), dtype=torch.int16 if dtype_np == np.int16 else torch.float32, device=I.device)
+                return np.zeros(shape + (512,), dtype_np) if host else torch.zeros(shape + (512,), dtype=tdtype, device=I.device)
             ok = tuple(buf.shape) == shape + (512,) and (
                 (isinstance(buf, np.ndarray) and buf.dtype == dtype_np and buf.flags["C_CONTIGUOUS"] and buf.flags["WRITEABLE"]) if host
-                else (buf.is_cuda and buf.is_contiguous() and buf.device == I.device
-                      and buf.dtype == (torch.int16 if dtype_np == np.int16 else torch.float32)))
+                else cuda_tensor(buf, tdtype, self.device))
             if not ok:
                 raise ValueError("%s must be a contiguous %s buffer of shape %r next to I/Q" % (what, np.dtype(dtype_np).name, shape + (512,)))
             return buf
 
         pixel, spec = side(pixel, np.int16, "pixel"), side(spec, np.float32, "spec")
-        if host:
-            u = None
-            if update is not None:
-                u = np.ascontiguousarray(np.asarray(update) != 0, dtype=np.uint8)
-                if u.shape != (nfr,):
-                    raise ValueError("update must hold n_frames=%d flags, got %r" % (nfr, u.shape))
-            res = np.zeros(shape + (3,), np.float32)
-            p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)  # noqa: E731
-            fn = self._lib.t41rx_calibrate_host_q15 if q15 else self._lib.t41rx_calibrate_host
-            check(fn(self._ctx, p(I), p(Q), int(bool(shared_input)), p(u), p(res), p(pixel), p(spec), nfr))
-            return res, pixel, spec
         u = None
-        if update is not None:
+        if update is not None and host:
+            u = np.ascontiguousarray(np.asarray(update) != 0, dtype=np.uint8)
+            if u.shape != (nfr,):
+                raise ValueError("update must hold n_frames=%d flags, got %r" % (nfr, u.shape))
+        elif update is not None:
             u = update if isinstance(update, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(update) != 0, dtype=np.uint8)).to(I.device)
-            if not (u.is_cuda and u.dtype == torch.uint8 and u.is_contiguous() and tuple(u.shape) == (nfr,)):
+            if not (cuda_tensor(u, torch.uint8) and tuple(u.shape) == (nfr,)):
                 raise ValueError("update must hold n_frames=%d uint8 flags" % nfr)
-        res = torch.zeros(shape + (3,), dtype=torch.float32, device=I.device)
-        p = lambda x: None if x is None else x.data_ptr()  # noqa: E731
-        stream = torch.cuda.current_stream(I.device).cuda_stream
-        fn = self._lib.t41rx_calibrate_device_q15 if q15 else self._lib.t41rx_calibrate_device
-        check(fn(self._ctx, p(I), p(Q), int(bool(shared_input)), p(u), p(res), p(pixel), p(spec), nfr, C.c_void_p(stream)))
-        self._cal_keep = (I, Q, u)  # alive until the next call: the launch is asynchronous
+        res = np.zeros(shape + (3,), np.float32) if host else torch.zeros(shape + (3,), dtype=torch.float32, device=I.device)
+        lib = self._lib
+        run(host, lib.t41rx_calibrate_host_q15 if q15 else lib.t41rx_calibrate_host,
+            lib.t41rx_calibrate_device_q15 if q15 else lib.t41rx_calibrate_device, self.device,
+            self._ctx, ptr(I), ptr(Q), int(bool(shared_input)), ptr(u), ptr(res), ptr(pixel), ptr(spec), nfr)
+        if not host:
+            self._cal_keep = (I, Q, u)  # alive until the next call: the launch is asynchronous
         return res, pixel, spec
 
     def _out_shape(self, nfr):
@@ -842,17 +686,12 @@ class RxChain:
             return (nfr, self.n_channels, self.frame_len)
         return (self.n_channels, nfr * self.frame_len)
 
-    def _new_out_torch(self, like, nfr):
-        import torch
-        return torch.empty(self._out_shape(nfr), dtype=like.dtype, device=like.device)
-
     def _rows_text(self):
         return "(n_channels=%d, n_streams=%d)" % (self.n_channels, self.n_streams)
 
     def _check_out_torch(self, out, like, nfr):
         shape = self._out_shape(nfr)
-        if not (out.is_cuda and out.dtype == like.dtype and out.is_contiguous() and tuple(out.shape) == shape
-                and out.device == like.device):
+        if not (cuda_tensor(out, like.dtype) and tuple(out.shape) == shape and out.device == like.device):
             raise ValueError("out must be a contiguous %s CUDA tensor of shape %r on %s %s"
                              % (like.dtype, shape, like.device, self._rows_text()))
         return out
@@ -878,12 +717,6 @@ class RxChain:
         return si[1] // self.frame_len
 
     def close(self):
-        if getattr(self, "_ctx", None) is not None and self._ctx:
-            self._lib.t41rx_destroy(self._ctx)
-            self._ctx = C.c_void_p()
+        _args.close(self, "t41rx_destroy")
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    __del__ = _args.finalize

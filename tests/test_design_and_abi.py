@@ -227,3 +227,44 @@ def test_no_source_includes_a_kernel_file():
     listed = set(re.findall(r"\b(\w+)\.o\b", open(os.path.join(csrc, "Makefile")).read()))
     hips = {os.path.splitext(n)[0] for n in os.listdir(csrc) if n.endswith(".hip")}
     assert hips and hips <= listed, sorted(hips - listed)
+
+
+def _prototypes(header):
+    """{name: (return type, [parameter types])} of every T41RX_API declaration of a header, names and comments dropped"""
+    hdr = open(os.path.join(ROOT, "include", header)).read()
+    hdr = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S))
+    out = {}
+    for ret, name, params in re.findall(r"\bT41RX_API\s+([\w \*]+?)\s*\b(t41[rt]x_\w+)\s*\(([^;{]*)\)\s*;", hdr):
+        params = [re.sub(r"\s+", " ", p).strip() for p in params.split(",")]
+        if params in (["void"], [""]):
+            params = []
+        out[name] = (re.sub(r"\s+", " ", ret).strip(), [re.match(r"(.*?)\w+$", p).group(1).strip() for p in params])
+    return out
+
+
+@pytest.mark.parametrize("header,table", [("t41rx.h", "SYMBOLS"), ("t41tx.h", "TX_SYMBOLS")])
+def test_binding_tables_match_the_headers(T, header, table):
+    """Every entry point of both headers is in its ctypes table (_lib.SYMBOLS receive, _lib.TX_SYMBOLS transmit) and
+    nothing else is, with the header's return type, its number of parameters, every scalar parameter's exact type and a
+    pointer type for every pointer; load() binds both tables to the one handle.  A wrong arity would not fail a call:
+    it would corrupt it."""
+    from t41_sdr_amd import _lib, tx
+    protos, mirror = _prototypes(header), getattr(_lib, table)
+    assert len(protos) >= 20 and set(protos) == _declared(header)  # the parser saw every declaration
+    assert set(mirror) == set(protos), sorted(set(mirror) ^ set(protos))
+    results = {"int": C.c_int, "size_t": C.c_size_t, "const char *": C.c_char_p, "void": None}
+    scalars = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "size_t": C.c_size_t, "float": C.c_float}
+    lib = T.load()
+    for name, (ret, params) in protos.items():
+        res, args = mirror[name]
+        assert res is results[ret], (name, ret, res)
+        assert len(args) == len(params), (name, params, args)
+        for want, got in zip(params, args):
+            if "*" in want:
+                assert got is C.c_void_p or issubclass(got, C._Pointer), (name, want, got)
+            else:
+                assert got is scalars[want], (name, want, got)
+        fn = getattr(lib, name)  # bound by load(), whichever chain is used first
+        assert fn.restype is res and list(fn.argtypes) == list(args), name
+    assert tx._load() is lib and tx.TX_SYMBOLS is _lib.TX_SYMBOLS and tx.TxParams is _lib.TxParams is T.TxParams
+    assert not set(_lib.SYMBOLS) & set(_lib.TX_SYMBOLS)
