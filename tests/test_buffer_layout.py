@@ -9,17 +9,9 @@ import pytest
 
 import oracle_lib as O
 import siggen
+from rx_harness import T, from_time_major, to_q15, to_time_major  # noqa: F401  (T: the loaded package, a fixture)
 
 L = 2048
-
-
-@pytest.fixture(scope="module")
-def T(built):
-    import torch
-    import t41_sdr_amd
-    assert torch.cuda.is_available()
-    t41_sdr_amd.load()
-    return t41_sdr_amd
 
 
 def test_layout_symbols_and_constants(built):
@@ -83,8 +75,7 @@ def test_time_major_q15_and_host_entry_points(T):
     nch, nfr = 19, 5
     nco = siggen.nco_grid(nch, seed=4)
     I, Q = siggen.make_iq(nch, nfr * L, nco, mode=0, seed=22)
-    qi = np.clip(np.round(I * 32768.0), -32768, 32767).astype(np.int16)
-    qq = np.clip(np.round(Q * 32768.0), -32768, 32767).astype(np.int16)
+    qi, qq = to_q15(I), to_q15(Q)
     a = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
     b = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
     b.set_buffer_layout("time")
@@ -98,7 +89,7 @@ def test_time_major_q15_and_host_entry_points(T):
     d = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
     d.set_buffer_layout("time")
     oc = c.ProcessIQData(I, Q)
-    od = d.ProcessIQData(np.ascontiguousarray(I.reshape(nch, nfr, L).transpose(1, 0, 2)), np.ascontiguousarray(Q.reshape(nch, nfr, L).transpose(1, 0, 2)))
+    od = d.ProcessIQData(to_time_major(I, nch, nfr, L), to_time_major(Q, nch, nfr, L))
     assert np.array_equal(oc.reshape(nch, nfr, L).transpose(1, 0, 2), od)
 
 
@@ -114,8 +105,7 @@ def test_time_major_side_outputs_and_taps(T, fmt):
     nco = siggen.nco_grid(nch, seed=6)
     I, Q = siggen.make_iq(nch, nfr * L, nco, mode=0, seed=24)
     if fmt == "q15":
-        I = np.clip(np.round(I * 32768.0), -32768, 32767).astype(np.int16)
-        Q = np.clip(np.round(Q * 32768.0), -32768, 32767).astype(np.int16)
+        I, Q = to_q15(I), to_q15(Q)
     outs = {}
     for layout in ("channel", "time"):
         rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
@@ -150,9 +140,8 @@ def test_time_major_against_the_oracle(T):
     I, Q = siggen.make_iq(nch, nfr * L, nco, mode=0, seed=23)
     rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
     rx.set_buffer_layout("time")
-    tI = torch.from_numpy(np.ascontiguousarray(I.reshape(nch, nfr, L).transpose(1, 0, 2))).cuda()
-    tQ = torch.from_numpy(np.ascontiguousarray(Q.reshape(nch, nfr, L).transpose(1, 0, 2))).cuda()
-    got = rx.ProcessIQData(tI, tQ).cpu().numpy().transpose(1, 0, 2).reshape(nch, nfr * L)
+    tI, tQ = torch.from_numpy(to_time_major(I, nch, nfr, L)).cuda(), torch.from_numpy(to_time_major(Q, nch, nfr, L)).cuda()
+    got = from_time_major(rx.ProcessIQData(tI, tQ).cpu().numpy(), nch, nfr, L)
     ref = O.OracleBatch(O.default_params(**kw), nco).process(I, Q)
     err = siggen.block_rel_err(got, ref, L)
     assert err.max() <= 1e-5, err.max()

@@ -19,9 +19,9 @@ import pytest
 import cw_decode_model as DM
 import cw_model as CWM
 import siggen
+from rx_harness import assert_entry_points, one_call, refused
 
 L = 2048
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CW = dict(mode=0, xmtMode=1)  # USB, xmtMode = CW_MODE
 NEW = ("t41rx_set_cw_decode_tree", "t41rx_set_cw_decoder", "t41rx_get_cw_decoder", "t41rx_set_cw_clock",
        "t41rx_reset_cw_histograms")
@@ -68,15 +68,9 @@ def test_model_ignores_one_frame_blips():
 
 def test_entry_points_declared_exported_and_bound(built):
     import t41_sdr_amd._lib as lib
-    hdr = open(os.path.join(ROOT, "include", "t41rx.h")).read()
-    m = open(os.path.join(ROOT, "t41_sdr_amd", "csrc", "exports.map")).read()
-    for name in NEW:
-        assert re.search(r"T41RX_API\s+int\s+%s\s*\(" % name, hdr) and (name + ";") in m and name in lib.SYMBOLS, name
-        assert hasattr(C.CDLL(lib.LIB_PATH), name)
-    import t41_sdr_amd as T
-    for meth in ("set_cw_decode_tree", "set_cw_decoder", "cw_decoder", "cw_text", "set_cw_clock", "reset_cw_histograms"):
-        assert hasattr(T.RxChain, meth)
-    assert "T41RX_ABI_VERSION 5" in hdr and lib.load().t41rx_abi_version() == 5
+    assert_entry_points(NEW, ("set_cw_decode_tree", "set_cw_decoder", "cw_decoder", "cw_text", "set_cw_clock", "reset_cw_histograms"),
+                        abi_version=5, pattern=r"T41RX_API\s+int\s+%s\s*\(")
+    assert lib.load().t41rx_abi_version() == 5
 
 
 def test_tree_fixture_is_the_firmware_literal():
@@ -220,26 +214,18 @@ def make_rx(nch, nco, frames, dec=1, det=1, kw=CW, clock=CLOCK):
 
 def run(rx, nco, keys, edges, seed, how="f32", keep_audio=False):
     """the stream in calls of frames edges[k] .. edges[k + 1]: (GPU key bits, d_cw, d_text, audio or None)"""
-    import torch
-    nch = keys.shape[0]
     dets, texts, auds = [], [], []
     for a, b in zip(edges[:-1], edges[1:]):
         I, Q = call_iq(nco, keys[:, a:b], a, seed)
-        if how == "time":
-            I, Q = [v.reshape(nch, b - a, L).transpose(1, 0, 2).copy() for v in (I, Q)]
-        if how == "q15":
-            Iq, Qq = [torch.from_numpy(np.clip(np.round(v * 32768.0), -32768, 32767).astype(np.int16)).cuda() for v in (I, Q)]
-            o = rx.ProcessIQData_q15(Qq, Iq)
-        else:
-            o = rx.ProcessIQData(torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda())
+        o, _ = one_call(rx, I, Q, layout="time" if how == "time" else "channel", q15_scale=1.0 if how == "q15" else None)
         if keep_audio:
-            auds.append(o.cpu().numpy())
+            auds.append(o)
         dets.append(rx.cw_results(b - a).cpu().numpy().copy())
         if rx.cw_decoder:
             texts.append(rx.cw_text(b - a).cpu().numpy().copy())
     det = np.concatenate(dets, 1)
     return ((det[:, :, 3] > np.float32(50)).astype(np.int32), det, np.concatenate(texts, 1) if texts else None,
-            np.concatenate(auds, 0 if how == "time" else 1) if keep_audio else None)
+            np.concatenate(auds, 1) if keep_audio else None)
 
 
 def dec_section(ck, nch):
@@ -412,13 +398,6 @@ def test_gpu_gating_and_refusals(built):
     import t41_sdr_amd._lib as lib
     L_ = lib.load()
     nch, nfr, words, keys, nco = small_case()
-
-    def refused(fn, status, *parts):
-        with pytest.raises(T.T41RxError) as ei:
-            fn()
-        assert ei.value.status == status, ei.value
-        for p in parts:
-            assert p in str(ei.value), ei.value
 
     # gating: another xmtMode, or the detector off: d_text untouched, the section unchanged
     rx = make_rx(nch, nco, nfr)

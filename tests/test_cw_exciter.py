@@ -16,6 +16,7 @@ import pytest
 import cw_tx_model as W
 import oracle_lib as O
 import tx_model as M
+from tx_harness import cat, mic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F, K = 2048, 16
@@ -23,23 +24,6 @@ USB, LSB, AM = O.DEMOD_USB, O.DEMOD_LSB, O.DEMOD_AM
 OK, ERR_ARG = 0, -1
 CASES = {"usb": (USB, 1.0, 0.0), "lsb-corr": (LSB, 0.97, -0.02), "usb-corr": (USB, 1.03, 0.015), "am": (AM, 1.0, 0.3)}
 NEW_SYMBOLS = ("t41tx_set_cw_tone", "t41tx_process_cw_device_q15", "t41tx_process_cw_host_q15")
-
-
-def mic(nch, nfr, seed=1, level=0.5):
-    """speech-band multi-tone + noise at 192 kS/s as q15 (test_tx_exciter.py's recipe)"""
-    rng = np.random.default_rng(seed)
-    n = np.arange(nfr * F)
-    x = np.zeros((nch, nfr * F))
-    for c in range(nch):
-        for _ in range(4):
-            x[c] += rng.uniform(0.05, 0.3) * np.sin(2 * np.pi * rng.uniform(300, 2800) / 192000.0 * n + rng.uniform(0, 6.28))
-        x[c] += 0.01 * rng.standard_normal(n.size)
-    x *= level / np.abs(x).max()
-    return np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16)
-
-
-def cat(parts):
-    return tuple(np.concatenate([p[i] for p in parts], axis=1) for i in (0, 1))
 
 
 def assert_same(got, ref, what=""):

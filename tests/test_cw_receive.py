@@ -8,23 +8,19 @@ The library has no copy; the caller loads them (t41rx_set_cw_tables).
 CPU: the fixture, the f32 restatement (tests/cw_model.py) against float64 models, the detector's exact-tone and stale-R
 properties, why the filter kernel must not contract, the entry points.  GPU (-m gpu): USB with xmtMode = CW; the
 expected audio is the HIP path's own `demod` tap through the restatement and the oracle's interpolators
-(test_receive_eq.interp), the expected detector output is the tap through the restatement; comparisons are
+(stage_reference.interp), the expected detector output is the tap through the restatement; comparisons are
 np.array_equal.
 """
-import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 
 import cw_model as M
 import eq_model as EQ
 import siggen
-from test_receive_eq import interp
+from rx_harness import assert_entry_points, calls, refused, to_q15
+from stage_reference import interp
 
 L, D = 2048, 256
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CW = dict(mode=0, xmtMode=1)  # USB, xmtMode = CW_MODE
 NEW = ("t41rx_set_cw_tables", "t41rx_set_cw_filter", "t41rx_get_cw_filter", "t41rx_set_cw_detector", "t41rx_get_cw_detector")
 
@@ -122,16 +118,8 @@ def test_contraction_changes_the_filter_within_a_few_blocks():
 
 
 def test_entry_points_declared_exported_and_bound(built):
-    import t41_sdr_amd._lib as lib
-    hdr = open(os.path.join(ROOT, "include", "t41rx.h")).read()
-    m = open(os.path.join(ROOT, "t41_sdr_amd", "csrc", "exports.map")).read()
-    for name in NEW:
-        assert re.search(r"T41RX_API\s+int\s+%s\s*\(" % name, hdr) and (name + ";") in m and name in lib.SYMBOLS, name
-        assert hasattr(C.CDLL(lib.LIB_PATH), name)
-    import t41_sdr_amd as T
-    for meth in ("set_cw_tables", "set_cw_filter", "cw_filter", "set_cw_detector", "cw_detector"):
-        assert hasattr(T.RxChain, meth)
-    assert "T41RX_ABI_VERSION 5" in hdr
+    assert_entry_points(NEW, ("set_cw_tables", "set_cw_filter", "cw_filter", "set_cw_detector", "cw_detector"), abi_version=5,
+                        pattern=r"T41RX_API\s+int\s+%s\s*\(")
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------
@@ -170,31 +158,18 @@ def make_rx(nch, nco, kw=CW, index=5, det=0, frames=8, tables=True, eq=0, nb=0):
     return rx
 
 
-def run(rx, I, Q, edges, q15=False, layout="channel"):
-    """the stream in calls of edges[k] .. edges[k + 1] frames: (audio, demod tap, detector results [nch][nfr][4])"""
-    import torch
+def run(rx, I, Q, edges, layout="channel"):
+    """the stream in calls of edges[k] .. edges[k + 1] frames: (audio, demod tap, detector results [nch][nfr][4]); int16
+    rows go through the q15 entry point"""
     nch = I.shape[0]
-    outs, taps, dets = [], [], []
     if layout == "time":
         rx.set_buffer_layout("time")
-    for a, b in zip(edges[:-1], edges[1:]):
-        t = torch.zeros(nch, (b - a) * D, device="cuda")
-        rx.set_debug_taps(demod=t)
-        i, q = np.ascontiguousarray(I[:, a * L:b * L]), np.ascontiguousarray(Q[:, a * L:b * L])
-        if layout == "time":
-            i = i.reshape(nch, b - a, L).transpose(1, 0, 2).copy()
-            q = q.reshape(nch, b - a, L).transpose(1, 0, 2).copy()
-        if q15:
-            o = rx.ProcessIQData_q15(torch.from_numpy(q).cuda(), torch.from_numpy(i).cuda())
-        else:
-            o = rx.ProcessIQData(torch.from_numpy(i).cuda(), torch.from_numpy(q).cuda())
-        o = o.cpu().numpy()
-        if layout == "time":
-            o = o.reshape(b - a, nch, L).transpose(1, 0, 2).reshape(nch, (b - a) * L)
-        outs.append(o)
-        taps.append(t.cpu().numpy())
-        dets.append(rx.cw_results(b - a).cpu().numpy().copy() if rx.cw_detector and rx.params.xmtMode == 1 else np.full((nch, b - a, 4), np.nan, np.float32))
-    return np.concatenate(outs, 1), np.concatenate(taps, 1), np.concatenate(dets, 1)
+
+    def det(rx, a, b):
+        return rx.cw_results(b - a).cpu().numpy().copy() if rx.cw_detector and rx.params.xmtMode == 1 else np.full((nch, b - a, 4), np.nan, np.float32)
+
+    out, tap, dets = calls(rx, I, Q, edges, after=det, layout=layout, tap_floats=D)
+    return out, tap, np.concatenate(dets, 1)
 
 
 def model(tap, index=5, detector=False, on=None, pre=None):
@@ -417,10 +392,10 @@ def test_gpu_formats(built, how):
         return
     # q15 in: the f32 path on the converted samples (x / 32768, arm_q15_to_float) is the same stream; q15 out: the
     # firmware's conversion of the f32 result (truncating, saturating arm_float_to_q15)
-    Iq, Qq = [np.clip(np.round(v * 32768.0 / 4), -32768, 32767).astype(np.int16) for v in (I, Q)]
+    Iq, Qq = to_q15(I, 1 / 4), to_q15(Q, 1 / 4)
     If, Qf = [(v.astype(np.float32) / np.float32(32768.0)) for v in (Iq, Qq)]
     whole, _, dwhole = run(make_rx(nch, nco, index=4, det=1), If, Qf, [0, nfr])
-    got, _, det = run(make_rx(nch, nco, index=4, det=1), Iq, Qq, [0, nfr], q15=True)
+    got, _, det = run(make_rx(nch, nco, index=4, det=1), Iq, Qq, [0, nfr])
     ref = np.clip(np.trunc(whole.astype(np.float64) * 32768.0), -32768, 32767).astype(np.int16)
     assert np.abs(ref).max() > 100
     assert np.array_equal(det, dwhole) and np.array_equal(got, ref)
@@ -434,13 +409,6 @@ def test_gpu_refusals(built):
     L_ = lib.load()
     nch = 3
     rx = T.RxChain(nch, T.default_params(**CW))
-
-    def refused(fn, status, *words):
-        with pytest.raises(T.T41RxError) as ei:
-            fn()
-        assert ei.value.status == status, ei.value
-        for w in words:
-            assert w in str(ei.value), ei.value
 
     assert rx.cw_filter == 5 and rx.cw_detector == 0  # the firmware's defaults
     refused(lambda: rx.set_cw_filter(6), lib.ERR_ARG, "CWFilterIndex")

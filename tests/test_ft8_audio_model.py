@@ -4,7 +4,6 @@ forms, its quirks, a whole slot through it and the decode model, the entry point
 The four transmissions of `CASES` (CQ K1ABC FN42 as continuous-phase 8-FSK at 12 kS/s, 1920 samples per symbol) run through
 the gulp form for all 1380 frames and through tests/ft8_decode_model.py; test_ft8_audio.py reuses slots() on the GPU.
 """
-import ctypes as C
 import functools
 import os
 import re
@@ -18,6 +17,7 @@ import ft8_audio_model as A
 import ft8_codec as Cd
 import ft8_decode_model as D
 import ft8_model as M
+from rx_harness import assert_entry_points
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("t41rx_ft8_audio_device_q15", "t41rx_ft8_audio_device", "t41rx_ft8_audio_host_q15", "t41rx_ft8_audio_host",
@@ -194,12 +194,7 @@ def test_transmission_decodes(k):
 def test_entry_points_declared_exported_and_bound(built):
     import t41_sdr_amd as T
     import t41_sdr_amd._lib as lib
-    hdr = open(os.path.join(ROOT, "include", "t41rx.h")).read()
-    m = open(os.path.join(ROOT, "t41_sdr_amd", "csrc", "exports.map")).read()
-    so = C.CDLL(lib.LIB_PATH)
-    for name in NEW:
-        assert re.search(r"T41RX_API\s+int\s+%s\s*\(" % name, hdr) and (name + ";") in m and name in lib.SYMBOLS, name
-        assert hasattr(so, name), name
+    hdr = assert_entry_points(NEW, pattern=r"T41RX_API\s+int\s+%s\s*\(")
     # nothing else is exported: the dynamic symbol table is what the two headers declare
     declared = set()
     for h in ("t41rx.h", "t41tx.h"):

@@ -256,18 +256,14 @@ def test_entry_points_declared_exported_and_bound(built):
     import ctypes as C
     import os
     import re
-    import t41_sdr_amd._lib as lib
-    root = D.ROOT
-    hdr = open(os.path.join(root, "include", "t41rx.h")).read()
-    m = open(os.path.join(root, "t41_sdr_amd", "csrc", "exports.map")).read()
-    for name in NEW:
-        assert re.search(r"T41RX_API\s+int\s+%s\s*\(" % name, hdr) and (name + ";") in m and name in lib.SYMBOLS, name
-        assert hasattr(C.CDLL(lib.LIB_PATH), name)
     import t41_sdr_amd as T
-    for meth in ("set_ft8_decode_tables", "set_ft8_decode", "ft8_decode_params", "ft8_decode"):
-        assert hasattr(T.RxChain, meth)
+    import t41_sdr_amd._lib as lib
+    from rx_harness import assert_entry_points
+    root = D.ROOT
+    hdr = assert_entry_points(NEW, ("set_ft8_decode_tables", "set_ft8_decode", "ft8_decode_params", "ft8_decode"), abi_version=5,
+                              pattern=r"T41RX_API\s+int\s+%s\s*\(")
     assert callable(T.ft8.unpack77_fields) and callable(T.ft8.messages)
-    assert "T41RX_ABI_VERSION 5" in hdr and lib.load().t41rx_abi_version() == 5
+    assert lib.load().t41rx_abi_version() == 5
     assert not open(os.path.join(root, "include", "t41tx.h")).read().count("ft8")
     assert "#define T41RX_FT8_MAX_CANDIDATES 20" in hdr and "#define T41RX_FT8_SLOT_BYTES 135424" in hdr and 92 * 1472 == 135424
 

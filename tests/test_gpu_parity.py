@@ -14,36 +14,21 @@ import pytest
 
 import oracle_lib as O
 import siggen
+from rx_harness import TOL, T, calls  # noqa: F401  (T: the loaded package, a fixture)
 
 pytestmark = pytest.mark.gpu
 
 L = 2048
-TOL = 1e-5
 AM_TOL = 5e-5  # see the note above test_parity_am
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-@pytest.fixture(scope="module")
-def T(built):
-    import torch
-    import t41_sdr_amd
-    assert torch.cuda.is_available()
-    t41_sdr_amd.load()
-    return t41_sdr_amd
-
-
 def gpu_run(T, kw, nco, I, Q, split=None):
-    import torch
-    kw = dict(kw)
+    """the stream in one call, or in calls cut at the samples of split (whole frames)"""
     rx = T.RxChain(I.shape[0], T.default_params(**kw), NCOFreq=nco)
-    dI, dQ = torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()
-    if split is None:
-        out = rx.ProcessIQData(dI, dQ)
-    else:
-        out = torch.cat([rx.ProcessIQData(dI[:, a:b].contiguous(), dQ[:, a:b].contiguous())
-                         for a, b in zip(split[:-1], split[1:])], dim=1)
-    torch.cuda.synchronize()
-    return out.cpu().numpy(), rx
+    Lf = rx.frame_len
+    assert I.shape[1] % Lf == 0 and not any(s % Lf for s in split or ())
+    return calls(rx, I, Q, [s // Lf for s in split or (0, I.shape[1])])[0], rx
 
 
 def oracle_run(kw, nco, I, Q):

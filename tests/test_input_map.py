@@ -11,7 +11,7 @@ import pytest
 
 import oracle_lib as O
 import siggen
-from test_gpu_parity import TOL  # the bound test_parity_vs_oracle applies
+from rx_harness import TOL, T, one_call, to_q15  # noqa: F401  (TOL: the bound test_parity_vs_oracle applies; T: a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -22,45 +22,20 @@ ERR_ARG = -1
 assert MAP.shape == (NCH,) and set(MAP) == set(range(NS))
 
 
-@pytest.fixture(scope="module")
-def T(built):
-    import torch
-    import t41_sdr_amd
-    assert torch.cuda.is_available()
-    t41_sdr_amd.load()
-    return t41_sdr_amd
-
-
 def streams(ns, nsamp, seed, q15=False):
     """distinct random samples per stream [ns, nsamp]: a wrong row cannot pass"""
     rng = np.random.default_rng(seed)
     I = (0.2 * rng.standard_normal((ns, nsamp))).astype(np.float32)
     Q = (0.2 * rng.standard_normal((ns, nsamp))).astype(np.float32)
     if q15:
-        I = np.clip(np.round(I * 32768.0), -32768, 32767).astype(np.int16)
-        Q = np.clip(np.round(Q * 32768.0), -32768, 32767).astype(np.int16)
+        I, Q = to_q15(I), to_q15(Q)
     return I, Q
 
 
 def run(rx, I, Q, host=False):
     """one call on channel-major numpy rows [rows, nfr * Lf] in the context's layout and the arrays' sample format;
     returns the audio as channel-major numpy [n_channels, nfr * Lf]"""
-    import torch
-    Lf = rx.frame_len
-    rows, nfr = I.shape[0], I.shape[1] // Lf
-    tm = rx.layout == "time"
-    if tm:
-        I = np.ascontiguousarray(I.reshape(rows, nfr, Lf).transpose(1, 0, 2))
-        Q = np.ascontiguousarray(Q.reshape(rows, nfr, Lf).transpose(1, 0, 2))
-    q15 = I.dtype == np.int16
-    if not host:
-        I, Q = torch.from_numpy(I.copy()).cuda(), torch.from_numpy(Q.copy()).cuda()
-    out = rx.ProcessIQData_q15(Q, I) if q15 else rx.ProcessIQData(I, Q)  # q15: I comes from the R queue
-    if not host:
-        torch.cuda.synchronize()
-        out = out.cpu().numpy()
-    assert out.shape == ((nfr, rx.n_channels, Lf) if tm else (rx.n_channels, nfr * Lf))
-    return out.transpose(1, 0, 2).reshape(rx.n_channels, nfr * Lf) if tm else out
+    return one_call(rx, I, Q, layout=rx.layout, host=host)[0]
 
 
 def pair(T, kw, nco=None, smap=MAP, ns=None, layout="channel", setup=None):

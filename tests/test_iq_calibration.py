@@ -14,6 +14,7 @@ import pytest
 
 import cal_model as M
 import oracle_lib as O
+from rx_harness import to_q15
 from test_cw_exciter import assert_same, cat, mic, rows
 from test_display_spectrum import ZOOM_TOL
 
@@ -76,8 +77,7 @@ LEVELS = {0: (0.21, 0.037), 2: (0.21, 0.1), 4: (0.21273, 0.17221)}
 
 def to_queues(I, Q):
     """the q15 wire format: float_buffer_L (= I) is filled from the R queue, float_buffer_R (= Q) from the L queue"""
-    q = lambda v: np.clip(np.round(v * 32768.0), -32768, 32767).astype(np.int16)  # noqa: E731
-    return q(Q), q(I)  # Q_in_L, Q_in_R
+    return to_q15(Q), to_q15(I)  # Q_in_L, Q_in_R
 
 
 def corrections(nch):

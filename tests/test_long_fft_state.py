@@ -30,9 +30,9 @@ import pytest
 
 import oracle_lib as O
 import siggen
-from test_gpu_parity import AM_TOL, TOL, T  # noqa: F401  (T: the loaded package, a fixture)
+from rx_harness import TOL, T, calls, one_call, to_q15  # noqa: F401  (T: the loaded package, a fixture)
+from test_gpu_parity import AM_TOL
 from test_noise_blanker import WIDE, clicky_iq
-from test_q15_boundary import to_q15
 
 pytestmark = pytest.mark.gpu
 
@@ -58,18 +58,14 @@ def cut(x, a, b, Lf):
 
 def dev(rx, i, q):
     """one call through the device-pointer entry point"""
-    import torch
-    return rx.ProcessIQData(torch.from_numpy(i).cuda(), torch.from_numpy(q).cuda()).cpu().numpy()
+    return one_call(rx, i, q)[0]
 
 
 def run(rx, I, Q, Lf, edges, between=None):
     """frames edges[k] .. edges[k + 1] per call; between(k) runs after call k (not after the last one)"""
-    out = []
-    for k, (a, b) in enumerate(zip(edges[:-1], edges[1:])):
-        out.append(dev(rx, cut(I, a, b, Lf), cut(Q, a, b, Lf)))
-        if between is not None and k < len(edges) - 2:
-            between(k)
-    return np.concatenate(out, axis=1)
+    assert rx.frame_len == Lf
+    after = None if between is None else lambda rx, a, b: b < edges[-1] and between(edges.index(a))
+    return calls(rx, I, Q, edges, after=after)[0]
 
 
 def check_vs_oracle(got, ref, N, tol, what):

@@ -4,19 +4,16 @@ CPU: the f32 restatement (tests/nb_model.py) against the independent float64 mod
 the quirks it keeps, the new entry points.  GPU (-m gpu): the HIP path with the blanker on against the HIP path's own
 demodulated audio through the restatement and the oracle's interpolators.
 """
-import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 
 import nb_model as M
 import oracle_lib as O
 import siggen
+from rx_harness import assert_entry_points, calls
+from stage_reference import interp, nb_stage, nr_stage
 
 L, D = 2048, 256
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def audio(nblocks, seed, tone=(700.0, 0.2), noise=0.05):
@@ -100,12 +97,7 @@ def test_cap_upper_boundary_and_the_carry_quirk():
 
 
 def test_entry_points_declared_and_exported(built):
-    import t41_sdr_amd._lib as lib
-    hdr = open(os.path.join(ROOT, "include", "t41rx.h")).read()
-    m = open(os.path.join(ROOT, "t41_sdr_amd", "csrc", "exports.map")).read()
-    for name in ("t41rx_set_noise_blanker", "t41rx_get_noise_blanker"):
-        assert re.search(r"\b%s\s*\(" % name, hdr) and (name + ";") in m and name in lib.SYMBOLS
-        assert hasattr(C.CDLL(lib.LIB_PATH), name)
+    assert_entry_points(("t41rx_set_noise_blanker", "t41rx_get_noise_blanker"))
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------
@@ -128,73 +120,27 @@ WIDE = {0: dict(FLoCut=100, FHiCut=11000), 1: dict(FLoCut=-11000, FHiCut=-100), 
         3: {}, 8: dict(FLoCut=-11000, FHiCut=11000)}
 
 
-def _vol_scale(v):
-    x = np.float32(v) / np.float32(100.0)
-    return np.float32(8.0) * (np.float32(5) * x * x * x * x * x)
-
-
 def stage24(pre, kw, model="f32", on=None, carry=None):
     """the HIP path's pre-stage audio through the oracle's NR stage (if on) and the blanker model on the blocks where
     on[b] (default: all); the carry is the input of the last block the blanker saw, as in the reference"""
-    lib = O.lib()
     p = O.default_params(**kw)
-    nch, n = pre.shape
-    nb = n // D
-    on = [True] * nb if on is None else on
     out = np.empty(pre.shape, np.float32)
-    R = np.zeros(D, np.float32)
     stats = dict(repairs=0, low=0, cap=0, near=0)
-    pos_all, near = [], np.zeros((nch, nb), bool)
-    for ch in range(nch):
+    pos_all, near = [], np.zeros((pre.shape[0], pre.shape[1] // D), bool)
+    for ch in range(pre.shape[0]):
         a = pre[ch].copy()
         if p.nrOptionSelect or p.ANR_notchOn:
-            s = lib.t41o_nr_create()
-            for b in range(nb):
-                blk = a[b * D:(b + 1) * D].copy()
-                lib.t41o_nr_block(s, C.byref(p), O.fptr(blk), O.fptr(R))
-                a[b * D:(b + 1) * D] = blk
-            lib.t41o_nr_destroy(s)
-        cy = np.zeros(M.NCARRY + 1) if carry is None else carry[ch]
-        pos_ch = []
-        for b in range(nb):
-            blk = a[b * D:(b + 1) * D]
-            if not on[b]:
-                pos_ch.append(None)
-                continue
-            if model == "f32":
-                y, pos, mg, _ = M.block_f32(blk, cy)
-                stats["near"] += int(mg < 1e-4)
-                near[ch, b] = mg < 1e-4
-            else:
-                y, pos, _ = M.block_f64(blk, cy)
-            stats["repairs"] += len(pos)
-            stats["low"] += sum(q < 13 for q in pos)
-            stats["cap"] += len(pos) == M.MAXIMP
-            pos_ch.append(pos)
-            cy = blk[M.N - 1 - M.ORDER - M.PL:].copy()
-            a[b * D:(b + 1) * D] = y
-        out[ch] = a
+            nr_stage(a, p)
+        out[ch], pos_ch, mags = nb_stage(a, model, on, None if carry is None else carry[ch])
+        near[ch] = mags < 1e-4
+        ran = [q for q in pos_ch if q is not None]
+        stats["repairs"] += sum(map(len, ran))
+        stats["low"] += sum(q < 13 for pos in ran for q in pos)
+        stats["cap"] += sum(len(pos) == M.MAXIMP for pos in ran)
         pos_all.append(pos_ch)
+    stats["near"] = int(near.sum())
     stats["near_blocks"] = near
     return out, stats, pos_all
-
-
-def interp(a24, kw):
-    """the oracle's interpolators and volume (Process.cpp:917-931), continuous over the stream"""
-    lib = O.lib()
-    p = O.default_params(**kw)
-    c = O.design(p)
-    nch, n = a24.shape
-    out = np.empty((nch, 8 * n), np.float32)
-    for ch in range(nch):
-        st1, st2 = np.zeros(23 + D, np.float32), np.zeros(7 + 2 * D, np.float32)
-        mid, hi = np.empty(2 * D, np.float32), np.empty(8 * D, np.float32)
-        for b in range(n // D):
-            blk = np.ascontiguousarray(a24[ch, b * D:(b + 1) * D], np.float32)
-            lib.t41o_fir_interpolate_f32(c.int1, 48, 2, O.fptr(st1), O.fptr(blk), O.fptr(mid), D)
-            lib.t41o_fir_interpolate_f32(c.int2, 32, 4, O.fptr(st2), O.fptr(mid), O.fptr(hi), 2 * D)
-            out[ch, b * L:(b + 1) * L] = hi * _vol_scale(p.audioVolume)
-    return out
 
 
 def expect(pre, kw, **k):
@@ -203,7 +149,6 @@ def expect(pre, kw, **k):
 
 
 def run_hip(kw, nch, nfr, seed, q15=False, layout="channel", splits=None, nb=1, iq=None):
-    import torch
     import t41_sdr_amd as T
     nco = siggen.nco_grid(nch, seed=seed)
     I, Q = clicky_iq(nch, nfr, seed) if iq is None else iq
@@ -211,28 +156,8 @@ def run_hip(kw, nch, nfr, seed, q15=False, layout="channel", splits=None, nb=1, 
     rx.set_noise_blanker(nb)
     if layout == "time":
         rx.set_buffer_layout("time")
-    tap = torch.zeros(nch, nfr * D, device="cuda")
-    if q15:
-        I, Q = [np.clip(np.round(v * 32768.0 / 64), -32768, 32767).astype(np.int16) for v in (I, Q)]
-    got = []
-    edges = splits or [0, nfr]
-    for a, b in zip(edges[:-1], edges[1:]):
-        t = torch.zeros(nch, (b - a) * D, device="cuda")
-        rx.set_debug_taps(demod=t)
-        i, q = I[:, a * L:b * L], Q[:, a * L:b * L]
-        if layout == "time":
-            i = i.reshape(nch, b - a, L).transpose(1, 0, 2).copy()
-            q = q.reshape(nch, b - a, L).transpose(1, 0, 2).copy()
-        if q15:
-            o = rx.ProcessIQData_q15(torch.from_numpy(np.ascontiguousarray(q)).cuda(), torch.from_numpy(np.ascontiguousarray(i)).cuda())
-        else:
-            o = rx.ProcessIQData(torch.from_numpy(np.ascontiguousarray(i)).cuda(), torch.from_numpy(np.ascontiguousarray(q)).cuda())
-        o = o.cpu().numpy()
-        if layout == "time":
-            o = o.reshape(b - a, nch, L).transpose(1, 0, 2).reshape(nch, (b - a) * L)
-        got.append(o)
-        tap[:, a * D:b * D] = t
-    return np.concatenate(got, axis=1), tap.cpu().numpy(), rx
+    got, tap, _ = calls(rx, I, Q, splits or [0, nfr], layout=layout, q15_scale=1 / 64 if q15 else None, tap_floats=D)
+    return got, tap, rx
 
 
 CASES = {  # name: (params, least repairs, least impulses at pos < 13) over the 12 x 16 stream of clicky_iq(seed 21)
@@ -360,24 +285,17 @@ def test_gpu_on_off_on_keeps_the_stale_carry(built):
     saw before it was switched off (last_frame_end only changes while it runs): the whole stream, interpolators
     continuous, against the restatement with that carry; frame 6 holds an impulse at pos < 13, and a zeroed carry would
     not match"""
-    import torch
     import t41_sdr_amd as T
     kw = CASES["sam"][0]
     nch, nfr = 12, 10
     nco = siggen.nco_grid(nch, seed=24)
     I, Q = clicky_iq(nch, nfr, 24)
-    dI, dQ = torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()
     rz = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-    tap = torch.zeros(nch, nfr * D, device="cuda")
-    outs = []
+    parts = []
     for (s, e), on in zip(((0, 3), (3, 6), (6, nfr)), (1, 0, 1)):
         rz.set_noise_blanker(on)
-        t = torch.zeros(nch, (e - s) * D, device="cuda")
-        rz.set_debug_taps(demod=t)
-        outs.append(rz.ProcessIQData(dI[:, s * L:e * L].contiguous(), dQ[:, s * L:e * L].contiguous()).cpu().numpy())
-        tap[:, s * D:e * D] = t
-    got = np.concatenate(outs, axis=1)
-    pre = tap.cpu().numpy()
+        parts.append(calls(rz, I, Q, [s, e], tap_floats=D))
+    got, pre = (np.concatenate([p[k] for p in parts], axis=1) for k in (0, 1))
     on = [b < 3 or b >= 6 for b in range(nfr)]
     a24, st, pos = stage24(pre, kw, on=on)
     e = siggen.block_rel_err(got, interp(a24, kw), L)
@@ -431,18 +349,8 @@ def test_gpu_degenerate_input_and_no_detection(built):
 
 @pytest.mark.gpu
 def test_gpu_nb_large_batch_spot_check(built):
-    import torch
-    import t41_sdr_amd as T
-    nch, nfr = 4096, 4
+    got, pre, _ = run_hip(CASES["usb"][0], 4096, 4, seed=30)
     kw = CASES["usb"][0]
-    nco = siggen.nco_grid(nch, seed=30)
-    I, Q = clicky_iq(nch, nfr, 30)
-    rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-    rx.set_noise_blanker(1)
-    tap = torch.zeros(nch, nfr * D, device="cuda")
-    rx.set_debug_taps(demod=tap)
-    got = rx.ProcessIQData(torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()).cpu().numpy()
-    pre = tap.cpu().numpy()
     pick = [0, 1, 63, 64, 2047, 4095]
     want, st = expect(pre[pick], kw)
     assert siggen.block_rel_err(got[pick], want, L).max() <= 1e-5, st

@@ -12,6 +12,8 @@ import pytest
 import nr_model as M
 import oracle_lib as O
 import siggen
+from rx_harness import calls, one_call, to_q15
+from stage_reference import interp, nr_stage, vol_scale
 
 L, D = 2048, 256
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -206,33 +208,10 @@ def test_oracle_stage_conditioning(built):
 
 
 # ---- the HIP path ------------------------------------------------------------------------------------------------
-def _vol_scale(audioVolume=30):
-    x = np.float32(audioVolume) / np.float32(100.0)
-    ampl = np.float32(5) * x * x * x * x * x
-    return np.float32(8.0) * ampl  # DF * VolumeToAmplification(), Process.cpp:929, 955-967
-
-
 def _oracle_stage_and_interpolators(pre, kw):
     """the oracle's stage (Process.cpp:841-866) and interpolators (Process.cpp:917-931) on given 24 kS/s audio, per channel"""
-    lib = O.lib()
     p = O.default_params(**kw)
-    c = O.design(p)
-    nch, n = pre.shape
-    out = np.empty((nch, 8 * n), np.float32)
-    R = np.zeros(D, np.float32)
-    scale = _vol_scale(p.audioVolume)
-    for ch in range(nch):
-        s = lib.t41o_nr_create()
-        st1, st2 = np.zeros(23 + D, np.float32), np.zeros(7 + 2 * D, np.float32)
-        mid, hi = np.empty(2 * D, np.float32), np.empty(8 * D, np.float32)
-        for b in range(n // D):
-            blk = pre[ch, b * D:(b + 1) * D].copy()
-            lib.t41o_nr_block(s, C.byref(p), O.fptr(blk), O.fptr(R))
-            lib.t41o_fir_interpolate_f32(c.int1, 48, 2, O.fptr(st1), O.fptr(blk), O.fptr(mid), D)
-            lib.t41o_fir_interpolate_f32(c.int2, 32, 4, O.fptr(st2), O.fptr(mid), O.fptr(hi), 2 * D)
-            out[ch, b * L:(b + 1) * L] = hi * scale
-        lib.t41o_nr_destroy(s)
-    return out
+    return interp(np.stack([nr_stage(pre[ch].copy(), p) for ch in range(pre.shape[0])]), kw)
 
 
 NR_CASES = {
@@ -264,22 +243,13 @@ def test_gpu_stage_in_isolation(built, name):
     """The stage and what follows it, on IDENTICAL input: the HIP path's own demodulated audio (the stage tap in front
     of it) through the oracle's stage and interpolators must give the HIP path's output.  70 channels = one full wave
     of the lane-per-channel kernel and a ragged one; three calls."""
-    import torch
     import t41_sdr_amd as T
     kw, tol, how = NR_CASES[name]
     nch, nfr = 70, 36
     nco = siggen.nco_grid(nch, seed=5)
     I, Q = siggen.make_iq(nch, nfr * L, nco, mode=kw.get("mode", 0), seed=50)
     rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-    dI, dQ = torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()
-    got, pre, pos = [], [], 0
-    for n in (1, 15, 20):
-        tap = torch.zeros(nch, n * D, device="cuda")
-        rx.set_debug_taps(demod=tap)
-        got.append(rx.ProcessIQData(dI[:, pos * L:(pos + n) * L].contiguous(), dQ[:, pos * L:(pos + n) * L].contiguous()))
-        pre.append(tap)
-        pos += n
-    got, pre = torch.cat(got, dim=1).cpu().numpy(), torch.cat(pre, dim=1).cpu().numpy()
+    got, pre, _ = calls(rx, I, Q, [0, 1, 16, nfr], tap_floats=D)  # calls of 1, 15 and 20 frames
     assert np.isfinite(got).all()
     want = _oracle_stage_and_interpolators(pre, kw)
     e = siggen.block_rel_err(got, want, L)
@@ -303,7 +273,7 @@ def _exact_stage_and_interpolators(pre, kw):
         aud = M.run(pre[ch], p.FLoCut, p.FHiCut, nrOptionSelect=p.nrOptionSelect, ANR_notchOn=p.ANR_notchOn,
                     alpha=float(p.NR_alpha), beta=float(p.NR_beta), psi=float(p.NR_PSI))
         a1 = signal.upfirdn(g1, aud, up=2)[:2 * aud.size]
-        out[ch] = signal.upfirdn(g2, a1, up=4)[:4 * a1.size] * float(_vol_scale(p.audioVolume))
+        out[ch] = signal.upfirdn(g2, a1, up=4)[:4 * a1.size] * float(vol_scale(p.audioVolume))
     return out
 
 
@@ -316,17 +286,13 @@ def test_gpu_stage_is_as_close_to_the_exact_model_as_the_oracle(built, name):
     functions evaluated exactly (tests/test_noise_reduction.py::test_kim_matches_the_f64_model allows the ORACLE 5e-5).
     On identical input (the HIP path's own pre-stage audio): the HIP output is no farther from the float64 model than
     the oracle is, frame by frame in distribution; the per-frame distributions go into the assertion message."""
-    import torch
     import t41_sdr_amd as T
     kw, tol, how = NR_CASES[name]
     nch, nfr = 24, 40
     nco = siggen.nco_grid(nch, seed=15)
     I, Q = siggen.make_iq(nch, nfr * L, nco, mode=0, seed=150)
     rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-    tap = torch.zeros(nch, nfr * D, device="cuda")
-    rx.set_debug_taps(demod=tap)
-    got = rx.ProcessIQData(torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()).cpu().numpy()
-    pre = tap.cpu().numpy()
+    got, pre = one_call(rx, I, Q, tap_floats=D)
     orc = _oracle_stage_and_interpolators(pre, kw)
     exact = _exact_stage_and_interpolators(pre, kw)
     d_hip = siggen.block_rel_err(got, exact, L)
@@ -412,8 +378,7 @@ def test_gpu_nr_q15(built, kw):
     kw = dict(kw, audioVolume=70)
     nco = siggen.nco_grid(nch, seed=9)
     I, Q = siggen.make_iq(nch, nfr * L, nco, mode=0, seed=90)
-    qI = np.clip(np.round(I * 32768.0), -32768, 32767).astype(np.int16)
-    qQ = np.clip(np.round(Q * 32768.0), -32768, 32767).astype(np.int16)
+    qI, qQ = to_q15(I), to_q15(Q)
     rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
     got = rx.ProcessIQData_q15(torch.from_numpy(qQ).cuda(), torch.from_numpy(qI).cuda()).cpu().numpy()
     rx.reset()

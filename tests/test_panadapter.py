@@ -12,6 +12,7 @@ import pytest
 
 import panadapter_model as M
 import siggen
+from rx_harness import one_call
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 L, R = 2048, 512
@@ -346,15 +347,9 @@ def test_gpu_entry_forms(built, form):
     params = dict(mode=T.DEMOD_AM) if form == "am" else {}
 
     def run(rx):
-        if form == "q15":
-            qi = torch.from_numpy(np.clip(np.round(s["I"] * 32768.0), -32768, 32767).astype(np.int16)).cuda()
-            qq = torch.from_numpy(np.clip(np.round(s["Q"] * 32768.0), -32768, 32767).astype(np.int16)).cuda()
-            return rx.ProcessIQData_q15(qq, qi)
-        dI, dQ = frames(False, 0, NFR)
         if form == "time":
             rx.set_buffer_layout("time")
-            return rx.ProcessIQData(dI.view(NCH, NFR, L).transpose(0, 1).contiguous(), dQ.view(NCH, NFR, L).transpose(0, 1).contiguous())
-        return rx.ProcessIQData(dI, dQ)
+        return one_call(rx, s["I"], s["Q"], layout="time" if form == "time" else "channel", q15_scale=1.0 if form == "q15" else None)[0]
 
     twin = chain(T, **params)
     ts, to = torch.zeros(NCH, NFR, R, device="cuda"), torch.zeros(NCH, NFR, R, device="cuda")
@@ -366,7 +361,7 @@ def test_gpu_entry_forms(built, form):
     nf = np.array([10, 0, -30], np.int32)
     rx.set_panadapter_levels(noise_floor=nf)
     audio = run(rx)
-    assert torch.equal(audio, run(chain(T, **params)))
+    assert np.array_equal(audio, run(chain(T, **params)))
     assert rx.panadapter_status() == (True, NFR, 3, 1)
     got = snap(bufs, 3)
     assert same_bits(got["spec"], host(ts)[:, flagged])

@@ -7,13 +7,9 @@ import pytest
 
 import oracle_lib as O
 import siggen
+from rx_harness import to_q15  # what the codec would deliver for a float waveform in (-1, 1)
 
 L = 2048
-
-
-def to_q15(x):
-    """what the codec would deliver for a float waveform in (-1, 1)"""
-    return np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16)
 
 
 def test_conversions_follow_cmsis(built):
@@ -156,8 +152,7 @@ def test_gpu_q15_side_outputs_and_taps(built, kw):
     nch, nfr = 7, 3
     nco = siggen.nco_grid(nch, seed=31)
     I, Q = siggen.make_iq(nch, 2 * nfr * L, nco, mode=min(kw["mode"], 2) if kw["mode"] != 3 else 3, seed=32)
-    qI = np.clip(np.round(I * 32768.0), -32768, 32767).astype(np.int16)
-    qQ = np.clip(np.round(Q * 32768.0), -32768, 32767).astype(np.int16)
+    qI, qQ = to_q15(I), to_q15(Q)
     fI, fQ = qI.astype(np.float32) / np.float32(32768), qQ.astype(np.float32) / np.float32(32768)
     kw = dict(kw, audioVolume=60)
     for zoom in (0, 2):

@@ -12,20 +12,16 @@ new entry points.  GPU (-m gpu): the HIP path with the equalizer on against the 
 through the restatement, the oracle's NR stage, the blanker model and the oracle's interpolators; a physical check
 against the float64 model alone; streaming, checkpoints, formats, refusals, a large batch.
 """
-import ctypes as C
-import os
-import re
-
 import numpy as np
 import pytest
 
 import eq_model as M
-import nb_model as NB
 import oracle_lib as O
 import siggen
+from rx_harness import assert_entry_points, calls
+from stage_reference import interp, nb_stage, nr_stage
 
 L, D = 2048, 256
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RAMP = [0, 15, 30, 0, 61, 77, 92, 108, 0, 138, 154, 169, 185, 200]  # non-default levels, some zero
 
 
@@ -125,69 +121,27 @@ def test_zero_levels_give_silence_and_the_state_still_advances():
 
 
 def test_entry_points_declared_and_exported(built):
-    import t41_sdr_amd._lib as lib
-    hdr = open(os.path.join(ROOT, "include", "t41rx.h")).read()
-    m = open(os.path.join(ROOT, "t41_sdr_amd", "csrc", "exports.map")).read()
-    for name in ("t41rx_set_receive_eq_bands", "t41rx_set_receive_eq", "t41rx_get_receive_eq"):
-        assert re.search(r"\b%s\s*\(" % name, hdr) and (name + ";") in m and name in lib.SYMBOLS
-        assert hasattr(C.CDLL(lib.LIB_PATH), name)
+    assert_entry_points(("t41rx_set_receive_eq_bands", "t41rx_set_receive_eq", "t41rx_get_receive_eq"))
 
 
 # ---- GPU ---------------------------------------------------------------------------------------------------------------
-def _vol_scale(v):
-    x = np.float32(v) / np.float32(100.0)
-    return np.float32(8.0) * (np.float32(5) * x * x * x * x * x)
-
-
 def stage24(pre, kw, levels, model="f32", on=None, nb=False, lv_per_block=None):
     """the HIP path's pre-stage audio through the equalizer model on the blocks where on[b] (default: all), then the
     oracle's NR stage (if on) and the blanker model (if nb), as in Process.cpp:828-876"""
-    lib = O.lib()
     p = O.default_params(**kw)
-    nch, n = pre.shape
-    nblk = n // D
     out = np.empty(pre.shape, np.float32)
-    R = np.zeros(D, np.float32)
-    for ch in range(nch):
+    for ch in range(pre.shape[0]):
         eq = M.Restatement() if model == "f32" else M.F64()
         a = pre[ch].copy()
-        for b in range(nblk):
+        for b in range(a.size // D):
             if on is None or on[b]:
                 lv = levels if lv_per_block is None else lv_per_block[b]
                 a[b * D:(b + 1) * D] = eq.block(pre[ch, b * D:(b + 1) * D], lv)
         if p.nrOptionSelect or p.ANR_notchOn:
-            s = lib.t41o_nr_create()
-            for b in range(nblk):
-                blk = a[b * D:(b + 1) * D].copy()
-                lib.t41o_nr_block(s, C.byref(p), O.fptr(blk), O.fptr(R))
-                a[b * D:(b + 1) * D] = blk
-            lib.t41o_nr_destroy(s)
+            nr_stage(a, p)
         if nb:
-            cy = np.zeros(NB.NCARRY + 1)
-            for b in range(nblk):
-                blk = a[b * D:(b + 1) * D]
-                y, _, _, _ = NB.block_f32(blk, cy)
-                cy = blk[NB.N - 1 - NB.ORDER - NB.PL:].copy()
-                a[b * D:(b + 1) * D] = y
+            nb_stage(a)
         out[ch] = a
-    return out
-
-
-def interp(a24, kw):
-    """the oracle's interpolators and volume (Process.cpp:917-931), continuous over the stream"""
-    lib = O.lib()
-    p = O.default_params(**kw)
-    c = O.design(p)
-    nch, n = a24.shape
-    out = np.empty((nch, 8 * n), np.float32)
-    for ch in range(nch):
-        st1, st2 = np.zeros(23 + D, np.float32), np.zeros(7 + 2 * D, np.float32)
-        mid, hi = np.empty(2 * D, np.float32), np.empty(8 * D, np.float32)
-        for b in range(n // D):
-            blk = np.ascontiguousarray(a24[ch, b * D:(b + 1) * D], np.float32)
-            lib.t41o_fir_interpolate_f32(c.int1, 48, 2, O.fptr(st1), O.fptr(blk), O.fptr(mid), D)
-            lib.t41o_fir_interpolate_f32(c.int2, 32, 4, O.fptr(st2), O.fptr(mid), O.fptr(hi), 2 * D)
-            out[ch, b * L:(b + 1) * L] = hi * _vol_scale(p.audioVolume)
     return out
 
 
@@ -206,34 +160,13 @@ def make_rx(nch, kw, nco, levels=RAMP, on=1, nb=0):
 
 
 def run_hip(kw, nch, nfr, seed, levels=RAMP, q15=False, layout="channel", splits=None, on=1, nb=0, iq=None):
-    import torch
     nco = siggen.nco_grid(nch, seed=seed)
     I, Q = siggen.make_iq(nch, nfr * L, nco, mode=kw.get("mode", 0), seed=seed, sigma=0.05) if iq is None else iq
     rx = make_rx(nch, kw, nco, levels, on, nb)
     if layout == "time":
         rx.set_buffer_layout("time")
-    tap = torch.zeros(nch, nfr * D, device="cuda")
-    if q15:
-        I, Q = [np.clip(np.round(v * 32768.0 / 4), -32768, 32767).astype(np.int16) for v in (I, Q)]
-    got = []
-    edges = splits or [0, nfr]
-    for a, b in zip(edges[:-1], edges[1:]):
-        t = torch.zeros(nch, (b - a) * D, device="cuda")
-        rx.set_debug_taps(demod=t)
-        i, q = I[:, a * L:b * L], Q[:, a * L:b * L]
-        if layout == "time":
-            i = i.reshape(nch, b - a, L).transpose(1, 0, 2).copy()
-            q = q.reshape(nch, b - a, L).transpose(1, 0, 2).copy()
-        if q15:
-            o = rx.ProcessIQData_q15(torch.from_numpy(np.ascontiguousarray(q)).cuda(), torch.from_numpy(np.ascontiguousarray(i)).cuda())
-        else:
-            o = rx.ProcessIQData(torch.from_numpy(np.ascontiguousarray(i)).cuda(), torch.from_numpy(np.ascontiguousarray(q)).cuda())
-        o = o.cpu().numpy()
-        if layout == "time":
-            o = o.reshape(b - a, nch, L).transpose(1, 0, 2).reshape(nch, (b - a) * L)
-        got.append(o)
-        tap[:, a * D:b * D] = t
-    return np.concatenate(got, axis=1), tap.cpu().numpy(), rx
+    got, tap, _ = calls(rx, I, Q, splits or [0, nfr], layout=layout, q15_scale=1 / 4 if q15 else None, tap_floats=D)
+    return got, tap, rx
 
 
 CASES = {  # name: (params, NB behind it, tolerance)
@@ -331,17 +264,13 @@ def test_gpu_splits_checkpoint_reset_levels_and_params(built):
     # levels changed between calls take effect at the next call
     lv2 = [200 - v for v in RAMP]
     rz = make_rx(nch, kw, nco)
-    tap = torch.zeros(nch, nfr * D, device="cuda")
-    outs = []
+    parts = []
     for (s, e), levels in zip(((0, cut), (cut, nfr)), (RAMP, lv2)):
         rz.set_receive_eq(1, levels)
-        t = torch.zeros(nch, (e - s) * D, device="cuda")
-        rz.set_debug_taps(demod=t)
-        outs.append(rz.ProcessIQData(*part(s, e)).cpu().numpy())
-        tap[:, s * D:e * D] = t
-    got = np.concatenate(outs, axis=1)
+        parts.append(calls(rz, I, Q, [s, e], tap_floats=D))
+    got, tap = (np.concatenate([p[k] for p in parts], axis=1) for k in (0, 1))
     per = [RAMP if b < cut else lv2 for b in range(nfr)]
-    e = siggen.block_rel_err(got, interp(stage24(tap.cpu().numpy(), kw, None, lv_per_block=per), kw), L)
+    e = siggen.block_rel_err(got, interp(stage24(tap, kw, None, lv_per_block=per), kw), L)
     assert e.max() <= 1e-5, e.max()
     assert not np.array_equal(got[:, cut * L:], whole[:, cut * L:])
 
@@ -351,24 +280,17 @@ def test_gpu_off_on_keeps_the_stale_state(built):
     """switched off and on again, the equalizer resumes from the memories it had when it was switched off (they only
     change while it runs): the whole stream against the restatement that skips the off blocks; memories zeroed at the
     switch would not match"""
-    import torch
     kw = dict(mode=0)
     nch, nfr = 6, 10
     nco = siggen.nco_grid(nch, seed=24)
     I, Q = siggen.make_iq(nch, nfr * L, nco, mode=0, seed=24, sigma=0.05)
-    dI, dQ = torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()
     rz = make_rx(nch, kw, nco)
-    tap = torch.zeros(nch, nfr * D, device="cuda")
-    outs = []
+    parts = []
     for (s, e), on in zip(((0, 3), (3, 6), (6, nfr)), (1, 0, 1)):
         rz.set_receive_eq(on)
         assert rz.receive_eq[0] == on and list(rz.receive_eq[1]) == RAMP
-        t = torch.zeros(nch, (e - s) * D, device="cuda")
-        rz.set_debug_taps(demod=t)
-        outs.append(rz.ProcessIQData(dI[:, s * L:e * L].contiguous(), dQ[:, s * L:e * L].contiguous()).cpu().numpy())
-        tap[:, s * D:e * D] = t
-    got = np.concatenate(outs, axis=1)
-    pre = tap.cpu().numpy()
+        parts.append(calls(rz, I, Q, [s, e], tap_floats=D))
+    got, pre = (np.concatenate([p[k] for p in parts], axis=1) for k in (0, 1))
     on = [b < 3 or b >= 6 for b in range(nfr)]  # (one 256-sample block per frame)
     e = siggen.block_rel_err(got, interp(stage24(pre, kw, RAMP, on=on), kw), L)
     assert e.max() <= 1e-5, e.max()
@@ -444,15 +366,7 @@ def test_gpu_eq_refusals(built):
 
 @pytest.mark.gpu
 def test_gpu_eq_large_batch_spot_check(built):
-    import torch
-    nch, nfr = 4096, 4
     kw = dict(mode=0)
-    nco = siggen.nco_grid(nch, seed=30)
-    I, Q = siggen.make_iq(nch, nfr * L, nco, mode=0, seed=30, sigma=0.05)
-    rx = make_rx(nch, kw, nco)
-    tap = torch.zeros(nch, nfr * D, device="cuda")
-    rx.set_debug_taps(demod=tap)
-    got = rx.ProcessIQData(torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()).cpu().numpy()
-    pre = tap.cpu().numpy()
+    got, pre, _ = run_hip(kw, 4096, 4, seed=30)
     pick = [0, 1, 63, 64, 2047, 4095]
     assert siggen.block_rel_err(got[pick], expect(pre[pick], kw, RAMP), L).max() <= 1e-5

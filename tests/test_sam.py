@@ -8,6 +8,7 @@ import pytest
 import f64_model as M
 import oracle_lib as O
 import siggen
+from rx_harness import calls, to_q15
 
 L = 2048
 SAM = O.DEMOD_SAM
@@ -128,14 +129,9 @@ def test_oracle_sam_locks_and_recovers_the_modulation(built):
 
 # ---- the HIP path ---------------------------------------------------------------------------
 def _gpu_run(T, kw, nco, I, Q, splits):
-    import torch
+    """the stream in calls of splits[k] frames"""
     rx = T.RxChain(len(nco), T.default_params(**kw), NCOFreq=nco)
-    x, y = torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()
-    outs, pos = [], 0
-    for n in splits:
-        outs.append(rx.ProcessIQData(x[:, pos * L:(pos + n) * L].contiguous(), y[:, pos * L:(pos + n) * L].contiguous()))
-        pos += n
-    return torch.cat(outs, dim=1).cpu().numpy(), rx
+    return calls(rx, I, Q, [sum(splits[:k]) for k in range(len(splits) + 1)])[0], rx
 
 
 @pytest.mark.gpu
@@ -280,8 +276,7 @@ def test_gpu_sam_q15(built, agc):
     kw = dict(KW, AGCMode=agc, audioVolume=60)
     nco = siggen.nco_grid(nch, seed=23)
     I, Q = siggen.make_am_carrier(nch, nfr * L, nco, seed=91)
-    qI = np.clip(np.round(I * 32768.0), -32768, 32767).astype(np.int16)
-    qQ = np.clip(np.round(Q * 32768.0), -32768, 32767).astype(np.int16)
+    qI, qQ = to_q15(I), to_q15(Q)
     rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
     got = rx.ProcessIQData_q15(torch.from_numpy(qQ).cuda(), torch.from_numpy(qI).cuda()).cpu().numpy()  # L queue = Q, R queue = I
     rx.reset()

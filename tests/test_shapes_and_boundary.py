@@ -12,18 +12,9 @@ import pytest
 
 import oracle_lib as O
 import siggen
+from rx_harness import TOL, T, to_q15  # noqa: F401  (T: the loaded package, a fixture)
 
 L = 2048
-TOL = 1e-5
-
-
-@pytest.fixture(scope="module")
-def T(built):
-    import torch
-    import t41_sdr_amd
-    assert torch.cuda.is_available()
-    t41_sdr_amd.load()
-    return t41_sdr_amd
 
 
 @pytest.mark.gpu
@@ -48,8 +39,8 @@ def test_single_channel_single_frame_host_calls_q15(T):
     nfr = 8
     nco = np.array([-12500], np.int32)
     I, Q = siggen.make_iq(1, nfr * L, nco, mode=0, seed=78)
-    qi = np.clip(np.round(I * 32768.0), -32768, 32767).astype(np.int16)  # R queue -> float_buffer_L = I (Process.cpp:107)
-    qq = np.clip(np.round(Q * 32768.0), -32768, 32767).astype(np.int16)  # L queue -> float_buffer_R = Q
+    qi = to_q15(I)  # R queue -> float_buffer_L = I (Process.cpp:107)
+    qq = to_q15(Q)  # L queue -> float_buffer_R = Q
     rx = T.RxChain(1, T.default_params(**kw), NCOFreq=nco)
     got = np.concatenate([rx.ProcessIQData_q15(qq[:, f * L:(f + 1) * L].copy(), qi[:, f * L:(f + 1) * L].copy()) for f in range(nfr)], axis=1)
     ref = O.OracleBatch(O.default_params(**kw), nco).process_q15(qq, qi)

@@ -13,41 +13,15 @@ import pytest
 
 import oracle_lib as O
 import tx_model as M
+from tx_harness import F, assert_same, cat, mic, run
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = 2048
 USB, LSB, AM = O.DEMOD_USB, O.DEMOD_LSB, O.DEMOD_AM
 OK, ERR_ARG, ERR_STATE = 0, -1, -5
 ALL100 = (100,) * 14
 QUIRK = (50, 99, 100, 150, 199, 200, -50, -100, -199, 0, 1, 250, 100, 100)
 NEW_SYMBOLS = ("t41tx_set_transmit_eq_bands", "t41tx_set_transmit_eq", "t41tx_get_transmit_eq",
                "t41tx_state_bytes", "t41tx_get_state", "t41tx_set_state")
-
-
-def mic(nch, nfr, seed=1, level=0.5):
-    """speech-band multi-tone + noise at 192 kS/s as q15 (test_tx_exciter.py's recipe)"""
-    rng = np.random.default_rng(seed)
-    n = np.arange(nfr * F)
-    x = np.zeros((nch, nfr * F))
-    for c in range(nch):
-        for _ in range(4):
-            x[c] += rng.uniform(0.05, 0.3) * np.sin(2 * np.pi * rng.uniform(300, 2800) / 192000.0 * n + rng.uniform(0, 6.28))
-        x[c] += 0.01 * rng.standard_normal(n.size)
-    x *= level / np.abs(x).max()
-    return np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16)
-
-
-def cat(parts):
-    return tuple(np.concatenate([p[i] for p in parts], axis=1) for i in (0, 1))
-
-
-def assert_same(got, ref, what=""):
-    for g, r, side in ((got[0], ref[0], "I"), (got[1], ref[1], "Q")):
-        if not np.array_equal(g, r):
-            d = g.astype(np.int32) - r.astype(np.int32)
-            bad = np.argwhere(d)
-            raise AssertionError("%s %s: %d of %d samples differ (max |d| %d), first at [channel, sample] %s"
-                                 % (what, side, len(bad), d.size, np.abs(d).max(), bad[0].tolist()))
 
 
 # ---- CPU: the models
@@ -148,19 +122,6 @@ def test_tx_equaliser_abi_symbols_and_null_refusals(built):
 
 
 # ---- GPU helpers
-def dev(q):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(q)).cuda()
-
-
-def run(tx, q):
-    """one device call on the current stream; numpy (I, Q)"""
-    import torch
-    oL, oR = tx.ExciterIQData(dev(q))
-    torch.cuda.synchronize()
-    return oL.cpu().numpy(), oR.cpu().numpy()
-
-
 def chain(nch, mode=USB, amp=1.0, phase=0.0, on=True, levels=None):
     """a context with the band table loaded and the equaliser switched"""
     import t41_sdr_amd as T

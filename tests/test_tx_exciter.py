@@ -10,22 +10,9 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from tx_harness import F, mic
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F = 2048
-
-
-def mic(nch, nfr, seed=1, level=0.5):
-    """speech-band multi-tone + noise at 192 kS/s as q15 (what the codec would deliver)"""
-    rng = np.random.default_rng(seed)
-    n = np.arange(nfr * F)
-    x = np.zeros((nch, nfr * F))
-    for c in range(nch):
-        for _ in range(4):
-            x[c] += rng.uniform(0.05, 0.3) * np.sin(2 * np.pi * rng.uniform(300, 2800) / 192000.0 * n + rng.uniform(0, 6.28))
-        x[c] += 0.01 * rng.standard_normal(n.size)
-    x *= level / np.abs(x).max()
-    return np.clip(np.round(x * 32768.0), -32768, 32767).astype(np.int16)
 
 
 def stream_model(q, mode, amp, phase, tabs):

@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from test_tx_exciter import F, mic, stream_model
+from test_tx_exciter import stream_model
+from tx_harness import F, assert_same, dev, mic, run
 
 USB, LSB, AM, NFM, SAM = O.DEMOD_USB, O.DEMOD_LSB, O.DEMOD_AM, O.DEMOD_NFM, O.DEMOD_SAM
 ERR_ARG, OK = -1, 0
@@ -66,19 +67,6 @@ def params(mode, amp=1.0, phase=0.0):
     return T.default_tx_params(mode=mode, IQXAmpCorrectionFactor=amp, IQXPhaseCorrectionFactor=phase)
 
 
-def dev(q):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(q)).cuda()
-
-
-def run(tx, q):
-    """one device call on the current stream; numpy (I, Q)"""
-    import torch
-    oL, oR = tx.ExciterIQData(dev(q))
-    torch.cuda.synchronize()
-    return oL.cpu().numpy(), oR.cpu().numpy()
-
-
 def chain(nch, mode=USB, amp=1.0, phase=0.0):
     import t41_sdr_amd as T
     return T.TxChain(nch, params(mode, amp, phase))
@@ -86,15 +74,6 @@ def chain(nch, mode=USB, amp=1.0, phase=0.0):
 
 def oracle(q, mode=USB, amp=1.0, phase=0.0):
     return O.TxOracleBatch(q.shape[0], mode, amp, phase).process(q)
-
-
-def assert_same(got, ref, what=""):
-    for g, r, side in ((got[0], ref[0], "I"), (got[1], ref[1], "Q")):
-        if not np.array_equal(g, r):
-            d = g.astype(np.int32) - r.astype(np.int32)
-            bad = np.argwhere(d)
-            raise AssertionError("%s %s: %d of %d samples differ (max |d| %d), first at [channel, sample] %s"
-                                 % (what, side, len(bad), d.size, np.abs(d).max(), bad[0].tolist()))
 
 
 # ---- A. bit-exact parity: every value of every axis appears in some row
