@@ -754,6 +754,69 @@ T41RX_API int t41rx_set_panadapter_levels(t41rx_ctx *ctx, const int32_t *noise_f
 T41RX_API int t41rx_get_panadapter(const t41rx_ctx *ctx, int64_t *frame_counter, int32_t *rows_written, int64_t *first_row_frame);
 T41RX_API int t41rx_set_panadapter_counter(t41rx_ctx *ctx, int64_t n);
 
+/* ---- the beacon monitor: BeaconLoop()'s per-beacon SNR table (Beacon.cpp:204-208, 455-569) ----
+ * A stage behind the panadapter stage, default off.  The firmware calls BeaconLoop() once per loop() pass, which is once
+ * per ShowBeacon() sweep, and the only thing it reads is the sweep's dbm: here one BeaconLoop() call per panadapter row,
+ * rows 0 .. k-1 of a process call in order, dbm = the row's smeter[3], the clock evaluated at the row's frame number n
+ * (the panadapter's counter).  A process call that wrote no row launches nothing for the stage, and a context that does
+ * not switch it on launches exactly what it launched before.  The audio of every call, t41rx_state_bytes(), the section
+ * mask and the ABI are unchanged.
+ *
+ * A channel is one receiver on one band: monitorFreq[] of a channel has exactly one band set, band[c] in 0 .. 4 (20, 17,
+ * 15, 12, 10 m); it cannot retune.  The firmware's walk over the other four bands is kept as the four calls of `band++`
+ * that find nothing to do.  Five channels, one per band, fill the 18 x 5 table the firmware needs over 15 minutes for in
+ * one cycle of three.  The library carries no beacon names, maps or bearings: indices 0 .. 17 are the interface.
+ * Clock.  slot(n) = ((t0_ms + floor(n * num / den)) / 1000 % 180) / 10 in int64 -- GetBeacon20mNow() -- and
+ *   GetBeaconNow(band) = slot - band, plus 18 if negative.  t0_ms in [0, 180000), num >= 0, den > 0; the default 0, 32, 3
+ *   is one frame of 2048 samples at 192 kS/s, the CW and FT8 stages' clock.  n is the row's update frame, the FIRST frame
+ *   of the firmware's sweep; a caller who wants the time of the sweep's end folds the sweep's length into t0_ms.
+ *   t41rx_set_beacon() reads the clock (for currentBeacon): set the clock first.  T41RX_ERR_ARG otherwise, and when
+ *   n * num would not fit 64 bits (also from a process call, which then processes nothing).
+ * Per call of BeaconLoop(), the synced branch as written:
+ *   count == 0 && changeBandFlag: band++, wrapping at 5; on the channel's own band changeBandFlag = false.
+ *   count > 0: snrCount++; `if (dbm < min) min = dbm; if (dbm > max) max = dbm;` (plain comparisons: a NaN moves neither,
+ *     -inf moves min only); on GetBeaconNow(band) != currentBeacon: snr[that NEW beacon] = (snrCount == 23) ? 0 :
+ *     (max - min > 0 ? max - min : 0), a float subtraction; snrCount = 0, currentBeacon = it, min = 0, max = -1000,
+ *     count++, and count > 18 gives count = 0, changeBandFlag = true.  The firmware's quirks stay: the slot that ended is
+ *     booked under the beacon that just began, the call that sees the change has already entered min / max, and a slot
+ *     of exactly 23 calls reads as noise.
+ *   count == 0 && !changeBandFlag: on GetBeaconNow(band) != currentBeacon count++ (currentBeacon stays).
+ *   mode 0 is this cycle: 18 records, then the walk over the four other bands and a wait for the next change -- with
+ *     one monitored band it loses the slots the firmware loses.  mode 1 is continuous: count is held at 1 once the first
+ *     change has been seen, so every later change records; everything else is identical.
+ * Switching on is the unsynced branch (Beacon.cpp:610-614) at the panadapter's n: currentBeacon = slot(n), count = 0,
+ *   changeBandFlag = true, band = the channel's, min = 0, max = -1000, snrCount = 0, and a table of zeros (BeaconInit()).
+ *   t41rx_reset() does the same at n = 0.  t41rx_set_state() leaves the stage alone.
+ * t41rx_set_beacon(): band: host array of n_channels entries, copied.  d_snr: device float [n_channels][18], the channel's
+ *   column beaconSNR[.][band]; written by the stage only, it persists across calls (zeroed at switch-on and reset).
+ *   d_events: device int32 [n_channels][max_rows][4], 16-byte aligned, or NULL: per row {beacon recorded or -1, snrCount as
+ *   the call compared it (before a record clears it), count behind the call, band behind the call}; a call with k rows
+ *   writes records 0 .. k-1.  on = 0 switches the stage off (the other arguments are ignored).  T41RX_ERR_ARG, nothing
+ *   changed: a band outside 0..4, a mode outside 0..1, a NULL band, a NULL or unaligned d_snr, an unaligned d_events,
+ *   max_rows smaller than the panadapter's.  T41RX_ERR_UNSUPPORTED: the panadapter stage off, or on without an smeter
+ *   buffer.  While the stage is on, t41rx_set_panadapter() refuses to switch the panadapter off or on again without
+ *   smeter (T41RX_ERR_UNSUPPORTED) or with more max_rows than the stage's (T41RX_ERR_ARG).  Synchronises.
+ * t41rx_get_beacon(): 1 / 0 = the stage is on / off (negative: an error status).  On: synchronises and copies the table
+ *   [n_channels][18] and the status [n_channels][8] int32 {min as float bits, max as float bits, snrCount, count,
+ *   changeBandFlag, currentBeacon, band, the channel's band} to host arrays; either may be NULL.
+ * The stage's record is t41rx_beacon_state_bytes() / _get_state / _set_state: a header of 8 int32 {magic "T41B", ABI,
+ *   n_channels, words per channel = 26, 0, 0, 0, 0}, then per channel the 8 status words and snr[18].  Both need the stage
+ *   on (T41RX_ERR_STATE otherwise); _set_state refuses (T41RX_ERR_STATE, nothing written) another size or header, a
+ *   negative snrCount, count outside 0..18, changeBandFlag outside 0 / 1, currentBeacon outside 0..17, a band outside
+ *   0..4, and a channel that listens (count > 0 or changeBandFlag 0) on a band that is not its own.  The record's bands
+ *   replace t41rx_set_beacon()'s; mode, clock and buffers are configuration and stay.
+ * DisplayBeacons(), DisplayBeaconsSNR() and T41BeaconSendData(), the maps and bearings, and BeaconInit() / BeaconExit()'s
+ *   retuning and 500 .. 1500 Hz filter (FLoCut / FHiCut of the params) stay with the caller. */
+#define T41RX_BEACON_COUNT 18
+#define T41RX_BEACON_BANDS 5
+#define T41RX_BEACON_STATUS_WORDS 8
+T41RX_API int t41rx_set_beacon(t41rx_ctx *ctx, int on, int mode, const int32_t *band, float *d_snr, int32_t *d_events, int max_rows);
+T41RX_API int t41rx_set_beacon_clock(t41rx_ctx *ctx, int32_t t0_ms, int32_t num, int32_t den);
+T41RX_API int t41rx_get_beacon(t41rx_ctx *ctx, float *snr, int32_t *status);
+T41RX_API size_t t41rx_beacon_state_bytes(const t41rx_ctx *ctx);
+T41RX_API int t41rx_beacon_get_state(t41rx_ctx *ctx, void *host_buf, size_t bytes);
+T41RX_API int t41rx_beacon_set_state(t41rx_ctx *ctx, const void *host_buf, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

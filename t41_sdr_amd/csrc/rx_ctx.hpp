@@ -1,8 +1,9 @@
 // t41_sdr_amd/csrc/rx_ctx.hpp -- the receive context (struct t41rx_ctx) and what the host files of the receive side share.
 // Private to them: rx_host.cpp (the core and the process call), rx_state.cpp (checkpoints and reset) and one file per
-// stage family -- rx_audio.cpp, rx_cw.cpp, rx_ft8.cpp, rx_ft8_decode.cpp, rx_display.cpp, rx_cal.cpp.  Each stage family
-// holds its part of the context in a struct of its own below, and exports the few functions the process call and the
-// checkpoint table name.  No kernel is compiled into a host file: they see the kernels through the *_kernels.hpp headers.
+// stage family -- rx_audio.cpp, rx_cw.cpp, rx_ft8.cpp, rx_ft8_decode.cpp, rx_display.cpp, rx_beacon.cpp, rx_cal.cpp.  Each
+// stage family holds its part of the context in a struct of its own below, and exports the few functions the process
+// call and the checkpoint table name.  No kernel is compiled into a host file: they see the kernels through the
+// *_kernels.hpp headers.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "beacon_kernels.hpp"
 #include "cw_kernels.hpp"
 #include "dev_buf.hpp"
 #include "eq_kernels.hpp"
@@ -147,6 +149,20 @@ struct Panadapter {
   DevBuf<float> d_gc, d_pre, d_max, d_mem;
 };
 
+// the beacon monitor behind the panadapter (BeaconLoop(), Beacon.cpp:455-569; t41rx_set_beacon / _beacon_clock): the
+// switch with the caller's table and event buffers, the mode, the channels' bands (host copy, for t41rx_reset()), the
+// clock, and BeaconLoop()'s statics per channel [nchan][kBeaconWords] (beacon_kernels.hpp).  The context's own: no
+// checkpoint section (its record is t41rx_beacon_get_state / _set_state).  It runs in the calls that wrote panadapter rows.
+struct BeaconStage {
+  bool on = false;
+  int mode = 0, max_rows = 0;
+  float *snr = nullptr;       // [nchan][18]
+  int32_t *events = nullptr;  // [nchan][max_rows][4], or null
+  std::vector<int32_t> band;  // [nchan]
+  StageClock clock;
+  DevBuf<int32_t> d_state;
+};
+
 // IQ calibration (ProcessIQData2() / PlotCalSpectrum(), Process2.cpp:352-397, 478-547; t41rx_set_calibration): its
 // settings, a correction candidate per channel, and the calibration memory [nchan][kCalFloats] (cal_kernel.hip),
 // allocated when calibration is first configured.  The context's own: no checkpoint section, no audio-path kernel
@@ -200,6 +216,7 @@ struct t41rx_ctx {
   t41::Ft8Decode ft8d;
   t41::DisplayTap disp;
   t41::Panadapter pan;
+  t41::BeaconStage beacon;
   t41::Calibration cal;
   t41::Staging staging;
 };
@@ -292,6 +309,10 @@ int display_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
 int pan_prepare(t41rx_ctx *ctx, int n_frames);  // which frames of the call are update frames, and the stage's refusals
 int pan_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
 int pan_reset(t41rx_ctx *ctx);
+// rx_beacon.cpp
+int beacon_prepare(t41rx_ctx *ctx);  // the call's refusals, once pan_prepare() has counted its rows
+int beacon_run(t41rx_ctx *ctx, hipStream_t s);  // behind pan_run(), on the rows it wrote
+int beacon_reset(t41rx_ctx *ctx);  // behind pan_reset(): switch-on again at frame 0
 // rx_cal.cpp
 int cal_reset(t41rx_ctx *ctx);
 

@@ -188,11 +188,16 @@ int t41rx_set_panadapter(t41rx_ctx *ctx, int on, int spectrumZoom, int currentSc
   HIP_TRY(hipDeviceSynchronize());
   Panadapter &pan = ctx->pan;
   if (!on) {
+    if (ctx->beacon.on) return fail(T41RX_ERR_UNSUPPORTED, "the beacon monitor is on and reads the panadapter's rows: switch it off first (t41rx_set_beacon)");
     pan.on = false;
     return T41RX_OK;
   }
   // every refusal in front of the first change: a refused call leaves the stage as it was
   if (!out) return fail(T41RX_ERR_ARG, "null argument");
+  if (ctx->beacon.on && !out->smeter)
+    return fail(T41RX_ERR_UNSUPPORTED, "the beacon monitor is on and reads the smeter rows: switch it off first (t41rx_set_beacon)");
+  if (ctx->beacon.on && max_rows > ctx->beacon.max_rows)
+    return fail(T41RX_ERR_ARG, "max_rows exceeds the max_rows the beacon monitor's buffers were set with");
   if (!pan.have_tables) return fail(T41RX_ERR_ARG, "panadapter: no colour table loaded (t41rx_set_panadapter_tables)");
   if (spectrumZoom < 0 || spectrumZoom > 4) return fail(T41RX_ERR_ARG, "spectrumZoom must be 0 (1x) .. 4 (16x)");
   if (currentScale < 0 || currentScale > 4) return fail(T41RX_ERR_ARG, "currentScale must be 0 .. 4");

@@ -213,6 +213,7 @@ int prepare_call(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
   int rc = T41RX_OK;
   // the panadapter stage: which frames of this call are update frames, in front of everything that allocates
   if ((rc = pan_prepare(ctx, n_frames)) != T41RX_OK) return rc;
+  if (ctx->beacon.on && (rc = beacon_prepare(ctx)) != T41RX_OK) return rc;
   if ((nr_on(ctx) && (rc = ensure_nr(ctx)) != T41RX_OK) || (ctx->nb.on && (rc = ensure_nb(ctx)) != T41RX_OK) ||
       (ctx->eq.on && (rc = ensure_eq(ctx)) != T41RX_OK) ||
       ((cw_filter_on(ctx) || cw_det_on(ctx)) && (rc = ensure_cw(ctx)) != T41RX_OK))
@@ -361,6 +362,8 @@ int launch_chain(t41rx_ctx *ctx, RxArgs a, int n_frames, hipStream_t s) {
   if (a.seg > 1) ctx->nco_sel ^= 1;  // the kernels wrote the other copy
   if (ctx->disp.spec && (rc = display_run(ctx, n_frames, s)) != T41RX_OK) return rc;
   if (ctx->pan.on && (rc = pan_run(ctx, n_frames, s)) != T41RX_OK) return rc;
+  // the beacon monitor reads the rows the panadapter wrote: a call without an update frame launches nothing for it
+  if (ctx->beacon.on && ctx->pan.last_rows > 0 && (rc = beacon_run(ctx, s)) != T41RX_OK) return rc;
   return T41RX_OK;
 }
 

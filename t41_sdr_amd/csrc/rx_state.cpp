@@ -147,8 +147,9 @@ int t41rx_reset(t41rx_ctx *ctx) {
   HIP_TRY(hipDeviceSynchronize());
   int rc = pipe_timeouts_clear(ctx);  // (and the pipelined kernels' time-out counter)
   if (rc != T41RX_OK) return rc;
-  // the memories outside the checkpoint likewise: the calibration's, the panadapter's with its frame counter
-  if ((rc = cal_reset(ctx)) != T41RX_OK || (rc = pan_reset(ctx)) != T41RX_OK) return rc;
+  // the memories outside the checkpoint likewise: the calibration's, the panadapter's with its frame counter, and the
+  // beacon monitor's behind it
+  if ((rc = cal_reset(ctx)) != T41RX_OK || (rc = pan_reset(ctx)) != T41RX_OK || (rc = beacon_reset(ctx)) != T41RX_OK) return rc;
   return reset_state(ctx);
 }
 

@@ -605,6 +605,62 @@ class RxChain:
         """the stage's frame counter (t41rx_set_panadapter_counter), n >= 0"""
         check(self._lib.t41rx_set_panadapter_counter(self._ctx, int(n)))
 
+    # -- the beacon monitor behind the panadapter ------------------------------------------------
+    def set_beacon(self, on=True, mode=0, band=None, max_rows=None):
+        """BeaconLoop()'s per-beacon SNR table as a stage behind the panadapter (Beacon.cpp:455-569; t41rx_set_beacon):
+        one BeaconLoop() call per panadapter row on the row's dbm.  band: n_channels ints 0 .. 4, the one band each
+        channel monitors.  mode 0 is the firmware's cycle, 1 records every beacon change.  on allocates and returns (snr,
+        events): float32 CUDA [n_channels, 18], the channel's column of beaconSNR, kept across calls, and int32 CUDA
+        [n_channels, max_rows, 4], per row of the last call {beacon recorded or -1, snrCount, count, band}.  max_rows:
+        None = the panadapter's.  on = False switches it off and returns None.  Needs set_panadapter() with the smeter
+        rows; set_beacon_clock() first: the switch reads the clock."""
+        if not on:
+            check(self._lib.t41rx_set_beacon(self._ctx, 0, 0, None, None, None, 0))
+            self._beacon = None
+            return None
+        b = int_table(band if band is not None else [], np.int32, (self.n_channels,),
+                      "band must be n_channels = %d int32 values, got %%r %%s" % self.n_channels)
+        if b.min() < 0 or b.max() > 4:
+            raise ValueError("band must be 0 .. 4 (20, 17, 15, 12, 10 m), got %r" % (b.tolist(),))
+        if int(mode) not in (0, 1):
+            raise ValueError("mode must be 0 (the firmware's cycle) or 1 (continuous), got %r" % (mode,))
+        if max_rows is None:
+            pan = getattr(self, "_pan", None)
+            max_rows = next(iter(pan.values())).shape[1] if pan else 1
+        if int(max_rows) < 1:
+            raise ValueError("max_rows must be >= 1")
+        return self._result_stage("_beacon", lambda ctx, on_, snr, ev, rows: self._lib.t41rx_set_beacon(ctx, on_, int(mode), ptr(b, I32P), snr, ev, rows),
+                                  on, max_rows, ("float32", 18), ("int32", None, 4))
+
+    def set_beacon_clock(self, t0_ms=0, num=32, den=3):
+        """The schedule's clock (t41rx_set_beacon_clock): slot(n) = ((t0_ms + floor(n * num / den)) // 1000 % 180) // 10 at
+        the panadapter's frame number n of a row; t0_ms in [0, 180000).  The default is one frame of 2048 samples at
+        192 kS/s.  n is the row's update frame, the first of the firmware's sweep: fold the sweep's length into t0_ms for
+        the time of its end."""
+        check(self._lib.t41rx_set_beacon_clock(self._ctx, int(t0_ms), int(num), int(den)))
+
+    def _get_beacon(self):
+        snr, st = np.zeros((self.n_channels, 18), np.float32), np.zeros((self.n_channels, 8), np.int32)
+        if not value(self._lib.t41rx_get_beacon(self._ctx, ptr(snr, F32P), ptr(st, I32P))):
+            raise ValueError("the beacon monitor is off")
+        return snr, st
+
+    def beacon_snr(self):
+        """the SNR table, float32 [n_channels, 18] (t41rx_get_beacon; synchronises): row c is beaconSNR[.][band of c]"""
+        return self._get_beacon()[0]
+
+    def beacon_status(self):
+        """BeaconLoop()'s statics, int32 [n_channels, 8] (t41rx_get_beacon; synchronises): beacon.STATUS_WORDS, min and
+        max as their floats' bits"""
+        return self._get_beacon()[1]
+
+    def beacon_state(self):
+        """the stage's record (t41rx_beacon_get_state): 8 int32 of header, then per channel 8 status words and snr[18]"""
+        return get_blob(self._lib.t41rx_beacon_get_state, self._ctx, self._lib.t41rx_beacon_state_bytes(self._ctx))
+
+    def set_beacon_state(self, buf):
+        set_blob(self._lib.t41rx_beacon_set_state, self._ctx, buf)
+
     # -- IQ calibration ----------------------------------------------------------------------
     CAL_BINS = {("rx", DEMOD_LSB): (310, 460), ("rx", DEMOD_USB): (65, 192),   # cal_bins[], Process2.cpp:429-444
                 ("tx", DEMOD_LSB): (240, 305), ("tx", DEMOD_USB): (209, 273)}
