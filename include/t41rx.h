@@ -335,6 +335,52 @@ T41RX_API int t41rx_get_buffer_layout(const t41rx_ctx *ctx);
 T41RX_API int t41rx_set_input_map(t41rx_ctx *ctx, const int32_t *stream_of_channel, int n, int n_streams);
 T41RX_API int t41rx_get_input_map(const t41rx_ctx *ctx, int32_t *stream_of_channel_out, int n);
 
+/* ---- receiver groups: parameter sets, one t41rx_params per group of channels (ABI 5) ----
+ * The receivers of one band differ in more than NCOFreq: the phone receivers are LSB at 2.8 kHz, the FT8 receiver is USB
+ * at 200..3000 Hz, the CW receivers want a few hundred hertz.  A context's own t41rx_params (t41rx_create,
+ * t41rx_set_params, t41rx_get_params, as ever) is set 0.  On top of it a context holds up to T41RX_MAX_PARAM_SETS - 1
+ * extra sets, numbered 1..K, and a table set_of_channel[n_channels].  Channel c is processed exactly as a context created
+ * with sets[set_of_channel[c]] would process it, with the same NCOFreq[c], input and history: audio, side outputs, taps
+ * and the channel's state records match bit for bit.  The sets are configuration, like the input map: state,
+ * t41rx_state_bytes() and every checkpoint section are what they are without them, the sets survive t41rx_reset and
+ * t41rx_set_state, and a checkpoint taken with sets restores into a context without.  The CW side tone folded into the
+ * oscillator follows the channel's own set.
+ *
+ * The compatibility rule (one rule; t41rx_param_sets_compatible() is it): two sets may share a context when the
+ * library picks the same kernel for both and both name the same stages.  They must have equal
+ *     fft_length, which must be 512 (the long-FFT pipeline refuses sets);
+ *     demodulator family -- USB and LSB are one family; AM, NFM and SAM one each;
+ *     AGC off (AGCMode 0) versus on (AGCMode 1..4);
+ *     nfm_demod;  xmtMode;
+ *     nrOptionSelect and ANR_notchOn, both 0 (the stages that split the chain read set 0 on the host: see below);
+ *     the classification of the first stage's gains as "plain" -- RFgain 1 and, in the modes with the IQ correction
+ *       (USB, LSB, AM, SAM), IQAmpCorrectionFactor 1 and IQPhaseCorrectionFactor 0 -- or general.
+ * Free to differ: USB / LSB; FLoCut, FHiCut; rfGainAllBands; RFgain and the IQ corrections within the general class;
+ * audioVolume; AGCMode among 1..4 and AGC_thresh; am_lpf_f0, nfmFilterBW, CWFreqShift; the NR_* numbers (unused).
+ *
+ * t41rx_set_param_sets(): sets[i] becomes set i + 1 (host array of n_sets entries, 1 <= n_sets < T41RX_MAX_PARAM_SETS);
+ *   set_of_channel is a host array of n == n_channels entries in [0, n_sets].  n_sets == 0 with both pointers NULL
+ *   removes the sets.  Everything is checked on the host before anything changes; a refused call leaves the previous sets
+ *   in place: T41RX_ERR_ARG for a wrong n, an entry out of range, n_sets beyond the cap or an invalid set (the text names
+ *   it), T41RX_ERR_UNSUPPORTED with the reason for a set the rule refuses against set 0 or another set, at a long
+ *   fft_length, and while a stage that splits the chain is on -- the receive equalizer, noise reduction / notch, the noise
+ *   blanker, the CW filter, the CW detector and decoder.  Those stages refuse to be switched on while sets are loaded
+ *   (T41RX_ERR_UNSUPPORTED), in the same words.  What only taps the fused chain works with sets: the audio spectrum, the
+ *   display spectrum, the panadapter and the beacon monitor behind it, FT8 receive, the stage taps.  The calibration calls
+ *   keep reading the context's own parameters.  Synchronises the device, then uploads: the sets hold from the next
+ *   process call on.
+ * t41rx_set_params() changes set 0 and is refused (T41RX_ERR_UNSUPPORTED) if it would break the rule against a loaded
+ *   set; t41rx_set_coeffs() applies to set 0 and is held to the same rule through the blob's embedded parameters;
+ *   t41rx_get_coeffs() returns set 0's blob.
+ * t41rx_get_param_sets(): returns K, the number of extra sets (0: none; negative: an error status).  sets_out (cap
+ *   entries, cap >= K) and set_of_channel_out (n == n_channels entries) receive them; either may be NULL.
+ * t41rx_param_sets_compatible(): the rule on two parameter structs, on the host, without a context: T41RX_OK, or
+ *   T41RX_ERR_UNSUPPORTED with the clause in t41rx_last_error() (T41RX_ERR_ARG for NULL or an invalid struct). */
+#define T41RX_MAX_PARAM_SETS 64
+T41RX_API int t41rx_set_param_sets(t41rx_ctx *ctx, const t41rx_params *sets, int n_sets, const int32_t *set_of_channel, int n);
+T41RX_API int t41rx_get_param_sets(const t41rx_ctx *ctx, t41rx_params *sets_out, int cap, int32_t *set_of_channel_out, int n);
+T41RX_API int t41rx_param_sets_compatible(const t41rx_params *a, const t41rx_params *b);
+
 /* ---- the hot path: ProcessIQData() on every channel ----
  * Device-pointer form: dI, dQ, dAudio are device pointers ([n_channels][n_frames*frame_len], or time-major:
  * t41rx_set_buffer_layout; with an input map dI / dQ hold n_streams rows: t41rx_set_input_map);

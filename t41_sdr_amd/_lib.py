@@ -90,6 +90,9 @@ SYMBOLS = {
     "t41rx_get_buffer_layout": (C.c_int, [_vp]),
     "t41rx_set_input_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int, C.c_int]),
     "t41rx_get_input_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int]),
+    "t41rx_set_param_sets": (C.c_int, [_vp, C.POINTER(Params), C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "t41rx_get_param_sets": (C.c_int, [_vp, C.POINTER(Params), C.c_int, C.POINTER(C.c_int32), C.c_int]),
+    "t41rx_param_sets_compatible": (C.c_int, [C.POINTER(Params), C.POINTER(Params)]),
     "t41rx_process_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
     "t41rx_process_host": (C.c_int, [_vp, _fp, _fp, _fp, C.c_int]),
     "t41rx_set_audio_spectrum": (C.c_int, [_vp, _vp, _vp, C.c_int]),

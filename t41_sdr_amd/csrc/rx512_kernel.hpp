@@ -88,13 +88,24 @@ static_assert(!Geo<0>::kResident || (Geo<0>::kH1 + 24 <= Geo<0>::kSlice && Geo<0
 // unmapped instantiations keep the template arguments, and with them the names, they had before the map existed, and the
 // kernel stays one function: a shared body inlined into two kernels compiles the unmapped ones to other instruction
 // streams (commuted operands, a few instructions moved), which the product's kernels are not to have.
+// SET (receiver groups, t41rx_set_param_sets): the channel takes its constants -- coefficient block, filter mask, AM scan
+// constants, the first stage's gains -- from parameter set a.set_of[ch] instead of the context's one set.  Where a wave
+// takes its constants from, and nothing else: the arithmetic is the instantiation's.  It rides on PARTM like the map, and
+// exists only as a twin of the mapped form (PART + kPartMap + kPartSet): a context with sets and no input map runs with
+// an identity map.  Three things follow from channels of different sets sharing a workgroup:
+//   * the mask comes from the set's global table in every set form, also where the plain form reads the workgroup's LDS copy;
+//   * a wave that runs a serial chain for other waves' channels takes the constants of the channel it serves (CoefBySet);
+//   * cf0, the pointer every fresh_coef() / load_taps() site re-derives from, is the set's block.
 constexpr int kPartMap = 4;
+constexpr int kPartSet = 8;
 template <int MODE, bool DEBUG, int PARTM, bool PLAIN, bool AGC = false, bool WQ15 = false, bool SEGPAR = false, bool PIPE = false>
 __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 64), 4) void rx512_kernel(const RxArgs a) {
   T41RX_CLK_BEGIN();
   constexpr int PART = PARTM & 3;
   constexpr bool MAP = (PARTM & kPartMap) != 0;
-  static_assert(PART <= 2 && (PARTM & ~(3 | kPartMap)) == 0, "PARTM = PART, or PART + kPartMap");
+  constexpr bool SET = (PARTM & kPartSet) != 0;
+  static_assert(PART <= 2 && (PARTM & ~(3 | kPartMap | kPartSet)) == 0, "PARTM = PART, PART + kPartMap, or PART + kPartMap + kPartSet");
+  static_assert(!SET || (MAP && PART == 0 && !SEGPAR), "the set form is a twin of the mapped FFT_LENGTH 512 kernels");
   static_assert(!MAP || PART != 2, "the back end of the long-FFT pipeline reads no antenna samples");
   static_assert(!SEGPAR || (PART == 1 && MODE != kModeNfm) || (PART == 2 && MODE == kModeSsb && !AGC), "SEGPAR variants");
   static_assert(!PIPE || ((AGC || MODE == kModeSam) && PART == 0 && !DEBUG && !SEGPAR),
@@ -175,12 +186,29 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
   // coefficients are read-only for the kernel: constant address space -> scalar (SMEM) loads,
   // re-derived through an opaque asm per phase so the compiler keeps the tap loads next to
   // their use instead of hoisting all 180 of them (and spilling SGPRs).
-  const CoefPtr cf0 = (CoefPtr)a.coef;
+  // SET: the channel's parameter set.  Wave-uniform and read-only like the map entry below: one scalar load per wave
+  typedef const __attribute__((address_space(4))) int *MapPtr;
+  const int pset = SET ? ((MapPtr)a.set_of)[ch] : 0;
+  const CoefPtr cf0 = SET ? (CoefPtr)a.coef + pset : (CoefPtr)a.coef;
   const NcoPtr nco = (NcoPtr)(a.nco + ch);
   const float2 *__restrict__ tab = a.tab;
+  // the set's own table for what depends on the parameters (kTabMask, kTabAm); the rest is read from set 0's, which
+  // every wave of the chip shares
+  const float2 *__restrict__ ptab = SET ? a.tab + (size_t)pset * kTabEntries512 : a.tab;
+  // whose constants the serial chains this wave may run for the workgroup's channels take (rx_device.hpp)
+  const auto chain_coef = [&]() {
+    if constexpr (SET) return CoefBySet{a.coef, a.set_of + NW * (int)blockIdx.x};
+    else return CoefOwn{cf0};
+  }();
+  // SET: the first stage's gains of the channel's set, in place of the five words RxArgs carries for set 0
+  typedef const __attribute__((address_space(4))) SetGains *GainPtr;
+  SetGains sg{};
+  if (SET) {
+    const GainPtr gp = (GainPtr)a.set_gain + pset;
+    sg.g_rf = gp->g_rf, sg.g_band = gp->g_band, sg.neg_iq_amp = gp->neg_iq_amp, sg.iq_phase = gp->iq_phase, sg.iq_corr_on = gp->iq_corr_on;
+  }
   // MAP: the row of I / Q this channel reads.  ch is wave-uniform and the map read-only: one scalar load per wave, not one
   // per frame; the host has checked the entry (t41rx_set_input_map), the kernel does not
-  typedef const __attribute__((address_space(4))) int *MapPtr;
   const int strm = MAP ? ((MapPtr)a.in_map)[ch] : ch;
 
   // per-channel NCO constants and state (wave-uniform).  Only the LOADS are issued here; the
@@ -411,17 +439,18 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
       float g_rf, g_rf_i, g_hp, g_hp_i, iq_phase_neg = 0.0f, iq_phase_pos = 0.0f;
       f2 g_iq = splat(1.0f);
       {
-        g_rf = a.g_rf;
+        const int iq_corr_on = SET ? sg.iq_corr_on : a.iq_corr_on;
+        g_rf = SET ? sg.g_rf : a.g_rf;
         if (WQ15) g_rf *= 1.0f / 32768.0f;  // arm_q15_to_float
         // PLAIN: sign of the I path (-1 when the IQ amplitude correction applies, Process.cpp:165-173)
-        g_rf_i = (PLAIN && a.iq_corr_on) ? -g_rf : g_rf;
+        g_rf_i = (PLAIN && iq_corr_on) ? -g_rf : g_rf;
         g_hp = g_rf * (float)kHpB0;  // what the samples are multiplied by: the DC high-pass takes b0 x (dc_highpass)
-        g_hp_i = (PLAIN && a.iq_corr_on) ? -g_hp : g_hp;
+        g_hp_i = (PLAIN && iq_corr_on) ? -g_hp : g_hp;
         if (!PLAIN) {
-          const float gb = a.g_band;
-          const bool iq_on = a.iq_corr_on != 0;
-          g_iq = f2{iq_on ? gb * a.neg_iq_amp : gb, gb};
-          const float ph = iq_on ? a.iq_phase : 0.0f;
+          const float gb = SET ? sg.g_band : a.g_band;
+          const bool iq_on = iq_corr_on != 0;
+          g_iq = f2{iq_on ? gb * (SET ? sg.neg_iq_amp : a.neg_iq_amp) : gb, gb};
+          const float ph = iq_on ? (SET ? sg.iq_phase : a.iq_phase) : 0.0f;
           iq_phase_neg = ph < 0.0f ? ph : 0.0f;
           iq_phase_pos = ph > 0.0f ? ph : 0.0f;
         }
@@ -1063,6 +1092,16 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
         cf tw1[7], tw2[7];
         cf mk[8];  // KEEP: FIR_filter_mask[lane + 64 r] / N, requested from the L2-resident table inside the forward FFT
         constexpr bool GMASK = KEEP || MODE == kModeSam;  // (on the 4-wave geometry, measured: +1.2 .. 2.5 % against mask and twiddles in LDS / registers)
+        // SET on the geometry that stages the mask in LDS: the workgroup's four channels may be of four sets, so the mask
+        // comes from the set's global table here too, requested ahead of the forward FFT; the twiddles stay where they are
+        constexpr bool SMASK = SET && !GMASK;
+        if (SMASK) {
+  #pragma unroll
+          for (int r = 0; r < 8; ++r) {
+            const float2 t = ptab[kTabMask + 64 * r + lane];
+            mk[r] = cf{t.x, t.y};
+          }
+        }
         if (!GMASK) {
   #pragma unroll
           for (int q = 0; q < 7; ++q) {
@@ -1074,7 +1113,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
           fft512_ldstw<false>(v, ltab + G::kTw1 + lane, ltab + G::kTw2 + (lane & 7), lds + kScr, lane, [&]() {
   #pragma unroll
             for (int r = 0; r < 8; ++r) {
-              const float2 t = tab[kTabMask + 64 * r + lane];
+              const float2 t = ptab[kTabMask + 64 * r + lane];
               mk[r] = cf{t.x, t.y};
             }
           });
@@ -1082,7 +1121,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
           fft512<false>(v, tw1, tw2, lds + kScr, lane);
         }
   #pragma unroll
-        for (int r = 0; r < 8; ++r) v[r] = cmul(v[r], GMASK ? mk[r] : ltab[kLdsTabMask + 64 * r + lane]);
+        for (int r = 0; r < 8; ++r) v[r] = cmul(v[r], (GMASK || SMASK) ? mk[r] : ltab[kLdsTabMask + 64 * r + lane]);
         if (DEBUG && a.spect_max && tap_row >= 0) {
           // ---- audio spectrum side output (Process.cpp:550-570 with updateDisplayFlag == 1):
           // audioSpectBuffer[1023 - k] = iFFT_buffer[k]^2 over the 1024 floats of the masked
@@ -1165,7 +1204,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
             PRIO(3);
             unsigned long long *pipe_stat = reinterpret_cast<unsigned long long *>(a.agc_pipe + (size_t)a.nchan * kPipeSlots * kPipeSlotFloats) + (size_t)job * 16;
             agc_chain_pipe(a.agc_pipe + (ch0 * kPipeSlots + g % kPipeSlots) * kPipeSlotFloats, a.state + ch0 * state_stride + st_agc(512) + kAgcHistFloats,
-                           state_stride, lds + kScr, fa + 3, (unsigned)g, nvalid, cf0, lane, pipe_stat, pipe_err);
+                           state_stride, lds + kScr, fa + 3, (unsigned)g, nvalid, chain_coef, lane, pipe_stat, pipe_err);
             PRIO(1);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             if (lane == 0) __hip_atomic_store(fa + 3, (unsigned)(g + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1194,7 +1233,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
             if (lane == 0) __hip_atomic_store(fs + g % kPipeSlots, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             PRIO(3);
             sam_chain_pipe(sam_slots + (ch0 * kPipeSlots + g % kPipeSlots) * kPipeSlotFloats, a.state + ch0 * state_stride + kStMisc, state_stride,
-                           lds + kScr, reinterpret_cast<const float *>(a.tab + kTabSam), fs + 3, (unsigned)g, nvalid, cf0, lane, pipe_err);
+                           lds + kScr, reinterpret_cast<const float *>(a.tab + kTabSam), fs + 3, (unsigned)g, nvalid, chain_coef, lane, pipe_err);
             PRIO(1);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             if (lane == 0) __hip_atomic_store(fs + 3, (unsigned)(g + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1279,10 +1318,10 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
                         "chain staging: 16 channels, inside the X scratch");
           if (PSAM)
             sam_chain_pipe(a.agc_pipe + (ch0 * kPipeSlots + g % kPipeSlots) * kPipeSlotFloats, a.state + ch0 * state_stride + kStMisc, state_stride,
-                           lds + kScr, reinterpret_cast<const float *>(a.tab + kTabSam), flags + 3, (unsigned)g, nvalid, cf0, lane, pipe_err);
+                           lds + kScr, reinterpret_cast<const float *>(a.tab + kTabSam), flags + 3, (unsigned)g, nvalid, chain_coef, lane, pipe_err);
           else
             agc_chain_pipe(a.agc_pipe + (ch0 * kPipeSlots + g % kPipeSlots) * kPipeSlotFloats, a.state + ch0 * state_stride + st_agc(512) + kAgcHistFloats,
-                           state_stride, lds + kScr, flags + 3, (unsigned)g, nvalid, cf0, lane, pipe_stat, pipe_err);
+                           state_stride, lds + kScr, flags + 3, (unsigned)g, nvalid, chain_coef, lane, pipe_stat, pipe_err);
           PRIO(1);
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
           if (lane == 0) __hip_atomic_store(flags + 3, (unsigned)(g + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1306,7 +1345,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
         if (KEEP) hist2 = hist2c;
       } else if (AGC) {
         const int left = a.nchan - NW * (int)blockIdx.x;
-        agc_apply<AgcLds<KEEP>, NW, G::kSlice>(v, agst, lds, smem + G::kTab, st + st_agc(512 * seg), cf0, lane, wv,
+        agc_apply<AgcLds<KEEP>, NW, G::kSlice>(v, agst, lds, smem + G::kTab, st + st_agc(512 * seg), cf0, chain_coef, lane, wv,
                                                left < NW ? left : NW, og STAMP_ARGS);
       }
       if (PSAM || PSA) {
@@ -1329,7 +1368,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
           PRIO(3);  // the frame's critical path, one dependent instruction at a time
           const int c = (nvalid == NW) ? (lane & (NW - 1)) : lane % nvalid;
           sam_chain(smem + G::kTab + c * G::kSlice, smem, a.state + (size_t)(NW * (int)blockIdx.x + c) * state_stride + kStMisc,
-                    cf0, lane < nvalid);
+                    chain_coef, c, lane < nvalid);
           PRIO(1);
         }
         __syncthreads();
@@ -1379,7 +1418,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
         {
           const double a4 = ca * ca * ca * ca, a8 = a4 * a4, a16 = a8 * a8, a32 = a16 * a16;
           // ca^(4 ((lane&15)+1)), ca^(4 ((lane&31)+1)): per-lane constants from the table
-          const double2 pw = *reinterpret_cast<const double2 *>(tab + kTabAm + 6 * lane);
+          const double2 pw = *reinterpret_cast<const double2 *>(ptab + kTabAm + 6 * lane);
           const double p15 = pw.x, p31 = pw.y;
           B = fma(a4, dpp_d<kDppRowShr1, 0xf, true>(B), B);
           B = fma(a8, dpp_d<kDppRowShr2, 0xf, true>(B), B);
@@ -1432,8 +1471,8 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
           const M2 Mq = mm(M, M);
           const M2 P1 = mm(Mq, Mq), P2 = mm(P1, P1), P4 = mm(P2, P2), P8 = mm(P4, P4);
           // (M^4)^((lane&15)+1), (M^4)^((lane&31)+1): per-lane constants from the table
-          const float4 q15t = *reinterpret_cast<const float4 *>(tab + kTabAm + 6 * lane + 2);
-          const float4 q31t = *reinterpret_cast<const float4 *>(tab + kTabAm + 6 * lane + 4);
+          const float4 q15t = *reinterpret_cast<const float4 *>(ptab + kTabAm + 6 * lane + 2);
+          const float4 q31t = *reinterpret_cast<const float4 *>(ptab + kTabAm + 6 * lane + 4);
           const M2 Q15{q15t.x, q15t.y, q15t.z, q15t.w}, Q31{q31t.x, q31t.y, q31t.z, q31t.w};
           auto step = [&](M2 P, float o1, float o2) {
             s1 = s1 + P.a * o1 + P.b * o2;

@@ -14,12 +14,15 @@ namespace t41 {
 // frames of the launch.  Everything else: 4-wave workgroups (see Geo).
 // MAP: the call carries an input map (RxArgs::in_map, receiver groups) -- the same instantiation in its mapped form
 // (PART + kPartMap), same geometry.
-template <int MODE, bool DEBUG, int PART, bool PLAIN, bool AGC, bool WQ15, bool SEGPAR = false, bool PIPE = false, bool MAP = false>
+// SET: the call carries parameter sets (RxArgs::set_of, t41rx_set_param_sets) -- the mapped form's twin that takes a
+// channel's constants from its set (PART + kPartMap + kPartSet), same geometry.
+template <int MODE, bool DEBUG, int PART, bool PLAIN, bool AGC, bool WQ15, bool SEGPAR = false, bool PIPE = false, bool MAP = false, bool SET = false>
 static hipError_t launch_rx512(const RxArgs &a, hipStream_t s) {
+  static_assert(!SET || MAP, "the set form exists as a twin of the mapped form only");
   constexpr size_t NW = Rx512Geo<MODE, PART, AGC, PIPE>::kWaves;
   const size_t runs = SEGPAR ? (size_t)((a.nframes + a.seg_run - 1) / a.seg_run) : 1;
   const size_t jobs = (size_t)a.nchan * runs;
-  hipLaunchKernelGGL((rx512_kernel<MODE, DEBUG, PART + (MAP ? kPartMap : 0), PLAIN, AGC, WQ15, SEGPAR, PIPE>),
+  hipLaunchKernelGGL((rx512_kernel<MODE, DEBUG, PART + (MAP ? kPartMap : 0) + (SET ? kPartSet : 0), PLAIN, AGC, WQ15, SEGPAR, PIPE>),
                      dim3((unsigned)((jobs + NW - 1) / NW)), dim3(NW * 64), 0, s, a);
   return hipGetLastError();
 }
@@ -34,14 +37,17 @@ static hipError_t launch512(const RxArgs &a, hipStream_t s, bool debug) {
   // calls have nothing to overlap and take the barrier form, which computes the same values
   const bool pipe = (a.agc || SAM) && a.agc_pipe && !debug && a.nframes >= 4;
   // an input map changes none of the rules above: a mapped call takes the instantiation the same call would take without
-  // the map, in its mapped form, and a call without a map never reaches a mapped one
+  // the map, in its mapped form, and a call without a map never reaches a mapped one.  Parameter sets likewise: the
+  // host has made sure that every set answers the rules above alike (t41rx_param_sets_compatible) and passes an input
+  // map with them, so the call takes the set twin of the mapped instantiation; a call without sets never reaches one
+  if (a.set_of != nullptr && (a.in_map == nullptr || a.set_gain == nullptr)) return hipErrorInvalidValue;
   return with_bools(
-      [&](auto DBG, auto PLN, auto AGC, auto Q15, auto PIPE, auto MAP) {
+      [&](auto DBG, auto PLN, auto AGC, auto Q15, auto PIPE, auto MAP, auto SET) {
         // what the rules above never select is not compiled
-        if constexpr ((DBG && (PLN || PIPE)) || (PLN && SAM) || (PIPE && !(AGC || SAM))) return hipErrorInvalidValue;
-        else return launch_rx512<MODE, DBG, 0, PLN, AGC, Q15, false, PIPE, MAP>(a, s);
+        if constexpr ((DBG && (PLN || PIPE)) || (PLN && SAM) || (PIPE && !(AGC || SAM)) || (SET && !MAP)) return hipErrorInvalidValue;
+        else return launch_rx512<MODE, DBG, 0, PLN, AGC, Q15, false, PIPE, MAP, SET>(a, s);
       },
-      debug, plain, a.agc != 0, a.q15 != 0, pipe, a.in_map != nullptr);
+      debug, plain, a.agc != 0, a.q15 != 0, pipe, a.in_map != nullptr, a.set_of != nullptr);
 }
 
 }  // namespace t41

@@ -168,6 +168,7 @@ int t41rx_set_noise_blanker(t41rx_ctx *ctx, int NB_on) {
   if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
   if (NB_on != 0 && NB_on != 1) return fail(T41RX_ERR_ARG, "NB_on must be 0 or 1");
   if (NB_on && ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the noise blanker is built for fft_length 512");
+  if (NB_on && sets_loaded(ctx)) return sets_refuse_stage("the noise blanker");
   ctx->nb.on = NB_on;
   return T41RX_OK;
 }
@@ -189,6 +190,7 @@ int t41rx_set_receive_eq(t41rx_ctx *ctx, int receiveEQFlag, const int32_t *equal
     return fail(T41RX_ERR_UNSUPPORTED, "the receive equalizer is built for fft_length 512");
   if (receiveEQFlag && !ctx->eq.have_bands)
     return fail(T41RX_ERR_ARG, "receive equalizer: no band table loaded (t41rx_set_receive_eq_bands)");
+  if (receiveEQFlag && sets_loaded(ctx)) return sets_refuse_stage("the receive equalizer");
   if (equalizerRec) std::memcpy(ctx->eq.levels, equalizerRec, sizeof(ctx->eq.levels));
   ctx->eq.on = receiveEQFlag;
   return T41RX_OK;

@@ -503,8 +503,9 @@ struct SamPll {
     S = (1.0f - is.fract) * sa + is.fract * sb;
     C = (1.0f - ic.fract) * ca + ic.fract * cb;
   }
-  __device__ __forceinline__ void load(const float *Tab, const float *ms, CoefPtr cf0) {
-    const CoefPtr c = fresh_coef(cf0);
+  template <typename SRC>
+  __device__ __forceinline__ void load(const float *Tab, const float *ms, const SRC &src, int ch) {  // ch: the channel the lane serves (CoefOwn / CoefBySet)
+    const auto c = src.of(ch);
     T = Tab;
     omega_min = c->sc[kScSamWmin], omega_max = c->sc[kScSamWmax], g1 = c->sc[kScSamG1], g2 = c->sc[kScSamG2];
     phzerror = ms[kMiscSamPhz], fil_out = ms[kMiscSamFil], omega2 = ms[kMiscSamOmega];
@@ -543,9 +544,10 @@ struct SamPll {
   }
 };
 // zs = the channel's 256 complex samples (audio replaces the real parts), T = arm_sin_f32's table in LDS, ms = the channel's kStMisc words
-__device__ __forceinline__ void sam_chain(float *zs, const float *T, float *ms, CoefPtr cf0, bool store) {
+template <typename SRC>
+__device__ __forceinline__ void sam_chain(float *zs, const float *T, float *ms, const SRC &src, int ch, bool store) {
   SamPll pll;
-  pll.load(T, ms, cf0);
+  pll.load(T, ms, src, ch);
   cf zn = *reinterpret_cast<const cf *>(zs);
   for (int i = 0; i < 256; ++i) {
     const cf z = zn;
@@ -555,10 +557,10 @@ __device__ __forceinline__ void sam_chain(float *zs, const float *T, float *ms, 
   if (store) pll.store(ms);
 }
 
-template <typename AL>
-__device__ __forceinline__ void agc_chain(float *sl, CoefPtr cf0, int lane STAMP_PARAMS) {
+template <typename AL, typename SRC>
+__device__ __forceinline__ void agc_chain(float *sl, const SRC &src, int ch, int lane STAMP_PARAMS) {
   constexpr int kAgR = AL::R, kAgS = AL::S;
-  const CoefPtr c = fresh_coef(cf0);
+  const auto c = src.of(ch);
   AgcConsts g;
   g.attack_mult = c->agc[kAgcAttackMult];
   g.decay_mult = c->agc[kAgcDecayMult];
@@ -626,9 +628,10 @@ __device__ __forceinline__ float agc_group_max(const float *p) {
 // float4 of the channel's AGC record (lanes 0..49 delay line, 50..51 state words).
 // og[k] = AGC output sample 4 lane + k.
 // slices: the first wave slice of the workgroup, NW / SLICE: waves per workgroup / floats per slice.
-template <typename AL, int NW, int SLICE>
+// cf0: the wave's own channel's constants; src: those of the channels whose chains wave 0 runs
+template <typename AL, int NW, int SLICE, typename SRC>
 __device__ __forceinline__ void agc_apply(const cf (&v)[8], float4 agst, float *lds, float *slices, float *st_ag,
-                                          CoefPtr cf0, int lane, int wv, int nvalid, cf (&og)[4] STAMP_PARAMS) {
+                                          CoefPtr cf0, const SRC &src, int lane, int wv, int nvalid, cf (&og)[4] STAMP_PARAMS) {
   constexpr int kAgZ = AL::Z, kAgA = AL::A, kAgG = AL::G, kAgR = AL::R, kAgS = AL::S;
   wave_sync();
   if (lane < 50) *reinterpret_cast<float4 *>(lds + kAgZ + 4 * lane) = agst;
@@ -689,7 +692,8 @@ __device__ __forceinline__ void agc_apply(const cf (&v)[8], float4 agst, float *
     // phases of the other workgroups' waves on its SIMD (51 k cycles per frame, stamps).
     if (wv == cw) {
       PRIO(3);
-      agc_chain<AL>(slices + (nvalid == NW ? (lane & (NW - 1)) : lane % nvalid) * SLICE, cf0, lane STAMP_ARGS);
+      const int c = nvalid == NW ? (lane & (NW - 1)) : lane % nvalid;
+      agc_chain<AL>(slices + c * SLICE, src, c, lane STAMP_ARGS);
       PRIO(1);
     }
     STAMP(21);  // AGC: the serial chain (chain wave only)
@@ -859,9 +863,10 @@ constexpr int kPipeAhead = 2;
 // block of every chunk did, ~185 cycles behind fifteen other waves' LDS traffic); the chunk's volts never touch the stage
 // (see `keep`).  Chunk k + 1 is written at the top of chunk k and read a chunk later: the LDS unit executes one wave's
 // instructions in order, the compiler is held by wave_sync().
+template <typename SRC>
 __device__ __forceinline__ void agc_chain_pipe(float *grp, float *stw0, size_t stride, float *stage, const unsigned *done, unsigned g,
-                                               int nvalid, CoefPtr cf0, int lane, unsigned long long *pipe_stat, unsigned *err) {
-  const CoefPtr c = fresh_coef(cf0);
+                                               int nvalid, const SRC &src, int lane, unsigned long long *pipe_stat, unsigned *err) {
+  const auto c = src.of((nvalid == 16) ? (lane & 15) : (lane & 15) % nvalid);  // (the lane's channel, `ch` below)
   AgcConsts gc;
   gc.attack_mult = c->agc[kAgcAttackMult];
   gc.decay_mult = c->agc[kAgcDecayMult];
@@ -1053,8 +1058,9 @@ __device__ __forceinline__ void sam_prep_pipe(const cf (&v)[8], float fixed_gain
   for (int j = 0; j < 4; ++j) *reinterpret_cast<cf *>(slot + 2 * (lane + 64 * j)) = v[4 + j] * splat(fixed_gain);
 }
 //   grp : slot (frame g) of the workgroup's first channel; ms0 : its kStMisc words, channel c's stride floats further
+template <typename SRC>
 __device__ __forceinline__ void sam_chain_pipe(float *grp, float *ms0, size_t stride, float *stage, const float *tab, const unsigned *done,
-                                               unsigned g, int nvalid, CoefPtr cf0, int lane, unsigned *err) {
+                                               unsigned g, int nvalid, const SRC &src, int lane, unsigned *err) {
   const int ch = (nvalid == 16) ? (lane & 15) : (lane & 15) % nvalid;
   const int q = lane >> 4;
   float *gsrc = grp + (size_t)ch * (kPipeSlots * kPipeSlotFloats);
@@ -1072,7 +1078,7 @@ __device__ __forceinline__ void sam_chain_pipe(float *grp, float *ms0, size_t st
   wave_sync();
   float *ms = ms0 + (size_t)ch * stride;
   SamPll pll;
-  pll.load(stage, ms, cf0);
+  pll.load(stage, ms, src, ch);
 #pragma nounroll
   for (int k = 0; k < 16; ++k) {
     {

@@ -1,6 +1,7 @@
 // t41_sdr_amd/csrc/rx_ctx.hpp -- the receive context (struct t41rx_ctx) and what the host files of the receive side share.
 // Private to them: rx_host.cpp (the core and the process call), rx_state.cpp (checkpoints and reset) and one file per
-// stage family -- rx_audio.cpp, rx_cw.cpp, rx_ft8.cpp, rx_ft8_decode.cpp, rx_display.cpp, rx_beacon.cpp, rx_cal.cpp.  Each
+// stage family -- rx_audio.cpp, rx_cw.cpp, rx_ft8.cpp, rx_ft8_decode.cpp, rx_display.cpp, rx_beacon.cpp, rx_cal.cpp -- and
+// rx_sets.cpp (the parameter sets).  Each
 // stage family holds its part of the context in a struct of its own below, and exports the few functions the process
 // call and the checkpoint table name.  No kernel is compiled into a host file: they see the kernels through the
 // *_kernels.hpp headers.
@@ -174,6 +175,21 @@ struct Calibration {
   DevBuf<float> d_mem, d_corr;
 };
 
+// parameter sets (t41rx_set_param_sets; rx_sets.cpp): the extra sets 1..K with their designed blobs, the channels' table,
+// and what the set kernels read -- the coefficient blocks [K + 1], the constant tables [K + 1][kTabEntries512], the first
+// stage's gains [K + 1] (entry 0 of each is the context's own set, kept in step with d_coef / d_tab), the table, and the
+// identity input map a context with sets and no input map runs with.  Configuration like the input map: in no
+// checkpoint, untouched by reset / set_state.  K == 0: no sets, nothing allocated, the calls pass what they always passed.
+struct ParamSets {
+  std::vector<t41rx_params> params;        // [K]
+  std::vector<std::vector<float>> blobs;   // [K]
+  std::vector<int32_t> set_of;             // [nchan]
+  DevBuf<DevCoef> d_coef;
+  DevBuf<float2> d_tab;
+  DevBuf<SetGains> d_gain;
+  DevBuf<int32_t> d_set_of, d_ident;
+};
+
 // staging for t41rx_process_host
 struct Staging {
   DevBuf<float> d_in_i, d_in_q, d_out;
@@ -208,6 +224,7 @@ struct t41rx_ctx {
   int n_streams = 0;
   t41::DevBuf<int32_t> d_in_map;  // [nchan], allocated with the first map
   t41::DevBuf<double> d_win;      // the display FFT's window (ensure_window): display spectrum, panadapter, calibration
+  t41::ParamSets sets;
   t41::NrStage nr;
   t41::NbStage nb;
   t41::EqStage eq;
@@ -248,6 +265,18 @@ inline bool stages_on(const t41rx_ctx *ctx) { return ctx->eq.on || nr_on(ctx) ||
 inline bool pipe_on(const t41rx_ctx *ctx, int n_frames) {
   return (ctx->params.AGCMode != 0 || ctx->params.mode == T41RX_DEMOD_SAM) && ctx->params.fft_length == 512 && n_frames >= 4;
 }
+// parameter sets: loaded, and what a chain-splitting stage's switch answers then (those stages read set 0's parameters
+// on the host; rx_sets.cpp refuses in the other order with split_stage_on())
+inline bool sets_loaded(const t41rx_ctx *ctx) { return !ctx->sets.params.empty(); }
+inline int sets_refuse_stage(const char *stage) {
+  return fail(T41RX_ERR_UNSUPPORTED, std::string(stage) + " splits the fused chain and reads one parameter set on the host: it cannot run "
+                                         "while parameter sets are loaded (t41rx_set_param_sets); remove the sets first");
+}
+// the chain-splitting stage whose switch is on, or null (the noise reduction / notch are parameters: the sets' rule has them)
+inline const char *split_stage_on(const t41rx_ctx *ctx) {
+  return ctx->eq.on ? "the receive equalizer" : ctx->nb.on ? "the noise blanker" : ctx->cw.filter != kCwFilters ? "the CW audio filter"
+         : ctx->cw.det ? "the CW detector" : ctx->cw.dec ? "the CW decoder" : nullptr;
+}
 // rows of I / Q a process call reads: one per channel, or the input map's n_streams
 inline int input_rows(const t41rx_ctx *ctx) { return ctx->n_streams > 0 ? ctx->n_streams : ctx->nchan; }
 
@@ -265,6 +294,15 @@ int ensure_window(t41rx_ctx *ctx);
 // displayScale[] (Display.cpp:127-135): dBScale, baseOffset -- the calibration's and the panadapter's pixel mapping
 constexpr float kDbScale[5] = {10.0f, 20.0f, 40.0f, 100.0f, 200.0f};
 constexpr int kBaseOffset[5] = {24, 10, 58, 120, 200};
+// blob -> the device's coefficient block, constant table (FFT_LENGTH 512 form) and first-stage gains with their `plain`
+// classification (rx_host.cpp: what upload_coeffs() and rx_args() make of set 0, rx_sets.cpp of every set)
+void fill_dev_coef(const BlobView &v, DevCoef &dc);
+void fill_tab512(const BlobView &v, int fft_length, std::vector<float2> &tab);
+bool gains_of(const float *scalars, SetGains &g);  // returns plain
+int upload_nco(t41rx_ctx *ctx);
+// rx_sets.cpp: set 0 changed (set_params / set_coeffs) -- the rule against the loaded sets, and entry 0 of the set arrays
+int sets_check_set0(const t41rx_ctx *ctx, const t41rx_params &p);
+int sets_upload(t41rx_ctx *ctx);
 // the pipelined kernels' time-out counter (rx_host.cpp)
 int pipe_timeouts_clear(t41rx_ctx *ctx);
 int pipe_status(const t41rx_ctx *ctx);

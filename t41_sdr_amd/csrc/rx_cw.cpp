@@ -191,6 +191,7 @@ int t41rx_set_cw_filter(t41rx_ctx *ctx, int CWFilterIndex) {
   if (CWFilterIndex != kCwFilters) {
     if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the CW audio filters are built for fft_length 512");
     if (!ctx->cw.have_filters) return fail(T41RX_ERR_ARG, "CW audio filter: no filter tables loaded (t41rx_set_cw_tables)");
+    if (sets_loaded(ctx)) return sets_refuse_stage("the CW audio filter");
   }
   ctx->cw.filter = CWFilterIndex;
   return T41RX_OK;
@@ -206,6 +207,7 @@ int t41rx_set_cw_detector(t41rx_ctx *ctx, int decoderFlag, float *d_cw, int max_
     if (reinterpret_cast<uintptr_t>(d_cw) & 3u) return fail(T41RX_ERR_ARG, "unaligned pointer");
     if (max_frames <= 0) return fail(T41RX_ERR_ARG, "max_frames must be > 0");
     if (!ctx->cw.have_fir) return fail(T41RX_ERR_ARG, "CW detector: no decode FIR loaded (t41rx_set_cw_tables)");
+    if (sets_loaded(ctx)) return sets_refuse_stage("the CW detector");
   }
   ctx->cw.det = decoderFlag;
   ctx->cw.out = decoderFlag ? d_cw : nullptr;
@@ -231,6 +233,7 @@ int t41rx_set_cw_decoder(t41rx_ctx *ctx, int on, int32_t *d_text, int max_frames
     if (reinterpret_cast<uintptr_t>(d_text) & 3u) return fail(T41RX_ERR_ARG, "unaligned pointer");
     if (max_frames <= 0) return fail(T41RX_ERR_ARG, "max_frames must be > 0");
     if (!ctx->cw.have_tree) return fail(T41RX_ERR_ARG, "CW decoder: no decode tree loaded (t41rx_set_cw_decode_tree)");
+    if (sets_loaded(ctx)) return sets_refuse_stage("the CW decoder");
   }
   ctx->cw.dec = on;
   ctx->cw.text = on ? d_text : nullptr;

@@ -356,6 +356,20 @@ __device__ __forceinline__ CoefPtr fresh_coef(CoefPtr p) {
   asm volatile("" : "+s"(p));
   return p;
 }
+// Whose constants a serial chain runs with.  The wave that runs the chains of a workgroup's channels, one lane per channel
+// (agc_chain, sam_chain and their pipelined forms), does not own those channels: of(c) is the coefficient block of the
+// workgroup's channel c.  CoefOwn: one block for every channel, the wave's own scalar pointer (a context without
+// parameter sets).  CoefBySet: coef[set_of[c]], a per-lane pointer and vector loads (set_of = the table from the
+// workgroup's first channel on).
+struct CoefOwn {
+  CoefPtr p;
+  __device__ __forceinline__ CoefPtr of(int) const { return fresh_coef(p); }
+};
+struct CoefBySet {
+  const DevCoef *base;
+  const int *set_of;
+  __device__ __forceinline__ const DevCoef *of(int c) const { return base + set_of[c]; }
+};
 
 __device__ __forceinline__ float4 lds4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 // "whatever is in the registers": the start value of a float4 that some lanes load under a condition and the same lanes

@@ -63,6 +63,11 @@ int pan_prepare(t41rx_ctx *ctx, int n_frames) {
   p.call_rows = 0;
   p.call_first = n_frames;
   if (!p.on) return T41RX_OK;
+  if (p.out.smeter)  // (parameter sets: DrawSmeterBar()'s dBm takes the two gains by value, one pair per launch)
+    for (const t41rx_params &s : ctx->sets.params)
+      if (s.RFgain != ctx->params.RFgain || s.rfGainAllBands != ctx->params.rfGainAllBands)
+        return fail(T41RX_ERR_UNSUPPORTED, "panadapter: the S-meter's dBm reads one RFgain / rfGainAllBands per context and a loaded "
+                                               "parameter set differs from set 0 in them; drop the smeter rows or give the sets equal gains");
   p.call_rows = pan_rows_of_call(p.counter, n_frames, p.period, p.phase, &p.call_first);
   if (p.call_rows > p.max_rows)
     return fail(T41RX_ERR_ARG, "the call holds more update frames than the max_rows the panadapter buffers were set with");

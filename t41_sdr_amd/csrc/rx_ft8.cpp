@@ -43,6 +43,9 @@ int ft8_power_on(t41rx_ctx *ctx) {
 int ft8_prepare(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
   if (ctx->params.mode != T41RX_DEMOD_USB)
     return fail(T41RX_ERR_UNSUPPORTED, "FT8 receive: the firmware demodulates DEMOD_FT8 as USB (Process.cpp:616-617); this context's mode is not T41RX_DEMOD_USB");
+  for (const t41rx_params &p : ctx->sets.params)  // (parameter sets: FT8 runs on every channel)
+    if (p.mode != T41RX_DEMOD_USB)
+      return fail(T41RX_ERR_UNSUPPORTED, "FT8 receive: the firmware demodulates DEMOD_FT8 as USB (Process.cpp:616-617); a loaded parameter set's mode is not T41RX_DEMOD_USB");
   if (n_frames > ctx->ft8.frames) return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the FT8 status buffer was set with");
   if (const int rc = ensure_ft8(ctx)) return rc;
   if (!stages_on(ctx) && !ctx->dbg_demod && n_frames > ctx->ft8.tap_frames) {

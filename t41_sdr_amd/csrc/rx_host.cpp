@@ -72,19 +72,22 @@ ChanNco make_nco(int32_t nco_freq_hz, int side_tone_hz) {
   return n;
 }
 
-int upload_nco(t41rx_ctx *ctx) {
+}  // namespace
+
+// (the side tone folded into the oscillator is the channel's own set's)
+int t41::upload_nco(t41rx_ctx *ctx) {
   std::vector<ChanNco> h((size_t)ctx->nchan);
-  const int side = (int)blob_view(ctx->blob.data()).scalars[kScSideTone];
-  for (int i = 0; i < ctx->nchan; ++i) h[(size_t)i] = make_nco(ctx->nco_hz[(size_t)i], side);
+  for (int i = 0; i < ctx->nchan; ++i) {
+    const int set = sets_loaded(ctx) ? ctx->sets.set_of[(size_t)i] : 0;
+    float *blob = set == 0 ? ctx->blob.data() : ctx->sets.blobs[(size_t)set - 1].data();
+    h[(size_t)i] = make_nco(ctx->nco_hz[(size_t)i], (int)blob_view(blob).scalars[kScSideTone]);
+  }
   HIP_TRY(hipMemcpy(ctx->d_nco.get(), h.data(), sizeof(ChanNco) * h.size(), hipMemcpyHostToDevice));
   return T41RX_OK;
 }
 
-// blob -> device constant block + lane-ordered tables
-int upload_coeffs(t41rx_ctx *ctx) {
-  const int N = ctx->params.fft_length;
-  BlobView v = blob_view(ctx->blob.data());
-  DevCoef dc;
+// blob -> the device's coefficient block
+void t41::fill_dev_coef(const BlobView &v, DevCoef &dc) {
   std::memset(&dc, 0, sizeof(dc));
   std::memcpy(dc.dec1, v.dec1, sizeof(float) * kDec1Taps);
   // FIR_dec2_coeffs times the level adjust volScaleFactor (Process.cpp:481-492), the multiply right behind that filter
@@ -97,18 +100,37 @@ int upload_coeffs(t41rx_ctx *ctx) {
   std::memcpy(dc.sc, v.scalars, sizeof(float) * kNumScalars);
   std::memcpy(dc.agc, v.agc, sizeof(float) * kNumAgc);
   std::memcpy(dc.deemph, kDeemphFir24000, sizeof(float) * kDeemphTaps);
+}
+
+// the first stage's gains of a blob's scalars, and whether they are `plain`
+bool t41::gains_of(const float *sc, SetGains &g) {
+  const bool iq_on = sc[kScIqCorrOn] != 0.0f;
+  const float gi = iq_on ? sc[kScBandGain] * sc[kScNegIqAmp] : sc[kScBandGain];
+  g = SetGains{};
+  g.g_rf = sc[kScRfGain];
+  g.g_band = sc[kScBandGain];
+  g.neg_iq_amp = sc[kScNegIqAmp];
+  g.iq_phase = sc[kScIqPhase];
+  g.iq_corr_on = iq_on ? 1 : 0;
+  // PLAIN folds "I <- -I" (IQ correction on, amplitude factor 1) into the sign of the RF gain; with
+  // the correction on and gi = +1 (IQAmpCorrectionFactor = -1) the general kernel must run
+  return (iq_on ? gi == -1.0f : gi == 1.0f) && sc[kScBandGain] == 1.0f && (!iq_on || sc[kScIqPhase] == 0.0f);
+}
+
+namespace {
+// blob -> device constant block + lane-ordered tables
+int upload_coeffs(t41rx_ctx *ctx) {
+  const int N = ctx->params.fft_length;
+  BlobView v = blob_view(ctx->blob.data());
+  DevCoef dc;
+  fill_dev_coef(v, dc);
   HIP_TRY(hipMemcpy(ctx->d_coef.get(), &dc, sizeof(dc), hipMemcpyHostToDevice));
 
   const int R = N / 512;  // 2048-sample segments per frame
-  std::vector<float2> tab((size_t)kTabEntries512, make_float2(0.0f, 0.0f));
+  std::vector<float2> tab;
+  fill_tab512(v, N, tab);
   const float invN = 1.0f / (float)N;  // exact power of two: folding it into the mask is lossless
-  if (N == 512) {
-    for (int r = 0; r < 8; ++r)
-      for (int l = 0; l < 64; ++l) {
-        const int k = l + 64 * r;
-        tab[(size_t)(kTabMask + 64 * r + l)] = make_float2(v.mask[2 * k] * invN, v.mask[2 * k + 1] * invN);
-      }
-  } else {
+  if (N != 512) {
     // N = R x 512 decomposition: radix-R twiddles W_N^(k' q) and the mask in [q][m] order
     std::vector<float2> t4((size_t)tab_long_entries(R));
     const double tp = 6.283185307179586476925286766559;
@@ -123,6 +145,22 @@ int upload_coeffs(t41rx_ctx *ctx) {
         t4[(size_t)((R - 1) * 512 + 512 * q + m)] = make_float2(v.mask[2 * k] * invN, v.mask[2 * k + 1] * invN);
       }
     HIP_TRY(hipMemcpy(ctx->d_tab4k.get(), t4.data(), sizeof(float2) * t4.size(), hipMemcpyHostToDevice));
+  }
+  HIP_TRY(hipMemcpy(ctx->d_tab.get(), tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
+  return T41RX_OK;
+}
+}  // namespace
+
+// blob -> the constant table of the fused kernels (the mask only at fft_length 512: the long pipeline has its own)
+void t41::fill_tab512(const BlobView &v, int N, std::vector<float2> &tab) {
+  tab.assign((size_t)kTabEntries512, make_float2(0.0f, 0.0f));
+  const float invN = 1.0f / (float)N;  // exact power of two: folding it into the mask is lossless
+  if (N == 512) {
+    for (int r = 0; r < 8; ++r)
+      for (int l = 0; l < 64; ++l) {
+        const int k = l + 64 * r;
+        tab[(size_t)(kTabMask + 64 * r + l)] = make_float2(v.mask[2 * k] * invN, v.mask[2 * k + 1] * invN);
+      }
   }
   const double two_pi = 6.283185307179586476925286766559;
   for (int q = 1; q < 8; ++q)
@@ -174,9 +212,9 @@ int upload_coeffs(t41rx_ctx *ctx) {
     t[256] = 0.0f;
     t[512] = -0.0f;
   }
-  HIP_TRY(hipMemcpy(ctx->d_tab.get(), tab.data(), sizeof(float2) * tab.size(), hipMemcpyHostToDevice));
-  return T41RX_OK;
 }
+
+namespace {
 
 // a broken hand-over protocol of the pipelined kernels leaves wrong samples and a count of waits that ran out, not a hung
 // GPU -- reported at the calls that synchronise anyway
@@ -240,6 +278,8 @@ int prepare_call(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
   }
   if (ctx->params.AGCMode != 0 && (int)blob_view(ctx->blob.data()).agc[kAgcAttackBuffsize] != kAgcDelay)
     return fail(T41RX_ERR_STATE, "coefficient blob carries an AGC look-ahead the kernel is not built for");
+  if (sets_loaded(ctx) && (seg > 1 || stages_on(ctx)))  // (the setters keep these apart: not reached)
+    return fail(T41RX_ERR_STATE, "parameter sets are loaded with a long fft_length or a chain-splitting stage");
   if ((ctx->dbg_nco || ctx->dbg_dec || ctx->dbg_demod) && n_frames > ctx->tap_frames)
     return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the debug tap buffers were set with");
   if (ctx->spect && n_frames > ctx->spect_frames)
@@ -293,17 +333,27 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
   a.aud24 = ctx->d_aud24.get();
   a.tab4k = ctx->d_tab4k.get();
   {
-    const float *sc = blob_view(ctx->blob.data()).scalars;
-    const bool iq_on = sc[kScIqCorrOn] != 0.0f;
-    const float gi = iq_on ? sc[kScBandGain] * sc[kScNegIqAmp] : sc[kScBandGain];
-    a.g_rf = sc[kScRfGain];
-    a.g_band = sc[kScBandGain];
-    a.neg_iq_amp = sc[kScNegIqAmp];
-    a.iq_phase = sc[kScIqPhase];
-    a.iq_corr_on = iq_on ? 1 : 0;
-    // PLAIN folds "I <- -I" (IQ correction on, amplitude factor 1) into the sign of the RF gain; with
-    // the correction on and gi = +1 (IQAmpCorrectionFactor = -1) the general kernel must run
-    a.plain = ((iq_on ? gi == -1.0f : gi == 1.0f) && sc[kScBandGain] == 1.0f && (!iq_on || sc[kScIqPhase] == 0.0f)) ? 1 : 0;
+    SetGains g;
+    a.plain = gains_of(blob_view(ctx->blob.data()).scalars, g) ? 1 : 0;
+    a.g_rf = g.g_rf;
+    a.g_band = g.g_band;
+    a.neg_iq_amp = g.neg_iq_amp;
+    a.iq_phase = g.iq_phase;
+    a.iq_corr_on = g.iq_corr_on;
+  }
+  if (sets_loaded(ctx)) {
+    // parameter sets: the arrays [K + 1] in place of set 0's block and table, the channels' table and the sets' gains.
+    // The rule (t41rx_param_sets_compatible) makes everything else in here -- plain, agc, nfm_atan, the pipelined
+    // form -- the same for every set.  The set kernels are twins of the mapped ones: without an input map, the identity
+    a.coef = ctx->sets.d_coef.get();
+    a.tab = ctx->sets.d_tab.get();
+    a.set_of = ctx->sets.d_set_of.get();
+    a.set_gain = ctx->sets.d_gain.get();
+    if (!a.in_map) {
+      a.in_map = ctx->sets.d_ident.get();
+      a.in_chan_stride = a.chan_stride;
+      a.in_frame_stride = a.frame_stride;
+    }
   }
   a.q15 = q15 ? 1 : 0;
   a.nco_rd = ctx->nco_sel;
@@ -542,7 +592,7 @@ int t41rx_set_params(t41rx_ctx *ctx, const t41rx_params *p) {
   const char *why = nullptr;
   if (!params_valid(*p, &why)) return fail(T41RX_ERR_ARG, why ? why : "bad params");
   if (p->fft_length != ctx->params.fft_length) return fail(T41RX_ERR_ARG, "fft_length cannot change on a live context");
-
+  if (sets_loaded(ctx) && sets_check_set0(ctx, *p) != T41RX_OK) return T41RX_ERR_UNSUPPORTED;  // (the rule's text stands)
 
   std::vector<float> nb(ctx->blob.size());
   int rc = design_blob(*p, nb.data(), nb.size() * sizeof(float));
@@ -552,6 +602,7 @@ int t41rx_set_params(t41rx_ctx *ctx, const t41rx_params *p) {
   ctx->blob.swap(nb);
   ctx->params = *p;
   if ((rc = upload_coeffs(ctx)) != T41RX_OK) return rc;
+  if (sets_loaded(ctx) && (rc = sets_upload(ctx)) != T41RX_OK) return rc;  // entry 0 of the set arrays
   return upload_nco(ctx);  // the CW side-tone offset may have changed
 }
 
@@ -585,6 +636,7 @@ int t41rx_set_coeffs(t41rx_ctx *ctx, const void *blob, size_t blob_bytes) {
   const char *why = nullptr;
   if (!params_valid(bp, &why) || bp.fft_length != h[2] || bp.mode != h[3])
     return fail(T41RX_ERR_STATE, std::string("blob parameters invalid: ") + (why ? why : "header mismatch"));
+  if (sets_loaded(ctx) && sets_check_set0(ctx, bp) != T41RX_OK) return T41RX_ERR_UNSUPPORTED;  // (the rule's text stands)
 
   DeviceGuard g(ctx->device);
   HIP_TRY(hipDeviceSynchronize());
@@ -592,6 +644,7 @@ int t41rx_set_coeffs(t41rx_ctx *ctx, const void *blob, size_t blob_bytes) {
   ctx->params = bp;
   int rc = upload_coeffs(ctx);
   if (rc != T41RX_OK) return rc;
+  if (sets_loaded(ctx) && (rc = sets_upload(ctx)) != T41RX_OK) return rc;  // entry 0 of the set arrays
   return upload_nco(ctx);
 }
 

@@ -27,6 +27,14 @@ constexpr int kTabAm = kTabHp4 + 64;
 constexpr int kTabSam = kTabAm + 64 * 6;
 constexpr int kTabEntries512 = kTabSam + 260;
 
+// the gains of the first stage of one parameter set (RxArgs::set_gain): what RxArgs carries by value for set 0
+struct SetGains {
+  float g_rf, g_band, neg_iq_amp, iq_phase;
+  int iq_corr_on;
+  int pad[3];
+};
+static_assert(sizeof(SetGains) == 32, "SetGains: one 32-byte scalar load");
+
 struct RxArgs {
   const float *__restrict__ I;
   const float *__restrict__ Q;
@@ -88,6 +96,13 @@ struct RxArgs {
   int tap_period;
   int tap_first;
   int tap_rows;
+  // parameter sets (t41rx_set_param_sets), or null: channel c runs with set set_of[c] -- coefficient block coef[set],
+  // constant table tab + set * kTabEntries512 (the mask and the AM scan constants; every other part is the same in all
+  // of them and is read from set 0's) and the first stage's gains set_gain[set] in place of the five words above.  The
+  // host has checked every entry against the number of sets.  Only the set instantiations read these fields; a call
+  // with sets always carries in_map too (an identity map when the caller set none).
+  const int *__restrict__ set_of;
+  const SetGains *__restrict__ set_gain;
 };
 
 // constant table of the N = 512 R point fast convolution (float2 units):

@@ -1,0 +1,175 @@
+// t41_sdr_amd/csrc/rx_sets.cpp -- parameter sets (t41rx_set_param_sets / _get_param_sets / _param_sets_compatible): one
+// t41rx_params per group of channels of a context.  The context's own parameters are set 0; the extra sets 1..K are
+// designed here exactly as set 0 is (design_blob, fill_dev_coef, fill_tab512, gains_of) and uploaded as arrays [K + 1]
+// the set forms of rx512_kernel index with set_of_channel[ch].  The rule that decides which sets may share a context is
+// compatible() below, once.
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "rx_ctx.hpp"
+
+using namespace t41;
+
+namespace {
+
+int family(int mode) { return mode == T41RX_DEMOD_LSB ? T41RX_DEMOD_USB : mode; }  // USB and LSB are one kernel
+const char *family_name(int mode) {
+  return mode == T41RX_DEMOD_AM ? "AM" : mode == T41RX_DEMOD_NFM ? "NFM" : mode == T41RX_DEMOD_SAM ? "SAM" : "USB/LSB";
+}
+
+bool plain_of(const t41rx_params &p) {
+  std::vector<float> blob(blob_floats(p.fft_length));
+  if (design_blob(p, blob.data(), blob.size() * sizeof(float)) != T41RX_OK) return false;  // (the callers have validated p)
+  SetGains g;
+  return gains_of(blob_view(blob.data()).scalars, g);
+}
+
+// The rule: launch512() picks the same rx512_kernel instantiation for both, and both name the same stages.  `who`
+// opens the refusal ("set 2 against set 0: ").
+int compatible(const t41rx_params &a, const t41rx_params &b, const std::string &who) {
+  auto no = [&](const std::string &why) { return fail(T41RX_ERR_UNSUPPORTED, "parameter sets: " + who + why); };
+  if (a.fft_length != b.fft_length)
+    return no("fft_length differs (" + std::to_string(a.fft_length) + " and " + std::to_string(b.fft_length) + ")");
+  if (a.fft_length != 512)
+    return no("fft_length " + std::to_string(a.fft_length) + ": the long-FFT pipeline carries one parameter set; sets are built for fft_length 512");
+  if (family(a.mode) != family(b.mode))
+    return no(std::string("the demodulators differ (") + family_name(a.mode) + " and " + family_name(b.mode) + "): one kernel runs all the channels of a context");
+  if ((a.AGCMode != 0) != (b.AGCMode != 0)) return no("the AGC is off in one and on in the other (AGCMode 0 against 1..4)");
+  if (a.nfm_demod != b.nfm_demod) return no("nfm_demod differs");
+  if (a.xmtMode != b.xmtMode) return no("xmtMode differs");
+  if (a.nrOptionSelect != 0 || b.nrOptionSelect != 0 || a.ANR_notchOn != 0 || b.ANR_notchOn != 0)
+    return no("noise reduction / notch (nrOptionSelect, ANR_notchOn) split the fused chain and read one parameter set on the host: both must be 0");
+  if (plain_of(a) != plain_of(b))
+    return no("the first stage's gains are unit gains in one (RFgain 1, IQAmpCorrectionFactor 1, IQPhaseCorrectionFactor 0) and general in "
+              "the other: two kernels");
+  return T41RX_OK;
+}
+
+// the arrays the set kernels read, entry 0 from the context's own blob, entry i from blobs[i - 1]
+int upload_arrays(const t41rx_ctx *ctx, const std::vector<std::vector<float>> &blobs, DevCoef *d_coef, float2 *d_tab, SetGains *d_gain) {
+  const size_t n = blobs.size() + 1;
+  std::vector<DevCoef> coef(n);
+  std::vector<SetGains> gain(n);
+  std::vector<float2> tabs, one;
+  tabs.reserve(n * (size_t)kTabEntries512);
+  for (size_t i = 0; i < n; ++i) {
+    // (blob_view() takes a mutable pointer; nothing is written through it)
+    const BlobView v = blob_view(const_cast<float *>(i == 0 ? ctx->blob.data() : blobs[i - 1].data()));
+    fill_dev_coef(v, coef[i]);
+    fill_tab512(v, 512, one);
+    tabs.insert(tabs.end(), one.begin(), one.end());
+    (void)gains_of(v.scalars, gain[i]);
+  }
+  HIP_TRY(hipMemcpy(d_coef, coef.data(), sizeof(DevCoef) * n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_tab, tabs.data(), sizeof(float2) * tabs.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_gain, gain.data(), sizeof(SetGains) * n, hipMemcpyHostToDevice));
+  return T41RX_OK;
+}
+
+}  // namespace
+
+// t41rx_set_params() / t41rx_set_coeffs() with sets loaded: the new set 0 against every loaded set
+int t41::sets_check_set0(const t41rx_ctx *ctx, const t41rx_params &p) {
+  for (size_t i = 0; i < ctx->sets.params.size(); ++i) {
+    const int rc = compatible(p, ctx->sets.params[i], "the new set 0 against set " + std::to_string(i + 1) + ": ");
+    if (rc != T41RX_OK) return rc;
+  }
+  return T41RX_OK;
+}
+
+// set 0 has changed: the set arrays again (the extra sets' entries are rewritten with what they held)
+int t41::sets_upload(t41rx_ctx *ctx) {
+  return upload_arrays(ctx, ctx->sets.blobs, ctx->sets.d_coef.get(), ctx->sets.d_tab.get(), ctx->sets.d_gain.get());
+}
+
+extern "C" {
+
+int t41rx_param_sets_compatible(const t41rx_params *a, const t41rx_params *b) {
+  if (!a || !b) return fail(T41RX_ERR_ARG, "null argument");
+  const char *why = nullptr;
+  if (!params_valid(*a, &why)) return fail(T41RX_ERR_ARG, std::string("parameter sets: the first struct is invalid: ") + (why ? why : "bad params"));
+  if (!params_valid(*b, &why)) return fail(T41RX_ERR_ARG, std::string("parameter sets: the second struct is invalid: ") + (why ? why : "bad params"));
+  return compatible(*a, *b, "");
+}
+
+int t41rx_set_param_sets(t41rx_ctx *ctx, const t41rx_params *sets, int n_sets, const int32_t *set_of_channel, int n) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  const std::string counts = " (n_channels " + std::to_string(ctx->nchan) + ", n_sets " + std::to_string(n_sets) + ")";
+  if (n_sets == 0) {
+    if (sets || set_of_channel) return fail(T41RX_ERR_ARG, "parameter sets: n_sets 0 removes the sets and takes two null pointers" + counts);
+    if (!sets_loaded(ctx)) return T41RX_OK;
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+    HIP_TRY(hipDeviceSynchronize());  // (calls in flight were launched with the sets they found)
+    ctx->sets = ParamSets{};
+    return upload_nco(ctx);  // every channel's side tone is set 0's again
+  }
+  // everything is checked here, on the host, before anything changes: the kernels index the set arrays with these entries unchecked
+  if (n_sets < 0 || n_sets > T41RX_MAX_PARAM_SETS - 1)
+    return fail(T41RX_ERR_ARG, "parameter sets: n_sets must lie in [0, " + std::to_string(T41RX_MAX_PARAM_SETS - 1) + "]" + counts);
+  if (!sets || !set_of_channel) return fail(T41RX_ERR_ARG, "parameter sets: null argument" + counts);
+  if (n != ctx->nchan) return fail(T41RX_ERR_ARG, "parameter sets: n (" + std::to_string(n) + ") must equal n_channels" + counts);
+  for (int i = 0; i < n; ++i)
+    if (set_of_channel[i] < 0 || set_of_channel[i] > n_sets)
+      return fail(T41RX_ERR_ARG, "parameter sets: channel " + std::to_string(i) + " names set " + std::to_string(set_of_channel[i]) +
+                                     ", outside [0, n_sets]" + counts);
+  for (int i = 0; i < n_sets; ++i) {
+    const char *why = nullptr;
+    if (!params_valid(sets[i], &why))
+      return fail(T41RX_ERR_ARG, "parameter sets: set " + std::to_string(i + 1) + " is invalid: " + (why ? why : "bad params"));
+  }
+  if (ctx->params.fft_length != 512)
+    return fail(T41RX_ERR_UNSUPPORTED, "parameter sets: fft_length " + std::to_string(ctx->params.fft_length) +
+                                           ": the long-FFT pipeline carries one parameter set; sets are built for fft_length 512");
+  if (const char *stage = split_stage_on(ctx)) return sets_refuse_stage(stage);
+  for (int i = 0; i < n_sets; ++i) {
+    const int rc = compatible(ctx->params, sets[i], "set " + std::to_string(i + 1) + " against set 0: ");
+    if (rc != T41RX_OK) return rc;
+  }
+  ParamSets fresh;
+  fresh.params.assign(sets, sets + n_sets);
+  fresh.blobs.resize((size_t)n_sets);
+  for (int i = 0; i < n_sets; ++i) {
+    fresh.blobs[(size_t)i].assign(blob_floats(512), 0.0f);
+    const int rc = design_blob(sets[i], fresh.blobs[(size_t)i].data(), fresh.blobs[(size_t)i].size() * sizeof(float));
+    if (rc != T41RX_OK) return fail(rc, "parameter sets: coefficient design of set " + std::to_string(i + 1) + " failed");
+    if (sets[i].AGCMode != 0 && (int)blob_view(fresh.blobs[(size_t)i].data()).agc[kAgcAttackBuffsize] != kAgcDelay)
+      return fail(T41RX_ERR_UNSUPPORTED, "parameter sets: set " + std::to_string(i + 1) + " asks for an AGC look-ahead the kernel is not built for");
+  }
+  fresh.set_of.assign(set_of_channel, set_of_channel + n);
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  HIP_TRY(hipDeviceSynchronize());
+  // fresh buffers, filled before the context sees them: a failure leaves the previous sets whole
+  const size_t k1 = (size_t)n_sets + 1;
+  HIP_TRY(dev_alloc(fresh.d_coef, sizeof(DevCoef) * k1));
+  HIP_TRY(dev_alloc(fresh.d_tab, sizeof(float2) * k1 * (size_t)kTabEntries512));
+  HIP_TRY(dev_alloc(fresh.d_gain, sizeof(SetGains) * k1));
+  HIP_TRY(dev_alloc(fresh.d_set_of, sizeof(int32_t) * (size_t)n));
+  HIP_TRY(dev_alloc(fresh.d_ident, sizeof(int32_t) * (size_t)n));
+  int rc = upload_arrays(ctx, fresh.blobs, fresh.d_coef.get(), fresh.d_tab.get(), fresh.d_gain.get());
+  if (rc != T41RX_OK) return rc;
+  std::vector<int32_t> ident((size_t)n);
+  for (int i = 0; i < n; ++i) ident[(size_t)i] = i;
+  HIP_TRY(hipMemcpy(fresh.d_set_of.get(), set_of_channel, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(fresh.d_ident.get(), ident.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+  ctx->sets = std::move(fresh);
+  return upload_nco(ctx);  // the side tone follows the channel's own set
+}
+
+int t41rx_get_param_sets(const t41rx_ctx *ctx, t41rx_params *sets_out, int cap, int32_t *set_of_channel_out, int n) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  const int k = (int)ctx->sets.params.size();
+  if (k > 0 && sets_out) {
+    if (cap < k) return fail(T41RX_ERR_ARG, "parameter sets: cap (" + std::to_string(cap) + ") is smaller than the number of sets (" + std::to_string(k) + ")");
+    std::memcpy(sets_out, ctx->sets.params.data(), sizeof(t41rx_params) * (size_t)k);
+  }
+  if (k > 0 && set_of_channel_out) {
+    if (n != ctx->nchan) return fail(T41RX_ERR_ARG, "parameter sets: n (" + std::to_string(n) + ") must equal n_channels (" + std::to_string(ctx->nchan) + ")");
+    std::memcpy(set_of_channel_out, ctx->sets.set_of.data(), sizeof(int32_t) * (size_t)n);
+  }
+  return k;
+}
+
+}  // extern "C"

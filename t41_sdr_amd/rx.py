@@ -34,6 +34,17 @@ def design_coeffs(params):
     return get_blob(lib.t41rx_design_coeffs, C.byref(params), n)
 
 
+def param_sets_compatible(a, b):
+    """The rule of RxChain.set_param_sets() on two t41rx_params, on the host (t41rx_param_sets_compatible): (True, "")
+    when they may share a chain, else (False, the clause they break).  An invalid struct raises T41RxError."""
+    lib = _lib.load()
+    rc = lib.t41rx_param_sets_compatible(C.byref(a), C.byref(b))
+    if rc == _lib.ERR_UNSUPPORTED:
+        return False, lib.t41rx_last_error().decode()
+    check(rc)
+    return True, ""
+
+
 def ft8_tables():
     """(window[2048], mag_db[16385]) for RxChain.set_ft8_tables(), in the firmware's types: ft_blackman_i(i, 2048) in f32
     (ft8.cpp:168-178) and (float)(10.0 * log((float)(10 * m) + 0.1)) with the sum and the logarithm in double
@@ -154,6 +165,44 @@ class RxChain:
         """the input map as an int32 array [n_channels] (a copy), or None with the map off"""
         m = np.zeros(self.n_channels, np.int32)
         return m if value(self._lib.t41rx_get_input_map(self._ctx, ptr(m, I32P), self.n_channels)) > 0 else None
+
+    def set_param_sets(self, sets, set_of_channel=None):
+        """Receiver groups (t41rx_set_param_sets): the context's own parameters are set 0, sets[i] becomes set i + 1, and
+        channel c is processed exactly as a chain created with set set_of_channel[c] would process it.  sets: a sequence
+        of t41rx_params, or of dicts of changes against set 0 (dict(mode=DEMOD_LSB, FLoCut=-3000, FHiCut=-200)).  Which
+        sets may share a chain is one rule, param_sets_compatible().  None removes the sets.  Configuration, like the
+        input map: in no checkpoint, kept across reset() / set_state(); CalcFilters() changes set 0."""
+        if sets is None:
+            if set_of_channel is not None:
+                raise ValueError("set_of_channel goes with sets: pass both, or None to remove the sets")
+            check(self._lib.t41rx_set_param_sets(self._ctx, None, 0, None, 0))
+            return
+        if set_of_channel is None:
+            raise ValueError("set_of_channel must be given with sets: n_channels=%d set numbers in [0, %d]" % (self.n_channels, len(sets)))
+        arr = (Params * max(len(sets), 1))()
+        for i, s in enumerate(sets):
+            if isinstance(s, Params):
+                arr[i] = s
+            elif isinstance(s, dict):
+                arr[i] = with_fields(Params.from_buffer_copy(self.params), "t41rx_params", s)
+            else:
+                raise ValueError("sets[%d] must be a t41rx_params or a dict of changes against set 0, got %s" % (i, type(s).__name__))
+        m = int_table(set_of_channel, np.int32, None, "set_of_channel must be a 1-d array of int32 set numbers, got %r %s")
+        check(self._lib.t41rx_set_param_sets(self._ctx, arr, len(sets), ptr(m, I32P), int(m.size)))
+
+    @property
+    def param_sets(self):
+        """the extra parameter sets 1..K as a list of t41rx_params (copies); empty without sets"""
+        k = value(self._lib.t41rx_get_param_sets(self._ctx, None, 0, None, 0))
+        arr = (Params * max(k, 1))()
+        value(self._lib.t41rx_get_param_sets(self._ctx, arr, k, None, 0))
+        return [Params.from_buffer_copy(arr[i]) for i in range(k)]
+
+    @property
+    def set_of_channel(self):
+        """the channels' set numbers as an int32 array [n_channels] (a copy), or None without sets"""
+        m = np.zeros(self.n_channels, np.int32)
+        return m if value(self._lib.t41rx_get_param_sets(self._ctx, None, 0, ptr(m, I32P), self.n_channels)) > 0 else None
 
     def set_noise_blanker(self, on):
         """NB_on (Process.cpp:873-876): the receive noise blanker on the demodulated audio, behind the noise reduction and
