@@ -130,7 +130,12 @@ T41RX_API int    t41rx_design_coeffs(const t41rx_params *p, void *blob, size_t b
 
 /* ---- context ---- */
 /* InitializeDataArrays() (T41_SDR.ino:473-667): allocate state for n_channels channels on HIP
- * device `device_id`, power-on state, design + upload coefficients for *p. */
+ * device `device_id`, power-on state, design + upload coefficients for *p.
+ * The environment is read here and by no other call.  T41RX_SEG_RUN=n is a test hook: the context's long-FFT calls run
+ * their segment-parallel kernels with runs of n segments, and at fft_length 4096 the two-kernel pipeline where the
+ * one-kernel form would run (the tests compare the two); set it before the context exists.  A library whose kernels were
+ * built with diagnostics is refused (T41RX_ERR_UNSUPPORTED) unless T41RX_ALLOW_EXPERIMENT=1; only such a library reads
+ * the diagnostics' own T41RX_PIPE_STAT and T41RX_STAMP_TAPS. */
 T41RX_API int t41rx_create(t41rx_ctx **out, int device_id, int n_channels, const t41rx_params *p);
 T41RX_API int t41rx_destroy(t41rx_ctx *ctx);
 

@@ -18,7 +18,9 @@
 //   ZoomFFTExe() on the 2048 shifted samples          :391-395, FFT.cpp:67-157       (spectrumZoom 1..4)
 //   pixelnew[] = baseOffset + pixel_offset + (int16_t)(dBScale * log10f_fast(FFT_spec[]))   FFT.cpp:157, 245
 // and in every frame, from the channel's current pixelnew[]: arm_max_q15 over the two windows and adjdB (:498-505, 524).
+#include "rx_experiments.hpp"
 #include "rx_kernels.hpp"
+#include "rx_launch.hpp"
 #include "display_pixel.hpp"
 #include "wave_fft.hpp"
 #include "zoom_fft.hpp"
@@ -221,5 +223,7 @@ hipError_t launch_cal(const CalArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(cal_kernel, dim3(a.nchan), dim3(64), 0, s, a);
   return hipGetLastError();
 }
+
+T41RX_BUILD_FLAGS(cal_kernel)
 
 }  // namespace t41

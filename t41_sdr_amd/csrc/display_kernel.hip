@@ -1,5 +1,6 @@
 // t41_sdr_amd/csrc/display_kernel.hip -- the display FFT side output (t41rx_set_display_spectrum).
 #include "rx_device.hpp"
+#include "rx_launch.hpp"
 #include "zoom_fft.hpp"
 
 namespace t41 {
@@ -84,5 +85,7 @@ hipError_t launch_display(const DispArgs &a, hipStream_t s) {
   hipLaunchKernelGGL(display_kernel, dim3(a.nchan), dim3(64), 0, s, a);
   return hipGetLastError();
 }
+
+T41RX_BUILD_FLAGS(display_kernel)
 
 }  // namespace t41

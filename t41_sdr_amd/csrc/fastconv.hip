@@ -41,5 +41,6 @@ hipError_t launch_fastconv_fused(const RxArgs &a, hipStream_t s) {
 }
 
 T41RX_CLK_READER(t41rx_debug_read_clk_fc)
+T41RX_BUILD_FLAGS(fastconv)
 
 }  // namespace t41

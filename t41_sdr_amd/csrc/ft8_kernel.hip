@@ -61,6 +61,8 @@ __device__ __forceinline__ Cq twmul(unsigned w, Cq x) {
 __device__ __forceinline__ int to_q15(float x) { return sat16((int)(x * 32768.0f)); }
 }  // namespace ft8
 
+// (NT: 256, a workgroup per channel, is the one instantiation.  The wave-per-channel arm, NT = 64, was measured and is
+// gone -- DESIGN.md, "FT8 receive"; the parameter stays because the kernel's name carries it)
 template <int NT>
 __global__ __launch_bounds__(NT) void ft8_kernel(Ft8Args a) {
 #pragma clang fp contract(off)
@@ -307,10 +309,7 @@ void ft8_make_fft_tables(uint32_t *tab) {
 hipError_t launch_ft8(const Ft8Args &a, hipStream_t s) {
   if (a.nchan <= 0 || a.nframes <= 0 || !a.aud || !a.state || !a.power || !a.status || !a.window || !a.mag_db || !a.tab || a.num < 0 || a.den <= 0)
     return hipErrorInvalidConfiguration;
-  if (a.threads == 64)
-    hipLaunchKernelGGL(ft8_kernel<64>, dim3((unsigned)a.nchan), dim3(64), 0, s, a);
-  else
-    hipLaunchKernelGGL(ft8_kernel<256>, dim3((unsigned)a.nchan), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(ft8_kernel<256>, dim3((unsigned)a.nchan), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -51,7 +51,6 @@ struct Ft8Args {
   const uint32_t *tab;    // [kFt8TabWords] (device)
   int nchan, nframes;
   int32_t t0, num, den;   // the clock (t41rx_set_ft8_clock)
-  int threads;            // 256: a workgroup per channel (the product); 64: a wave per channel (tools/ft8_probe.py)
 };
 hipError_t launch_ft8(const Ft8Args &a, hipStream_t s);
 // auto_sync_FT8()'s success branch on the channels whose mask byte is non-zero (mask: device pointer, or null for all)

@@ -7,5 +7,6 @@ namespace t41 {
 hipError_t launch512_sam(const RxArgs &a, hipStream_t s, bool debug) { return launch512<kModeSam>(a, s, debug); }
 
 T41RX_CLK_READER(t41rx_debug_read_clk_sam)
+T41RX_BUILD_FLAGS(rx512_sam)
 
 }  // namespace t41

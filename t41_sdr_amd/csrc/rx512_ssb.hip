@@ -6,5 +6,6 @@ namespace t41 {
 hipError_t launch512_ssb(const RxArgs &a, hipStream_t s, bool debug) { return launch512<kModeSsb>(a, s, debug); }
 
 T41RX_CLK_READER(t41rx_debug_read_clk)
+T41RX_BUILD_FLAGS(rx512_ssb)
 
 }  // namespace t41

@@ -761,8 +761,8 @@ __device__ __forceinline__ void agc_apply(const cf (&v)[8], float4 agst, float *
 constexpr int kPipeFlags = 1008;                        // float index in the table area: ready[3], done, next frame to claim
 constexpr int kPipeSpinCap = 1 << 20;
 
-// -DT41RX_PIPE_STAT (diagnostic build, tools/build_variant.sh pstat -DT41RX_PIPE_STAT; T41RX_PIPE_STAT=1 prints them when
-// the context is destroyed): 16 cycle counters per wave behind the slots -- [0] chain [1] chains [2] slow blocks [3] waiting
+// -DT41RX_PIPE_STAT (diagnostic build, tools/build_variant.sh pstat -DT41RX_PIPE_STAT; T41RX_PIPE_STAT=1, set before the
+// context is created, prints them when it is destroyed): 16 cycle counters per wave behind the slots -- [0] chain [1] chains [2] slow blocks [3] waiting
 // for a chain's results [4] duty wave waiting before its chain [5] blocks [6] chain: staging [7] chain: the steps
 // [8] front end [9] AGC preparation [10] back end [11] iterations
 #ifdef T41RX_PIPE_STAT

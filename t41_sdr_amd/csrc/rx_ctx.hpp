@@ -218,6 +218,12 @@ struct t41rx_ctx {
   int scratch_frames = 0;
   int layout = T41RX_LAYOUT_CHANNEL_MAJOR;  // of I / Q / audio (t41rx_set_buffer_layout)
   int nco_sel = 0;               // long FFT: which NcoState copy is current (flips with every process call)
+  // the environment as t41rx_create() found it.  T41RX_SEG_RUN=n, a test hook: the long-FFT pipeline's run length, and at
+  // FFT_LENGTH 4096 the two-kernel pipeline in place of the one-kernel form.  T41RX_PIPE_STAT / T41RX_STAMP_TAPS: read on
+  // a diagnostic library only (kernel_build_flags() != 0) -- the counters' print-out at destruction, and the demod tap
+  // at the long FFT lengths, where the -DT41RX_STAMP kernels put their cycle stamps
+  bool seg_run_set = false, pipe_stat = false, stamp_taps = false;
+  long seg_run = 0;
   // receiver groups (t41rx_set_input_map): channel c reads row in_map[c] of the n_streams rows of I / Q; n_streams == 0:
   // no map, one row per channel.  Configuration like `layout`: in no checkpoint, untouched by reset / set_state / set_params
   std::vector<int32_t> in_map;   // (host)

@@ -75,8 +75,6 @@ int ft8_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t s) {
   f.t0 = ctx->ft8.clock.t0;
   f.num = ctx->ft8.clock.num;
   f.den = ctx->ft8.clock.den;
-  f.threads = 256;
-  if (const char *env = std::getenv("T41RX_FT8_THREADS")) f.threads = std::atoi(env) == 64 ? 64 : 256;  // experiments (tools/ft8_probe.py)
   return hip_check(launch_ft8(f, s), "FT8 kernel launch");
 }
 

@@ -365,7 +365,7 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
     // memories, so runs are as long as still gives every slot a wave (and never longer than 8).
     const long segs = (long)a.nframes, waves = 4096;
     long run = (long)ctx->nchan * segs / waves;
-    if (const char *e = std::getenv("T41RX_SEG_RUN")) run = std::atol(e);  // experiments
+    if (ctx->seg_run_set) run = ctx->seg_run;  // the tests' hook (T41RX_SEG_RUN at creation)
     a.seg_run = (int)(run < 1 ? 1 : (run > 8 ? 8 : (run > segs ? segs : run)));
   }
   a.agc = ctx->params.AGCMode != 0 ? 1 : 0;
@@ -394,7 +394,7 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
 // (c) the stage chain: fused front end, FT8 on the demodulated audio, then on the audio @24 kS/s the equalizer, noise
 // reduction / notch and the blanker, the CW detector, decoder and narrow filter, the back end, and the display stages
 int launch_chain(t41rx_ctx *ctx, RxArgs a, int n_frames, hipStream_t s) {
-  int rc = hip_check(launch_rx(a, ctx->params.fft_length, ctx->params.mode, s), "kernel launch");
+  int rc = hip_check(launch_rx(a, ctx->params.fft_length, ctx->params.mode, ctx->seg_run_set, s), "kernel launch");
   if (rc != T41RX_OK) return rc;
   if (ctx->ft8.on && (rc = ft8_run(ctx, a, n_frames, s)) != T41RX_OK) return rc;
   if (ctx->eq.on && (rc = eq_run(ctx, n_frames, s)) != T41RX_OK) return rc;
@@ -553,6 +553,14 @@ int t41rx_create(t41rx_ctx **out, int device_id, int n_channels, const t41rx_par
   ctx->params = *p;
   ctx->blob.assign(blob_floats(p->fft_length), 0.0f);
   ctx->nco_hz.assign((size_t)n_channels, 0);
+  if (const char *e = std::getenv("T41RX_SEG_RUN")) {  // a test hook, read here and nowhere else (include/t41rx.h)
+    ctx->seg_run_set = true;
+    ctx->seg_run = std::atol(e);
+  }
+  if (kernel_build_flags() != 0) {  // the diagnostic builds' own variables: a product library reads neither
+    ctx->pipe_stat = std::getenv("T41RX_PIPE_STAT") != nullptr;
+    ctx->stamp_taps = std::getenv("T41RX_STAMP_TAPS") != nullptr;
+  }
   int rc = design_blob(*p, ctx->blob.data(), ctx->blob.size() * sizeof(float));
   if (rc != T41RX_OK) return fail(rc, "coefficient design failed");
   hipError_t e;
@@ -573,7 +581,7 @@ int t41rx_destroy(t41rx_ctx *ctx) {
   if (!ctx) return T41RX_OK;
   DeviceGuard g(ctx->device);
   (void)hipDeviceSynchronize();
-  if (ctx->d_agc_pipe && std::getenv("T41RX_PIPE_STAT")) {  // the diagnostic build's counters (rx_chains.hpp: PIPE_STAT_*)
+  if (ctx->d_agc_pipe && ctx->pipe_stat) {  // the diagnostic build's counters (rx_chains.hpp: PIPE_STAT_*)
     unsigned long long c[16] = {};
     std::vector<unsigned long long> all((size_t)ctx->nchan * 16);
     (void)hipMemcpy(all.data(), ctx->d_agc_pipe.get() + pipe_layout(ctx->nchan).counters, all.size() * sizeof(unsigned long long),
@@ -766,7 +774,7 @@ int t41rx_set_debug_taps(t41rx_ctx *ctx, float *d_post_nco, float *d_dec, float 
   if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
   const bool any = d_post_nco || d_dec || d_demod;
   // (T41RX_STAMP_TAPS: the -DT41RX_STAMP diagnostic kernels of the long-FFT pipeline put their cycle stamps behind the demod tap)
-  if (any && ctx->params.fft_length != 512 && !std::getenv("T41RX_STAMP_TAPS"))
+  if (any && ctx->params.fft_length != 512 && !ctx->stamp_taps)
     return fail(T41RX_ERR_UNSUPPORTED, "the stage taps are built for fft_length 512");
   if (any && max_frames <= 0) return fail(T41RX_ERR_ARG, "max_frames must be > 0");
   ctx->dbg_nco = d_post_nco;

@@ -110,9 +110,10 @@ struct RxArgs {
 //   mask[R][512]   : FIR_filter_mask[q + R m] / N at [q][m]
 constexpr int tab_long_entries(int R) { return (R - 1) * 512 + R * 512; }
 
-hipError_t launch_rx(const RxArgs &a, int fft_length, int mode, hipStream_t s);
-// what the kernel translation units of this library were built as (rx_experiments.hpp; rx_dispatch.hip): 0 = the product,
-// bit 1 = a diagnostic build (stamps / counters)
+// long_pipeline: FFT_LENGTH 4096 runs the two-kernel pipeline where the one-kernel form would (t41rx_ctx::seg_run)
+hipError_t launch_rx(const RxArgs &a, int fft_length, int mode, bool long_pipeline, hipStream_t s);
+// what the kernel objects of this library were built as (rx_experiments.hpp; rx_dispatch.hip: the OR of every object's
+// own answer): 0 = the product, bit 1 = a diagnostic build (stamps / counters)
 int kernel_build_flags();
 // FFT_LENGTH 512, behind launch_rx() with aud_out set: interpolators, volume and stores from a.aud24 (f32 or q15 samples out)
 hipError_t launch_back512(const RxArgs &a, hipStream_t s);

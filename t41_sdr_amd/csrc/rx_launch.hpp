@@ -31,4 +31,15 @@ hipError_t launch_long_back(const RxArgs &a, int mode, hipStream_t s);
 hipError_t launch_fastconv(const RxArgs &a, bool cplx, bool fused_back, hipStream_t s);
 hipError_t launch_fastconv_fused(const RxArgs &a, hipStream_t s);
 
+// what each kernel object was built as (rx_experiments.hpp: T41RX_BUILD_FLAGS), one function per object of the Makefile's
+// RXK_OBJS; kernel_build_flags() (rx_dispatch.hip) is the OR of them and the dispatch unit's own
+int build_flags_rx512_ssb();
+int build_flags_rx512_am();
+int build_flags_rx512_nfm();
+int build_flags_rx512_sam();
+int build_flags_rx_long();
+int build_flags_fastconv();
+int build_flags_display_kernel();
+int build_flags_cal_kernel();
+
 }  // namespace t41

@@ -46,5 +46,6 @@ hipError_t launch_back512(const RxArgs &a, hipStream_t s) {
 }
 
 T41RX_CLK_READER(t41rx_debug_read_clk_long)
+T41RX_BUILD_FLAGS(rx_long)
 
 }  // namespace t41

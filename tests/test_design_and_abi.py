@@ -158,35 +158,110 @@ def test_diagnostic_builds_are_fenced(T, tmp_path):
     """the diagnostic switches (T41RX_STAMP, _CLK, _PIPE_STAT: stamps / counters next to the product's
     values) sit behind ONE guard (t41_sdr_amd/csrc/rx_experiments.hpp): without -DT41RX_EXPERIMENT=1 they do not compile,
     and a library built with them refuses t41rx_create() unless the environment opts in.  Checked here with the dispatch
-    translation unit (no kernels: seconds) linked against the product's objects."""
+    translation unit (no kernels: seconds) linked against the product's objects, and the other way round: every kernel
+    object answers for itself (T41RX_BUILD_FLAGS), so a diagnostic display_kernel.o (the cheapest unit that includes
+    rx_device.hpp) among the product's objects, the product's rx_dispatch.o included, is fenced the same way."""
     import subprocess
     csrc = os.path.join(ROOT, "t41_sdr_amd", "csrc")
     base = ["hipcc", "-O1", "-std=c++17", "-fPIC", "-fvisibility=hidden", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include")]
-    for flag in ("-DT41RX_STAMP", "-DT41RX_CLK", "-DT41RX_PIPE_STAT"):
-        r = subprocess.run(base + [flag, "-fsyntax-only", "rx_dispatch.hip"], cwd=csrc, capture_output=True, text=True)
-        assert r.returncode != 0 and "T41RX_EXPERIMENT=1" in r.stderr, (flag, r.stderr[-400:])
-    obj = str(tmp_path / "rx_dispatch_exp.o")
-    subprocess.check_call(base + ["-DT41RX_EXPERIMENT=1", "-DT41RX_CLK", "-c", "rx_dispatch.hip", "-o", obj], cwd=csrc)
-    # the product's objects, as the Makefile lists them (the one list): every one but the dispatch unit built above
+    for unit in ("rx_dispatch.hip", "cal_kernel.hip"):
+        for flag in ("-DT41RX_STAMP", "-DT41RX_CLK", "-DT41RX_PIPE_STAT"):
+            r = subprocess.run(base + [flag, "-fsyntax-only", unit], cwd=csrc, capture_output=True, text=True)
+            assert r.returncode != 0 and "T41RX_EXPERIMENT=1" in r.stderr, (unit, flag, r.stderr[-400:])
+    # the product's objects, as the Makefile lists them (the one list)
     listed = [subprocess.check_output(["make", "-s", target], cwd=csrc, text=True).split() for target in ("print-rxk-objs", "print-host-objs")]
-    assert "rx_dispatch.o" in listed[0] and "rx_host.o" in listed[1]
-    objs = [os.path.join(csrc, o) for o in listed[0] + listed[1] if o != "rx_dispatch.o"]
-    lib_path = str(tmp_path / "libt41rx_exp.so")
-    subprocess.check_call(["hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", obj] + objs + ["-o", lib_path])
-    code = ("import ctypes as C, sys; lib = C.CDLL(%r); lib.t41rx_last_error.restype = C.c_char_p; ctx = C.c_void_p(); "
-            "p = (C.c_int32 * 32)(); lib.t41rx_default_params(p); rc = lib.t41rx_create(C.byref(ctx), 0, 4, p); "
-            "print(rc, lib.t41rx_last_error().decode())" % lib_path)
-    env = {k: v for k, v in os.environ.items() if k != "T41RX_ALLOW_EXPERIMENT"}
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-500:]
-    rc, msg = r.stdout.strip().split(" ", 1)
-    assert int(rc) == -2 and "diagnostics" in msg and "T41RX_ALLOW_EXPERIMENT" in msg   # T41RX_ERR_UNSUPPORTED
-    env["T41RX_ALLOW_EXPERIMENT"] = "1"
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
-    assert "EXPERIMENT BUILD" in r.stderr and "diagnostics on" in r.stderr
-    assert "kernel diagnostics" not in r.stdout   # past the fence (and, without a GPU, on to T41RX_ERR_HIP)
+    assert "rx_dispatch.o" in listed[0] and "display_kernel.o" in listed[0] and "rx_host.o" in listed[1]
+    # one unit built with a switch, every other object the product's
+    for unit in ("rx_dispatch", "display_kernel"):
+        obj = str(tmp_path / (unit + "_exp.o"))
+        subprocess.check_call(base + ["-DT41RX_EXPERIMENT=1", "-DT41RX_CLK", "-c", unit + ".hip", "-o", obj], cwd=csrc)
+        objs = [os.path.join(csrc, o) for o in listed[0] + listed[1] if o != unit + ".o"]
+        lib_path = str(tmp_path / ("libt41rx_%s_exp.so" % unit))
+        subprocess.check_call(["hipcc", "-shared", "-fPIC", "--offload-arch=gfx950", obj] + objs + ["-o", lib_path])
+        code = ("import ctypes as C, sys; lib = C.CDLL(%r); lib.t41rx_last_error.restype = C.c_char_p; ctx = C.c_void_p(); "
+                "p = (C.c_int32 * 32)(); lib.t41rx_default_params(p); rc = lib.t41rx_create(C.byref(ctx), 0, 4, p); "
+                "print(rc, lib.t41rx_last_error().decode())" % lib_path)
+        env = {k: v for k, v in os.environ.items() if k != "T41RX_ALLOW_EXPERIMENT"}
+        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, (unit, r.stderr[-500:])
+        rc, msg = r.stdout.strip().split(" ", 1)
+        assert int(rc) == -2 and "diagnostics" in msg and "T41RX_ALLOW_EXPERIMENT" in msg, (unit, rc, msg)   # T41RX_ERR_UNSUPPORTED
+        env["T41RX_ALLOW_EXPERIMENT"] = "1"
+        r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
+        assert "EXPERIMENT BUILD" in r.stderr and "diagnostics on" in r.stderr, unit
+        assert "kernel diagnostics" not in r.stdout, unit   # past the fence (and, without a GPU, on to T41RX_ERR_HIP)
     # the product library is not one
     assert T.load().t41rx_abi_version() == 5
+
+
+def _rxk_objs(csrc):
+    import subprocess
+    return subprocess.check_output(["make", "-s", "print-rxk-objs"], cwd=csrc, text=True).split()
+
+
+def test_every_kernel_object_reports_its_build_flags(built):
+    """The fence asks every object of the Makefile's RXK_OBJS (the one list of what an experiment build recompiles): each
+    defines its own t41::build_flags_<object>() (rx_experiments.hpp: T41RX_BUILD_FLAGS), and rx_dispatch.o, whose
+    kernel_build_flags() is their OR, references each of them.  An object that joins the list without one fails here."""
+    import subprocess
+    csrc = os.path.join(ROOT, "t41_sdr_amd", "csrc")
+    names = [o[:-2] for o in _rxk_objs(csrc)]
+    assert len(names) >= 9 and "rx_dispatch" in names and "cal_kernel" in names
+    symbols = lambda o: subprocess.check_output(["nm", "-C", os.path.join(csrc, o + ".o")], text=True).splitlines()  # noqa: E731
+    dispatch = symbols("rx_dispatch")
+    assert any(re.search(r"\bT t41::kernel_build_flags\(\)$", s) for s in dispatch)
+    for name in names:
+        if name == "rx_dispatch":
+            continue
+        fn = re.escape("t41::build_flags_%s()" % name)
+        assert any(re.search(r"\bT %s$" % fn, s) for s in symbols(name)), "%s.o does not define %s" % (name, fn)
+        assert any(re.search(r"\bU %s$" % fn, s) for s in dispatch), "rx_dispatch.o does not ask %s" % fn
+
+
+def _to_rebuild(csrc, *make_args):
+    """the objects `make -n` would compile"""
+    import subprocess
+    out = subprocess.check_output(["make", "-n"] + list(make_args), cwd=csrc, text=True)
+    return sorted(m.group(1) for m in re.finditer(r"^\S.* -c \S+ -o (\S+\.o)$", out, re.M))
+
+
+def test_objects_depend_on_their_flags_and_their_own_headers(built, tmp_path):
+    """The Makefile on the tree just built: with the same flags nothing is to do; with other KFLAGS exactly RXK_OBJS are
+    rebuilt (objects depend on their class's compile line); and header dependencies are the compiler's own, so a change
+    to a stage's header (here cw_kernels.hpp, in a copy of csrc) rebuilds that stage's kernel and the receive host, and
+    none of the fused rx512 kernels."""
+    import shutil
+    import subprocess
+    csrc = os.path.join(ROOT, "t41_sdr_amd", "csrc")
+    rxk = sorted(_rxk_objs(csrc))
+    assert subprocess.run(["make", "-q"], cwd=csrc).returncode == 0 and _to_rebuild(csrc) == []
+    assert _to_rebuild(csrc, "KFLAGS=-DT41RX_EXPERIMENT=1") == rxk
+    # a copy at the same depth (the rules name ../../include and ../libt41rx.so), with the times of the original
+    for d in ("include", "examples"):
+        shutil.copytree(os.path.join(ROOT, d), str(tmp_path / d), copy_function=shutil.copy2)
+    copy = str(tmp_path / "t41_sdr_amd" / "csrc")
+    shutil.copytree(csrc, copy, copy_function=shutil.copy2)
+    shutil.copy2(os.path.join(ROOT, "t41_sdr_amd", "libt41rx.so"), str(tmp_path / "t41_sdr_amd"))
+    assert _to_rebuild(copy) == []
+    os.utime(os.path.join(copy, "cw_kernels.hpp"))
+    again = _to_rebuild(copy)
+    host = subprocess.check_output(["make", "-s", "print-host-objs"], cwd=csrc, text=True).split()
+    assert "cw_kernel.o" in again and {o for o in host if o.startswith("rx_")} <= set(again), again
+    assert not [o for o in again if o.startswith("rx512_")] and not set(again) & set(rxk), again
+
+
+def test_the_environment_is_read_in_one_place():
+    """getenv occurs in rx_host.cpp only, and names the fence's opt-in, the tests' hook and the two variables of the
+    diagnostic builds (which t41rx_create() reads on a diagnostic library only): no kernel file, no dispatch and no stage
+    host consults the environment."""
+    csrc = os.path.join(ROOT, "t41_sdr_amd", "csrc")
+    found = {}
+    for name in sorted(os.listdir(csrc)):
+        if os.path.splitext(name)[1] in (".hpp", ".hip", ".cpp", ".h", ".inc"):
+            names = re.findall(r"getenv\s*\(\s*\"?(\w*)", open(os.path.join(csrc, name)).read())
+            if names:
+                found[name] = sorted(names)
+    assert found == {"rx_host.cpp": ["T41RX_ALLOW_EXPERIMENT", "T41RX_PIPE_STAT", "T41RX_SEG_RUN", "T41RX_STAMP_TAPS"]}, found
 
 
 def test_kernel_sources_carry_no_build_switches():

@@ -482,6 +482,23 @@ def test_d_refused_calls_change_nothing(T, N, kw):
     assert np.abs(plain).reshape(nch, nfr, Lf).max(axis=2)[:, 1:].min() > 0
 
 
+@pytest.mark.parametrize("stamp_taps", [None, "1"], ids=["unset", "T41RX_STAMP_TAPS"])
+def test_d_product_ignores_the_stamp_taps_variable(T, stamp_taps, monkeypatch):
+    """T41RX_STAMP_TAPS lets a -DT41RX_STAMP diagnostic build put its cycle stamps behind the demod tap at the long FFT
+    lengths.  The product library does not read it: with it in the environment, as without, the demod tap at fft_length
+    1024 is refused with T41RX_ERR_UNSUPPORTED.  One channel, no process call."""
+    import torch
+    from t41_sdr_amd import _lib
+    if stamp_taps is None:
+        monkeypatch.delenv("T41RX_STAMP_TAPS", raising=False)
+    else:
+        monkeypatch.setenv("T41RX_STAMP_TAPS", stamp_taps)  # before the context exists
+    rx = T.RxChain(1, T.default_params(fft_length=1024, **USB))
+    tap = torch.zeros(1, 512, device="cuda")
+    assert refused(T, lambda: rx.set_debug_taps(demod=tap)) == _lib.ERR_UNSUPPORTED
+    assert "stage taps" in T.load().t41rx_last_error().decode()
+
+
 def test_d_noise_blanker_carry_under_launch_parity(T):
     """fft_length 512, blanker on: its carry (last_frame_end) lives in two slots and `nb_sel` flips with every blanker
     launch.  Checkpoints behind x1 after one (odd) and two (even) launches are the same bytes; x2 continues bit for

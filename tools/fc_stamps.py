@@ -9,6 +9,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.environ.setdefault("T41RX_ALLOW_EXPERIMENT", "1")  # a diagnostic build: t41rx_create() refuses it otherwise
+os.environ.setdefault("T41RX_STAMP_TAPS", "1")  # ... and reads this at creation: the demod tap at fft_length 4096 holds the stamps
 import t41_sdr_amd as T  # noqa: E402
 
 NAMES = ["tail of the previous frame", "barrier (array free)", "assemble: loads -> LDS", "mask loads issued", "barrier",

@@ -43,7 +43,7 @@ def main():
     audio.set_ft8_tables()
     audio.set_ft8(1, nfr)
     audio.ft8_audio_begin()
-    # the live arms (tools/ft8_probe.py's `tap` and `on_256`): the same tone in the USB passband
+    # the live arms (tools/ft8_probe.py's `tap` and `on`): the same tone in the USB passband
     n = torch.arange(lfr * 2048, device="cuda", dtype=torch.float32)
     ph = 2 * torch.pi * (47000.0 / 192000.0) * n
     I = (0.1 * torch.cos(ph) + 0.02 * torch.randn(nch, lfr * 2048, device="cuda", generator=g)).contiguous()

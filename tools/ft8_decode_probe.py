@@ -9,7 +9,7 @@ Three waterfalls, every channel its own:
   signal  three transmissions of different levels over byte noise 0..19 (the tests' encoder, tests/ft8_codec.py), each
           channel at its own offsets
 hipEvents around each decode call, after warm-up; median, min and max in us per call.  Beside them the receive path of the
-same context with the FT8 stage on (tools/ft8_probe.py's arm `on_256`), timed at --frames frames per launch and scaled to
+same context with the FT8 stage on (tools/ft8_probe.py's arm `on`), timed at --frames frames per launch and scaled to
 the 1380 frames of a slot.  No threshold: the figures go into README.md and DESIGN.md.
 
   python tools/ft8_decode_probe.py [--channels 4096] [--frames 128] [--rounds 10] [--out FILE.json]

@@ -4,9 +4,9 @@ off and on, every channel synced (at 128 frames per launch each channel then run
 transforms), all arms interleaved in one process on one device.  hipEvents around each launch, after warm-up; median, min
 and max.
 
-The stage's two thread layouts are timed side by side: a workgroup of 256 threads per channel (the product) and one wave
-per channel (T41RX_FT8_THREADS=64, read at every launch).  `off` is the fused kernel alone; `tap` adds the demod tap the
-stage reads (the tap kernels), without the stage; `on_*` add the stage behind it.
+`off` is the fused kernel alone; `tap` adds the demod tap the stage reads (the tap kernels), without the stage; `on` adds
+the stage behind it (a workgroup of 256 threads per channel; the wave-per-channel layout once timed beside it is recorded
+in DESIGN.md, "FT8 receive", and gone from the library).
 
   python tools/ft8_probe.py [--channels 4096] [--frames 128] [--rounds 10] [--out FILE.json]
 """
@@ -28,7 +28,6 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    import numpy as np
     import torch
     import t41_sdr_amd as T
     if not torch.cuda.is_available():
@@ -41,13 +40,13 @@ def main():
     I = (0.1 * torch.cos(ph) + 0.02 * torch.randn(nch, nfr * 2048, device="cuda", generator=g)).contiguous()
     Q = (0.1 * torch.sin(ph) + 0.02 * torch.randn(nch, nfr * 2048, device="cuda", generator=g)).contiguous()
     out = torch.empty_like(I)
-    arms, threads = {}, {"on_256": "256", "on_64": "64"}
-    for name in ("off", "tap", "on_256", "on_64"):
+    arms = {}
+    for name in ("off", "tap", "on"):
         rx = T.RxChain(nch, T.default_params(mode=0))
         if name == "tap":
             tap = torch.zeros(nch, nfr * 256, dtype=torch.float32, device="cuda")
             rx.set_debug_taps(demod=tap)
-        if name in threads:
+        if name == "on":
             rx.set_ft8_tables()
             rx.set_ft8(1, nfr)
             rx.ft8_sync()
@@ -56,23 +55,17 @@ def main():
     blocks = {}
     for r in range(a.warmup + a.rounds):
         for k, rx in arms.items():
-            if k in threads:
-                os.environ["T41RX_FT8_THREADS"] = threads[k]
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             rx.ProcessIQData(I, Q, out=out)
             e1.record()
             e1.synchronize()
-            os.environ.pop("T41RX_FT8_THREADS", None)
             if r >= a.warmup:
                 times[k].append(e0.elapsed_time(e1) * 1e3)
-            if k in threads:  # blocks per channel in this launch: FT_8_counter moves by 8 or 9 (mod 92 across a slot's end)
+            if k == "on":  # blocks per channel in this launch: FT_8_counter moves by 8 or 9 (mod 92 across a slot's end)
                 blocks[k] = int(rx.ft8_status(nfr)[0, -1, 0])
-    # the two layouts compute the same thing
-    p = [arms[k].ft8_power().cpu().numpy() for k in threads]
-    s = [arms[k].ft8_state() for k in threads]
     res = {"channels": nch, "frames": nfr, "rounds": a.rounds, "device": torch.cuda.get_device_name(0), "unit": "us per launch",
-           "layouts_agree": bool(np.array_equal(p[0], p[1]) and np.array_equal(s[0], s[1])), "FT_8_counter_after": blocks}
+           "FT_8_counter_after": blocks}
     for k, t in times.items():
         res[k] = {"median": round(statistics.median(t), 1), "min": round(min(t), 1), "max": round(max(t), 1),
                   "per_frame": round(statistics.median(t) / nfr, 2)}

@@ -2,10 +2,12 @@
 """Register / LDS / spill table of every gfx950 kernel in a .hip file (no GPU needed).
 
 usage: python tools/kernel_resources.py [file.hip ...] [-D...] [--grep REGEX]   (default: every kernel translation unit of t41_sdr_amd/csrc)
-Compiles device-only with -Rpass-analysis=kernel-resource-usage and prints one line per kernel.
+Compiles device-only with the Makefile's compile line of the RX kernels (`make -s print-cc-rxk`, the -D arguments as its
+KFLAGS) and -Rpass-analysis=kernel-resource-usage, and prints one line per kernel.
 """
 import os
 import re
+import shlex
 import subprocess
 import sys
 
@@ -25,9 +27,9 @@ def main():
     # default: every translation unit of the RX kernels (one per kernel family)
     srcs = [os.path.abspath(f) for f in files] if files else [os.path.join(csrc, f) for f in ("rx512_ssb.hip", "rx512_am.hip", "rx512_nfm.hip", "rx512_sam.hip", "rx_long.hip",
                                                                "fastconv.hip", "display_kernel.hip", "nr_kernels.hip")]
-    procs = [subprocess.Popen(["hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-slp-vectorize", "-I" + os.path.join(ROOT, "include"),
-                               "--offload-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"] + defs,
-                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=os.path.dirname(os.path.abspath(src))) for src in srcs]
+    cc = shlex.split(subprocess.check_output(["make", "-s", "-C", csrc, "print-cc-rxk", "KFLAGS=" + " ".join(shlex.quote(d) for d in defs)], text=True))
+    procs = [subprocess.Popen(cc + ["-I" + csrc, "--offload-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"],
+                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=csrc) for src in srcs]
     err = ""
     for p in procs:
         _, e = p.communicate()
