@@ -16,7 +16,9 @@
  * arm_q15_to_float conversion of Process.cpp:107-108, i.e. float_buffer_L = I, _R = Q):
  *   I, Q   : const float [n_channels][n_frames * frame_len]   planar f32, read-only
  *   audio  : float       [n_channels][n_frames * frame_len]   mono f32 @192 kS/s
- *            (= float_buffer_L just before arm_float_to_q15, Process.cpp:929-936)
+ *            (= float_buffer_L just before arm_float_to_q15, Process.cpp:929-936; or, with
+ *            t41rx_set_audio_rate(T41RX_AUDIO_RATE_24K), [n_channels][n_frames * 256] @24 kS/s:
+ *            float_buffer_L in front of the interpolators, Process.cpp:917, times the volume)
  *   frame_len = BUFFER_SIZE * N_BLOCKS = 4 * fft_length  (2048 for FFT_LENGTH 512;
  *   SDT.h:39,70, T41_SDR.ino:368).
  *
@@ -315,6 +317,38 @@ T41RX_API int t41rx_frame_len(const t41rx_ctx *ctx);
 #define T41RX_LAYOUT_TIME_MAJOR 1
 T41RX_API int t41rx_set_buffer_layout(t41rx_ctx *ctx, int layout);
 T41RX_API int t41rx_get_buffer_layout(const t41rx_ctx *ctx);
+
+/* ---- audio at 24 kS/s: the receive chain without its interpolators (ABI 5) ----
+ * The firmware interpolates the finished audio x2 and x4 (Process.cpp:917-920) because the Teensy's DAC runs at 192 kS/s.
+ * A caller that streams, records or decodes the audio wants the 24 kS/s the demodulator works at, and takes it here.
+ *   T41RX_AUDIO_RATE_192K (default)  every process entry writes frame_len samples per channel and frame, as documented
+ *                                    with the entries;
+ *   T41RX_AUDIO_RATE_24K             every process entry -- device and host, f32 and q15, both buffer layouts, with or
+ *                                    without an input map and parameter sets -- writes 256 samples per channel and frame:
+ *                                    channel-major [n_channels][n_frames * 256], time-major [n_frames][n_channels][256].
+ *                                    The inputs keep their frames of frame_len samples.
+ * Sample i of a frame is float_buffer_L[i] as it stands in front of Process.cpp:917 -- behind the demodulator, the AGC and
+ * every optional stage that is on (equaliser, noise reduction, notch, blanker, CW filter) -- multiplied once, as an f32
+ * multiply of its own, by g = VolumeToAmplification(audioVolume) (Process.cpp:955-967): Process.cpp:929's factor without
+ * DF, which only makes up for the interpolators' zero stuffing.  With parameter sets g is the channel's own set's.  The
+ * q15 entries convert with the arm_float_to_q15 the 192 kS/s q15 output goes through (Process.cpp:936).
+ * The interpolator memories are neither read nor written at 24 kS/s: after a switch back to 192 kS/s the interpolators
+ * continue from what they last held, as the firmware's statics would if lines 917-920 were skipped meanwhile (the first
+ * frames' worth of their impulse responses, 24 + 8 samples of history, then belong to older audio).  t41rx_state_bytes(),
+ * the checkpoint layout and every section are the same at either rate; every other memory, side output, stage tap and
+ * stage (FT8, audio spectrum, display spectrum, panadapter, beacon monitor, CW detector and decoder) computes and
+ * holds what it does at 192 kS/s.
+ * The rate is configuration, like the buffer layout: in no checkpoint, kept across t41rx_reset / t41rx_set_state /
+ * t41rx_set_params, and it may change between any two calls.  fft_length 512 only: at a long fft_length
+ * T41RX_AUDIO_RATE_24K is refused with T41RX_ERR_UNSUPPORTED (the long-FFT pipeline's back kernel interpolates); an
+ * unknown rate is T41RX_ERR_ARG; a refused call leaves the rate as it was.
+ * t41rx_audio_frame_len(): samples per channel and frame the process entries write at the current rate, frame_len or 256
+ * (t41rx_frame_len() stays the input frame). */
+#define T41RX_AUDIO_RATE_192K 0
+#define T41RX_AUDIO_RATE_24K 1
+T41RX_API int t41rx_set_audio_rate(t41rx_ctx *ctx, int rate);
+T41RX_API int t41rx_get_audio_rate(const t41rx_ctx *ctx);
+T41RX_API int t41rx_audio_frame_len(const t41rx_ctx *ctx);
 
 /* ---- receiver groups: many channels on one shared I/Q stream (ABI 5) ----
  * One radio delivers one 192 kS/s stream and the channels of a context are the receivers tuned across it (NCOFreq per

@@ -88,6 +88,9 @@ SYMBOLS = {
     "t41rx_frame_len": (C.c_int, [_vp]),
     "t41rx_set_buffer_layout": (C.c_int, [_vp, C.c_int]),
     "t41rx_get_buffer_layout": (C.c_int, [_vp]),
+    "t41rx_set_audio_rate": (C.c_int, [_vp, C.c_int]),
+    "t41rx_get_audio_rate": (C.c_int, [_vp]),
+    "t41rx_audio_frame_len": (C.c_int, [_vp]),
     "t41rx_set_input_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int, C.c_int]),
     "t41rx_get_input_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int]),
     "t41rx_set_param_sets": (C.c_int, [_vp, C.POINTER(Params), C.c_int, C.POINTER(C.c_int32), C.c_int]),

@@ -96,15 +96,26 @@ static_assert(!Geo<0>::kResident || (Geo<0>::kH1 + 24 <= Geo<0>::kSlice && Geo<0
 //   * the mask comes from the set's global table in every set form, also where the plain form reads the workgroup's LDS copy;
 //   * a wave that runs a serial chain for other waves' channels takes the constants of the channel it serves (CoefBySet);
 //   * cf0, the pointer every fresh_coef() / load_taps() site re-derives from, is the set's block.
+// A24 (t41rx_set_audio_rate, T41RX_AUDIO_RATE_24K): the call's result is the audio @24 kS/s.  Behind the demodulator the
+// frame's 256 samples are multiplied by g = VolumeToAmplification(audioVolume) (sc[kScOutScale] / DF: the power of two DF
+// only makes up for the interpolators' zero stuffing), converted for q15 and stored to a.out, whose strides then count 256
+// samples per frame; the wave goes on to the next frame.  No interpolator runs, their windows are not staged in LDS and
+// their memories (kStInt1, kStInt2; on chip H1, hist2c) are neither read nor written.  It rides on PARTM like the map and
+// exists only as a twin of the mapped forms (PART + kPartMap [+ kPartSet] + kPartA24) without stage taps: a call without
+// an input map runs with an identity map, a call with taps or a chain-splitting stage ends in aud24_finish_kernel.
 constexpr int kPartMap = 4;
 constexpr int kPartSet = 8;
+constexpr int kPartA24 = 16;
 template <int MODE, bool DEBUG, int PARTM, bool PLAIN, bool AGC = false, bool WQ15 = false, bool SEGPAR = false, bool PIPE = false>
 __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 64), 4) void rx512_kernel(const RxArgs a) {
   T41RX_CLK_BEGIN();
   constexpr int PART = PARTM & 3;
   constexpr bool MAP = (PARTM & kPartMap) != 0;
   constexpr bool SET = (PARTM & kPartSet) != 0;
-  static_assert(PART <= 2 && (PARTM & ~(3 | kPartMap | kPartSet)) == 0, "PARTM = PART, PART + kPartMap, or PART + kPartMap + kPartSet");
+  constexpr bool A24 = (PARTM & kPartA24) != 0;
+  static_assert(PART <= 2 && (PARTM & ~(3 | kPartMap | kPartSet | kPartA24)) == 0,
+                "PARTM = PART, PART + kPartMap, or PART + kPartMap + kPartSet, each of the mapped ones with or without kPartA24");
+  static_assert(!A24 || (MAP && PART == 0 && !DEBUG && !SEGPAR), "the 24 kS/s form is a twin of the mapped FFT_LENGTH 512 kernels without taps");
   static_assert(!SET || (MAP && PART == 0 && !SEGPAR), "the set form is a twin of the mapped FFT_LENGTH 512 kernels");
   static_assert(!MAP || PART != 2, "the back end of the long-FFT pipeline reads no antenna samples");
   static_assert(!SEGPAR || (PART == 1 && MODE != kModeNfm) || (PART == 2 && MODE == kModeSsb && !AGC), "SEGPAR variants");
@@ -430,8 +441,10 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
         if (KEEP) {  // the rest of the channel's record: overlap block, interpolator histories
           ovl0 = *reinterpret_cast<const float4 *>(st + kStOverlap + 4 * lane);
           ovl1 = *reinterpret_cast<const float4 *>(st + kStOverlap + 256 + 4 * lane);
-          if (lane < 6) ovl2 = *reinterpret_cast<const float4 *>(st + kStInt1 + 4 * lane);
-          if (lane < 8) hist2c = st[kStInt2 + lane];
+          if (!A24) {
+            if (lane < 6) ovl2 = *reinterpret_cast<const float4 *>(st + kStInt1 + 4 * lane);
+            if (lane < 8) hist2c = st[kStInt2 + lane];
+          }
         }
       }
       // gains (Process.cpp:117-134, 165-166).  g_band and -IQAmp are folded into one factor on I
@@ -483,7 +496,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
         if (KEEP) {
           *reinterpret_cast<float4 *>(lds + G::kOV + 4 * lane) = ovl0;
           *reinterpret_cast<float4 *>(lds + G::kOV + 256 + 4 * lane) = ovl1;
-          if (lane < 6) *reinterpret_cast<float4 *>(lds + G::kH1 + 4 * lane) = ovl2;
+          if (!A24 && lane < 6) *reinterpret_cast<float4 *>(lds + G::kH1 + 4 * lane) = ovl2;
         }
       }
       STAMP(18);  // prologue c: delay lines -> LDS
@@ -875,7 +888,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
       if (!KEEP && (!SEGPAR || (seg0 == 0 && f == seg1 - 1))) {
         if (lane < 14) *reinterpret_cast<float4 *>(st + kStDec1 + 4 * lane) = lds4(lds + kX + 2 * xpad(2 * lane));
         if (lane < 24) *reinterpret_cast<float4 *>(st + kStDec2 + 4 * lane) = lds4(lds + kY1 + y1slot(lane));
-        if (PART != 1) {
+        if (PART != 1 && !A24) {
           if (lane < 6) hist1 = *reinterpret_cast<const float4 *>(st + kStInt1 + 4 * lane);
           if (lane < 8) hist2 = st[kStInt2 + lane];
         }
@@ -1512,6 +1525,39 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
       }
 
     }
+    if constexpr (A24) {
+      // ---- the call's result @24 kS/s: volume (Process.cpp:929 without DF) as a multiply of its own, arm_float_to_q15
+      // (Process.cpp:936), and stores of 16 bytes per lane to consecutive addresses -- one request of 1 KiB per frame
+      // (f32), of 512 B from the lower half of the wave (q15: a lane packs 8 samples)
+      const float g24 = fresh_coef(cf0)->sc[kScOutScale] * 0.125f;
+      {  // (arm_scale_f32: one rounding of its own, whatever produced the sample)
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) aud[j] = aud[j] * g24;
+      }
+      if (CONTIG && !WQ15) {  // the lane holds samples 4 lane .. 4 lane + 3 already
+        stg_stream(gO, fresh_off(4 * lane), make_float4(aud[0], aud[1], aud[2], aud[3]));
+      } else {
+        // time order through the wave's scratch (X[kScr ..), free behind the inverse transform like the x2 window it replaces)
+        float *tb = lds + kI1 + 24;
+        wave_sync();
+        if (CONTIG) {
+          *reinterpret_cast<float4 *>(tb + 4 * lane) = make_float4(aud[0], aud[1], aud[2], aud[3]);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) tb[lane + 64 * j] = aud[j];
+        }
+        wave_sync();
+        if (!WQ15) {
+          stg_stream(gO, fresh_off(4 * lane), lds4(tb + 4 * lane));
+        } else if (lane < 32) {
+          const float4 lo = lds4(tb + 8 * lane), hi = lds4(tb + 8 * lane + 4);
+          const uint4 q = make_uint4(q15_pack2(lo.x, lo.y), q15_pack2(lo.z, lo.w), q15_pack2(hi.x, hi.y), q15_pack2(hi.z, hi.w));
+          stg_stream(gO, fresh_off(4 * lane), make_float4(__uint_as_float(q.x), __uint_as_float(q.y), __uint_as_float(q.z), __uint_as_float(q.w)));
+        }
+      }
+      continue;
+    }
     if ((DEBUG || WQ15) && PART == 0 && a.aud_out) {
       // noise reduction / notch on (Process.cpp:841-866): those stages sit between the demodulator and the
       // interpolators and run in kernels of their own (nr_kernels.hip) on the whole call's audio; this kernel
@@ -1718,8 +1764,10 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
     if (lane < 24) *reinterpret_cast<float4 *>(st + kStDec2 + 4 * lane) = lds4(lds + kY1 + y1slot(lane));
     *reinterpret_cast<float4 *>(st + kStOverlap + 4 * lane) = lds4(lds + G::kOV + 4 * lane);
     *reinterpret_cast<float4 *>(st + kStOverlap + 256 + 4 * lane) = lds4(lds + G::kOV + 256 + 4 * lane);
-    if (lane < 6) *reinterpret_cast<float4 *>(st + kStInt1 + 4 * lane) = lds4(lds + G::kH1 + 4 * lane);
-    if (lane < 8) st[kStInt2 + lane] = (lane == 0) ? 0.0f : hist2c;
+    if (!A24) {
+      if (lane < 6) *reinterpret_cast<float4 *>(st + kStInt1 + 4 * lane) = lds4(lds + G::kH1 + 4 * lane);
+      if (lane < 8) st[kStInt2 + lane] = (lane == 0) ? 0.0f : hist2c;
+    }
   }
   if (PART != 2 && lane == 0) {
     if (!SEGPAR || seg0 == 0) {  // (SEGPAR: phase0 / dc_carry were advanced to the end of the call above)

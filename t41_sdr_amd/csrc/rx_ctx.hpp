@@ -217,6 +217,10 @@ struct t41rx_ctx {
   t41::DevBuf<char> d_agc_pipe;  // FFT_LENGTH 512, AGC on or SAM: the pipelined kernels' buffer (pipe_layout), allocated on first use
   int scratch_frames = 0;
   int layout = T41RX_LAYOUT_CHANNEL_MAJOR;  // of I / Q / audio (t41rx_set_buffer_layout)
+  // the rate the process entries return the audio at (t41rx_set_audio_rate).  Configuration like `layout`: in no
+  // checkpoint, untouched by reset / set_state / set_params.  24 kS/s: fft_length 512 only (the setter refuses)
+  int audio_rate = T41RX_AUDIO_RATE_192K;
+  t41::DevBuf<int32_t> d_ident24;  // [nchan] 0, 1, ..: the map of a 24 kS/s call without one (the fused 24 kS/s kernels are twins of the mapped forms)
   int nco_sel = 0;               // long FFT: which NcoState copy is current (flips with every process call)
   // the environment as t41rx_create() found it.  T41RX_SEG_RUN=n, a test hook: the long-FFT pipeline's run length, and at
   // FFT_LENGTH 4096 the two-kernel pipeline in place of the one-kernel form.  T41RX_PIPE_STAT / T41RX_STAMP_TAPS: read on
@@ -284,6 +288,11 @@ inline const char *split_stage_on(const t41rx_ctx *ctx) {
          : ctx->cw.det ? "the CW detector" : ctx->cw.dec ? "the CW decoder" : nullptr;
 }
 // rows of I / Q a process call reads: one per channel, or the input map's n_streams
+// samples per channel and frame the process entries write: the input frame, or its 256 samples @24 kS/s
+inline bool audio_24k(const t41rx_ctx *ctx) { return ctx->audio_rate == T41RX_AUDIO_RATE_24K; }
+inline int audio_frame_len(const t41rx_ctx *ctx) { return audio_24k(ctx) ? 256 : 4 * ctx->params.fft_length; }
+// rx_host.cpp: volume, conversion and stores of a 24 kS/s call from the scratch (launch_chain, cw_filter_run)
+int aud24_finish_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t s);
 inline int input_rows(const t41rx_ctx *ctx) { return ctx->n_streams > 0 ? ctx->n_streams : ctx->nchan; }
 
 // ---- helpers more than one file uses

@@ -30,9 +30,10 @@ static hipError_t launch_long(const RxArgs &a, int mode, bool pipeline, hipStrea
   return launch_long_back(a, mode, s);
 }
 
-hipError_t launch_rx(const RxArgs &a, int fft_length, int mode, bool long_pipeline, hipStream_t s) {
+hipError_t launch_rx(const RxArgs &a, int fft_length, int mode, bool long_pipeline, bool a24, hipStream_t s) {
   const bool debug = a.dbg_nco || a.dbg_dec || a.dbg_demod || a.spect || a.dbg_pre || a.aud_out;  // side outputs (and the NR hand-over) ride on the tap kernels
   if (fft_length == 1024 || fft_length == 2048 || fft_length == 4096) {
+    if (a24) return hipErrorInvalidValue;  // (t41rx_set_audio_rate refuses: the long-FFT pipeline's back kernel interpolates)
     if (a.seg * 512 != fft_length) return hipErrorInvalidValue;
     return launch_long(a, mode, long_pipeline, s);
   }
@@ -40,13 +41,13 @@ hipError_t launch_rx(const RxArgs &a, int fft_length, int mode, bool long_pipeli
   switch (mode) {
     case T41RX_DEMOD_USB:
     case T41RX_DEMOD_LSB:
-      return launch512_ssb(a, s, debug);
+      return launch512_ssb(a, s, debug, a24);
     case T41RX_DEMOD_AM:
-      return launch512_am(a, s, debug);
+      return launch512_am(a, s, debug, a24);
     case T41RX_DEMOD_NFM:
-      return launch512_nfm(a, s, debug);
+      return launch512_nfm(a, s, debug, a24);
     case T41RX_DEMOD_SAM:
-      return launch512_sam(a, s, debug);
+      return launch512_sam(a, s, debug, a24);
     default:
       return hipErrorInvalidValue;
   }

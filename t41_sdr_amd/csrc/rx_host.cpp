@@ -245,6 +245,23 @@ namespace {
 
 // ---- a process call: (a) prepare_call, (b) rx_args, (c) launch_chain
 
+// 24 kS/s (t41rx_set_audio_rate): does the call end in aud24_finish_kernel?  With a chain-splitting stage, and with anything
+// that puts the call on the tap kernels (rx_dispatch.hip: `debug`) -- stage taps, the audio spectrum, the display spectrum,
+// the FT8 stage's demod tap, the panadapter in a call with an update frame (pan_prepare has counted them).  Every other
+// 24 kS/s call stores from the fused kernel.
+bool finish24(const t41rx_ctx *ctx) {
+  return audio_24k(ctx) && (stages_on(ctx) || ctx->dbg_nco || ctx->dbg_dec || ctx->dbg_demod || ctx->spect || ctx->disp.spec || ctx->ft8.on ||
+                            (ctx->pan.on && ctx->pan.call_rows > 0));
+}
+// where (row, frame) of a call's I / Q or audio starts, in samples: rows of frames of `len` samples in the context's layout
+struct Strides {
+  long long chan, frame;
+};
+Strides strides_of(const t41rx_ctx *ctx, int rows, int frames, int len) {
+  if (ctx->layout == T41RX_LAYOUT_TIME_MAJOR) return Strides{len, (long long)rows * len};  // [frame][row][len]
+  return Strides{(long long)frames * len, len};
+}
+
 // (a) what the call needs allocated (stages and scratch on first use, kept) and the refusals that depend on the context
 int prepare_call(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
   const int seg = ctx->params.fft_length / 512;
@@ -256,7 +273,8 @@ int prepare_call(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
       (ctx->eq.on && (rc = ensure_eq(ctx)) != T41RX_OK) ||
       ((cw_filter_on(ctx) || cw_det_on(ctx)) && (rc = ensure_cw(ctx)) != T41RX_OK))
     return rc;
-  if ((seg > 1 || stages_on(ctx)) && n_frames > ctx->scratch_frames) {
+  // (24 kS/s with a stage tap or side output: the tap kernels hand the audio over like the stages' calls, finish24())
+  if ((seg > 1 || stages_on(ctx) || finish24(ctx)) && n_frames > ctx->scratch_frames) {
     // scratch between the kernels of the long-FFT pipeline / the noise-reduction pipeline (grown on demand, kept)
     HIP_TRY(hipStreamSynchronize(s));
     ctx->scratch_frames = 0;
@@ -315,17 +333,16 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
   a.nco = ctx->d_nco.get();
   a.nchan = ctx->nchan;
   a.nframes = seg * n_frames;  // 2048-sample segments
-  if (ctx->layout == T41RX_LAYOUT_TIME_MAJOR) {  // [frame][channel][frame_len] (fft_length 512: set_buffer_layout / set_params)
-    a.chan_stride = 2048;
-    a.frame_stride = (long long)ctx->nchan * 2048;
-  } else {
-    a.chan_stride = (long long)a.nframes * 2048;
-    a.frame_stride = 2048;
+  {  // time-major: [frame][channel][frame_len] (fft_length 512: set_buffer_layout / set_params)
+    const Strides io = strides_of(ctx, ctx->nchan, a.nframes, 2048);
+    a.chan_stride = io.chan;
+    a.frame_stride = io.frame;
   }
   if (ctx->n_streams > 0) {  // receiver groups: I / Q hold n_streams rows in the same layout, the output nchan as above
+    const Strides in = strides_of(ctx, ctx->n_streams, a.nframes, 2048);
     a.in_map = ctx->d_in_map.get();
-    a.in_chan_stride = a.chan_stride;
-    a.in_frame_stride = ctx->layout == T41RX_LAYOUT_TIME_MAJOR ? (long long)ctx->n_streams * 2048 : a.frame_stride;
+    a.in_chan_stride = in.chan;
+    a.in_frame_stride = in.frame;
   }
   a.seg = seg;
   a.nframes4k = n_frames;
@@ -388,13 +405,50 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
     a.tap_rows = ctx->pan.max_rows;
   }
   if (stages_on(ctx)) a.aud_out = ctx->d_aud24.get();  // the fused kernel stops behind the demodulator
+  if (finish24(ctx)) {
+    // 24 kS/s on the tap kernels: the same hand-over, and launch_chain() finishes from it (the strides above stay the
+    // input's: a tap kernel without a map places its input with them, and stores no audio)
+    a.aud_out = ctx->d_aud24.get();
+  } else if (audio_24k(ctx)) {
+    // 24 kS/s from the fused kernel, the twin of the call's mapped form: the input keeps its place under the map's
+    // strides (the identity when the caller set no map), the output's count frames of 256
+    if (!a.in_map) {
+      a.in_map = ctx->d_ident24.get();
+      a.in_chan_stride = a.chan_stride;
+      a.in_frame_stride = a.frame_stride;
+    }
+    const Strides o = strides_of(ctx, ctx->nchan, a.nframes, 256);
+    a.chan_stride = o.chan;
+    a.frame_stride = o.frame;
+  }
   return a;
 }
+
+}  // namespace
+
+// the finish of a 24 kS/s call that left its audio in the scratch (finish24()): volume, q15 conversion, the call's layout
+int t41::aud24_finish_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t s) {
+  const Strides o = strides_of(ctx, ctx->nchan, n_frames, 256);
+  Aud24Args f{};
+  f.aud = ctx->d_aud24.get();
+  f.out = a.out;
+  f.chan_stride = o.chan;
+  f.frame_stride = o.frame;
+  f.nchan = ctx->nchan;
+  f.nframes = n_frames;
+  f.q15 = a.q15;
+  f.coef = a.coef;      // (with parameter sets: the sets' array and the channels' table)
+  f.set_of = a.set_of;
+  return hip_check(launch_aud24_finish(f, s), "24 kS/s finish kernel launch");
+}
+
+namespace {
 
 // (c) the stage chain: fused front end, FT8 on the demodulated audio, then on the audio @24 kS/s the equalizer, noise
 // reduction / notch and the blanker, the CW detector, decoder and narrow filter, the back end, and the display stages
 int launch_chain(t41rx_ctx *ctx, RxArgs a, int n_frames, hipStream_t s) {
-  int rc = hip_check(launch_rx(a, ctx->params.fft_length, ctx->params.mode, ctx->seg_run_set, s), "kernel launch");
+  const bool a24 = audio_24k(ctx);
+  int rc = hip_check(launch_rx(a, ctx->params.fft_length, ctx->params.mode, ctx->seg_run_set, a24, s), "kernel launch");
   if (rc != T41RX_OK) return rc;
   if (ctx->ft8.on && (rc = ft8_run(ctx, a, n_frames, s)) != T41RX_OK) return rc;
   if (ctx->eq.on && (rc = eq_run(ctx, n_frames, s)) != T41RX_OK) return rc;
@@ -404,6 +458,9 @@ int launch_chain(t41rx_ctx *ctx, RxArgs a, int n_frames, hipStream_t s) {
   if (cw_dec_on(ctx) && (rc = cw_decode_run(ctx, n_frames, s)) != T41RX_OK) return rc;
   if (cw_filter_on(ctx)) {
     if ((rc = cw_filter_run(ctx, a, n_frames, s)) != T41RX_OK) return rc;
+  } else if (a24 && a.aud_out) {
+    // 24 kS/s: the volume and the stores alone (Process.cpp:929-937 without DF); the interpolator memories stay as they are
+    if ((rc = aud24_finish_run(ctx, a, n_frames, s)) != T41RX_OK) return rc;
   } else if (stages_on(ctx)) {
     // then the interpolators, volume and stores (Process.cpp:917-937) from a.aud24
     a.aud_out = nullptr;
@@ -715,6 +772,29 @@ int t41rx_get_input_map(const t41rx_ctx *ctx, int32_t *stream_of_channel_out, in
   return ctx->n_streams;
 }
 
+int t41rx_set_audio_rate(t41rx_ctx *ctx, int rate) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (rate != T41RX_AUDIO_RATE_192K && rate != T41RX_AUDIO_RATE_24K) return fail(T41RX_ERR_ARG, "unknown audio rate");
+  if (rate == T41RX_AUDIO_RATE_24K) {
+    if (ctx->params.fft_length != 512)
+      return fail(T41RX_ERR_UNSUPPORTED, "audio at 24 kS/s is built for fft_length 512 (the long-FFT pipeline's back kernel interpolates and stores at 192 kS/s)");
+    if (!ctx->d_ident24) {  // the map of a call without one: the fused 24 kS/s kernels are twins of the mapped forms
+      DeviceGuard g(ctx->device);
+      if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+      std::vector<int32_t> ident((size_t)ctx->nchan);
+      for (int i = 0; i < ctx->nchan; ++i) ident[(size_t)i] = i;
+      DevBuf<int32_t> fresh;
+      HIP_TRY(dev_alloc(fresh, sizeof(int32_t) * ident.size()));
+      HIP_TRY(hipMemcpy(fresh.get(), ident.data(), sizeof(int32_t) * ident.size(), hipMemcpyHostToDevice));
+      ctx->d_ident24 = std::move(fresh);
+    }
+  }
+  ctx->audio_rate = rate;  // (calls in flight were launched with the rate they found)
+  return T41RX_OK;
+}
+int t41rx_get_audio_rate(const t41rx_ctx *ctx) { return ctx ? ctx->audio_rate : T41RX_ERR_ARG; }
+int t41rx_audio_frame_len(const t41rx_ctx *ctx) { return ctx ? audio_frame_len(ctx) : T41RX_ERR_ARG; }
+
 int t41rx_n_channels(const t41rx_ctx *ctx) { return ctx ? ctx->nchan : T41RX_ERR_ARG; }
 int t41rx_frame_len(const t41rx_ctx *ctx) { return ctx ? 4 * ctx->params.fft_length : T41RX_ERR_ARG; }
 
@@ -736,8 +816,8 @@ int t41rx_process_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, const int16_t 
   if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
-  const size_t bytes = (size_t)ctx->nchan * (size_t)n_frames * (size_t)(4 * ctx->params.fft_length) * sizeof(int16_t);
-  const size_t in_bytes = bytes / (size_t)ctx->nchan * (size_t)input_rows(ctx);  // an input map: n_streams rows come in
+  const size_t in_bytes = (size_t)input_rows(ctx) * (size_t)n_frames * (size_t)(4 * ctx->params.fft_length) * sizeof(int16_t);  // an input map: n_streams rows come in
+  const size_t bytes = (size_t)ctx->nchan * (size_t)n_frames * (size_t)audio_frame_len(ctx) * sizeof(int16_t);
   int rc = ensure_staging(ctx, in_bytes, bytes);
   if (rc != T41RX_OK) return rc;
   HIP_TRY(hipMemcpy(ctx->staging.d_in_i.get(), Q_in_L, in_bytes, hipMemcpyHostToDevice));
@@ -755,8 +835,8 @@ int t41rx_process_host(t41rx_ctx *ctx, const float *I, const float *Q, float *au
   if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
-  const size_t nfl = (size_t)ctx->nchan * (size_t)n_frames * (size_t)(4 * ctx->params.fft_length);
-  const size_t in_fl = nfl / (size_t)ctx->nchan * (size_t)input_rows(ctx);  // an input map: n_streams rows come in
+  const size_t in_fl = (size_t)input_rows(ctx) * (size_t)n_frames * (size_t)(4 * ctx->params.fft_length);  // an input map: n_streams rows come in
+  const size_t nfl = (size_t)ctx->nchan * (size_t)n_frames * (size_t)audio_frame_len(ctx);
   {
     const int rc0 = ensure_staging(ctx, in_fl * sizeof(float), nfl * sizeof(float));
     if (rc0 != T41RX_OK) return rc0;

@@ -111,12 +111,31 @@ struct RxArgs {
 constexpr int tab_long_entries(int R) { return (R - 1) * 512 + R * 512; }
 
 // long_pipeline: FFT_LENGTH 4096 runs the two-kernel pipeline where the one-kernel form would (t41rx_ctx::seg_run)
-hipError_t launch_rx(const RxArgs &a, int fft_length, int mode, bool long_pipeline, hipStream_t s);
+// a24: the audio leaves @24 kS/s (t41rx_set_audio_rate; FFT_LENGTH 512): a.chan_stride / a.frame_stride place frames of 256
+// output samples (the input's strides are then a.in_chan_stride / a.in_frame_stride: the call carries a map), and either
+// the fused kernel stores them itself or, with a.aud_out set, the caller finishes with launch_aud24_finish()
+hipError_t launch_rx(const RxArgs &a, int fft_length, int mode, bool long_pipeline, bool a24, hipStream_t s);
 // what the kernel objects of this library were built as (rx_experiments.hpp; rx_dispatch.hip: the OR of every object's
 // own answer): 0 = the product, bit 1 = a diagnostic build (stamps / counters)
 int kernel_build_flags();
 // FFT_LENGTH 512, behind launch_rx() with aud_out set: interpolators, volume and stores from a.aud24 (f32 or q15 samples out)
 hipError_t launch_back512(const RxArgs &a, hipStream_t s);
+
+// The audio @24 kS/s as the call's result, behind the tap kernels and the chain-splitting stages (aud24_kernel.hip) in
+// place of launch_back512() / the CW path's interpolators: out = aud * g (one f32 multiply, Process.cpp:929 without DF),
+// arm_float_to_q15 for the q15 entries, in the call's layout.  The interpolator memories are not touched.
+struct Aud24Args {
+  const float *aud;        // [nchan][nframes * 256], time order (RxArgs::aud_out)
+  void *out;               // f32 or q15 samples, frames of 256
+  long long chan_stride;   // where (channel c, frame f) of out starts, in samples: c * chan_stride + f * frame_stride
+  long long frame_stride;
+  int nchan, nframes;
+  int q15;
+  // g = coef[set_of ? set_of[c] : 0].sc[kScOutScale] / DF: the context's block, or with parameter sets the channel's own set's
+  const DevCoef *coef;
+  const int *set_of;
+};
+hipError_t launch_aud24_finish(const Aud24Args &a, hipStream_t s);
 
 // display FFT (CalcZoom1Magn / ZoomFFTExe, FFT.cpp:67-251) on the dbg_pre tap of the frames just processed
 struct DispArgs {

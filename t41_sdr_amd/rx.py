@@ -96,6 +96,7 @@ class RxChain:
         self.device = int(device)
         self.frame_len = self._lib.t41rx_frame_len(self._ctx)
         self.layout = "channel"
+        self._audio_rate = 192000  # set_audio_rate
         self._n_streams = 0  # the input map's row count (set_input_map), 0 = no map
         if NCOFreq is not None:
             self.SetNCOFreq(NCOFreq)
@@ -139,6 +140,28 @@ class RxChain:
         code = {"channel": 0, "time": 1}[layout]
         check(self._lib.t41rx_set_buffer_layout(self._ctx, code))
         self.layout = layout
+
+    _AUDIO_RATES = {192000: 0, 24000: 1}  # T41RX_AUDIO_RATE_192K, T41RX_AUDIO_RATE_24K
+
+    def set_audio_rate(self, rate):
+        """192000 (default): the process calls return frame_len samples per channel and frame, the firmware's DAC rate;
+        24000: the audio as it leaves the demodulator and the stages behind it, times VolumeToAmplification(audioVolume),
+        256 samples per channel and frame, no interpolators (t41rx_set_audio_rate; FFT_LENGTH 512).  Configuration, like
+        the buffer layout; a refused change leaves the rate as it was."""
+        if isinstance(rate, bool) or rate not in self._AUDIO_RATES:
+            raise ValueError("audio rate must be 24000 or 192000, got %r" % (rate,))
+        check(self._lib.t41rx_set_audio_rate(self._ctx, self._AUDIO_RATES[rate]))
+        self._audio_rate = int(rate)
+
+    @property
+    def audio_rate(self):
+        """samples per second of the audio the process calls return: 192000 or 24000"""
+        return getattr(self, "_audio_rate", 192000)
+
+    @property
+    def audio_frame_len(self):
+        """samples per channel and frame the process calls return: frame_len, or 256 at 24 kS/s"""
+        return 256 if self.audio_rate == 24000 else self.frame_len
 
     def set_input_map(self, stream_of_channel, n_streams=None):
         """Receiver groups (t41rx_set_input_map): channel c reads row stream_of_channel[c] of I / Q, which then hold
@@ -513,7 +536,8 @@ class RxChain:
 
         torch CUDA tensors [n_channels, n_frames*frame_len] (float32, contiguous) run on the
         current torch stream without synchronising and return a tensor; numpy arrays go
-        through the host-pointer entry point and return a numpy array.
+        through the host-pointer entry point and return a numpy array.  The result (and `out`) holds
+        audio_frame_len samples per channel and frame: frame_len, or 256 after set_audio_rate(24000).
         """
         return self._process(float_buffer_L, float_buffer_R, out, "float32", F32P, self._lib.t41rx_process_host, self._lib.t41rx_process_device,
                              "I/Q must be contiguous float32 CUDA tensors", "I/Q live on another device than this RxChain")
@@ -788,8 +812,8 @@ class RxChain:
     def _out_shape(self, nfr):
         """the audio's shape for a call of nfr frames: n_channels rows, whatever the input map makes of the input's"""
         if self.layout == "time":
-            return (nfr, self.n_channels, self.frame_len)
-        return (self.n_channels, nfr * self.frame_len)
+            return (nfr, self.n_channels, self.audio_frame_len)
+        return (self.n_channels, nfr * self.audio_frame_len)
 
     def _rows_text(self):
         return "(n_channels=%d, n_streams=%d)" % (self.n_channels, self.n_streams)
