@@ -30,14 +30,14 @@ hipError_t launch_fastconv(const RxArgs &a, bool cplx, bool fused_back, hipStrea
 }
 
 // FFT_LENGTH 4096, SSB audio with the fixed gain, f32 samples: the whole chain in one kernel
-hipError_t launch_fastconv_fused(const RxArgs &a, hipStream_t s) {
+hipError_t launch_fastconv_fused(const RxArgs &a, const KernelForm &k, hipStream_t s) {
   // (an input map -- receiver groups -- selects the same kernel in its mapped form; no call without a map reaches it)
   return with_bools(
       [&](auto PLN, auto MAP) {
         if constexpr (MAP) return launch_fc<&fastconv_fused_map_kernel<PLN>, fcb_lds_floats(8)>(a, s);
         else return launch_fc<&fastconv_fused_kernel<PLN>, fcb_lds_floats(8)>(a, s);
       },
-      a.plain != 0, a.in_map != nullptr);
+      k.plain, k.map_form);
 }
 
 T41RX_CLK_READER(t41rx_debug_read_clk_fc)

@@ -3,7 +3,7 @@
 
 namespace t41 {
 
-hipError_t launch512_am(const RxArgs &a, hipStream_t s, bool debug, bool a24) { return launch512<kModeAm>(a, s, debug, a24); }
+hipError_t launch512_am(const RxArgs &a, const KernelForm &k, hipStream_t s) { return launch512<kModeAm>(a, k, s); }
 
 T41RX_CLK_READER(t41rx_debug_read_clk_am)
 T41RX_BUILD_FLAGS(rx512_am)

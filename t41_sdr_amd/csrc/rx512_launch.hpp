@@ -1,6 +1,6 @@
 // t41_sdr_amd/csrc/rx512_launch.hpp -- the one launcher of rx512_kernel (grid and block from the kernel's own geometry)
-// and the rules that pick the instantiation for an FFT_LENGTH 512 call; included by the translation units that
-// instantiate the kernel (one per demodulator family, and rx_long.hip).
+// and launch512(), which instantiates the form an FFT_LENGTH 512 call's plan names (the rules are rx_plan.hpp's);
+// included by the translation units that instantiate the kernel (one per demodulator family, and rx_long.hip).
 #pragma once
 #include "rx512_kernel.hpp"
 #include "rx_launch.hpp"
@@ -32,33 +32,16 @@ static hipError_t launch_rx512(const RxArgs &a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// FFT_LENGTH 512, the whole chain in one kernel (PART 0).  `debug`: side outputs / stage taps.  `a24`: the audio leaves
-// @24 kS/s -- a.out's strides count 256 samples per frame; with `debug` the host has set a.aud_out and finishes the call
-// itself (launch_aud24_finish), without it the call takes the 24 kS/s twin of its mapped form and carries a map.
+// FFT_LENGTH 512, the whole chain in one kernel (PART 0): the instantiation the call's plan names (rx_plan.hpp).
 template <int MODE>
-static hipError_t launch512(const RxArgs &a, hipStream_t s, bool debug, bool a24) {
-  constexpr bool SAM = MODE == kModeSam;
-  // the side outputs / stage taps and the synchronous detector run on the general front end
-  const bool plain = a.plain && !debug && !SAM;
-  // the pipelined variants (agc_prep_pipe, sam_chain_pipe, PSA): calls of four frames or more without taps; shorter
-  // calls have nothing to overlap and take the barrier form, which computes the same values
-  const bool pipe = (a.agc || SAM) && a.agc_pipe && !debug && a.nframes >= 4;
-  // an input map changes none of the rules above: a mapped call takes the instantiation the same call would take without
-  // the map, in its mapped form, and a call without a map never reaches a mapped one.  Parameter sets likewise: the
-  // host has made sure that every set answers the rules above alike (t41rx_param_sets_compatible) and passes an input
-  // map with them, so the call takes the set twin of the mapped instantiation; a call without sets never reaches one
-  if (a.set_of != nullptr && (a.in_map == nullptr || a.set_gain == nullptr)) return hipErrorInvalidValue;
-  // the 24 kS/s rate likewise: the twin of the mapped instantiation the call would take @192 kS/s (an identity map from the
-  // host when the caller set none); the tap kernels hand the audio over instead (a.aud_out) and have no such twin
-  const bool fused24 = a24 && !debug;
-  if ((fused24 && a.in_map == nullptr) || (a24 && debug && a.aud_out == nullptr)) return hipErrorInvalidValue;
+static hipError_t launch512(const RxArgs &a, const KernelForm &k, hipStream_t s) {
   return with_bools(
       [&](auto DBG, auto PLN, auto AGC, auto Q15, auto PIPE, auto MAP, auto SET, auto A24) {
-        // what the rules above never select is not compiled
-        if constexpr ((DBG && (PLN || PIPE)) || (PLN && SAM) || (PIPE && !(AGC || SAM)) || (SET && !MAP) || (A24 && (!MAP || DBG))) return hipErrorInvalidValue;
+        // what the plan never names is not compiled
+        if constexpr (!form_compiled(MODE == kModeSam, DBG, PLN, AGC, PIPE, MAP, SET, A24)) return hipErrorInvalidValue;
         else return launch_rx512<MODE, DBG, 0, PLN, AGC, Q15, false, PIPE, MAP, SET, A24>(a, s);
       },
-      debug, plain, a.agc != 0, a.q15 != 0, pipe, a.in_map != nullptr, a.set_of != nullptr, fused24);
+      k.taps, k.plain, k.agc, k.q15, k.pipe, k.map_form, k.set_form, k.a24_form);
 }
 
 }  // namespace t41

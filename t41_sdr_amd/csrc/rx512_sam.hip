@@ -4,7 +4,7 @@
 
 namespace t41 {
 
-hipError_t launch512_sam(const RxArgs &a, hipStream_t s, bool debug, bool a24) { return launch512<kModeSam>(a, s, debug, a24); }
+hipError_t launch512_sam(const RxArgs &a, const KernelForm &k, hipStream_t s) { return launch512<kModeSam>(a, k, s); }
 
 T41RX_CLK_READER(t41rx_debug_read_clk_sam)
 T41RX_BUILD_FLAGS(rx512_sam)

@@ -177,9 +177,9 @@ struct Calibration {
 
 // parameter sets (t41rx_set_param_sets; rx_sets.cpp): the extra sets 1..K with their designed blobs, the channels' table,
 // and what the set kernels read -- the coefficient blocks [K + 1], the constant tables [K + 1][kTabEntries512], the first
-// stage's gains [K + 1] (entry 0 of each is the context's own set, kept in step with d_coef / d_tab), the table, and the
-// identity input map a context with sets and no input map runs with.  Configuration like the input map: in no
-// checkpoint, untouched by reset / set_state.  K == 0: no sets, nothing allocated, the calls pass what they always passed.
+// stage's gains [K + 1] (entry 0 of each is the context's own set, kept in step with d_coef / d_tab) and the table.
+// Configuration like the input map: in no checkpoint, untouched by reset / set_state.  K == 0: no sets, nothing
+// allocated, the calls pass what they always passed.
 struct ParamSets {
   std::vector<t41rx_params> params;        // [K]
   std::vector<std::vector<float>> blobs;   // [K]
@@ -187,7 +187,7 @@ struct ParamSets {
   DevBuf<DevCoef> d_coef;
   DevBuf<float2> d_tab;
   DevBuf<SetGains> d_gain;
-  DevBuf<int32_t> d_set_of, d_ident;
+  DevBuf<int32_t> d_set_of;
 };
 
 // staging for t41rx_process_host
@@ -220,7 +220,9 @@ struct t41rx_ctx {
   // the rate the process entries return the audio at (t41rx_set_audio_rate).  Configuration like `layout`: in no
   // checkpoint, untouched by reset / set_state / set_params.  24 kS/s: fft_length 512 only (the setter refuses)
   int audio_rate = T41RX_AUDIO_RATE_192K;
-  t41::DevBuf<int32_t> d_ident24;  // [nchan] 0, 1, ..: the map of a 24 kS/s call without one (the fused 24 kS/s kernels are twins of the mapped forms)
+  // [nchan] 0, 1, ..: the map of a call that takes a mapped form without a map of the caller's (CallPlan::need_ident: the
+  // set forms and the fused 24 kS/s forms are twins of the mapped ones), made by the first such call
+  t41::DevBuf<int32_t> d_ident;
   int nco_sel = 0;               // long FFT: which NcoState copy is current (flips with every process call)
   // the environment as t41rx_create() found it.  T41RX_SEG_RUN=n, a test hook: the long-FFT pipeline's run length, and at
   // FFT_LENGTH 4096 the two-kernel pipeline in place of the one-kernel form.  T41RX_PIPE_STAT / T41RX_STAMP_TAPS: read on
@@ -260,7 +262,9 @@ inline int hip_check(hipError_t e, const char *what) { return e == hipSuccess ? 
     if (e__ != hipSuccess) return t41::hip_fail(e__, #expr); \
   } while (0)
 
-// ---- which stages a process call runs
+// ---- which stages a process call runs.  These are the switches; which kernels a call runs with them -- the tap kernels,
+// the hand-over, the scratch, the pipelined forms, the back end -- is decided once per call by plan_call() (rx_plan.hpp),
+// from the CallFacts the process call fills with these predicates (rx_host.cpp: call_facts)
 inline bool nr_on(const t41rx_ctx *ctx) { return ctx->params.nrOptionSelect != 0 || ctx->params.ANR_notchOn != 0; }  // (fft_length 512: params_valid)
 // the CW block runs in T41State == CW_RECEIVE (Process.cpp:878), which in receive is xmtMode == CW_MODE
 // (T41_SDR.ino:1039-1040, 1144-1148); with another xmtMode the switches are kept and nothing runs
@@ -268,13 +272,6 @@ inline bool cw_filter_on(const t41rx_ctx *ctx) { return ctx->params.xmtMode == T
 inline bool cw_det_on(const t41rx_ctx *ctx) { return ctx->params.xmtMode == T41RX_CW_MODE && ctx->cw.det != 0; }
 // the decoder runs exactly when the detector runs (in the firmware one decoderFlag gates both, CWProcessing.cpp:322-372)
 inline bool cw_dec_on(const t41rx_ctx *ctx) { return cw_det_on(ctx) && ctx->cw.dec != 0; }
-// the fused kernel stops behind the demodulator; stage kernels; back kernel (fft_length 512: t41rx_set_noise_blanker,
-// t41rx_set_receive_eq, t41rx_set_cw_filter, t41rx_set_cw_detector)
-inline bool stages_on(const t41rx_ctx *ctx) { return ctx->eq.on || nr_on(ctx) || ctx->nb.on || cw_filter_on(ctx) || cw_det_on(ctx); }
-// the pipelined kernels' buffer: AGC on (with the synchronous detector behind it: PSA), or the synchronous detector alone
-inline bool pipe_on(const t41rx_ctx *ctx, int n_frames) {
-  return (ctx->params.AGCMode != 0 || ctx->params.mode == T41RX_DEMOD_SAM) && ctx->params.fft_length == 512 && n_frames >= 4;
-}
 // parameter sets: loaded, and what a chain-splitting stage's switch answers then (those stages read set 0's parameters
 // on the host; rx_sets.cpp refuses in the other order with split_stage_on())
 inline bool sets_loaded(const t41rx_ctx *ctx) { return !ctx->sets.params.empty(); }
@@ -314,6 +311,7 @@ constexpr int kBaseOffset[5] = {24, 10, 58, 120, 200};
 void fill_dev_coef(const BlobView &v, DevCoef &dc);
 void fill_tab512(const BlobView &v, int fft_length, std::vector<float2> &tab);
 bool gains_of(const float *scalars, SetGains &g);  // returns plain
+CallFacts params_facts(const t41rx_params &p, bool plain_gains);  // what plan_call() reads of a parameter struct
 int upload_nco(t41rx_ctx *ctx);
 // rx_sets.cpp: set 0 changed (set_params / set_coeffs) -- the rule against the loaded sets, and entry 0 of the set arrays
 int sets_check_set0(const t41rx_ctx *ctx, const t41rx_params &p);
@@ -347,12 +345,12 @@ int ensure_cw_decode(t41rx_ctx *ctx);
 const char *cw_split_stage(const t41rx_ctx *ctx);
 int cw_detect_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
 int cw_decode_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
-int cw_filter_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t s);  // the narrow filter and its back end
+int cw_filter_run(t41rx_ctx *ctx, const CallPlan &plan, const RxArgs &a, int n_frames, hipStream_t s);  // the narrow filter and its back end
 int check_cw_decode(const t41rx_ctx *ctx, const int32_t *hdr, const float *sec);
 int cw_decode_reset(t41rx_ctx *ctx, size_t bytes);
 // rx_ft8.cpp
-int ft8_prepare(t41rx_ctx *ctx, int n_frames, hipStream_t s);  // the call's refusals, the memory and the demod tap of its own
-int ft8_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t s);
+int ft8_prepare(t41rx_ctx *ctx, const CallPlan &plan, int n_frames, hipStream_t s);  // the call's refusals, the memory and the demod tap of its own
+int ft8_run(t41rx_ctx *ctx, const CallPlan &plan, const RxArgs &a, int n_frames, hipStream_t s);
 int ft8_power_on(t41rx_ctx *ctx);
 // rx_ft8_decode.cpp
 void ft8_decode_release(t41rx_ctx *ctx);  // t41rx_destroy(): the pinned copy and the event

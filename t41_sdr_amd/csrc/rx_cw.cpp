@@ -127,7 +127,7 @@ int cw_decode_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
   return hip_check(launch_cw_decode(d, s), "CW decoder kernel launch");
 }
 
-int cw_filter_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t s) {
+int cw_filter_run(t41rx_ctx *ctx, const CallPlan &plan, const RxArgs &a, int n_frames, hipStream_t s) {
   // Process.cpp:882-912: the narrow filter CWFilterIndex selects, on its own memory
   CwFilterArgs f{};
   f.aud = ctx->d_aud24.get();
@@ -139,7 +139,7 @@ int cw_filter_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t s) 
   hipError_t e = launch_cw_filter(f, s);
   if (e != hipSuccess) return hip_fail(e, "CW filter kernel launch");
   // 24 kS/s (t41rx_set_audio_rate): the filtered audio is the result -- volume and stores, no interpolator
-  if (audio_24k(ctx)) return aud24_finish_run(ctx, a, n_frames, s);
+  if (plan.back == Back::cw_24k) return aud24_finish_run(ctx, a, n_frames, s);
   // then the interpolators, volume and stores (Process.cpp:917-937) in the firmware's own operations and order
   // (cw_back_kernel): the narrow filter's audio is held to the oracle's interpolators bit for bit
   const BlobView v = blob_view(ctx->blob.data());

@@ -13,44 +13,29 @@ int kernel_build_flags() {
 }
 
 // FFT_LENGTH 512 R (R = 2, 4, 8): front half (R segments per frame) -> N-point fast convolution -> back half
-static hipError_t launch_long(const RxArgs &a, int mode, bool pipeline, hipStream_t s) {
-  // FFT_LENGTH 4096, SSB audio with the fixed gain, f32 samples: the whole chain in one kernel (`pipeline`, the
-  // context's T41RX_SEG_RUN, selects the two-kernel pipeline: the tests that compare the two)
-  if (a.seg == 8 && mode != T41RX_DEMOD_NFM && mode != T41RX_DEMOD_AM && !a.agc && !a.q15 && !pipeline) {
-    return launch_fastconv_fused(a, s);
-  }
-  hipError_t e = launch_long_front(a, mode, s);
+static hipError_t launch_long(const RxArgs &a, const CallPlan &p, hipStream_t s) {
+  if (p.one_kernel) return launch_fastconv_fused(a, p.form, s);
+  hipError_t e = launch_long_front(a, p.form, s);
   if (e != hipSuccess) return e;
-  const bool cplx = a.agc || mode == T41RX_DEMOD_AM;
-  // real audio with the fixed gain, f32 samples out: the interpolators run behind pass 3 of the
-  // fast convolution (no `aud24` round trip, no third kernel)
-  const bool fused = !cplx && !a.q15;
-  e = launch_fastconv(a, cplx, fused, s);
-  if (e != hipSuccess || fused) return e;
-  return launch_long_back(a, mode, s);
+  e = launch_fastconv(a, p.cplx, p.fused_back, s);
+  if (e != hipSuccess || p.fused_back) return e;
+  return launch_long_back(a, p.form, s);
 }
 
-hipError_t launch_rx(const RxArgs &a, int fft_length, int mode, bool long_pipeline, bool a24, hipStream_t s) {
-  const bool debug = a.dbg_nco || a.dbg_dec || a.dbg_demod || a.spect || a.dbg_pre || a.aud_out;  // side outputs (and the NR hand-over) ride on the tap kernels
-  if (fft_length == 1024 || fft_length == 2048 || fft_length == 4096) {
-    if (a24) return hipErrorInvalidValue;  // (t41rx_set_audio_rate refuses: the long-FFT pipeline's back kernel interpolates)
-    if (a.seg * 512 != fft_length) return hipErrorInvalidValue;
-    return launch_long(a, mode, long_pipeline, s);
+hipError_t launch_rx(const RxArgs &a, const CallPlan &p, hipStream_t s) {
+  if (!p.valid || a.seg != p.seg) return hipErrorInvalidValue;
+  if (p.seg > 1) return launch_long(a, p, s);
+  // the one guard: the plan and the arguments agree on the tap kernels (side outputs and the hand-over ride on them).
+  // rx_args() fills the pointers from the same plan, so this is not reached
+  const bool debug = a.dbg_nco || a.dbg_dec || a.dbg_demod || a.spect || a.dbg_pre || a.aud_out;
+  if (debug != p.form.taps) return hipErrorInvalidValue;
+  switch (p.form.family) {
+    case Family::ssb: return launch512_ssb(a, p.form, s);
+    case Family::am: return launch512_am(a, p.form, s);
+    case Family::nfm: return launch512_nfm(a, p.form, s);
+    case Family::sam: return launch512_sam(a, p.form, s);
   }
-  if (fft_length != 512) return hipErrorInvalidValue;
-  switch (mode) {
-    case T41RX_DEMOD_USB:
-    case T41RX_DEMOD_LSB:
-      return launch512_ssb(a, s, debug, a24);
-    case T41RX_DEMOD_AM:
-      return launch512_am(a, s, debug, a24);
-    case T41RX_DEMOD_NFM:
-      return launch512_nfm(a, s, debug, a24);
-    case T41RX_DEMOD_SAM:
-      return launch512_sam(a, s, debug, a24);
-    default:
-      return hipErrorInvalidValue;
-  }
+  return hipErrorInvalidValue;
 }
 
 }  // namespace t41

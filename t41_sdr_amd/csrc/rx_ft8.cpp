@@ -40,7 +40,7 @@ int ft8_power_on(t41rx_ctx *ctx) {
   return hip_check(hipMemset(ctx->ft8.d_state.get(), 0, sizeof(int32_t) * kFt8Words * (size_t)ctx->nchan), "FT8 reset");
 }
 
-int ft8_prepare(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
+int ft8_prepare(t41rx_ctx *ctx, const CallPlan &plan, int n_frames, hipStream_t s) {
   if (ctx->params.mode != T41RX_DEMOD_USB)
     return fail(T41RX_ERR_UNSUPPORTED, "FT8 receive: the firmware demodulates DEMOD_FT8 as USB (Process.cpp:616-617); this context's mode is not T41RX_DEMOD_USB");
   for (const t41rx_params &p : ctx->sets.params)  // (parameter sets: FT8 runs on every channel)
@@ -48,7 +48,7 @@ int ft8_prepare(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
       return fail(T41RX_ERR_UNSUPPORTED, "FT8 receive: the firmware demodulates DEMOD_FT8 as USB (Process.cpp:616-617); a loaded parameter set's mode is not T41RX_DEMOD_USB");
   if (n_frames > ctx->ft8.frames) return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the FT8 status buffer was set with");
   if (const int rc = ensure_ft8(ctx)) return rc;
-  if (!stages_on(ctx) && !ctx->dbg_demod && n_frames > ctx->ft8.tap_frames) {
+  if (plan.ft8_own_tap && n_frames > ctx->ft8.tap_frames) {
     // the demod tap of the context's own (grown on demand, kept)
     HIP_TRY(hipStreamSynchronize(s));
     ctx->ft8.tap_frames = 0;
@@ -60,10 +60,10 @@ int ft8_prepare(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
 }
 
 // Process.cpp:627-685 on float_buffer_L as the demodulator and the AGC leave it, in front of the equalizer: the
-// hand-over buffer when other stages split the chain, else the demod tap.  The stage only reads the audio.
-int ft8_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t s) {
+// hand-over buffer when the call has one, else the demod tap (the plan's ft8_source).  The stage only reads the audio.
+int ft8_run(t41rx_ctx *ctx, const CallPlan &plan, const RxArgs &a, int n_frames, hipStream_t s) {
   Ft8Args f{};
-  f.aud = a.aud_out ? a.aud_out : a.dbg_demod;
+  f.aud = plan.ft8_source == Ft8Source::handover ? a.aud_out : a.dbg_demod;
   f.state = ctx->ft8.d_state.get();
   f.power = ctx->ft8.power;
   f.status = ctx->ft8.status;

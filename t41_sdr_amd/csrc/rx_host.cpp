@@ -102,6 +102,18 @@ void t41::fill_dev_coef(const BlobView &v, DevCoef &dc) {
   std::memcpy(dc.deemph, kDeemphFir24000, sizeof(float) * kDeemphTaps);
 }
 
+// what plan_call() reads of a parameter struct (the process call adds the context's part; rx_sets.cpp compares two sets)
+CallFacts t41::params_facts(const t41rx_params &p, bool plain_gains) {
+  CallFacts f;
+  f.seg = p.fft_length / 512;
+  f.family = p.mode == T41RX_DEMOD_AM ? Family::am : p.mode == T41RX_DEMOD_NFM ? Family::nfm : p.mode == T41RX_DEMOD_SAM ? Family::sam : Family::ssb;
+  f.agc = p.AGCMode != 0;
+  f.nfm_atan = p.mode == T41RX_DEMOD_NFM && p.nfm_demod == 1;
+  f.plain_gains = plain_gains;
+  f.nr = p.nrOptionSelect != 0 || p.ANR_notchOn != 0;
+  return f;
+}
+
 // the first stage's gains of a blob's scalars, and whether they are `plain`
 bool t41::gains_of(const float *sc, SetGains &g) {
   const bool iq_on = sc[kScIqCorrOn] != 0.0f;
@@ -245,13 +257,30 @@ namespace {
 
 // ---- a process call: (a) prepare_call, (b) rx_args, (c) launch_chain
 
-// 24 kS/s (t41rx_set_audio_rate): does the call end in aud24_finish_kernel?  With a chain-splitting stage, and with anything
-// that puts the call on the tap kernels (rx_dispatch.hip: `debug`) -- stage taps, the audio spectrum, the display spectrum,
-// the FT8 stage's demod tap, the panadapter in a call with an update frame (pan_prepare has counted them).  Every other
-// 24 kS/s call stores from the fused kernel.
-bool finish24(const t41rx_ctx *ctx) {
-  return audio_24k(ctx) && (stages_on(ctx) || ctx->dbg_nco || ctx->dbg_dec || ctx->dbg_demod || ctx->spect || ctx->disp.spec || ctx->ft8.on ||
-                            (ctx->pan.on && ctx->pan.call_rows > 0));
+// what the call is, for plan_call() (rx_plan.hpp); behind pan_prepare(), which counts the call's panadapter rows
+CallFacts call_facts(const t41rx_ctx *ctx, int n_frames, bool q15) {
+  SetGains g;
+  CallFacts f = params_facts(ctx->params, gains_of(blob_view(const_cast<float *>(ctx->blob.data())).scalars, g));
+  f.q15 = q15;
+  f.n_frames = n_frames;
+  f.seg_run_set = ctx->seg_run_set;
+  f.map = ctx->n_streams > 0;
+  f.sets = sets_loaded(ctx);
+  f.a24 = audio_24k(ctx);
+  // (a diagnostic library's stamps ride behind the demod tap pointer at the long lengths, T41RX_STAMP_TAPS: no tap to the plan)
+  const bool taps = f.seg == 1 || !ctx->stamp_taps;
+  f.tap_nco = taps && ctx->dbg_nco;
+  f.tap_dec = taps && ctx->dbg_dec;
+  f.tap_demod = taps && ctx->dbg_demod;
+  f.spect = ctx->spect != nullptr;
+  f.disp = ctx->disp.spec != nullptr;
+  f.pan_rows = ctx->pan.on && ctx->pan.call_rows > 0;
+  f.ft8 = ctx->ft8.on != 0;
+  f.eq = ctx->eq.on != 0;
+  f.nb = ctx->nb.on != 0;
+  f.cw_filter = cw_filter_on(ctx);
+  f.cw_det = cw_det_on(ctx);
+  return f;
 }
 // where (row, frame) of a call's I / Q or audio starts, in samples: rows of frames of `len` samples in the context's layout
 struct Strides {
@@ -263,41 +292,43 @@ Strides strides_of(const t41rx_ctx *ctx, int rows, int frames, int len) {
 }
 
 // (a) what the call needs allocated (stages and scratch on first use, kept) and the refusals that depend on the context
-int prepare_call(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
-  const int seg = ctx->params.fft_length / 512;
+int prepare_call(t41rx_ctx *ctx, const CallPlan &plan, int n_frames, hipStream_t s) {
   int rc = T41RX_OK;
-  // the panadapter stage: which frames of this call are update frames, in front of everything that allocates
-  if ((rc = pan_prepare(ctx, n_frames)) != T41RX_OK) return rc;
   if (ctx->beacon.on && (rc = beacon_prepare(ctx)) != T41RX_OK) return rc;
   if ((nr_on(ctx) && (rc = ensure_nr(ctx)) != T41RX_OK) || (ctx->nb.on && (rc = ensure_nb(ctx)) != T41RX_OK) ||
       (ctx->eq.on && (rc = ensure_eq(ctx)) != T41RX_OK) ||
       ((cw_filter_on(ctx) || cw_det_on(ctx)) && (rc = ensure_cw(ctx)) != T41RX_OK))
     return rc;
-  // (24 kS/s with a stage tap or side output: the tap kernels hand the audio over like the stages' calls, finish24())
-  if ((seg > 1 || stages_on(ctx) || finish24(ctx)) && n_frames > ctx->scratch_frames) {
-    // scratch between the kernels of the long-FFT pipeline / the noise-reduction pipeline (grown on demand, kept)
+  if (plan.scratch && n_frames > ctx->scratch_frames) {
+    // scratch between the kernels of the long-FFT pipeline / behind the hand-over (grown on demand, kept)
     HIP_TRY(hipStreamSynchronize(s));
     ctx->scratch_frames = 0;
     ctx->d_mid.reset();
     ctx->d_aud24.reset();
-    const size_t per = (size_t)ctx->nchan * (size_t)n_frames * (size_t)(256 * seg);  // fft_length / 2 per frame
+    const size_t per = (size_t)ctx->nchan * (size_t)n_frames * (size_t)(256 * plan.seg);  // fft_length / 2 per frame
     HIP_TRY(dev_alloc(ctx->d_mid, per * 2 * sizeof(float)));
     HIP_TRY(dev_alloc(ctx->d_aud24, per * 2 * sizeof(float)));  // complex when the back kernel demodulates
     ctx->scratch_frames = n_frames;
   }
-  if (ctx->params.mode == T41RX_DEMOD_NFM && ctx->params.nfm_demod == 1 && seg > 1)
-    return fail(T41RX_ERR_UNSUPPORTED, "nfm_demod = 1 is built for fft_length 512");
-  if (pipe_on(ctx, n_frames) && !ctx->d_agc_pipe) {
+  if (plan.nfm_atan_long) return fail(T41RX_ERR_UNSUPPORTED, plan.why);
+  if (plan.pipe_buffer && !ctx->d_agc_pipe) {
     const size_t bytes = pipe_layout(ctx->nchan).bytes;
     DevBuf<char> pipe;  // the context only ever sees a buffer whose counters are zero
     HIP_TRY(dev_alloc(pipe, bytes));
     HIP_TRY(hipMemset(pipe.get(), 0, bytes));
     ctx->d_agc_pipe = std::move(pipe);
   }
+  if (plan.need_ident && !ctx->d_ident) {  // 0, 1, ..: the map of a mapped form's call without one of the caller's
+    std::vector<int32_t> ident((size_t)ctx->nchan);
+    for (int i = 0; i < ctx->nchan; ++i) ident[(size_t)i] = i;
+    DevBuf<int32_t> fresh;
+    HIP_TRY(dev_alloc(fresh, sizeof(int32_t) * ident.size()));
+    HIP_TRY(hipMemcpy(fresh.get(), ident.data(), sizeof(int32_t) * ident.size(), hipMemcpyHostToDevice));
+    ctx->d_ident = std::move(fresh);
+  }
   if (ctx->params.AGCMode != 0 && (int)blob_view(ctx->blob.data()).agc[kAgcAttackBuffsize] != kAgcDelay)
     return fail(T41RX_ERR_STATE, "coefficient blob carries an AGC look-ahead the kernel is not built for");
-  if (sets_loaded(ctx) && (seg > 1 || stages_on(ctx)))  // (the setters keep these apart: not reached)
-    return fail(T41RX_ERR_STATE, "parameter sets are loaded with a long fft_length or a chain-splitting stage");
+  if (!plan.valid) return fail(T41RX_ERR_STATE, plan.why);  // (the setters keep these apart: not reached)
   if ((ctx->dbg_nco || ctx->dbg_dec || ctx->dbg_demod) && n_frames > ctx->tap_frames)
     return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the debug tap buffers were set with");
   if (ctx->spect && n_frames > ctx->spect_frames)
@@ -314,15 +345,14 @@ int prepare_call(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
                                              " leaves float_buffer_L different from float_buffer_R and neither the notch nor the noise "
                                              "blanker joins them behind it; the library carries one audio stream");
   if (ctx->disp.spec && (!ctx->disp.d_pre || !ctx->disp.d_state || !ctx->d_win)) return fail(T41RX_ERR_STATE, "display spectrum enabled without its buffers");
-  if (ctx->ft8.on && (rc = ft8_prepare(ctx, n_frames, s)) != T41RX_OK) return rc;
+  if (ctx->ft8.on && (rc = ft8_prepare(ctx, plan, n_frames, s)) != T41RX_OK) return rc;
   // the decoder's words, behind every refusal: its checkpoint section appears with the first call in which it runs
   if (cw_dec_on(ctx) && (rc = ensure_cw_decode(ctx)) != T41RX_OK) return rc;
   return T41RX_OK;
 }
 
 // (b) the kernels' arguments
-RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, int n_frames, bool q15) {
-  const int seg = ctx->params.fft_length / 512;
+RxArgs rx_args(t41rx_ctx *ctx, const CallPlan &plan, const float *dI, const float *dQ, float *dAudio, int n_frames, bool q15) {
   RxArgs a{};
   a.I = dI;
   a.Q = dQ;
@@ -332,7 +362,7 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
   a.tab = ctx->d_tab.get();
   a.nco = ctx->d_nco.get();
   a.nchan = ctx->nchan;
-  a.nframes = seg * n_frames;  // 2048-sample segments
+  a.nframes = plan.seg * n_frames;  // 2048-sample segments
   {  // time-major: [frame][channel][frame_len] (fft_length 512: set_buffer_layout / set_params)
     const Strides io = strides_of(ctx, ctx->nchan, a.nframes, 2048);
     a.chan_stride = io.chan;
@@ -344,7 +374,7 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
     a.in_chan_stride = in.chan;
     a.in_frame_stride = in.frame;
   }
-  a.seg = seg;
+  a.seg = plan.seg;
   a.nframes4k = n_frames;
   a.mid = ctx->d_mid.get();
   a.aud24 = ctx->d_aud24.get();
@@ -361,16 +391,16 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
   if (sets_loaded(ctx)) {
     // parameter sets: the arrays [K + 1] in place of set 0's block and table, the channels' table and the sets' gains.
     // The rule (t41rx_param_sets_compatible) makes everything else in here -- plain, agc, nfm_atan, the pipelined
-    // form -- the same for every set.  The set kernels are twins of the mapped ones: without an input map, the identity
+    // form -- the same for every set
     a.coef = ctx->sets.d_coef.get();
     a.tab = ctx->sets.d_tab.get();
     a.set_of = ctx->sets.d_set_of.get();
     a.set_gain = ctx->sets.d_gain.get();
-    if (!a.in_map) {
-      a.in_map = ctx->sets.d_ident.get();
-      a.in_chan_stride = a.chan_stride;
-      a.in_frame_stride = a.frame_stride;
-    }
+  }
+  if (plan.need_ident) {  // the input keeps its place under the map's strides
+    a.in_map = ctx->d_ident.get();
+    a.in_chan_stride = a.chan_stride;
+    a.in_frame_stride = a.frame_stride;
   }
   a.q15 = q15 ? 1 : 0;
   a.nco_rd = ctx->nco_sel;
@@ -386,12 +416,12 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
     a.seg_run = (int)(run < 1 ? 1 : (run > 8 ? 8 : (run > segs ? segs : run)));
   }
   a.agc = ctx->params.AGCMode != 0 ? 1 : 0;
-  if (pipe_on(ctx, n_frames)) a.agc_pipe = reinterpret_cast<float *>(ctx->d_agc_pipe.get());
+  if (plan.pipe_buffer) a.agc_pipe = reinterpret_cast<float *>(ctx->d_agc_pipe.get());
   a.dbg_pre = ctx->disp.spec ? ctx->disp.d_pre.get() : nullptr;
   a.dbg_nco = ctx->dbg_nco;
   a.dbg_dec = ctx->dbg_dec;
   a.dbg_demod = ctx->dbg_demod;
-  if (ctx->ft8.on && !stages_on(ctx) && !a.dbg_demod) a.dbg_demod = ctx->ft8.d_tap.get();  // the FT8 stage reads the demod tap
+  if (plan.ft8_own_tap) a.dbg_demod = ctx->ft8.d_tap.get();  // the FT8 stage reads the demod tap
   a.spect = ctx->spect;
   a.spect_max = ctx->spect_max;
   if (ctx->pan.on && ctx->pan.call_rows > 0) {
@@ -404,19 +434,10 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
     a.tap_first = ctx->pan.call_first;
     a.tap_rows = ctx->pan.max_rows;
   }
-  if (stages_on(ctx)) a.aud_out = ctx->d_aud24.get();  // the fused kernel stops behind the demodulator
-  if (finish24(ctx)) {
-    // 24 kS/s on the tap kernels: the same hand-over, and launch_chain() finishes from it (the strides above stay the
-    // input's: a tap kernel without a map places its input with them, and stores no audio)
-    a.aud_out = ctx->d_aud24.get();
-  } else if (audio_24k(ctx)) {
-    // 24 kS/s from the fused kernel, the twin of the call's mapped form: the input keeps its place under the map's
-    // strides (the identity when the caller set no map), the output's count frames of 256
-    if (!a.in_map) {
-      a.in_map = ctx->d_ident24.get();
-      a.in_chan_stride = a.chan_stride;
-      a.in_frame_stride = a.frame_stride;
-    }
+  // the kernel stops behind the demodulator.  (At 24 kS/s the strides above stay the input's: a tap kernel without a map
+  // places its input with them, and stores no audio)
+  if (plan.handover) a.aud_out = ctx->d_aud24.get();
+  if (plan.form.a24_form) {  // 24 kS/s from the fused kernel: the output's strides count frames of 256
     const Strides o = strides_of(ctx, ctx->nchan, a.nframes, 256);
     a.chan_stride = o.chan;
     a.frame_stride = o.frame;
@@ -426,7 +447,7 @@ RxArgs rx_args(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, 
 
 }  // namespace
 
-// the finish of a 24 kS/s call that left its audio in the scratch (finish24()): volume, q15 conversion, the call's layout
+// the finish of a 24 kS/s call that left its audio in the scratch (Back::finish24, Back::cw_24k): volume, q15 conversion, the call's layout
 int t41::aud24_finish_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t s) {
   const Strides o = strides_of(ctx, ctx->nchan, n_frames, 256);
   Aud24Args f{};
@@ -446,26 +467,34 @@ namespace {
 
 // (c) the stage chain: fused front end, FT8 on the demodulated audio, then on the audio @24 kS/s the equalizer, noise
 // reduction / notch and the blanker, the CW detector, decoder and narrow filter, the back end, and the display stages
-int launch_chain(t41rx_ctx *ctx, RxArgs a, int n_frames, hipStream_t s) {
-  const bool a24 = audio_24k(ctx);
-  int rc = hip_check(launch_rx(a, ctx->params.fft_length, ctx->params.mode, ctx->seg_run_set, a24, s), "kernel launch");
+int launch_chain(t41rx_ctx *ctx, const CallPlan &plan, RxArgs a, int n_frames, hipStream_t s) {
+  int rc = hip_check(launch_rx(a, plan, s), "kernel launch");
   if (rc != T41RX_OK) return rc;
-  if (ctx->ft8.on && (rc = ft8_run(ctx, a, n_frames, s)) != T41RX_OK) return rc;
+  if (ctx->ft8.on && (rc = ft8_run(ctx, plan, a, n_frames, s)) != T41RX_OK) return rc;
   if (ctx->eq.on && (rc = eq_run(ctx, n_frames, s)) != T41RX_OK) return rc;
   if (nr_on(ctx) && (rc = nr_run(ctx, n_frames, s)) != T41RX_OK) return rc;
   if (ctx->nb.on && (rc = nb_run(ctx, n_frames, s)) != T41RX_OK) return rc;
   if (cw_det_on(ctx) && (rc = cw_detect_run(ctx, n_frames, s)) != T41RX_OK) return rc;
   if (cw_dec_on(ctx) && (rc = cw_decode_run(ctx, n_frames, s)) != T41RX_OK) return rc;
-  if (cw_filter_on(ctx)) {
-    if ((rc = cw_filter_run(ctx, a, n_frames, s)) != T41RX_OK) return rc;
-  } else if (a24 && a.aud_out) {
-    // 24 kS/s: the volume and the stores alone (Process.cpp:929-937 without DF); the interpolator memories stay as they are
-    if ((rc = aud24_finish_run(ctx, a, n_frames, s)) != T41RX_OK) return rc;
-  } else if (stages_on(ctx)) {
-    // then the interpolators, volume and stores (Process.cpp:917-937) from a.aud24
-    a.aud_out = nullptr;
-    if ((rc = hip_check(launch_back512(a, s), "interpolator kernel launch")) != T41RX_OK) return rc;
+  switch (plan.back) {
+    case Back::cw_back:
+    case Back::cw_24k:
+      rc = cw_filter_run(ctx, plan, a, n_frames, s);
+      break;
+    case Back::finish24:
+      // 24 kS/s: the volume and the stores alone (Process.cpp:929-937 without DF); the interpolator memories stay as they are
+      rc = aud24_finish_run(ctx, a, n_frames, s);
+      break;
+    case Back::back512:
+      // then the interpolators, volume and stores (Process.cpp:917-937) from a.aud24
+      a.aud_out = nullptr;
+      rc = hip_check(launch_back512(a, s), "interpolator kernel launch");
+      break;
+    case Back::fused:
+    case Back::long_pipe:
+      break;  // the front kernels stored the audio
   }
+  if (rc != T41RX_OK) return rc;
   if (a.seg > 1) ctx->nco_sel ^= 1;  // the kernels wrote the other copy
   if (ctx->disp.spec && (rc = display_run(ctx, n_frames, s)) != T41RX_OK) return rc;
   if (ctx->pan.on && (rc = pan_run(ctx, n_frames, s)) != T41RX_OK) return rc;
@@ -483,9 +512,12 @@ int process_device_impl(t41rx_ctx *ctx, const float *dI, const float *dQ, float 
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
   const hipStream_t s = (hipStream_t)hip_stream;
-  const int rc = prepare_call(ctx, n_frames, s);
+  // the panadapter stage: which frames of this call are update frames, in front of the plan and everything that allocates
+  int rc = pan_prepare(ctx, n_frames);
   if (rc != T41RX_OK) return rc;
-  return launch_chain(ctx, rx_args(ctx, dI, dQ, dAudio, n_frames, q15), n_frames, s);
+  const CallPlan plan = plan_call(call_facts(ctx, n_frames, q15));
+  if ((rc = prepare_call(ctx, plan, n_frames, s)) != T41RX_OK) return rc;
+  return launch_chain(ctx, plan, rx_args(ctx, plan, dI, dQ, dAudio, n_frames, q15), n_frames, s);
 }
 
 // staging buffers of the host-pointer entry points, sized in bytes per array: the two inputs (with an input map they
@@ -775,20 +807,8 @@ int t41rx_get_input_map(const t41rx_ctx *ctx, int32_t *stream_of_channel_out, in
 int t41rx_set_audio_rate(t41rx_ctx *ctx, int rate) {
   if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
   if (rate != T41RX_AUDIO_RATE_192K && rate != T41RX_AUDIO_RATE_24K) return fail(T41RX_ERR_ARG, "unknown audio rate");
-  if (rate == T41RX_AUDIO_RATE_24K) {
-    if (ctx->params.fft_length != 512)
-      return fail(T41RX_ERR_UNSUPPORTED, "audio at 24 kS/s is built for fft_length 512 (the long-FFT pipeline's back kernel interpolates and stores at 192 kS/s)");
-    if (!ctx->d_ident24) {  // the map of a call without one: the fused 24 kS/s kernels are twins of the mapped forms
-      DeviceGuard g(ctx->device);
-      if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
-      std::vector<int32_t> ident((size_t)ctx->nchan);
-      for (int i = 0; i < ctx->nchan; ++i) ident[(size_t)i] = i;
-      DevBuf<int32_t> fresh;
-      HIP_TRY(dev_alloc(fresh, sizeof(int32_t) * ident.size()));
-      HIP_TRY(hipMemcpy(fresh.get(), ident.data(), sizeof(int32_t) * ident.size(), hipMemcpyHostToDevice));
-      ctx->d_ident24 = std::move(fresh);
-    }
-  }
+  if (rate == T41RX_AUDIO_RATE_24K && ctx->params.fft_length != 512)
+    return fail(T41RX_ERR_UNSUPPORTED, "audio at 24 kS/s is built for fft_length 512 (the long-FFT pipeline's back kernel interpolates and stores at 192 kS/s)");
   ctx->audio_rate = rate;  // (calls in flight were launched with the rate they found)
   return T41RX_OK;
 }

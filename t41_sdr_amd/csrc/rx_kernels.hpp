@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rx_internal.hpp"
+#include "rx_plan.hpp"
 
 namespace t41 {
 
@@ -110,11 +111,10 @@ struct RxArgs {
 //   mask[R][512]   : FIR_filter_mask[q + R m] / N at [q][m]
 constexpr int tab_long_entries(int R) { return (R - 1) * 512 + R * 512; }
 
-// long_pipeline: FFT_LENGTH 4096 runs the two-kernel pipeline where the one-kernel form would (t41rx_ctx::seg_run)
-// a24: the audio leaves @24 kS/s (t41rx_set_audio_rate; FFT_LENGTH 512): a.chan_stride / a.frame_stride place frames of 256
-// output samples (the input's strides are then a.in_chan_stride / a.in_frame_stride: the call carries a map), and either
-// the fused kernel stores them itself or, with a.aud_out set, the caller finishes with launch_aud24_finish()
-hipError_t launch_rx(const RxArgs &a, int fft_length, int mode, bool long_pipeline, bool a24, hipStream_t s);
+// the front of the call's plan (rx_plan.hpp): the fused kernel, the tap kernel, or the long-FFT pipeline.  With
+// p.form.a24_form a.chan_stride / a.frame_stride place frames of 256 output samples (the input's strides are then
+// a.in_chan_stride / a.in_frame_stride: the call carries a map); with p.handover the caller finishes from a.aud_out
+hipError_t launch_rx(const RxArgs &a, const CallPlan &p, hipStream_t s);
 // what the kernel objects of this library were built as (rx_experiments.hpp; rx_dispatch.hip: the OR of every object's
 // own answer): 0 = the product, bit 1 = a diagnostic build (stamps / counters)
 int kernel_build_flags();

@@ -6,19 +6,18 @@
 
 namespace t41 {
 
-hipError_t launch_long_front(const RxArgs &a, int mode, hipStream_t s) {
-  if (mode == T41RX_DEMOD_NFM)  // nfmdemod()'s "last sample" chains the frames: sequential, on the general front end
+hipError_t launch_long_front(const RxArgs &a, const KernelForm &k, hipStream_t s) {
+  if (k.family == Family::nfm)  // nfmdemod()'s "last sample" chains the frames: sequential, on the general front end
     return with_bools([&](auto Q15, auto MAP) { return launch_rx512<kModeNfm, false, 1, false, false, Q15, false, false, MAP>(a, s); },
-                      a.q15 != 0, a.in_map != nullptr);
-  // everything else: one wave per (channel, run of segments), the segments run independently (SEGPAR).  PLAIN -- unit
-  // band / IQ gains (the firmware defaults): the correction stage drops out -- for f32 samples only.
+                      k.q15, k.map_form);
+  // everything else: one wave per (channel, run of segments), the segments run independently (SEGPAR).
   // An input map (receiver groups) selects the same instantiation in its mapped form; the back end reads no antenna samples.
   return with_bools(
       [&](auto PLN, auto Q15, auto MAP) {
-        if constexpr (PLN && Q15) return hipErrorInvalidValue;  // never selected: not compiled
+        if constexpr (!long_front_compiled(PLN, Q15)) return hipErrorInvalidValue;  // never planned: not compiled
         else return launch_rx512<kModeSsb, false, 1, PLN, false, Q15, true, false, MAP>(a, s);
       },
-      a.plain && !a.q15, a.q15 != 0, a.in_map != nullptr);
+      k.plain, k.q15, k.map_form);
 }
 
 // SSB / NFM audio with the fixed gain: the gain law and the demodulators keep no state here
@@ -27,14 +26,13 @@ static hipError_t launch_back_par(const RxArgs &a, hipStream_t s) {
   return launch_rx512<kModeSsb, false, 2, false, false, Q15, true>(a, s);
 }
 
-hipError_t launch_long_back(const RxArgs &a, int mode, hipStream_t s) {
-  const bool am = mode == T41RX_DEMOD_AM;
+hipError_t launch_long_back(const RxArgs &a, const KernelForm &k, hipStream_t s) {
   return with_bools(
       [&](auto AM, auto AGC, auto Q15) {
         if constexpr (AM || AGC) return launch_rx512<AM ? kModeAm : kModeSsb, false, 2, false, AGC, Q15>(a, s);  // sequential
         else return launch_back_par<Q15>(a, s);
       },
-      am, a.agc != 0, a.q15 != 0);
+      k.family == Family::am, k.agc, k.q15);
 }
 
 hipError_t launch_back512(const RxArgs &a, hipStream_t s) {

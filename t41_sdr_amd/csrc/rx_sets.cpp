@@ -13,7 +13,6 @@ using namespace t41;
 
 namespace {
 
-int family(int mode) { return mode == T41RX_DEMOD_LSB ? T41RX_DEMOD_USB : mode; }  // USB and LSB are one kernel
 const char *family_name(int mode) {
   return mode == T41RX_DEMOD_AM ? "AM" : mode == T41RX_DEMOD_NFM ? "NFM" : mode == T41RX_DEMOD_SAM ? "SAM" : "USB/LSB";
 }
@@ -25,24 +24,27 @@ bool plain_of(const t41rx_params &p) {
   return gains_of(blob_view(blob.data()).scalars, g);
 }
 
-// The rule: launch512() picks the same rx512_kernel instantiation for both, and both name the same stages.  `who`
-// opens the refusal ("set 2 against set 0: ").
+// The rule: the plan (rx_plan.hpp) names the same rx512_kernel instantiation for both, and both name the same stages.
+// The clauses say which difference it is; the last check asks plan_call() itself, so the rule cannot drift from what is
+// launched.  `who` opens the refusal ("set 2 against set 0: ").
 int compatible(const t41rx_params &a, const t41rx_params &b, const std::string &who) {
   auto no = [&](const std::string &why) { return fail(T41RX_ERR_UNSUPPORTED, "parameter sets: " + who + why); };
   if (a.fft_length != b.fft_length)
     return no("fft_length differs (" + std::to_string(a.fft_length) + " and " + std::to_string(b.fft_length) + ")");
   if (a.fft_length != 512)
     return no("fft_length " + std::to_string(a.fft_length) + ": the long-FFT pipeline carries one parameter set; sets are built for fft_length 512");
-  if (family(a.mode) != family(b.mode))
+  const CallFacts fa = params_facts(a, plain_of(a)), fb = params_facts(b, plain_of(b));
+  if (fa.family != fb.family)  // (USB and LSB are one kernel)
     return no(std::string("the demodulators differ (") + family_name(a.mode) + " and " + family_name(b.mode) + "): one kernel runs all the channels of a context");
   if ((a.AGCMode != 0) != (b.AGCMode != 0)) return no("the AGC is off in one and on in the other (AGCMode 0 against 1..4)");
   if (a.nfm_demod != b.nfm_demod) return no("nfm_demod differs");
   if (a.xmtMode != b.xmtMode) return no("xmtMode differs");
   if (a.nrOptionSelect != 0 || b.nrOptionSelect != 0 || a.ANR_notchOn != 0 || b.ANR_notchOn != 0)
     return no("noise reduction / notch (nrOptionSelect, ANR_notchOn) split the fused chain and read one parameter set on the host: both must be 0");
-  if (plain_of(a) != plain_of(b))
+  if (fa.plain_gains != fb.plain_gains)
     return no("the first stage's gains are unit gains in one (RFgain 1, IQAmpCorrectionFactor 1, IQPhaseCorrectionFactor 0) and general in "
               "the other: two kernels");
+  if (!(plan_call(fa).form == plan_call(fb).form)) return no("the two take different kernels");
   return T41RX_OK;
 }
 
@@ -147,13 +149,9 @@ int t41rx_set_param_sets(t41rx_ctx *ctx, const t41rx_params *sets, int n_sets, c
   HIP_TRY(dev_alloc(fresh.d_tab, sizeof(float2) * k1 * (size_t)kTabEntries512));
   HIP_TRY(dev_alloc(fresh.d_gain, sizeof(SetGains) * k1));
   HIP_TRY(dev_alloc(fresh.d_set_of, sizeof(int32_t) * (size_t)n));
-  HIP_TRY(dev_alloc(fresh.d_ident, sizeof(int32_t) * (size_t)n));
   int rc = upload_arrays(ctx, fresh.blobs, fresh.d_coef.get(), fresh.d_tab.get(), fresh.d_gain.get());
   if (rc != T41RX_OK) return rc;
-  std::vector<int32_t> ident((size_t)n);
-  for (int i = 0; i < n; ++i) ident[(size_t)i] = i;
   HIP_TRY(hipMemcpy(fresh.d_set_of.get(), set_of_channel, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(fresh.d_ident.get(), ident.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
   ctx->sets = std::move(fresh);
   return upload_nco(ctx);  // the side tone follows the channel's own set
 }
