@@ -374,6 +374,44 @@ T41RX_API int t41rx_audio_frame_len(const t41rx_ctx *ctx);
 T41RX_API int t41rx_set_input_map(t41rx_ctx *ctx, const int32_t *stream_of_channel, int n, int n_streams);
 T41RX_API int t41rx_get_input_map(const t41rx_ctx *ctx, int32_t *stream_of_channel_out, int n);
 
+/* ---- receiver groups: an output map, audio rows only for the channels somebody listens to (ABI 5) ----
+ * The mirror of the input map.  A skimmer or a bank of FT8 receivers runs thousands of channels for their detectors and
+ * decoders; a listener hears one or two.  With an output map set, channel c writes its audio to row row_of_channel[c] of
+ * the audio buffer, or with row_of_channel[c] == -1 writes none, and the audio of every t41rx_process_* entry holds
+ * n_rows rows instead of n_channels:
+ *   channel-major  out [n_rows][n_frames * audio_frame_len]
+ *   time-major     out [n_frames][n_rows][audio_frame_len]
+ * for the device and the host entries, f32 and q15, at both audio rates, with or without an input map and parameter
+ * sets.  The inputs, every side output, every stage tap and every stage result keep their [n_channels]... shapes.
+ * With n_rows == 0 the audio pointer may be NULL (without a map a NULL audio pointer stays T41RX_ERR_ARG).
+ * A listened channel c with row r: row r is, bit for bit, the row channel c gets from the same call without an output
+ * map.  A muted channel: everything up to the demodulator and everything that reads behind it -- the AGC, every stage
+ * that is on (the narrow CW filter and its memories too), every tap and side output, FT8, the panadapter, the beacon
+ * monitor, the CW detector and decoder, every state record -- computes and holds what it does without a map, bit for
+ * bit, with two exceptions: the two interpolators do not run and nothing is stored to the audio buffer.  The
+ * interpolator memories of a muted channel stay in its state record as they were: the 24 kS/s rule
+ * (t41rx_set_audio_rate) per channel.  When the channel is listened to again the interpolators continue from what they
+ * last held.  Rows no channel names are not written.
+ * The map is configuration, like the input map: it is in no checkpoint, survives t41rx_reset, t41rx_set_state,
+ * t41rx_set_params and t41rx_set_coeffs, and may change between any two calls.  t41rx_state_bytes() and every
+ * checkpoint section are what they are without a map.  The calibration entries (t41rx_calibrate_*) and the
+ * t41rx_ft8_audio_* entries write no audio and ignore the map.  fft_length 512 only: at a long fft_length
+ * t41rx_set_output_map() answers T41RX_ERR_UNSUPPORTED (the long-FFT pipeline's back kernel stores every channel).
+ * t41rx_set_output_map(): row_of_channel is a host array of n == n_channels entries, each -1 or in [0, n_rows), with
+ *   0 <= n_rows <= n_channels.  No row may be named twice (two waves would store to one row); rows may go unused.  NULL
+ *   with n == 0 and n_rows == 0 switches the map off: one row per channel again.  Everything is checked on the host
+ *   before anything changes: any violation returns T41RX_ERR_ARG with a t41rx_last_error() text that names the entry and
+ *   leaves the previous map as it was.  Synchronises the device, then uploads (the ordering rule of
+ *   t41rx_set_input_map): the map holds from the next process call on.
+ * t41rx_get_output_map(): returns 1 with a map set, 0 with none (negative: an error status).  n_rows_out receives
+ *   t41rx_audio_rows(); row_of_channel_out, n == n_channels entries, receives the map when one is set.  Either may be NULL.
+ * t41rx_audio_rows(): rows of audio the process entries write: n_rows with a map, n_channels without.  The host-pointer
+ *   process forms allocate and copy back that many rows; with a map that leaves rows unused they copy the caller's rows
+ *   in first, so that an unused row comes back as it went in. */
+T41RX_API int t41rx_set_output_map(t41rx_ctx *ctx, const int32_t *row_of_channel, int n, int n_rows);
+T41RX_API int t41rx_get_output_map(const t41rx_ctx *ctx, int32_t *row_of_channel_out, int n, int *n_rows_out);
+T41RX_API int t41rx_audio_rows(const t41rx_ctx *ctx);
+
 /* ---- receiver groups: parameter sets, one t41rx_params per group of channels (ABI 5) ----
  * The receivers of one band differ in more than NCOFreq: the phone receivers are LSB at 2.8 kHz, the FT8 receiver is USB
  * at 200..3000 Hz, the CW receivers want a few hundred hertz.  A context's own t41rx_params (t41rx_create,
@@ -422,7 +460,8 @@ T41RX_API int t41rx_param_sets_compatible(const t41rx_params *a, const t41rx_par
 
 /* ---- the hot path: ProcessIQData() on every channel ----
  * Device-pointer form: dI, dQ, dAudio are device pointers ([n_channels][n_frames*frame_len], or time-major:
- * t41rx_set_buffer_layout; with an input map dI / dQ hold n_streams rows: t41rx_set_input_map);
+ * t41rx_set_buffer_layout; with an input map dI / dQ hold n_streams rows: t41rx_set_input_map; with an output map
+ * dAudio holds n_rows rows: t41rx_set_output_map);
  * the kernel is enqueued on `hip_stream` (a hipStream_t, may be NULL = default stream) and the
  * call returns without synchronising. */
 T41RX_API int t41rx_process_device(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio,

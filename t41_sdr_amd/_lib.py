@@ -93,6 +93,9 @@ SYMBOLS = {
     "t41rx_audio_frame_len": (C.c_int, [_vp]),
     "t41rx_set_input_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int, C.c_int]),
     "t41rx_get_input_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int]),
+    "t41rx_set_output_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int, C.c_int]),
+    "t41rx_get_output_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]),
+    "t41rx_audio_rows": (C.c_int, [_vp]),
     "t41rx_set_param_sets": (C.c_int, [_vp, C.POINTER(Params), C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "t41rx_get_param_sets": (C.c_int, [_vp, C.POINTER(Params), C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "t41rx_param_sets_compatible": (C.c_int, [C.POINTER(Params), C.POINTER(Params)]),

@@ -22,8 +22,10 @@ __device__ __forceinline__ unsigned q15_pack2(float x0, float x1) {
 }
 }  // namespace
 
-template <bool Q15>
-__global__ __launch_bounds__(256) void aud24_finish_kernel(const Aud24Args a) {
+// OMAP (t41rx_set_output_map): the frame goes to row a.out_map[channel] of the output; a muted channel's threads leave
+// before they read the audio.
+template <bool Q15, bool OMAP>
+__device__ __forceinline__ void aud24_finish_body(const Aud24Args &a) {
 #pragma clang fp contract(off)
   constexpr int kPieces = Q15 ? 32 : 64;  // 16-byte pieces of a frame's 256 samples
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -33,7 +35,9 @@ __global__ __launch_bounds__(256) void aud24_finish_kernel(const Aud24Args a) {
   const int piece = (int)(i % kPieces);
   const size_t ch = job / (size_t)a.nframes, f = job % (size_t)a.nframes;
   const float *src = a.aud + job * 256;
-  const size_t o = ch * (size_t)a.chan_stride + f * (size_t)a.frame_stride;  // samples
+  const int row = OMAP ? a.out_map[ch] : 0;
+  if (OMAP && row < 0) return;
+  const size_t o = (OMAP ? (size_t)row : ch) * (size_t)a.chan_stride + f * (size_t)a.frame_stride;  // samples
   const float g = a.coef[a.set_of ? a.set_of[ch] : 0].sc[kScOutScale] * 0.125f;  // (exact: DF = 8)
   if (!Q15) {
     const float4 x = *reinterpret_cast<const float4 *>(src + 4 * piece);
@@ -45,10 +49,25 @@ __global__ __launch_bounds__(256) void aud24_finish_kernel(const Aud24Args a) {
   }
 }
 
+template <bool Q15>
+__global__ __launch_bounds__(256) void aud24_finish_kernel(const Aud24Args a) {
+  aud24_finish_body<Q15, false>(a);
+}
+template <bool Q15>
+__global__ __launch_bounds__(256) void aud24_finish_omap_kernel(const Aud24Args a) {
+  aud24_finish_body<Q15, true>(a);
+}
+
 hipError_t launch_aud24_finish(const Aud24Args &a, hipStream_t s) {
-  if (a.nchan <= 0 || a.nframes <= 0 || !a.aud || !a.out || !a.coef) return hipErrorInvalidConfiguration;
+  // (an output map without a listened channel comes with no audio buffer: no thread stores)
+  if (a.nchan <= 0 || a.nframes <= 0 || !a.aud || (!a.out && !a.out_map) || !a.coef) return hipErrorInvalidConfiguration;
   const size_t pieces = (size_t)a.nchan * (size_t)a.nframes * (a.q15 ? 32 : 64);
   const dim3 grid((unsigned)((pieces + 255) / 256));
+  if (a.out_map) {
+    if (a.q15) hipLaunchKernelGGL(aud24_finish_omap_kernel<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(aud24_finish_omap_kernel<false>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+  }
   if (a.q15) hipLaunchKernelGGL(aud24_finish_kernel<true>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(aud24_finish_kernel<false>, grid, dim3(256), 0, s, a);
   return hipGetLastError();

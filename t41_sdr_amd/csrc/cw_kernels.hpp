@@ -59,6 +59,9 @@ struct CwBackArgs {
   float scale;       // DF * VolumeToAmplification(audioVolume)
   float int1[48];    // FIR_int1_coeffs
   float int2[32];    // FIR_int2_coeffs (not scaled)
+  // the output map (t41rx_set_output_map), or null: channel c's audio goes to row out_map[c] of out; with out_map[c] < 0
+  // the channel's block leaves before it reads the audio or the interpolator memories
+  const int *out_map;
 };
 hipError_t launch_cw_back(const CwBackArgs &a, hipStream_t s);
 

@@ -103,9 +103,20 @@ static_assert(!Geo<0>::kResident || (Geo<0>::kH1 + 24 <= Geo<0>::kSlice && Geo<0
 // their memories (kStInt1, kStInt2; on chip H1, hist2c) are neither read nor written.  It rides on PARTM like the map and
 // exists only as a twin of the mapped forms (PART + kPartMap [+ kPartSet] + kPartA24) without stage taps: a call without
 // an input map runs with an identity map, a call with taps or a chain-splitting stage ends in aud24_finish_kernel.
+// OUT (receiver groups, t41rx_set_output_map): the channel stores its audio to row a.out_map[ch] of a.out -- the row
+// takes the channel's place in the output's base and nothing else changes -- or, with a.out_map[ch] < 0, to none: the wave
+// then leaves the frame behind the demodulator, where the A24 form and the hand-over leave it.  No interpolator runs for
+// that channel, their windows are not staged and their memories (kStInt1, kStInt2; on chip H1, hist2c) are neither read
+// nor written: the 24 kS/s rule, per channel.  The branch is wave-uniform (one wave, one channel; the entry is a scalar
+// load).  It rides on PARTM like the map and exists as a twin of the mapped FFT_LENGTH 512 forms without taps (PART +
+// kPartMap [+ kPartSet] [+ kPartA24] + kPartOut; the A24 twin stores its 256 samples to the row or not at all) and of
+// the segment-parallel back kernel behind the hand-over (PART 2 + kPartOut, launch_back512: a muted channel's waves
+// leave before they read audio or state; + kPartSet with parameter sets loaded: the interpolator taps, which carry the
+// volume, are then the channel's own set's).  A call with taps hands over and finishes in a back kernel that knows the map.
 constexpr int kPartMap = 4;
 constexpr int kPartSet = 8;
 constexpr int kPartA24 = 16;
+constexpr int kPartOut = 32;
 template <int MODE, bool DEBUG, int PARTM, bool PLAIN, bool AGC = false, bool WQ15 = false, bool SEGPAR = false, bool PIPE = false>
 __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 64), 4) void rx512_kernel(const RxArgs a) {
   T41RX_CLK_BEGIN();
@@ -113,10 +124,14 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
   constexpr bool MAP = (PARTM & kPartMap) != 0;
   constexpr bool SET = (PARTM & kPartSet) != 0;
   constexpr bool A24 = (PARTM & kPartA24) != 0;
-  static_assert(PART <= 2 && (PARTM & ~(3 | kPartMap | kPartSet | kPartA24)) == 0,
-                "PARTM = PART, PART + kPartMap, or PART + kPartMap + kPartSet, each of the mapped ones with or without kPartA24");
+  constexpr bool OUT = (PARTM & kPartOut) != 0;
+  static_assert(PART <= 2 && (PARTM & ~(3 | kPartMap | kPartSet | kPartA24 | kPartOut)) == 0,
+                "PARTM = PART, PART + kPartMap, or PART + kPartMap + kPartSet, each of the mapped ones with or without kPartA24 and kPartOut");
+  static_assert(!OUT || (MAP && PART == 0 && !DEBUG && !SEGPAR) || ((PARTM & ~kPartSet) == 2 + kPartOut && SEGPAR),
+                "the output-map form is a twin of the mapped FFT_LENGTH 512 kernels without taps, and of the segment-parallel back kernel");
   static_assert(!A24 || (MAP && PART == 0 && !DEBUG && !SEGPAR), "the 24 kS/s form is a twin of the mapped FFT_LENGTH 512 kernels without taps");
-  static_assert(!SET || (MAP && PART == 0 && !SEGPAR), "the set form is a twin of the mapped FFT_LENGTH 512 kernels");
+  static_assert(!SET || (MAP && PART == 0 && !SEGPAR) || (PARTM == 2 + kPartOut + kPartSet && SEGPAR),
+                "the set form is a twin of the mapped FFT_LENGTH 512 kernels, and of the back kernel's output-map form");
   static_assert(!MAP || PART != 2, "the back end of the long-FFT pipeline reads no antenna samples");
   static_assert(!SEGPAR || (PART == 1 && MODE != kModeNfm) || (PART == 2 && MODE == kModeSsb && !AGC), "SEGPAR variants");
   static_assert(!PIPE || ((AGC || MODE == kModeSam) && PART == 0 && !DEBUG && !SEGPAR),
@@ -221,6 +236,11 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
   // MAP: the row of I / Q this channel reads.  ch is wave-uniform and the map read-only: one scalar load per wave, not one
   // per frame; the host has checked the entry (t41rx_set_input_map), the kernel does not
   const int strm = MAP ? ((MapPtr)a.in_map)[ch] : ch;
+  // OUT: the row of the output this channel stores to, or < 0: none.  Wave-uniform and read-only like the two above, and
+  // checked by the host (t41rx_set_output_map) like them
+  const int out_row = OUT ? ((MapPtr)a.out_map)[ch] : ch;
+  const bool muted = OUT && out_row < 0;
+  if (PART == 2 && muted) return;  // the back kernel: before any audio or interpolator state is read (no barrier in PART 2 + SEGPAR)
 
   // per-channel NCO constants and state (wave-uniform).  Only the LOADS are issued here; the
   // values are made uniform (which waits for them) after the first frame's input loads are in
@@ -323,7 +343,8 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
     }
     // sample offset of (channel, frame) in I / Q / audio: RxArgs::chan_stride / frame_stride (channel-major
     // [channel][frame][2048]: nframes * 2048 and 2048; time-major [frame][channel][2048]: 2048 and nchan * 2048)
-    const size_t chbase = (size_t)ch * (size_t)a.chan_stride;
+    // (OUT: the channel's row takes its place; a muted channel forms no output address it uses)
+    const size_t chbase = (size_t)(OUT ? out_row : ch) * (size_t)a.chan_stride;
     // MAP: the input has its own strides and the channel's row is in_map[ch]; everything derived from the input base --
     // the next frame's prefetch, the q15 halving, the pre-roll in front of a run -- follows it
     const size_t in_frame_stride = MAP ? (size_t)a.in_frame_stride : (size_t)a.frame_stride;
@@ -441,7 +462,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
         if (KEEP) {  // the rest of the channel's record: overlap block, interpolator histories
           ovl0 = *reinterpret_cast<const float4 *>(st + kStOverlap + 4 * lane);
           ovl1 = *reinterpret_cast<const float4 *>(st + kStOverlap + 256 + 4 * lane);
-          if (!A24) {
+          if (!A24 && !muted) {
             if (lane < 6) ovl2 = *reinterpret_cast<const float4 *>(st + kStInt1 + 4 * lane);
             if (lane < 8) hist2c = st[kStInt2 + lane];
           }
@@ -496,7 +517,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
         if (KEEP) {
           *reinterpret_cast<float4 *>(lds + G::kOV + 4 * lane) = ovl0;
           *reinterpret_cast<float4 *>(lds + G::kOV + 256 + 4 * lane) = ovl1;
-          if (!A24 && lane < 6) *reinterpret_cast<float4 *>(lds + G::kH1 + 4 * lane) = ovl2;
+          if (!A24 && !muted && lane < 6) *reinterpret_cast<float4 *>(lds + G::kH1 + 4 * lane) = ovl2;
         }
       }
       STAMP(18);  // prologue c: delay lines -> LDS
@@ -888,7 +909,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
       if (!KEEP && (!SEGPAR || (seg0 == 0 && f == seg1 - 1))) {
         if (lane < 14) *reinterpret_cast<float4 *>(st + kStDec1 + 4 * lane) = lds4(lds + kX + 2 * xpad(2 * lane));
         if (lane < 24) *reinterpret_cast<float4 *>(st + kStDec2 + 4 * lane) = lds4(lds + kY1 + y1slot(lane));
-        if (PART != 1 && !A24) {
+        if (PART != 1 && !A24 && !muted) {
           if (lane < 6) hist1 = *reinterpret_cast<const float4 *>(st + kStInt1 + 4 * lane);
           if (lane < 8) hist2 = st[kStInt2 + lane];
         }
@@ -1525,6 +1546,8 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
       }
 
     }
+    // OUT, a channel nobody listens to: the frame ends behind the demodulator (wave-uniform)
+    if (muted) continue;
     if constexpr (A24) {
       // ---- the call's result @24 kS/s: volume (Process.cpp:929 without DF) as a multiply of its own, arm_float_to_q15
       // (Process.cpp:936), and stores of 16 bytes per lane to consecutive addresses -- one request of 1 KiB per frame
@@ -1764,7 +1787,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
     if (lane < 24) *reinterpret_cast<float4 *>(st + kStDec2 + 4 * lane) = lds4(lds + kY1 + y1slot(lane));
     *reinterpret_cast<float4 *>(st + kStOverlap + 4 * lane) = lds4(lds + G::kOV + 4 * lane);
     *reinterpret_cast<float4 *>(st + kStOverlap + 256 + 4 * lane) = lds4(lds + G::kOV + 256 + 4 * lane);
-    if (!A24) {
+    if (!A24 && !muted) {
       if (lane < 6) *reinterpret_cast<float4 *>(st + kStInt1 + 4 * lane) = lds4(lds + G::kH1 + 4 * lane);
       if (lane < 8) st[kStInt2 + lane] = (lane == 0) ? 0.0f : hist2c;
     }

@@ -1,7 +1,7 @@
 // t41_sdr_amd/csrc/rx_ctx.hpp -- the receive context (struct t41rx_ctx) and what the host files of the receive side share.
 // Private to them: rx_host.cpp (the core and the process call), rx_state.cpp (checkpoints and reset) and one file per
 // stage family -- rx_audio.cpp, rx_cw.cpp, rx_ft8.cpp, rx_ft8_decode.cpp, rx_display.cpp, rx_beacon.cpp, rx_cal.cpp -- and
-// rx_sets.cpp (the parameter sets).  Each
+// rx_sets.cpp (the parameter sets) and rx_outmap.cpp (the output map).  Each
 // stage family holds its part of the context in a struct of its own below, and exports the few functions the process
 // call and the checkpoint table name.  No kernel is compiled into a host file: they see the kernels through the
 // *_kernels.hpp headers.
@@ -235,6 +235,14 @@ struct t41rx_ctx {
   std::vector<int32_t> in_map;   // (host)
   int n_streams = 0;
   t41::DevBuf<int32_t> d_in_map;  // [nchan], allocated with the first map
+  // the output map (t41rx_set_output_map; rx_outmap.cpp): channel c stores its audio to row out_map[c] of the out_rows
+  // rows of the audio buffer, or with -1 to none; out_map_on == false: no map, one row per channel.  Configuration like
+  // the input map: in no checkpoint, untouched by reset / set_state / set_params
+  std::vector<int32_t> out_map;   // (host)
+  bool out_map_on = false;
+  int out_rows = 0;               // may be 0 with the map on: nobody listens
+  int out_listened = 0;           // channels with a row; fewer than out_rows: rows go unused and are not written
+  t41::DevBuf<int32_t> d_out_map;  // [nchan], allocated with the first map
   t41::DevBuf<double> d_win;      // the display FFT's window (ensure_window): display spectrum, panadapter, calibration
   t41::ParamSets sets;
   t41::NrStage nr;
@@ -291,6 +299,19 @@ inline int audio_frame_len(const t41rx_ctx *ctx) { return audio_24k(ctx) ? 256 :
 // rx_host.cpp: volume, conversion and stores of a 24 kS/s call from the scratch (launch_chain, cw_filter_run)
 int aud24_finish_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t s);
 inline int input_rows(const t41rx_ctx *ctx) { return ctx->n_streams > 0 ? ctx->n_streams : ctx->nchan; }
+// rows of audio a process call writes: one per channel, or the output map's n_rows
+inline int audio_rows(const t41rx_ctx *ctx) { return ctx->out_map_on ? ctx->out_rows : ctx->nchan; }
+// the output map leaves rows unused: the host-pointer forms then carry the caller's rows through the staging buffer, so
+// that a row no channel names comes back as it went in
+inline bool audio_rows_unused(const t41rx_ctx *ctx) { return ctx->out_map_on && ctx->out_listened < ctx->out_rows; }
+// where (row, frame) of a call's I / Q or audio starts, in samples: rows of frames of `len` samples in the context's layout
+struct Strides {
+  long long chan, frame;
+};
+inline Strides strides_of(const t41rx_ctx *ctx, int rows, int frames, int len) {
+  if (ctx->layout == T41RX_LAYOUT_TIME_MAJOR) return Strides{len, (long long)rows * len};  // [frame][row][len]
+  return Strides{(long long)frames * len, len};
+}
 
 // ---- helpers more than one file uses
 // a stage memory whose power-on value is zero, on first use (rx_audio.cpp)

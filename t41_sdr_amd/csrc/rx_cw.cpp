@@ -153,6 +153,7 @@ int cw_filter_run(t41rx_ctx *ctx, const CallPlan &plan, const RxArgs &a, int n_f
   b.frame_stride = a.frame_stride;
   b.state_stride = (long long)state_floats(512);
   b.q15 = a.q15;
+  b.out_map = a.out_map;  // (the output map: a's strides then place its n_rows rows)
   b.scale = v.scalars[kScOutScale];
   std::memcpy(b.int1, v.int1, sizeof(b.int1));
   std::memcpy(b.int2, v.int2, sizeof(b.int2));

@@ -280,15 +280,8 @@ CallFacts call_facts(const t41rx_ctx *ctx, int n_frames, bool q15) {
   f.nb = ctx->nb.on != 0;
   f.cw_filter = cw_filter_on(ctx);
   f.cw_det = cw_det_on(ctx);
+  f.omap = ctx->out_map_on;
   return f;
-}
-// where (row, frame) of a call's I / Q or audio starts, in samples: rows of frames of `len` samples in the context's layout
-struct Strides {
-  long long chan, frame;
-};
-Strides strides_of(const t41rx_ctx *ctx, int rows, int frames, int len) {
-  if (ctx->layout == T41RX_LAYOUT_TIME_MAJOR) return Strides{len, (long long)rows * len};  // [frame][row][len]
-  return Strides{(long long)frames * len, len};
 }
 
 // (a) what the call needs allocated (stages and scratch on first use, kept) and the refusals that depend on the context
@@ -438,10 +431,16 @@ RxArgs rx_args(t41rx_ctx *ctx, const CallPlan &plan, const float *dI, const floa
   // places its input with them, and stores no audio)
   if (plan.handover) a.aud_out = ctx->d_aud24.get();
   if (plan.form.a24_form) {  // 24 kS/s from the fused kernel: the output's strides count frames of 256
-    const Strides o = strides_of(ctx, ctx->nchan, a.nframes, 256);
+    const Strides o = strides_of(ctx, audio_rows(ctx), a.nframes, 256);
+    a.chan_stride = o.chan;
+    a.frame_stride = o.frame;
+  } else if (plan.form.omap_form) {  // an output map on the fused kernel (a mapped form: the input has its own strides): n_rows rows
+    const Strides o = strides_of(ctx, audio_rows(ctx), a.nframes, 2048);
     a.chan_stride = o.chan;
     a.frame_stride = o.frame;
   }
+  // the output map: the fused twins read it, and the back kernels behind a hand-over (launch_chain)
+  if (ctx->out_map_on) a.out_map = ctx->d_out_map.get();
   return a;
 }
 
@@ -449,7 +448,7 @@ RxArgs rx_args(t41rx_ctx *ctx, const CallPlan &plan, const float *dI, const floa
 
 // the finish of a 24 kS/s call that left its audio in the scratch (Back::finish24, Back::cw_24k): volume, q15 conversion, the call's layout
 int t41::aud24_finish_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t s) {
-  const Strides o = strides_of(ctx, ctx->nchan, n_frames, 256);
+  const Strides o = strides_of(ctx, audio_rows(ctx), n_frames, 256);  // (an output map: n_rows rows)
   Aud24Args f{};
   f.aud = ctx->d_aud24.get();
   f.out = a.out;
@@ -460,6 +459,7 @@ int t41::aud24_finish_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStre
   f.q15 = a.q15;
   f.coef = a.coef;      // (with parameter sets: the sets' array and the channels' table)
   f.set_of = a.set_of;
+  f.out_map = a.out_map;
   return hip_check(launch_aud24_finish(f, s), "24 kS/s finish kernel launch");
 }
 
@@ -476,6 +476,13 @@ int launch_chain(t41rx_ctx *ctx, const CallPlan &plan, RxArgs a, int n_frames, h
   if (ctx->nb.on && (rc = nb_run(ctx, n_frames, s)) != T41RX_OK) return rc;
   if (cw_det_on(ctx) && (rc = cw_detect_run(ctx, n_frames, s)) != T41RX_OK) return rc;
   if (cw_dec_on(ctx) && (rc = cw_decode_run(ctx, n_frames, s)) != T41RX_OK) return rc;
+  if (plan.handover && a.out_map) {
+    // an output map behind the hand-over: the tap kernel placed its input with the strides so far and stored no audio;
+    // the back kernels place n_rows rows
+    const Strides o = strides_of(ctx, audio_rows(ctx), a.nframes, 2048);
+    a.chan_stride = o.chan;
+    a.frame_stride = o.frame;
+  }
   switch (plan.back) {
     case Back::cw_back:
     case Back::cw_24k:
@@ -505,7 +512,10 @@ int launch_chain(t41rx_ctx *ctx, const CallPlan &plan, RxArgs a, int n_frames, h
 
 int process_device_impl(t41rx_ctx *ctx, const float *dI, const float *dQ, float *dAudio, int n_frames,
                         void *hip_stream, bool q15) {
-  if (!ctx || !dI || !dQ || !dAudio) return fail(T41RX_ERR_ARG, "null argument");
+  // (an output map with no row, t41rx_set_output_map: no audio is written and the pointer is not looked at)
+  const bool no_audio = ctx && audio_rows(ctx) == 0;
+  if (no_audio) dAudio = nullptr;
+  if (!ctx || !dI || !dQ || (!dAudio && !no_audio)) return fail(T41RX_ERR_ARG, "null argument");
   if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
   if ((reinterpret_cast<uintptr_t>(dI) | reinterpret_cast<uintptr_t>(dQ) | reinterpret_cast<uintptr_t>(dAudio)) & 15u)
     return fail(T41RX_ERR_ARG, "I/Q/audio device pointers must be 16-byte aligned");
@@ -832,41 +842,43 @@ int t41rx_process_device_q15(t41rx_ctx *ctx, const int16_t *dQ_in_L, const int16
 }
 
 int t41rx_process_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, const int16_t *Q_in_R, int16_t *Q_out_L, int n_frames) {
-  if (!ctx || !Q_in_L || !Q_in_R || !Q_out_L) return fail(T41RX_ERR_ARG, "null argument");
+  if (!ctx || !Q_in_L || !Q_in_R || (!Q_out_L && audio_rows(ctx) != 0)) return fail(T41RX_ERR_ARG, "null argument");
   if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
   const size_t in_bytes = (size_t)input_rows(ctx) * (size_t)n_frames * (size_t)(4 * ctx->params.fft_length) * sizeof(int16_t);  // an input map: n_streams rows come in
-  const size_t bytes = (size_t)ctx->nchan * (size_t)n_frames * (size_t)audio_frame_len(ctx) * sizeof(int16_t);
+  const size_t bytes = (size_t)audio_rows(ctx) * (size_t)n_frames * (size_t)audio_frame_len(ctx) * sizeof(int16_t);  // an output map: n_rows rows go out
   int rc = ensure_staging(ctx, in_bytes, bytes);
   if (rc != T41RX_OK) return rc;
   HIP_TRY(hipMemcpy(ctx->staging.d_in_i.get(), Q_in_L, in_bytes, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(ctx->staging.d_in_q.get(), Q_in_R, in_bytes, hipMemcpyHostToDevice));
+  if (audio_rows_unused(ctx)) HIP_TRY(hipMemcpy(ctx->staging.d_out.get(), Q_out_L, bytes, hipMemcpyHostToDevice));  // (unused rows are not written)
   rc = t41rx_process_device_q15(ctx, reinterpret_cast<const int16_t *>(ctx->staging.d_in_i.get()), reinterpret_cast<const int16_t *>(ctx->staging.d_in_q.get()),
                                 reinterpret_cast<int16_t *>(ctx->staging.d_out.get()), n_frames, nullptr);
   if (rc != T41RX_OK) return rc;
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(Q_out_L, ctx->staging.d_out.get(), bytes, hipMemcpyDeviceToHost));
+  if (bytes) HIP_TRY(hipMemcpy(Q_out_L, ctx->staging.d_out.get(), bytes, hipMemcpyDeviceToHost));
   return pipe_status(ctx);  // (these calls synchronise: samples of a run whose hand-over broke do not leave with OK)
 }
 
 int t41rx_process_host(t41rx_ctx *ctx, const float *I, const float *Q, float *audio, int n_frames) {
-  if (!ctx || !I || !Q || !audio) return fail(T41RX_ERR_ARG, "null argument");
+  if (!ctx || !I || !Q || (!audio && audio_rows(ctx) != 0)) return fail(T41RX_ERR_ARG, "null argument");
   if (n_frames <= 0) return fail(T41RX_ERR_ARG, "n_frames must be > 0");
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
   const size_t in_fl = (size_t)input_rows(ctx) * (size_t)n_frames * (size_t)(4 * ctx->params.fft_length);  // an input map: n_streams rows come in
-  const size_t nfl = (size_t)ctx->nchan * (size_t)n_frames * (size_t)audio_frame_len(ctx);
+  const size_t nfl = (size_t)audio_rows(ctx) * (size_t)n_frames * (size_t)audio_frame_len(ctx);  // an output map: n_rows rows go out
   {
     const int rc0 = ensure_staging(ctx, in_fl * sizeof(float), nfl * sizeof(float));
     if (rc0 != T41RX_OK) return rc0;
   }
   HIP_TRY(hipMemcpy(ctx->staging.d_in_i.get(), I, in_fl * sizeof(float), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(ctx->staging.d_in_q.get(), Q, in_fl * sizeof(float), hipMemcpyHostToDevice));
+  if (audio_rows_unused(ctx)) HIP_TRY(hipMemcpy(ctx->staging.d_out.get(), audio, nfl * sizeof(float), hipMemcpyHostToDevice));  // (unused rows are not written)
   int rc = t41rx_process_device(ctx, ctx->staging.d_in_i.get(), ctx->staging.d_in_q.get(), ctx->staging.d_out.get(), n_frames, nullptr);
   if (rc != T41RX_OK) return rc;
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(audio, ctx->staging.d_out.get(), nfl * sizeof(float), hipMemcpyDeviceToHost));
+  if (nfl) HIP_TRY(hipMemcpy(audio, ctx->staging.d_out.get(), nfl * sizeof(float), hipMemcpyDeviceToHost));
   return pipe_status(ctx);  // (these calls synchronise: samples of a run whose hand-over broke do not leave with OK)
 }
 

@@ -104,6 +104,11 @@ struct RxArgs {
   // with sets always carries in_map too (an identity map when the caller set none).
   const int *__restrict__ set_of;
   const SetGains *__restrict__ set_gain;
+  // the output map (t41rx_set_output_map), or null: channel c stores its audio to row out_map[c] of `out`, whose (row,
+  // frame) starts at out_map[c] * chan_stride + f * frame_stride samples, or with out_map[c] < 0 stores none and leaves
+  // its interpolator memories alone.  The host has checked every entry against the number of rows and that no row is
+  // named twice.  Only the output-map instantiations read this field.
+  const int *__restrict__ out_map;
 };
 
 // constant table of the N = 512 R point fast convolution (float2 units):
@@ -134,6 +139,8 @@ struct Aud24Args {
   // g = coef[set_of ? set_of[c] : 0].sc[kScOutScale] / DF: the context's block, or with parameter sets the channel's own set's
   const DevCoef *coef;
   const int *set_of;
+  // the output map, or null: channel c's frames go to row out_map[c] of out, or with out_map[c] < 0 nowhere
+  const int *out_map;
 };
 hipError_t launch_aud24_finish(const Aud24Args &a, hipStream_t s);
 

@@ -40,7 +40,16 @@ hipError_t launch_back512(const RxArgs &a, hipStream_t s) {
   // memories from the channel's record and leaves the call's last ones there
   if (a.seg != 1 || !a.aud24) return hipErrorInvalidValue;
   // (q15: arm_float_to_q15 behind the volume, Process.cpp:936)
-  return with_bools([&](auto Q15) { return launch_back_par<Q15>(a, s); }, a.q15 != 0);
+  // An output map (a.out_map): the same kernel in its output-map form, whose waves store to the channel's row or leave.
+  // Only an output map brings a call with parameter sets here (the stages that split the chain refuse the sets): the
+  // form's set twin then interpolates with the taps of the channel's own set, which carry its volume
+  return with_bools(
+      [&](auto Q15, auto OUT, auto SET) {
+        if constexpr (OUT) return launch_rx512<kModeSsb, false, 2, false, false, Q15, true, false, false, SET, false, true>(a, s);
+        else if constexpr (SET) return hipErrorInvalidValue;  // never planned: not compiled
+        else return launch_back_par<Q15>(a, s);
+      },
+      a.q15 != 0, a.out_map != nullptr, a.set_of != nullptr);
 }
 
 T41RX_CLK_READER(t41rx_debug_read_clk_long)

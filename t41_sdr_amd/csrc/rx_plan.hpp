@@ -22,6 +22,7 @@ struct CallFacts {
   bool tap_nco = false, tap_dec = false, tap_demod = false, spect = false, disp = false, pan_rows = false, ft8 = false;
   // the stages that split the chain behind the demodulator
   bool eq = false, nr = false, nb = false, cw_filter = false, cw_det = false;
+  bool omap = false;  // the caller's output map (t41rx_set_output_map): audio rows for the listened channels only
 };
 
 // an rx512_kernel instantiation of the whole chain (PART 0): two calls with equal forms launch the same kernel
@@ -31,18 +32,20 @@ struct KernelForm {
   bool plain = false, agc = false, q15 = false;
   bool pipe = false;   // the pipelined AGC / SAM variants
   bool map_form = false, set_form = false, a24_form = false;  // the mapped form and its set and 24 kS/s twins
+  bool omap_form = false;  // the output-map twin of the mapped forms: the wave stores to row out_map[ch], or to none
 };
 constexpr bool operator==(const KernelForm &x, const KernelForm &y) {
   return x.family == y.family && x.taps == y.taps && x.plain == y.plain && x.agc == y.agc && x.q15 == y.q15 && x.pipe == y.pipe &&
-         x.map_form == y.map_form && x.set_form == y.set_form && x.a24_form == y.a24_form;
+         x.map_form == y.map_form && x.set_form == y.set_form && x.a24_form == y.a24_form && x.omap_form == y.omap_form;
 }
 
 // is this form instantiated?  The launchers' `if constexpr` leaves out exactly what this refuses.
-constexpr bool form_compiled(bool sam, bool taps, bool plain, bool agc, bool pipe, bool map_form, bool set_form, bool a24_form) {
-  return !((taps && (plain || pipe)) || (plain && sam) || (pipe && !(agc || sam)) || (set_form && !map_form) || (a24_form && (!map_form || taps)));
+constexpr bool form_compiled(bool sam, bool taps, bool plain, bool agc, bool pipe, bool map_form, bool set_form, bool a24_form, bool omap_form = false) {
+  return !((taps && (plain || pipe)) || (plain && sam) || (pipe && !(agc || sam)) || (set_form && !map_form) || (a24_form && (!map_form || taps)) ||
+           (omap_form && (!map_form || taps)));
 }
 constexpr bool form_compiled(const KernelForm &k) {
-  return form_compiled(k.family == Family::sam, k.taps, k.plain, k.agc, k.pipe, k.map_form, k.set_form, k.a24_form);
+  return form_compiled(k.family == Family::sam, k.taps, k.plain, k.agc, k.pipe, k.map_form, k.set_form, k.a24_form, k.omap_form);
 }
 // the long-FFT front end (PART 1): PLAIN is built for f32 samples only
 constexpr bool long_front_compiled(bool plain, bool q15) { return !(plain && q15); }
@@ -92,13 +95,17 @@ constexpr CallPlan plan_call(const CallFacts &f) {
   } else if (lng && (f.a24 || stage_taps || stages)) {
     p.valid = false;
     p.why = "audio at 24 kS/s, the stage taps and the chain-splitting stages are built for fft_length 512";
+  } else if (f.omap && lng) {
+    p.valid = false;
+    p.why = "the output map is built for fft_length 512";
   }
   p.seg = f.seg;
   // fft_length 512.  Everything that reads behind the demodulator rides on the tap kernels (the FT8 stage through a demod
   // tap or the hand-over); they hand the audio over when a stage follows or when it leaves @24 kS/s.  The long lengths have
   // neither (params_valid and the setters refuse the side outputs there).
   const bool taps = !lng && (stage_taps || f.spect || f.disp || f.pan_rows || f.ft8 || stages);
-  p.handover = !lng && (stages || (f.a24 && taps));
+  // An output map on the tap kernels hands over as well: they have no output-map twins, the back kernels know the map
+  p.handover = !lng && (stages || ((f.a24 || f.omap) && taps));
   p.scratch = lng || p.handover;
   // AGC on (with the synchronous detector behind it: PSA), or the synchronous detector alone, in calls of four frames or
   // more: shorter calls have nothing to overlap and take the barrier form, which computes the same values
@@ -116,7 +123,10 @@ constexpr CallPlan plan_call(const CallFacts &f) {
   // and the fused 24 kS/s forms are twins of the mapped ones: without a map of the caller's they run with the identity
   k.a24_form = f.a24 && !taps && !lng;
   k.set_form = f.sets && !lng;
-  k.map_form = f.map || k.set_form || k.a24_form;
+  // ... and so is the output-map form: the fused kernel without taps places its stores by the map, or leaves the frame
+  // behind the demodulator for a muted channel
+  k.omap_form = f.omap && !taps && !lng;
+  k.map_form = f.map || k.set_form || k.a24_form || k.omap_form;
   p.need_ident = k.map_form && !f.map;
   if (lng) {
     // 4096, SSB audio with the fixed gain, f32 samples: the whole chain in one kernel (T41RX_SEG_RUN selects the

@@ -98,6 +98,7 @@ class RxChain:
         self.layout = "channel"
         self._audio_rate = 192000  # set_audio_rate
         self._n_streams = 0  # the input map's row count (set_input_map), 0 = no map
+        self._audio_rows = None  # the output map's row count (set_output_map), None = no map
         if NCOFreq is not None:
             self.SetNCOFreq(NCOFreq)
 
@@ -188,6 +189,37 @@ class RxChain:
         """the input map as an int32 array [n_channels] (a copy), or None with the map off"""
         m = np.zeros(self.n_channels, np.int32)
         return m if value(self._lib.t41rx_get_input_map(self._ctx, ptr(m, I32P), self.n_channels)) > 0 else None
+
+    def set_output_map(self, row_of_channel, n_rows=None):
+        """Receiver groups (t41rx_set_output_map): channel c writes its audio to row row_of_channel[c] of the audio, or with
+        -1 writes none; the audio then holds n_rows rows -- [n_rows, n_frames*audio_frame_len], time-major [n_frames,
+        n_rows, audio_frame_len] -- while I / Q and every side output keep their shapes.  No row may be named twice;
+        n_rows defaults to max + 1 (0 with every channel muted: the process calls then return an empty (0, ...) result).
+        A muted channel computes everything but its interpolators and its audio stores.  None switches the map off.
+        Configuration, like the input map: in no checkpoint, kept across reset() / set_state() / CalcFilters(); FFT_LENGTH 512."""
+        if row_of_channel is None:
+            check(self._lib.t41rx_set_output_map(self._ctx, None, 0, 0))
+            self._audio_rows = None
+            return
+        m = int_table(row_of_channel, np.int32, None, "row_of_channel must be a 1-d array of int32 row numbers (-1: no audio), got %r %s")
+        if n_rows is None:
+            n_rows = max(int(m.max()) + 1, 0) if m.size else 0
+        check(self._lib.t41rx_set_output_map(self._ctx, ptr(m, I32P), int(m.size), int(n_rows)))
+        self._audio_rows = int(n_rows)
+
+    @property
+    def audio_rows(self):
+        """rows of audio a process call writes: the output map's n_rows, or n_channels with the map off"""
+        # kept here like the input map's row count and the audio rate, and read the same way: the shape checks make no call
+        # into the library and work on an object that never set a map.  (A map set through the raw handle is not seen.)
+        rows = getattr(self, "_audio_rows", None)
+        return self.n_channels if rows is None else rows
+
+    @property
+    def output_map(self):
+        """the output map as an int32 array [n_channels] (a copy, -1: muted), or None with the map off"""
+        m = np.zeros(self.n_channels, np.int32)
+        return m if value(self._lib.t41rx_get_output_map(self._ctx, ptr(m, I32P), self.n_channels, None)) > 0 else None
 
     def set_param_sets(self, sets, set_of_channel=None):
         """Receiver groups (t41rx_set_param_sets): the context's own parameters are set 0, sets[i] becomes set i + 1, and
@@ -810,13 +842,16 @@ class RxChain:
         return res, pixel, spec
 
     def _out_shape(self, nfr):
-        """the audio's shape for a call of nfr frames: n_channels rows, whatever the input map makes of the input's"""
+        """the audio's shape for a call of nfr frames: audio_rows rows (n_channels, or the output map's n_rows), whatever
+        the input map makes of the input's"""
+        rows = self.audio_rows
         if self.layout == "time":
-            return (nfr, self.n_channels, self.audio_frame_len)
-        return (self.n_channels, nfr * self.audio_frame_len)
+            return (nfr, rows, self.audio_frame_len)
+        return (rows, nfr * self.audio_frame_len)
 
     def _rows_text(self):
-        return "(n_channels=%d, n_streams=%d)" % (self.n_channels, self.n_streams)
+        rows = getattr(self, "_audio_rows", None)  # (named with an output map set only)
+        return "(n_channels=%d, n_streams=%d%s)" % (self.n_channels, self.n_streams, "" if rows is None else ", audio_rows=%d" % rows)
 
     def _check_out_torch(self, out, like, nfr):
         shape = self._out_shape(nfr)

@@ -31,8 +31,11 @@ def fingerprints(lib):
             name, body, base = None, [], None
             def flush():
                 # the padding behind a code object's last s_endpgm (s_nop / s_code_end up to the section's alignment) belongs
-                # to no kernel: without this the last kernel of a translation unit changes hash when another one joins it
-                while body and body[-1].split()[0] in ("s_nop", "s_code_end") and any(b.startswith("s_endpgm") for b in body):
+                # to no kernel: without this the last kernel of a translation unit changes hash when another one joins it.
+                # A zero word of alignment padding between two kernels disassembles as "v_cndmask_b32_e32 v0, s0, v0, vcc".
+                def padding(b):
+                    return b.split()[0] in ("s_nop", "s_code_end") or b == "v_cndmask_b32_e32 v0, s0, v0, vcc"
+                while body and padding(body[-1]) and any(b.startswith("s_endpgm") for b in body[:-1]) and not body[-1].startswith("s_endpgm"):
                     body.pop()
                 if name is not None and body:
                     out[name] = {"sha": hashlib.sha256("\n".join(body).encode()).hexdigest()[:20], "instructions": len(body)}
