@@ -1,5 +1,5 @@
-"""The GPU-side driver of the receive tests, once: sample formats, buffer layouts, one process call, a stream cut into
-calls, and the small checks the stage tests share.  A test file keeps what is its own -- which signal it generates,
+"""The GPU-side driver of the receive tests, once: sample formats, buffer layouts, one process call (its rows, frame
+length and layout taken from the chain), a stream cut into calls, and the small checks the stage tests share.  A test file keeps what is its own -- which signal it generates,
 which setters it calls on the chain, which q15 scale it uses -- as a thin wrapper over calls().  Pure numpy up to
 one_call(); torch and the package are imported where a device is used.
 """
@@ -12,6 +12,10 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-5  # the whole-path bar (test_gpu_parity.py's docstring): block-relative error against the oracle
+ERR_ARG, ERR_UNSUPPORTED = -1, -2  # T41RX_ERR_ARG, T41RX_ERR_UNSUPPORTED (include/t41rx.h)
+INT1, INT2 = slice(152, 176), slice(176, 184)  # kStInt1, kStInt2 in a channel's state record (rx_internal.hpp): the x2 and x4 interpolator memories
+SENT_F32, SENT_Q15 = np.float32(-7777.25), np.int16(0x5A5A)  # what one_call(guard=True) prefills the audio buffer with
+GUARD = 512  # samples behind the audio's rows that must keep the sentinel
 
 
 def to_q15(x, scale=1.0):
@@ -42,11 +46,50 @@ def pack(i, q, layout="channel", q15_scale=None, L=2048):
     return (q, i) if i.dtype == np.int16 else (i, q)
 
 
-def one_call(rx, i, q, *, layout="channel", q15_scale=None, tap_floats=None, host=False):
-    """one process call on channel-major numpy rows: (audio [n_channels, nfr * L], demod tap [n_channels, nfr *
-    tap_floats] or None).  layout says how the context was set up (the caller calls set_buffer_layout); host=True
-    hands numpy arrays to the host-pointer form of the entry point."""
+def streams(rows, nsamp, seed, q15=False):
+    """distinct random samples per row [rows, nsamp]: a wrong row cannot pass"""
+    rng = np.random.default_rng(seed)
+    I = (0.2 * rng.standard_normal((rows, nsamp))).astype(np.float32)
+    Q = (0.2 * rng.standard_normal((rows, nsamp))).astype(np.float32)
+    if q15:
+        I, Q = to_q15(I), to_q15(Q)
+    return I, Q
+
+
+def sentinel_of(a):
+    return SENT_Q15 if a.dtype == np.int16 else SENT_F32
+
+
+def guarded_call(entry, args, shape, sent, host):
+    """entry(*args, out=) into a sentinel-filled buffer of this shape with GUARD samples behind it: the entry returns that
+    very object and leaves the guard alone.  Returns the buffer's rows as numpy, what nobody wrote still the sentinel."""
+    n = int(np.prod(shape))
+    if host:
+        big = np.full(n + GUARD, sent, sent.dtype)
+        out = big[:n].reshape(shape)
+        assert entry(*args, out=out) is out
+    else:
+        import torch
+        q15 = sent.dtype == np.int16
+        big = torch.full((n + GUARD,), int(sent) if q15 else float(sent), dtype=torch.int16 if q15 else torch.float32, device="cuda")
+        out = big[:n].view(shape)
+        assert entry(*args, out=out) is out
+        torch.cuda.synchronize()
+        big = big.cpu().numpy()
+    assert (big[n:] == sent).all(), "the call wrote behind the audio's rows"
+    return big[:n].reshape(shape)
+
+
+def one_call(rx, i, q, *, layout=None, q15_scale=None, tap_floats=None, host=False, guard=False):
+    """one process call on channel-major numpy rows [input rows, nfr * frame_len]: (audio [audio_rows, nfr *
+    audio_frame_len], demod tap [n_channels, nfr * tap_floats] or None).  The rows and the frame length of the audio are
+    the chain's (audio_rows, audio_frame_len; n_channels and frame_len for a chain that has neither), the layout is the
+    chain's unless given (the caller calls set_buffer_layout), the input rows are the arrays'.  host=True hands numpy
+    arrays to the host-pointer form of the entry point; guard=True passes out= through guarded_call()."""
     L, nch = rx.frame_len, rx.n_channels
+    rows, La = getattr(rx, "audio_rows", nch), getattr(rx, "audio_frame_len", L)
+    if layout is None:
+        layout = getattr(rx, "layout", "channel")
     nfr = i.shape[1] // L
     tap = None
     if tap_floats:
@@ -54,16 +97,21 @@ def one_call(rx, i, q, *, layout="channel", q15_scale=None, tap_floats=None, hos
         tap = torch.zeros(nch, nfr * tap_floats, device="cuda")
         rx.set_debug_taps(demod=tap)
     args = pack(i, q, layout, q15_scale, L)
-    entry = rx.ProcessIQData_q15 if args[0].dtype == np.int16 else rx.ProcessIQData
+    q15 = args[0].dtype == np.int16
+    entry = rx.ProcessIQData_q15 if q15 else rx.ProcessIQData
+    shape = (nfr, rows, La) if layout == "time" else (rows, nfr * La)
     if not host:
         import torch
         args = tuple(torch.from_numpy(v).cuda() for v in args)
-    out = entry(*args)
-    if not host:
-        out = out.cpu().numpy()
-    assert out.shape == ((nfr, nch, L) if layout == "time" else (nch, nfr * L))
+    if guard:
+        out = guarded_call(entry, args, shape, SENT_Q15 if q15 else SENT_F32, host)
+    else:
+        out = entry(*args)
+        if not host:
+            out = out.cpu().numpy()
+    assert out.shape == shape
     if layout == "time":
-        out = from_time_major(out, nch, nfr, L)
+        out = from_time_major(out, rows, nfr, La)
     return out, None if tap is None else tap.cpu().numpy()
 
 
@@ -79,6 +127,22 @@ def calls(rx, I, Q, edges, *, after=None, **one_call_options):
         if after is not None:
             seen.append(after(rx, a, b))
     return np.concatenate(outs, axis=1), None if taps[0] is None else np.concatenate(taps, axis=1), seen
+
+
+def bits(x):
+    """float32 arrays as their words: a state record holds the oscillator's 64-bit phase, whose halves read as floats may
+    be NaNs, and equal NaNs do not compare equal"""
+    x = np.ascontiguousarray(x)
+    return x.view(np.uint32) if x.dtype == np.float32 else x
+
+
+def same(a, b):
+    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
+
+
+def first(t, nch, nfr, per):
+    """what a call of nfr frames wrote to a side-output tensor sized for more: [nch][nfr * per] from its start"""
+    return t.reshape(-1)[:nch * nfr * per].reshape(nch, nfr * per).cpu().numpy()
 
 
 @pytest.fixture(scope="module")

@@ -8,10 +8,6 @@ either rate), and the 192 kS/s context for everything that must not move.  19 ch
 tail, five 4-wave ones with a ragged last.  Calls of 1, 3 and 6 frames: 3 takes the barrier form of the AGC / SAM
 kernels, 6 the pipelined one.
 
-rx_harness.one_call() checks its result against the 192 kS/s shape, so the calls go through call24() below, the same
-driver on rx.audio_frame_len (it serves both rates); pack(), the layout helpers, TOL, to_q15 and refused are the
-harness's.
-
 The synchronous detector is compared with the oracle as tests/test_sam.py compares it at 192 kS/s -- from frame LOCKED
 on, within 1e-5, over a stream of three 6-frame calls -- because before lock two evaluations of the loop follow different
 trajectories (test_gpu_sam_pull_in_bound's docstring); its first 6 frames are pinned bit for bit to the HIP path's own
@@ -22,18 +18,15 @@ import pytest
 
 import oracle_lib as O
 import siggen
-from rx_harness import TOL, T, from_time_major, pack, refused, to_q15  # noqa: F401  (T: a fixture)
+import group_harness as G
+from group_harness import D, L, NCH, SET_OF as SETOF
+from rx_harness import ERR_UNSUPPORTED, INT1, INT2, TOL, T, calls, one_call, refused, same, to_q15  # noqa: F401  (T: a fixture)
 from stage_reference import nr_stage, vol_scale
 
 pytestmark = pytest.mark.gpu
 
-L, D = 2048, 256
-NCH = 19
 AM_TOL = 5e-5  # tests/test_gpu_parity.py: the bound test_stage_taps_match_the_oracle applies to the AM demod tap
-ERR_ARG, ERR_UNSUPPORTED = -1, -2
-# the state record (t41_sdr_amd/csrc/rx_internal.hpp): the x2 and x4 interpolator memories
-INT1, INT2 = slice(152, 176), slice(176, 184)
-GENERAL = dict(RFgain=3, IQAmpCorrectionFactor=1.02, IQPhaseCorrectionFactor=-0.013)  # the general front end
+GENERAL = dict(RFgain=3, IQAmpCorrectionFactor=1.02, IQPhaseCorrectionFactor=-0.013)  # the general front end (this file's)
 
 
 def g_of(audioVolume=30):
@@ -41,49 +34,8 @@ def g_of(audioVolume=30):
     return np.float32(vol_scale(audioVolume) / np.float32(8.0))
 
 
-def bits(x):
-    x = np.ascontiguousarray(x)
-    return x.view(np.uint32) if x.dtype == np.float32 else x
-
-
-def same(a, b):
-    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
-
-
-def call24(rx, i, q, *, layout="channel", q15_scale=None, host=False, tap=False):
-    """one process call on channel-major numpy rows at the context's audio rate: (audio [n_channels, nfr *
-    audio_frame_len], demod tap [n_channels, nfr * 256] or None)"""
-    import torch
-    nch, nfr, A = rx.n_channels, i.shape[1] // L, rx.audio_frame_len
-    t = None
-    if tap:
-        t = torch.zeros(nch, nfr * D, device="cuda")
-        rx.set_debug_taps(demod=t)
-    args = pack(i, q, layout, q15_scale, L)
-    entry = rx.ProcessIQData_q15 if args[0].dtype == np.int16 else rx.ProcessIQData
-    if not host:
-        args = tuple(torch.from_numpy(v).cuda() for v in args)
-    out = entry(*args)
-    if not host:
-        out = out.cpu().numpy()
-    assert out.shape == ((nfr, nch, A) if layout == "time" else (nch, nfr * A))
-    if layout == "time":
-        out = from_time_major(out, nch, nfr, A)
-    return out, None if t is None else t.cpu().numpy()
-
-
-def stream24(rx, I, Q, edges, **kw):
-    outs = [call24(rx, I[:, a * L:b * L], Q[:, a * L:b * L], **kw) for a, b in zip(edges[:-1], edges[1:])]
-    return np.concatenate([o for o, _ in outs], axis=1), None if outs[0][1] is None else np.concatenate([t for _, t in outs], axis=1)
-
-
 def chain(T, kw, nco, rate=24000, layout="channel"):
-    rx = T.RxChain(len(nco), T.default_params(**kw), NCOFreq=nco)
-    if layout != "channel":
-        rx.set_buffer_layout(layout)
-    if rate != 192000:
-        rx.set_audio_rate(rate)
-    return rx
+    return G.chain(T, kw, nco, rate=rate, layout=layout)[0]
 
 
 def signal(kw, nch, nfr, nco, seed):
@@ -136,7 +88,7 @@ def test_fused_form_against_the_oracle(T, name, agc):
     nfr = 6
     nco = siggen.nco_grid(NCH, seed=21)
     I, Q = signal(kw, NCH, nfr, nco, seed=22)
-    got, _ = call24(chain(T, kw, nco), I, Q)
+    got, _ = one_call(chain(T, kw, nco), I, Q)
     ref = oracle_demod(kw, nco, I, Q) * g_of()
     e = tap_rel(got, ref)
     print("%s AGCMode %d: worst relative error %.2e (bound %.0e)" % (name, agc, e.max(), tol))
@@ -154,13 +106,13 @@ def test_sam_against_the_oracle_and_its_own_tap(T, agc):
     nfr = 18
     nco = siggen.nco_grid(NCH, seed=21)
     I, Q = siggen.make_am_carrier(NCH, nfr * L, nco, seed=40 + agc)
-    got, _ = stream24(chain(T, kw, nco), I, Q, [0, 6, 12, 18])
+    got, _, _ = calls(chain(T, kw, nco), I, Q, [0, 6, 12, 18])
     ref = oracle_demod(kw, nco, I, Q) * g_of()
     e = tap_rel(got, ref)
     print("SAM AGCMode %d: worst relative error per frame %s" % (agc, " ".join("%.1e" % v for v in e.max(axis=0))))
     assert np.isfinite(got).all() and np.abs(ref[:, S.LOCKED * D:]).max() > 1e-4
     assert e[:, S.LOCKED:].max() <= TOL, e[:, S.LOCKED:].max()
-    _, tap = call24(chain(T, kw, nco, rate=192000), I[:, :6 * L], Q[:, :6 * L], tap=True)
+    _, tap = one_call(chain(T, kw, nco, rate=192000), I[:, :6 * L], Q[:, :6 * L], tap_floats=D)
     assert same(got[:, :6 * D], tap * g_of())
 
 
@@ -181,11 +133,11 @@ def test_output_is_the_demod_tap_times_g(T, name, kw, layout):
     nfr = 6
     nco = siggen.nco_grid(NCH, seed=31)
     I, Q = signal(kw, NCH, nfr, nco, seed=32)
-    with_tap, tap = call24(chain(T, kw, nco, layout=layout), I, Q, layout=layout, tap=True)
+    with_tap, tap = one_call(chain(T, kw, nco, layout=layout), I, Q, layout=layout, tap_floats=D)
     g = g_of(kw.get("audioVolume", 30))
     assert np.abs(tap).reshape(NCH, nfr, D).max(axis=2).min() > 0
     assert same(with_tap, tap * g)
-    fused, _ = call24(chain(T, kw, nco, layout=layout), I, Q, layout=layout)
+    fused, _ = one_call(chain(T, kw, nco, layout=layout), I, Q, layout=layout)
     if name == "nfm":
         e = tap_rel(fused, with_tap)
         print("nfm: fused form against the tap kernel's audio, worst relative difference %.2e" % e.max())
@@ -205,16 +157,16 @@ def test_state_records_equal_but_for_the_interpolator_memories(T, name, kw):
     nco = siggen.nco_grid(NCH, seed=41)
     I, Q = signal(kw, NCH, 9, nco, seed=42)
     a, b = chain(T, kw, nco, rate=192000), chain(T, kw, nco, rate=192000)
-    first, _ = call24(a, I[:, :2 * L], Q[:, :2 * L])
-    call24(b, I[:, :2 * L], Q[:, :2 * L])
+    first, _ = one_call(a, I[:, :2 * L], Q[:, :2 * L])
+    one_call(b, I[:, :2 * L], Q[:, :2 * L])
     before = a.state_records().copy()
     assert same(before, b.state_records()) and before[:, INT1].any() and before[:, INT2].any()
     size = len(a.get_state())
     a.set_audio_rate(24000)
     assert a.audio_rate == 24000 and a.audio_frame_len == D and len(a.get_state()) == size
     sl = slice(2 * L, 8 * L)
-    got, _ = call24(a, I[:, sl], Q[:, sl])
-    call24(b, I[:, sl], Q[:, sl])
+    got, _ = one_call(a, I[:, sl], Q[:, sl])
+    one_call(b, I[:, sl], Q[:, sl])
     ra, rb = a.state_records(), b.state_records()
     rest = np.ones(ra.shape[1], bool)
     rest[INT1] = rest[INT2] = False
@@ -223,20 +175,18 @@ def test_state_records_equal_but_for_the_interpolator_memories(T, name, kw):
     assert not same(rb[:, INT1], before[:, INT1])  # (the 192 kS/s context's did move)
     assert np.abs(got).reshape(NCH, 6, D).max(axis=2).min() > 0
     a.set_audio_rate(192000)
-    again, _ = call24(a, I[:, 8 * L:], Q[:, 8 * L:])
+    again, _ = one_call(a, I[:, 8 * L:], Q[:, 8 * L:])
     assert again.shape == (NCH, L) and np.isfinite(again).all() and np.abs(again).max() > 0
 
 
 def test_side_outputs_equal_the_192k_context(T):
     """audio spectrum / S-meter words, the panadapter's rows and the FT8 stage's status words and power bytes: the same
     bits at either rate (16 frames, so that the FT8 stage finishes a block of 15)"""
-    import os
     import torch
     nfr = 16
     kw = dict(mode=0, FLoCut=200, FHiCut=3000)
     nco = siggen.nco_grid(NCH, seed=51)
     I, Q = signal(kw, NCH, nfr, nco, seed=52)
-    grad = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "display", "gradient.npz"))["gradient"]
 
     def spectrum(rx):
         sp, mx = torch.zeros(NCH, nfr, 1024, device="cuda"), torch.zeros(NCH, nfr, 3, device="cuda")
@@ -244,23 +194,20 @@ def test_side_outputs_equal_the_192k_context(T):
         return lambda: [sp.cpu().numpy(), mx.cpu().numpy()]
 
     def panadapter(rx):
-        rx.set_panadapter_tables(grad)
-        bufs = rx.set_panadapter(True, spectrumZoom=1, currentScale=1, update_period=3, max_rows=nfr)
+        bufs = G.panadapter(rx, nfr, spectrumZoom=1, currentScale=1, update_period=3)
         return lambda: [bufs[n].cpu().numpy() for n, _, _ in rx.PANADAPTER_ROWS]
 
     def ft8(rx):
-        rx.set_ft8_tables()
-        rx.set_ft8(1, nfr)
-        rx.ft8_sync()
-        return lambda: [rx.ft8_status(nfr).cpu().numpy(), rx.ft8_power().cpu().numpy()]
+        G.ft8_receive(rx, nfr)
+        return lambda: G.ft8_results(rx, nfr)
 
-    plain, _ = call24(chain(T, dict(kw, **GENERAL), nco), I, Q)
+    plain, _ = one_call(chain(T, dict(kw, **GENERAL), nco), I, Q)
     for what, setup in (("audio spectrum", spectrum), ("panadapter", panadapter), ("FT8", ft8)):
         res, aud = [], []
         for rate in (24000, 192000):
             rx = chain(T, dict(kw, **GENERAL), nco, rate=rate)
             read = setup(rx)
-            aud.append(call24(rx, I, Q)[0])
+            aud.append(one_call(rx, I, Q)[0])
             res.append(read())
         assert all(same(x, y) for x, y in zip(*res)) and any(x.any() for x in res[0]), what
         # and the audio of the call with the side output on is the fused form's (general front end in both)
@@ -275,8 +222,8 @@ def test_time_major_equals_channel_major(T, kw, q15):
     nco = siggen.nco_grid(NCH, seed=61)
     I, Q = signal(kw, NCH, 6, nco, seed=62)
     opt = dict(q15_scale=1.0) if q15 else {}
-    a, _ = call24(chain(T, dict(kw, audioVolume=100), nco), I, Q, **opt)
-    b, _ = call24(chain(T, dict(kw, audioVolume=100), nco, layout="time"), I, Q, layout="time", **opt)
+    a, _ = one_call(chain(T, dict(kw, audioVolume=100), nco), I, Q, **opt)
+    b, _ = one_call(chain(T, dict(kw, audioVolume=100), nco, layout="time"), I, Q, layout="time", **opt)
     assert a.dtype == (np.int16 if q15 else np.float32) and np.abs(a.astype(np.float64)).max(axis=1).min() > 0
     assert same(a, b)
 
@@ -289,22 +236,11 @@ def test_mapped_call_equals_replicated_rows(T, kw, layout):
     I, Q = (0.2 * np.random.default_rng(64).standard_normal((2, 2, 6 * L))).astype(np.float32)  # two streams of noise
     a = chain(T, kw, nco, layout=layout)
     a.set_input_map(smap, 2)
-    got, _ = call24(a, I, Q, layout=layout) if layout == "channel" else _mapped_time(a, I, Q)
-    want, _ = call24(chain(T, kw, nco, layout=layout), I[smap], Q[smap], layout=layout)
+    got, _ = one_call(a, I, Q, layout=layout)
+    want, _ = one_call(chain(T, kw, nco, layout=layout), I[smap], Q[smap], layout=layout)
     assert np.abs(got).max(axis=1).min() > 0 and same(got, want)
 
 
-def _mapped_time(rx, I, Q):
-    """call24 for a time-major mapped call: the input holds n_streams rows, the output n_channels"""
-    import torch
-    nfr = I.shape[1] // L
-    args = tuple(torch.from_numpy(v).cuda() for v in pack(I, Q, "time", None, L))
-    out = rx.ProcessIQData(*args).cpu().numpy()
-    assert out.shape == (nfr, rx.n_channels, D)
-    return from_time_major(out, rx.n_channels, nfr, D), None
-
-
-SETOF = np.array([2, 0, 0, 1, 2, 1, 1, 0, 2, 2, 0, 1, 0, 0, 2, 1, 2, 0, 1], np.int32)
 # the sets differ in sideband, pass band and audioVolume
 SETS = [dict(mode=1, FLoCut=-3000, FHiCut=-200, audioVolume=45), dict(mode=0, FLoCut=300, FHiCut=1000, audioVolume=18)]
 
@@ -321,11 +257,11 @@ def test_mixed_context_equals_the_per_set_contexts(T, agc, q15):
     opt = dict(q15_scale=1.0) if q15 else {}
     mixed = chain(T, base, nco)
     mixed.set_param_sets(extra, SETOF)
-    got, _ = call24(mixed, I, Q, **opt)
+    got, _ = one_call(mixed, I, Q, **opt)
     assert np.abs(got.astype(np.float64)).max(axis=1).min() > 0
     for k, e in enumerate([{}] + extra):
         ref = chain(T, dict(base, **e), nco)
-        want, _ = call24(ref, I, Q, **opt)
+        want, _ = one_call(ref, I, Q, **opt)
         sel = SETOF == k
         assert same(got[sel], want[sel]), "audio of set %d" % k
         assert same(mixed.state_records()[sel], ref.state_records()[sel]), "records of set %d" % k
@@ -338,8 +274,8 @@ def test_calls_of_1_2_3_frames_equal_one_call_of_6(T, kw):
     nco = siggen.nco_grid(NCH, seed=67)
     I, Q = signal(kw, NCH, 6, nco, seed=68)
     a, b = chain(T, kw, nco), chain(T, kw, nco)
-    whole, _ = call24(a, I, Q)
-    parts, _ = stream24(b, I, Q, [0, 1, 3, 6])
+    whole, _ = one_call(a, I, Q)
+    parts, _, _ = calls(b, I, Q, [0, 1, 3, 6])
     assert np.abs(whole).max(axis=1).min() > 0
     assert same(parts, whole) and same(a.state_records(), b.state_records())
 
@@ -352,14 +288,14 @@ def test_host_entry_equals_device_entry(T, layout, q15):
     I, Q = signal(kw, NCH, 6, nco, seed=70)
     opt = dict(q15_scale=1.0) if q15 else {}
     a, b = chain(T, kw, nco, layout=layout), chain(T, kw, nco, layout=layout)
-    dev, _ = call24(a, I, Q, layout=layout, **opt)
-    host, _ = call24(b, I, Q, layout=layout, host=True, **opt)
+    dev, _ = one_call(a, I, Q, layout=layout, **opt)
+    host, _ = one_call(b, I, Q, layout=layout, host=True, **opt)
     assert host.dtype == (np.int16 if q15 else np.float32) and np.abs(dev.astype(np.float64)).max() > 0
     assert same(dev, host) and np.array_equal(a.get_state(), b.get_state())
     # the stage-tap path (tap kernel + finish kernel) through the host entry too
     c = chain(T, dict(kw, **GENERAL), nco, layout=layout)
     d = chain(T, dict(kw, **GENERAL), nco, layout=layout)
-    assert same(call24(c, I, Q, layout=layout, host=True, tap=True, **opt)[0], call24(d, I, Q, layout=layout, **opt)[0])
+    assert same(one_call(c, I, Q, layout=layout, host=True, tap_floats=D, **opt)[0], one_call(d, I, Q, layout=layout, **opt)[0])
 
 
 # ---- 5. q15 ---------------------------------------------------------------------------------------------------------------
@@ -374,7 +310,7 @@ def test_q15_entries_against_the_oracle(T, name, kw, host):
     nco = siggen.nco_grid(NCH, seed=71)
     I, Q = signal(kw, NCH, nfr, nco, seed=72)
     qI, qQ = to_q15(I), to_q15(Q)
-    got, _ = call24(chain(T, kw, nco), qI, qQ, host=host)
+    got, _ = one_call(chain(T, kw, nco), qI, qQ, host=host)
     want = to_q15(oracle_demod(kw, nco, qI, qQ, q15=True).astype(np.float64) * np.float64(g_of(100)))
     d = np.abs(got.astype(np.int32) - want.astype(np.int32))
     print("%s: worst difference %d LSB, differing %.3f, peak %d" % (name, d.max(), (d > 0).mean(), np.abs(want.astype(np.int32)).max()))
@@ -384,7 +320,7 @@ def test_q15_entries_against_the_oracle(T, name, kw, host):
 
 # ---- 6. stages ------------------------------------------------------------------------------------------------------------
 def _stage_run(T, rx, I, Q):
-    got, tap = call24(rx, I, Q, tap=True)
+    got, tap = one_call(rx, I, Q, tap_floats=D)
     assert np.isfinite(got).all() and np.abs(tap).max() > 0
     return got, tap
 

@@ -4,14 +4,15 @@ they arrive -- instead of [n_channels][n_frames * frame_len].  Same arithmetic o
 checkpoints must match the channel-major call bit for bit, in every mode, sample format and kernel form; and against
 the oracle like any other call.
 """
+from functools import partial
+
 import numpy as np
 import pytest
 
 import oracle_lib as O
 import siggen
-from rx_harness import T, from_time_major, to_q15, to_time_major  # noqa: F401  (T: the loaded package, a fixture)
-
-L = 2048
+from group_harness import L, chain, side_outputs
+from rx_harness import T, one_call, to_q15  # noqa: F401  (T: the loaded package, a fixture)
 
 
 def test_layout_symbols_and_constants(built):
@@ -49,48 +50,30 @@ CASES = [
 @pytest.mark.gpu
 @pytest.mark.parametrize("name,kw,nfr", CASES, ids=[c[0] for c in CASES])
 def test_time_major_equals_channel_major(T, name, kw, nfr):
-    import torch
     nch = 37  # ragged last workgroup
     nco = siggen.nco_grid(nch, seed=3)
     I, Q = siggen.make_iq(nch, 2 * nfr * L, nco, mode=min(kw["mode"], 3) if kw["mode"] != 8 else 2, seed=21)
-    a = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-    b = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-    b.set_buffer_layout("time")
+    (a, _), (b, _) = chain(T, kw, nco), chain(T, kw, nco, layout="time")
     for call in range(2):  # the second call continues from the state the first left
         sl = slice(call * nfr * L, (call + 1) * nfr * L)
-        dI, dQ = torch.from_numpy(I[:, sl].copy()).cuda(), torch.from_numpy(Q[:, sl].copy()).cuda()
-        oa = a.ProcessIQData(dI, dQ)
-        tI = dI.view(nch, nfr, L).transpose(0, 1).contiguous()
-        tQ = dQ.view(nch, nfr, L).transpose(0, 1).contiguous()
-        ob = b.ProcessIQData(tI, tQ)
-        assert tuple(ob.shape) == (nfr, nch, L)
-        assert torch.equal(oa.view(nch, nfr, L).transpose(0, 1), ob), (name, call)
+        oa, ob = one_call(a, I[:, sl], Q[:, sl])[0], one_call(b, I[:, sl], Q[:, sl])[0]  # (b's is [nfr, nch, L]: one_call checks)
+        assert np.array_equal(oa, ob), (name, call)
     assert np.array_equal(a.get_state(), b.get_state())
 
 
 @pytest.mark.gpu
 def test_time_major_q15_and_host_entry_points(T):
-    import torch
     kw = dict(mode=0, FLoCut=200, FHiCut=3000, AGCMode=1)
     nch, nfr = 19, 5
     nco = siggen.nco_grid(nch, seed=4)
     I, Q = siggen.make_iq(nch, nfr * L, nco, mode=0, seed=22)
     qi, qq = to_q15(I), to_q15(Q)
-    a = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-    b = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-    b.set_buffer_layout("time")
-    oa = a.ProcessIQData_q15(torch.from_numpy(qq).cuda(), torch.from_numpy(qi).cuda())
-    tq = torch.from_numpy(qq).cuda().view(nch, nfr, L).transpose(0, 1).contiguous()
-    ti = torch.from_numpy(qi).cuda().view(nch, nfr, L).transpose(0, 1).contiguous()
-    ob = b.ProcessIQData_q15(tq, ti)
-    assert torch.equal(oa.view(nch, nfr, L).transpose(0, 1), ob)
+    (a, _), (b, _) = chain(T, kw, nco), chain(T, kw, nco, layout="time")
+    oa, ob = one_call(a, qi, qq)[0], one_call(b, qi, qq)[0]
+    assert oa.dtype == np.int16 and np.array_equal(oa, ob)
     # host pointers, f32
-    c = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-    d = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-    d.set_buffer_layout("time")
-    oc = c.ProcessIQData(I, Q)
-    od = d.ProcessIQData(to_time_major(I, nch, nfr, L), to_time_major(Q, nch, nfr, L))
-    assert np.array_equal(oc.reshape(nch, nfr, L).transpose(1, 0, 2), od)
+    (c, _), (d, _) = chain(T, kw, nco), chain(T, kw, nco, layout="time")
+    assert np.array_equal(one_call(c, I, Q, host=True)[0], one_call(d, I, Q, host=True)[0])
 
 
 @pytest.mark.gpu
@@ -108,23 +91,10 @@ def test_time_major_side_outputs_and_taps(T, fmt):
         I, Q = to_q15(I), to_q15(Q)
     outs = {}
     for layout in ("channel", "time"):
-        rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-        rx.set_buffer_layout(layout)
-        spect, mx = torch.zeros(nch, nfr, 1024, device="cuda"), torch.zeros(nch, nfr, 3, device="cuda")
-        spec, old = torch.zeros(nch, nfr, 512, device="cuda"), torch.zeros(nch, nfr, 512, device="cuda")
-        dec, dem = torch.zeros(nch, nfr * 512, device="cuda"), torch.zeros(nch, nfr * 256, device="cuda")
-        rx.set_audio_spectrum(spect, mx)
-        rx.set_display_spectrum(spec, old, spectrumZoom=2)
-        rx.set_debug_taps(dec=dec, demod=dem)
-        dI, dQ = torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()
-        if layout == "time":
-            dI = dI.view(nch, nfr, L).transpose(0, 1).contiguous()
-            dQ = dQ.view(nch, nfr, L).transpose(0, 1).contiguous()
-        o = rx.ProcessIQData_q15(dQ, dI) if fmt == "q15" else rx.ProcessIQData(dI, dQ)
-        if layout == "time":
-            o = o.transpose(0, 1).reshape(nch, nfr * L)
+        rx, side = chain(T, kw, nco, layout=layout, setup=partial(side_outputs, nfr=nfr, taps=("dec", "demod"), nch=nch))
+        o, _ = one_call(rx, I, Q)
         torch.cuda.synchronize()
-        outs[layout] = [t.cpu().numpy() for t in (o, spect, mx, spec, old, dec, dem)] + [rx.get_state()]
+        outs[layout] = [o] + [t.cpu().numpy() for t in side] + [rx.get_state()]  # audio, spect, mx, spec, old, dec, dem, state
     for a, b in zip(outs["channel"], outs["time"]):
         assert np.array_equal(a, b)
     assert np.abs(outs["time"][1]).max() > 0 and np.abs(outs["time"][3]).max() > 0 and np.abs(outs["time"][6]).max() > 0
@@ -133,15 +103,11 @@ def test_time_major_side_outputs_and_taps(T, fmt):
 @pytest.mark.gpu
 def test_time_major_against_the_oracle(T):
     """not only equal to the other layout: the time-major call is checked against the oracle directly"""
-    import torch
     kw = dict(mode=0, FLoCut=200, FHiCut=3000)
     nch, nfr = 24, 6
     nco = siggen.nco_grid(nch, seed=5)
     I, Q = siggen.make_iq(nch, nfr * L, nco, mode=0, seed=23)
-    rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-    rx.set_buffer_layout("time")
-    tI, tQ = torch.from_numpy(to_time_major(I, nch, nfr, L)).cuda(), torch.from_numpy(to_time_major(Q, nch, nfr, L)).cuda()
-    got = from_time_major(rx.ProcessIQData(tI, tQ).cpu().numpy(), nch, nfr, L)
+    got, _ = one_call(chain(T, kw, nco, layout="time")[0], I, Q)
     ref = O.OracleBatch(O.default_params(**kw), nco).process(I, Q)
     err = siggen.block_rel_err(got, ref, L)
     assert err.max() <= 1e-5, err.max()

@@ -1,11 +1,16 @@
-"""The test support code itself (tests/rx_harness.py, tests/stage_reference.py), without a device: layouts, sample
-formats, the (Q, I) order of the q15 entry points, a stream cut into calls against a stub chain, and the reference
-interpolators against the oracle's primitive called directly."""
+"""The test support code itself (tests/rx_harness.py, tests/group_harness.py, tests/stage_reference.py), without a device:
+layouts, sample formats, the (Q, I) order of the q15 entry points, a stream cut into calls against a stub chain, one call
+on a stub receiver group (rows, frame length and layout from the chain; the guard), the group tests' checkers made to
+fail, and the reference interpolators against the oracle's primitive called directly."""
+from types import SimpleNamespace
+
 import numpy as np
 import pytest
 
+import group_harness as G
 import oracle_lib as O
-from rx_harness import calls, from_time_major, one_call, pack, to_q15, to_time_major
+from rx_harness import (GUARD, INT1, INT2, SENT_F32, SENT_Q15, bits, calls, from_time_major, one_call, pack, same, sentinel_of,
+                        streams, to_q15, to_time_major)
 from stage_reference import interp, vol_scale
 
 
@@ -93,6 +98,150 @@ def test_calls_reassemble_the_uncut_stream(layout, q15):
             i, q = to_time_major(i, nch, b - a, L), to_time_major(q, nch, b - a, L)
         assert entry == ("q15" if q15 else "f32") and first.flags["C_CONTIGUOUS"] and second.flags["C_CONTIGUOUS"]
         assert np.array_equal(first, q if q15 else i) and np.array_equal(second, i if q15 else q)
+
+
+class GroupStub:
+    """a numpy model of a receiver group in the shapes one_call() reads from a chain: channel c takes samples c .. c + 2
+    of every frame of stream STREAM_OF[c]'s I and writes them to row ROW_OF[c] of the audio, or with -1 nowhere; row 1
+    has no channel.  fault: "behind" writes one sample behind out's rows, "copy" returns another object than out, "shape"
+    returns the input's shape."""
+    frame_len, audio_frame_len, n_channels, n_streams, audio_rows = 8, 2, 5, 3, 4
+    STREAM_OF, ROW_OF, UNUSED = (2, 0, 1, 0, 2), (3, -1, 0, -1, 2), 1
+
+    def __init__(self, layout="channel", fault=None):
+        self.layout, self.fault, self.seen = layout, fault, []
+
+    def ProcessIQData(self, i, q, out=None):
+        return self.process("f32", i, q, i, out)
+
+    def ProcessIQData_q15(self, q, i, out=None):
+        return self.process("q15", q, i, i, out)
+
+    def process(self, entry, first, second, i, out):
+        self.seen.append((entry, first, second, out))
+        L, La, time = self.frame_len, self.audio_frame_len, self.layout == "time"
+        nfr = i.shape[0] if time else i.shape[1] // L
+        if out is None:
+            out = np.zeros((nfr, self.audio_rows, La) if time else (self.audio_rows, nfr * La), i.dtype)
+        for c, (s, r) in enumerate(zip(self.STREAM_OF, self.ROW_OF)):
+            for f in range(nfr if r >= 0 else 0):
+                if time:
+                    out[f, r] = i[f, s, c:c + La]
+                else:
+                    out[r, f * La:(f + 1) * La] = i[s, f * L + c:f * L + c + La]
+        if self.fault == "behind":
+            out.base[out.size] = 0  # (out is a view of the guarded buffer's front)
+        return {"copy": out.copy(), "shape": np.zeros(i.shape, i.dtype)}.get(self.fault, out)
+
+
+@pytest.mark.parametrize("guard", [False, True], ids=["plain", "guard"])
+@pytest.mark.parametrize("q15", [False, True], ids=["f32", "q15"])
+@pytest.mark.parametrize("layout", ["channel", "time"])
+def test_one_call_takes_rows_frame_length_and_layout_from_the_chain(layout, q15, guard):
+    """3 streams in, 5 channels, 4 rows out with one unused, 2 frames of 8 samples in and 2 out: the host form, with the
+    layout left to the chain"""
+    rx, nfr = GroupStub(layout), 2
+    I, Q = streams(rx.n_streams, nfr * rx.frame_len, 7, q15)
+    assert I.dtype == (np.int16 if q15 else np.float32) and len({r.tobytes() for r in np.concatenate([I, Q])}) == 2 * rx.n_streams
+    got, tap = one_call(rx, I, Q, host=True, guard=guard)
+    (entry, first, second, out), = rx.seen
+    want_in = (nfr, rx.n_streams, rx.frame_len) if layout == "time" else (rx.n_streams, nfr * rx.frame_len)
+    assert entry == ("q15" if q15 else "f32") and first.shape == second.shape == want_in  # the input's rows, not n_channels
+    assert np.array_equal(first, pack(I, Q, layout, None, rx.frame_len)[0])
+    if guard:
+        assert out.shape == ((nfr, rx.audio_rows, rx.audio_frame_len) if layout == "time" else (rx.audio_rows, nfr * rx.audio_frame_len))
+        assert out.dtype == I.dtype
+    else:
+        assert out is None
+    want = np.full((rx.audio_rows, nfr * rx.audio_frame_len), sentinel_of(I) if guard else 0, I.dtype)  # what nobody writes
+    for c, (s, r) in enumerate(zip(rx.STREAM_OF, rx.ROW_OF)):
+        if r >= 0:
+            want[r] = I[s].reshape(nfr, rx.frame_len)[:, c:c + rx.audio_frame_len].reshape(-1)
+    assert tap is None and got.dtype == I.dtype and np.array_equal(got, want) and rx.UNUSED not in rx.ROW_OF
+    assert np.array_equal(one_call(GroupStub(layout), I, Q, layout=layout, host=True, guard=guard)[0], got)  # given = the chain's own
+
+
+@pytest.mark.parametrize("q15", [False, True], ids=["f32", "q15"])
+@pytest.mark.parametrize("layout", ["channel", "time"])
+def test_guard_and_shape_checks_fail_when_they_should(layout, q15):
+    assert (SENT_F32, SENT_Q15, GUARD) == (np.float32(-7777.25), np.int16(0x5A5A), 512) and SENT_Q15.dtype == np.int16
+    I, Q = streams(GroupStub.n_streams, 2 * GroupStub.frame_len, 8, q15)
+    one_call(GroupStub(layout), I, Q, host=True, guard=True)  # (the stub without a fault passes)
+    with pytest.raises(AssertionError, match="behind"):
+        one_call(GroupStub(layout, "behind"), I, Q, host=True, guard=True)
+    with pytest.raises(AssertionError):
+        one_call(GroupStub(layout, "copy"), I, Q, host=True, guard=True)  # equal values in another object
+    with pytest.raises(AssertionError):
+        one_call(GroupStub(layout, "shape"), I, Q, host=True)
+    one_call(GroupStub(layout, "copy"), I, Q, host=True)  # (without out= any object of the right shape is the result)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.int16], ids=["f32", "q15"])
+def test_check_rows_fails_when_it_should(dtype):
+    ref = np.random.default_rng(9).integers(1, 1000, (GroupStub.n_channels, 6)).astype(dtype)  # per channel, no sample zero
+    omap, nrows = np.array(GroupStub.ROW_OF, np.int32), GroupStub.audio_rows
+    got = np.full((nrows, 6), sentinel_of(ref), dtype)
+    got[omap[omap >= 0]] = ref[omap >= 0]
+    G.check_rows(got, ref, omap, nrows)
+    bad = got.copy()
+    bad[[0, 3]] = bad[[3, 0]]  # two listened rows swapped
+    with pytest.raises(AssertionError, match="channel 0, row 3"):
+        G.check_rows(bad, ref, omap, nrows)
+    bad = got.copy()
+    bad[GroupStub.UNUSED, 5] = 0  # one sample of the row nobody names
+    with pytest.raises(AssertionError, match="row 1 has no channel"):
+        G.check_rows(bad, ref, omap, nrows)
+    zero, bad = ref.copy(), got.copy()
+    zero[2] = bad[omap[2]] = 0  # equal, and nothing was compared
+    with pytest.raises(AssertionError):
+        G.check_rows(bad, zero, omap, nrows)
+    with pytest.raises(AssertionError):
+        G.check_rows(got.astype(np.float64), ref, omap, nrows)
+    with pytest.raises(AssertionError):
+        G.check_rows(got[:3], ref, omap, nrows)
+    with pytest.raises(AssertionError):
+        G.check_rows(got, ref, omap, nrows + 1)
+
+
+def test_rows_equal_fails_for_the_channels_own_set_only():
+    setof = np.array([2, 0, 1, 0, 2], np.int32)
+    got = np.random.default_rng(10).standard_normal((5, 6)).astype(np.float32)
+    got[2, 1] = np.array([0x7FC00001], np.uint32).view(np.float32)[0]  # a NaN word, as a state record may hold
+    refs = [got.copy() for _ in range(3)]
+    G.rows_equal(got, refs, setof, "rows")
+    refs[1][0] += 1  # channel 0 runs set 2: what set 1's context holds for it does not count
+    G.rows_equal(got, refs, setof, "rows")
+    refs[1][2, 5] += 1  # channel 2 runs set 1
+    with pytest.raises(AssertionError, match="rows differs for the channels of set 1"):
+        G.rows_equal(got, refs, setof, "rows")
+
+
+def test_expected_state_moves_the_interpolator_memories_of_muted_channels_only():
+    chain = SimpleNamespace(state_records=lambda blob: blob.reshape(GroupStub.n_channels, 190))  # a view, like RxChain's
+    rng = np.random.default_rng(11)
+    ref, before = rng.standard_normal((2, GroupStub.n_channels * 190)).astype(np.float32)
+    kept = ref.copy()
+    omap = np.array(GroupStub.ROW_OF)
+    want = G.expected_state(chain, ref, before, omap).reshape(-1, 190)
+    assert np.array_equal(ref, kept)  # a copy: the reference's checkpoint stays
+    r, b = ref.reshape(-1, 190), before.reshape(-1, 190)
+    moved = np.zeros(190, bool)
+    moved[INT1] = moved[INT2] = True
+    assert moved.sum() == 32 and (INT1.start, INT2.stop) == (152, 184)
+    assert np.array_equal(want[omap >= 0], r[omap >= 0])
+    assert np.array_equal(want[omap < 0][:, moved], b[omap < 0][:, moved]) and np.array_equal(want[omap < 0][:, ~moved], r[omap < 0][:, ~moved])
+    assert not np.array_equal(want[omap < 0], r[omap < 0])
+
+
+def test_bits_and_same():
+    nan = np.array([0x7FC00001, 0x3F800000, 0xFFC00000], np.uint32).view(np.float32)
+    assert not np.array_equal(nan, nan.copy()) and same(nan, nan.copy()) and bits(nan).dtype == np.uint32
+    assert not same(nan, np.array([0x7FC00002, 0x3F800000, 0xFFC00000], np.uint32).view(np.float32))  # another NaN word
+    x = np.arange(12, dtype=np.float32)
+    assert same(x, x.copy()) and not same(x, x.reshape(3, 4)) and not same(x[:6], x)
+    assert same(x.reshape(3, 4)[:, ::2], x.reshape(3, 4)[:, ::2].copy())  # not contiguous on the way in
+    q = np.arange(6, dtype=np.int16)
+    assert bits(q).dtype == np.int16 and same(q, q.copy()) and not same(q, q[::-1])
 
 
 def test_interp_is_the_oracles_two_interpolators(built):

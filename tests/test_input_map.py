@@ -5,53 +5,23 @@ bytes must be equal (np.array_equal, no tolerance).  19 channels (ragged against
 3 streams, a map with repeats in a non-monotone order, distinct random samples per stream.
 """
 import ctypes as C
+from functools import partial
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
 import siggen
-from rx_harness import TOL, T, one_call, to_q15  # noqa: F401  (TOL: the bound test_parity_vs_oracle applies; T: a fixture)
+from group_harness import L, NCH, NS, USB, chain, cw_receive, ft8_receive, ft8_results, run, side_outputs
+from group_harness import STREAM_OF as MAP
+from rx_harness import ERR_ARG, ERR_UNSUPPORTED, TOL, T, streams  # noqa: F401  (TOL: the bound test_parity_vs_oracle applies; T: a fixture)
 
 pytestmark = pytest.mark.gpu
 
-L = 2048
-NCH, NS = 19, 3
-MAP = np.array([2, 0, 0, 1, 2, 1, 1, 0, 2, 2, 0, 1, 0, 0, 2, 1, 2, 0, 1], np.int32)
-ERR_ARG = -1
-assert MAP.shape == (NCH,) and set(MAP) == set(range(NS))
 
-
-def streams(ns, nsamp, seed, q15=False):
-    """distinct random samples per stream [ns, nsamp]: a wrong row cannot pass"""
-    rng = np.random.default_rng(seed)
-    I = (0.2 * rng.standard_normal((ns, nsamp))).astype(np.float32)
-    Q = (0.2 * rng.standard_normal((ns, nsamp))).astype(np.float32)
-    if q15:
-        I, Q = to_q15(I), to_q15(Q)
-    return I, Q
-
-
-def run(rx, I, Q, host=False):
-    """one call on channel-major numpy rows [rows, nfr * Lf] in the context's layout and the arrays' sample format;
-    returns the audio as channel-major numpy [n_channels, nfr * Lf]"""
-    return one_call(rx, I, Q, layout=rx.layout, host=host)[0]
-
-
-def pair(T, kw, nco=None, smap=MAP, ns=None, layout="channel", setup=None):
+def pair(T, kw, smap=MAP, ns=None, layout="channel", setup=None):
     """(mapped context, reference context without a map), configured alike"""
-    nch = len(smap)
-    nco = siggen.nco_grid(nch, seed=11) if nco is None else nco
-    out = []
-    for mapped in (True, False):
-        rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-        if layout != "channel":
-            rx.set_buffer_layout(layout)
-        keep = setup(rx) if setup else None
-        if mapped:
-            rx.set_input_map(smap, ns)
-        out.append((rx, keep))
-    return out[0], out[1]
+    return tuple(chain(T, kw, nch=len(smap), layout=layout, setup=setup, imap=m, ns=ns) for m in (smap, None))
 
 
 def check_equal(T, kw, nfr, layout="channel", q15=False, smap=MAP, ns=NS, seed=5, setup=None, calls=None):
@@ -77,7 +47,6 @@ def check_equal(T, kw, nfr, layout="channel", q15=False, smap=MAP, ns=NS, seed=5
 
 
 # ---- 1. modes and shapes ------------------------------------------------------------------------------------------------
-USB = dict(mode=0, FLoCut=200, FHiCut=3000)
 MODES = [
     ("usb-channel", USB, 5, "channel", False),
     ("usb-time", USB, 5, "time", False),      # input and output frame strides differ
@@ -134,10 +103,7 @@ def test_split_calls_equal_one_call(T, kw):
     b, _ = check_equal(T, kw, 5, calls=[2, 3])
     assert np.array_equal(a.get_state(), b.get_state())
     I, Q = streams(NS, 5 * L, 5)
-    one = T.RxChain(NCH, T.default_params(**kw), NCOFreq=siggen.nco_grid(NCH, seed=11))
-    two = T.RxChain(NCH, T.default_params(**kw), NCOFreq=siggen.nco_grid(NCH, seed=11))
-    one.set_input_map(MAP)
-    two.set_input_map(MAP)
+    (one, _), (two, _) = chain(T, kw, imap=MAP), chain(T, kw, imap=MAP)
     whole = run(one, I, Q)
     parts = np.concatenate([run(two, I[:, :2 * L], Q[:, :2 * L]), run(two, I[:, 2 * L:], Q[:, 2 * L:])], axis=1)
     assert np.array_equal(whole, parts)
@@ -196,19 +162,8 @@ def test_checkpoint_with_a_map_restores_without_one(T):
 # ---- 4. paths behind the split ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("q15", [False, True], ids=["f32", "q15"])
 def test_side_outputs_and_taps(T, q15):
-    import torch
     nfr = 5
-
-    def setup(rx):
-        z = lambda *s: torch.zeros(*s, device="cuda")  # noqa: E731
-        spect, mx, spec, old = z(NCH, nfr, 1024), z(NCH, nfr, 3), z(NCH, nfr, 512), z(NCH, nfr, 512)
-        nco_t, dec, dem = z(NCH, nfr * 2 * L), z(NCH, nfr * 512), z(NCH, nfr * 256)
-        rx.set_audio_spectrum(spect, mx)
-        rx.set_display_spectrum(spec, old, spectrumZoom=2)
-        rx.set_debug_taps(post_nco=nco_t, dec=dec, demod=dem)
-        return spect, mx, spec, old, nco_t, dec, dem
-
-    check_equal(T, dict(AGCMode=1, **USB), nfr, q15=q15, setup=setup)
+    check_equal(T, dict(AGCMode=1, **USB), nfr, q15=q15, setup=partial(side_outputs, nfr=nfr))
 
 
 def test_side_outputs_are_written(T):
@@ -234,31 +189,20 @@ def test_stages_behind_the_demodulator(T, name, kw, nb, q15):
 
 
 def test_cw_detector_and_decoder(T):
-    import cw_decode_model as DM
-    import cw_model as CWM
     nfr = 6
-
-    def setup(rx):
-        rx.set_cw_tables(*CWM.tables())
-        rx.set_cw_decode_tree(DM.tree())
-        return rx.set_cw_detector(1, nfr), rx.set_cw_decoder(1, nfr)
-
-    check_equal(T, dict(xmtMode=1, **USB), nfr, setup=setup)
+    check_equal(T, dict(xmtMode=1, **USB), nfr, setup=partial(cw_receive, nfr=nfr))
 
 
 def test_ft8_receive(T):
     nfr = 16
     (a, _), (b, _) = pair(T, USB)
     for rx in (a, b):
-        rx.set_ft8_tables()
-        rx.set_ft8(1, nfr)
-        rx.ft8_sync()
+        ft8_receive(rx, nfr)
     I, Q = streams(NS, nfr * L, 16)
     assert np.array_equal(run(a, I, Q), run(b, I[MAP], Q[MAP]))
-    sa, sb = a.ft8_status(nfr).cpu().numpy(), b.ft8_status(nfr).cpu().numpy()
+    (sa, pa), (sb, pb) = ft8_results(a, nfr), ft8_results(b, nfr)
     assert np.array_equal(sa, sb) and (sa[:, -1, 0] == 1).all()  # FT_8_counter: the 15 frames' two FFTs ran in the call
-    pa = a.ft8_power().cpu().numpy()
-    assert np.array_equal(pa, b.ft8_power().cpu().numpy()) and pa.reshape(NCH, -1).any(axis=1).all()  # ... and left their rows
+    assert np.array_equal(pa, pb) and pa.reshape(NCH, -1).any(axis=1).all()  # ... and left their rows
     assert np.array_equal(a.ft8_state(), b.ft8_state())
     assert np.array_equal(a.get_state(), b.get_state())
 
@@ -286,7 +230,7 @@ def test_time_major_stays_refused_for_the_long_fft(T):
     rx.set_input_map(MAP)
     with pytest.raises(T.T41RxError) as e:
         rx.set_buffer_layout("time")
-    assert e.value.status == -2  # T41RX_ERR_UNSUPPORTED
+    assert e.value.status == ERR_UNSUPPORTED
     assert np.array_equal(rx.input_map, MAP)
 
 
@@ -313,9 +257,7 @@ def test_mapped_call_against_the_oracle(T):
     # stream s carries the signals of the channels tuned across it
     I = np.stack([Ic[MAP == s].mean(axis=0) for s in range(NS)]).astype(np.float32)
     Q = np.stack([Qc[MAP == s].mean(axis=0) for s in range(NS)]).astype(np.float32)
-    rx = T.RxChain(NCH, T.default_params(), NCOFreq=nco)
-    rx.set_input_map(MAP)
-    got = run(rx, I, Q)
+    got = run(chain(T, {}, nco, imap=MAP)[0], I, Q)
     ref = O.OracleBatch(O.default_params(), nco).process(I[MAP], Q[MAP])
     err = siggen.block_rel_err(got, ref, L)
     assert np.isfinite(got).all()

@@ -8,21 +8,20 @@ others, muted and listened channels sharing workgroups.  5 frames take the pipel
 forms.  The audio buffer is prefilled with a sentinel, and has a guard behind its n_rows rows.
 """
 import ctypes as C
-import os
+from functools import partial
 
 import numpy as np
 import pytest
 
+import group_harness as G
 import oracle_lib as O
 import siggen
-from rx_harness import ROOT, TOL, T, from_time_major, pack, to_q15  # noqa: F401  (TOL: the bound test_parity_vs_oracle applies; T: a fixture)
+from group_harness import D, L, NCH, NS, USB, check_rows, cw_receive, expected_state, ft8_receive, ft8_results, side_outputs
+from group_harness import STREAM_OF as IMAP  # the input map of the cases that name one
+from rx_harness import ERR_ARG, ERR_UNSUPPORTED, INT1, INT2, SENT_F32, TOL, T, first, pack, streams  # noqa: F401  (TOL: the bound test_parity_vs_oracle applies; T: a fixture)
 
 pytestmark = pytest.mark.gpu
 
-L, D = 2048, 256
-NCH, NS = 19, 3
-INT1, INT2 = slice(152, 176), slice(176, 184)  # kStInt1, kStInt2 in a channel's record (rx_internal.hpp)
-ERR_ARG, ERR_UNSUPPORTED = -1, -2
 # the standard map: 10 of 19 muted, the other 9 permuted over 10 rows, row 4 unused; channel 18 (the ragged end) listened
 OMAP = np.array([-1, 7, -1, 0, 9, -1, -1, 2, -1, 5, -1, 1, -1, -1, 8, -1, 3, -1, 6], np.int32)
 NROWS = 10
@@ -30,94 +29,15 @@ UNUSED = 4
 LISTENED = np.flatnonzero(OMAP >= 0)
 MUTED = np.flatnonzero(OMAP < 0)
 assert OMAP.shape == (NCH,) and len(LISTENED) == NROWS - 1 and UNUSED not in OMAP and len(set(OMAP[LISTENED])) == len(LISTENED)
-IMAP = np.array([2, 0, 0, 1, 2, 1, 1, 0, 2, 2, 0, 1, 0, 0, 2, 1, 2, 0, 1], np.int32)  # the input map of the cases that name one
 SETOF = np.array([1, 0, 0, 1, 1, 0, 1, 0, 0, 1, 1, 0, 0, 1, 0, 1, 1, 0, 1], np.int32)
 SETS = [dict(mode=0, FLoCut=300, FHiCut=1000, audioVolume=45)]  # two pass bands and volumes: set 0 is USB 200..3000 at 30 (45: some hundred q15 steps on the tests' noise; at 18 a q15 row is all zero)
-SENT_F32, SENT_Q15 = np.float32(-7777.25), np.int16(0x5A5A)
-GUARD = 2 * D  # samples behind the n_rows rows that must keep the sentinel
 
 
-def streams(rows, nsamp, seed, q15=False):
-    """distinct random samples per row [rows, nsamp]: a wrong row cannot pass"""
-    rng = np.random.default_rng(seed)
-    I = (0.2 * rng.standard_normal((rows, nsamp))).astype(np.float32)
-    Q = (0.2 * rng.standard_normal((rows, nsamp))).astype(np.float32)
-    if q15:
-        I, Q = to_q15(I), to_q15(Q)
-    return I, Q
+run = partial(G.run, guard=True)  # every call into a sentinel-filled buffer of audio_rows rows with a guard behind it
 
 
-def run(rx, I, Q, host=False):
-    """one call on channel-major numpy rows [input rows, nfr * L] in the context's layout and the arrays' sample format, into
-    a sentinel-filled buffer of audio_rows rows with a guard behind it; returns the audio as channel-major numpy
-    [audio_rows, nfr * audio_frame_len] after checking that the guard kept the sentinel"""
-    nfr, La, rows = I.shape[1] // L, rx.audio_frame_len, rx.audio_rows
-    args = pack(I, Q, rx.layout, None, L)
-    q15 = args[0].dtype == np.int16
-    entry = rx.ProcessIQData_q15 if q15 else rx.ProcessIQData
-    sent = SENT_Q15 if q15 else SENT_F32
-    shape = (nfr, rows, La) if rx.layout == "time" else (rows, nfr * La)
-    n = rows * nfr * La
-    if host:
-        big = np.full(n + GUARD, sent, sent.dtype)
-        out = big[:n].reshape(shape)
-        assert entry(*args, out=out) is out
-    else:
-        import torch
-        big = torch.full((n + GUARD,), float(sent) if not q15 else int(sent), dtype=torch.int16 if q15 else torch.float32, device="cuda")
-        out = big[:n].view(shape)
-        assert entry(*(torch.from_numpy(v).cuda() for v in args), out=out) is out
-        torch.cuda.synchronize()
-        big = big.cpu().numpy()
-    assert (big[n:] == sent).all(), "the call wrote behind the audio's n_rows rows"
-    o = big[:n].reshape(shape)
-    return from_time_major(o, rows, nfr, La) if rx.layout == "time" else o
-
-
-def first(t, nfr, per):
-    """what a call of nfr frames wrote to a side-output tensor sized for more: [n_channels][nfr * per] from its start"""
-    return t.reshape(-1)[:NCH * nfr * per].reshape(NCH, nfr * per).cpu().numpy()
-
-
-def sentinel_of(a):
-    return SENT_Q15 if a.dtype == np.int16 else SENT_F32
-
-
-def chain(T, kw, nco=None, layout="channel", rate=192000, imap=None, sets=False, setup=None):
-    nco = siggen.nco_grid(NCH, seed=11) if nco is None else nco
-    rx = T.RxChain(NCH, T.default_params(**kw), NCOFreq=nco)
-    if layout != "channel":
-        rx.set_buffer_layout(layout)
-    if rate != 192000:
-        rx.set_audio_rate(rate)
-    keep = setup(rx) if setup else None
-    if imap is not None:
-        rx.set_input_map(imap, NS)
-    if sets:
-        rx.set_param_sets(SETS, SETOF)
-    return rx, keep
-
-
-def check_rows(got, ref, omap, nrows):
-    """listened rows are the reference's rows of their channels; rows nobody names keep the sentinel"""
-    omap = np.asarray(omap)
-    assert got.shape == (nrows, ref.shape[1]) and got.dtype == ref.dtype
-    for c in np.flatnonzero(omap >= 0):
-        assert np.array_equal(got[omap[c]], ref[c]), "channel %d, row %d" % (c, omap[c])
-        assert np.abs(ref[c].astype(np.float64)).max() > 0
-    for r in sorted(set(range(nrows)) - set(omap[omap >= 0].tolist())):
-        assert (got[r] == sentinel_of(got)).all(), "row %d has no channel and was written" % r
-
-
-def expected_state(a, ref_state, before, omap):
-    """the reference's checkpoint with the interpolator memories of the muted channels as `before` (a checkpoint of the
-    mapped context in front of the call) held them"""
-    want = ref_state.copy()
-    rw, rb = a.state_records(want), a.state_records(before)
-    for c in np.flatnonzero(np.asarray(omap) < 0):
-        rw[c, INT1] = rb[c, INT1]
-        rw[c, INT2] = rb[c, INT2]
-    return want
+def chain(T, kw, imap=None, sets=False, **options):
+    return G.chain(T, kw, imap=imap, ns=None if imap is None else NS, sets=SETS if sets else None, setof=SETOF, **options)
 
 
 def check_call(T, kw, nfr, layout="channel", q15=False, rate=192000, imap=None, sets=False, omap=OMAP, nrows=NROWS, setup=None,
@@ -156,7 +76,6 @@ def check_call(T, kw, nfr, layout="channel", q15=False, rate=192000, imap=None, 
 
 
 # ---- 1. modes and shapes, 2. state ---------------------------------------------------------------------------------------
-USB = dict(mode=0, FLoCut=200, FHiCut=3000)
 LSB = dict(mode=1, FLoCut=-3000, FHiCut=-200)
 AM = dict(mode=2, FLoCut=-4000, FHiCut=4000)
 SAM = dict(mode=8, FLoCut=-4000, FHiCut=4000)
@@ -222,7 +141,7 @@ def test_nobody_listens(T, kw):
         return tap
 
     mute = np.full(NCH, -1, np.int32)
-    a, b = check_call(T, kw, nfr, omap=mute, nrows=0, setup=setup, results=lambda rx, tap: [first(tap, nfr, D)])
+    a, b = check_call(T, kw, nfr, omap=mute, nrows=0, setup=setup, results=lambda rx, tap: [first(tap, NCH, nfr, D)])
     # the C entry with no audio pointer at all
     I, Q = streams(NCH, 3 * L, 31)
     dI, dQ = torch.from_numpy(I).cuda(), torch.from_numpy(Q).cuda()
@@ -255,9 +174,7 @@ def test_pure_permutation(T):
 # ---- 4. streaming --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kw", [USB, dict(USB, AGCMode=2)], ids=["usb", "usb-agc"])
 def test_split_calls_equal_one_call(T, kw):
-    (one, _), (two, _) = chain(T, kw), chain(T, kw)
-    one.set_output_map(OMAP, NROWS)
-    two.set_output_map(OMAP, NROWS)
+    (one, _), (two, _) = (chain(T, kw, omap=OMAP, nrows=NROWS) for _ in range(2))
     I, Q = streams(NCH, 5 * L, 41)
     whole = run(one, I, Q)
     parts = np.concatenate([run(two, I[:, :2 * L], Q[:, :2 * L]), run(two, I[:, 2 * L:], Q[:, 2 * L:])], axis=1)
@@ -331,8 +248,7 @@ def test_map_survives_reset_checkpoint_and_set_params(T):
 
 def test_checkpoint_with_a_map_restores_without_one(T):
     kw = dict(USB, AGCMode=1)
-    (a, _), (b, _) = chain(T, kw), chain(T, kw)
-    a.set_output_map(OMAP, NROWS)
+    (a, _), (b, _) = chain(T, kw, omap=OMAP, nrows=NROWS), chain(T, kw)
     I, Q = streams(NCH, 7 * L, 45)
     run(a, I[:, :3 * L], Q[:, :3 * L])
     b.set_state(a.get_state())
@@ -349,22 +265,14 @@ def test_checkpoint_with_a_map_restores_without_one(T):
 def test_side_outputs_and_the_demod_tap(T, q15, rate):
     """audio spectrum, display spectrum and the demod tap: the tap kernels hand over, launch_back512's twin (or the 24 kS/s
     finish) stores"""
-    import torch
     nfr = 5
 
-    def setup(rx):
-        z = lambda *s: torch.zeros(*s, device="cuda")  # noqa: E731
-        spect, mx, spec, old, dem = z(NCH, 7, 1024), z(NCH, 7, 3), z(NCH, 7, 512), z(NCH, 7, 512), z(NCH, 7 * D)
-        rx.set_audio_spectrum(spect, mx)
-        rx.set_display_spectrum(spec, old, spectrumZoom=2)
-        rx.set_debug_taps(demod=dem)
-        return spect, mx, spec, dem
-
     def results(rx, keep):
-        spect, mx, spec, dem = keep
-        return [first(spect, nfr, 1024), first(mx, nfr, 3), first(spec, nfr, 512), first(dem, nfr, D)]
+        spect, mx, spec, _, dem = keep
+        return [first(spect, NCH, nfr, 1024), first(mx, NCH, nfr, 3), first(spec, NCH, nfr, 512), first(dem, NCH, nfr, D)]
 
-    check_call(T, dict(USB, AGCMode=1), nfr, q15=q15, rate=rate, layout="time" if q15 else "channel", setup=setup, results=results)
+    check_call(T, dict(USB, AGCMode=1), nfr, q15=q15, rate=rate, layout="time" if q15 else "channel",
+               setup=partial(side_outputs, nfr=2 + nfr, taps=("demod",)), results=results)  # (room for the 2 warm-up frames too)
 
 
 @pytest.mark.parametrize("q15", [False, True], ids=["f32", "q15"])
@@ -377,18 +285,15 @@ def test_parameter_sets_behind_the_hand_over(T, side, q15):
 
     def setup(rx):
         if side == "ft8":
-            rx.set_ft8_tables()
-            rx.set_ft8(1, nfr)
-            rx.ft8_sync()
-            return None
+            return ft8_receive(rx, nfr)
         spect, mx = torch.zeros(NCH, 7, 1024, device="cuda"), torch.zeros(NCH, 7, 3, device="cuda")
         rx.set_audio_spectrum(spect, mx)
         return spect, mx
 
     def results(rx, keep):
         if side == "ft8":
-            return [rx.ft8_status(nfr).cpu().numpy(), rx.ft8_power().cpu().numpy()]
-        return [first(keep[0], nfr, 1024), first(keep[1], nfr, 3)]
+            return ft8_results(rx, nfr)
+        return [first(keep[0], NCH, nfr, 1024), first(keep[1], NCH, nfr, 3)]
 
     a, b = check_call(T, USB, nfr, warm=0 if side == "ft8" else 2, q15=q15, layout="time" if q15 else "channel", sets=True,
                       setup=setup, results=results)
@@ -421,15 +326,8 @@ def test_noise_reduction_and_blanker(T, name, kw, nb):
 def test_cw_filter_detector_and_decoder(T, rate, index):
     """the narrow filter runs for every channel; cw_back_kernel's twin (192 kS/s) or the finish (24 kS/s) stores the listened
     rows; with CWFilterIndex 5 the detector alone splits the chain and launch_back512's twin stores"""
-    import cw_decode_model as DM
-    import cw_model as CWM
     nfr = 6
-
-    def setup(rx):
-        rx.set_cw_tables(*CWM.tables())
-        rx.set_cw_decode_tree(DM.tree())
-        rx.set_cw_filter(index)
-        return rx.set_cw_detector(1, nfr), rx.set_cw_decoder(1, nfr)
+    setup = partial(cw_receive, nfr=nfr, index=index)
 
     def results(rx, keep):
         return [keep[0].cpu().numpy(), rx.cw_text(nfr).cpu().numpy()[:, :, 1:]]  # (the character word is 0 in most frames)
@@ -443,27 +341,20 @@ def test_cw_filter_detector_and_decoder(T, rate, index):
 def test_ft8_receive(T, rate):
     nfr = 16
 
-    def setup(rx):
-        rx.set_ft8_tables()
-        rx.set_ft8(1, nfr)
-        rx.ft8_sync()
-
     def results(rx, keep):
-        st = rx.ft8_status(nfr).cpu().numpy()
+        st, power = ft8_results(rx, nfr)
         assert (st[:, -1, 0] == 1).all()  # FT_8_counter: the 15 frames' two FFTs ran in the call
-        return [st, rx.ft8_power().cpu().numpy()]
+        return [st, power]
 
-    a, b = check_call(T, USB, nfr, warm=0, rate=rate, setup=setup, results=results)
+    a, b = check_call(T, USB, nfr, warm=0, rate=rate, setup=partial(ft8_receive, nfr=nfr), results=results)
     assert np.array_equal(a.ft8_state(), b.ft8_state())
 
 
 def test_panadapter_with_the_beacon_monitor(T):
     nfr = 9
-    grad = np.load(os.path.join(ROOT, "tests", "golden", "display", "gradient.npz"))["gradient"]
 
     def setup(rx):
-        rx.set_panadapter_tables(grad)
-        bufs = rx.set_panadapter(True, spectrumZoom=1, currentScale=1, update_period=3, max_rows=nfr)
+        bufs = G.panadapter(rx, nfr, spectrumZoom=1, currentScale=1, update_period=3)
         rx.set_beacon_clock(0, 32, 3)
         snr, ev = rx.set_beacon(True, 1, (np.arange(NCH) * 3 + 1) % 5)
         return bufs, ev
@@ -484,9 +375,7 @@ def test_panadapter_with_the_beacon_monitor(T):
 @pytest.mark.parametrize("layout", ["channel", "time"])
 def test_host_forms_equal_device_forms(T, layout, q15, nrows):
     omap = OMAP if nrows else np.full(NCH, -1, np.int32)
-    (a, _), (b, _) = chain(T, USB, layout=layout), chain(T, USB, layout=layout)
-    a.set_output_map(omap, nrows)
-    b.set_output_map(omap, nrows)
+    (a, _), (b, _) = (chain(T, USB, layout=layout, omap=omap, nrows=nrows) for _ in range(2))
     I, Q = streams(NCH, 5 * L, 61, q15)
     dev, host = run(a, I, Q), run(b, I, Q, host=True)
     assert host.dtype == (np.int16 if q15 else np.float32) and host.shape == (nrows, 5 * L) and np.array_equal(dev, host)
@@ -505,9 +394,7 @@ def test_mapped_call_against_the_oracle(T):
     nfr = 6
     nco = siggen.nco_grid(NCH, seed=3)
     I, Q = siggen.make_iq(NCH, nfr * L, nco, mode=0, seed=21)
-    rx = T.RxChain(NCH, T.default_params(), NCOFreq=nco)
-    rx.set_output_map(OMAP, NROWS)
-    got = run(rx, I, Q)
+    got = run(chain(T, {}, nco=nco, omap=OMAP, nrows=NROWS)[0], I, Q)
     ref = O.OracleBatch(O.default_params(), nco).process(I, Q)
     assert np.isfinite(got[OMAP[LISTENED]]).all() and (got[UNUSED] == SENT_F32).all()
     err = siggen.block_rel_err(got[OMAP[LISTENED]], ref[LISTENED], L)
@@ -518,9 +405,8 @@ def test_mapped_call_against_the_oracle(T):
 # ---- 8. refusals ---------------------------------------------------------------------------------------------------------
 def test_refusals_leave_the_previous_map(T):
     import torch
-    (a, _), (b, _) = chain(T, USB), chain(T, USB)
+    (a, _), (b, _) = chain(T, USB, omap=OMAP, nrows=NROWS), chain(T, USB)
     lib = a._lib
-    a.set_output_map(OMAP, NROWS)
     I, Q = streams(NCH, 2 * L, 71)
     ip = lambda m: np.ascontiguousarray(m, np.int32).ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
     at = lambda i, v: np.where(np.arange(NCH) == i, v, OMAP)  # noqa: E731

@@ -7,72 +7,31 @@ all zero.  19 channels (ragged against the 16-wave and the 4-wave workgroups, so
 sets in a non-monotone table with repeats, every set used, set 0 used by some channels.
 """
 import ctypes as C
-import os
+from functools import partial
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
 import siggen
-from rx_harness import TOL, T, one_call, refused, to_q15  # noqa: F401  (TOL: the bound test_parity_vs_oracle applies; T: a fixture)
+from group_harness import L, NCH, USB, chain, ft8_receive, ft8_results, panadapter, rows_equal, run, side_outputs
+from group_harness import SET_OF as SETOF, STREAM_OF as MAP
+from rx_harness import ERR_ARG, ERR_UNSUPPORTED, TOL, T, refused, streams  # noqa: F401  (TOL: the bound test_parity_vs_oracle applies; T: a fixture)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-L = 2048
-NCH, NS = 19, 3
-SETOF = np.array([2, 0, 0, 1, 2, 1, 1, 0, 2, 2, 0, 1, 0, 0, 2, 1, 2, 0, 1], np.int32)
-MAP = np.array([2, 0, 0, 1, 2, 1, 1, 0, 2, 2, 0, 1, 0, 0, 2, 1, 2, 0, 1], np.int32)  # the input-map test's
 MAXSETS = 64
-ERR_ARG, ERR_UNSUPPORTED = -1, -2
 assert SETOF.shape == (NCH,) and set(SETOF) == {0, 1, 2}
 
 
-def streams(rows, nsamp, seed, q15=False):
-    """distinct random samples per row [rows, nsamp]"""
-    rng = np.random.default_rng(seed)
-    I = (0.2 * rng.standard_normal((rows, nsamp))).astype(np.float32)
-    Q = (0.2 * rng.standard_normal((rows, nsamp))).astype(np.float32)
-    if q15:
-        I, Q = to_q15(I), to_q15(Q)
-    return I, Q
-
-
-def run(rx, I, Q, host=False):
-    return one_call(rx, I, Q, layout=rx.layout, host=host)[0]
-
-
-def group(T, base, extra, setof=SETOF, layout="channel", setup=None, smap=None, seed=11):
+def group(T, base, extra, setof=SETOF, layout="channel", setup=None, smap=None):
     """(mixed context, its setup's tensors), [(plain context of set k, its tensors) for k = 0..K]: base = set 0 as keywords
     of default_params, extra = the sets 1..K as dicts of changes against it"""
-    nch = len(setof)
-    nco = siggen.nco_grid(nch, seed=seed)
-
-    def make(kw):
-        rx = T.RxChain(nch, T.default_params(**kw), NCOFreq=nco)
-        if layout != "channel":
-            rx.set_buffer_layout(layout)
-        return rx, (setup(rx) if setup else None)
-
-    mixed = make(base)
-    mixed[0].set_param_sets(extra, setof)
+    make = lambda kw, **sets: chain(T, kw, nch=len(setof), layout=layout, setup=setup, **sets)  # noqa: E731
+    mixed = make(base, sets=extra, setof=setof)
     if smap is not None:
-        mixed[0].set_input_map(smap)
+        mixed[0].set_input_map(smap)  # (behind the sets, as ever)
     return mixed, [make(dict(base, **e)) for e in [{}] + list(extra)]
-
-
-def bits(x):
-    """float32 arrays as their words: a state record holds the oscillator's 64-bit phase, whose halves read as floats may
-    be NaNs, and equal NaNs do not compare equal"""
-    x = np.asarray(x)
-    return x.view(np.uint32) if x.dtype == np.float32 else x
-
-
-def rows_equal(got, refs, setof, what):
-    for k, ref in enumerate(refs):
-        sel = np.asarray(setof) == k
-        if sel.any():
-            assert np.array_equal(bits(got)[sel], bits(ref)[sel]), "%s differs for the channels of set %d" % (what, k)
 
 
 def check_sets(T, base, extra, nfr, setof=SETOF, layout="channel", q15=False, setup=None, smap=None, calls=None, seed=5):
@@ -101,7 +60,6 @@ def check_sets(T, base, extra, nfr, setof=SETOF, layout="channel", q15=False, se
     return a, [b for b, _ in refs]
 
 
-USB = dict(mode=0, FLoCut=200, FHiCut=3000)
 SSB3 = [dict(mode=1, FLoCut=-3000, FHiCut=-200), dict(mode=0, FLoCut=300, FHiCut=1000)]  # + LSB + a narrow USB
 
 
@@ -266,29 +224,16 @@ def test_checkpoint_with_sets_restores_without(T):
 # ---- 11. what taps the fused chain --------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("q15", [False, True], ids=["f32", "q15"])
 def test_side_outputs_and_taps(T, q15):
-    import torch
     nfr = 5
-
-    def setup(rx):
-        z = lambda *s: torch.zeros(*s, device="cuda")  # noqa: E731
-        spect, mx, spec, old = z(NCH, nfr, 1024), z(NCH, nfr, 3), z(NCH, nfr, 512), z(NCH, nfr, 512)
-        nco_t, dec, dem = z(NCH, nfr * 2 * L), z(NCH, nfr * 512), z(NCH, nfr * 256)
-        rx.set_audio_spectrum(spect, mx)
-        rx.set_display_spectrum(spec, old, spectrumZoom=2)
-        rx.set_debug_taps(post_nco=nco_t, dec=dec, demod=dem)
-        return spect, mx, spec, old, nco_t, dec, dem
-
-    a, _ = check_sets(T, dict(AGCMode=1, **USB), AGC3, nfr, q15=q15, setup=setup)
+    a, _ = check_sets(T, dict(AGCMode=1, **USB), AGC3, nfr, q15=q15, setup=partial(side_outputs, nfr=nfr))
     assert all(float(t.abs().amax(dim=tuple(range(1, t.dim()))).min()) > 0 for t in (a._spect[0], a._taps[2]))  # written, every channel
 
 
 def test_panadapter_rows(T):
     nfr = 3
-    g = np.load(os.path.join(ROOT, "tests", "golden", "display", "gradient.npz"))["gradient"]
 
     def setup(rx):
-        rx.set_panadapter_tables(g)
-        bufs = rx.set_panadapter(True, spectrumZoom=1, currentScale=1, update_period=1, max_rows=nfr)
+        bufs = panadapter(rx, nfr, spectrumZoom=1, currentScale=1, update_period=1)
         return tuple(bufs[name] for name, _, _ in rx.PANADAPTER_ROWS)
 
     check_sets(T, USB, SSB3, nfr, setup=setup)
@@ -298,12 +243,10 @@ def test_beacon_monitor_behind_the_panadapter(T):
     """the monitor reads the dBm of the panadapter's rows: a fast clock (a slot per frame) so that beacons change inside
     the call, three calls; the SNR table, the events and the monitor's record per set"""
     nfr = 4
-    g = np.load(os.path.join(ROOT, "tests", "golden", "display", "gradient.npz"))["gradient"]
     kept = []
 
     def setup(rx):
-        rx.set_panadapter_tables(g)
-        sm = rx.set_panadapter(True, update_period=1, max_rows=nfr, outputs=["smeter"])["smeter"]
+        sm = panadapter(rx, nfr, update_period=1, outputs=["smeter"])["smeter"]
         rx.set_panadapter_levels(gain_correction=np.linspace(-6.0, 6.0, NCH).astype(np.float32))
         rx.set_beacon_clock(0, 10000, 1)
         snr, ev = rx.set_beacon(True, 1, (np.arange(NCH) * 3 + 1) % 5)
@@ -322,16 +265,13 @@ def test_ft8_receive_on_a_mixed_usb_context(T):
     (a, _), refs = group(T, USB, extra)
     chains = [a] + [b for b, _ in refs]
     for rx in chains:
-        rx.set_ft8_tables()
-        rx.set_ft8(1, nfr)
-        rx.ft8_sync()
+        ft8_receive(rx, nfr)
     I, Q = streams(NCH, nfr * L, 16)
     outs = [run(rx, I, Q) for rx in chains]
     rows_equal(outs[0], outs[1:], SETOF, "audio")
-    st = [rx.ft8_status(nfr).cpu().numpy() for rx in chains]
+    st, pw = zip(*(ft8_results(rx, nfr) for rx in chains))
     rows_equal(st[0], st[1:], SETOF, "FT8 status")
     assert (st[0][:, -1, 0] == 1).all()
-    pw = [rx.ft8_power().cpu().numpy() for rx in chains]
     rows_equal(pw[0], pw[1:], SETOF, "FT8 power")
     assert pw[0].reshape(NCH, -1).any(axis=1).all()
     # an LSB set cannot run under FT8 receive: the call is refused, nothing is processed
@@ -362,9 +302,7 @@ def test_mixed_context_against_the_oracle(T):
     for k, kw in enumerate(kws):  # every channel gets a signal inside its own set's pass band
         Ik, Qk = siggen.make_iq(NCH, nfr * L, nco, mode=kw["mode"], seed=21, audio_hz=(400.0, 900.0))
         I[SETOF == k], Q[SETOF == k] = Ik[SETOF == k], Qk[SETOF == k]
-    rx = T.RxChain(NCH, T.default_params(**USB), NCOFreq=nco)
-    rx.set_param_sets(SSB3, SETOF)
-    got = run(rx, I, Q)
+    got = run(chain(T, USB, nco, sets=SSB3, setof=SETOF)[0], I, Q)
     assert np.isfinite(got).all()
     for k, kw in enumerate(kws):
         ref = O.OracleBatch(O.default_params(**kw), nco).process(I, Q)
