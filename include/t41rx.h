@@ -412,6 +412,49 @@ T41RX_API int t41rx_set_output_map(t41rx_ctx *ctx, const int32_t *row_of_channel
 T41RX_API int t41rx_get_output_map(const t41rx_ctx *ctx, int32_t *row_of_channel_out, int n, int *n_rows_out);
 T41RX_API int t41rx_audio_rows(const t41rx_ctx *ctx);
 
+/* ---- receiver groups: a stage map, the stages behind the demodulator only on the channels that ask (ABI 5) ----
+ * The fourth map of the series.  The stages between the demodulator and the interpolators are switches of the whole
+ * context (t41rx_set_receive_eq, nrOptionSelect / ANR_notchOn, t41rx_set_noise_blanker, t41rx_set_cw_detector,
+ * t41rx_set_cw_decoder) and the expensive part of a call; a skimmer wants the notch and the equalizer on the two
+ * channels somebody hears and the Morse decoder on the slices that show a carrier.  With a stage map set, every channel
+ * carries a mask of T41RX_STAGE_* bits.
+ * The rule: stage S runs on channel c in a call exactly when the context's switch for S is on, as the setters and
+ * parameters above say, and bit S of stages_of_channel[c] is set.  A channel whose bit is clear is processed as the same
+ * channel of a context in which S is switched off: the stage neither reads nor writes the channel's audio, S's memory for
+ * the channel stays exactly as it was (the firmware's stale statics when a flag goes off and on again, and the rule the
+ * output map applies to a muted channel's interpolators), and the channel's rows of the detector's and the decoder's
+ * result buffers are not written.  A bit for a stage that is off in the context is allowed and has no effect until the
+ * stage is switched on.  T41RX_STAGE_NR covers nrOptionSelect and the notch together: both take the same channels.
+ * What the map does not reach: which kernels a call runs stays a function of the context's switches (a call with a stage
+ * on hands over to the stage scratch even if that stage lists no channel); the narrow CW filter (t41rx_set_cw_filter)
+ * stays a switch of the context -- it selects the call's back kernel, whose operation order differs from the other's, so
+ * a filter per channel would need two back ends per call --; FT8 receive, the panadapter, the beacon monitor, the side
+ * outputs and the stage taps stay context-wide; parameter sets and the chain-splitting stages go on refusing each other.
+ * The map composes with the input map, the output map, both audio rates, both layouts, f32 and q15, and the host and
+ * device entries: none of them sees it.
+ * The map is configuration, like the output map: it is in no checkpoint, survives t41rx_reset, t41rx_set_state,
+ * t41rx_set_params and t41rx_set_coeffs, and may change between any two calls.  t41rx_state_bytes(), every checkpoint
+ * section and t41rx_reset() are what they are without a map and carry all channels.  fft_length 512 only: at a long
+ * fft_length t41rx_set_stage_map() answers T41RX_ERR_UNSUPPORTED, as the stages themselves refuse there.
+ * t41rx_set_stage_map(): stages_of_channel is a host array of n == n_channels masks.  NULL with n == 0 removes the map:
+ *   every stage on every channel again, and the launches of a context that never had one.  Everything is checked on the
+ *   host before anything changes: n != n_channels, a bit outside T41RX_STAGE_ALL, or a channel with
+ *   T41RX_STAGE_CW_DECODE and without T41RX_STAGE_CW_DETECT (the decoder reads the detector's rows of its own channel)
+ *   return T41RX_ERR_ARG with a t41rx_last_error() text that names the entry and leave the previous map as it was.
+ *   Synchronises the device, then uploads (the ordering rule of t41rx_set_input_map): the map holds from the next
+ *   process call on.  A caller who wants every stage on every channel sets no map: the identity map runs the list forms
+ *   of the stage kernels over all channels and buys nothing.
+ * t41rx_get_stage_map(): returns 1 with a map set, 0 with none (negative: an error status).  stages_of_channel_out,
+ *   n == n_channels entries, receives the map, or T41RX_STAGE_ALL in every entry with none; it may be NULL. */
+#define T41RX_STAGE_EQ        1u   /* DoReceiveEQ(),               Process.cpp:828-832 */
+#define T41RX_STAGE_NR        2u   /* nrOptionSelect and the notch, Process.cpp:841-866 */
+#define T41RX_STAGE_NB        4u   /* NoiseBlanker(),              Process.cpp:873-876 */
+#define T41RX_STAGE_CW_DETECT 8u   /* DoCWReceiveProcessing(),     Process.cpp:878-879 */
+#define T41RX_STAGE_CW_DECODE 16u  /* DoCWDecoding() behind it */
+#define T41RX_STAGE_ALL       31u
+T41RX_API int t41rx_set_stage_map(t41rx_ctx *ctx, const uint32_t *stages_of_channel, int n);  /* NULL, 0: remove */
+T41RX_API int t41rx_get_stage_map(const t41rx_ctx *ctx, uint32_t *stages_of_channel_out, int n);
+
 /* ---- receiver groups: parameter sets, one t41rx_params per group of channels (ABI 5) ----
  * The receivers of one band differ in more than NCOFreq: the phone receivers are LSB at 2.8 kHz, the FT8 receiver is USB
  * at 200..3000 Hz, the CW receivers want a few hundred hertz.  A context's own t41rx_params (t41rx_create,

@@ -6,7 +6,7 @@ import numpy as np
 
 from ._lib import check
 
-F32P, I32P, U16P = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint16)
+F32P, I32P, U16P, U32P = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint16), C.POINTER(C.c_uint32)
 
 
 def value(v):

@@ -19,6 +19,9 @@ ERR_ARG, ERR_UNSUPPORTED, ERR_HIP, ERR_NOMEM, ERR_STATE = -1, -2, -3, -4, -5
 DEMOD_USB, DEMOD_LSB, DEMOD_AM, DEMOD_NFM = 0, 1, 2, 3
 DEMOD_SAM = 8  # synchronous AM (SDT.h:67), fft_length 512
 SSB_MODE, CW_MODE, DATA_MODE = 0, 1, 2
+# the bits of a channel's mask in the stage map (T41RX_STAGE_*, t41rx_set_stage_map)
+STAGE_EQ, STAGE_NR, STAGE_NB, STAGE_CW_DETECT, STAGE_CW_DECODE = 1, 2, 4, 8, 16
+STAGE_ALL = 31
 
 
 class Params(C.Structure):
@@ -96,6 +99,8 @@ SYMBOLS = {
     "t41rx_set_output_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int, C.c_int]),
     "t41rx_get_output_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]),
     "t41rx_audio_rows": (C.c_int, [_vp]),
+    "t41rx_set_stage_map": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.c_int]),
+    "t41rx_get_stage_map": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.c_int]),
     "t41rx_set_param_sets": (C.c_int, [_vp, C.POINTER(Params), C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "t41rx_get_param_sets": (C.c_int, [_vp, C.POINTER(Params), C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "t41rx_param_sets_compatible": (C.c_int, [C.POINTER(Params), C.POINTER(Params)]),

@@ -42,6 +42,10 @@ struct CwDetectArgs {
   float coeff, cosine, sine;  // goertzel_mag(256, 750, 24000, .)'s constants in the firmware's types (host)
   float fir[kCwFirTaps];      // CW_Filter_Coeffs2
   float sinb[kCwBlock];       // sinBuffer (Utility.cpp:72-74)
+  // the stage map (t41rx_set_stage_map), or null: the nlist > 0 channels the detector runs on, ascending; the others'
+  // rows of `out` are not written
+  const int *list;
+  int nlist;
 };
 hipError_t launch_cw_detect(const CwDetectArgs &a, hipStream_t s);
 
@@ -116,6 +120,10 @@ struct CwDecodeArgs {
   int nchan, nframes;
   int32_t t0, num, den;               // the clock (t41rx_set_cw_clock)
   uint8_t tree[kCwTreeChars + 3];     // bigMorseCodeTree (the caller's)
+  // the stage map (t41rx_set_stage_map), or null: the nlist > 0 channels the decoder runs on, ascending -- a subset of the
+  // detector's list, whose rows of `cw` it reads; the others' rows of `text` are not written
+  const int *list;
+  int nlist;
 };
 hipError_t launch_cw_decode(const CwDecodeArgs &a, hipStream_t s);
 // ResetHistograms() (CWProcessing.cpp:501-517) on the channels whose mask byte is non-zero (mask: device pointer, or null

@@ -18,6 +18,10 @@ struct EqArgs {
   int nchan, nsamp;  // nsamp = n_frames * 256 (a multiple of 64)
   float coef[kEqCoefs];   // [band][stage][5]
   float scale[16];        // per band: -recEQ_LevelScale for bands 1, 3, .., 13, +recEQ_LevelScale for 2, 4, .., 14
+  // the stage map (t41rx_set_stage_map), or null: the nlist > 0 channels the stage runs on, ascending; the others' audio
+  // and memories are neither read nor written
+  const int *list;
+  int nlist;
 };
 hipError_t launch_eq(const EqArgs &a, hipStream_t s);
 

@@ -20,6 +20,10 @@ struct NbArgs {
   float *carry;   // [2][nchan][kNbCarryPitch]: last_frame_end, ping-pong
   int nchan, nframes;
   int sel;        // carry slot frame 0 reads; the last frame writes slot sel ^ 1
+  // the stage map (t41rx_set_stage_map), or null: the nlist > 0 channels the blanker runs on, ascending, and the nrest =
+  // nchan - nlist it leaves out, whose carry the launch copies from slot sel to slot sel ^ 1
+  const int *list, *rest;
+  int nlist, nrest;
 };
 hipError_t launch_nb(const NbArgs &a, hipStream_t s);
 

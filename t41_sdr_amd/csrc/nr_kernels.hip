@@ -215,98 +215,20 @@ __device__ __forceinline__ void anr_pass_sigma(const float *T, float *SIG, int l
   }
 }
 
-__global__ __launch_bounds__(128, 2) void anr_kernel(const NrArgs a) {
-  // (The copy / scale loops below are kept rolled: fully unrolled, with every address hoisted out of the frame loop, they
-  // took the kernel to 353 VGPRs; 161 now.  Measured at the end of round 4, all bit-identical to this form
-  // (tools/anr_ab_check.py) and none faster than 1 %: no workgroup barrier per sample -- sigma through two slots guarded
-  // by LDS counters, wave 1 up to two samples ahead --, the next sample's window and this sample's sigma requested a
-  // chain ahead of their use, both outcomes of the leak logic formed off the path and selected, the window read through
-  // one lane-dependent base with immediate offsets (8 ds_read2_b32 instead of 16 address computations and 16 reads), the
-  // first sample's "no pending update" as a compile-time case (16 selects per sample fewer): 187 -> 165 instructions per
-  // sample, 138 us per frame either way.  Timing experiments: 16 instead of 64 additions per chain -25 us (4.5 cycles
-  // per addition), no leak decision -5, no sigma wave -6.  A sample is ONE dependent sequence -- update, product, 64
-  // additions, 5 lane swaps, error, two double-precision expressions, select, update -- on one wave; what it costs is that
-  // sequence's latency, ~1000 cycles, and neither the instruction count nor the synchronisation.)
-#pragma clang fp contract(off)
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  float *T = sm, *O = sm + kAnrTile * kAnrRow, *SIG = sm + kAnrSigOff;  // (16-byte aligned)
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // 0: filter output and update, 1: sum of squares
-  const int c = lane & 15, g = lane >> 4, tb = anr_tap_base(g);
-  const int ch0 = blockIdx.x * kAnrCw;
-  const int nlive = (a.nchan - ch0 < kAnrCw) ? a.nchan - ch0 : kAnrCw;
-  const int ch = ch0 + (c < nlive ? c : nlive - 1);  // dead lanes shadow the last live channel (their stores are skipped)
-  const size_t nch = (size_t)a.nchan;
-  f2 w[8];  // ANR_w (wave 0): this lane's 16 taps, two per register pair: (.x, .y) = taps (tb + 2 t + 1, tb + 2 t)
-  float lidx = 0, ngamma = 0;
-  if (wv == 0) {
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-      w[t] = f2{a.anr[(size_t)(kAnrStW + tb + 2 * t + 1) * nch + ch], a.anr[(size_t)(kAnrStW + tb + 2 * t) * nch + ch]};
-    _Pragma("unroll 4") for (int r = g; r < kAnrHist; r += 4) T[r * kAnrRow + c] = a.anr[(size_t)(kAnrStHist + r) * nch + ch];
-    lidx = a.anr[(size_t)kAnrStLidx * nch + ch], ngamma = a.anr[(size_t)kAnrStNgamma * nch + ch];
-  }
-  for (int f = 0; f < a.nframes; ++f) {
-    // stage the frame in: column cc of the tile = channel ch0 + cc, 256 consecutive samples, 4 x 256 B per channel (the
-    // two waves take alternate channels)
-    __syncthreads();
-_Pragma("nounroll")
-    for (int cc = wv; cc < nlive; cc += 2) {
-      const float *src = a.aud + ((size_t)(ch0 + cc) * a.nframes + f) * 256;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) T[(kAnrHist + lane + 64 * q) * kAnrRow + cc] = src[lane + 64 * q];
-    }
-_Pragma("nounroll")
-    for (int cc = nlive + ((nlive ^ wv) & 1); cc < kAnrCw; cc += 2) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) T[(kAnrHist + lane + 64 * q) * kAnrRow + cc] = 0.0f;
-    }
-    __syncthreads();
-    if (a.nr_option == 3) {  // Process.cpp:852-857: Xanr() as noise reduction; its result stays in float_buffer_R, float_buffer_L is scaled by 1.5
-      if (wv == 0) anr_pass_y<false>(T, nullptr, SIG, w, lidx, ngamma, lane);
-      else anr_pass_sigma(T, SIG, lane);
-      __syncthreads();
-      if (wv == 0) {
-        if (a.notch) {
-          // the notch pass sees the scaled block behind the unscaled one: its delay line = the last 79 unscaled samples
-          _Pragma("unroll 4") for (int r = g; r < kAnrHist; r += 4) T[r * kAnrRow + c] = T[(256 + r) * kAnrRow + c];
-          __builtin_amdgcn_wave_barrier();
-          _Pragma("unroll 4") for (int i = g; i < 256; i += 4) T[(kAnrHist + i) * kAnrRow + c] = T[(kAnrHist + i) * kAnrRow + c] * 1.5f;
-        } else {
-          _Pragma("unroll 4") for (int i = g; i < 256; i += 4) O[i * kAnrRow + c] = T[(kAnrHist + i) * kAnrRow + c] * 1.5f;
-        }
-      }
-      __syncthreads();
-    }
-    if (a.notch) {  // Process.cpp:862-866
-      if (wv == 0) anr_pass_y<true>(T, O, SIG, w, lidx, ngamma, lane);
-      else anr_pass_sigma(T, SIG, lane);
-      __syncthreads();
-    }
-    // the delay line's live part for the next block
-    if (wv == 0)
-      _Pragma("unroll 4") for (int r = g; r < kAnrHist; r += 4) T[r * kAnrRow + c] = T[(256 + r) * kAnrRow + c];
-    __syncthreads();
-_Pragma("nounroll")
-    for (int cc = wv; cc < nlive; cc += 2) {
-      float *dst = a.aud + ((size_t)(ch0 + cc) * a.nframes + f) * 256;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) dst[lane + 64 * q] = O[(lane + 64 * q) * kAnrRow + cc];
-    }
-  }
-  if (wv == 0 && c < nlive) {
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-      a.anr[(size_t)(kAnrStW + tb + 2 * t + 1) * nch + ch] = w[t].x;
-      a.anr[(size_t)(kAnrStW + tb + 2 * t) * nch + ch] = w[t].y;
-    }
-    _Pragma("unroll 4") for (int r = g; r < kAnrHist; r += 4) a.anr[(size_t)(kAnrStHist + r) * nch + ch] = T[r * kAnrRow + c];
-    if (g == 0) {
-      a.anr[(size_t)kAnrStLidx * nch + ch] = lidx;
-      a.anr[(size_t)kAnrStNgamma * nch + ch] = ngamma;
-    }
-  }
-}
+// LIST: the stage map's form (t41rx_set_stage_map).  Column c of workgroup b serves channel list[16 b + c]: the audio
+// staging addresses the listed channel's rows (a scalar load per column), and the state rows, channel-minor, are gathered
+// and scattered per lane -- 16 lanes of a request name 16 arbitrary channels of a row where the form without a map reads
+// 64 consecutive bytes.  That is once per launch and state row, against 256 samples per frame of the serial chain.
+#define T41_STAGE_KERNEL anr_kernel
+#define T41_STAGE_LIST 0
+#include "anr_kernel.inc"
+#undef T41_STAGE_KERNEL
+#undef T41_STAGE_LIST
+#define T41_STAGE_KERNEL anr_list_kernel
+#define T41_STAGE_LIST 1
+#include "anr_kernel.inc"
+#undef T41_STAGE_KERNEL
+#undef T41_STAGE_LIST
 
 // ------------------------------------------------------------------------------------------
 // Kim1_NR() / SpectralNoiseReduction(), one wave per channel
@@ -345,9 +267,16 @@ __device__ __forceinline__ bool nr_ratio_near_edge(unsigned rb) {
   return near;
 }
 
-template <int KIND>
+// KINDL = KIND, or KIND + kNrList for the stage map's form (t41rx_set_stage_map): the grid is the list's length and the
+// wave takes its channel from the list, one scalar load.  The switch rides on the KIND argument, as the input map rides on
+// rx512_kernel's PART, so that nrspec_kernel<1> and nrspec_kernel<2> keep their names and their instruction streams.
+constexpr int kNrList = 4;
+template <int KINDL>
 __global__ __launch_bounds__(64) void nrspec_kernel(const NrArgs a) {
 #pragma clang fp contract(off)
+  constexpr int KIND = KINDL & 3;
+  constexpr bool LIST = (KINDL & kNrList) != 0;
+  static_assert(KIND == 1 || KIND == 2, "Kim1_NR() or SpectralNoiseReduction()");
   // One region serves, one after the other within a frame, as the FFT's exchange buffer, the spectrum for the partner
   // access, the two weighted spectra and the two output frames: a workgroup is ONE wave, whose LDS operations execute
   // in program order, and each tenant is dead (in registers) before the next one is written.  With the per-bin
@@ -368,8 +297,8 @@ __global__ __launch_bounds__(64) void nrspec_kernel(const NrArgs a) {
   float *Gst = GstP + 8;
   __shared__ float Lout[128], Nest[128], Pslp[128], Xt[128], Hk[128];
   const int lane = threadIdx.x;
-  const int ch = blockIdx.x;
-  if (ch >= a.nchan) return;
+  if (!LIST && (int)blockIdx.x >= a.nchan) return;
+  const int ch = LIST ? a.list[blockIdx.x] : (int)blockIdx.x;
   float *st = a.spec + (size_t)ch * kNrSpecFloats;
   const float *win = a.tab_nr + (KIND == 1 ? kNrTabHann : kNrTabSqrtHann);
   const cf *tab = reinterpret_cast<const cf *>(a.tab);
@@ -807,7 +736,29 @@ __global__ __launch_bounds__(64) void nrspec_kernel(const NrArgs a) {
   }
 }
 
+namespace {
+// the spectral function and Xanr() of one call take the same channels (with a list: both the same list)
+hipError_t launch_nr_list(const NrArgs &a, hipStream_t s) {
+  if (a.nlist <= 0 || a.nlist > a.nchan) return hipErrorInvalidConfiguration;
+  if (a.nr_option == 1)
+    hipLaunchKernelGGL((nrspec_kernel<1 + kNrList>), dim3(a.nlist), dim3(64), 0, s, a);
+  else if (a.nr_option == 2)
+    hipLaunchKernelGGL((nrspec_kernel<2 + kNrList>), dim3(a.nlist), dim3(64), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (a.nr_option == 3 || a.notch) {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(&anr_list_kernel),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)kAnrLdsBytes);
+    if (attr != hipSuccess) return attr;
+    hipLaunchKernelGGL(anr_list_kernel, dim3((a.nlist + kAnrCw - 1) / kAnrCw), dim3(128), kAnrLdsBytes, s, a);
+    e = hipGetLastError();
+  }
+  return e;
+}
+}  // namespace
+
 hipError_t launch_nr(const NrArgs &a, hipStream_t s) {
+  if (a.list) return launch_nr_list(a, s);
   if (a.nr_option == 1)
     hipLaunchKernelGGL((nrspec_kernel<1>), dim3(a.nchan), dim3(64), 0, s, a);
   else if (a.nr_option == 2)

@@ -52,6 +52,10 @@ struct NrArgs {
   int notch;             // ANR_notchOn
   float alpha, beta, psi;  // NR_alpha, NR_beta, NR_PSI
   int vad_lo, vad_hi;    // design.cpp: nr_vad_range()
+  // the stage map (t41rx_set_stage_map), or null: the nlist > 0 channels the stages run on, ascending; the spectral
+  // function and Xanr() of one call take the same list
+  const int *list;
+  int nlist;
 };
 hipError_t launch_nr(const NrArgs &a, hipStream_t s);
 

@@ -27,7 +27,11 @@ int ensure_eq(t41rx_ctx *ctx) {
 
 // Process.cpp:828-832 on the call's audio @24 kS/s
 int eq_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
+  const StageList l = stage_list(ctx, kStageEq);
+  if (l.empty()) return T41RX_OK;  // the stage map lists no channel: nothing to launch
   EqArgs q{};
+  q.list = l.list;
+  q.nlist = l.n;
   q.aud = ctx->d_aud24.get();
   q.state = ctx->eq.d_state.get();
   q.nchan = ctx->nchan;
@@ -76,7 +80,11 @@ int ensure_nr(t41rx_ctx *ctx) {
 
 // Process.cpp:841-866 behind the equalizer
 int nr_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
+  const StageList l = stage_list(ctx, kStageNr);
+  if (l.empty()) return T41RX_OK;  // the stage map lists no channel: nothing to launch
   NrArgs n{};
+  n.list = l.list;  // (the spectral function and Xanr() of this call: the same list)
+  n.nlist = l.n;
   n.aud = ctx->d_aud24.get();
   n.anr = ctx->nr.d_anr.get();
   n.spec = ctx->nr.d_spec.get();
@@ -133,7 +141,13 @@ int ensure_nb(t41rx_ctx *ctx) {
 
 // Process.cpp:873-876 behind the noise reduction
 int nb_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
+  const StageList l = stage_list(ctx, kStageNb), rest = stage_list(ctx, kStageCount);
+  if (l.empty()) return T41RX_OK;  // the stage map lists no channel: nothing to launch, and the slot does not flip
   NbArgs b{};
+  b.list = l.list;  // (the launch carries the channels it leaves out from slot sel to slot sel ^ 1: nb_kernel.hip)
+  b.nlist = l.n;
+  b.rest = rest.list;
+  b.nrest = rest.n;
   b.aud = ctx->d_aud24.get();
   b.carry = ctx->nb.d_carry.get();
   b.nchan = ctx->nchan;

@@ -1,7 +1,7 @@
 // t41_sdr_amd/csrc/rx_ctx.hpp -- the receive context (struct t41rx_ctx) and what the host files of the receive side share.
 // Private to them: rx_host.cpp (the core and the process call), rx_state.cpp (checkpoints and reset) and one file per
 // stage family -- rx_audio.cpp, rx_cw.cpp, rx_ft8.cpp, rx_ft8_decode.cpp, rx_display.cpp, rx_beacon.cpp, rx_cal.cpp -- and
-// rx_sets.cpp (the parameter sets) and rx_outmap.cpp (the output map).  Each
+// rx_sets.cpp (the parameter sets), rx_outmap.cpp (the output map) and rx_stagemap.cpp (the stage map).  Each
 // stage family holds its part of the context in a struct of its own below, and exports the few functions the process
 // call and the checkpoint table name.  No kernel is compiled into a host file: they see the kernels through the
 // *_kernels.hpp headers.
@@ -24,6 +24,7 @@
 #include "rx_experiments.hpp"
 #include "rx_internal.hpp"
 #include "rx_kernels.hpp"
+#include "rx_stagemap.hpp"
 
 // the product's host side is never a diagnostic build; what the KERNEL objects were built as is asked at run time
 // (kernel_build_flags(), rx_dispatch.hip): tools/build_variant.sh links these very objects with diagnostic kernels
@@ -190,6 +191,24 @@ struct ParamSets {
   DevBuf<int32_t> d_set_of;
 };
 
+// the stage map (t41rx_set_stage_map; rx_stagemap.cpp): the caller's mask per channel, the lists made of it
+// (rx_stagemap.hpp) and their device copy -- kStageCount + 1 rows of nchan entries, row s the list of stage s, the last
+// row the blanker's complement.  Configuration like the output map: in no checkpoint, untouched by reset / set_state /
+// set_params.  on == false: no map, every stage launches what it always launched.
+struct StageMap {
+  bool on = false;
+  std::vector<uint32_t> map;  // [nchan] (host)
+  StageLists lists;
+  DevBuf<int32_t> d_lists;    // allocated with the first map
+};
+// what a stage's *_run passes to its launcher: null and 0 without a map
+struct StageList {
+  const int32_t *list = nullptr;
+  int n = 0;
+  bool mapped = false;
+  bool empty() const { return mapped && n == 0; }  // nothing to launch: a grid of zero blocks is a launch error
+};
+
 // staging for t41rx_process_host
 struct Staging {
   DevBuf<float> d_in_i, d_in_q, d_out;
@@ -245,6 +264,7 @@ struct t41rx_ctx {
   t41::DevBuf<int32_t> d_out_map;  // [nchan], allocated with the first map
   t41::DevBuf<double> d_win;      // the display FFT's window (ensure_window): display spectrum, panadapter, calibration
   t41::ParamSets sets;
+  t41::StageMap stages;
   t41::NrStage nr;
   t41::NbStage nb;
   t41::EqStage eq;
@@ -301,6 +321,12 @@ int aud24_finish_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t 
 inline int input_rows(const t41rx_ctx *ctx) { return ctx->n_streams > 0 ? ctx->n_streams : ctx->nchan; }
 // rows of audio a process call writes: one per channel, or the output map's n_rows
 inline int audio_rows(const t41rx_ctx *ctx) { return ctx->out_map_on ? ctx->out_rows : ctx->nchan; }
+// the list of a stage of a call (rx_stagemap.hpp: StageIndex), row kStageCount: the blanker's complement
+inline StageList stage_list(const t41rx_ctx *ctx, int row) {
+  if (!ctx->stages.on) return StageList{};
+  const std::vector<int32_t> &l = row < kStageCount ? ctx->stages.lists.list[row] : ctx->stages.lists.nb_rest;
+  return StageList{ctx->stages.d_lists.get() + (size_t)row * (size_t)ctx->nchan, (int)l.size(), true};
+}
 // the output map leaves rows unused: the host-pointer forms then carry the caller's rows through the staging buffer, so
 // that a row no channel names comes back as it went in
 inline bool audio_rows_unused(const t41rx_ctx *ctx) { return ctx->out_map_on && ctx->out_listened < ctx->out_rows; }

@@ -88,7 +88,11 @@ const char *cw_split_stage(const t41rx_ctx *ctx) {
 
 // Process.cpp:878-879 behind the blanker: DoCWReceiveProcessing() reads the audio, its results go to the caller's buffer
 int cw_detect_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
+  const StageList l = stage_list(ctx, kStageCwDetect);
+  if (l.empty()) return T41RX_OK;  // the stage map lists no channel: nothing to launch
   CwDetectArgs d{};
+  d.list = l.list;
+  d.nlist = l.n;
   d.aud = ctx->d_aud24.get();
   d.state = ctx->cw.d_state.get();
   d.out = ctx->cw.out;
@@ -114,7 +118,11 @@ int cw_detect_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
 
 // CWProcessing.cpp:365-371 behind it: the threshold on the detector's combinedCoeff and DoCWDecoding()
 int cw_decode_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
+  const StageList l = stage_list(ctx, kStageCwDecode);  // (a subset of the detector's: the setter's rule)
+  if (l.empty()) return T41RX_OK;  // the stage map lists no channel: nothing to launch
   CwDecodeArgs d{};
+  d.list = l.list;
+  d.nlist = l.n;
   d.cw = ctx->cw.out;
   d.state = ctx->cw.d_dec.get();
   d.text = ctx->cw.text;

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _args, _lib, panadapter
-from ._args import F32P, I32P, U16P, channel_mask, cuda, cuda_tensor, get_blob, int_table, kept, ptr, run, set_blob, table, table_pair, value, with_fields
+from ._args import F32P, I32P, U16P, U32P, channel_mask, cuda, cuda_tensor, get_blob, int_table, kept, ptr, run, set_blob, table, table_pair, value, with_fields
 from ._lib import DEMOD_AM, DEMOD_LSB, DEMOD_NFM, DEMOD_SAM, DEMOD_USB, Params, T41RxError, check  # noqa: F401
 
 
@@ -220,6 +220,25 @@ class RxChain:
         """the output map as an int32 array [n_channels] (a copy, -1: muted), or None with the map off"""
         m = np.zeros(self.n_channels, np.int32)
         return m if value(self._lib.t41rx_get_output_map(self._ctx, ptr(m, I32P), self.n_channels, None)) > 0 else None
+
+    def set_stage_map(self, stages):
+        """Receiver groups (t41rx_set_stage_map): stages[c] is channel c's mask of STAGE_EQ, STAGE_NR (noise reduction and
+        notch), STAGE_NB, STAGE_CW_DETECT and STAGE_CW_DECODE.  A stage runs on a channel when the chain's switch for it
+        is on and the channel's bit is set; a channel whose bit is clear is processed as with the stage switched off, and
+        the stage's memory for it stays as it was.  STAGE_CW_DECODE needs STAGE_CW_DETECT.  None removes the map: every
+        stage on every channel.  Configuration, like the output map: in no checkpoint, kept across reset() / set_state()
+        / CalcFilters(); FFT_LENGTH 512."""
+        if stages is None:
+            check(self._lib.t41rx_set_stage_map(self._ctx, None, 0))
+            return
+        m = int_table(stages, np.uint32, None, "stages must be a 1-d array of n_channels STAGE_* masks, got %r %s")
+        check(self._lib.t41rx_set_stage_map(self._ctx, ptr(m, U32P), int(m.size)))
+
+    @property
+    def stage_map(self):
+        """the stage map as a uint32 array [n_channels] of STAGE_* masks (a copy), or None with no map set"""
+        m = np.zeros(self.n_channels, np.uint32)
+        return m if value(self._lib.t41rx_get_stage_map(self._ctx, ptr(m, U32P), self.n_channels)) > 0 else None
 
     def set_param_sets(self, sets, set_of_channel=None):
         """Receiver groups (t41rx_set_param_sets): the context's own parameters are set 0, sets[i] becomes set i + 1, and
