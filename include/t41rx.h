@@ -455,6 +455,57 @@ T41RX_API int t41rx_audio_rows(const t41rx_ctx *ctx);
 T41RX_API int t41rx_set_stage_map(t41rx_ctx *ctx, const uint32_t *stages_of_channel, int n);  /* NULL, 0: remove */
 T41RX_API int t41rx_get_stage_map(const t41rx_ctx *ctx, uint32_t *stages_of_channel_out, int n);
 
+/* ---- receiver groups: stage parameters per channel -- the CW filter and the equalizer's levels (ABI 5) ----
+ * The stage map says on which channels a stage runs, not with which parameters: every listener of a CW skimmer got the
+ * same CWFilterIndex and the same fourteen equalizerRec levels.  These two maps give each channel its own.  Both are new
+ * entry points: no call above changes what it does, and a context that sets neither launches what it always launched.
+ *
+ * THE CW FILTER MAP.  The rule: while a map is loaded, channel c is processed exactly as the same channel of a context
+ * without a map whose t41rx_set_cw_filter() value is filter_of_channel[c] -- 0 .. 4, or 5 for off.  That covers the
+ * channel's audio row, the five per-filter memories (only the selected one advances, the other four stay stale, as the
+ * firmware's statics do), the interpolator memories and every other state word.  The context-wide index is kept, is not
+ * consulted while a map is loaded, and is still what t41rx_get_cw_filter() returns; removing the map returns to it.  As
+ * before, nothing of the CW block runs unless xmtMode == T41RX_CW_MODE.  The detector and the decoder read ahead of the
+ * filter and do not see the map.
+ * How a call runs it: the narrow filter runs in one launch over the list of filtered channels, each with its own index.
+ * A filtered channel ends in the firmware's interpolators operation for operation, an unfiltered one in the fused back
+ * kernel; the two differ in the last bit, so a call at 192 kS/s with both classes launches both back kernels, each in
+ * its output-map form with the other class muted.  At 24 kS/s one finish serves both.  A map that filters nobody is a
+ * call without the filter; a map that filters everybody a call with it.
+ * t41rx_set_cw_filter_map(): filter_of_channel is a host array of n == n_channels values.  NULL with n == 0 removes the
+ *   map.  Everything is checked on the host before anything changes, and a refused call leaves the previous map whole:
+ *   n != n_channels, an entry outside [0, 5] (the text names the channel), or an entry < 5 before t41rx_set_cw_tables()
+ *   loaded the filter tables return T41RX_ERR_ARG; fft_length != 512 returns T41RX_ERR_UNSUPPORTED; so does a map with
+ *   an entry < 5 while parameter sets are loaded, in the words of the other chain-splitting stages, and
+ *   t41rx_set_param_sets() refuses a context with such a map.  A map of 5s is accepted next to parameter sets, as
+ *   t41rx_set_cw_filter(ctx, 5) is.  Synchronises the device, then uploads (the ordering rule of t41rx_set_input_map).
+ *   Composes with the input map, the output map (set before or after), the stage map, both audio rates, both layouts,
+ *   f32 and q15.
+ * t41rx_get_cw_filter_map(): returns 1 with a map loaded, 0 with none (negative: an error status).
+ *   filter_of_channel_out, n == n_channels entries, receives the map, or the context-wide index in every entry with
+ *   none; it may be NULL.
+ *
+ * THE EQUALIZER LEVEL MAP.  The rule: while a map is loaded and the equalizer runs on channel c -- the context's switch
+ * is on (t41rx_set_receive_eq) and the stage map's T41RX_STAGE_EQ bit is set or no stage map is loaded -- channel c is
+ * processed exactly as a context whose t41rx_set_receive_eq(1, equalizerRec[c]) would process it.  The switch, the band
+ * table and the stage map stay what they are; the context-wide levels are kept and returned by t41rx_get_receive_eq()
+ * as before.  The levels are converted on the host, (float)equalizerRec / 100.0 with the sign of odd bands turned, as
+ * for the context-wide vector, and uploaded when the map is set.
+ * t41rx_set_receive_eq_map(): equalizerRec is a host array [n][14] with n == n_channels.  NULL with n == 0 removes the
+ *   map.  n != n_channels returns T41RX_ERR_ARG, fft_length != 512 T41RX_ERR_UNSUPPORTED, and the previous map stays
+ *   whole; no level vector is refused, as t41rx_set_receive_eq() refuses none.  Synchronises the device, then uploads.
+ * t41rx_get_receive_eq_map(): returns 1 with a map loaded, 0 with none (negative: an error status).  equalizerRec_out,
+ *   [n][14] with n == n_channels, receives the map, or the context-wide levels in every row with none; it may be NULL.
+ *
+ * Both maps are configuration, like the stage map: they are in no checkpoint, survive t41rx_reset, t41rx_set_state,
+ * t41rx_set_params and t41rx_set_coeffs, and may change between any two calls.  t41rx_state_bytes() and every
+ * checkpoint section are what they are without a map.  Still per context: nrOptionSelect and the notch, FT8, the
+ * panadapter and the beacon monitor; parameter sets and the chain-splitting stages go on refusing each other. */
+T41RX_API int t41rx_set_cw_filter_map(t41rx_ctx *ctx, const int32_t *filter_of_channel, int n);  /* NULL, 0: remove */
+T41RX_API int t41rx_get_cw_filter_map(const t41rx_ctx *ctx, int32_t *filter_of_channel_out, int n);
+T41RX_API int t41rx_set_receive_eq_map(t41rx_ctx *ctx, const int32_t *equalizerRec, int n);  /* [n][14]; NULL, 0: remove */
+T41RX_API int t41rx_get_receive_eq_map(const t41rx_ctx *ctx, int32_t *equalizerRec_out, int n);
+
 /* ---- receiver groups: parameter sets, one t41rx_params per group of channels (ABI 5) ----
  * The receivers of one band differ in more than NCOFreq: the phone receivers are LSB at 2.8 kHz, the FT8 receiver is USB
  * at 200..3000 Hz, the CW receivers want a few hundred hertz.  A context's own t41rx_params (t41rx_create,

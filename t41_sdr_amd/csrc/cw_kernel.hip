@@ -47,81 +47,22 @@ constexpr int kInPitch = df2t::kChunk + 4;  // (4 banks apart per channel row: t
 constexpr int kRowShr1 = 0x111;             // DPP row_shr:1: lane l reads lane l - 1 (stage s reads stage s - 1)
 }  // namespace cw
 
-__global__ __launch_bounds__(64) void cw_filter_kernel(CwFilterArgs a) {
-#pragma clang fp contract(off)
-  using namespace cw;
-  using namespace df2t;
-  __shared__ __attribute__((aligned(16))) float xin[kCwChanPerWave * kInPitch];
-  __shared__ __attribute__((aligned(16))) float ring[kCwChanPerWave * kRowPitch];
-  const int lane = threadIdx.x;
-  const int grp = lane >> 3, stage = lane & 7;
-  const int ch0 = blockIdx.x * kCwChanPerWave;
-  const int nlive = min(kCwChanPerWave, a.nchan - ch0);  // channels of this wave (the ragged last one has fewer)
-  const bool live = stage < kCwStages && grp < nlive;
-  float *x = a.aud + (size_t)ch0 * a.nsamp;
-  float *st = a.state + (size_t)(ch0 + grp) * kCwStateFloats + kCwStFilter + 2 * kCwStages * a.index + 2 * stage;
-  const int nchunk = a.nsamp / kChunk;
-
-  Pipe<kCwStages, kRowShr1, false, true> p;
-  p.head = stage == 0;
-  p.tail = live && stage == kCwStages - 1;
-  if (live) {
-    const float *c = a.coef + 5 * stage;
-    p.q = Section{c[0], c[1], c[2], c[3], c[4], st[0], st[1]};
-  }
-  const float *in_row = xin + grp * kInPitch;
-  p.row = ring + grp * kRowPitch;
-
-  // samples 64 k .. 64 k + 63 of every channel of the wave back to the scratch, coalesced
-  auto store_chunk = [&](int k) {
-    for (int kk = 0; kk < nlive; ++kk)
-      x[(size_t)kk * a.nsamp + (size_t)k * kChunk + lane] = ring[kk * kRowPitch + (k & 1) * kChunk + lane];
-  };
-
-  float nxt[kCwChanPerWave];
-#pragma unroll
-  for (int kk = 0; kk < kCwChanPerWave; ++kk) nxt[kk] = kk < nlive ? x[(size_t)kk * a.nsamp + lane] : 0.0f;
-  for (int c = 0; c < nchunk; ++c) {
-#pragma unroll
-    for (int kk = 0; kk < kCwChanPerWave; ++kk) xin[kk * kInPitch + lane] = nxt[kk];
-    if (c + 1 < nchunk) {
-#pragma unroll
-      for (int kk = 0; kk < kCwChanPerWave; ++kk)
-        if (kk < nlive) nxt[kk] = x[(size_t)kk * a.nsamp + (size_t)(c + 1) * kChunk + lane];
-    }
-    __syncthreads();
-    if (c == 0) {  // the pipeline fills: stage s starts at step s
-#pragma unroll
-      for (int j = 0; j < kChunk; j += 4) {
-        const float4 v = *reinterpret_cast<const float4 *>(in_row + j);
-        p.run(v.x, j, 0, j >= stage);
-        p.run(v.y, j + 1, 0, j + 1 >= stage);
-        p.run(v.z, j + 2, 0, j + 2 >= stage);
-        p.run(v.w, j + 3, 0, j + 3 >= stage);
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < kChunk; j += 4) {
-        const float4 v = *reinterpret_cast<const float4 *>(in_row + j);
-        p.run(v.x, j, c, true);
-        p.run(v.y, j + 1, c, true);
-        p.run(v.z, j + 2, c, true);
-        p.run(v.w, j + 3, c, true);
-      }
-    }
-    __syncthreads();
-    if (c > 0) store_chunk(c - 1);
-  }
-  // the pipeline drains: step 64 n + d runs stages d + 1 .. 5 on the last samples
-#pragma unroll
-  for (int d = 0; d < kCwStages - 1; ++d) p.run(0.0f, kChunk + d, nchunk - 1, stage > d);
-  __syncthreads();
-  store_chunk(nchunk - 1);
-  if (live) {
-    st[0] = p.q.d1;
-    st[1] = p.q.d2;
-  }
-}
+// MAP: the CW filter map's form (t41rx_set_cw_filter_map).  The grid is the filtered channels' list over eight, the wave
+// takes its eight channels from the list and every group of eight lanes its own channel's CWFilterIndex; see the text.
+#define T41_STAGE_KERNEL cw_filter_kernel
+#define T41_STAGE_ARGS CwFilterArgs
+#define T41_STAGE_MAP 0
+#include "cw_filter_kernel.inc"
+#undef T41_STAGE_KERNEL
+#undef T41_STAGE_ARGS
+#undef T41_STAGE_MAP
+#define T41_STAGE_KERNEL cw_filter_map_kernel
+#define T41_STAGE_ARGS CwFilterMapArgs
+#define T41_STAGE_MAP 1
+#include "cw_filter_kernel.inc"
+#undef T41_STAGE_KERNEL
+#undef T41_STAGE_ARGS
+#undef T41_STAGE_MAP
 
 // LIST: the stage map's form (t41rx_set_stage_map).  The grid is the list's length and the wave takes its channel from the
 // list, one scalar load; the rows of `out` of the channels the list leaves out are not written.
@@ -365,6 +306,13 @@ hipError_t launch_cw_filter(const CwFilterArgs &a, hipStream_t s) {
   if (a.nchan <= 0 || a.nsamp <= 0 || a.nsamp % df2t::kChunk || a.index < 0 || a.index >= kCwFilters) return hipErrorInvalidConfiguration;
   const unsigned waves = (unsigned)((a.nchan + kCwChanPerWave - 1) / kCwChanPerWave);
   hipLaunchKernelGGL(cw_filter_kernel, dim3(waves), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_cw_filter_map(const CwFilterMapArgs &a, hipStream_t s) {
+  if (a.nchan <= 0 || a.nsamp <= 0 || a.nsamp % df2t::kChunk || !a.list || !a.index_of || a.nlist <= 0 || a.nlist > a.nchan) return hipErrorInvalidConfiguration;
+  const unsigned waves = (unsigned)((a.nlist + kCwChanPerWave - 1) / kCwChanPerWave);
+  hipLaunchKernelGGL(cw_filter_map_kernel, dim3(waves), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 

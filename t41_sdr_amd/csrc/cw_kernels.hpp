@@ -34,6 +34,19 @@ struct CwFilterArgs {
 };
 hipError_t launch_cw_filter(const CwFilterArgs &a, hipStream_t s);
 
+// The same with a CWFilterIndex per channel (t41rx_set_cw_filter_map): the filter runs on the nlist channels of `list`,
+// each with the memory and the coefficient row of its own index; the others' audio and memories are neither read nor
+// written.  Eight channels of the list per wave.
+struct CwFilterMapArgs {
+  float *aud;           // [nchan][nsamp] audio @24 kS/s, the listed channels' rows filtered in place
+  float *state;         // [nchan][kCwStateFloats]
+  const int *list;      // the filtered channels, ascending; readable up to the next multiple of kCwChanPerWave entries
+  const int *index_of;  // [nchan] CWFilterIndex per channel; 0 .. 4 for every channel of the list
+  int nlist, nchan, nsamp;
+  float coef[kCwFilters * kCwFilterCoefs];  // all five filters' [filter][stage][5]
+};
+hipError_t launch_cw_filter_map(const CwFilterMapArgs &a, hipStream_t s);
+
 struct CwDetectArgs {
   const float *aud;  // [nchan][nframes * 256] audio @24 kS/s (read only)
   float *state;      // [nchan][kCwStateFloats]

@@ -29,6 +29,8 @@ static_assert(kEqBands == df2t::kBands, "df2t::sum_bands sums the equalizer's ba
 
 // LIST: the stage map's form (t41rx_set_stage_map).  The grid is the list's length and the wave takes its channel from the
 // list, one scalar load; everything else is the kernel as it is without a map.
+// LEVELS: the equalizer level map's forms (t41rx_set_receive_eq_map), plain and list: the band's level is the channel's own.
+#define T41_STAGE_LEVELS 0
 #define T41_STAGE_KERNEL eq_kernel
 #define T41_STAGE_LIST 0
 #include "eq_kernel.inc"
@@ -39,10 +41,25 @@ static_assert(kEqBands == df2t::kBands, "df2t::sum_bands sums the equalizer's ba
 #include "eq_kernel.inc"
 #undef T41_STAGE_KERNEL
 #undef T41_STAGE_LIST
+#undef T41_STAGE_LEVELS
+#define T41_STAGE_LEVELS 1
+#define T41_STAGE_KERNEL eq_levels_kernel
+#define T41_STAGE_LIST 0
+#include "eq_kernel.inc"
+#undef T41_STAGE_KERNEL
+#undef T41_STAGE_LIST
+#define T41_STAGE_KERNEL eq_levels_list_kernel
+#define T41_STAGE_LIST 1
+#include "eq_kernel.inc"
+#undef T41_STAGE_KERNEL
+#undef T41_STAGE_LIST
+#undef T41_STAGE_LEVELS
 
 hipError_t launch_eq(const EqArgs &a, hipStream_t s) {
   if (a.nchan <= 0 || a.nsamp <= 0 || a.nsamp % df2t::kChunk || (a.list && a.nlist <= 0)) return hipErrorInvalidConfiguration;
-  if (a.list) hipLaunchKernelGGL(eq_list_kernel, dim3((unsigned)a.nlist), dim3(64), 0, s, a);
+  if (a.levels && a.list) hipLaunchKernelGGL(eq_levels_list_kernel, dim3((unsigned)a.nlist), dim3(64), 0, s, a);
+  else if (a.levels) hipLaunchKernelGGL(eq_levels_kernel, dim3((unsigned)a.nchan), dim3(64), 0, s, a);
+  else if (a.list) hipLaunchKernelGGL(eq_list_kernel, dim3((unsigned)a.nlist), dim3(64), 0, s, a);
   else hipLaunchKernelGGL(eq_kernel, dim3((unsigned)a.nchan), dim3(64), 0, s, a);
   return hipGetLastError();
 }

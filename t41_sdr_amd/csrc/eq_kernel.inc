@@ -2,6 +2,8 @@
 // T41_STAGE_LIST 0 makes the kernel as it is without a stage map, 1 its list form (t41rx_set_stage_map).  Two kernels
 // of one text, not one body shared by two kernels: an argument block handed on by reference compiles to another
 // instruction stream, and the form without a map must stay the stream it was.
+// T41_STAGE_LEVELS 1 (t41rx_set_receive_eq_map) makes either form with the levels per channel: a band's signed level comes
+// from row `channel` of a.levels ([nchan][kEqBands], converted on the host like a.scale) and nothing else changes.
 __global__ __launch_bounds__(64) void T41_STAGE_KERNEL(EqArgs a) {
 #pragma clang fp contract(off)
   constexpr bool LIST = T41_STAGE_LIST != 0;
@@ -22,7 +24,11 @@ __global__ __launch_bounds__(64) void T41_STAGE_KERNEL(EqArgs a) {
   if (live) {
     const float *c = a.coef + 5 * lane;
     p.q = Section{c[0], c[1], c[2], c[3], c[4], st[2 * lane], st[2 * lane + 1]};
+#if T41_STAGE_LEVELS
+    p.level = a.levels[(size_t)ch * kEqBands + band];
+#else
     p.level = a.scale[band];
+#endif
   }
   p.row = ring + (live ? band : 0) * kRowPitch;
   // samples 64 k .. 64 k + 63 through the sum and back

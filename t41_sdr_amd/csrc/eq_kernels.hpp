@@ -22,6 +22,9 @@ struct EqArgs {
   // and memories are neither read nor written
   const int *list;
   int nlist;
+  // the level map (t41rx_set_receive_eq_map), or null: [nchan][kEqBands] signed levels in `scale`'s form, which then is
+  // not read
+  const float *levels;
 };
 hipError_t launch_eq(const EqArgs &a, hipStream_t s);
 

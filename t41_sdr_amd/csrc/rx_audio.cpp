@@ -36,6 +36,7 @@ int eq_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
   q.state = ctx->eq.d_state.get();
   q.nchan = ctx->nchan;
   q.nsamp = n_frames * 256;
+  if (ctx->eq.map_on) q.levels = ctx->eq.d_levels.get();  // (the level map: converted at set time by the expression below)
   std::memcpy(q.coef, ctx->eq.coef, sizeof(q.coef));
   for (int b = 0; b < kEqBands; ++b) {
     // recEQ_LevelScale[b] = (float)EEPROMData.equalizerRec[b] / 100.0 (Filter.cpp:119-121); arm_scale_f32 by its

@@ -1,7 +1,8 @@
 // t41_sdr_amd/csrc/rx_ctx.hpp -- the receive context (struct t41rx_ctx) and what the host files of the receive side share.
 // Private to them: rx_host.cpp (the core and the process call), rx_state.cpp (checkpoints and reset) and one file per
 // stage family -- rx_audio.cpp, rx_cw.cpp, rx_ft8.cpp, rx_ft8_decode.cpp, rx_display.cpp, rx_beacon.cpp, rx_cal.cpp -- and
-// rx_sets.cpp (the parameter sets), rx_outmap.cpp (the output map) and rx_stagemap.cpp (the stage map).  Each
+// rx_sets.cpp (the parameter sets), rx_outmap.cpp (the output map), rx_stagemap.cpp (the stage map) and
+// rx_stageparams.cpp (the CW filter map and the equalizer level map).  Each
 // stage family holds its part of the context in a struct of its own below, and exports the few functions the process
 // call and the checkpoint table name.  No kernel is compiled into a host file: they see the kernels through the
 // *_kernels.hpp headers.
@@ -25,6 +26,7 @@
 #include "rx_internal.hpp"
 #include "rx_kernels.hpp"
 #include "rx_stagemap.hpp"
+#include "rx_stageparams.hpp"
 
 // the product's host side is never a diagnostic build; what the KERNEL objects were built as is asked at run time
 // (kernel_build_flags(), rx_dispatch.hip): tools/build_variant.sh links these very objects with diagnostic kernels
@@ -55,6 +57,12 @@ struct EqStage {
   float coef[kEqCoefs] = {};
   int32_t levels[kEqBands] = {100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100, 100};
   DevBuf<float> d_state;
+  // the level map (t41rx_set_receive_eq_map; rx_stageparams.cpp): equalizerRec per channel and its device form, the
+  // signed level scales [nchan][kEqBands] as eq_run() makes them of `levels`.  Configuration like the stage map: in no
+  // checkpoint, untouched by reset / set_state / set_params.  map_on == false: every channel takes `levels`.
+  bool map_on = false;
+  std::vector<int32_t> level_map;  // [nchan][kEqBands] (host)
+  DevBuf<float> d_levels;          // allocated with the first map
 };
 
 // a stage's clock, millis(n) = t0 + floor(n * num / den): 2048 samples at 192 kS/s
@@ -86,7 +94,18 @@ struct CwStage {
   int text_frames = 0;      // frames per call `text` is sized for
   StageClock clock;
   DevBuf<int32_t> d_dec;
+  // the filter map (t41rx_set_cw_filter_map; rx_stageparams.cpp): CWFilterIndex per channel, the lists made of it and of
+  // the output map (rx_stageparams.hpp), and their device copy -- four rows of cw_map_pitch(nchan) entries: the indices,
+  // the filtered channels' list, the filtered and the unfiltered channels' rows.  Configuration like the stage map: in
+  // no checkpoint, untouched by reset / set_state / set_params.  map_on == false: every channel takes `filter`.
+  bool map_on = false;
+  std::vector<int32_t> filter_map;  // [nchan] (host)
+  CwFilterLists lists;
+  DevBuf<int32_t> d_map;            // allocated with the first map
 };
+// a row of CwStage::d_map: nchan entries, up to a multiple of eight (cw_filter_map_kernel reads its list eight at a time)
+inline size_t cw_map_pitch(int nchan) { return ((size_t)nchan + kCwChanPerWave - 1) / kCwChanPerWave * kCwChanPerWave; }
+enum CwMapRow : int { kCwMapIndex = 0, kCwMapList, kCwMapRowsFiltered, kCwMapRowsPlain, kCwMapRows };
 
 // FT8 receive up to the waterfall (Process.cpp:627-686, ft8.cpp:153-268; t41rx_set_ft8_tables / _ft8 / _ft8_clock /
 // t41rx_ft8_sync): the caller's window and mag_db (device copies), arm_rfft_q15's tables, the switch with the caller's
@@ -296,7 +315,10 @@ inline int hip_check(hipError_t e, const char *what) { return e == hipSuccess ? 
 inline bool nr_on(const t41rx_ctx *ctx) { return ctx->params.nrOptionSelect != 0 || ctx->params.ANR_notchOn != 0; }  // (fft_length 512: params_valid)
 // the CW block runs in T41State == CW_RECEIVE (Process.cpp:878), which in receive is xmtMode == CW_MODE
 // (T41_SDR.ino:1039-1040, 1144-1148); with another xmtMode the switches are kept and nothing runs
-inline bool cw_filter_on(const t41rx_ctx *ctx) { return ctx->params.xmtMode == T41RX_CW_MODE && ctx->cw.filter != kCwFilters; }
+// (a filter map, t41rx_set_cw_filter_map: the narrow filter runs when some channel has an index; the context's is not consulted)
+inline bool cw_filter_on(const t41rx_ctx *ctx) {
+  return ctx->params.xmtMode == T41RX_CW_MODE && (ctx->cw.map_on ? !ctx->cw.lists.filtered.empty() : ctx->cw.filter != kCwFilters);
+}
 inline bool cw_det_on(const t41rx_ctx *ctx) { return ctx->params.xmtMode == T41RX_CW_MODE && ctx->cw.det != 0; }
 // the decoder runs exactly when the detector runs (in the firmware one decoderFlag gates both, CWProcessing.cpp:322-372)
 inline bool cw_dec_on(const t41rx_ctx *ctx) { return cw_det_on(ctx) && ctx->cw.dec != 0; }
@@ -309,7 +331,8 @@ inline int sets_refuse_stage(const char *stage) {
 }
 // the chain-splitting stage whose switch is on, or null (the noise reduction / notch are parameters: the sets' rule has them)
 inline const char *split_stage_on(const t41rx_ctx *ctx) {
-  return ctx->eq.on ? "the receive equalizer" : ctx->nb.on ? "the noise blanker" : ctx->cw.filter != kCwFilters ? "the CW audio filter"
+  return ctx->eq.on ? "the receive equalizer" : ctx->nb.on ? "the noise blanker"
+         : (ctx->cw.filter != kCwFilters || (ctx->cw.map_on && !ctx->cw.lists.filtered.empty())) ? "the CW audio filter"
          : ctx->cw.det ? "the CW detector" : ctx->cw.dec ? "the CW decoder" : nullptr;
 }
 // rows of I / Q a process call reads: one per channel, or the input map's n_streams
@@ -395,6 +418,8 @@ int cw_decode_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
 int cw_filter_run(t41rx_ctx *ctx, const CallPlan &plan, const RxArgs &a, int n_frames, hipStream_t s);  // the narrow filter and its back end
 int check_cw_decode(const t41rx_ctx *ctx, const int32_t *hdr, const float *sec);
 int cw_decode_reset(t41rx_ctx *ctx, size_t bytes);
+// rx_stageparams.cpp: the filter map's row maps again, behind a change of the output map (no map loaded: nothing)
+int cw_filter_map_refresh(t41rx_ctx *ctx);
 // rx_ft8.cpp
 int ft8_prepare(t41rx_ctx *ctx, const CallPlan &plan, int n_frames, hipStream_t s);  // the call's refusals, the memory and the demod tap of its own
 int ft8_run(t41rx_ctx *ctx, const CallPlan &plan, const RxArgs &a, int n_frames, hipStream_t s);

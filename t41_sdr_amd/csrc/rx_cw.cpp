@@ -137,14 +137,32 @@ int cw_decode_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
 
 int cw_filter_run(t41rx_ctx *ctx, const CallPlan &plan, const RxArgs &a, int n_frames, hipStream_t s) {
   // Process.cpp:882-912: the narrow filter CWFilterIndex selects, on its own memory
-  CwFilterArgs f{};
-  f.aud = ctx->d_aud24.get();
-  f.state = ctx->cw.d_state.get();
-  f.nchan = ctx->nchan;
-  f.nsamp = n_frames * 256;
-  f.index = ctx->cw.filter;
-  std::memcpy(f.coef, ctx->cw.coef + kCwFilterCoefs * ctx->cw.filter, sizeof(f.coef));
-  hipError_t e = launch_cw_filter(f, s);
+  hipError_t e = hipSuccess;
+  const int32_t *map = ctx->cw.d_map.get();
+  const size_t pitch = cw_map_pitch(ctx->nchan);
+  if (ctx->cw.map_on) {
+    // the filter map (t41rx_set_cw_filter_map): the filtered channels' list, each with its own index (the plan sends a
+    // map that filters nobody past this function: the list is not empty)
+    CwFilterMapArgs f{};
+    f.aud = ctx->d_aud24.get();
+    f.state = ctx->cw.d_state.get();
+    f.list = map + (size_t)kCwMapList * pitch;
+    f.index_of = map + (size_t)kCwMapIndex * pitch;
+    f.nlist = (int)ctx->cw.lists.filtered.size();
+    f.nchan = ctx->nchan;
+    f.nsamp = n_frames * 256;
+    std::memcpy(f.coef, ctx->cw.coef, sizeof(f.coef));
+    e = launch_cw_filter_map(f, s);
+  } else {
+    CwFilterArgs f{};
+    f.aud = ctx->d_aud24.get();
+    f.state = ctx->cw.d_state.get();
+    f.nchan = ctx->nchan;
+    f.nsamp = n_frames * 256;
+    f.index = ctx->cw.filter;
+    std::memcpy(f.coef, ctx->cw.coef + kCwFilterCoefs * ctx->cw.filter, sizeof(f.coef));
+    e = launch_cw_filter(f, s);
+  }
   if (e != hipSuccess) return hip_fail(e, "CW filter kernel launch");
   // 24 kS/s (t41rx_set_audio_rate): the filtered audio is the result -- volume and stores, no interpolator
   if (plan.back == Back::cw_24k) return aud24_finish_run(ctx, a, n_frames, s);
@@ -162,11 +180,21 @@ int cw_filter_run(t41rx_ctx *ctx, const CallPlan &plan, const RxArgs &a, int n_f
   b.state_stride = (long long)state_floats(512);
   b.q15 = a.q15;
   b.out_map = a.out_map;  // (the output map: a's strides then place its n_rows rows)
+  // both classes in one call: this kernel for the filtered channels, the unfiltered ones muted, each at its own row
+  if (plan.back == Back::cw_mixed) b.out_map = map + (size_t)kCwMapRowsFiltered * pitch;
   b.scale = v.scalars[kScOutScale];
   std::memcpy(b.int1, v.int1, sizeof(b.int1));
   std::memcpy(b.int2, v.int2, sizeof(b.int2));
   e = launch_cw_back(b, s);
   if (e != hipSuccess) return hip_fail(e, "CW interpolator kernel launch");
+  if (plan.back == Back::cw_mixed) {
+    // ... and the fused back kernel for the unfiltered ones, as a call without the filter ends (launch_chain: back512)
+    RxArgs r = a;
+    r.aud_out = nullptr;
+    r.out_map = map + (size_t)kCwMapRowsPlain * pitch;
+    e = launch_back512(r, s);
+    if (e != hipSuccess) return hip_fail(e, "interpolator kernel launch");
+  }
   return T41RX_OK;
 }
 

@@ -281,6 +281,8 @@ CallFacts call_facts(const t41rx_ctx *ctx, int n_frames, bool q15) {
   f.cw_filter = cw_filter_on(ctx);
   f.cw_det = cw_det_on(ctx);
   f.omap = ctx->out_map_on;
+  // the CW filter map: cw_filter above says that some channel is filtered, this that some channel is not
+  f.cw_unfiltered = ctx->cw.map_on && ctx->cw.lists.filtered.size() < (size_t)ctx->nchan;
   return f;
 }
 
@@ -486,6 +488,7 @@ int launch_chain(t41rx_ctx *ctx, const CallPlan &plan, RxArgs a, int n_frames, h
   switch (plan.back) {
     case Back::cw_back:
     case Back::cw_24k:
+    case Back::cw_mixed:
       rc = cw_filter_run(ctx, plan, a, n_frames, s);
       break;
     case Back::finish24:

@@ -23,7 +23,7 @@ int t41rx_set_output_map(t41rx_ctx *ctx, const int32_t *row_of_channel, int n, i
     ctx->out_map_on = false;
     ctx->out_rows = 0;
     ctx->out_listened = 0;
-    return T41RX_OK;
+    return cw_filter_map_refresh(ctx);  // (a CW filter map's row maps name the channels' own rows again)
   }
   if (ctx->params.fft_length != 512)
     return fail(T41RX_ERR_UNSUPPORTED, "the output map is built for fft_length 512 (the long-FFT pipeline's back kernel interpolates and stores every channel)");
@@ -54,7 +54,7 @@ int t41rx_set_output_map(t41rx_ctx *ctx, const int32_t *row_of_channel, int n, i
   ctx->out_rows = n_rows;
   ctx->out_listened = listened;
   ctx->out_map_on = true;
-  return T41RX_OK;
+  return cw_filter_map_refresh(ctx);  // (a CW filter map's row maps follow the rows)
 }
 
 int t41rx_get_output_map(const t41rx_ctx *ctx, int32_t *row_of_channel_out, int n, int *n_rows_out) {

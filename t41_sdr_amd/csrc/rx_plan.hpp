@@ -23,6 +23,9 @@ struct CallFacts {
   // the stages that split the chain behind the demodulator
   bool eq = false, nr = false, nb = false, cw_filter = false, cw_det = false;
   bool omap = false;  // the caller's output map (t41rx_set_output_map): audio rows for the listened channels only
+  // the CW filter map (t41rx_set_cw_filter_map) is loaded and leaves some channel without the narrow filter (index 5).
+  // cw_filter then says that some channel has it; a map that filters nobody is a call without the filter
+  bool cw_unfiltered = false;
 };
 
 // an rx512_kernel instantiation of the whole chain (PART 0): two calls with equal forms launch the same kernel
@@ -56,6 +59,7 @@ enum class Back {
   back512,    // launch_back512: interpolators, volume, stores
   cw_back,    // CW filter + cw_back_kernel
   cw_24k,     // CW filter + the 24 kS/s finish
+  cw_mixed,   // CW filter map with both classes: cw_back_kernel for the filtered channels, launch_back512 for the others
   finish24,   // the 24 kS/s finish
   long_pipe,  // the long-FFT pipeline's own back end
 };
@@ -137,7 +141,7 @@ constexpr CallPlan plan_call(const CallFacts &f) {
     p.fused_back = !p.one_kernel && !p.cplx && !f.q15;
   }
   p.back = lng           ? Back::long_pipe
-           : f.cw_filter ? (f.a24 ? Back::cw_24k : Back::cw_back)
+           : f.cw_filter ? (f.a24 ? Back::cw_24k : f.cw_unfiltered ? Back::cw_mixed : Back::cw_back)
            : !p.handover ? Back::fused
            : f.a24       ? Back::finish24
                          : Back::back512;

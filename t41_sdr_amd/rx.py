@@ -308,6 +308,28 @@ class RxChain:
         lv = np.zeros(14, np.int32)
         return value(self._lib.t41rx_get_receive_eq(self._ctx, ptr(lv))), lv
 
+    def set_receive_eq_map(self, levels):
+        """Receiver groups (t41rx_set_receive_eq_map): levels[c] is channel c's EEPROMData.equalizerRec, [n_channels][14]
+        ints.  Where the equalizer runs on channel c -- the switch of set_receive_eq() on, and STAGE_EQ in the stage map
+        or no stage map -- the channel is processed exactly as a chain with set_receive_eq(1, levels[c]) would process
+        it.  The switch, the band table, the stage map and the chain's own levels stay what they are.  None removes the
+        map.  Configuration, like the stage map: in no checkpoint, kept across reset() / set_state() / CalcFilters();
+        FFT_LENGTH 512."""
+        if levels is None:
+            check(self._lib.t41rx_set_receive_eq_map(self._ctx, None, 0))
+            return
+        a = np.asarray(levels)
+        if a.ndim != 2 or a.shape[1] != 14 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("levels must be an [n_channels][14] array of ints, got %r %s" % (a.shape, a.dtype))
+        m = int_table(a.reshape(-1), np.int32, None, "levels must fit int32, got %r %s")
+        check(self._lib.t41rx_set_receive_eq_map(self._ctx, ptr(m, I32P), int(a.shape[0])))
+
+    @property
+    def receive_eq_map(self):
+        """the equalizer level map as an int32 array [n_channels][14] (a copy), or None with no map set"""
+        m = np.zeros((self.n_channels, 14), np.int32)
+        return m if value(self._lib.t41rx_get_receive_eq_map(self._ctx, ptr(m, I32P), self.n_channels)) > 0 else None
+
     def set_cw_tables(self, audio_filters=None, decode_fir=None):
         """The CW receive tables (t41rx_set_cw_tables): audio_filters = the firmware's CW_AudioFilterCoeffs1..5 as
         [5][6][5] or [5][30], {b0, b1, b2, a1, a2} per section with the a's negated; decode_fir = CW_Filter_Coeffs2, 64
@@ -328,6 +350,26 @@ class RxChain:
     @property
     def cw_filter(self):
         return value(self._lib.t41rx_get_cw_filter(self._ctx))
+
+    def set_cw_filter_map(self, filter_of_channel):
+        """Receiver groups (t41rx_set_cw_filter_map): filter_of_channel[c] is channel c's CWFilterIndex, 0 .. 4 or 5 = off.
+        While the map is loaded channel c is processed exactly as the same channel of a chain with
+        set_cw_filter(filter_of_channel[c]) would be: its audio, the five filter memories (only the selected one
+        advances), the interpolator memories.  The chain's own index is kept, not consulted, and still what cw_filter
+        returns.  None removes the map.  An index below 5 needs the filter tables and cannot stand next to parameter
+        sets.  Configuration, like the stage map: in no checkpoint, kept across reset() / set_state() / CalcFilters();
+        FFT_LENGTH 512."""
+        if filter_of_channel is None:
+            check(self._lib.t41rx_set_cw_filter_map(self._ctx, None, 0))
+            return
+        m = int_table(filter_of_channel, np.int32, None, "filter_of_channel must be a 1-d array of n_channels CWFilterIndex values (0 .. 5), got %r %s")
+        check(self._lib.t41rx_set_cw_filter_map(self._ctx, ptr(m, I32P), int(m.size)))
+
+    @property
+    def cw_filter_map(self):
+        """the CW filter map as an int32 array [n_channels] (a copy), or None with no map set"""
+        m = np.zeros(self.n_channels, np.int32)
+        return m if value(self._lib.t41rx_get_cw_filter_map(self._ctx, ptr(m, I32P), self.n_channels)) > 0 else None
 
     def set_cw_detector(self, on, max_frames=1):
         """decoderFlag (DoCWReceiveProcessing(), CWProcessing.cpp:322-373).  on = 1 allocates and returns the result
