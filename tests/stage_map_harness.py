@@ -22,9 +22,10 @@ EQ, NR, NB, DET, DEC, ALL = 1, 2, 4, 8, 16, 31
 SENT_F, SENT_I = -7777.25, 0x5A5A5A5A
 SECTION_OF = {EQ: "eq", NR: "nr", NB: "nb", DET: "cw", DEC: "cwdec"}
 # the checkpoint's sections in bit order with their words per channel (rx_state.cpp: kSections; nr_kernels.hpp,
-# nb_kernels.hpp, eq_kernels.hpp, cw_kernels.hpp); the display section (bit 2) is not carried by these tests' contexts
+# nb_kernels.hpp, eq_kernels.hpp, cw_kernels.hpp; the display section, bit 2, is rx_internal.hpp's kDispFloats and is carried
+# while the display spectrum is on: tests/test_batch_isolation.py's tap cases)
 ANR_ROWS, NR_SPEC = 64 + 79 + 2, 3 * 128 + 15 * 128 + 9 * 128 + 8
-SECTIONS = ((1, "nr", ANR_ROWS + NR_SPEC), (4, "nb", 16), (8, "eq", 112), (16, "cw", 128), (32, "cwdec", 3104))
+SECTIONS = ((1, "nr", ANR_ROWS + NR_SPEC), (2, "disp", 64 + 1024 + 512), (4, "nb", 16), (8, "eq", 112), (16, "cw", 128), (32, "cwdec", 3104))
 
 
 def sections(rx, buf=None):
@@ -33,7 +34,6 @@ def sections(rx, buf=None):
     buf = rx.get_state() if buf is None else buf
     nch, hdr = rx.n_channels, buf[:32].view(np.int32)
     per, sec = int(hdr[4]), int(hdr[5])
-    assert not sec & 2, "a display section: not one of these tests' contexts"
     off = 32 + 4 * per * nch
     out = {"path": buf[32:off].view(np.uint32).reshape(nch, per)}
     for bit, name, k in SECTIONS:

@@ -269,3 +269,112 @@ def test_interp_is_the_oracles_two_interpolators(built):
     lib.t41o_fir_interpolate_f32(c.int1, 48, 2, O.fptr(st1), O.fptr(x), O.fptr(mid), 4 * D)
     lib.t41o_fir_interpolate_f32(c.int2, 32, 4, O.fptr(st2), O.fptr(mid), O.fptr(hi), 8 * D)
     assert np.array_equal(hi * scale, want)
+
+
+# ---- the batch-isolation engine (tests/batch_harness.py) on stub chains ----------------------------------------------------
+class BatchStub:
+    """a case of the engine whose chain is numpy: channel c's audio is a function of its own rows, its NCO and its own
+    earlier state, and its record holds its last sample -- or, with a fault, not quite"""
+    L, schedule, dagger, env = 8, (2, 3), True, None
+
+    def __init__(self, fault=None):
+        self.fault = fault
+
+    def signal(self, rows, nfr, seed, nco):
+        rng = np.random.default_rng([seed, 12])
+        return tuple((0.05 * rng.standard_normal((rows, nfr * self.L))).astype(np.float32) for _ in range(2))
+
+    def open(self, T, comp, nco):
+        assert T is None and nco.shape == (comp.nch,)
+        return BatchStubChain(self.fault, comp.nch, nco)
+
+
+class BatchStubChain:
+    def __init__(self, fault, nch, nco):
+        self.fault, self.nch, self.nco = fault, nch, nco
+        self.state = np.zeros((nch, 3), np.float32)
+
+    def call(self, I, Q, nfr):
+        assert I.shape == Q.shape == (self.nch, nfr * BatchStub.L)
+        n, c = self.nch, np.arange(self.nch)
+        y = np.float32(0.5) * I + np.float32(0.25) * Q + (self.nco[:, None] * np.float32(1e-6) + self.state[:, :1])
+        if self.fault == "neighbour":  # 2**-20 of the left neighbour's sample
+            y[1:] += np.float32(2.0 ** -20) * I[:-1]
+        if self.fault == "mod16":  # the place in a group of 16
+            y += ((c % 16) * np.float32(2.0 ** -20))[:, None]
+        if self.fault == "tail" and n % 4 == 1:  # the single channel of a ragged group of 4
+            y[-1] += np.float32(2.0 ** -20)
+        if self.fault == "big tail" and n % 4 == 1 and n > 64:  # the same, in batches of more than one group of 64 only
+            y[-1] += np.float32(2.0 ** -20)
+        if self.fault == "zero":
+            y[:] = 0
+        self.state[:, 0], self.state[:, 1] = y[:, -1], I[:, 0]
+        if self.fault == "record":  # the audio is clean: only a record holds the neighbour's value
+            self.state[1:, 2] = I[:-1, -1]
+        return {"audio": y.astype(np.float32), "tap": (y * np.float32(2)).astype(np.float32)}
+
+    def records(self):
+        return {"path": self.state.copy()}
+
+
+def test_batch_engine_compositions():
+    import batch_harness as B
+    comps = {c.name: c for c in B.compositions(True)}
+    assert sorted(comps) == ["A", "B", "C", "D", "one"] and "D" not in [c.name for c in B.compositions(False)]
+    assert B.POS == (0, 3, 4, 15, 16, 17, 63, 64, 66) and (comps["B"].nch, comps["D"].nch, comps["A"].nch, comps["one"].nch) == (67, 65, 9, 1)
+    assert comps["A"].pos.tolist() == list(range(9))[::-1] and comps["B"].pos.tolist() == list(B.POS) == comps["C"].pos.tolist()
+    assert comps["D"].pos.tolist() == list(B.POS[:8]) + [-1] and comps["D"].pos.max() == 64  # the ragged tail is one probe
+    assert (comps["one"].pos >= 0).sum() == 1 and len(comps["B"].crowd) == 58 and len(comps["D"].crowd) == 57
+    assert not set(comps["B"].crowd) & set(B.POS)
+    # both sides of every grouping: a probe on the last channel of a group and one on the first of the next
+    for g in (4, 16, 64):
+        assert any(p % g == g - 1 and p + 1 in B.POS for p in B.POS), g
+    # the crowd: a third of each class, rotated in C; full scale, exact silence, the signal class loud and clipped
+    case = BatchStub()
+    I, Q, nco = B.crowd_rows(case, 5, 1, 0)
+    cls = B.crowd_class(0)
+    assert sorted(np.bincount(cls)) == [19, 19, 20] and (B.crowd_class(1) != cls).all()
+    assert (np.abs(I[cls == B.FULL]) == np.float32(0.999)).all() and len(np.unique(I[cls == B.FULL])) == 2
+    assert not I[cls == B.SILENT].any() and not Q[cls == B.SILENT].any()
+    loud = I[cls == B.LOUD]
+    assert np.abs(loud).max() == np.float32(0.999) and 0.2 < np.abs(loud).mean() < 0.6 and I.dtype == np.float32
+    assert not np.array_equal(nco, B.crowd_rows(case, 5, 2, 1)[2])
+
+
+def test_batch_engine_passes_a_per_channel_chain():
+    import batch_harness as B
+    got = B.run_composition(None, BatchStub())
+    assert sorted(got) == ["A", "B", "C", "D", "one"] and len(got["B"]) == 2
+    assert sorted(got["B"][0]) == ["audio", "record:path", "tap"] and sorted(got["B"][0]["audio"]) == list(range(9))
+    assert sorted(got["D"][1]["audio"]) == list(range(8)) and sorted(got["one"][1]["audio"]) == [B.ONE]
+    assert got["B"][1]["audio"][3].dtype == np.uint32 and got["B"][1]["audio"][3].shape == (3 * BatchStub.L,)
+
+
+@pytest.mark.parametrize("fault,where", [
+    ("neighbour", "B vs C: audio of probe 1 "), ("mod16", "A vs B: audio of probe 0 "), ("record", "B vs C: record:path of probe 1 "),
+    ("tail", "A vs B: audio of probe 0 "), ("big tail", r"B vs D: audio of probe 7 \(channel 64 of 67\)"), ("zero", "audio is all zero")])
+def test_batch_engine_fails_a_leaking_chain(fault, where):
+    import batch_harness as B
+    with pytest.raises(AssertionError, match=where):
+        B.run_composition(None, BatchStub(fault))
+
+
+def test_batch_engine_wants_crowds_that_differ():
+    import batch_harness as B
+
+    class Deaf(BatchStub):  # the crowd's audio does not follow its rows: equal probes would prove nothing
+        def open(self, T, comp, nco):
+            ch = BatchStubChain(None, comp.nch, nco)
+            inner = ch.call
+            probes = comp.pos[comp.pos >= 0]
+
+            def call(I, Q, nfr):
+                out = inner(I, Q, nfr)
+                keep = out["audio"][probes].copy()
+                out["audio"][:] = 1
+                out["audio"][probes] = keep
+                return out
+            ch.call = call
+            return ch
+    with pytest.raises(AssertionError, match="the crowd's audio is the same in B and C"):
+        B.run_composition(None, Deaf())
