@@ -499,12 +499,55 @@ T41RX_API int t41rx_get_stage_map(const t41rx_ctx *ctx, uint32_t *stages_of_chan
  *
  * Both maps are configuration, like the stage map: they are in no checkpoint, survive t41rx_reset, t41rx_set_state,
  * t41rx_set_params and t41rx_set_coeffs, and may change between any two calls.  t41rx_state_bytes() and every
- * checkpoint section are what they are without a map.  Still per context: nrOptionSelect and the notch, FT8, the
- * panadapter and the beacon monitor; parameter sets and the chain-splitting stages go on refusing each other. */
+ * checkpoint section are what they are without a map.  nrOptionSelect and the notch have a map of their own
+ * (t41rx_set_nr_map, below).  Still per context: FT8, the panadapter and the beacon monitor; parameter sets and the
+ * chain-splitting stages go on refusing each other. */
 T41RX_API int t41rx_set_cw_filter_map(t41rx_ctx *ctx, const int32_t *filter_of_channel, int n);  /* NULL, 0: remove */
 T41RX_API int t41rx_get_cw_filter_map(const t41rx_ctx *ctx, int32_t *filter_of_channel_out, int n);
 T41RX_API int t41rx_set_receive_eq_map(t41rx_ctx *ctx, const int32_t *equalizerRec, int n);  /* [n][14]; NULL, 0: remove */
 T41RX_API int t41rx_get_receive_eq_map(const t41rx_ctx *ctx, int32_t *equalizerRec_out, int n);
+
+/* ---- receiver groups: the noise-reduction kind and the notch per channel (ABI 5) ----
+ * The stage map's T41RX_STAGE_NR bit says on which channels "the noise reduction" runs; which of the four functions --
+ * Kim1_NR(), SpectralNoiseReduction(), Xanr() as LMS noise reduction, Xanr() as the automatic notch -- was one value for
+ * the whole context (params.nrOptionSelect, params.ANR_notchOn).  This map gives each channel its own two values.  New
+ * entry points: no call above changes what it does, and a context that sets no map launches what it always launched.
+ * The rule: while a map is loaded, channel c is processed exactly as the same channel of a context without a map whose
+ * parameters carry nrOptionSelect = nr_of_channel[c] (0 .. 3) and ANR_notchOn = notch_of_channel[c] (0 / 1).  That covers
+ * the channel's audio row, Xanr()'s record, the Kim / spectral record and every other state word, bit for bit -- the
+ * firmware's stale statics when a channel's kind changes between two calls included: the spectral function leaves
+ * NR_X[.][1..2] and NR_E alone and Kim1_NR() then starts from them; LMS and notch share one Xanr() record.  The context's
+ * own nrOptionSelect / ANR_notchOn are kept, are not consulted while a map is loaded, and are still what
+ * t41rx_get_params() returns; removing the map returns to them.  NR_alpha, NR_beta, NR_PSI and the VAD range from FLoCut /
+ * FHiCut stay those of the context for every channel.  A function runs on channel c when its map entry asks for it and
+ * either no stage map is loaded or the channel's T41RX_STAGE_NR bit is set; a channel with 0 / 0, or with the bit clear,
+ * is processed as the stage map processes a channel whose bit is clear: audio not touched, both records as they were.
+ * How a call runs it: one launch serves the Kim and the spectral channels, each workgroup reading its channel and its kind
+ * from a list, and one launch behind it serves Xanr() -- LMS only, notch only, LMS then notch -- from a list sorted by
+ * those three classes, so a mixed call costs about the longest of the serial chains, not their sum.  A launch whose list
+ * is empty is not made.  "Noise reduction on" is "some entry of the map is non-zero": an all-zero map launches what a
+ * context with nrOptionSelect 0 and ANR_notchOn 0 launches; a map with a non-zero entry hands over to the stage scratch
+ * even if the stage map lists nobody.
+ * The CW detector's one-audio-stream rule (a process call with the detector on refuses Kim or LMS noise reduction without
+ * the notch or the blanker behind it) is evaluated per channel with the channel's own two values while a map is loaded:
+ * the call is refused if any channel trips it, and the text names the first such channel.
+ * t41rx_set_nr_map(): two host arrays of n == n_channels values.  NULL, NULL with n == 0 removes the map.  Everything is
+ *   checked on the host before anything changes, and a refused call leaves the previous map whole: n != n_channels, one
+ *   array NULL, an entry outside 0 .. 3 or 0 .. 1 (the text names the channel) return T41RX_ERR_ARG; fft_length != 512
+ *   returns T41RX_ERR_UNSUPPORTED; a map with an entry 2 while the context's pass band fails the spectral function's
+ *   array-bounds check returns what t41rx_set_params() returns for nrOptionSelect = 2 there, with its text; a map with a
+ *   non-zero entry while parameter sets are loaded returns T41RX_ERR_UNSUPPORTED in the words of the chain-splitting
+ *   stages, and t41rx_set_param_sets() refuses a context with such a map.  An all-zero map stands next to parameter
+ *   sets.  While a map with an entry 2 is loaded t41rx_set_params() and t41rx_set_coeffs() refuse a pass band that fails
+ *   that check, and the previous parameters stay.  Synchronises the device, then uploads (the ordering rule of
+ *   t41rx_set_input_map).  Configuration, like the other maps: in no checkpoint, survives t41rx_reset, t41rx_set_state,
+ *   t41rx_set_params and t41rx_set_coeffs, may change between any two calls; t41rx_state_bytes() and every checkpoint
+ *   section are what they are without a map.  Composes with the input map, the output map, the stage map (set before or
+ *   after), the CW filter map, the level map, both audio rates, both layouts, f32 and q15, host and device entries.
+ * t41rx_get_nr_map(): returns 1 with a map loaded, 0 with none (negative: an error status).  The two outputs, n ==
+ *   n_channels entries each, receive the map, or the context's own values in every entry with none; either may be NULL. */
+T41RX_API int t41rx_set_nr_map(t41rx_ctx *ctx, const int32_t *nr_of_channel, const int32_t *notch_of_channel, int n);  /* NULL, NULL, 0: remove */
+T41RX_API int t41rx_get_nr_map(const t41rx_ctx *ctx, int32_t *nr_of_channel_out, int32_t *notch_of_channel_out, int n);
 
 /* ---- receiver groups: parameter sets, one t41rx_params per group of channels (ABI 5) ----
  * The receivers of one band differ in more than NCOFreq: the phone receivers are LSB at 2.8 kHz, the FT8 receiver is USB

@@ -126,6 +126,8 @@ SYMBOLS = {
     "t41rx_get_cw_filter": (C.c_int, [_vp]),
     "t41rx_set_cw_filter_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int]),
     "t41rx_get_cw_filter_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int]),
+    "t41rx_set_nr_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
+    "t41rx_get_nr_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]),
     "t41rx_set_cw_detector": (C.c_int, [_vp, C.c_int, _vp, C.c_int]),
     "t41rx_get_cw_detector": (C.c_int, [_vp]),
     "t41rx_set_cw_decode_tree": (C.c_int, [_vp, _vp, C.c_int]),

@@ -1,8 +1,21 @@
-// t41_sdr_amd/csrc/anr_kernel.inc -- the text of anr_kernel, included twice by nr_kernels.hip: T41_STAGE_KERNEL names the kernel,
-// T41_STAGE_LIST 0 makes the kernel as it is without a stage map, 1 its list form (t41rx_set_stage_map).  Two kernels
-// of one text, not one body shared by two kernels: an argument block handed on by reference compiles to another
+// t41_sdr_amd/csrc/anr_kernel.inc -- the text of anr_kernel, included three times by nr_kernels.hip: T41_STAGE_KERNEL names the kernel,
+// T41_STAGE_LIST 0 makes the kernel as it is without a stage map, 1 its list form (t41rx_set_stage_map), 2 the
+// noise-reduction map's form (t41rx_set_nr_map): the list form whose workgroups take their segment of the list and their
+// passes from the map's table.  Three kernels
+// of one text, not one body shared by three kernels: an argument block handed on by reference compiles to another
 // instruction stream, and the form without a map must stay the stream it was.
-__global__ __launch_bounds__(128, 2) void T41_STAGE_KERNEL(const NrArgs a) {
+// What the forms differ in, as the text below names it: the argument block, and which passes the workgroup runs -- for
+// forms 0 and 1 the launch's two switches, read where they are used, for form 2 the class of the workgroup's row.
+#if T41_STAGE_LIST == 2
+#define T41_ANR_ARGS NrMapArgs
+#define T41_ANR_LMS (wg.z != 1)    // (rx_nrmap.hpp: the classes LMS only 0, notch only 1, LMS then notch 2)
+#define T41_ANR_NOTCH (wg.z != 0)
+#else
+#define T41_ANR_ARGS NrArgs
+#define T41_ANR_LMS (a.nr_option == 3)
+#define T41_ANR_NOTCH (a.notch)
+#endif
+__global__ __launch_bounds__(128, 2) void T41_STAGE_KERNEL(const T41_ANR_ARGS a) {
   // (The copy / scale loops below are kept rolled: fully unrolled, with every address hoisted out of the frame loop, they
   // took the kernel to 353 VGPRs; 161 now.  Measured at the end of round 4, all bit-identical to this form
   // (tools/anr_ab_check.py) and none faster than 1 %: no workgroup barrier per sample -- sigma through two slots guarded
@@ -21,9 +34,15 @@ __global__ __launch_bounds__(128, 2) void T41_STAGE_KERNEL(const NrArgs a) {
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // 0: filter output and update, 1: sum of squares
   const int c = lane & 15, g = lane >> 4, tb = anr_tap_base(g);
+#if T41_STAGE_LIST == 2
+  const int4 wg = a.rows[blockIdx.x];  // {offset into the list, live columns 1 .. 16, class}: uniform, one scalar load
+  const int ch0 = wg.x;
+  const int nlive = wg.y;
+#else
   const int ch0 = blockIdx.x * kAnrCw;
   const int nserved = LIST ? a.nlist : a.nchan;
   const int nlive = (nserved - ch0 < kAnrCw) ? nserved - ch0 : kAnrCw;
+#endif
   const int col = ch0 + (c < nlive ? c : nlive - 1);  // dead lanes shadow the last live channel (their stores are skipped)
   const int ch = LIST ? a.list[col] : col;            // (a list: the last LISTED channel of the workgroup)
   const size_t nch = (size_t)a.nchan;
@@ -52,12 +71,12 @@ _Pragma("nounroll")
       for (int q = 0; q < 4; ++q) T[(kAnrHist + lane + 64 * q) * kAnrRow + cc] = 0.0f;
     }
     __syncthreads();
-    if (a.nr_option == 3) {  // Process.cpp:852-857: Xanr() as noise reduction; its result stays in float_buffer_R, float_buffer_L is scaled by 1.5
+    if (T41_ANR_LMS) {  // Process.cpp:852-857: Xanr() as noise reduction; its result stays in float_buffer_R, float_buffer_L is scaled by 1.5
       if (wv == 0) anr_pass_y<false>(T, nullptr, SIG, w, lidx, ngamma, lane);
       else anr_pass_sigma(T, SIG, lane);
       __syncthreads();
       if (wv == 0) {
-        if (a.notch) {
+        if (T41_ANR_NOTCH) {
           // the notch pass sees the scaled block behind the unscaled one: its delay line = the last 79 unscaled samples
           _Pragma("unroll 4") for (int r = g; r < kAnrHist; r += 4) T[r * kAnrRow + c] = T[(256 + r) * kAnrRow + c];
           __builtin_amdgcn_wave_barrier();
@@ -68,7 +87,7 @@ _Pragma("nounroll")
       }
       __syncthreads();
     }
-    if (a.notch) {  // Process.cpp:862-866
+    if (T41_ANR_NOTCH) {  // Process.cpp:862-866
       if (wv == 0) anr_pass_y<true>(T, O, SIG, w, lidx, ngamma, lane);
       else anr_pass_sigma(T, SIG, lane);
       __syncthreads();
@@ -97,3 +116,6 @@ _Pragma("nounroll")
     }
   }
 }
+#undef T41_ANR_ARGS
+#undef T41_ANR_LMS
+#undef T41_ANR_NOTCH

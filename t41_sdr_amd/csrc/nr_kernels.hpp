@@ -59,4 +59,17 @@ struct NrArgs {
 };
 hipError_t launch_nr(const NrArgs &a, hipStream_t s);
 
+// The noise-reduction map (t41rx_set_nr_map; rx_nrmap.hpp makes the lists): nrOptionSelect and ANR_notchOn per channel.
+// NrArgs as it is -- nr_option and notch are not read, list / nlist are the Xanr() list -- and behind it what the two map
+// kernels read through uniform indices.  A block of its own, so that NrArgs and the kernels that take it stay what they were.
+struct NrMapArgs : NrArgs {
+  const int *spec_list;  // [nspec] the channels Kim1_NR() or SpectralNoiseReduction() runs on, ascending
+  const int *spec_kind;  // [nspec] 1 or 2
+  int nspec;
+  const int4 *rows;      // [nrows] a workgroup of anr_map_kernel: {offset into list, live columns 1 .. 16, class, -}
+  int nrows;
+};
+// nrspec_map_kernel over the spectral list, then anr_map_kernel over the rows; nothing for an empty list
+hipError_t launch_nr_map(const NrMapArgs &a, hipStream_t s);
+
 }  // namespace t41

@@ -81,6 +81,7 @@ int ensure_nr(t41rx_ctx *ctx) {
 
 // Process.cpp:841-866 behind the equalizer
 int nr_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
+  if (ctx->nr.map_on) return nr_map_run(ctx, n_frames, s);  // the noise-reduction map: every channel its own two values (rx_nrmap.cpp)
   const StageList l = stage_list(ctx, kStageNr);
   if (l.empty()) return T41RX_OK;  // the stage map lists no channel: nothing to launch
   NrArgs n{};

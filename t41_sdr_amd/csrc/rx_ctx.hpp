@@ -25,6 +25,7 @@
 #include "rx_experiments.hpp"
 #include "rx_internal.hpp"
 #include "rx_kernels.hpp"
+#include "rx_nrmap.hpp"
 #include "rx_stagemap.hpp"
 #include "rx_stageparams.hpp"
 
@@ -38,6 +39,14 @@ namespace t41 {
 // allocated when a call first needs them
 struct NrStage {
   DevBuf<float> d_anr, d_spec, d_tab;
+  // the noise-reduction map (t41rx_set_nr_map; rx_nrmap.cpp): nrOptionSelect and ANR_notchOn per channel, the lists made
+  // of them and of the stage map (rx_nrmap.hpp), and their device copy (nr_map_layout()).  Configuration like the stage
+  // map: in no checkpoint, untouched by reset / set_state / set_params.  map_on == false: every channel takes the
+  // context's params.nrOptionSelect / params.ANR_notchOn.
+  bool map_on = false;
+  std::vector<int32_t> kind_map, notch_map;  // [nchan] each (host)
+  NrMapLists lists;
+  DevBuf<int32_t> d_map;                     // allocated with the first map
 };
 
 // noise blanker (NB_on, Process.cpp:873-876; t41rx_set_noise_blanker): AltNoiseBlanking()'s last_frame_end per channel,
@@ -312,7 +321,10 @@ inline int hip_check(hipError_t e, const char *what) { return e == hipSuccess ? 
 // ---- which stages a process call runs.  These are the switches; which kernels a call runs with them -- the tap kernels,
 // the hand-over, the scratch, the pipelined forms, the back end -- is decided once per call by plan_call() (rx_plan.hpp),
 // from the CallFacts the process call fills with these predicates (rx_host.cpp: call_facts)
-inline bool nr_on(const t41rx_ctx *ctx) { return ctx->params.nrOptionSelect != 0 || ctx->params.ANR_notchOn != 0; }  // (fft_length 512: params_valid)
+// (a noise-reduction map, t41rx_set_nr_map: on when some entry of the map is non-zero; the context's two values are not consulted)
+inline bool nr_on(const t41rx_ctx *ctx) {
+  return ctx->nr.map_on ? ctx->nr.lists.any : ctx->params.nrOptionSelect != 0 || ctx->params.ANR_notchOn != 0;  // (fft_length 512: params_valid)
+}
 // the CW block runs in T41State == CW_RECEIVE (Process.cpp:878), which in receive is xmtMode == CW_MODE
 // (T41_SDR.ino:1039-1040, 1144-1148); with another xmtMode the switches are kept and nothing runs
 // (a filter map, t41rx_set_cw_filter_map: the narrow filter runs when some channel has an index; the context's is not consulted)
@@ -325,13 +337,16 @@ inline bool cw_dec_on(const t41rx_ctx *ctx) { return cw_det_on(ctx) && ctx->cw.d
 // parameter sets: loaded, and what a chain-splitting stage's switch answers then (those stages read set 0's parameters
 // on the host; rx_sets.cpp refuses in the other order with split_stage_on())
 inline bool sets_loaded(const t41rx_ctx *ctx) { return !ctx->sets.params.empty(); }
+constexpr const char *kNrMapStageName = "the noise reduction / notch of a noise-reduction map";
 inline int sets_refuse_stage(const char *stage) {
   return fail(T41RX_ERR_UNSUPPORTED, std::string(stage) + " splits the fused chain and reads one parameter set on the host: it cannot run "
                                          "while parameter sets are loaded (t41rx_set_param_sets); remove the sets first");
 }
-// the chain-splitting stage whose switch is on, or null (the noise reduction / notch are parameters: the sets' rule has them)
+// the chain-splitting stage whose switch is on, or null (the context-wide noise reduction / notch are parameters: the
+// sets' rule has them; a noise-reduction map with a non-zero entry is a switch of the context like the others)
 inline const char *split_stage_on(const t41rx_ctx *ctx) {
   return ctx->eq.on ? "the receive equalizer" : ctx->nb.on ? "the noise blanker"
+         : (ctx->nr.map_on && ctx->nr.lists.any) ? kNrMapStageName
          : (ctx->cw.filter != kCwFilters || (ctx->cw.map_on && !ctx->cw.lists.filtered.empty())) ? "the CW audio filter"
          : ctx->cw.det ? "the CW detector" : ctx->cw.dec ? "the CW decoder" : nullptr;
 }
@@ -412,7 +427,7 @@ int nb_reset(t41rx_ctx *ctx, size_t bytes);
 // rx_cw.cpp
 int ensure_cw(t41rx_ctx *ctx);
 int ensure_cw_decode(t41rx_ctx *ctx);
-const char *cw_split_stage(const t41rx_ctx *ctx);
+const char *cw_split_stage(const t41rx_ctx *ctx, int *channel);  // (*channel: with a noise-reduction map the first channel that trips it, else -1)
 int cw_detect_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
 int cw_decode_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
 int cw_filter_run(t41rx_ctx *ctx, const CallPlan &plan, const RxArgs &a, int n_frames, hipStream_t s);  // the narrow filter and its back end
@@ -420,6 +435,11 @@ int check_cw_decode(const t41rx_ctx *ctx, const int32_t *hdr, const float *sec);
 int cw_decode_reset(t41rx_ctx *ctx, size_t bytes);
 // rx_stageparams.cpp: the filter map's row maps again, behind a change of the output map (no map loaded: nothing)
 int cw_filter_map_refresh(t41rx_ctx *ctx);
+// rx_nrmap.cpp: the noise-reduction map's launches of a call (nr_run() with a map loaded); its lists again, behind a change
+// of the stage map (no map loaded: nothing); and the new parameters of t41rx_set_params / _set_coeffs against a loaded map
+int nr_map_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
+int nr_map_refresh(t41rx_ctx *ctx);
+int nr_map_check_params(const t41rx_ctx *ctx, const t41rx_params &p);
 // rx_ft8.cpp
 int ft8_prepare(t41rx_ctx *ctx, const CallPlan &plan, int n_frames, hipStream_t s);  // the call's refusals, the memory and the demod tap of its own
 int ft8_run(t41rx_ctx *ctx, const CallPlan &plan, const RxArgs &a, int n_frames, hipStream_t s);

@@ -78,11 +78,25 @@ int check_cw_decode(const t41rx_ctx *c, const int32_t *, const float *sec) {
 // Kim1_NR() and SpectralNoiseReduction() end with R = L (Noise.cpp:307-308, 636-637) but x30 behind Kim scales L only
 // (Process.cpp:846), Xanr() writes R only and x1.5 behind it scales L only (Noise.cpp:345-347, Process.cpp:855); the
 // notch and the blanker end in arm_copy_f32(R, L) (Process.cpp:865, 875), which joins them again.
-const char *cw_split_stage(const t41rx_ctx *ctx) {
-  if (ctx->params.ANR_notchOn != 0 || ctx->nb.on) return nullptr;
-  if (ctx->params.nrOptionSelect == 1) return "Kim noise reduction (nrOptionSelect 1)";
-  if (ctx->params.nrOptionSelect == 3) return "LMS noise reduction (nrOptionSelect 3)";
-  if (ctx->eq.on && ctx->params.nrOptionSelect == 0) return "receive equalizer";
+namespace {
+const char *cw_split_stage_of(const t41rx_ctx *ctx, int nrOptionSelect, int ANR_notchOn) {
+  if (ANR_notchOn != 0 || ctx->nb.on) return nullptr;
+  if (nrOptionSelect == 1) return "Kim noise reduction (nrOptionSelect 1)";
+  if (nrOptionSelect == 3) return "LMS noise reduction (nrOptionSelect 3)";
+  if (ctx->eq.on && nrOptionSelect == 0) return "receive equalizer";
+  return nullptr;
+}
+}  // namespace
+// With a noise-reduction map (t41rx_set_nr_map) the rule is each channel's, with the channel's own two values in place of
+// the context's: the first channel that trips it, in *channel.
+const char *cw_split_stage(const t41rx_ctx *ctx, int *channel) {
+  *channel = -1;
+  if (!ctx->nr.map_on) return cw_split_stage_of(ctx, ctx->params.nrOptionSelect, ctx->params.ANR_notchOn);
+  for (int c = 0; c < ctx->nchan; ++c)
+    if (const char *stage = cw_split_stage_of(ctx, ctx->nr.kind_map[(size_t)c], ctx->nr.notch_map[(size_t)c])) {
+      *channel = c;
+      return stage;
+    }
   return nullptr;
 }
 

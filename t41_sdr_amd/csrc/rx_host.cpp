@@ -261,6 +261,7 @@ namespace {
 CallFacts call_facts(const t41rx_ctx *ctx, int n_frames, bool q15) {
   SetGains g;
   CallFacts f = params_facts(ctx->params, gains_of(blob_view(const_cast<float *>(ctx->blob.data())).scalars, g));
+  f.nr = nr_on(ctx);  // (a noise-reduction map: some entry non-zero)
   f.q15 = q15;
   f.n_frames = n_frames;
   f.seg_run_set = ctx->seg_run_set;
@@ -334,9 +335,11 @@ int prepare_call(t41rx_ctx *ctx, const CallPlan &plan, int n_frames, hipStream_t
     return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the CW decoder's buffer was set with");
   if (cw_det_on(ctx) && n_frames > ctx->cw.frames)
     return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the CW detector's buffer was set with");
+  int split_ch = -1;
   if (cw_det_on(ctx))
-    if (const char *stage = cw_split_stage(ctx))
+    if (const char *stage = cw_split_stage(ctx, &split_ch))
       return fail(T41RX_ERR_UNSUPPORTED, std::string("CW detector: the ") + stage +
+                                             (split_ch >= 0 ? " of channel " + std::to_string(split_ch) + " (noise-reduction map)" : std::string()) +
                                              " leaves float_buffer_L different from float_buffer_R and neither the notch nor the noise "
                                              "blanker joins them behind it; the library carries one audio stream");
   if (ctx->disp.spec && (!ctx->disp.d_pre || !ctx->disp.d_state || !ctx->d_win)) return fail(T41RX_ERR_STATE, "display spectrum enabled without its buffers");
@@ -703,6 +706,7 @@ int t41rx_set_params(t41rx_ctx *ctx, const t41rx_params *p) {
   if (!params_valid(*p, &why)) return fail(T41RX_ERR_ARG, why ? why : "bad params");
   if (p->fft_length != ctx->params.fft_length) return fail(T41RX_ERR_ARG, "fft_length cannot change on a live context");
   if (sets_loaded(ctx) && sets_check_set0(ctx, *p) != T41RX_OK) return T41RX_ERR_UNSUPPORTED;  // (the rule's text stands)
+  if (nr_map_check_params(ctx, *p) != T41RX_OK) return T41RX_ERR_ARG;  // (a noise-reduction map with an entry 2: the pass band's check)
 
   std::vector<float> nb(ctx->blob.size());
   int rc = design_blob(*p, nb.data(), nb.size() * sizeof(float));
@@ -747,6 +751,7 @@ int t41rx_set_coeffs(t41rx_ctx *ctx, const void *blob, size_t blob_bytes) {
   if (!params_valid(bp, &why) || bp.fft_length != h[2] || bp.mode != h[3])
     return fail(T41RX_ERR_STATE, std::string("blob parameters invalid: ") + (why ? why : "header mismatch"));
   if (sets_loaded(ctx) && sets_check_set0(ctx, bp) != T41RX_OK) return T41RX_ERR_UNSUPPORTED;  // (the rule's text stands)
+  if (nr_map_check_params(ctx, bp) != T41RX_OK) return T41RX_ERR_ARG;
 
   DeviceGuard g(ctx->device);
   HIP_TRY(hipDeviceSynchronize());

@@ -371,6 +371,35 @@ class RxChain:
         m = np.zeros(self.n_channels, np.int32)
         return m if value(self._lib.t41rx_get_cw_filter_map(self._ctx, ptr(m, I32P), self.n_channels)) > 0 else None
 
+    def set_nr_map(self, nr_of_channel, notch_of_channel=None):
+        """Receiver groups (t41rx_set_nr_map): nr_of_channel[c] is channel c's nrOptionSelect (0 off, 1 Kim, 2 spectral,
+        3 LMS) and notch_of_channel[c] its ANR_notchOn (0 / 1).  While the map is loaded channel c is processed exactly
+        as the same channel of a chain with CalcFilters(nrOptionSelect=nr_of_channel[c], ANR_notchOn=notch_of_channel[c])
+        would be: its audio, Xanr()'s record, the Kim / spectral record -- the stale statics of a kind that changes
+        between two calls included.  A function runs where the channel's entry asks for it and STAGE_NR is in the stage
+        map or no stage map is set; a channel with 0 / 0 is not touched.  The chain's own two values are kept, not
+        consulted, and still what params returns; NR_alpha, NR_beta, NR_PSI and the pass band stay the chain's.
+        set_nr_map(None) removes the map.  A non-zero entry cannot stand next to parameter sets; an entry 2 needs a pass
+        band the spectral function accepts.  Configuration, like the stage map: in no checkpoint, kept across reset() /
+        set_state() / CalcFilters(); FFT_LENGTH 512."""
+        if nr_of_channel is None:
+            if notch_of_channel is not None:
+                raise ValueError("notch_of_channel goes with nr_of_channel: pass both, or None to remove the map")
+            check(self._lib.t41rx_set_nr_map(self._ctx, None, None, 0))
+            return
+        if notch_of_channel is None:
+            raise ValueError("notch_of_channel must be given with nr_of_channel: n_channels=%d values 0 / 1" % self.n_channels)
+        k = int_table(nr_of_channel, np.int32, None, "nr_of_channel must be a 1-d array of n_channels nrOptionSelect values (0 .. 3), got %r %s")
+        t = int_table(notch_of_channel, np.int32, (int(k.size),), "notch_of_channel must be a 1-d array of ANR_notchOn values (0 / 1) as long as nr_of_channel, got %r %s")
+        check(self._lib.t41rx_set_nr_map(self._ctx, ptr(k, I32P), ptr(t, I32P), int(k.size)))
+
+    @property
+    def nr_map(self):
+        """the noise-reduction map as two int32 arrays [n_channels] (copies), (nr_of_channel, notch_of_channel), or None
+        with no map set"""
+        k, t = np.zeros(self.n_channels, np.int32), np.zeros(self.n_channels, np.int32)
+        return (k, t) if value(self._lib.t41rx_get_nr_map(self._ctx, ptr(k, I32P), ptr(t, I32P), self.n_channels)) > 0 else None
+
     def set_cw_detector(self, on, max_frames=1):
         """decoderFlag (DoCWReceiveProcessing(), CWProcessing.cpp:322-373).  on = 1 allocates and returns the result
         tensor, float32 CUDA [n_channels, max_frames, 4]; a process call of n <= max_frames frames fills its first
