@@ -429,7 +429,8 @@ T41RX_API int t41rx_audio_rows(const t41rx_ctx *ctx);
  * on hands over to the stage scratch even if that stage lists no channel); the narrow CW filter (t41rx_set_cw_filter)
  * stays a switch of the context -- it selects the call's back kernel, whose operation order differs from the other's, so
  * a filter per channel would need two back ends per call --; FT8 receive, the panadapter, the beacon monitor, the side
- * outputs and the stage taps stay context-wide; parameter sets and the chain-splitting stages go on refusing each other.
+ * outputs and the stage taps stay context-wide; the refusal between parameter sets and the chain-splitting stages
+ * stands for sets loaded without T41RX_SETS_STAGES (t41rx_set_param_sets_ex).
  * The map composes with the input map, the output map, both audio rates, both layouts, f32 and q15, and the host and
  * device entries: none of them sees it.
  * The map is configuration, like the output map: it is in no checkpoint, survives t41rx_reset, t41rx_set_state,
@@ -500,8 +501,8 @@ T41RX_API int t41rx_get_stage_map(const t41rx_ctx *ctx, uint32_t *stages_of_chan
  * Both maps are configuration, like the stage map: they are in no checkpoint, survive t41rx_reset, t41rx_set_state,
  * t41rx_set_params and t41rx_set_coeffs, and may change between any two calls.  t41rx_state_bytes() and every
  * checkpoint section are what they are without a map.  nrOptionSelect and the notch have a map of their own
- * (t41rx_set_nr_map, below).  Still per context: FT8, the panadapter and the beacon monitor; parameter sets and the
- * chain-splitting stages go on refusing each other. */
+ * (t41rx_set_nr_map, below).  Still per context: FT8, the panadapter and the beacon monitor; the refusal between parameter
+ * sets and the chain-splitting stages stands for sets loaded without T41RX_SETS_STAGES (t41rx_set_param_sets_ex). */
 T41RX_API int t41rx_set_cw_filter_map(t41rx_ctx *ctx, const int32_t *filter_of_channel, int n);  /* NULL, 0: remove */
 T41RX_API int t41rx_get_cw_filter_map(const t41rx_ctx *ctx, int32_t *filter_of_channel_out, int n);
 T41RX_API int t41rx_set_receive_eq_map(t41rx_ctx *ctx, const int32_t *equalizerRec, int n);  /* [n][14]; NULL, 0: remove */
@@ -594,6 +595,44 @@ T41RX_API int t41rx_get_nr_map(const t41rx_ctx *ctx, int32_t *nr_of_channel_out,
 T41RX_API int t41rx_set_param_sets(t41rx_ctx *ctx, const t41rx_params *sets, int n_sets, const int32_t *set_of_channel, int n);
 T41RX_API int t41rx_get_param_sets(const t41rx_ctx *ctx, t41rx_params *sets_out, int cap, int32_t *set_of_channel_out, int n);
 T41RX_API int t41rx_param_sets_compatible(const t41rx_params *a, const t41rx_params *b);
+
+/* ---- receiver groups: parameter sets next to the chain-splitting stages (ABI 5) ----
+ * The refusals above stand for sets loaded without T41RX_SETS_STAGES.  Sets loaded through t41rx_set_param_sets_ex() with
+ * that flag ("staged sets") run next to the receive equalizer, noise reduction / notch, the noise blanker, the narrow CW
+ * filter, the CW detector and the CW decoder.  New entry points: flags == 0 is t41rx_set_param_sets() /
+ * t41rx_param_sets_compatible() word for word (those are this call with flags 0), an unknown flag bit returns
+ * T41RX_ERR_ARG, and t41rx_get_param_sets() returns staged sets as ever.
+ * The rule: channel c is processed exactly as the same channel of a context created with sets[set_of_channel[c]] and
+ * carrying the same stage switches, stage map, CW filter map, equalizer level map, noise-reduction map, output map, input
+ * map, audio rate and layout: audio, side outputs, taps, the detector's and the decoder's rows and every state record, bit
+ * for bit; f32 and q15, both layouts, host and device entries, 192 and 24 kS/s.
+ * The compatibility rule under the flag keeps every clause except "both 0" on nrOptionSelect / ANR_notchOn; xmtMode
+ * stays equal, so the CW block runs for all sets or for none.  Without a noise-reduction map a channel takes its own
+ * set's nrOptionSelect and ANR_notchOn; with a map the map supplies the two, as it overrides the context's without sets.
+ * Either way the channel takes its own set's NR_alpha, NR_beta, NR_PSI and the VAD range of its own pass band.  Under
+ * staged sets the noise reduction always runs through the map's two launches, over lists made of the effective values.
+ * The narrow CW filter's interpolators take the volume and the taps of the channel's own set.
+ * The spectral function's array-bounds check (t41rx_set_params with nrOptionSelect = 2) is made per channel against the
+ * channel's own set, by every setter that can break it -- this one, t41rx_set_nr_map(), and t41rx_set_params() /
+ * t41rx_set_coeffs() for set 0: T41RX_ERR_ARG, the text names the channel and the set, and everything stays as it was.
+ * A set whose own nrOptionSelect is 2 and whose pass band fails the check is an invalid t41rx_params and is refused as
+ * such (T41RX_ERR_ARG, "set i is invalid") whether a channel names it or not; a set with another kind and such a pass
+ * band is accepted as long as no channel runs kind 2 on it.
+ * Setter interplay: the stage setters and the two maps (t41rx_set_cw_filter_map with an entry < 5, t41rx_set_nr_map with a
+ * non-zero entry) accept while staged sets are loaded, and staged sets load while those stages are on.
+ * t41rx_set_param_sets() called while a stage is on refuses as ever and leaves loaded staged sets in place; sets loaded
+ * without the flag followed by a stage setter refuse as ever.  The CW detector's one-audio-stream rule is evaluated per
+ * channel with the channel's effective kind and notch; the refusal names the first offending channel.  Still refused, in
+ * the words above: the long fft_lengths, and FT8 receive on a non-USB set.  The panadapter, the beacon monitor and the
+ * side outputs stay context-wide and work with staged sets as with plain ones.
+ * flags is an int32_t holding T41RX_SETS_* bits (the scalar types of this header are int, int32_t, int64_t, size_t and
+ * float); a negative value has unknown bits set.
+ * t41rx_get_param_sets_flags(): the flags of the loaded sets; 0 with none or with sets loaded without a flag
+ *   (negative: an error status). */
+#define T41RX_SETS_STAGES 1u
+T41RX_API int t41rx_set_param_sets_ex(t41rx_ctx *ctx, const t41rx_params *sets, int n_sets, const int32_t *set_of_channel, int n, int32_t flags);
+T41RX_API int t41rx_get_param_sets_flags(const t41rx_ctx *ctx);
+T41RX_API int t41rx_param_sets_compatible_ex(const t41rx_params *a, const t41rx_params *b, int32_t flags);
 
 /* ---- the hot path: ProcessIQData() on every channel ----
  * Device-pointer form: dI, dQ, dAudio are device pointers ([n_channels][n_frames*frame_len], or time-major:

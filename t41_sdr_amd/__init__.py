@@ -6,7 +6,7 @@ creating an RxChain does.
 """
 from ._lib import (DEMOD_AM, DEMOD_LSB, DEMOD_NFM, DEMOD_SAM, DEMOD_USB, LIB_PATH, Params, T41RxError,  # noqa: F401
                    load)
-from ._lib import STAGE_ALL, STAGE_CW_DECODE, STAGE_CW_DETECT, STAGE_EQ, STAGE_NB, STAGE_NR  # noqa: F401
+from ._lib import SETS_STAGES, STAGE_ALL, STAGE_CW_DECODE, STAGE_CW_DETECT, STAGE_EQ, STAGE_NB, STAGE_NR  # noqa: F401
 from .rx import RxChain, blob_fields, blob_params, default_params, design_coeffs, ft8_tables, param_sets_compatible  # noqa: F401
 from . import beacon  # noqa: F401
 from . import ft8  # noqa: F401

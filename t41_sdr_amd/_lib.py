@@ -22,6 +22,7 @@ SSB_MODE, CW_MODE, DATA_MODE = 0, 1, 2
 # the bits of a channel's mask in the stage map (T41RX_STAGE_*, t41rx_set_stage_map)
 STAGE_EQ, STAGE_NR, STAGE_NB, STAGE_CW_DETECT, STAGE_CW_DECODE = 1, 2, 4, 8, 16
 STAGE_ALL = 31
+SETS_STAGES = 1  # T41RX_SETS_STAGES: parameter sets loaded next to the chain-splitting stages (t41rx_set_param_sets_ex)
 
 
 class Params(C.Structure):
@@ -104,6 +105,9 @@ SYMBOLS = {
     "t41rx_set_param_sets": (C.c_int, [_vp, C.POINTER(Params), C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "t41rx_get_param_sets": (C.c_int, [_vp, C.POINTER(Params), C.c_int, C.POINTER(C.c_int32), C.c_int]),
     "t41rx_param_sets_compatible": (C.c_int, [C.POINTER(Params), C.POINTER(Params)]),
+    "t41rx_set_param_sets_ex": (C.c_int, [_vp, C.POINTER(Params), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int32]),
+    "t41rx_get_param_sets_flags": (C.c_int, [_vp]),
+    "t41rx_param_sets_compatible_ex": (C.c_int, [C.POINTER(Params), C.POINTER(Params), C.c_int32]),
     "t41rx_process_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp]),
     "t41rx_process_host": (C.c_int, [_vp, _fp, _fp, _fp, C.c_int]),
     "t41rx_set_audio_spectrum": (C.c_int, [_vp, _vp, _vp, C.c_int]),

@@ -193,6 +193,68 @@ __global__ __launch_bounds__(64) void cw_back_omap_kernel(CwBackArgs a) {
   if (lane < P2 - 1) st[kStInt2 + 1 + lane] = s2[lane];
 }
 
+// The same with parameter sets next to the stages (t41rx_set_param_sets_ex with T41RX_SETS_STAGES): the text a third time,
+// with or without the output map's row, and the volume factor and the taps from entry set_of[channel] of the sets' table.
+// A block is one channel, so the set's number and the volume factor are scalar loads and the taps' rows are read from a
+// uniform base; every product and every sum is cw_back_kernel's, in its order (tests/test_stage_sets.py holds the rows to
+// that kernel's on a plain context of the channel's set, bit for bit).
+__global__ __launch_bounds__(64) void cw_back_sets_kernel(CwBackSetsArgs a) {
+#pragma clang fp contract(off)
+  constexpr int N = kCwBlock, P1 = 24, P2 = 8;
+  const int row = a.out_map ? a.out_map[blockIdx.x] : (int)blockIdx.x;
+  if (row < 0) return;  // block-uniform, ahead of every barrier
+  __shared__ float s1[P1 - 1 + N + 1];      // arm_fir_interpolate_f32's state of the x2 stage: history, then the block
+  __shared__ float s2[P2 - 1 + 2 * N + 1];  // ... of the x4 stage
+  __shared__ float c1[48], c2[32];
+  const int lane = threadIdx.x;
+  const CwSetBack *set = a.sets + a.set_of[blockIdx.x];
+  const float scale = set->scale;
+  float *st = a.state + (size_t)blockIdx.x * a.state_stride;
+  const float *x = a.aud + (size_t)blockIdx.x * a.nframes * N;
+  if (lane < 48) c1[lane] = set->int1[lane];
+  if (lane < 32) c2[lane] = set->int2[lane];
+  if (lane < P1 - 1) s1[lane] = st[kStInt1 + 1 + lane];
+  if (lane < P2 - 1) s2[lane] = st[kStInt2 + 1 + lane];
+  for (int f = 0; f < a.nframes; ++f) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) s1[P1 - 1 + lane + 64 * m] = x[(size_t)f * N + lane + 64 * m];
+    __syncthreads();
+    // x2: output 2 n + (j - 1) = sum_t state[n + t] * coeffs[(2 - j) + 2 t]
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int o = lane + 64 * k, n = o >> 1, c0 = 1 - (o & 1);
+      float acc = 0.0f;
+      for (int t = 0; t < P1; ++t) acc += s1[n + t] * c1[c0 + 2 * t];
+      s2[P2 - 1 + o] = acc;
+    }
+    const float h1 = lane < P1 - 1 ? s1[N + lane] : 0.0f;
+    __syncthreads();
+    if (lane < P1 - 1) s1[lane] = h1;
+    // x4: output 4 n + (j - 1) = sum_t state[n + t] * coeffs[(4 - j) + 4 t]; then the volume
+    const size_t base = (size_t)row * a.chan_stride + (size_t)f * a.frame_stride;
+    for (int k = 0; k < 32; ++k) {
+      const int o = lane + 64 * k, n = o >> 2, c0 = 3 - (o & 3);
+      float acc = 0.0f;
+#pragma unroll
+      for (int t = 0; t < P2; ++t) acc += s2[n + t] * c2[c0 + 4 * t];
+      const float y = acc * scale;
+      if (!a.q15) {
+        static_cast<float *>(a.out)[base + o] = y;
+      } else {  // arm_float_to_q15: (q15_t)__SSAT((q31_t)(x * 32768.0f), 16), toward zero
+        int q = (int)(y * 32768.0f);
+        q = q < -32768 ? -32768 : (q > 32767 ? 32767 : q);
+        static_cast<short *>(a.out)[base + o] = (short)q;
+      }
+    }
+    const float h2 = lane < P2 - 1 ? s2[2 * N + lane] : 0.0f;
+    __syncthreads();
+    if (lane < P2 - 1) s2[lane] = h2;
+  }
+  __syncthreads();
+  if (lane < P1 - 1) st[kStInt1 + 1 + lane] = s1[lane];
+  if (lane < P2 - 1) st[kStInt2 + 1 + lane] = s2[lane];
+}
+
 // ---- the Morse decoder (cw_decode_kernel) -----------------------------------------------------------------------------
 namespace cwd {
 constexpr int kChunk = 32;                 // frames per staging pass: one key bit per frame in a 32-bit mask
@@ -321,6 +383,12 @@ hipError_t launch_cw_back(const CwBackArgs &a, hipStream_t s) {
   if (a.nchan <= 0 || a.nframes <= 0 || !a.aud || !a.state || (!a.out && !a.out_map)) return hipErrorInvalidConfiguration;
   if (a.out_map) hipLaunchKernelGGL(cw_back_omap_kernel, dim3((unsigned)a.nchan), dim3(64), 0, s, a);
   else hipLaunchKernelGGL(cw_back_kernel, dim3((unsigned)a.nchan), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_cw_back_sets(const CwBackSetsArgs &a, hipStream_t s) {
+  if (a.nchan <= 0 || a.nframes <= 0 || !a.aud || !a.state || (!a.out && !a.out_map) || !a.set_of || !a.sets) return hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(cw_back_sets_kernel, dim3((unsigned)a.nchan), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 

@@ -82,6 +82,22 @@ struct CwBackArgs {
 };
 hipError_t launch_cw_back(const CwBackArgs &a, hipStream_t s);
 
+// The same with parameter sets (t41rx_set_param_sets_ex with T41RX_SETS_STAGES): the volume factor and the two
+// interpolators' taps are those of the channel's own set, entry set_of[channel] of a table the host makes of every set's
+// blob (rx_sets.cpp) -- int2 unscaled, where DevCoef::int2 carries the volume folded in.  scale, int1 and int2 of the
+// block above are not read.
+struct CwSetBack {
+  float scale;     // DF * VolumeToAmplification(audioVolume) of the set
+  float pad[15];   // (the taps on a 64-byte boundary)
+  float int1[48];  // FIR_int1_coeffs
+  float int2[32];  // FIR_int2_coeffs (not scaled)
+};
+struct CwBackSetsArgs : CwBackArgs {
+  const int *set_of;      // [nchan] the channel's set
+  const CwSetBack *sets;  // [K + 1]
+};
+hipError_t launch_cw_back_sets(const CwBackSetsArgs &a, hipStream_t s);
+
 // ---- the Morse decoder behind the detector: DoCWDecoding() and its histograms (CWProcessing.cpp:365-371, :501-815) ----
 // Per channel kCwDecWords int32 words, the checkpoint section's layout and the device's alike: kCwDecScalars scalars (by
 // name below; thresholdGeometricMean as its float's bits, the two flags as 0 / 1, words 28 .. 31 zero), then

@@ -29,6 +29,7 @@
 
 #include "nr_kernels.hpp"
 #include "rx_kernels.hpp"
+#include "rx_stagesets.hpp"
 #include "wave_fft.hpp"
 
 namespace t41 {
@@ -312,6 +313,36 @@ __global__ __launch_bounds__(64) void nrspec_map_kernel(const NrMapArgs a) {
   }
 }
 
+// Parameter sets next to the stages (t41rx_set_param_sets_ex with T41RX_SETS_STAGES): nrspec_map_kernel's text again, and
+// the five values the body reads of its argument block -- NR_alpha, NR_beta, NR_PSI, the VAD range -- come from the
+// channel's row of a table [nchan] made at set time.  The workgroup's channel is uniform (a scalar load of the list), so
+// the row is one scalar load of eight dwords and the values sit in scalar registers, as the kernel arguments of the other
+// forms do; nothing is written through the scalar path.  `a` below is what the body names: the block's pointers and
+// counts with the row's values in the places of the block's.
+__global__ __launch_bounds__(64) void nrspec_sets_kernel(const NrSetsArgs b) {
+#pragma clang fp contract(off)
+  constexpr int KLDS = 1;
+#include "nrspec_lds.inc"
+  const int lane = threadIdx.x;
+  const int ch = b.spec_list[blockIdx.x];
+  const NrSetRow row = b.set_rows[ch];
+  const struct {
+    float *aud, *spec;
+    const float *tab_nr;
+    const float2 *tab;
+    int nframes;
+    float alpha, beta, psi;
+    int vad_lo, vad_hi;
+  } a = {b.aud, b.spec, b.tab_nr, b.tab, b.nframes, row.alpha, row.beta, row.psi, row.vad_lo, row.vad_hi};
+  if (b.spec_kind[blockIdx.x] == 1) {
+    constexpr int KIND = 1;
+#include "nrspec_body.inc"
+  } else {
+    constexpr int KIND = 2;
+#include "nrspec_body.inc"
+  }
+}
+
 namespace {
 // the spectral function and Xanr() of one call take the same channels (with a list: both the same list)
 hipError_t launch_nr_list(const NrArgs &a, hipStream_t s) {
@@ -349,6 +380,18 @@ hipError_t launch_nr_map(const NrMapArgs &a, hipStream_t s) {
     e = hipGetLastError();
   }
   return e;
+}
+
+hipError_t launch_nr_sets(const NrSetsArgs &a, hipStream_t s) {
+  if (a.nspec < 0 || a.nspec > a.nchan || a.nrows < 0 || a.nrows > a.nchan / kAnrCw + 3 || !a.set_rows) return hipErrorInvalidConfiguration;
+  if (a.nspec > 0) {
+    hipLaunchKernelGGL(nrspec_sets_kernel, dim3(a.nspec), dim3(64), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  NrMapArgs m = a;  // Xanr()'s launch alone
+  m.nspec = 0;
+  return a.nrows > 0 ? launch_nr_map(m, s) : hipSuccess;
 }
 
 hipError_t launch_nr(const NrArgs &a, hipStream_t s) {

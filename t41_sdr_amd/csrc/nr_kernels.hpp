@@ -72,4 +72,13 @@ struct NrMapArgs : NrArgs {
 // nrspec_map_kernel over the spectral list, then anr_map_kernel over the rows; nothing for an empty list
 hipError_t launch_nr_map(const NrMapArgs &a, hipStream_t s);
 
+// Parameter sets loaded with T41RX_SETS_STAGES (rx_stagesets.hpp makes the table and the lists): the map's two launches,
+// and the spectral one reads NR_alpha, NR_beta, NR_PSI and the VAD range from the channel's row of set_rows instead of the
+// argument block (alpha .. vad_hi are not read).  anr_map_kernel reads none of them and is launched as it is.
+struct NrSetRow;
+struct NrSetsArgs : NrMapArgs {
+  const NrSetRow *set_rows;  // [nchan]
+};
+hipError_t launch_nr_sets(const NrSetsArgs &a, hipStream_t s);
+
 }  // namespace t41

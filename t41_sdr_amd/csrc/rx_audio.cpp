@@ -81,6 +81,7 @@ int ensure_nr(t41rx_ctx *ctx) {
 
 // Process.cpp:841-866 behind the equalizer
 int nr_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
+  if (sets_staged(ctx)) return nr_sets_run(ctx, n_frames, s);  // parameter sets next to the stages: every channel its own set's values (rx_sets.cpp)
   if (ctx->nr.map_on) return nr_map_run(ctx, n_frames, s);  // the noise-reduction map: every channel its own two values (rx_nrmap.cpp)
   const StageList l = stage_list(ctx, kStageNr);
   if (l.empty()) return T41RX_OK;  // the stage map lists no channel: nothing to launch
@@ -184,7 +185,7 @@ int t41rx_set_noise_blanker(t41rx_ctx *ctx, int NB_on) {
   if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
   if (NB_on != 0 && NB_on != 1) return fail(T41RX_ERR_ARG, "NB_on must be 0 or 1");
   if (NB_on && ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the noise blanker is built for fft_length 512");
-  if (NB_on && sets_loaded(ctx)) return sets_refuse_stage("the noise blanker");
+  if (NB_on && sets_plain(ctx)) return sets_refuse_stage("the noise blanker");
   ctx->nb.on = NB_on;
   return T41RX_OK;
 }
@@ -206,7 +207,7 @@ int t41rx_set_receive_eq(t41rx_ctx *ctx, int receiveEQFlag, const int32_t *equal
     return fail(T41RX_ERR_UNSUPPORTED, "the receive equalizer is built for fft_length 512");
   if (receiveEQFlag && !ctx->eq.have_bands)
     return fail(T41RX_ERR_ARG, "receive equalizer: no band table loaded (t41rx_set_receive_eq_bands)");
-  if (receiveEQFlag && sets_loaded(ctx)) return sets_refuse_stage("the receive equalizer");
+  if (receiveEQFlag && sets_plain(ctx)) return sets_refuse_stage("the receive equalizer");
   if (equalizerRec) std::memcpy(ctx->eq.levels, equalizerRec, sizeof(ctx->eq.levels));
   ctx->eq.on = receiveEQFlag;
   return T41RX_OK;

@@ -28,6 +28,7 @@
 #include "rx_nrmap.hpp"
 #include "rx_stagemap.hpp"
 #include "rx_stageparams.hpp"
+#include "rx_stagesets.hpp"
 
 // the product's host side is never a diagnostic build; what the KERNEL objects were built as is asked at run time
 // (kernel_build_flags(), rx_dispatch.hip): tools/build_variant.sh links these very objects with diagnostic kernels
@@ -217,6 +218,16 @@ struct ParamSets {
   DevBuf<float2> d_tab;
   DevBuf<SetGains> d_gain;
   DevBuf<int32_t> d_set_of;
+  // loaded with T41RX_SETS_STAGES (t41rx_set_param_sets_ex): the sets run next to the chain-splitting stages.  Then, and
+  // only then: every channel's effective nrOptionSelect / ANR_notchOn, its noise-reduction row and the lists made of
+  // them (rx_stagesets.hpp) with their device copies -- the lists in nr_map_layout(), the rows [nchan] -- and what
+  // cw_back_sets_kernel reads of every set [K + 1].  Made again when the sets, the noise-reduction map, the stage map or
+  // set 0 change (stage_sets_refresh).
+  uint32_t flags = 0;
+  StageSetsNr stage;
+  DevBuf<int32_t> d_nr_map;
+  DevBuf<NrSetRow> d_nr_rows;
+  DevBuf<CwSetBack> d_cw_back;
 };
 
 // the stage map (t41rx_set_stage_map; rx_stagemap.cpp): the caller's mask per channel, the lists made of it
@@ -322,7 +333,9 @@ inline int hip_check(hipError_t e, const char *what) { return e == hipSuccess ? 
 // the hand-over, the scratch, the pipelined forms, the back end -- is decided once per call by plan_call() (rx_plan.hpp),
 // from the CallFacts the process call fills with these predicates (rx_host.cpp: call_facts)
 // (a noise-reduction map, t41rx_set_nr_map: on when some entry of the map is non-zero; the context's two values are not consulted)
+// (parameter sets loaded with T41RX_SETS_STAGES: on when some channel's effective kind or notch is non-zero)
 inline bool nr_on(const t41rx_ctx *ctx) {
+  if (!ctx->sets.params.empty() && (ctx->sets.flags & T41RX_SETS_STAGES)) return ctx->sets.stage.lists.any;
   return ctx->nr.map_on ? ctx->nr.lists.any : ctx->params.nrOptionSelect != 0 || ctx->params.ANR_notchOn != 0;  // (fft_length 512: params_valid)
 }
 // the CW block runs in T41State == CW_RECEIVE (Process.cpp:878), which in receive is xmtMode == CW_MODE
@@ -337,6 +350,10 @@ inline bool cw_dec_on(const t41rx_ctx *ctx) { return cw_det_on(ctx) && ctx->cw.d
 // parameter sets: loaded, and what a chain-splitting stage's switch answers then (those stages read set 0's parameters
 // on the host; rx_sets.cpp refuses in the other order with split_stage_on())
 inline bool sets_loaded(const t41rx_ctx *ctx) { return !ctx->sets.params.empty(); }
+// ... loaded with T41RX_SETS_STAGES: the stages run next to them, each channel with its own set's values; and loaded
+// without: the stages' setters refuse (sets_refuse_stage)
+inline bool sets_staged(const t41rx_ctx *ctx) { return sets_loaded(ctx) && (ctx->sets.flags & T41RX_SETS_STAGES) != 0; }
+inline bool sets_plain(const t41rx_ctx *ctx) { return sets_loaded(ctx) && !sets_staged(ctx); }
 constexpr const char *kNrMapStageName = "the noise reduction / notch of a noise-reduction map";
 inline int sets_refuse_stage(const char *stage) {
   return fail(T41RX_ERR_UNSUPPORTED, std::string(stage) + " splits the fused chain and reads one parameter set on the host: it cannot run "
@@ -401,6 +418,13 @@ int upload_nco(t41rx_ctx *ctx);
 // rx_sets.cpp: set 0 changed (set_params / set_coeffs) -- the rule against the loaded sets, and entry 0 of the set arrays
 int sets_check_set0(const t41rx_ctx *ctx, const t41rx_params &p);
 int sets_upload(t41rx_ctx *ctx);
+// rx_sets.cpp, sets loaded with T41RX_SETS_STAGES: the channels' effective values, rows and lists of these sets, table
+// and noise-reduction map (null, null: none) with the context's stage map -- the refusal's text names the channel and the
+// set --; the context's own made again and uploaded (nothing without such sets); a call's noise-reduction launches
+int stage_sets_build(const t41rx_ctx *ctx, const t41rx_params &set0, const t41rx_params *extra, int n_extra, const int32_t *set_of,
+                     const int32_t *kind_map, const int32_t *notch_map, StageSetsNr &out);
+int stage_sets_refresh(t41rx_ctx *ctx);
+int nr_sets_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
 // the pipelined kernels' time-out counter (rx_host.cpp)
 int pipe_timeouts_clear(t41rx_ctx *ctx);
 int pipe_status(const t41rx_ctx *ctx);
@@ -427,7 +451,7 @@ int nb_reset(t41rx_ctx *ctx, size_t bytes);
 // rx_cw.cpp
 int ensure_cw(t41rx_ctx *ctx);
 int ensure_cw_decode(t41rx_ctx *ctx);
-const char *cw_split_stage(const t41rx_ctx *ctx, int *channel);  // (*channel: with a noise-reduction map the first channel that trips it, else -1)
+const char *cw_split_stage(const t41rx_ctx *ctx, int *channel, int *set);  // (*channel: with a noise-reduction map or staged sets the first channel that trips it, else -1; *set: its set where the set supplied the values, else -1)
 int cw_detect_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
 int cw_decode_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
 int cw_filter_run(t41rx_ctx *ctx, const CallPlan &plan, const RxArgs &a, int n_frames, hipStream_t s);  // the narrow filter and its back end

@@ -89,8 +89,20 @@ const char *cw_split_stage_of(const t41rx_ctx *ctx, int nrOptionSelect, int ANR_
 }  // namespace
 // With a noise-reduction map (t41rx_set_nr_map) the rule is each channel's, with the channel's own two values in place of
 // the context's: the first channel that trips it, in *channel.
-const char *cw_split_stage(const t41rx_ctx *ctx, int *channel) {
+// With parameter sets loaded next to the stages (T41RX_SETS_STAGES) it is each channel's too, with the channel's effective
+// values (rx_stagesets.hpp): the map's, or without a map its own set's, and then *set says which.
+const char *cw_split_stage(const t41rx_ctx *ctx, int *channel, int *set) {
   *channel = -1;
+  *set = -1;
+  if (sets_staged(ctx)) {
+    for (int c = 0; c < ctx->nchan; ++c)
+      if (const char *stage = cw_split_stage_of(ctx, ctx->sets.stage.kind[(size_t)c], ctx->sets.stage.notch[(size_t)c])) {
+        *channel = c;
+        if (!ctx->nr.map_on) *set = ctx->sets.set_of[(size_t)c];
+        return stage;
+      }
+    return nullptr;
+  }
   if (!ctx->nr.map_on) return cw_split_stage_of(ctx, ctx->params.nrOptionSelect, ctx->params.ANR_notchOn);
   for (int c = 0; c < ctx->nchan; ++c)
     if (const char *stage = cw_split_stage_of(ctx, ctx->nr.kind_map[(size_t)c], ctx->nr.notch_map[(size_t)c])) {
@@ -199,7 +211,16 @@ int cw_filter_run(t41rx_ctx *ctx, const CallPlan &plan, const RxArgs &a, int n_f
   b.scale = v.scalars[kScOutScale];
   std::memcpy(b.int1, v.int1, sizeof(b.int1));
   std::memcpy(b.int2, v.int2, sizeof(b.int2));
-  e = launch_cw_back(b, s);
+  if (sets_staged(ctx)) {
+    // parameter sets next to the stages: the volume factor and the taps of the channel's own set (rx_sets.cpp makes the table)
+    CwBackSetsArgs bs{};
+    static_cast<CwBackArgs &>(bs) = b;
+    bs.set_of = ctx->sets.d_set_of.get();
+    bs.sets = ctx->sets.d_cw_back.get();
+    e = launch_cw_back_sets(bs, s);
+  } else {
+    e = launch_cw_back(b, s);
+  }
   if (e != hipSuccess) return hip_fail(e, "CW interpolator kernel launch");
   if (plan.back == Back::cw_mixed) {
     // ... and the fused back kernel for the unfiltered ones, as a call without the filter ends (launch_chain: back512)
@@ -244,7 +265,7 @@ int t41rx_set_cw_filter(t41rx_ctx *ctx, int CWFilterIndex) {
   if (CWFilterIndex != kCwFilters) {
     if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "the CW audio filters are built for fft_length 512");
     if (!ctx->cw.have_filters) return fail(T41RX_ERR_ARG, "CW audio filter: no filter tables loaded (t41rx_set_cw_tables)");
-    if (sets_loaded(ctx)) return sets_refuse_stage("the CW audio filter");
+    if (sets_plain(ctx)) return sets_refuse_stage("the CW audio filter");
   }
   ctx->cw.filter = CWFilterIndex;
   return T41RX_OK;
@@ -260,7 +281,7 @@ int t41rx_set_cw_detector(t41rx_ctx *ctx, int decoderFlag, float *d_cw, int max_
     if (reinterpret_cast<uintptr_t>(d_cw) & 3u) return fail(T41RX_ERR_ARG, "unaligned pointer");
     if (max_frames <= 0) return fail(T41RX_ERR_ARG, "max_frames must be > 0");
     if (!ctx->cw.have_fir) return fail(T41RX_ERR_ARG, "CW detector: no decode FIR loaded (t41rx_set_cw_tables)");
-    if (sets_loaded(ctx)) return sets_refuse_stage("the CW detector");
+    if (sets_plain(ctx)) return sets_refuse_stage("the CW detector");
   }
   ctx->cw.det = decoderFlag;
   ctx->cw.out = decoderFlag ? d_cw : nullptr;
@@ -286,7 +307,7 @@ int t41rx_set_cw_decoder(t41rx_ctx *ctx, int on, int32_t *d_text, int max_frames
     if (reinterpret_cast<uintptr_t>(d_text) & 3u) return fail(T41RX_ERR_ARG, "unaligned pointer");
     if (max_frames <= 0) return fail(T41RX_ERR_ARG, "max_frames must be > 0");
     if (!ctx->cw.have_tree) return fail(T41RX_ERR_ARG, "CW decoder: no decode tree loaded (t41rx_set_cw_decode_tree)");
-    if (sets_loaded(ctx)) return sets_refuse_stage("the CW decoder");
+    if (sets_plain(ctx)) return sets_refuse_stage("the CW decoder");
   }
   ctx->cw.dec = on;
   ctx->cw.text = on ? d_text : nullptr;

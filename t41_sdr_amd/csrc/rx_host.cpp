@@ -267,6 +267,7 @@ CallFacts call_facts(const t41rx_ctx *ctx, int n_frames, bool q15) {
   f.seg_run_set = ctx->seg_run_set;
   f.map = ctx->n_streams > 0;
   f.sets = sets_loaded(ctx);
+  f.stage_sets = sets_staged(ctx);
   f.a24 = audio_24k(ctx);
   // (a diagnostic library's stamps ride behind the demod tap pointer at the long lengths, T41RX_STAMP_TAPS: no tap to the plan)
   const bool taps = f.seg == 1 || !ctx->stamp_taps;
@@ -314,7 +315,9 @@ int prepare_call(t41rx_ctx *ctx, const CallPlan &plan, int n_frames, hipStream_t
     HIP_TRY(hipMemset(pipe.get(), 0, bytes));
     ctx->d_agc_pipe = std::move(pipe);
   }
-  if (plan.need_ident && !ctx->d_ident) {  // 0, 1, ..: the map of a mapped form's call without one of the caller's
+  // (staged parameter sets ending in the fused back kernel: its set twin is an output-map form, run with the identity)
+  const bool ident_back = sets_staged(ctx) && plan.back == Back::back512 && !ctx->out_map_on;
+  if ((plan.need_ident || ident_back) && !ctx->d_ident) {  // 0, 1, ..: the map of a mapped form's call without one of the caller's
     std::vector<int32_t> ident((size_t)ctx->nchan);
     for (int i = 0; i < ctx->nchan; ++i) ident[(size_t)i] = i;
     DevBuf<int32_t> fresh;
@@ -335,11 +338,13 @@ int prepare_call(t41rx_ctx *ctx, const CallPlan &plan, int n_frames, hipStream_t
     return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the CW decoder's buffer was set with");
   if (cw_det_on(ctx) && n_frames > ctx->cw.frames)
     return fail(T41RX_ERR_ARG, "n_frames exceeds the max_frames the CW detector's buffer was set with");
-  int split_ch = -1;
+  int split_ch = -1, split_set = -1;
   if (cw_det_on(ctx))
-    if (const char *stage = cw_split_stage(ctx, &split_ch))
+    if (const char *stage = cw_split_stage(ctx, &split_ch, &split_set))
       return fail(T41RX_ERR_UNSUPPORTED, std::string("CW detector: the ") + stage +
-                                             (split_ch >= 0 ? " of channel " + std::to_string(split_ch) + " (noise-reduction map)" : std::string()) +
+                                             (split_ch < 0    ? std::string()
+                                              : split_set < 0 ? " of channel " + std::to_string(split_ch) + " (noise-reduction map)"
+                                                              : " of channel " + std::to_string(split_ch) + " (parameter set " + std::to_string(split_set) + ")") +
                                              " leaves float_buffer_L different from float_buffer_R and neither the notch nor the noise "
                                              "blanker joins them behind it; the library carries one audio stream");
   if (ctx->disp.spec && (!ctx->disp.d_pre || !ctx->disp.d_state || !ctx->d_win)) return fail(T41RX_ERR_STATE, "display spectrum enabled without its buffers");
@@ -501,6 +506,9 @@ int launch_chain(t41rx_ctx *ctx, const CallPlan &plan, RxArgs a, int n_frames, h
     case Back::back512:
       // then the interpolators, volume and stores (Process.cpp:917-937) from a.aud24
       a.aud_out = nullptr;
+      // parameter sets next to the stages: the back kernel's set twin is its output-map form; without a map of the
+      // caller's every channel stores to its own row (the strides are those of n_channels rows already)
+      if (a.set_of && !a.out_map) a.out_map = ctx->d_ident.get();
       rc = hip_check(launch_back512(a, s), "interpolator kernel launch");
       break;
     case Back::fused:
@@ -705,7 +713,8 @@ int t41rx_set_params(t41rx_ctx *ctx, const t41rx_params *p) {
   const char *why = nullptr;
   if (!params_valid(*p, &why)) return fail(T41RX_ERR_ARG, why ? why : "bad params");
   if (p->fft_length != ctx->params.fft_length) return fail(T41RX_ERR_ARG, "fft_length cannot change on a live context");
-  if (sets_loaded(ctx) && sets_check_set0(ctx, *p) != T41RX_OK) return T41RX_ERR_UNSUPPORTED;  // (the rule's text stands)
+  if (sets_loaded(ctx))  // (the rule's text stands; staged sets: and the spectral check of set 0's channels)
+    if (const int src = sets_check_set0(ctx, *p)) return src;
   if (nr_map_check_params(ctx, *p) != T41RX_OK) return T41RX_ERR_ARG;  // (a noise-reduction map with an entry 2: the pass band's check)
 
   std::vector<float> nb(ctx->blob.size());
@@ -750,7 +759,8 @@ int t41rx_set_coeffs(t41rx_ctx *ctx, const void *blob, size_t blob_bytes) {
   const char *why = nullptr;
   if (!params_valid(bp, &why) || bp.fft_length != h[2] || bp.mode != h[3])
     return fail(T41RX_ERR_STATE, std::string("blob parameters invalid: ") + (why ? why : "header mismatch"));
-  if (sets_loaded(ctx) && sets_check_set0(ctx, bp) != T41RX_OK) return T41RX_ERR_UNSUPPORTED;  // (the rule's text stands)
+  if (sets_loaded(ctx))  // (the rule's text stands; staged sets: and the spectral check of set 0's channels)
+    if (const int src = sets_check_set0(ctx, bp)) return src;
   if (nr_map_check_params(ctx, bp) != T41RX_OK) return T41RX_ERR_ARG;
 
   DeviceGuard g(ctx->device);

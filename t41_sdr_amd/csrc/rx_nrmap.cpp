@@ -58,6 +58,7 @@ int nr_map_refresh(t41rx_ctx *ctx) {
 
 // t41rx_set_params() / t41rx_set_coeffs() with a map loaded: a map with an entry 2 needs the spectral function's pass band
 int nr_map_check_params(const t41rx_ctx *ctx, const t41rx_params &p) {
+  if (sets_staged(ctx)) return T41RX_OK;  // (the check is each channel's, against its own set: sets_check_set0)
   return ctx->nr.map_on && ctx->nr.lists.spectral ? spectral_check(p) : T41RX_OK;
 }
 
@@ -104,7 +105,7 @@ int t41rx_set_nr_map(t41rx_ctx *ctx, const int32_t *nr_of_channel, const int32_t
     if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
     HIP_TRY(hipDeviceSynchronize());  // (calls in flight were launched with the lists they found)
     ctx->nr.map_on = false;
-    return T41RX_OK;
+    return stage_sets_refresh(ctx);  // (staged parameter sets: every channel's kind and notch are its own set's again)
   }
   if (!nr_of_channel || !notch_of_channel)
     return fail(T41RX_ERR_ARG, std::string("noise-reduction map: ") + (nr_of_channel ? "notch_of_channel" : "nr_of_channel") +
@@ -128,12 +129,18 @@ int t41rx_set_nr_map(t41rx_ctx *ctx, const int32_t *nr_of_channel, const int32_t
       return fail(T41RX_ERR_ARG, "noise-reduction map: channel " + std::to_string(v.channel) + " has ANR_notchOn " + std::to_string(notch_of_channel[v.channel]) +
                                      ", not 0 or 1" + counts);
   }
-  if (lists.spectral) {  // (params_valid()'s error and text)
+  if (sets_staged(ctx)) {
+    // parameter sets next to the stages: the spectral check is each channel's, against the pass band of its own set
+    StageSetsNr probe;
+    const int rc = stage_sets_build(ctx, ctx->params, ctx->sets.params.data(), (int)ctx->sets.params.size(), ctx->sets.set_of.data(),
+                                    nr_of_channel, notch_of_channel, probe);
+    if (rc != T41RX_OK) return rc;
+  } else if (lists.spectral) {  // (params_valid()'s error and text)
     const int rc = spectral_check(ctx->params);
     if (rc != T41RX_OK) return rc;
   }
   // (an all-zero map is accepted next to parameter sets, as nrOptionSelect 0 and ANR_notchOn 0 are)
-  if (lists.any && sets_loaded(ctx)) return sets_refuse_stage(kNrMapStageName);
+  if (lists.any && sets_plain(ctx)) return sets_refuse_stage(kNrMapStageName);
   const std::vector<int32_t> words = nr_map_words(lists, ctx->nchan);
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
@@ -146,7 +153,7 @@ int t41rx_set_nr_map(t41rx_ctx *ctx, const int32_t *nr_of_channel, const int32_t
   ctx->nr.notch_map.assign(notch_of_channel, notch_of_channel + n);
   ctx->nr.lists = std::move(lists);
   ctx->nr.map_on = true;
-  return T41RX_OK;
+  return stage_sets_refresh(ctx);  // (staged parameter sets: the map supplies every channel's kind and notch)
 }
 
 int t41rx_get_nr_map(const t41rx_ctx *ctx, int32_t *nr_of_channel_out, int32_t *notch_of_channel_out, int n) {

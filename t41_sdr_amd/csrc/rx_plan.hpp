@@ -26,6 +26,9 @@ struct CallFacts {
   // the CW filter map (t41rx_set_cw_filter_map) is loaded and leaves some channel without the narrow filter (index 5).
   // cw_filter then says that some channel has it; a map that filters nobody is a call without the filter
   bool cw_unfiltered = false;
+  // the parameter sets were loaded with T41RX_SETS_STAGES (t41rx_set_param_sets_ex): they run next to the chain-splitting
+  // stages.  Read only where sets && stages
+  bool stage_sets = false;
 };
 
 // an rx512_kernel instantiation of the whole chain (PART 0): two calls with equal forms launch the same kernel
@@ -93,7 +96,7 @@ constexpr CallPlan plan_call(const CallFacts &f) {
     p.valid = false;
     p.nfm_atan_long = true;
     p.why = "nfm_demod = 1 is built for fft_length 512";
-  } else if (f.sets && (lng || stages)) {
+  } else if (f.sets && (lng || (stages && !f.stage_sets))) {
     p.valid = false;
     p.why = "parameter sets are loaded with a long fft_length or a chain-splitting stage";
   } else if (lng && (f.a24 || stage_taps || stages)) {

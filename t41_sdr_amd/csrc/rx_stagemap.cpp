@@ -28,7 +28,8 @@ int t41rx_set_stage_map(t41rx_ctx *ctx, const uint32_t *stages_of_channel, int n
     if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
     HIP_TRY(hipDeviceSynchronize());  // (calls in flight were launched with the lists they found)
     ctx->stages.on = false;
-    return nr_map_refresh(ctx);  // (the noise-reduction map's lists are made of this map too: rx_nrmap.cpp)
+    if (const int rc = nr_map_refresh(ctx)) return rc;  // (the noise-reduction map's lists are made of this map too: rx_nrmap.cpp)
+    return stage_sets_refresh(ctx);                     // (... and those of parameter sets loaded next to the stages: rx_sets.cpp)
   }
   if (ctx->params.fft_length != 512)
     return fail(T41RX_ERR_UNSUPPORTED, "the stage map is built for fft_length 512 (the stages it lists refuse the long lengths themselves)");
@@ -64,7 +65,8 @@ int t41rx_set_stage_map(t41rx_ctx *ctx, const uint32_t *stages_of_channel, int n
   ctx->stages.map.assign(stages_of_channel, stages_of_channel + n);
   ctx->stages.lists = std::move(lists);
   ctx->stages.on = true;
-  return nr_map_refresh(ctx);
+  if (const int rc = nr_map_refresh(ctx)) return rc;
+  return stage_sets_refresh(ctx);
 }
 
 int t41rx_get_stage_map(const t41rx_ctx *ctx, uint32_t *stages_of_channel_out, int n) {

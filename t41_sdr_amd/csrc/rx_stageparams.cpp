@@ -79,7 +79,7 @@ int t41rx_set_cw_filter_map(t41rx_ctx *ctx, const int32_t *filter_of_channel, in
                                      " and no filter tables are loaded (t41rx_set_cw_tables)" + counts);
   }
   // (a map that filters nobody is accepted next to parameter sets, as t41rx_set_cw_filter(ctx, 5) is)
-  if (!lists.filtered.empty() && sets_loaded(ctx)) return sets_refuse_stage("the CW audio filter");
+  if (!lists.filtered.empty() && sets_plain(ctx)) return sets_refuse_stage("the CW audio filter");
   const std::vector<int32_t> rows = cw_map_rows(filter_of_channel, lists, ctx->nchan);
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");

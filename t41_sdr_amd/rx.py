@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _args, _lib, panadapter
 from ._args import F32P, I32P, U16P, U32P, channel_mask, cuda, cuda_tensor, get_blob, int_table, kept, ptr, run, set_blob, table, table_pair, value, with_fields
-from ._lib import DEMOD_AM, DEMOD_LSB, DEMOD_NFM, DEMOD_SAM, DEMOD_USB, Params, T41RxError, check  # noqa: F401
+from ._lib import DEMOD_AM, DEMOD_LSB, DEMOD_NFM, DEMOD_SAM, DEMOD_USB, SETS_STAGES, Params, T41RxError, check  # noqa: F401
 
 
 def default_params(**overrides):
@@ -34,11 +34,16 @@ def design_coeffs(params):
     return get_blob(lib.t41rx_design_coeffs, C.byref(params), n)
 
 
-def param_sets_compatible(a, b):
+def param_sets_compatible(a, b, stages=False):
     """The rule of RxChain.set_param_sets() on two t41rx_params, on the host (t41rx_param_sets_compatible): (True, "")
-    when they may share a chain, else (False, the clause they break).  An invalid struct raises T41RxError."""
+    when they may share a chain, else (False, the clause they break).  An invalid struct raises T41RxError.
+    stages=True: the rule of sets loaded next to the chain-splitting stages (t41rx_param_sets_compatible_ex with
+    T41RX_SETS_STAGES), which lets nrOptionSelect and ANR_notchOn differ."""
     lib = _lib.load()
-    rc = lib.t41rx_param_sets_compatible(C.byref(a), C.byref(b))
+    if stages:
+        rc = lib.t41rx_param_sets_compatible_ex(C.byref(a), C.byref(b), SETS_STAGES)
+    else:
+        rc = lib.t41rx_param_sets_compatible(C.byref(a), C.byref(b))
     if rc == _lib.ERR_UNSUPPORTED:
         return False, lib.t41rx_last_error().decode()
     check(rc)
@@ -240,12 +245,17 @@ class RxChain:
         m = np.zeros(self.n_channels, np.uint32)
         return m if value(self._lib.t41rx_get_stage_map(self._ctx, ptr(m, U32P), self.n_channels)) > 0 else None
 
-    def set_param_sets(self, sets, set_of_channel=None):
+    def set_param_sets(self, sets, set_of_channel=None, stages=False):
         """Receiver groups (t41rx_set_param_sets): the context's own parameters are set 0, sets[i] becomes set i + 1, and
         channel c is processed exactly as a chain created with set set_of_channel[c] would process it.  sets: a sequence
         of t41rx_params, or of dicts of changes against set 0 (dict(mode=DEMOD_LSB, FLoCut=-3000, FHiCut=-200)).  Which
         sets may share a chain is one rule, param_sets_compatible().  None removes the sets.  Configuration, like the
-        input map: in no checkpoint, kept across reset() / set_state(); CalcFilters() changes set 0."""
+        input map: in no checkpoint, kept across reset() / set_state(); CalcFilters() changes set 0.
+        stages=True loads them next to the chain-splitting stages (t41rx_set_param_sets_ex with T41RX_SETS_STAGES): the
+        equalizer, noise reduction / notch, the blanker and the CW stages then run with sets loaded, every channel with
+        its own set's values; without it sets and those stages refuse each other."""
+        if stages not in (False, True, 0, 1):
+            raise ValueError("stages must be False or True, got %r" % (stages,))
         if sets is None:
             if set_of_channel is not None:
                 raise ValueError("set_of_channel goes with sets: pass both, or None to remove the sets")
@@ -262,7 +272,16 @@ class RxChain:
             else:
                 raise ValueError("sets[%d] must be a t41rx_params or a dict of changes against set 0, got %s" % (i, type(s).__name__))
         m = int_table(set_of_channel, np.int32, None, "set_of_channel must be a 1-d array of int32 set numbers, got %r %s")
-        check(self._lib.t41rx_set_param_sets(self._ctx, arr, len(sets), ptr(m, I32P), int(m.size)))
+        if stages:
+            check(self._lib.t41rx_set_param_sets_ex(self._ctx, arr, len(sets), ptr(m, I32P), int(m.size), SETS_STAGES))
+        else:
+            check(self._lib.t41rx_set_param_sets(self._ctx, arr, len(sets), ptr(m, I32P), int(m.size)))
+
+    @property
+    def param_sets_stages(self):
+        """True when the loaded parameter sets were loaded with stages=True (t41rx_get_param_sets_flags); False with plain
+        sets or none"""
+        return bool(value(self._lib.t41rx_get_param_sets_flags(self._ctx)) & SETS_STAGES)
 
     @property
     def param_sets(self):
