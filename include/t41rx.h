@@ -428,8 +428,8 @@ T41RX_API int t41rx_audio_rows(const t41rx_ctx *ctx);
  * What the map does not reach: which kernels a call runs stays a function of the context's switches (a call with a stage
  * on hands over to the stage scratch even if that stage lists no channel); the narrow CW filter (t41rx_set_cw_filter)
  * stays a switch of the context -- it selects the call's back kernel, whose operation order differs from the other's, so
- * a filter per channel would need two back ends per call --; FT8 receive, the panadapter, the beacon monitor, the side
- * outputs and the stage taps stay context-wide; the refusal between parameter sets and the chain-splitting stages
+ * a filter per channel would need two back ends per call --; the panadapter, the beacon monitor, the side
+ * outputs and the stage taps stay context-wide (FT8 receive has a map of its own, t41rx_set_ft8_map); the refusal between parameter sets and the chain-splitting stages
  * stands for sets loaded without T41RX_SETS_STAGES (t41rx_set_param_sets_ex).
  * The map composes with the input map, the output map, both audio rates, both layouts, f32 and q15, and the host and
  * device entries: none of them sees it.
@@ -501,7 +501,8 @@ T41RX_API int t41rx_get_stage_map(const t41rx_ctx *ctx, uint32_t *stages_of_chan
  * Both maps are configuration, like the stage map: they are in no checkpoint, survive t41rx_reset, t41rx_set_state,
  * t41rx_set_params and t41rx_set_coeffs, and may change between any two calls.  t41rx_state_bytes() and every
  * checkpoint section are what they are without a map.  nrOptionSelect and the notch have a map of their own
- * (t41rx_set_nr_map, below).  Still per context: FT8, the panadapter and the beacon monitor; the refusal between parameter
+ * (t41rx_set_nr_map, below), and so has FT8 receive (t41rx_set_ft8_map).  Still per context: the panadapter and the
+ * beacon monitor; the refusal between parameter
  * sets and the chain-splitting stages stands for sets loaded without T41RX_SETS_STAGES (t41rx_set_param_sets_ex). */
 T41RX_API int t41rx_set_cw_filter_map(t41rx_ctx *ctx, const int32_t *filter_of_channel, int n);  /* NULL, 0: remove */
 T41RX_API int t41rx_get_cw_filter_map(const t41rx_ctx *ctx, int32_t *filter_of_channel_out, int n);
@@ -552,7 +553,8 @@ T41RX_API int t41rx_get_nr_map(const t41rx_ctx *ctx, int32_t *nr_of_channel_out,
 
 /* ---- receiver groups: parameter sets, one t41rx_params per group of channels (ABI 5) ----
  * The receivers of one band differ in more than NCOFreq: the phone receivers are LSB at 2.8 kHz, the FT8 receiver is USB
- * at 200..3000 Hz, the CW receivers want a few hundred hertz.  A context's own t41rx_params (t41rx_create,
+ * at 200..3000 Hz, the CW receivers want a few hundred hertz (the FT8 receiver next to LSB ones: t41rx_set_ft8_map, which
+ * asks only the channels it lists for USB).  A context's own t41rx_params (t41rx_create,
  * t41rx_set_params, t41rx_get_params, as ever) is set 0.  On top of it a context holds up to T41RX_MAX_PARAM_SETS - 1
  * extra sets, numbered 1..K, and a table set_of_channel[n_channels].  Channel c is processed exactly as a context created
  * with sets[set_of_channel[c]] would process it, with the same NCOFreq[c], input and history: audio, side outputs, taps
@@ -623,7 +625,8 @@ T41RX_API int t41rx_param_sets_compatible(const t41rx_params *a, const t41rx_par
  * t41rx_set_param_sets() called while a stage is on refuses as ever and leaves loaded staged sets in place; sets loaded
  * without the flag followed by a stage setter refuse as ever.  The CW detector's one-audio-stream rule is evaluated per
  * channel with the channel's effective kind and notch; the refusal names the first offending channel.  Still refused, in
- * the words above: the long fft_lengths, and FT8 receive on a non-USB set.  The panadapter, the beacon monitor and the
+ * the words above: the long fft_lengths, and FT8 receive on a non-USB set -- without an FT8 map; with one
+ * (t41rx_set_ft8_map) only the listed channels' sets are asked for USB.  The panadapter, the beacon monitor and the
  * side outputs stay context-wide and work with staged sets as with plain ones.
  * flags is an int32_t holding T41RX_SETS_* bits (the scalar types of this header are int, int32_t, int64_t, size_t and
  * float); a negative value has unknown bits set.
@@ -845,7 +848,8 @@ T41RX_API int t41rx_calibrate_host_q15(t41rx_ctx *ctx, const int16_t *Q_in_L, co
  *   long fft_length, T41RX_ERR_ARG with a NULL buffer or before the tables are loaded.  on = 0 switches the stage off (the
  *   other arguments are ignored; the FT8 memory stays).  While on, a process call with mode != T41RX_DEMOD_USB is refused
  *   with T41RX_ERR_UNSUPPORTED (t41rx_last_error() says why).  f32 and q15 entry points, both buffer layouts.  Kept across
- *   t41rx_set_params() / t41rx_set_coeffs().  t41rx_get_ft8() returns the switch.
+ *   t41rx_set_params() / t41rx_set_coeffs().  t41rx_get_ft8() returns the switch.  With an FT8 map (t41rx_set_ft8_map,
+ *   below) both buffers hold t41rx_ft8_rows() rows in place of n_channels.
  * t41rx_set_ft8_clock(): millis(n) = t0_ms + floor(n * num / den) in uint32; default 0, 32, 3 (one frame of 2048 samples
  *   at 192 kS/s).  From the next call; n is not touched.  T41RX_ERR_ARG for num < 0 or den <= 0.
  * t41rx_ft8_sync(): auto_sync_FT8()'s success branch on the channels whose byte is non-zero (host array of n = n_channels
@@ -978,6 +982,47 @@ T41RX_API int t41rx_ft8_decode_device(t41rx_ctx *ctx, const uint8_t *d_waterfall
                             int n, t41rx_ft8_result *d_results, void *hip_stream);
 T41RX_API int t41rx_ft8_decode_host(t41rx_ctx *ctx, const uint8_t *d_waterfall, size_t channel_stride_bytes, const int8_t *select,
                           int n, t41rx_ft8_result *results);
+
+/* ---- receiver groups: the FT8 map -- FT8 receive only on the channels that ask (ABI 5) ----
+ * FT8 receive was the one large stage still context-wide: a workgroup on every channel, d_power of 270 KB per channel,
+ * and a refusal as soon as any loaded parameter set was not USB.  The map is the output map's idea: a row per channel,
+ * or none.  New entry points: no call above changes what it does, and a context that sets no map launches what it
+ * always launched.
+ * The rule: FT8 receive runs on channel c in a call exactly when the context's switch (t41rx_set_ft8) is on and
+ * row_of_channel[c] >= 0.  A listed channel is processed exactly as the same channel of a context without a map: its
+ * status words, its power bytes and its FT8 memory are bit for bit the same; only their place differs -- d_power is
+ * [n_rows][2][92 * 1472], d_status [n_rows][n_frames][4], and channel c writes row row_of_channel[c].  A channel with -1 is
+ * processed as with FT8 off: its FT8 memory stays exactly as it was (n included) and no row is written for it.  A row no
+ * channel names is never written.  A map that lists nobody is allowed: the stage then launches nothing.  Which kernels a
+ * call runs stays a function of the context's switches, as with the stage map.
+ * The FT8 memory and its record stay [n_channels][3088]: t41rx_ft8_state_bytes / _get_state / _set_state, t41rx_ft8_sync,
+ * t41rx_ft8_audio_begin and _end keep addressing channels and are unchanged.
+ * USB per channel: with a map loaded a process call asks only the listed channels for T41RX_DEMOD_USB, each against its
+ * own effective set -- set 0, plain or staged sets alike --, and the refusal (T41RX_ERR_UNSUPPORTED) names the first
+ * offending channel and its set.  Without a map the refusals of t41rx_set_ft8 stand as they were.
+ * The audio entries (t41rx_ft8_audio_*): under a map pcm is [n_rows][n_frames * 128]; row r feeds the channel that names it,
+ * and a row nobody names is not read.
+ * The decode: with d_waterfall == NULL (the context's own d_power) and a map loaded, t41rx_ft8_decode_* work by row:
+ * n == t41rx_ft8_rows(); select, the results and the debug buffers are [n_rows]...; row r reads d_power + r * two slots +
+ * select[r] * T41RX_FT8_SLOT_BYTES.  With a caller's own d_waterfall everything stays by channel as ever.
+ * The map is configuration, like the stage map: it is in no checkpoint and survives t41rx_reset, t41rx_set_state,
+ * t41rx_set_params and t41rx_set_coeffs.  fft_length 512 only: T41RX_ERR_UNSUPPORTED at a long fft_length.
+ * The known remainder: the demod tap the stage reads and the hand-over buffer stay [n_channels] -- the fused front end
+ * writes them for every channel --, so the tap is now the larger allocation of a short list.
+ * t41rx_set_ft8_map(): row_of_channel is a host array of n == n_channels entries, each -1 or a row in [0, n_rows).  NULL
+ *   with n == 0 and n_rows == 0 removes the map.  Everything is checked on the host before anything changes; a refused
+ *   call leaves the previous map in place and t41rx_last_error() names the entry: T41RX_ERR_ARG for n != n_channels,
+ *   n_rows outside 1..n_channels, an entry outside [-1, n_rows), a row named twice, and -- while FT8 receive is on --
+ *   n_rows different from the current t41rx_ft8_rows(): the buffers given to t41rx_set_ft8 are sized by the rows, so the
+ *   caller switches FT8 off, sets the map, and switches FT8 on with buffers of the new size.  Removing the map while FT8
+ *   is on is held to the same rule against n_channels.  At equal n_rows the map may change between any two calls (a
+ *   skimmer moves its FT8 decoders).  Synchronises the device, then uploads (the ordering rule of t41rx_set_input_map).
+ * t41rx_get_ft8_map(): returns 1 with a map set, 0 with none (negative: an error status).  row_of_channel_out, n ==
+ *   n_channels entries, receives the map, or 0, 1, .. with none; n_rows_out receives t41rx_ft8_rows(); either may be NULL.
+ * t41rx_ft8_rows(): n_rows, or n_channels with no map: the rows of d_power, d_status and the audio entries' pcm. */
+T41RX_API int t41rx_set_ft8_map(t41rx_ctx *ctx, const int32_t *row_of_channel, int n, int n_rows);  /* NULL, 0, 0: remove */
+T41RX_API int t41rx_get_ft8_map(const t41rx_ctx *ctx, int32_t *row_of_channel_out, int n, int *n_rows_out);
+T41RX_API int t41rx_ft8_rows(const t41rx_ctx *ctx);
 
 /* ---- the panadapter: ShowSpectrum()'s pixels and waterfall row, DrawSmeterBar()'s dBm (Display.cpp:240-504, 955-1030) ----
  * A stage of the receive path, default off, fft_length 512: per channel the display FFT of t41rx_set_display_spectrum(),

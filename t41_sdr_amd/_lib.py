@@ -148,6 +148,9 @@ SYMBOLS = {
     "t41rx_set_ft8_tables": (C.c_int, [_vp, _vp, _vp]),
     "t41rx_set_ft8": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_int]),
     "t41rx_get_ft8": (C.c_int, [_vp]),
+    "t41rx_set_ft8_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int, C.c_int]),
+    "t41rx_get_ft8_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]),
+    "t41rx_ft8_rows": (C.c_int, [_vp]),
     "t41rx_set_ft8_clock": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32]),
     "t41rx_ft8_sync": (C.c_int, [_vp, _vp, C.c_int]),
     "t41rx_ft8_state_bytes": (C.c_size_t, [_vp]),

@@ -25,8 +25,8 @@
 // them to their bit-reversed places in a second buffer indexed through sw2(k) = k ^ (k >> 5 & 31): consecutive lanes
 // differ in the high bits of the reversed index, which sw2 folds into the bank; the split stage then reads it linearly.
 //
-// The block's text is ft8_block.inc, compiled into both kernels that run it: ft8_kernel and ft8_audio_kernel (FT8 from
-// 12 kS/s audio, below).  Two kernels from one text, not one body inlined into two: as a force-inlined device function it
+// The block's text is ft8_block.inc, compiled into the kernels that run it: ft8_kernel and ft8_audio_kernel (FT8 from
+// 12 kS/s audio, below), each with its list form (t41rx_set_ft8_map: ft8_kernel.inc, ft8_audio_kernel.inc).  Two kernels from one text, not one body inlined into two: as a force-inlined device function it
 // compiles ft8_kernel to another instruction stream (the swizzled indices simplified another way, two instructions more),
 // and a template argument for the source would rename the live kernel (profiles/ft8_audio_isa_fingerprint.txt).
 #include <hip/hip_runtime.h>
@@ -61,107 +61,21 @@ __device__ __forceinline__ Cq twmul(unsigned w, Cq x) {
 __device__ __forceinline__ int to_q15(float x) { return sat16((int)(x * 32768.0f)); }
 }  // namespace ft8
 
-// (NT: 256, a workgroup per channel, is the one instantiation.  The wave-per-channel arm, NT = 64, was measured and is
-// gone -- DESIGN.md, "FT8 receive"; the parameter stays because the kernel's name carries it)
-template <int NT>
-__global__ __launch_bounds__(NT) void ft8_kernel(Ft8Args a) {
-#pragma clang fp contract(off)
-  using namespace ft8;
-  __shared__ short sbuf[kFt8BufWords];
-  __shared__ __attribute__((aligned(16))) unsigned fz[1024];
-  __shared__ unsigned nat[1024];
-  __shared__ unsigned tw[768];
-  __shared__ unsigned short mg[kFt8Bins + 3];
-  __shared__ short qs[68];
-  constexpr int kIt = (68 + NT - 1) / NT;  // collector iterations per thread
-  const int ch = blockIdx.x, t = threadIdx.x;
-  int32_t *w = a.state + (size_t)ch * kFt8Words;
-  auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };  // the scalars are the same in every lane
-  unsigned n = (unsigned)uni(w[kFt8N]);
-  int sync = uni(w[kFt8Sync]), flag = uni(w[kFt8Flag]), dsp = uni(w[kFt8DspFlag]), counter = uni(w[kFt8Counter]);
-  int dataLoop = uni(w[kFt8DataLoop]), leftover = uni(w[kFt8Leftover]), half = uni(w[kFt8Half]);
-  const unsigned start = (unsigned)uni(w[kFt8Start]);
-  for (int i = t; i < kFt8BufWords; i += NT) sbuf[i] = (short)w[kFt8Scalars + i];
-  for (int i = t; i < 768; i += NT) tw[i] = a.tab[kFt8TabTw + i];
-  __syncthreads();
-
-  for (int f = 0; f < a.nframes; ++f) {
-    const float *x = a.aud + ((size_t)ch * a.nframes + f) * 256;
-    int done = 0;
-    if (sync) {
-      // ---- collector (Process.cpp:633-662)
-      const int base = 68 * dataLoop;
-      short q[kIt], r1[kIt], r2[kIt];
-#pragma unroll
-      for (int u = 0; u < kIt; ++u) {
-        const int i = t + NT * u;
-        if (i < 68) {
-          q[u] = (short)to_q15(x[(i * 15) >> 2]);
-          r1[u] = sbuf[1024 + base + i];
-          r2[u] = sbuf[2048 + base + i];
-          qs[i] = q[u];
-        }
-      }
-      const short q255 = (short)to_q15(x[255]);
-      __syncthreads();
-#pragma unroll
-      for (int u = 0; u < kIt; ++u) {
-        const int i = t + NT * u;
-        if (i < 68) {
-          sbuf[base + i] = r1[u];
-          sbuf[1024 + base + i] = (leftover >= 1 && i >= leftover) ? qs[i - leftover] : r2[u];
-          // (a record with leftover ahead of dataLoop / 4 would run past the buffer's end: such a write is dropped)
-          if (2048 + base + i + leftover < kFt8BufWords) sbuf[2048 + base + i + leftover] = q[u];
-        }
-      }
-      ++dataLoop;
-      if (dataLoop == 15) {
-        if (t == 0) sbuf[kFt8BufWords - 1] = q255;  // fill last cell
-        dataLoop = 0;
-        leftover = 0;
-        dsp = 1;
-      } else if (dataLoop == 4 || dataLoop == 8 || dataLoop == 12) {
-        if (t == 0 && 2048 + dataLoop * 68 + leftover < kFt8BufWords) sbuf[2048 + dataLoop * 68 + leftover] = q255;
-        ++leftover;
-      }
-      __syncthreads();
-    }
-    if (dsp == 1 && flag == 1) {
-      // ---- process_FT8_FFT() (ft8.cpp:259-268): extract_power(offset_step * FT_8_counter)
-      uint8_t *row = a.power + ((size_t)ch * 2 + (size_t)half) * kFt8HalfBytes + (size_t)kFt8BlockBytes * (size_t)counter;
-#include "ft8_block.inc"
-      ++counter;
-      if (counter == kFt8SlotBlocks) {
-        flag = 0;  // (ft8_decode_flag = 1: the decode belongs to the caller; this frame reports the finished half)
-        done = 1 + half;
-        half ^= 1;
-      }
-      dsp = 0;
-    }
-    if (flag == 0 && sync) {
-      // update_synchronization() (ft8.cpp:154-166)
-      const unsigned now = (unsigned)a.t0 + (unsigned)(((unsigned long long)n * (unsigned)a.num) / (unsigned)a.den);
-      if ((now - start) % 15000u <= 200u) {
-        flag = 1;
-        counter = 0;
-      }
-    }
-    ++n;
-    if (t == 0) *reinterpret_cast<int4 *>(a.status + ((size_t)ch * a.nframes + f) * 4) = make_int4(counter, flag, done, dataLoop);
-  }
-  __syncthreads();
-  for (int i = t; i < kFt8BufWords; i += NT) w[kFt8Scalars + i] = (int)sbuf[i];
-  if (t == 0) {
-    w[kFt8N] = (int)n;
-    w[kFt8Sync] = sync;
-    w[kFt8Flag] = flag;
-    w[kFt8DspFlag] = dsp;
-    w[kFt8Counter] = counter;
-    w[kFt8DataLoop] = dataLoop;
-    w[kFt8Leftover] = leftover;
-    w[kFt8Half] = half;
-  }
-}
+// ft8_kernel<256>, and its list form under an FT8 map (t41rx_set_ft8_map): the text is ft8_kernel.inc
+#define T41_STAGE_KERNEL ft8_kernel
+#define T41_STAGE_ARGS Ft8Args
+#define T41_STAGE_LIST 0
+#include "ft8_kernel.inc"
+#undef T41_STAGE_KERNEL
+#undef T41_STAGE_ARGS
+#undef T41_STAGE_LIST
+#define T41_STAGE_KERNEL ft8_list_kernel
+#define T41_STAGE_ARGS Ft8ListArgs
+#define T41_STAGE_LIST 1
+#include "ft8_kernel.inc"
+#undef T41_STAGE_KERNEL
+#undef T41_STAGE_ARGS
+#undef T41_STAGE_LIST
 
 // auto_sync_FT8()'s success branch (ft8.cpp:133-136), one lane per channel
 __global__ __launch_bounds__(64) void ft8_sync_kernel(int32_t *state, const uint8_t *mask, int nchan, int32_t t0, int32_t num, int32_t den) {
@@ -190,77 +104,21 @@ __device__ __forceinline__ short audio_q15(short x) { return x; }  // (raw / 327
 __device__ __forceinline__ short audio_q15(float x) { return (short)to_q15(x); }
 }  // namespace ft8
 
-template <typename Sample>
-__global__ __launch_bounds__(256) void ft8_audio_kernel(Ft8AudioArgs a) {
-#pragma clang fp contract(off)
-  using namespace ft8;
-  constexpr int NT = 256;
-  __shared__ short sbuf[kFt8BufWords];
-  __shared__ __attribute__((aligned(16))) unsigned fz[1024];
-  __shared__ unsigned nat[1024];
-  __shared__ unsigned tw[768];
-  __shared__ unsigned short mg[kFt8Bins + 3];
-  const int ch = blockIdx.x, t = threadIdx.x;
-  int32_t *w = a.state + (size_t)ch * kFt8Words;
-  auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
-  const int flag0 = uni(w[kFt8Flag]), counter0 = uni(w[kFt8Counter]), dataLoop0 = uni(w[kFt8DataLoop]), half0 = uni(w[kFt8Half]);
-  int flag = flag0, counter = counter0, half = half0;
-  for (int i = t; i < kFt8BufWords; i += NT) sbuf[i] = (short)w[kFt8Scalars + i];
-  for (int i = t; i < 768; i += NT) tw[i] = a.tab[kFt8TabTw + i];
-  __syncthreads();
-
-  const Sample *x = static_cast<const Sample *>(a.pcm) + (size_t)ch * (size_t)a.nframes * kFt8AudioFrame;
-  int d0 = dataLoop0;
-  for (int f = 0; f < a.nframes;) {
-    const int d1 = min(15, d0 + a.nframes - f);
-    for (int c = kFt8AudioCells * d0 + t; c < kFt8AudioCells * d1; c += NT) {  // c <= 1019
-      const int d = c / kFt8AudioCells, i = c - kFt8AudioCells * d;
-      const short q = audio_q15(x[(f + d - d0) * kFt8AudioFrame + ((i * 15) >> 3)]);  // frame < nframes, sample <= 125
-      sbuf[c] = sbuf[c + 1024];
-      sbuf[c + 1024] = sbuf[c + 2048];
-      sbuf[c + 2048] = q;
-    }
-    f += d1 - d0;
-    d0 = d1;
-    if (d1 == 15) {
-      d0 = 0;
-      __syncthreads();
-      if (counter < kFt8SlotBlocks) {
-        uint8_t *row = a.power + ((size_t)ch * 2 + (size_t)half) * kFt8HalfBytes + (size_t)kFt8BlockBytes * (size_t)counter;
-  #include "ft8_block.inc"
-        ++counter;
-        if (counter == kFt8SlotBlocks) {
-          flag = 0;
-          half ^= 1;
-          counter = 0;
-        }
-      }
-    }
-  }
-  // the status words: nb blocks have run behind frame f
-  for (int f = t; f < a.nframes; f += NT) {
-    const int fed = dataLoop0 + f + 1, nb = fed / 15;
-    int c = counter0, fl = flag0, done = 0;
-    if (counter0 < kFt8SlotBlocks) {
-      c = counter0 + nb;
-      if (c >= kFt8SlotBlocks) {  // at most one completion in kFt8MaxFrames frames
-        c -= kFt8SlotBlocks;
-        fl = 0;
-      }
-      if (fed == 15 * (kFt8SlotBlocks - counter0)) done = 1 + half0;
-    }
-    *reinterpret_cast<int4 *>(a.status + ((size_t)ch * a.nframes + f) * 4) = make_int4(c, fl, done, fed - 15 * nb);
-  }
-  __syncthreads();
-  for (int i = t; i < kFt8BufWords; i += NT) w[kFt8Scalars + i] = (int)sbuf[i];
-  if (t == 0) {
-    w[kFt8N] = (int)((unsigned)w[kFt8N] + (unsigned)a.nframes);
-    w[kFt8Flag] = flag;
-    w[kFt8Counter] = counter;
-    w[kFt8DataLoop] = d0;
-    w[kFt8Half] = half;
-  }
-}
+// ft8_audio_kernel<short | float>, and its list form: the text is ft8_audio_kernel.inc
+#define T41_STAGE_KERNEL ft8_audio_kernel
+#define T41_STAGE_ARGS Ft8AudioArgs
+#define T41_STAGE_LIST 0
+#include "ft8_audio_kernel.inc"
+#undef T41_STAGE_KERNEL
+#undef T41_STAGE_ARGS
+#undef T41_STAGE_LIST
+#define T41_STAGE_KERNEL ft8_audio_list_kernel
+#define T41_STAGE_ARGS Ft8AudioListArgs
+#define T41_STAGE_LIST 1
+#include "ft8_audio_kernel.inc"
+#undef T41_STAGE_KERNEL
+#undef T41_STAGE_ARGS
+#undef T41_STAGE_LIST
 
 // setupFT8Wav()'s FT_8_counter = 0 (ft8.cpp:1372; end = 0) or the mode's exit (Process.cpp:339-342; end = 1), one lane per channel
 __global__ __launch_bounds__(64) void ft8_audio_mark_kernel(int32_t *state, const uint8_t *mask, int nchan, int end) {
@@ -281,6 +139,18 @@ hipError_t launch_ft8_audio(const Ft8AudioArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(ft8_audio_kernel<short>, dim3((unsigned)a.nchan), dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL(ft8_audio_kernel<float>, dim3((unsigned)a.nchan), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// the list form: a workgroup per pair (the setter checked the pairs: channel < nchan, row < the rows of power / status / pcm)
+hipError_t launch_ft8_audio_list(const Ft8AudioListArgs &a, hipStream_t s) {
+  if (a.nchan <= 0 || a.nframes <= 0 || a.nframes > kFt8MaxFrames || !a.pcm || !a.state || !a.power || !a.status || !a.window || !a.mag_db || !a.tab ||
+      !a.list || a.nlist <= 0 || a.nlist > a.nchan)
+    return hipErrorInvalidConfiguration;
+  if (a.q15)
+    hipLaunchKernelGGL(ft8_audio_list_kernel<short>, dim3((unsigned)a.nlist), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL(ft8_audio_list_kernel<float>, dim3((unsigned)a.nlist), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
@@ -310,6 +180,14 @@ hipError_t launch_ft8(const Ft8Args &a, hipStream_t s) {
   if (a.nchan <= 0 || a.nframes <= 0 || !a.aud || !a.state || !a.power || !a.status || !a.window || !a.mag_db || !a.tab || a.num < 0 || a.den <= 0)
     return hipErrorInvalidConfiguration;
   hipLaunchKernelGGL(ft8_kernel<256>, dim3((unsigned)a.nchan), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_ft8_list(const Ft8ListArgs &a, hipStream_t s) {
+  if (a.nchan <= 0 || a.nframes <= 0 || !a.aud || !a.state || !a.power || !a.status || !a.window || !a.mag_db || !a.tab || a.num < 0 || a.den <= 0 ||
+      !a.list || a.nlist <= 0 || a.nlist > a.nchan)
+    return hipErrorInvalidConfiguration;
+  hipLaunchKernelGGL(ft8_list_kernel<256>, dim3((unsigned)a.nlist), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -8,6 +8,8 @@
 
 #include <cstdint>
 
+#include "rx_ft8map.hpp"
+
 namespace t41 {
 
 constexpr int kFt8Gulp = 1024;                      // input_gulp_size: samples @6.4 kS/s per 15 frames
@@ -53,6 +55,23 @@ struct Ft8Args {
   int32_t t0, num, den;   // the clock (t41rx_set_ft8_clock)
 };
 hipError_t launch_ft8(const Ft8Args &a, hipStream_t s);
+// the list form under an FT8 map (t41rx_set_ft8_map; rx_ft8map.hpp): a workgroup per pair of `list`, which indexes state
+// and aud by the pair's channel, power and status by its row.  Ft8Args' members in Ft8Args' order (ft8_kernel.inc is one
+// text for both), then the list.  An empty list is not launched.
+struct Ft8ListArgs {
+  const float *aud;       // [nchan][nframes * 256]
+  int32_t *state;         // [nchan][kFt8Words]
+  uint8_t *power;         // [rows][2][kFt8HalfBytes]
+  int32_t *status;        // [rows][nframes][4]
+  const float *window;
+  const float *mag_db;
+  const uint32_t *tab;
+  int nchan, nframes;
+  int32_t t0, num, den;
+  const Ft8Pair *list;    // [nlist] (device), ascending by channel, no row twice
+  int nlist;              // 1 .. nchan: the grid
+};
+hipError_t launch_ft8_list(const Ft8ListArgs &a, hipStream_t s);
 // auto_sync_FT8()'s success branch on the channels whose mask byte is non-zero (mask: device pointer, or null for all)
 hipError_t launch_ft8_sync(int32_t *state, const uint8_t *mask, int nchan, int32_t t0, int32_t num, int32_t den, hipStream_t s);
 // FT8 from 12 kS/s audio: the collector of DEMOD_FT8_WAV (Process.cpp:278-335) in front of the same transform, on the same
@@ -71,6 +90,21 @@ struct Ft8AudioArgs {
   int q15;
 };
 hipError_t launch_ft8_audio(const Ft8AudioArgs &a, hipStream_t s);
+// its list form: state by the pair's channel; pcm, power and status by its row
+struct Ft8AudioListArgs {
+  const void *pcm;        // [rows][nframes * 128]
+  int32_t *state;         // [nchan][kFt8Words]
+  uint8_t *power;         // [rows][2][kFt8HalfBytes]
+  int32_t *status;        // [rows][nframes][4]
+  const float *window;
+  const float *mag_db;
+  const uint32_t *tab;
+  int nchan, nframes;
+  int q15;
+  const Ft8Pair *list;    // [nlist] (device)
+  int nlist;              // 1 .. nchan: the grid
+};
+hipError_t launch_ft8_audio_list(const Ft8AudioListArgs &a, hipStream_t s);
 // setupFT8Wav()'s FT_8_counter = 0 (end = 0) or the mode's exit, syncFlag = FT_8_counter = ft8_flag = 0 (end = 1), on the
 // channels whose mask byte is non-zero (mask: device pointer, or null for all)
 hipError_t launch_ft8_audio_mark(int32_t *state, const uint8_t *mask, int nchan, int end, hipStream_t s);

@@ -2,7 +2,7 @@
 // Private to them: rx_host.cpp (the core and the process call), rx_state.cpp (checkpoints and reset) and one file per
 // stage family -- rx_audio.cpp, rx_cw.cpp, rx_ft8.cpp, rx_ft8_decode.cpp, rx_display.cpp, rx_beacon.cpp, rx_cal.cpp -- and
 // rx_sets.cpp (the parameter sets), rx_outmap.cpp (the output map), rx_stagemap.cpp (the stage map) and
-// rx_stageparams.cpp (the CW filter map and the equalizer level map).  Each
+// rx_stageparams.cpp (the CW filter map and the equalizer level map); the FT8 map lives with its stage in rx_ft8.cpp.  Each
 // stage family holds its part of the context in a struct of its own below, and exports the few functions the process
 // call and the checkpoint table name.  No kernel is compiled into a host file: they see the kernels through the
 // *_kernels.hpp headers.
@@ -134,6 +134,16 @@ struct Ft8Stage {
   DevBuf<float> d_win, d_mag, d_tap;
   DevBuf<uint32_t> d_tab;
   int tap_frames = 0;
+  // the FT8 map (t41rx_set_ft8_map; rx_ft8.cpp): the caller's row per channel, the rows d_power / d_status then hold, the
+  // list of {channel, row} pairs made of it (rx_ft8map.hpp) and its device copy [nchan] pairs.  With a map `power` is
+  // [rows][2][kFt8HalfBytes] and `status` [rows][n_frames][4]; the FT8 memory and the demod tap stay [nchan].
+  // Configuration like the stage map: in no checkpoint, untouched by reset / set_state / set_params.  map_on == false:
+  // no map, the stage runs on every channel and channel c writes row c.
+  bool map_on = false;
+  std::vector<int32_t> map;   // [nchan] (host)
+  int rows = 0;
+  std::vector<Ft8Pair> list;  // ascending by channel (host)
+  DevBuf<Ft8Pair> d_list;     // allocated with the first map
 };
 
 // FT8 decode of a finished slot (ft8.cpp:270-616, 669-703, 727-790; t41rx_set_ft8_decode_tables / _ft8_decode /
@@ -376,6 +386,8 @@ int aud24_finish_run(t41rx_ctx *ctx, const RxArgs &a, int n_frames, hipStream_t 
 inline int input_rows(const t41rx_ctx *ctx) { return ctx->n_streams > 0 ? ctx->n_streams : ctx->nchan; }
 // rows of audio a process call writes: one per channel, or the output map's n_rows
 inline int audio_rows(const t41rx_ctx *ctx) { return ctx->out_map_on ? ctx->out_rows : ctx->nchan; }
+// rows of d_power / d_status (and of the audio entry's pcm): one per channel, or the FT8 map's n_rows
+inline int ft8_rows(const t41rx_ctx *ctx) { return ctx->ft8.map_on ? ctx->ft8.rows : ctx->nchan; }
 // the list of a stage of a call (rx_stagemap.hpp: StageIndex), row kStageCount: the blanker's complement
 inline StageList stage_list(const t41rx_ctx *ctx, int row) {
   if (!ctx->stages.on) return StageList{};

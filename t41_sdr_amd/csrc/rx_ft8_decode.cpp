@@ -102,7 +102,14 @@ int t41rx_ft8_decode_device(t41rx_ctx *ctx, const uint8_t *d_waterfall, size_t c
   if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
   if (!d_results) return fail(T41RX_ERR_ARG, "FT8 decode: no result buffer (d_results is NULL)");
   if (!ctx->ft8d.have_tables) return fail(T41RX_ERR_ARG, "FT8 decode: no tables loaded (t41rx_set_ft8_decode_tables)");
-  if (n != ctx->nchan) return fail(T41RX_ERR_ARG, "FT8 decode: n must equal n_channels");
+  // the context's own d_power under an FT8 map (t41rx_set_ft8_map) is decoded by row: select, the results and the debug
+  // buffers are [n_rows], and the kernels below run with nchan = n_rows.  A caller's own waterfall stays by channel.
+  const bool by_row = !d_waterfall && ctx->ft8.on && ctx->ft8.map_on;
+  if (by_row) {
+    if (n != ft8_rows(ctx)) return fail(T41RX_ERR_ARG, "FT8 decode: with an FT8 map the context's own d_power is decoded by row: n must equal t41rx_ft8_rows()");
+  } else if (n != ctx->nchan) {
+    return fail(T41RX_ERR_ARG, "FT8 decode: n must equal n_channels");
+  }
   bool slot1 = false;
   if (select)
     for (int c = 0; c < n; ++c) {
@@ -124,8 +131,9 @@ int t41rx_ft8_decode_device(t41rx_ctx *ctx, const uint8_t *d_waterfall, size_t c
   Ft8Decode &d = ctx->ft8d;
   if (select) {
     if (!d.d_sel) {
-      HIP_TRY(dev_alloc(d.d_sel, (size_t)n));
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&d.h_sel), (size_t)n, hipHostMallocDefault));
+      // (n_channels entries: a by-row call takes fewer, and a later call by channel all of them)
+      HIP_TRY(dev_alloc(d.d_sel, (size_t)ctx->nchan));
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&d.h_sel), (size_t)ctx->nchan, hipHostMallocDefault));
       HIP_TRY(hipEventCreateWithFlags(&d.sel_ev, hipEventDisableTiming));
     } else {
       HIP_TRY(hipEventSynchronize(d.sel_ev));  // the upload of the call before has read the pinned copy
@@ -156,10 +164,10 @@ int t41rx_ft8_decode_host(t41rx_ctx *ctx, const uint8_t *d_waterfall, size_t cha
                           t41rx_ft8_result *results) {
   if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
   if (!results) return fail(T41RX_ERR_ARG, "FT8 decode: no result buffer (results is NULL)");
-  if (n != ctx->nchan) return fail(T41RX_ERR_ARG, "FT8 decode: n must equal n_channels");
+  if (n < 1 || n > ctx->nchan) return fail(T41RX_ERR_ARG, "FT8 decode: n must equal n_channels (with an FT8 map and the context's own d_power: t41rx_ft8_rows())");
   DeviceGuard g(ctx->device);
   if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
-  if (!ctx->ft8d.d_res) HIP_TRY(dev_alloc(ctx->ft8d.d_res, sizeof(t41rx_ft8_result) * (size_t)n));
+  if (!ctx->ft8d.d_res) HIP_TRY(dev_alloc(ctx->ft8d.d_res, sizeof(t41rx_ft8_result) * (size_t)ctx->nchan));
   if (const int rc = t41rx_ft8_decode_device(ctx, d_waterfall, channel_stride_bytes, select, n, ctx->ft8d.d_res.get(), nullptr)) return rc;
   HIP_TRY(hipMemcpy(results, ctx->ft8d.d_res.get(), sizeof(t41rx_ft8_result) * (size_t)n, hipMemcpyDeviceToHost));
   HIP_TRY(hipStreamSynchronize(nullptr));

@@ -104,6 +104,7 @@ class RxChain:
         self._audio_rate = 192000  # set_audio_rate
         self._n_streams = 0  # the input map's row count (set_input_map), 0 = no map
         self._audio_rows = None  # the output map's row count (set_output_map), None = no map
+        self._ft8_rows = None  # the FT8 map's row count (set_ft8_map), None = no map
         if NCOFreq is not None:
             self.SetNCOFreq(NCOFreq)
 
@@ -490,19 +491,51 @@ class RxChain:
         [n_channels, max_frames, 4]; a process call of n <= max_frames <= 1380 frames fills the status' first n_channels *
         n * 4 words as [n_channels][n][FT_8_counter, ft8_flag, 0 or 1 + the half completed in this frame, dataLoop]
         (ft8_status(n) is that view).  on = 0 switches it off and returns None.  Nothing is collected before ft8_sync().
-        fft_length 512, mode USB; the tables loaded first.  Kept across CalcFilters() / set_coeffs()."""
-        return self._result_stage("_ft8", self._lib.t41rx_set_ft8, on, max_frames, ("uint8", 2, 92 * 1472), ("int32", None, 4))
+        fft_length 512, mode USB; the tables loaded first.  Kept across CalcFilters() / set_coeffs().
+        With an FT8 map (set_ft8_map) both tensors hold ft8_rows rows in place of n_channels."""
+        return self._result_stage("_ft8", self._lib.t41rx_set_ft8, on, max_frames, ("uint8", 2, 92 * 1472), ("int32", None, 4), rows=self.ft8_rows)
+
+    def set_ft8_map(self, row_of_channel, n_rows=None):
+        """Receiver groups (t41rx_set_ft8_map): FT8 receive runs on channel c only when row_of_channel[c] >= 0, and then
+        writes row row_of_channel[c] of the power and status tensors, which hold n_rows rows -- [n_rows, 2, 92 * 1472] and
+        [n_rows, max_frames, 4]; a channel with -1 is processed as with FT8 off and its FT8 memory stays as it was.  No row
+        may be named twice; n_rows defaults to max + 1 (at least 1).  ft8_audio() then takes [n_rows, 128 * k], and
+        ft8_decode() without a waterfall takes and returns rows.  None removes the map.  While FT8 receive is on the rows
+        cannot change: set_ft8(0), set_ft8_map(...), set_ft8(1, ...); at equal n_rows the map may change between any two
+        calls.  Configuration, like the stage map: in no checkpoint, kept across reset() / set_state() / CalcFilters();
+        FFT_LENGTH 512."""
+        if row_of_channel is None:
+            check(self._lib.t41rx_set_ft8_map(self._ctx, None, 0, 0))
+            self._ft8_rows = None
+            return
+        m = int_table(row_of_channel, np.int32, None, "row_of_channel must be a 1-d array of int32 row numbers (-1: no FT8 receive), got %r %s")
+        if n_rows is None:
+            n_rows = max(int(m.max()) + 1, 1) if m.size else 1
+        check(self._lib.t41rx_set_ft8_map(self._ctx, ptr(m, I32P), int(m.size), int(n_rows)))
+        self._ft8_rows = int(n_rows)
+
+    @property
+    def ft8_map(self):
+        """the FT8 map as an int32 array [n_channels] (a copy, -1: not listed), or None with no map set"""
+        m = np.zeros(self.n_channels, np.int32)
+        return m if value(self._lib.t41rx_get_ft8_map(self._ctx, ptr(m, I32P), self.n_channels, None)) > 0 else None
+
+    @property
+    def ft8_rows(self):
+        """rows of the FT8 power and status tensors and of ft8_audio()'s pcm: the FT8 map's n_rows, or n_channels with no map"""
+        rows = getattr(self, "_ft8_rows", None)  # (kept here and read as audio_rows is: the shape checks make no call into the library)
+        return self.n_channels if rows is None else rows
 
     @property
     def ft8(self):
         return value(self._lib.t41rx_get_ft8(self._ctx))
 
     def ft8_status(self, n_frames):
-        """the FT8 status words of the last process call of n_frames frames: a view [n_channels, n_frames, 4]"""
-        return self._first_frames(kept(self, "_ft8", "FT8 receive is off")[1], n_frames, 4)
+        """the FT8 status words of the last process call of n_frames frames: a view [ft8_rows, n_frames, 4]"""
+        return self._first_frames(kept(self, "_ft8", "FT8 receive is off")[1], n_frames, 4, rows=self.ft8_rows)
 
     def ft8_power(self):
-        """export_fft_power, uint8 CUDA [n_channels, 2, 92 * 1472]: the half a status word reported complete holds the
+        """export_fft_power, uint8 CUDA [ft8_rows, 2, 92 * 1472]: the half a status word reported complete holds the
         finished slot, [92 blocks][time_sub 0 / 512][freq_sub 0 / 1][368]"""
         return kept(self, "_ft8", "FT8 receive is off")[0]
 
@@ -526,7 +559,7 @@ class RxChain:
     # -- FT8 from 12 kS/s audio (DEMOD_FT8_WAV) ----------------------------------------------
     def ft8_audio(self, pcm):
         """The collector of DEMOD_FT8_WAV (Process.cpp:278-335; t41rx_ft8_audio_*) on 12 kS/s audio, without the receive
-        chain: pcm [n_channels, 128 * k], int16 (a WAV file's samples, taken as they are) or float32 (through
+        chain: pcm [ft8_rows, 128 * k] (n_channels rows without an FT8 map), int16 (a WAV file's samples, taken as they are) or float32 (through
         arm_float_to_q15), a CUDA tensor (default stream, no synchronisation) or a numpy array.  Always channel-major:
         the input map and the buffer layout do not apply.  Needs set_ft8(1, max_frames >= k); writes the same power halves
         and returns the call's status words, the view ft8_status(k)."""
@@ -551,8 +584,9 @@ class RxChain:
         return self.ft8_status(k)
 
     def _ft8_audio_frames(self, shape):
-        if len(shape) != 2 or shape[0] != self.n_channels or shape[1] < 128 or shape[1] % 128:
-            raise ValueError("pcm must be [n_channels = %d, 128 * k], got %r" % (self.n_channels, tuple(shape)))
+        rows = self.ft8_rows
+        if len(shape) != 2 or shape[0] != rows or shape[1] < 128 or shape[1] % 128:
+            raise ValueError("pcm must be [%s = %d, 128 * k], got %r" % ("n_channels" if rows == self.n_channels else "ft8_rows", rows, tuple(shape)))
         kept(self, "_ft8", "FT8 receive is off")
         return shape[1] // 128
 
@@ -598,16 +632,17 @@ class RxChain:
         per channel] whose rows hold one or two slots of 92 * 1472 bytes; waterfall None reads the context's own
         export_fft_power (set_ft8), where select names the half a status word reported complete.  Returns a numpy array
         [n_channels] of dtype t41_sdr_amd.ft8.RESULT (ft8.messages() turns it into text); with debug also the stage taps
-        log174 [n_channels, 20, 174] f32 and plain [n_channels, 20, 174] uint8."""
+        log174 [n_channels, 20, 174] f32 and plain [n_channels, 20, 174] uint8.  With an FT8 map (set_ft8_map) and
+        waterfall None the decode is by row: select, the records and the taps are [ft8_rows, ...]."""
         import torch
         from . import ft8 as F
-        n = self.n_channels
+        n = self.ft8_rows if waterfall is None else self.n_channels
         dev = cuda(self.device)
         sel = None
         if select is not None:
             sel = np.asarray(select)
             if sel.shape != (n,):
-                raise ValueError("select must have n_channels = %d entries, got %r" % (n, sel.shape))
+                raise ValueError("select must have %s = %d entries, got %r" % ("n_channels" if n == self.n_channels else "ft8_rows", n, sel.shape))
             if ((sel < -128) | (sel > 127)).any():
                 raise ValueError("select does not fit int8")
             sel = np.ascontiguousarray(sel, dtype=np.int8)
@@ -649,9 +684,9 @@ class RxChain:
         per = int(buf[:STATE_HEADER_BYTES].view(np.int32)[4])  # floats per channel of the path's section (the side stages' follow it)
         return buf[STATE_HEADER_BYTES:STATE_HEADER_BYTES + 4 * per * self.n_channels].view(np.float32).reshape(self.n_channels, per)
 
-    def _result_stage(self, attr, entry, on, max_frames, *tensors):
-        """The switch of a stage that owns its result tensors, each (dtype, dimensions behind n_channels) with None for
-        max_frames.  Off: tells the library and drops them.  On: allocates them zeroed, hands them to entry(ctx, on,
+    def _result_stage(self, attr, entry, on, max_frames, *tensors, rows=None):
+        """The switch of a stage that owns its result tensors, each (dtype, dimensions behind n_channels -- or behind `rows`,
+        for a stage whose results have a row map --) with None for max_frames.  Off: tells the library and drops them.  On: allocates them zeroed, hands them to entry(ctx, on,
         pointers ..., max_frames) and keeps them alive in self.<attr>; a refused call leaves self.<attr> as it was."""
         if not on:
             check(entry(self._ctx, 0, *[None] * len(tensors), 0))
@@ -660,16 +695,18 @@ class RxChain:
         import torch
         if int(max_frames) < 1:
             raise ValueError("max_frames must be >= 1")
-        ts = tuple(torch.zeros((self.n_channels,) + tuple(int(max_frames) if d is None else d for d in dims),
+        ts = tuple(torch.zeros((self.n_channels if rows is None else int(rows),) + tuple(int(max_frames) if d is None else d for d in dims),
                                dtype=getattr(torch, dtype), device=cuda(self.device)) for dtype, *dims in tensors)
         check(entry(self._ctx, int(on), *[ptr(t) for t in ts], int(max_frames)))
         keep = ts[0] if len(ts) == 1 else ts
         setattr(self, attr, keep)  # keep alive
         return keep
 
-    def _first_frames(self, t, n_frames, width):
-        """the part of a result tensor [n_channels, max_frames, width] a call of n_frames frames filled, as [n_channels, n_frames, width]"""
-        return t.view(-1)[:self.n_channels * int(n_frames) * width].view(self.n_channels, int(n_frames), width)
+    def _first_frames(self, t, n_frames, width, rows=None):
+        """the part of a result tensor [n_channels, max_frames, width] a call of n_frames frames filled, as [n_channels, n_frames, width]
+        (rows: the leading dimension of a stage whose results have a row map)"""
+        rows = self.n_channels if rows is None else int(rows)
+        return t.view(-1)[:rows * int(n_frames) * width].view(rows, int(n_frames), width)
 
     # -- the hot path ----------------------------------------------------------------------
     def ProcessIQData(self, float_buffer_L, float_buffer_R, out=None):
