@@ -428,8 +428,9 @@ T41RX_API int t41rx_audio_rows(const t41rx_ctx *ctx);
  * What the map does not reach: which kernels a call runs stays a function of the context's switches (a call with a stage
  * on hands over to the stage scratch even if that stage lists no channel); the narrow CW filter (t41rx_set_cw_filter)
  * stays a switch of the context -- it selects the call's back kernel, whose operation order differs from the other's, so
- * a filter per channel would need two back ends per call --; the panadapter, the beacon monitor, the side
- * outputs and the stage taps stay context-wide (FT8 receive has a map of its own, t41rx_set_ft8_map); the refusal between parameter sets and the chain-splitting stages
+ * a filter per channel would need two back ends per call --; the side outputs and the stage taps stay context-wide
+ * (FT8 receive has a map of its own, t41rx_set_ft8_map, and so have the panadapter and the beacon monitor behind it,
+ * t41rx_set_panadapter_map); the refusal between parameter sets and the chain-splitting stages
  * stands for sets loaded without T41RX_SETS_STAGES (t41rx_set_param_sets_ex).
  * The map composes with the input map, the output map, both audio rates, both layouts, f32 and q15, and the host and
  * device entries: none of them sees it.
@@ -501,8 +502,8 @@ T41RX_API int t41rx_get_stage_map(const t41rx_ctx *ctx, uint32_t *stages_of_chan
  * Both maps are configuration, like the stage map: they are in no checkpoint, survive t41rx_reset, t41rx_set_state,
  * t41rx_set_params and t41rx_set_coeffs, and may change between any two calls.  t41rx_state_bytes() and every
  * checkpoint section are what they are without a map.  nrOptionSelect and the notch have a map of their own
- * (t41rx_set_nr_map, below), and so has FT8 receive (t41rx_set_ft8_map).  Still per context: the panadapter and the
- * beacon monitor; the refusal between parameter
+ * (t41rx_set_nr_map, below), and so have FT8 receive (t41rx_set_ft8_map) and the panadapter with the beacon monitor
+ * (t41rx_set_panadapter_map).  Still per context: the two display side outputs; the refusal between parameter
  * sets and the chain-splitting stages stands for sets loaded without T41RX_SETS_STAGES (t41rx_set_param_sets_ex). */
 T41RX_API int t41rx_set_cw_filter_map(t41rx_ctx *ctx, const int32_t *filter_of_channel, int n);  /* NULL, 0: remove */
 T41RX_API int t41rx_get_cw_filter_map(const t41rx_ctx *ctx, int32_t *filter_of_channel_out, int n);
@@ -626,8 +627,9 @@ T41RX_API int t41rx_param_sets_compatible(const t41rx_params *a, const t41rx_par
  * without the flag followed by a stage setter refuse as ever.  The CW detector's one-audio-stream rule is evaluated per
  * channel with the channel's effective kind and notch; the refusal names the first offending channel.  Still refused, in
  * the words above: the long fft_lengths, and FT8 receive on a non-USB set -- without an FT8 map; with one
- * (t41rx_set_ft8_map) only the listed channels' sets are asked for USB.  The panadapter, the beacon monitor and the
- * side outputs stay context-wide and work with staged sets as with plain ones.
+ * (t41rx_set_ft8_map) only the listed channels' sets are asked for USB.  The panadapter and the beacon monitor work with
+ * staged sets as with plain ones -- on every channel, or with a panadapter map (t41rx_set_panadapter_map) on the listed
+ * ones, each with its own set's RFgain / rfGainAllBands --; the side outputs are switches of the context.
  * flags is an int32_t holding T41RX_SETS_* bits (the scalar types of this header are int, int32_t, int64_t, size_t and
  * float); a negative value has unknown bits set.
  * t41rx_get_param_sets_flags(): the flags of the loaded sets; 0 with none or with sets loaded without a flag
@@ -1055,7 +1057,7 @@ T41RX_API int t41rx_ft8_rows(const t41rx_ctx *ctx);
  *                (float32_t)attenuator + slope (10) * log10f_fast(audioMaxSquaredAve) + cons (-92) in float, then
  *                - (float32_t)RFgain * 1.5 - rfGainAllBands in double, stored to a float, without contraction (whether the
  *                firmware's compiler contracts slope * log + sum is not pinned: DESIGN.md).  RFgain and rfGainAllBands
- *                are the params'.
+ *                are the params' (under a panadapter map: the channel's own set's, t41rx_set_panadapter_map).
  *   The drawing itself, map() for the bar's length, audioYPixel and the control-app records stay with the caller.
  * The stage's memory -- the display state, pixelold[512], oldNF and newSpectrumFlag per channel -- is the context's own,
  *   like the calibration memory: zero at t41rx_set_panadapter(on) and t41rx_reset(), NOT part of the checkpoint
@@ -1063,7 +1065,8 @@ T41RX_API int t41rx_ft8_rows(const t41rx_ctx *ctx);
  * t41rx_set_panadapter_tables(): gradient[] (Display.cpp:148-161), n == 117 uint16 colour words, a host array, copied
  *   (synchronises).  The library has no table of its own.  T41RX_ERR_ARG for NULL or n != 117.
  * t41rx_set_panadapter(): on = 0 switches the stage off (the other arguments are ignored).  out: device pointers of the
- *   caller's row buffers [n_channels][max_rows][...], each 16-byte aligned or NULL (not written); the struct is copied.
+ *   caller's row buffers [n_channels][max_rows][...] ([t41rx_panadapter_rows()][max_rows][...] under a panadapter map,
+ *   below), each 16-byte aligned or NULL (not written); the struct is copied.
  *   A call with k update frames writes rows 0 .. k-1 of every channel and leaves the others alone.  The stage's own tap
  *   buffer holds max_rows rows (16 KiB each per channel), not frames.  T41RX_ERR_ARG, nothing changed: no table loaded,
  *   spectrumZoom or currentScale outside 0..4, pixel_offset or spectrumNoiseFloor outside int16, update_period < 1,
@@ -1098,6 +1101,54 @@ T41RX_API int t41rx_set_panadapter(t41rx_ctx *ctx, int on, int spectrumZoom, int
 T41RX_API int t41rx_set_panadapter_levels(t41rx_ctx *ctx, const int32_t *noise_floor, const float *gain_correction, int attenuator);
 T41RX_API int t41rx_get_panadapter(const t41rx_ctx *ctx, int64_t *frame_counter, int32_t *rows_written, int64_t *first_row_frame);
 T41RX_API int t41rx_set_panadapter_counter(t41rx_ctx *ctx, int64_t n);
+
+/* ---- receiver groups: the panadapter map -- display rows only for the channels that ask (ABI 5) ----
+ * A skimmer of thousands of receivers shows a spectrum for the one or two somebody looks at, and monitors the beacons
+ * with five.  Without a map the panadapter taps 16 KiB per row on every channel, runs a wave per channel, wants seven
+ * row buffers of n_channels rows, and refuses smeter rows as soon as a loaded parameter set differs from set 0 in RFgain
+ * or rfGainAllBands.  The map is the FT8 map's idea: a row per channel, or none.  New entry points: no call above changes
+ * what it does, and a context that sets no map launches what it always launched.
+ * The rule: the panadapter stage runs on channel c in a call exactly when the context's switch (t41rx_set_panadapter)
+ * is on and row_of_channel[c] >= 0.  A listed channel is processed exactly as the same channel of a context without a
+ * map: its rows 0 .. k-1 of a call with k update frames, in all seven buffers, its panadapter memory and the path's
+ * audioMaxSquaredAve are bit for bit the same; only the rows' place differs -- the buffers of t41rx_panadapter_out are
+ * [n_rows][max_rows][...], and channel c writes out.*[row_of_channel[c]][0 .. k-1].  A channel with -1 is processed as
+ * with the panadapter off: it writes no tap, audioMaxSquaredAve stays, its panadapter memory stays exactly as it was and
+ * no row is written for it.  A row no channel names is never written; rows >= k of a named row are left alone as ever.
+ * A map that lists nobody is allowed: a call then launches exactly the kernels of a context without the stage, and the
+ * frame counter still counts (t41rx_get_panadapter's rows_written stays the call's number of update frames: the rows a
+ * listed channel would have written).  The audio of every call is bit for bit the audio without the stage, as before.
+ * The beacon monitor runs on the listed channels only, each reading the smeter row its channel names.  d_snr
+ * [n_channels][18], d_events [n_channels][max_rows][4] and the record (t41rx_beacon_state_bytes / _get_state /
+ * _set_state, t41rx_get_beacon) keep addressing channels; an unlisted channel's record, snr row and event rows are not
+ * touched, and a channel listed later continues from the record it has.
+ * Sizes under a map: the stage's own taps hold n_rows x max_rows rows; the panadapter memory, the levels
+ * (t41rx_set_panadapter_levels: n_channels entries) and the frame counter stay per channel / per context.
+ * dBm per channel: with a map loaded each listed channel's dbm takes RFgain and rfGainAllBands from its own effective
+ * parameter set -- set 0, plain sets and sets loaded with T41RX_SETS_STAGES alike --, so a listed channel's smeter rows
+ * equal those of a context created with its set, and the process call's refusal of sets that differ in the two gains
+ * is not raised.  Without a map that refusal stands word for word.
+ * The map is configuration, like the stage map: it is in no checkpoint and survives t41rx_reset, t41rx_set_state,
+ * t41rx_set_params and t41rx_set_coeffs (the listed channels' gains follow a changed set).  fft_length 512 only:
+ * T41RX_ERR_UNSUPPORTED at a long fft_length.  The two display side outputs (t41rx_set_display_spectrum,
+ * t41rx_set_audio_spectrum) have no map.
+ * t41rx_set_panadapter_map(): row_of_channel is a host array of n == n_channels entries, each -1 or a row in [0, n_rows).
+ *   NULL with n == 0 and n_rows == 0 removes the map.  Everything is checked on the host before anything changes; a
+ *   refused call leaves the previous map in place and t41rx_last_error() names the entry: T41RX_ERR_ARG for n !=
+ *   n_channels, n_rows outside 1..n_channels, an entry outside [-1, n_rows), a row named twice, and -- while the
+ *   panadapter is on -- n_rows different from the current t41rx_panadapter_rows(): the buffers given to
+ *   t41rx_set_panadapter are sized by the rows, so the caller switches the stage off, sets the map, and switches it on
+ *   with buffers of the new size.  Switching off is refused while the beacon monitor is on, so the order is: beacon off,
+ *   panadapter off, map, panadapter on, beacon on.  Removing the map while the panadapter is on is held to the same rule
+ *   against n_channels.  At equal n_rows the map may change between any two calls (somebody looks at another receiver).
+ *   Synchronises the device, then uploads (the ordering rule of t41rx_set_input_map); a process call uploads nothing.
+ * t41rx_get_panadapter_map(): returns 1 with a map set, 0 with none (negative: an error status).  row_of_channel_out, n
+ *   == n_channels entries, receives the map, or 0, 1, .. with none; n_rows_out receives t41rx_panadapter_rows(); either
+ *   may be NULL.
+ * t41rx_panadapter_rows(): n_rows, or n_channels with no map: the rows of the seven buffers of t41rx_panadapter_out. */
+T41RX_API int t41rx_set_panadapter_map(t41rx_ctx *ctx, const int32_t *row_of_channel, int n, int n_rows);  /* NULL, 0, 0: remove */
+T41RX_API int t41rx_get_panadapter_map(const t41rx_ctx *ctx, int32_t *row_of_channel_out, int n, int *n_rows_out);
+T41RX_API int t41rx_panadapter_rows(const t41rx_ctx *ctx);
 
 /* ---- the beacon monitor: BeaconLoop()'s per-beacon SNR table (Beacon.cpp:204-208, 455-569) ----
  * A stage behind the panadapter stage, default off.  The firmware calls BeaconLoop() once per loop() pass, which is once

@@ -173,6 +173,9 @@ SYMBOLS = {
     "t41rx_set_panadapter_levels": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int]),
     "t41rx_get_panadapter": (C.c_int, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "t41rx_set_panadapter_counter": (C.c_int, [_vp, C.c_int64]),
+    "t41rx_set_panadapter_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int, C.c_int]),
+    "t41rx_get_panadapter_map": (C.c_int, [_vp, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int)]),
+    "t41rx_panadapter_rows": (C.c_int, [_vp]),
     "t41rx_set_beacon": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int32), _vp, _vp, C.c_int]),
     "t41rx_set_beacon_clock": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32]),
     "t41rx_get_beacon": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]),

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "rx_panmap.hpp"
+
 namespace t41 {
 
 constexpr int kBeaconCount = 18;      // beacons of the NCDXF schedule, one slot of 10 s each
@@ -39,6 +41,24 @@ struct BeaconArgs {
   int32_t t0, num, den; // the clock: slot(n) = ((t0 + floor(n * num / den)) / 1000 % 180) / 10
 };
 hipError_t launch_beacon(const BeaconArgs &a, hipStream_t s);
+// the list form under a panadapter map (t41rx_set_panadapter_map; rx_panmap.hpp): a lane per entry of `list`, which
+// indexes state, snr and events by the entry's channel and smeter by its row.  BeaconArgs' members in BeaconArgs' order
+// (beacon_kernel.inc is one text for both), then the list.  An empty list is not launched.
+struct BeaconListArgs {
+  const float *smeter;  // [rows][pan_rows][4]
+  int32_t *state;       // [nchan][kBeaconWords]
+  float *snr;           // [nchan][18]
+  int32_t *events;      // [nchan][ev_rows][4] or null
+  int nchan, nrows;
+  int pan_rows, ev_rows;
+  long long n_first;
+  int period;
+  int mode;
+  int32_t t0, num, den;
+  const PanEntry *list; // [nlist] (device), ascending by channel, no row twice
+  int nlist;            // 1 .. nchan
+};
+hipError_t launch_beacon_list(const BeaconListArgs &a, hipStream_t s);
 
 // the schedule in int64, host and device alike: GetBeacon20mNow() and GetBeaconNow(band) (Beacon.cpp:204-211) at frame n
 __host__ __device__ inline int beacon_slot(long long n, int t0, int num, int den) {

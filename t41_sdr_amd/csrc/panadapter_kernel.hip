@@ -56,117 +56,36 @@ __device__ __forceinline__ float pan_dbm(float gain_correction, int attenuator, 
 
 }  // namespace
 
-template <bool ZOOMED>
-__global__ __launch_bounds__(64) void panadapter_kernel(const PanArgs a) {
-#pragma clang fp contract(off)
-  __shared__ __attribute__((aligned(16))) float xbuf[8 * kFftRow * 2];  // FFT exchange
-  __shared__ PanZoomLds<ZOOMED> z;
-  __shared__ unsigned short grad[128];
-  const int lane = threadIdx.x;
-  const int ch = blockIdx.x;
-  if (ch >= a.nchan) return;
-  constexpr int L = 2048, R = 512;
-  float *ds = a.mem + (size_t)ch * kPanFloats;
-  int *dsi = reinterpret_cast<int *>(ds);
-  const cf *tab = reinterpret_cast<const cf *>(a.tab);
-  cf tw1[7], tw2[7];
-#pragma unroll
-  for (int q = 0; q < 7; ++q) {
-    tw1[q] = tab[kTabTw1 + 64 * q + lane];
-    tw2[q] = tab[kTabTw2 + 64 * q + lane];
-  }
-  const int zoom = ZOOMED ? a.zoom : 0;
-  float st[16], fh[3];  // zoom filter memories of my chain
-  int ptr = 0;
-  if constexpr (ZOOMED) zoom_load(st, fh, ptr, z.ring, ds, lane);
-  float old[8];  // FFT_spec_old
-  int pold[8];   // pixelold
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    const int x = (lane + 64 * r + 256) & 511;  // display column of bin lane + 64 r
-    old[r] = ds[kDispOld + x];
-    pold[r] = reinterpret_cast<const short *>(ds + kPanPixel)[x];
-  }
-  double win[8];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) win[r] = a.win[lane + 64 * r];
-  for (int i = lane; i < 128; i += 64) grad[i] = i < kPanGradient ? a.gradient[i] : (unsigned short)0;
-  __syncthreads();
-  const int nf = a.noise_floor[ch];                            // currentNF: constant for every row of a call
-  int oldnf = dsi[kPanNewSpectrum] != 0 ? dsi[kPanOldNf] : nf;  // newSpectrumFlag == 0: oldNF = currentNF
-  const float gain_correction = a.gain_correction[ch];
-  for (int k = 0; k < a.nrows; ++k) {
-    const size_t row = (size_t)ch * (size_t)a.max_rows + (size_t)k;
-    const float *pI = a.pre + row * (2 * L), *pQ = pI + L;
-    cf v[8];
-    if constexpr (!ZOOMED) {
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {  // float * double -> double -> float, FFT.cpp:222-223
-        const int i = lane + 64 * r;
-        v[r] = cf{(float)((double)pI[i] * win[r]), (float)((double)pQ[i] * win[r])};
-      }
-    } else {
-      __syncthreads();
-      for (int n = lane; n < L; n += 64) {  // FreqShift1 (Freq_Shift.cpp:42-65): x j^n
-        const float xi = pI[n], xq = pQ[n];
-        const int m = n & 3;
-        z.stage[0][n] = (m == 0) ? xi : (m == 1) ? -xq : (m == 2) ? -xi : xq;
-        z.stage[1][n] = (m == 0) ? xq : (m == 1) ? xi : (m == 2) ? -xq : -xi;
-      }
-      __syncthreads();
-      zoom_frame(st, fh, ptr, z.stage, z.dec, z.ring, a.iir, a.fir, win, zoom, lane, v);
-    }
-    fft512<false>(v, tw1, tw2, xbuf, lane);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const int x = (lane + 64 * r + 256) & 511;  // bins 0..255 -> upper half, 256..511 -> lower half
-      const float m = v[r].x * v[r].x + v[r].y * v[r].y;
-      // the pixel: from the un-smoothed FFT_spec at zoom 0 (FFT.cpp:245), from the smoothed one at zoom 1..4 (:157)
-      const float spec = zoom_lowpass(zoom, m, old[r]);
-      const int p = display_pixel(a.base, a.dBScale, spec);
-      const int yn = pan_clamp(a.noise_floor_y - p - nf, kSpectrumTopY, kSpectrumBottom);
-      const int yo = pan_clamp(a.noise_floor_y - pold[r] - oldnf, kSpectrumTopY, kSpectrumBottom);
-      const unsigned short wf = x < R - 1 ? grad[pan_clamp(230 - yn, 0, kPanGradient - 1)] : (unsigned short)0;
-      pold[r] = p;
-      if (a.spec) a.spec[row * R + x] = spec;
-      // 2-byte stores from the registers, 128 contiguous bytes per instruction.  (Staged through LDS so that a row leaves
-      // as 64 16-byte stores it was slower: 5903 against 5850 us per 4096 x 128 launch at period 1, DESIGN.md "Panadapter")
-      if (a.pixel) a.pixel[row * R + x] = (int16_t)p;
-      if (a.y_new) a.y_new[row * R + x] = (int16_t)yn;
-      if (a.y_old) a.y_old[row * R + x] = (int16_t)yo;
-      if (a.waterfall) a.waterfall[row * R + x] = wf;
-    }
-    oldnf = nf;
-    if (lane == 0 && a.smeter) {
-      const float *mx = a.mx + row * 3;
-      float *sm = a.smeter + row * 4;
-      sm[0] = mx[0];
-      sm[1] = mx[1];
-      sm[2] = mx[2];
-      sm[3] = pan_dbm(gain_correction, a.attenuator, mx[2], a.RFgain, a.rfGainAllBands);
-    }
-  }
-  // the memory back
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    const int x = (lane + 64 * r + 256) & 511;
-    ds[kDispOld + x] = old[r];
-    reinterpret_cast<short *>(ds + kPanPixel)[x] = (short)pold[r];
-  }
-  if (lane == 0 && a.nrows > 0) {
-    dsi[kPanOldNf] = oldnf;
-    dsi[kPanNewSpectrum] = 1;
-  }
-  if constexpr (ZOOMED) {
-    __syncthreads();
-    zoom_store(ds, st, fh, ptr, z.ring, lane);
-  }
-}
+// panadapter_kernel<ZOOMED>, and its list form under a panadapter map (t41rx_set_panadapter_map): the text is
+// panadapter_kernel.inc
+#define T41_STAGE_KERNEL panadapter_kernel
+#define T41_STAGE_ARGS PanArgs
+#define T41_STAGE_LIST 0
+#include "panadapter_kernel.inc"
+#undef T41_STAGE_KERNEL
+#undef T41_STAGE_ARGS
+#undef T41_STAGE_LIST
+#define T41_STAGE_KERNEL panadapter_list_kernel
+#define T41_STAGE_ARGS PanListArgs
+#define T41_STAGE_LIST 1
+#include "panadapter_kernel.inc"
+#undef T41_STAGE_KERNEL
+#undef T41_STAGE_ARGS
+#undef T41_STAGE_LIST
 
 hipError_t launch_panadapter(const PanArgs &a, hipStream_t s) {
   const dim3 grid(a.nchan), block(64);
   if (a.zoom > 0) hipLaunchKernelGGL(panadapter_kernel<true>, grid, block, 0, s, a);
   else hipLaunchKernelGGL(panadapter_kernel<false>, grid, block, 0, s, a);
+  return hipGetLastError();
+}
+
+// the list form: one wave per entry; nobody listed launches nothing (a grid of zero blocks is a launch error)
+hipError_t launch_panadapter_list(const PanListArgs &a, hipStream_t s) {
+  if (a.nlist <= 0) return hipSuccess;
+  const dim3 grid(a.nlist), block(64);
+  if (a.zoom > 0) hipLaunchKernelGGL(panadapter_list_kernel<true>, grid, block, 0, s, a);
+  else hipLaunchKernelGGL(panadapter_list_kernel<false>, grid, block, 0, s, a);
   return hipGetLastError();
 }
 

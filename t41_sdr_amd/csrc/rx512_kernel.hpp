@@ -241,6 +241,11 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
   const int out_row = OUT ? ((MapPtr)a.out_map)[ch] : ch;
   const bool muted = OUT && out_row < 0;
   if (PART == 2 && muted) return;  // the back kernel: before any audio or interpolator state is read (no barrier in PART 2 + SEGPAR)
+  // the panadapter map (RxArgs::tap_map, with a tap cadence only): the row of the compact display taps this channel
+  // writes, or < 0: no tap in any frame.  Wave-uniform, read-only and checked by the host (t41rx_set_panadapter_map) like
+  // the three above; without a map the channel is its own row
+  int tap_chan = ch;
+  if (DEBUG && a.tap_period > 0 && a.tap_map) tap_chan = ((MapPtr)a.tap_map)[ch];
 
   // per-channel NCO constants and state (wave-uniform).  Only the LOADS are issued here; the
   // values are made uniform (which waits for them) after the first frame's input loads are in
@@ -334,11 +339,12 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
     // the row of this frame in the display taps (dbg_pre, spect, spect_max): its own, [nchan][nframes]; or with a tap
     // cadence (RxArgs::tap_period, the panadapter stage) compact rows [nchan][tap_rows] for the flagged frames tap_first
     // + k tap_period only, -1 for every other frame, which then writes no tap and leaves audioMaxSquaredAve alone
-    // (updateDisplayFlag == 0, Process.cpp:185, 212, 550).  Kernel arguments only: the same for every lane and channel.
+    // (updateDisplayFlag == 0, Process.cpp:185, 212, 550).  Kernel arguments only: the same for every lane and channel --
+    // but for a panadapter map, whose row (tap_chan) takes the channel's place and whose -1 makes every frame a -1.
     int tap_row = f, tap_stride = a.nframes;
     if (DEBUG && a.tap_period > 0) {
       const int d = f - a.tap_first;
-      tap_row = (d >= 0 && d % a.tap_period == 0) ? d / a.tap_period : -1;
+      tap_row = (tap_chan >= 0 && d >= 0 && d % a.tap_period == 0) ? d / a.tap_period : -1;
       tap_stride = a.tap_rows;
     }
     // sample offset of (channel, frame) in I / Q / audio: RxArgs::chan_stride / frame_stride (channel-major
@@ -760,7 +766,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
         // -- oscillator for my 8 samples.  Osc_n = V_n * W has phase phase0 + (n+1) dphi.
           const int n0 = 512 * s + 8 * lane;
           if (DEBUG && a.dbg_pre && tap_row >= 0) {  // what CalcZoom1Magn() sees (Process.cpp:185), input of the display FFT
-            float *dp = a.dbg_pre + ((size_t)ch * tap_stride + tap_row) * (2 * L);
+            float *dp = a.dbg_pre + ((size_t)tap_chan * tap_stride + tap_row) * (2 * L);
   #pragma unroll
             for (int k = 0; k < 8; ++k) {
               dp[n0 + k] = z[k].x;
@@ -1162,7 +1168,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
           // spectrum.  The mask table carries 1/N (the reference applies it in the inverse FFT):
           // a power of two, so squaring after undoing it is exact.  v[r] = bin lane + 64 r.
           // (a.spect may be null with the panadapter stage, which always takes the maximum: no spectrum rows then)
-          float *sp = a.spect ? a.spect + ((size_t)ch * tap_stride + tap_row) * 1024 : nullptr;
+          float *sp = a.spect ? a.spect + ((size_t)tap_chan * tap_stride + tap_row) * 1024 : nullptr;
           float best = -1.0f;
           int besti = 0;
   #pragma unroll
@@ -1182,7 +1188,7 @@ __global__ __launch_bounds__((Rx512Geo<MODE, (PARTM & 3), AGC, PIPE>::kWaves * 6
             if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }
           }
           if (lane == 0) {
-            float *mx = a.spect_max + ((size_t)ch * tap_stride + tap_row) * 3;
+            float *mx = a.spect_max + ((size_t)tap_chan * tap_stride + tap_row) * 3;
             const float ave = (float)(.5 * (double)best + .5 * (double)st[kStMisc + kMiscMaxSqAve]);  // :570
             mx[0] = best;
             mx[1] = (float)besti;

@@ -56,21 +56,34 @@ int beacon_prepare(t41rx_ctx *ctx) {
 int beacon_run(t41rx_ctx *ctx, hipStream_t s) {
   const BeaconStage &b = ctx->beacon;
   const Panadapter &p = ctx->pan;
+  // what both forms of the kernel take (BeaconArgs, and BeaconListArgs with the list behind the same members)
+  auto fill = [&](auto &a) {
+    a.smeter = p.out.smeter;
+    a.state = b.d_state.get();
+    a.snr = b.snr;
+    a.events = b.events;
+    a.nchan = ctx->nchan;
+    a.nrows = p.last_rows;
+    a.pan_rows = p.max_rows;
+    a.ev_rows = b.max_rows;
+    a.n_first = p.last_first;
+    a.period = p.period;
+    a.mode = b.mode;
+    a.t0 = b.clock.t0;
+    a.num = b.clock.num;
+    a.den = b.clock.den;
+  };
+  if (p.map_on) {
+    // a panadapter map: the listed channels only, each on the smeter row it names; nobody listed: nothing to launch
+    if (p.list.empty()) return T41RX_OK;
+    BeaconListArgs a{};
+    fill(a);
+    a.list = p.d_list.get();
+    a.nlist = (int)p.list.size();
+    return hip_check(launch_beacon_list(a, s), "beacon list kernel launch");
+  }
   BeaconArgs a{};
-  a.smeter = p.out.smeter;
-  a.state = b.d_state.get();
-  a.snr = b.snr;
-  a.events = b.events;
-  a.nchan = ctx->nchan;
-  a.nrows = p.last_rows;
-  a.pan_rows = p.max_rows;
-  a.ev_rows = b.max_rows;
-  a.n_first = p.last_first;
-  a.period = p.period;
-  a.mode = b.mode;
-  a.t0 = b.clock.t0;
-  a.num = b.clock.num;
-  a.den = b.clock.den;
+  fill(a);
   return hip_check(launch_beacon(a, s), "beacon kernel launch");
 }
 

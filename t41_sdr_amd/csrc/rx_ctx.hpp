@@ -2,7 +2,8 @@
 // Private to them: rx_host.cpp (the core and the process call), rx_state.cpp (checkpoints and reset) and one file per
 // stage family -- rx_audio.cpp, rx_cw.cpp, rx_ft8.cpp, rx_ft8_decode.cpp, rx_display.cpp, rx_beacon.cpp, rx_cal.cpp -- and
 // rx_sets.cpp (the parameter sets), rx_outmap.cpp (the output map), rx_stagemap.cpp (the stage map) and
-// rx_stageparams.cpp (the CW filter map and the equalizer level map); the FT8 map lives with its stage in rx_ft8.cpp.  Each
+// rx_stageparams.cpp (the CW filter map and the equalizer level map); the FT8 map lives with its stage in rx_ft8.cpp, the
+// panadapter map with its stage in rx_display.cpp.  Each
 // stage family holds its part of the context in a struct of its own below, and exports the few functions the process
 // call and the checkpoint table name.  No kernel is compiled into a host file: they see the kernels through the
 // *_kernels.hpp headers.
@@ -172,7 +173,7 @@ struct DisplayTap {
 
 // the panadapter stage (ShowSpectrum() / DrawSmeterBar(), Display.cpp:240-504, 955-1030; t41rx_set_panadapter_tables /
 // _panadapter / _panadapter_levels): the caller's gradient[] (device copy), the settings, the caller's row buffers, the
-// levels per channel (device copies), the compact taps of a call's update frames [nchan][max_rows][...] that the tap
+// levels per channel (device copies), the compact taps of a call's update frames [rows][max_rows][...] that the tap
 // kernels write and panadapter_kernel reads, and the panadapter memory [nchan][kPanFloats] (rx_internal.hpp).  The
 // context's own: no checkpoint section, t41rx_set_state() leaves it alone.  The frame counter lives here, on the host.
 struct Panadapter {
@@ -188,6 +189,20 @@ struct Panadapter {
   DevBuf<uint16_t> d_grad;
   DevBuf<int32_t> d_nf;
   DevBuf<float> d_gc, d_pre, d_max, d_mem;
+  // the panadapter map (t41rx_set_panadapter_map; rx_display.cpp): the caller's row per channel with its device copy
+  // (RxArgs::tap_map), the rows the taps and the caller's buffers then hold, and the list of {channel, row, RFgain,
+  // rfGainAllBands} entries made of it, of the parameter sets and of set 0 (rx_panmap.hpp) with its device copy [nchan]
+  // entries -- made again when any of the three changes (pan_map_refresh).  With a map d_pre / d_max and the caller's seven
+  // buffers are [rows][max_rows][...]; the memory and the levels stay [nchan].  Configuration like the stage map: in no
+  // checkpoint, untouched by reset / set_state / set_params.  map_on == false: no map, the stage runs on every channel
+  // and channel c writes row c.
+  bool map_on = false;
+  std::vector<int32_t> map;    // [nchan] (host)
+  int rows = 0;
+  int alloc_width = 0;         // rows of channels d_pre / d_max hold
+  std::vector<PanEntry> list;  // ascending by channel (host)
+  DevBuf<PanEntry> d_list;     // allocated with the first map
+  DevBuf<int32_t> d_map;       // allocated with the first map
 };
 
 // the beacon monitor behind the panadapter (BeaconLoop(), Beacon.cpp:455-569; t41rx_set_beacon / _beacon_clock): the
@@ -197,7 +212,7 @@ struct Panadapter {
 struct BeaconStage {
   bool on = false;
   int mode = 0, max_rows = 0;
-  float *snr = nullptr;       // [nchan][18]
+  float *snr = nullptr;       // [nchan][18] (by channel under a panadapter map too: only the smeter rows go by row)
   int32_t *events = nullptr;  // [nchan][max_rows][4], or null
   std::vector<int32_t> band;  // [nchan]
   StageClock clock;
@@ -388,6 +403,13 @@ inline int input_rows(const t41rx_ctx *ctx) { return ctx->n_streams > 0 ? ctx->n
 inline int audio_rows(const t41rx_ctx *ctx) { return ctx->out_map_on ? ctx->out_rows : ctx->nchan; }
 // rows of d_power / d_status (and of the audio entry's pcm): one per channel, or the FT8 map's n_rows
 inline int ft8_rows(const t41rx_ctx *ctx) { return ctx->ft8.map_on ? ctx->ft8.rows : ctx->nchan; }
+// rows of the panadapter's taps and of the caller's seven row buffers: one per channel, or the panadapter map's n_rows
+inline int pan_rows(const t41rx_ctx *ctx) { return ctx->pan.map_on ? ctx->pan.rows : ctx->nchan; }
+// the call being prepared writes display taps and runs the panadapter kernel: the stage is on, the call has an update
+// frame (pan_prepare) and, with a map, somebody is listed
+inline bool pan_call_rows(const t41rx_ctx *ctx) {
+  return ctx->pan.on && ctx->pan.call_rows > 0 && !(ctx->pan.map_on && ctx->pan.list.empty());
+}
 // the list of a stage of a call (rx_stagemap.hpp: StageIndex), row kStageCount: the blanker's complement
 inline StageList stage_list(const t41rx_ctx *ctx, int row) {
   if (!ctx->stages.on) return StageList{};
@@ -488,6 +510,7 @@ int display_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
 int pan_prepare(t41rx_ctx *ctx, int n_frames);  // which frames of the call are update frames, and the stage's refusals
 int pan_run(t41rx_ctx *ctx, int n_frames, hipStream_t s);
 int pan_reset(t41rx_ctx *ctx);
+int pan_map_refresh(t41rx_ctx *ctx);  // the parameter sets or set 0 changed (behind the setter's synchronisation): the map's list again (no map: nothing)
 // rx_beacon.cpp
 int beacon_prepare(t41rx_ctx *ctx);  // the call's refusals, once pan_prepare() has counted its rows
 int beacon_run(t41rx_ctx *ctx, hipStream_t s);  // behind pan_run(), on the rows it wrote

@@ -1,8 +1,10 @@
 // t41_sdr_amd/csrc/rx_display.cpp -- host side of the display stages behind a process call: the display FFT side output
 // (display_kernel.hip) and the panadapter stage (panadapter_kernel.hip), with the window and the zoom filters they share
-// with the calibration.
+// with the calibration -- and the panadapter map (t41rx_set_panadapter_map; its list is rx_panmap.hpp's): with a map the
+// stage launches the list form of its kernel over the list's length, or nothing for an empty list.
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -63,7 +65,9 @@ int pan_prepare(t41rx_ctx *ctx, int n_frames) {
   p.call_rows = 0;
   p.call_first = n_frames;
   if (!p.on) return T41RX_OK;
-  if (p.out.smeter)  // (parameter sets: DrawSmeterBar()'s dBm takes the two gains by value, one pair per launch)
+  // (parameter sets: DrawSmeterBar()'s dBm takes the two gains by value, one pair per launch -- but under a panadapter
+  // map, whose list carries every listed channel's own pair)
+  if (p.out.smeter && !p.map_on)
     for (const t41rx_params &s : ctx->sets.params)
       if (s.RFgain != ctx->params.RFgain || s.rfGainAllBands != ctx->params.rfGainAllBands)
         return fail(T41RX_ERR_UNSUPPORTED, "panadapter: the S-meter's dBm reads one RFgain / rfGainAllBands per context and a loaded "
@@ -78,8 +82,8 @@ int pan_prepare(t41rx_ctx *ctx, int n_frames) {
 
 int pan_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
   Panadapter &pan = ctx->pan;
-  if (pan.call_rows > 0) {
-    PanArgs p{};
+  // what both forms of the kernel take (PanArgs, and PanListArgs with the list behind the same members)
+  auto fill = [&](auto &p) {
     p.pre = pan.d_pre.get();
     p.mx = pan.d_max.get();
     p.mem = pan.d_mem.get();
@@ -105,12 +109,48 @@ int pan_run(t41rx_ctx *ctx, int n_frames, hipStream_t s) {
     p.attenuator = pan.attenuator;
     p.RFgain = ctx->params.RFgain;
     p.rfGainAllBands = ctx->params.rfGainAllBands;
+  };
+  if (pan.call_rows > 0 && pan.map_on) {
+    // the list form over the list's length; nobody listed: nothing to launch (the call wrote no tap either)
+    if (!pan.list.empty()) {
+      PanListArgs p{};
+      fill(p);
+      p.list = pan.d_list.get();
+      p.nlist = (int)pan.list.size();
+      const hipError_t e = launch_panadapter_list(p, s);
+      if (e != hipSuccess) return hip_fail(e, "panadapter list kernel launch");
+    }
+  } else if (pan.call_rows > 0) {
+    PanArgs p{};
+    fill(p);
     const hipError_t e = launch_panadapter(p, s);
     if (e != hipSuccess) return hip_fail(e, "panadapter kernel launch");
   }
+  // (under a map: the rows every listed channel wrote)
   pan.last_rows = pan.call_rows;
   pan.last_first = pan.call_rows > 0 ? pan.counter + pan.call_first : -1;
   pan.counter += n_frames;
+  return T41RX_OK;
+}
+
+// DrawSmeterBar()'s two gains of every set, [K + 1] with set 0 first, and the channels' table (null: no sets): what
+// rx_panmap.hpp makes the list's entries of
+namespace {
+std::vector<PanGains> pan_gains(const t41rx_ctx *ctx) {
+  std::vector<PanGains> gains{PanGains{ctx->params.RFgain, ctx->params.rfGainAllBands}};
+  for (const t41rx_params &s : ctx->sets.params) gains.push_back(PanGains{s.RFgain, s.rfGainAllBands});
+  return gains;
+}
+const int32_t *pan_set_of(const t41rx_ctx *ctx) { return sets_loaded(ctx) ? ctx->sets.set_of.data() : nullptr; }
+}  // namespace
+
+// the parameter sets or set 0 changed (behind the setter's device synchronisation): the listed channels' gains follow
+int pan_map_refresh(t41rx_ctx *ctx) {
+  Panadapter &pan = ctx->pan;
+  if (!pan.map_on) return T41RX_OK;
+  std::vector<PanEntry> list = pan_list_of(pan.map.data(), ctx->nchan, pan_gains(ctx).data(), pan_set_of(ctx));
+  if (!list.empty()) HIP_TRY(hipMemcpy(pan.d_list.get(), list.data(), sizeof(PanEntry) * list.size(), hipMemcpyHostToDevice));
+  pan.list = std::move(list);
   return T41RX_OK;
 }
 
@@ -220,11 +260,16 @@ int t41rx_set_panadapter(t41rx_ctx *ctx, int on, int spectrumZoom, int currentSc
     return fail(T41RX_ERR_UNSUPPORTED, "t41rx_set_display_spectrum / t41rx_set_audio_spectrum is set and owns its tap: switch it off first");
   // anything that fails from here on leaves the stage switched off
   pan.on = false;
-  if (max_rows > pan.alloc_rows || !pan.d_pre || !pan.d_max) {
-    pan.alloc_rows = 0;
-    HIP_TRY(dev_alloc(pan.d_pre, sizeof(float) * 4096 * (size_t)max_rows * (size_t)ctx->nchan));
-    HIP_TRY(dev_alloc(pan.d_max, sizeof(float) * 3 * (size_t)max_rows * (size_t)ctx->nchan));
+  // the taps, sized by the rows: one per channel, or the panadapter map's n_rows
+  const int width = pan_rows(ctx);
+  if (max_rows > pan.alloc_rows || width != pan.alloc_width || !pan.d_pre || !pan.d_max) {
+    pan.alloc_rows = pan.alloc_width = 0;
+    pan.d_pre.reset();
+    pan.d_max.reset();
+    HIP_TRY(dev_alloc(pan.d_pre, sizeof(float) * 4096 * (size_t)max_rows * (size_t)width));
+    HIP_TRY(dev_alloc(pan.d_max, sizeof(float) * 3 * (size_t)max_rows * (size_t)width));
     pan.alloc_rows = max_rows;
+    pan.alloc_width = width;
   }
   if (!pan.d_mem) HIP_TRY(dev_alloc(pan.d_mem, sizeof(float) * kPanFloats * (size_t)ctx->nchan));
   if (const int rc = ensure_window(ctx)) return rc;
@@ -248,6 +293,75 @@ int t41rx_set_panadapter(t41rx_ctx *ctx, int on, int spectrumZoom, int currentSc
   pan.on = true;
   return T41RX_OK;
 }
+
+// The panadapter map.  Everything is checked here, on the host, before anything changes: the tap instantiations and the
+// list kernels index every buffer with the rows unchecked.  A refused call leaves the previous map whole.
+int t41rx_set_panadapter_map(t41rx_ctx *ctx, const int32_t *row_of_channel, int n, int n_rows) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  Panadapter &pan = ctx->pan;
+  const std::string counts = " (n_channels " + std::to_string(ctx->nchan) + ", panadapter rows " + std::to_string(pan_rows(ctx)) + ")";
+  const std::string resize = ": the panadapter is on and its row buffers are sized by the rows; switch the beacon monitor and the "
+                             "panadapter off, set the map, and switch them on with buffers of the new size";
+  if (!row_of_channel) {
+    if (n != 0 || n_rows != 0) return fail(T41RX_ERR_ARG, "panadapter map: a null map removes the map and takes n 0 and n_rows 0" + counts);
+    if (pan.on && pan_rows(ctx) != ctx->nchan)
+      return fail(T41RX_ERR_ARG, "panadapter map: removing the map would change the rows from " + std::to_string(pan_rows(ctx)) + " to n_channels" + resize + counts);
+    DeviceGuard g(ctx->device);
+    if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+    HIP_TRY(hipDeviceSynchronize());  // (calls in flight were launched with the list they found)
+    pan.map_on = false;
+    return T41RX_OK;
+  }
+  if (ctx->params.fft_length != 512) return fail(T41RX_ERR_UNSUPPORTED, "panadapter map: the panadapter stage is built for fft_length 512");
+  std::vector<PanEntry> list;
+  const PanMapVerdict v = build_pan_list(row_of_channel, n, n_rows, ctx->nchan, pan.on ? pan_rows(ctx) : 0, pan_gains(ctx).data(), pan_set_of(ctx), list);
+  switch (v.fault) {
+    case PanMapFault::none:
+      break;
+    case PanMapFault::count:
+    case PanMapFault::null_map:
+      return fail(T41RX_ERR_ARG, "panadapter map: n (" + std::to_string(n) + ") must equal n_channels" + counts);
+    case PanMapFault::rows:
+      return fail(T41RX_ERR_ARG, "panadapter map: n_rows (" + std::to_string(n_rows) + ") must be 1 .. n_channels" + counts);
+    case PanMapFault::entry:
+      return fail(T41RX_ERR_ARG, "panadapter map: channel " + std::to_string(v.channel) + " has row " + std::to_string(row_of_channel[v.channel]) +
+                                     ", outside [-1, n_rows " + std::to_string(n_rows) + ")" + counts);
+    case PanMapFault::twice:
+      return fail(T41RX_ERR_ARG, "panadapter map: row " + std::to_string(row_of_channel[v.channel]) + " is named twice, by channel " + std::to_string(v.other) +
+                                     " and channel " + std::to_string(v.channel) + counts);
+    case PanMapFault::resize:
+      return fail(T41RX_ERR_ARG, "panadapter map: n_rows (" + std::to_string(n_rows) + ") differs from the current rows" + resize + counts);
+  }
+  DeviceGuard g(ctx->device);
+  if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
+  HIP_TRY(hipDeviceSynchronize());
+  DevBuf<PanEntry> fresh_list;  // (the first map; later ones reuse the buffers: a failure leaves the previous map whole)
+  DevBuf<int32_t> fresh_map;
+  if (!pan.d_list) HIP_TRY(dev_alloc(fresh_list, sizeof(PanEntry) * (size_t)ctx->nchan));
+  if (!pan.d_map) HIP_TRY(dev_alloc(fresh_map, sizeof(int32_t) * (size_t)ctx->nchan));
+  if (!list.empty())
+    HIP_TRY(hipMemcpy(fresh_list ? fresh_list.get() : pan.d_list.get(), list.data(), sizeof(PanEntry) * list.size(), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(fresh_map ? fresh_map.get() : pan.d_map.get(), row_of_channel, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+  if (fresh_list) pan.d_list = std::move(fresh_list);
+  if (fresh_map) pan.d_map = std::move(fresh_map);
+  pan.map.assign(row_of_channel, row_of_channel + n);
+  pan.list = std::move(list);
+  pan.rows = n_rows;
+  pan.map_on = true;
+  return T41RX_OK;
+}
+
+int t41rx_get_panadapter_map(const t41rx_ctx *ctx, int32_t *row_of_channel_out, int n, int *n_rows_out) {
+  if (!ctx) return fail(T41RX_ERR_ARG, "null argument");
+  if (row_of_channel_out) {
+    if (n != ctx->nchan) return fail(T41RX_ERR_ARG, "panadapter map: n (" + std::to_string(n) + ") must equal n_channels (" + std::to_string(ctx->nchan) + ")");
+    for (int i = 0; i < n; ++i) row_of_channel_out[i] = ctx->pan.map_on ? ctx->pan.map[(size_t)i] : i;
+  }
+  if (n_rows_out) *n_rows_out = pan_rows(ctx);
+  return ctx->pan.map_on ? 1 : 0;
+}
+
+int t41rx_panadapter_rows(const t41rx_ctx *ctx) { return ctx ? pan_rows(ctx) : T41RX_ERR_ARG; }
 
 int t41rx_set_panadapter_levels(t41rx_ctx *ctx, const int32_t *noise_floor, const float *gain_correction, int attenuator) {
   if (!ctx) return fail(T41RX_ERR_ARG, "null argument");

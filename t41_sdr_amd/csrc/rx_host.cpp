@@ -276,7 +276,7 @@ CallFacts call_facts(const t41rx_ctx *ctx, int n_frames, bool q15) {
   f.tap_demod = taps && ctx->dbg_demod;
   f.spect = ctx->spect != nullptr;
   f.disp = ctx->disp.spec != nullptr;
-  f.pan_rows = ctx->pan.on && ctx->pan.call_rows > 0;
+  f.pan_rows = pan_call_rows(ctx);  // (a panadapter map that lists nobody: the call is one without the stage)
   f.ft8 = ctx->ft8.on != 0;
   f.eq = ctx->eq.on != 0;
   f.nb = ctx->nb.on != 0;
@@ -427,7 +427,7 @@ RxArgs rx_args(t41rx_ctx *ctx, const CallPlan &plan, const float *dI, const floa
   if (plan.ft8_own_tap) a.dbg_demod = ctx->ft8.d_tap.get();  // the FT8 stage reads the demod tap
   a.spect = ctx->spect;
   a.spect_max = ctx->spect_max;
-  if (ctx->pan.on && ctx->pan.call_rows > 0) {
+  if (pan_call_rows(ctx)) {
     // the panadapter owns the display taps (one owner each: the setters refuse the other): compact rows for the call's
     // update frames.  A call without one sets no tap and so launches what a context without the stage launches.
     a.dbg_pre = ctx->pan.d_pre.get();
@@ -436,6 +436,7 @@ RxArgs rx_args(t41rx_ctx *ctx, const CallPlan &plan, const float *dI, const floa
     a.tap_period = ctx->pan.period;
     a.tap_first = ctx->pan.call_first;
     a.tap_rows = ctx->pan.max_rows;
+    if (ctx->pan.map_on) a.tap_map = ctx->pan.d_map.get();  // the taps by row, [n_rows][max_rows], for the listed channels only
   }
   // the kernel stops behind the demodulator.  (At 24 kS/s the strides above stay the input's: a tap kernel without a map
   // places its input with them, and stores no audio)
@@ -726,6 +727,7 @@ int t41rx_set_params(t41rx_ctx *ctx, const t41rx_params *p) {
   ctx->params = *p;
   if ((rc = upload_coeffs(ctx)) != T41RX_OK) return rc;
   if (sets_loaded(ctx) && (rc = sets_upload(ctx)) != T41RX_OK) return rc;  // entry 0 of the set arrays
+  if ((rc = pan_map_refresh(ctx)) != T41RX_OK) return rc;  // (a panadapter map: the listed channels' gains of set 0)
   return upload_nco(ctx);  // the CW side-tone offset may have changed
 }
 
@@ -770,6 +772,7 @@ int t41rx_set_coeffs(t41rx_ctx *ctx, const void *blob, size_t blob_bytes) {
   int rc = upload_coeffs(ctx);
   if (rc != T41RX_OK) return rc;
   if (sets_loaded(ctx) && (rc = sets_upload(ctx)) != T41RX_OK) return rc;  // entry 0 of the set arrays
+  if ((rc = pan_map_refresh(ctx)) != T41RX_OK) return rc;  // (a panadapter map: the listed channels' gains of set 0)
   return upload_nco(ctx);
 }
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rx_internal.hpp"
+#include "rx_panmap.hpp"
 #include "rx_plan.hpp"
 
 namespace t41 {
@@ -109,6 +110,12 @@ struct RxArgs {
   // its interpolator memories alone.  The host has checked every entry against the number of rows and that no row is
   // named twice.  Only the output-map instantiations read this field.
   const int *__restrict__ out_map;
+  // the panadapter map (t41rx_set_panadapter_map), or null: with tap_period > 0 channel c writes the update frames' rows of
+  // dbg_pre / spect / spect_max to row tap_map[c] of [n_rows][tap_rows] -- the row takes the channel's place in the three
+  // tap addresses and nothing else changes -- or, with tap_map[c] < 0, writes no tap in any frame and leaves
+  // audioMaxSquaredAve alone.  The host has checked every entry against the number of rows and that no row is named
+  // twice.  Only the tap instantiations read this field.
+  const int32_t *tap_map;
 };
 
 // constant table of the N = 512 R point fast convolution (float2 units):
@@ -210,5 +217,34 @@ struct PanArgs {
   int attenuator, RFgain, rfGainAllBands;  // DrawSmeterBar()'s integers (Display.cpp:980-981)
 };
 hipError_t launch_panadapter(const PanArgs &a, hipStream_t s);
+// the list form under a panadapter map (t41rx_set_panadapter_map; rx_panmap.hpp): a wave per entry of `list`, which
+// indexes mem, noise_floor and gain_correction by the entry's channel, pre, mx and the caller's rows by its row, and takes
+// RFgain / rfGainAllBands from the entry (the two members here are not read).  PanArgs' members in PanArgs' order
+// (panadapter_kernel.inc is one text for both), then the list.  An empty list is not launched.
+struct PanListArgs {
+  const float *pre;             // [rows][max_rows][2][2048]
+  const float *mx;              // [rows][max_rows][3]
+  float *mem;                   // [nchan][kPanFloats]
+  const float2 *tab;
+  const double *win;
+  const uint16_t *gradient;
+  const int32_t *noise_floor;   // [nchan]
+  const float *gain_correction; // [nchan]
+  // the caller's rows [rows][max_rows][...], each may be null
+  int16_t *pixel, *y_new, *y_old;
+  uint16_t *waterfall;
+  float *spec;
+  float *smeter;
+  float iir[20];
+  float fir[4];
+  int nchan, nrows, max_rows, zoom;
+  float dBScale;
+  int base;
+  int noise_floor_y;
+  int attenuator, RFgain, rfGainAllBands;
+  const PanEntry *list;         // [nlist] (device), ascending by channel, no row twice
+  int nlist;                    // 1 .. nchan: the grid
+};
+hipError_t launch_panadapter_list(const PanListArgs &a, hipStream_t s);
 
 }  // namespace t41

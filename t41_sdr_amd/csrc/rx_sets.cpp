@@ -241,6 +241,7 @@ int t41rx_set_param_sets_ex(t41rx_ctx *ctx, const t41rx_params *sets, int n_sets
     if (!g.ok) return fail(T41RX_ERR_HIP, "hipSetDevice failed");
     HIP_TRY(hipDeviceSynchronize());  // (calls in flight were launched with the sets they found)
     ctx->sets = ParamSets{};
+    if (const int rc = pan_map_refresh(ctx)) return rc;  // (a panadapter map: every listed channel's gains are set 0's again)
     return upload_nco(ctx);  // every channel's side tone is set 0's again
   }
   // everything is checked here, on the host, before anything changes: the kernels index the set arrays with these entries unchecked
@@ -303,6 +304,7 @@ int t41rx_set_param_sets_ex(t41rx_ctx *ctx, const t41rx_params *sets, int n_sets
     if ((rc = upload_cw_back(ctx, fresh.blobs, fresh.d_cw_back.get())) != T41RX_OK) return rc;
   }
   ctx->sets = std::move(fresh);
+  if ((rc = pan_map_refresh(ctx)) != T41RX_OK) return rc;  // (a panadapter map: the listed channels' gains follow their own sets)
   return upload_nco(ctx);  // the side tone follows the channel's own set
 }
 

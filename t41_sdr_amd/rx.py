@@ -805,7 +805,8 @@ class RxChain:
         names of PANADAPTER_ROWS allocates those, a dict name -> CUDA tensor [n_channels, max_rows, width] uses the
         caller's; what is left out is not written.  Returns the dict of row buffers: a call with k update frames writes
         rows 0 .. k-1 of every channel (panadapter_status()).  on = False switches the stage off and returns None.
-        Starts the stage's memory and its frame counter from power-on.  fft_length 512; the colour table loaded first."""
+        Starts the stage's memory and its frame counter from power-on.  fft_length 512; the colour table loaded first.
+        With a panadapter map (set_panadapter_map) every buffer holds panadapter_rows rows in place of n_channels."""
         if not on:
             check(self._lib.t41rx_set_panadapter(self._ctx, 0, 0, 0, 0, 0, 1, 0, None, 0))
             self._pan = None
@@ -821,7 +822,7 @@ class RxChain:
             if name not in kinds:
                 raise ValueError("unknown panadapter output %r (one of %s)" % (name, ", ".join(kinds)))
             dt, width = kinds[name]
-            shape = (self.n_channels, int(max_rows), width)
+            shape = (self.panadapter_rows, int(max_rows), width)
             t = outputs[name] if isinstance(outputs, dict) else None
             if t is None:  # (uint16: allocated as int16 and viewed, the type torch fills on every build)
                 t = torch.zeros(shape, dtype=torch.int16 if dt == torch.uint16 else dt, device=cuda(self.device)).view(dt)
@@ -834,6 +835,35 @@ class RxChain:
                                              int(update_period), int(update_phase), C.byref(out), int(max_rows)))
         self._pan = bufs  # keep alive
         return bufs
+
+    def set_panadapter_map(self, row_of_channel, n_rows=None):
+        """Receiver groups (t41rx_set_panadapter_map): the panadapter stage runs on channel c only when row_of_channel[c]
+        >= 0, and then writes row row_of_channel[c] of the seven row buffers, which hold n_rows rows -- [n_rows, max_rows,
+        width]; a channel with -1 is processed as with the panadapter off: no tap, audioMaxSquaredAve and its panadapter
+        memory stay as they were.  The beacon monitor behind it runs on the listed channels only (its snr, events and
+        record stay by channel).  Each listed channel's dbm takes RFgain / rfGainAllBands from its own parameter set.  No
+        row may be named twice; n_rows defaults to max + 1 (at least 1).  None removes the map.  While the panadapter is
+        on the rows cannot change: set_beacon(False), set_panadapter(False), set_panadapter_map(...), set_panadapter(...),
+        set_beacon(...); at equal n_rows the map may change between any two calls.  Configuration, like the stage map: in
+        no checkpoint, kept across reset() / set_state() / CalcFilters(); FFT_LENGTH 512."""
+        if row_of_channel is None:
+            check(self._lib.t41rx_set_panadapter_map(self._ctx, None, 0, 0))
+            return
+        m = int_table(row_of_channel, np.int32, None, "row_of_channel must be a 1-d array of int32 row numbers (-1: no panadapter), got %r %s")
+        if n_rows is None:
+            n_rows = max(int(m.max()) + 1, 1) if m.size else 1
+        check(self._lib.t41rx_set_panadapter_map(self._ctx, ptr(m, I32P), int(m.size), int(n_rows)))
+
+    @property
+    def panadapter_map(self):
+        """the panadapter map as an int32 array [n_channels] (a copy, -1: not listed), or None with no map set"""
+        m = np.zeros(self.n_channels, np.int32)
+        return m if value(self._lib.t41rx_get_panadapter_map(self._ctx, ptr(m, I32P), self.n_channels, None)) > 0 else None
+
+    @property
+    def panadapter_rows(self):
+        """rows of the panadapter's row buffers: the panadapter map's n_rows, or n_channels with no map"""
+        return value(self._lib.t41rx_panadapter_rows(self._ctx))  # (asked, not kept: a host call without a sync)
 
     def set_panadapter_levels(self, noise_floor=None, gain_correction=None, attenuator=0):
         """currentNoiseFloor[currentBand] (ints) and bands[currentBand].gainCorrection (floats) per channel, None = zeros,
